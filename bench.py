@@ -6,7 +6,7 @@ one candidate path per pixel per frame with the reference's four stages (G-buffe
 -> post/accumulate), static camera at the initial pose. One "step" = one frame. Synthetic data: the scene is procedural.
 Metric (BASELINE.json): Mrays/s = (closest-hit + any-hit rays issued, counted on the device) / wall seconds, and ms/frame.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N > 1: one process per GPU, the frame is cut into N horizontal strips, one batched halo exchange per frame and neighbour over RCCL (frt.dist);
@@ -14,8 +14,10 @@ total work is fixed ("strong" scaling). Rank 0 prints ONE JSON line. Either laun
 environment this process IS a rank; without them `--gpus N` starts its own N rank processes (fresh children, before this
 process has touched the GPU), relays rank 0's line and exits non-zero if any rank fails.
 `--native`: ONE process drives the N GPUs through the C ABI's frt_multi_renderer (include/frt.h), no torch.distributed.
-Extra objects: "roofline" (what binds the frame, from the committed counters) and, at N = 1,
-"cpu_baseline" (the scalar C++ oracle over the same BVH on the host cores — a reported baseline, never the target).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (`--dump-outputs DIR`) and prints the line.
+`--full` adds what takes runs of its own: "roofline" (what binds the frame, from the committed counters) and "stage_ms"
+(an instrumented pass), "config2_4k" (configs[2]), at N = 1 "cpu_baseline" (the scalar C++ oracle over the same BVH on the host cores — a
+reported baseline, never the target), at N > 1 the exposed halo-transfer time and the strip gather, with --native the display read-back.
 """
 import argparse
 import json
@@ -179,10 +181,40 @@ def parse_args(argv=None):
     ap.add_argument("--native", action="store_true",
                     help="N > 1 in ONE process through frt_multi_renderer (C ABI): strips on N devices, peer copies for the halos; "
                          "FRT_BENCH_ONE_GPU=1 maps every logical device to ordinal 0")
-    ap.add_argument("--no-4k", action="store_true", help="skip the extra configs[2] (3840x2160) measurement")
+    ap.add_argument("--no-4k", action="store_true", help="skip the extra configs[2] (3840x2160) measurement (--full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-stage times, roofline, CPU baseline (N = 1), configs[2] at 3840x2160, "
+                         "the exposed halo-transfer time and the strip gather (N > 1), the display read-back (--native)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): "
+                         "accum (HxWx4 accumulation), display (HxWx3 RGB of the RGBA8 image), rays (closest, any over the timed steps)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous plumbing only: every rank joins the process group and reports itself; nothing is rendered, no GPU is touched (CPU test)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def frame_outputs(accum, display, rays):
+    """The arrays a caller of the timed path receives after its last step. The display's alpha is left out: the post stage writes the
+    constant 255 there, and the full RGBA8 image as float32 next to the accumulation would pass DUMP_LIMIT_BYTES at 1920x1080."""
+    import numpy as np
+    return {"accum": np.ascontiguousarray(accum, np.float32), "display": np.ascontiguousarray(display[..., :3], np.float32),
+            "rays": np.asarray(rays, np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every array as out_dir/<name>.npy; float32 / float64 only, DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"bench.py: --dump-outputs: {name} is {v.dtype}, not float32 / float64")
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 # ------------------------------------------------------------------------------------------------------------ self-launch
@@ -399,7 +431,7 @@ def main():
     n_inst = min(16, a.steps)
     nq = max(8, a.steps // 2)
     cam_ctl = frt.CameraController()
-    cams = [cam_ctl.build_uniform(W / H, f, nl) for f in range(max(total + n_inst + nq + 1, a.cpu_frames + 1))]
+    cams = [cam_ctl.build_uniform(W / H, f, nl) for f in range(max(total + n_inst + nq + 1, a.cpu_frames + 1) if a.full else total)]
 
     # strips of equal WORK (probe render, identical on every rank), not equal height
     bounds = None
@@ -489,15 +521,6 @@ def main():
     sync = torch.cuda.synchronize
     barrier = dist.barrier if dist else (lambda: None)
     elapsed, s0, s1 = timed_loop(frame, 0, a.warmup, a.steps, sync, barrier, r.stats)
-    # instrumented pass (outside the timed region): the same frame loop with the per-stage HIP events on
-    r.set_timing(True)
-    si0 = r.stats()
-    for f in range(total, total + n_inst):
-        frame(f)
-    torch.cuda.synchronize()
-    si1 = r.stats()
-    r.set_timing(False)
-    first_extra = total + n_inst
 
     def reduce_time_rays(el, n_rays):
         if not dist:
@@ -509,8 +532,31 @@ def main():
         return float(t.item()), int(n.item())
 
     elapsed, rays = reduce_time_rays(elapsed, rays_of(s0, s1))      # MAX over ranks of the timed region, SUM of the rays: from here on job-wide figures
+    if a.dump_outputs:
+        # the last timed frame, before any other frame is rendered: at N > 1 every rank's own rows, gathered into the full frame
+        acc, disp = r.read_accum(), r.read_display()
+        split = [s1["rays_closest"] - s0["rays_closest"], s1["rays_any"] - s0["rays_any"]]
+        if dist:
+            from frt.dist import gather_strips
+            acc, disp = [gather_strips(torch.from_numpy(x[plan.row_begin:plan.row_end]).to(comm_dev), plan).cpu().numpy() for x in (acc, disp)]
+            n = torch.tensor(split, dtype=torch.int64, device=comm_dev)
+            dist.all_reduce(n, op=dist.ReduceOp.SUM)
+            split = n.tolist()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, frame_outputs(acc, disp, split))
+        del acc, disp
+    if a.full:
+        # instrumented pass (outside the timed region): the same frame loop with the per-stage HIP events on
+        r.set_timing(True)
+        si0 = r.stats()
+        for f in range(total, total + n_inst):
+            frame(f)
+        torch.cuda.synchronize()
+        si1 = r.stats()
+        r.set_timing(False)
+    first_extra = total + n_inst
     exposed_ms, gather = None, None
-    if dist:
+    if dist and a.full:
         # What the halo transfers cost per frame: the same frame loop with the transfers switched off (the pixels of those frames are
         # wrong — neighbours' rows are stale — but the work is the same), timed the same way and reduced the same way (MAX over ranks);
         # the difference of the two job-wide times is the exposed transfer time.
@@ -554,7 +600,7 @@ def main():
 
     # configs[2]: the same scene at 3840x2160, the workload BASELINE.json tiles over 8 GPUs (extra key; the headline stays configs[1])
     extra4k = None
-    if not a.no_4k:
+    if a.full and not a.no_4k:
         torch.cuda.synchronize()
         torch.cuda.set_stream(torch.cuda.default_stream())      # (the strip renderer's main stream goes away with the renderer)
         del r, rows, frame
@@ -574,30 +620,13 @@ def main():
 
     if rank == 0:
         K = a.steps
-        ms = [(b - c) / n_inst for b, c in zip(si1["ms_stage"], si0["ms_stage"])]
-        ms_merge = (si1["ms_merge"] - si0["ms_merge"]) / n_inst
-        stage_rays = [(s1["rays_stage"][i][0] + s1["rays_stage"][i][1] - s0["rays_stage"][i][0] - s0["rays_stage"][i][1]) / K for i in range(4)]
-        cpu, per_stage = (None, None)
-        if world == 1 and a.cpu_frames > 0:
-            cpu, per_stage = cpu_baseline(scene, cams, a.cpu_frames)
-        # Algorithmic bytes: rays * (32 B * nodes/ray + 48 B * tris/ray) + pixels * B_px per stage. nodes/ray and tris/ray
-        # are per-ray means on the canonical BVH2 measured by the oracle for that stage (same run at N = 1; the committed figures of
-        # DESIGN.md §6 otherwise).
-        defaults = {"gbuffer": (10.1, 1.7), "temporal": (18.8, 2.2), "spatial": (16.5, 2.1), "post": (0.0, 0.0)}
-        px = W * (plan.row_end - plan.row_begin)
-        stages = {}
-        for i, name in enumerate(STAGES):
-            npr, tpr = (per_stage[name]["nodes_per_ray"], per_stage[name]["tris_per_ray"]) if per_stage and name in per_stage else defaults[name]
-            algo = stage_rays[i] * (32.0 * npr + 48.0 * tpr) + px * B_PX[name]
-            stages[name] = {"event_ms": ms[i], "rays": stage_rays[i], "bytes_per_ray": 32.0 * npr + 48.0 * tpr, "algorithmic_bytes": algo}
-        stages["temporal"]["merge_event_ms"] = ms_merge
         frame_ms = elapsed / K * 1e3
-        roof = roofline_block(world, frame_ms, stages, px)
         par = "1 GPU, two-stream schedule"
         if world > 1:
             par = (f"{world} work-balanced image strips {bounds}; per frame ONE batched halo exchange with each neighbour ({('RCCL, grouped send / recv placed in the renderer edge stream (frt.rccl)' if comm is not None else 'RCCL through torch.distributed point-to-point operations') if a.backend == 'nccl' else 'gloo rehearsal'}), behind T-merge and overlapped with the "
-                   "spatial stage's interior rows: 12 reservoir rows + 1 row of the previous accumulation; "
-                   f"exposed transfer time {exposed_ms:.3f} ms/frame (frame loop with vs without the transfers)")
+                   "spatial stage's interior rows: 12 reservoir rows + 1 row of the previous accumulation")
+            if exposed_ms is not None:
+                par += f"; exposed transfer time {exposed_ms:.3f} ms/frame (frame loop with vs without the transfers)"
         out = {
             "metric": "Mrays/sec, 1920x1080 8-bounce Cornell Box", "value": rays / elapsed / 1e6, "unit": "Mrays/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": frame_ms,
@@ -606,19 +635,37 @@ def main():
                        "rays_per_frame": rays / a.steps, "parallelism": par,
                        "backend": (dist.get_backend() if dist else None), "process_group_world_size": (dist.get_world_size() if dist else 1),
                        "allreduce_of_ones": allreduce_ranks, "ranks": ranks, "one_gpu_rehearsal": one_gpu,
-                       "self_launched": os.environ.get("FRT_BENCH_SELF_LAUNCHED") == "1",
+                       "self_launched": os.environ.get("FRT_BENCH_SELF_LAUNCHED") == "1", "full": a.full,
                        "speculated_frames": s1["speculated_frames"] - s0["speculated_frames"], "queue_overflow": s1["queue_overflow"],
                        "exchange_exposed_ms": exposed_ms, "gather_ms": gather["ms"] if gather else None, "gather": gather,
                        "exchange": (None if not dist else "frt.rccl: grouped ncclSend / ncclRecv in the renderer's edge stream" if comm is not None
                                     else "torch.distributed batch_isend_irecv" + (" (gloo rehearsal)" if a.backend != "nccl" else ""))},
-            "roofline": roof,
-            "stage_ms": dict(zip(STAGES, ms)),
-            "stage_ms_note": f"per-stage HIP event times of a separate instrumented pass of {n_inst} frames after the timed region (the timed region records no events)",
         }
-        if extra4k:
-            out["config2_4k"] = extra4k
-        if cpu:
-            out["cpu_baseline"] = cpu
+        if a.full:
+            ms = [(b - c) / n_inst for b, c in zip(si1["ms_stage"], si0["ms_stage"])]
+            ms_merge = (si1["ms_merge"] - si0["ms_merge"]) / n_inst
+            stage_rays = [(s1["rays_stage"][i][0] + s1["rays_stage"][i][1] - s0["rays_stage"][i][0] - s0["rays_stage"][i][1]) / K for i in range(4)]
+            cpu, per_stage = (None, None)
+            if world == 1 and a.cpu_frames > 0:
+                cpu, per_stage = cpu_baseline(scene, cams, a.cpu_frames)
+            # Algorithmic bytes: rays * (32 B * nodes/ray + 48 B * tris/ray) + pixels * B_px per stage. nodes/ray and tris/ray
+            # are per-ray means on the canonical BVH2 measured by the oracle for that stage (same run at N = 1; the committed figures of
+            # DESIGN.md §6 otherwise).
+            defaults = {"gbuffer": (10.1, 1.7), "temporal": (18.8, 2.2), "spatial": (16.5, 2.1), "post": (0.0, 0.0)}
+            px = W * (plan.row_end - plan.row_begin)
+            stages = {}
+            for i, name in enumerate(STAGES):
+                npr, tpr = (per_stage[name]["nodes_per_ray"], per_stage[name]["tris_per_ray"]) if per_stage and name in per_stage else defaults[name]
+                algo = stage_rays[i] * (32.0 * npr + 48.0 * tpr) + px * B_PX[name]
+                stages[name] = {"event_ms": ms[i], "rays": stage_rays[i], "bytes_per_ray": 32.0 * npr + 48.0 * tpr, "algorithmic_bytes": algo}
+            stages["temporal"]["merge_event_ms"] = ms_merge
+            out["roofline"] = roofline_block(world, frame_ms, stages, px)
+            out["stage_ms"] = dict(zip(STAGES, ms))
+            out["stage_ms_note"] = f"per-stage HIP event times of a separate instrumented pass of {n_inst} frames after the timed region (the timed region records no events)"
+            if extra4k:
+                out["config2_4k"] = extra4k
+            if cpu:
+                out["cpu_baseline"] = cpu
         emit_result(out)
     if comm is not None:
         torch.cuda.synchronize()
@@ -642,16 +689,13 @@ def main_native(a):
         mr = frt.MultiRenderer(scene, width, height, devices, max_depth=MAX_DEPTH)
         cams = [frt.CameraController().build_uniform(width / height, f, nl) for f in range(warmup + steps)]
         el, s0, s1 = timed_loop(lambda f: mr.render(cams[f]), 0, warmup, steps, mr.sync, lambda: None, mr.stats)
-        return mr, el, rays_of(s0, s1)
+        return mr, el, s0, s1
 
-    mr, elapsed, rays = run(W, H, a.warmup, a.steps)
-    # the presented image: device-side gather of the strips' rows (peer copies over xGMI) on the first device + ONE device-to-host copy
-    rd = []
-    for _ in range(3):
-        mr.sync()
-        t0 = time.perf_counter()
-        img = mr.read_display()
-        rd.append((time.perf_counter() - t0) * 1e3)
+    mr, elapsed, s0, s1 = run(W, H, a.warmup, a.steps)
+    rays = rays_of(s0, s1)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, frame_outputs(mr.read_accum(), mr.read_display(),
+                                                   [s1["rays_closest"] - s0["rays_closest"], s1["rays_any"] - s0["rays_any"]]))
     peer = mr.peer_access()
     out = {"metric": "Mrays/sec, 1920x1080 8-bounce Cornell Box", "value": rays / elapsed / 1e6, "unit": "Mrays/s",
            "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
@@ -659,13 +703,23 @@ def main_native(a):
            "config": {"workload": "Cornell Box 1920x1080, MAX_DEPTH 8, 1 candidate path/pixel/frame, 4-stage ReSTIR-PT frame (BASELINE.json configs[1])",
                       "rays_per_frame": rays / a.steps,
                       "parallelism": f"frt_multi_renderer: ONE process, {a.gpus} strip renderers on devices {devices}, halo rows by hipMemcpyPeerAsync, boundaries {mr.boundaries()}",
-                      "one_gpu_rehearsal": one_gpu, "native": True, "peer_access": peer,
-                      "gather_ms": min(rd), "gather": {"ms": min(rd), "ms_first": rd[0], "bytes": int(img.nbytes),
-                                                       "what": "frt_multi_renderer_read_display: device-side gather of the strips (peer copies) + one device-to-host copy"}}}
+                      "one_gpu_rehearsal": one_gpu, "native": True, "peer_access": peer, "full": a.full}}
+    if a.full:
+        # the presented image: device-side gather of the strips' rows (peer copies over xGMI) on the first device + ONE device-to-host copy
+        rd = []
+        for _ in range(3):
+            mr.sync()
+            t0 = time.perf_counter()
+            img = mr.read_display()
+            rd.append((time.perf_counter() - t0) * 1e3)
+        out["config"]["gather_ms"] = min(rd)
+        out["config"]["gather"] = {"ms": min(rd), "ms_first": rd[0], "bytes": int(img.nbytes),
+                                   "what": "frt_multi_renderer_read_display: device-side gather of the strips (peer copies) + one device-to-host copy"}
     del mr
-    if not a.no_4k:
+    if a.full and not a.no_4k:
         k4 = max(4, min(16, a.steps))
-        mr4, el4, rays4 = run(W4K, H4K, 4, k4)
+        mr4, el4, q0, q1 = run(W4K, H4K, 4, k4)
+        rays4 = rays_of(q0, q1)
         out["config2_4k"] = {"workload": "Cornell Box 3840x2160, MAX_DEPTH 8 (BASELINE.json configs[2])", "value": rays4 / el4 / 1e6, "unit": "Mrays/s",
                              "ms_per_step": el4 / k4 * 1e3, "steps": k4, "warmup": 4, "rays_per_frame": rays4 / k4, "rows": mr4.boundaries()}
     emit_result(out)

@@ -45,3 +45,35 @@ def test_a_failing_rank_fails_the_launch():
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=300, env=_clean_env())
     assert p.returncode != 0
     assert "no HIP device" in p.stderr and "exited with code" in p.stderr
+
+
+def test_plain_run_options():
+    """A plain run measures the headline only; --full adds the rest, --dump-outputs names the folder of the last step's outputs."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """What --dump-outputs writes for a 1920x1080 frame: float32 / float64 .npy files, 64 MB at most, the values unchanged."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    acc = rng.random((1080, 1920, 4), dtype=np.float32)
+    disp = rng.integers(0, 256, (1080, 1920, 4), dtype=np.uint8)
+    arrays = bench.frame_outputs(acc, disp, [17, 5])
+    assert sum(v.nbytes for v in arrays.values()) <= bench.DUMP_LIMIT_BYTES == 64 * 10**6
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert sorted(os.listdir(tmp_path / "out")) == ["accum.npy", "display.npy", "rays.npy"]
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("accum", "display", "rays")}
+    assert got["accum"].dtype == np.float32 and np.array_equal(got["accum"], acc)
+    assert got["display"].dtype == np.float32 and np.array_equal(got["display"], disp[..., :3].astype(np.float32))
+    assert got["rays"].dtype == np.float64 and got["rays"].tolist() == [17.0, 5.0]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "int"), {"x": np.zeros(4, np.uint8)})

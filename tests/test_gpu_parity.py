@@ -531,15 +531,16 @@ def test_rccl_loopback_rehearsal_on_one_gpu(gpu):
         assert res[k]["direct_rows_arrive"] and res[k]["direct_equals_stepwise"], res
 
 
-def test_bench_self_launch_rehearsal_on_one_gpu(gpu):
-    """`python bench.py --gpus 2` from a bare shell (no RANK / WORLD_SIZE): bench.py starts its two ranks itself; both share this box's one
-    GPU over gloo (FRT_BENCH_ONE_GPU=1). One JSON line that names both ranks, their rows and devices."""
+def test_bench_self_launch_rehearsal_on_one_gpu(gpu, tmp_path):
+    """`python bench.py --gpus 2 --full` from a bare shell (no RANK / WORLD_SIZE): bench.py starts its two ranks itself; both share this box's one
+    GPU over gloo (FRT_BENCH_ONE_GPU=1). One JSON line that names both ranks, their rows and devices; the exposed transfer time and the gather
+    are measured; the strips' last timed frame, gathered by --dump-outputs, is the frame one renderer gives."""
     import json, subprocess, sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["FRT_BENCH_ONE_GPU"] = "1"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6", "--warmup", "2", "--no-4k"],
-                       capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6", "--warmup", "2", "--no-4k",
+                        "--full", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and p.stdout.strip().splitlines() == lines      # the JSON line and nothing else (gloo's chatter goes to stderr)
@@ -548,16 +549,60 @@ def test_bench_self_launch_rehearsal_on_one_gpu(gpu):
     assert res["n_gpus"] == 2 and cfg["process_group_world_size"] == 2 and cfg["allreduce_of_ones"] == 2 and cfg["self_launched"]
     assert [r["rank"] for r in cfg["ranks"]] == [0, 1] and cfg["ranks"][0]["rows"][1] == cfg["ranks"][1]["rows"][0]
     assert res["value"] > 0 and res["scaling"] == "strong"
+    assert cfg["exchange_exposed_ms"] is not None and cfg["gather"]["shape"][0] == 1080
+    _check_dumped_frame(gpu, tmp_path / "out", 2, 6, res)
+
+
+def _check_dumped_frame(frt, out_dir, warmup, steps, res):
+    """bench.py --dump-outputs DIR: the last timed 1920x1080 frame, bit for bit what one renderer in this process gives after the same
+    warmup + steps cameras, and the ray counts of the timed steps; float32 / float64 only, 64 MB at most."""
+    assert sorted(os.listdir(out_dir)) == ["accum.npy", "display.npy", "rays.npy"]
+    got = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in ("accum", "display", "rays")}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64e6
+    scene = frt.scenes.create_cornell_box()
+    r = frt.Renderer(scene, 1920, 1080, max_depth=8, flags=frt.FLAG_PIPELINE)
+    ctl = frt.CameraController()
+    cams = [ctl.build_uniform(1920 / 1080, f, scene.num_lights) for f in range(warmup + steps)]
+    for f in range(warmup):
+        r.render(cams[f])
+    s0 = r.stats()
+    for f in range(warmup, warmup + steps):
+        r.render(cams[f])
+    s1 = r.stats()
+    assert np.array_equal(got["accum"], r.read_accum())
+    assert np.array_equal(got["display"], r.read_display()[..., :3].astype(np.float32))
+    assert got["rays"].tolist() == [s1["rays_closest"] - s0["rays_closest"], s1["rays_any"] - s0["rays_any"]]
+    assert got["rays"].sum() == res["config"]["rays_per_frame"] * steps
+
+
+def test_bench_plain_line_and_outputs_at_one_gpu(gpu, tmp_path):
+    """The line every measurement parses: `python bench.py --gpus 1 --steps K --warmup W` prints exactly one JSON line with the headline keys
+    and leaves out what takes runs of its own (--full's); --dump-outputs writes the last of the K timed frames."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    out = p.stdout.strip().splitlines()
+    assert len(out) == 1, p.stdout[:2000]
+    res = json.loads(out[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 5 and res["warmup"] == 2 and res["unit"] == "Mrays/s" and res["dtype"] == "f32"
+    assert res["higher_is_better"] is True and res["metric"].startswith("Mrays/sec") and 0.5 < res["ms_per_step"] < 20 and res["config"]["full"] is False
+    assert abs(res["value"] - res["config"]["rays_per_frame"] / res["ms_per_step"] / 1e3) < 1e-6 * res["value"]
+    for k in ("roofline", "stage_ms", "cpu_baseline", "config2_4k"):
+        assert k not in res, k
+    _check_dumped_frame(gpu, tmp_path / "out", 2, 5, res)
 
 
 def test_bench_line_contract_at_one_gpu(gpu):
-    """The line the round driver parses: `python bench.py --gpus 1 --steps K --warmup W` prints exactly one line on stdout, a JSON object with the
+    """The full line: `python bench.py --gpus 1 --steps K --warmup W --full` prints exactly one line on stdout, a JSON object with the
     contract's keys, a roofline block (achieved / peak / frac / traffic from the committed counters when they match the kernel sources) and a CPU
     baseline measured in the same run."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--cpu-frames", "1", "--no-4k"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--cpu-frames", "1", "--no-4k", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     out = p.stdout.strip().splitlines()

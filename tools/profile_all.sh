@@ -2,7 +2,7 @@
 # Collects the evidence bench.py's roofline block cites, on the GPU box (run through gpurun from the repo root):
 #   1. rocprofv3 --kernel-trace --stats of the default bench command      -> gpurun_out/prof_<tag>/…kernel_stats.csv
 #   2. separate --pmc passes (never combined with other trace domains)     -> gpurun_out/pmc_<tag>_*/…counter_collection.csv
-#   3. the bench line itself, with the CPU baseline                        -> gpurun_out/bench_<tag>.json
+#   3. the full bench line (bench.py --full: roofline, CPU baseline)       -> the last line of this script's stdout
 # then prints tools/pmc_summary.py over the PMC passes. Afterwards, in the repository: python tools/pmc_to_json.py <tag> > profiles/<tag>_pmc.json
 # (bench.py's roofline block reads it) and copy what should be judged into profiles/.
 set -o pipefail
@@ -24,5 +24,4 @@ bash tools/pmc_ta.sh ${TAG}ta > gpurun_out/pmc_ta_$TAG.log 2>&1 || { tail -3 gpu
 python3 tools/pmc_summary.py gpurun_out/pmc_${TAG}_0 gpurun_out/pmc_${TAG}_1 gpurun_out/pmc_${TAG}_2 gpurun_out/pmc_${TAG}_3 > gpurun_out/pmc_$TAG.txt
 cat gpurun_out/pmc_$TAG.txt
 find gpurun_out/prof_$TAG -name "*kernel_stats.csv" -exec cp {} gpurun_out/kernel_stats_$TAG.csv \;
-timeout -k 10 400 python3 bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
-cut -c1-400 gpurun_out/bench_$TAG.json
+timeout -k 10 400 python3 bench.py --full || exit 1
