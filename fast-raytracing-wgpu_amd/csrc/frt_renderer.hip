@@ -150,6 +150,7 @@ struct frt_renderer {
     // progress and of the last finished frames (what reads through the ABI see)
     uint32_t logical_phys[2] = {0, 1};
     GSlots cur_slots{0, 1, 0}, last_slots{0, 1, 0}, before_last_slots{1, 0, 0};
+    uint32_t last_parity = 0;              // frame_count % 2 of the frame that recorded last_slots (the counter may move without a frame: end_frame, reset)
     // speculation: G-buffer + T-trace of the next frames, enqueued on `ahead` under the cameras a static scene will present
     struct Spec { frt_camera_uniform cam; uint32_t frame; GSlots slots; uint32_t logical_before[2]; int idx; };
     std::vector<Spec> specs;               // oldest first, at most kSpecDepth
@@ -1158,7 +1159,7 @@ int frt_renderer_end_frame(frt_renderer* r) {
     r->frame_count += 1;   // renderer.rs:515
     r->serial += 1;
     r->stats.frames += 1;
-    if (r->frame_open) { r->last_cam = r->cur_cam; r->have_last_cam = true; r->before_last_slots = r->last_slots; r->last_slots = r->cur_slots; }
+    if (r->frame_open) { r->last_cam = r->cur_cam; r->have_last_cam = true; r->before_last_slots = r->last_slots; r->last_slots = r->cur_slots; r->last_parity = (r->frame_count - 1u) & 1u; }
     r->frame_open = false;
     return FRT_OK;
 }
@@ -1232,16 +1233,16 @@ int frt_renderer_clear(frt_renderer* r) {
     r->failed = false;
     r->frame_open = false; r->specs.clear(); r->have_last_cam = false; r->camera_static = false;
     r->qparity[0] = r->qparity[1] = 0; r->logical_phys[0] = 0; r->logical_phys[1] = 1;
-    r->cur_slots = r->last_slots = GSlots{0, 1, 0}; r->before_last_slots = GSlots{1, 0, 0};
+    r->cur_slots = r->last_slots = GSlots{0, 1, 0}; r->before_last_slots = GSlots{1, 0, 0}; r->last_parity = 0;
     memset(&r->stats, 0, sizeof(r->stats));
     return FRT_OK;
 }
 
 // Reads through the ABI see the reference's two logical slots as of the last finished frame F: slot F % 2 is that frame's G-buffer, the other
-// one what it read as `prev` (work running ahead writes a third physical set and is invisible here).
+// one what it read as `prev` (work running ahead writes a third physical set and is invisible here). F's parity is the one recorded with
+// its slots, not frame_count - 1: end_frame without a rendered frame and reset move the counter but rename no slot.
 static int buf_index(const frt_renderer* r, int buf, int index) {
-    const uint32_t last_parity = r->frame_count ? ((r->frame_count - 1u) & 1u) : 0u;
-    const uint32_t g = ((uint32_t)index & 1u) == last_parity ? r->last_slots.g : r->last_slots.gprev;
+    const uint32_t g = ((uint32_t)index & 1u) == r->last_parity ? r->last_slots.g : r->last_slots.gprev;
     switch (buf) {
     case FRT_BUF_GPOS: return B_GPOS0 + (int)g;
     case FRT_BUF_GNORMAL: return B_GNRM0 + (int)g;

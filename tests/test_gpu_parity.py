@@ -32,7 +32,8 @@ def gpu(frt):
 
 
 @pytest.mark.parametrize("which,W,H,depth,frames", [("cornell", 128, 128, 8, 8), ("cornell", 128, 128, 1, 2), ("cornell", 200, 120, 8, 4),
-                                                    ("cornell", 37, 19, 8, 3), ("cornell", 96, 64, 16, 3), ("restir", 160, 96, 8, 4)])
+                                                    ("cornell", 37, 19, 8, 3), ("cornell", 96, 64, 16, 3), ("restir", 160, 96, 8, 4)] +
+                         [(w, W, H, 8, 3) for w in ("cornell", "restir") for W, H in ((1, 1), (1, 9), (9, 1), (2, 3), (7, 5), (15, 17), (16, 16), (17, 16))])
 def test_kernels_match_oracle_every_buffer(gpu, orc, which, W, H, depth, frames):
     frt = gpu
     fs = frt.scenes.create_cornell_box() if which == "cornell" else frt.scenes.create_restir_scene()
@@ -626,3 +627,21 @@ def test_bench_line_contract_at_one_gpu(gpu):
     assert abs(roof["frac"] - want) <= 1e-6 * want
     cpu = res["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and cpu["value"] > 0 and "sample" in cpu and cpu["unit"] == "Mrays/s"
+
+
+@pytest.mark.parametrize("W,H", [(1, 1), (9, 1), (2, 3), (17, 16)])
+def test_tiny_frames_pipeline_and_moving_camera(gpu, orc, W, H):
+    """Tiny frames with FRT_FLAG_PIPELINE (speculated G-buffer + T-trace) and with a moving camera: every buffer, exact ray counts."""
+    frt = gpu
+    import _scenes
+    fs, os_ = frt.scenes.create_cornell_box(), orc.cornell()
+    os_.set_bvh(fs.get("bvh2_nodes"), fs.get("bvh2_tri_index"))
+    for flags, cams in ((frt.FLAG_PIPELINE, [frt.CameraController().build_uniform(W / H, f, fs.num_lights) for f in range(3)]),
+                        (0, _scenes.moving_camera_uniforms(frt, W / H, fs.num_lights, 3))):
+        r = frt.Renderer(fs, W, H, max_depth=8, flags=flags)
+        ro = os_.renderer(W, H, 8, True, 16)
+        for f, cam in enumerate(cams):
+            r.render(cam); ro.render(cam)
+            compare_all(r.read_buffer, ro.read, f, f"{W}x{H} flags {flags}")
+        st, so = r.stats(), ro.stats()["total"]
+        assert (st["rays_closest"], st["rays_any"]) == (so["closest"], so["any"])

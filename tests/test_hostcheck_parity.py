@@ -83,3 +83,24 @@ def test_jittered_frames_match_oracle(frt, orc, hostcheck, scale):
         ro2.render(cam)
     assert ro2.read(7, 1).tobytes() != ro.read(7, 1).tobytes()
     assert ctl.get_halton_jitter(3, W, H) == (0.0, 0.0) or ctl.get_halton_jitter(3, W, H) == (-0.0, 0.0)     # the shipped reference: x 0
+
+
+TINY = [(1, 1), (1, 9), (9, 1), (2, 3), (7, 5), (15, 17), (16, 16), (17, 16)]
+
+
+@pytest.mark.parametrize("sm", [0, 1003, 2003], ids=["straight", "split_cut3", "stream_cut3"])
+@pytest.mark.parametrize("which", ["cornell", "restir"])
+@pytest.mark.parametrize("W,H", TINY, ids=[f"{w}x{h}" for w, h in TINY])
+def test_tiny_frames_match_oracle(frt, orc, hostcheck, W, H, which, sm):
+    """Frames below one 16 x 16 tile, a single row or column, and the sizes around the tile edge: every buffer, exact ray counts."""
+    fs = frt.scenes.create_cornell_box() if which == "cornell" else frt.scenes.create_restir_scene()
+    os_ = orc.cornell() if which == "cornell" else orc.restir_scene()
+    os_.set_bvh(fs.get("bvh2_nodes"), fs.get("bvh2_tri_index"))
+    ro = os_.renderer(W, H, 8, True, 8)
+    rh = hostcheck.renderer(fs, W, H, 8, 8, state_machine=sm)
+    for f in range(3):
+        cam = frt.CameraController().build_uniform(W / H, f, fs.num_lights)
+        ro.render(cam); rh.render(cam)
+        compare_all(rh.read, ro.read, f, f"{which} {W}x{H}")
+    st = ro.stats()["total"]
+    assert rh.rays() == (st["closest"], st["any"])

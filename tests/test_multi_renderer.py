@@ -213,3 +213,25 @@ def test_bench_native_rehearsal_on_one_gpu(gpu):
     assert res["n_gpus"] == 3 and res["config"]["native"] and res["value"] > 0
     assert res["config"]["full"] and res["config"]["gather"]["bytes"] == 1920 * 1080 * 4      # --full: the display read-back is timed
     assert 17.0e6 < res["config"]["rays_per_frame"] < 18.5e6          # the same frame as one renderer traces (17.76 M rays)
+
+
+@pytest.mark.parametrize("W", [1, 17])
+def test_multi_thinnest_strips(gpu, W):
+    """The thinnest strips frt_multi_renderer_create accepts (as tall as the 12-row halo, frt_multi.hip kHaloReservoir) equal a whole-frame
+    renderer bit for bit; one row less and creation is refused with FRT_ERR_INVALID_ARG, so nothing is rendered."""
+    frt = gpu
+    scene = frt.scenes.create_cornell_box()
+    H = 2 * 12
+    one = frt.Renderer(scene, W, H, flags=frt.FLAG_PIPELINE)
+    multi = frt.MultiRenderer(scene, W, H, [0, 0])
+    assert multi.boundaries() == [0, 12, 24]
+    for f in range(3):
+        cam = frt.CameraController().build_uniform(W / H, f, scene.num_lights)
+        one.render(cam); multi.render(cam)
+        got, want = _read_all(frt, multi), _read_all(frt, one)
+        for k in got:
+            assert got[k].tobytes() == want[k].tobytes(), f"frame {f}: {k} differs"
+    s1, sm = one.stats(), multi.stats()
+    assert (sm["rays_closest"], sm["rays_any"]) == (s1["rays_closest"], s1["rays_any"])
+    with pytest.raises(frt.FrtError, match="strips would be thinner than the halo"):    # set_error(FRT_ERR_INVALID_ARG, ...)
+        frt.MultiRenderer(scene, W, H - 1, [0, 0])

@@ -1,0 +1,36 @@
+"""The float64 references must be able to fail: each misreading of the shader text that motivates them (tests/_wgsl_f64.py, `mis`),
+applied to the float64 side only, makes the comparison against the oracle fail at the tolerances the comparisons use."""
+import numpy as np
+import pytest
+import _wgsl_f64 as R
+import test_wgsl_f64_gbuffer as G
+import test_wgsl_f64_post as P
+
+
+@pytest.mark.parametrize("mis,scene_name,cam_name", [("m_inv_transposed", "transforms", "static"), ("tbn_transposed", "textured", "static"),
+                                                     ("motion_sign", "cornell", "moving"), ("no_y_flip", "cornell", "moving"),
+                                                     ("oct_sign", "textured", "static"), ("clamp_to_edge", "textured", "static")])
+def test_gbuffer_misreading_is_caught(frt, orc, mis, scene_name, cam_name):
+    fs, os_, tex = G.SCENES[scene_name](frt, orc)
+    W, H = 128, 72
+    cam = G.camera(frt, cam_name, W / H)
+    ro = os_.renderer(W, H, 1, True, 8)
+    ro.render_phases(cam, 1, 0, H)
+    got = G._read_oracle(ro)
+    sc = R.scene_arrays(fs)
+    _, bad = G.residuals(got, G.reference(frt, scene_name, cam_name, W, H, sc, tex))
+    assert not bad, bad                                  # the faithful reading agrees ...
+    _, bad = G.residuals(got, R.gbuffer_f64(sc, cam, W, H, tex, mis={mis}))
+    assert bad, f"{mis}: the comparison does not notice this misreading"      # ... and the misreading does not
+    print(f" {mis}: {bad[0]}")
+
+
+
+@pytest.mark.parametrize("mis,W,H,fc", [("history_clamped", 15, 17, 1), ("speed_le", 16, 16, 1)])
+def test_post_misreading_is_caught(frt, orc, mis, W, H, fc):
+    """history_clamped: off-image history taps read the nearest pixel instead of contributing 0 (post.wgsl:219-222, kept on purpose);
+    speed_le: the still / moving switch taken at speed == 0.5 (crafted: exactly half a pixel along x, exact in f32 at W = 16)."""
+    _, _, (inp, accum, display) = P._oracle_case(frt, orc, W, H, fc, (0.0, 0.0))
+    P.check(inp, accum, display, W, H, fc, (0.0, 0.0))                              # the faithful reading agrees ...
+    with pytest.raises(AssertionError):
+        P.check(inp, accum, display, W, H, fc, (0.0, 0.0), mis={mis})               # ... and the misreading does not
