@@ -295,10 +295,12 @@ void SceneBuilder::ensure_wide8() const {
 }
 
 void SceneBuilder::build_gpu_layout() {
-    pair_nodes.clear(); tri_slots.clear(); instances_dev.clear(); shade_tris.clear();
+    pair_nodes.clear(); tri_slots.clear(); tri_slot_of.clear(); instances_dev.clear(); shade_tris.clear();
     if (!error.empty()) return;
     // triangle slots in leaf (bvh2_tri_index) order
     tri_slots.resize(tris.size());
+    tri_slot_of.resize(tris.size());
+    for (size_t s = 0; s < tris.size(); ++s) tri_slot_of[bvh2_tri_index[s]] = (uint32_t)s;
     for (size_t s = 0; s < tris.size(); ++s) {
         uint32_t id = bvh2_tri_index[s];
         const TriRec& t = tris[id];
@@ -381,6 +383,72 @@ void SceneBuilder::build_gpu_layout() {
         d.mesh_id = instances[i].mesh_id; d.mat_id = instances[i].mat_id; d.first_tri = instances[i].first_tri; d.flip = instances[i].flip;
         memcpy(d.w2o, instances[i].w2o, sizeof(d.w2o));
     }
+}
+
+// Refit after set_instance_transforms: the scene pad from the new triangle bounds as build_bvh2 takes it, then every box of the
+// binary, pair and quad trees bottom-up as the padded union of what lies below it (children have larger indices than their parent in all three).
+// min / max are exact, so the boxes equal those of any evaluation order, the device's level by level included. The quantized pair nodes are made
+// again from the refit pair nodes; the 8-wide tree is dropped and made again from the refit binary tree on first use (ensure_wide8).
+void SceneBuilder::refit() {
+    Box scene_box; scene_box.reset();
+    std::vector<Box> leaf(tri_slots.size());
+    for (size_t s = 0; s < tri_slots.size(); ++s) {
+        const float* q = tri_slots[s].q;
+        float v0[3] = {q[0], q[1], q[2]}, v1[3], v2[3];
+        for (int a = 0; a < 3; ++a) { v1[a] = v0[a] + q[4 + a]; v2[a] = v0[a] + q[8 + a]; }
+        leaf[s].reset(); leaf[s].grow(v0); leaf[s].grow(v1); leaf[s].grow(v2);
+        scene_box.grow(leaf[s]);
+    }
+    float ext = 0.0f;
+    for (int a = 0; a < 3; ++a) ext = std::max(ext, std::max(fabsf(scene_box.lo[a]), fabsf(scene_box.hi[a])));
+    const float pad = 1e-4f * std::max(ext, 1.0f);
+    // the padded box of a leaf reference (kLeafFlag | count << 24 | first slot)
+    auto leaf_box = [&](uint32_t first, uint32_t count, float lo[3], float hi[3]) {
+        Box b; b.reset();
+        for (uint32_t s = first; s < first + count; ++s) b.grow(leaf[s]);
+        for (int a = 0; a < 3; ++a) { lo[a] = b.lo[a] - pad; hi[a] = b.hi[a] + pad; }
+    };
+    for (size_t i = bvh2.size(); i-- > 0;) {
+        frt_bvh2_node& n = bvh2[i];
+        if (n.count > 0) { leaf_box(n.left_first, n.count, n.bmin, n.bmax); continue; }
+        const frt_bvh2_node &l = bvh2[n.left_first], &r = bvh2[n.left_first + 1];
+        for (int a = 0; a < 3; ++a) { n.bmin[a] = std::min(l.bmin[a], r.bmin[a]); n.bmax[a] = std::max(l.bmax[a], r.bmax[a]); }
+    }
+    for (size_t i = pair_nodes.size(); i-- > 0;) {
+        PairNode& p = pair_nodes[i];
+        for (int c = 0; c < 2; ++c) {
+            uint32_t ref; memcpy(&ref, &p.q[12 + c], 4);
+            if (ref == kNoChild) continue;
+            float lo[3], hi[3];
+            if (ref & kLeafFlag) leaf_box(ref & 0xFFFFFFu, (ref >> 24) & 0x7Fu, lo, hi);
+            else {
+                const PairNode& k = pair_nodes[ref];
+                for (int a = 0; a < 3; ++a) { lo[a] = std::min(k.q[4 * a], k.q[4 * a + 1]); hi[a] = std::max(k.q[4 * a + 2], k.q[4 * a + 3]); }   // (inner pair nodes have two children)
+            }
+            for (int a = 0; a < 3; ++a) { p.q[4 * a + c] = lo[a]; p.q[4 * a + 2 + c] = hi[a]; }
+        }
+    }
+    for (size_t i = quad_nodes.size(); i-- > 0;) {
+        QuadNode& q = quad_nodes[i];
+        for (int c = 0; c < 4; ++c) {
+            uint32_t ref; memcpy(&ref, &q.q[24 + c], 4);
+            if (ref == kNoChild) continue;
+            float lo[3], hi[3];
+            if (ref & kLeafFlag) leaf_box(ref & 0xFFFFFFu, (ref >> 24) & 0x7Fu, lo, hi);
+            else {
+                const QuadNode& k = quad_nodes[ref];
+                for (int a = 0; a < 3; ++a) { lo[a] = std::numeric_limits<float>::infinity(); hi[a] = -lo[a]; }
+                for (int j = 0; j < 4; ++j) {
+                    uint32_t kr; memcpy(&kr, &k.q[24 + j], 4);
+                    if (kr == kNoChild) continue;
+                    for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], k.q[8 * a + j]); hi[a] = std::max(hi[a], k.q[8 * a + 4 + j]); }
+                }
+            }
+            for (int a = 0; a < 3; ++a) { q.q[8 * a + c] = lo[a]; q.q[8 * a + 4 + c] = hi[a]; }
+        }
+    }
+    quantize_pair_nodes(*this);
+    wide8 = Wide8{}; tri_slots8.clear(); wide8_built = false;
 }
 
 } // namespace frt

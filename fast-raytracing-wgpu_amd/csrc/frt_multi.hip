@@ -446,6 +446,18 @@ int frt_multi_renderer_clear(frt_multi_renderer* m) {
     return FRT_OK;
 }
 
+// Every strip moves its own replica (frt_renderer_set_instance_transforms: ordered on the strip's streams). The copy streams move reservoir and
+// accumulation rows only, never scene data. Arguments are checked on the first strip before any replica changes.
+int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
+    if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_instance_transforms: null");
+    if (m->failed) return set_error(FRT_ERR_STATE, "multi set_instance_transforms: the handle is failed; call frt_multi_renderer_clear");
+    for (size_t i = 0; i < m->strips.size(); ++i) {
+        const int rc = frt_renderer_set_instance_transforms(m->strips[i].r, n, ids, m_colmajor16);
+        if (rc) { if (i > 0) m->failed = true; return rc; }      // (a later strip can only fail in HIP: the replicas now differ)
+    }
+    return FRT_OK;
+}
+
 int frt_multi_renderer_set_jitter(frt_multi_renderer* m, float jx, float jy) {
     if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_jitter: null");
     if (m->strips.size() > 1 && (jx != 0.0f || jy != 0.0f))

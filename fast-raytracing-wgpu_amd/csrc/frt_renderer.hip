@@ -3,6 +3,7 @@
 // ping-pong wiring of src/passes/{gbuffer,restir,restir_spatial,post}.rs. There is no CPU path in this file.
 #include "frt_scene.hpp"
 #include "frt_kernels.hpp"
+#include "frt_refit.hpp"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cstdio>
@@ -100,6 +101,25 @@ struct ExpState {
 };
 #endif
 
+// What frt_renderer_set_instance_transforms needs beside the scene replica, made at create. Device: the object-space positions of every
+// mesh (16 B per vertex), the slot of every flattened triangle (4 B per triangle), one word for the scene extent and the moved-instance records
+// (208 B each, grown on demand). Host: per instance what its record needs, the registered lights' emission, the level ranges of both trees.
+struct RefitState {
+    bool ok = false;                       // level ranges found (both trees are numbered breadth-first: frt_bvh.cpp)
+    const float4* d_pos = nullptr;
+    const uint32_t* d_slot_of = nullptr;
+    const unsigned int* d_ext = nullptr;
+    std::vector<uint32_t> pos_offset;      // per mesh: its first vertex in d_pos
+    std::vector<InstanceRec> inst;         // mesh, first_tri, tri_count, light link
+    std::vector<frt_light> lights;         // the scene's lights as uploaded (emission of the registered ones)
+    std::vector<uint32_t> index_offset;    // per mesh
+    std::vector<uint32_t> pair_levels, quad_levels;   // level L of a tree = nodes [levels[L], levels[L + 1])
+    MovedInstance* d_rec = nullptr; size_t d_cap = 0;
+    MovedInstance* h_rec = nullptr; size_t h_cap = 0;   // pinned staging of the records
+    hipEvent_t ev_rec = nullptr; bool rec_pending = false;   // the last copy out of h_rec
+    uint64_t device_bytes = 0;
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -161,6 +181,7 @@ struct frt_renderer {
     uint8_t* extras = nullptr; size_t extras_bytes = 0;      // the buffers of is_extra(), when this renderer has them
     uint32_t gsets = 2;                    // G-buffer sets in use
     uint64_t serial = 0;                   // frames finished since creation (never reset: parity of the per-frame events)
+    RefitState rf;
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };
@@ -196,6 +217,53 @@ static const size_t kVoteMinQuadNodes = FRT_VOTE_MIN_NODES;
 #endif
 static const size_t kWideLdsMaxBytes = FRT_WIDE_LDS_MAX;
 #endif
+// Level ranges of a breadth-first tree whose node i has `kids(i, out)` inner children: boundaries of the levels, or empty if the numbering is not
+// breadth-first (then the renderer cannot refit).
+template <class Kids>
+static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
+    std::vector<uint32_t> level(n, 0u), bounds(1, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t c[4]; const int k = kids(i, c);
+        for (int j = 0; j < k; ++j) { if (c[j] <= i || c[j] >= n) return {}; level[c[j]] = level[i] + 1u; }
+    }
+    for (size_t i = 1; i < n; ++i) {
+        if (level[i] < level[i - 1]) return {};
+        if (level[i] != level[i - 1]) bounds.push_back((uint32_t)i);
+    }
+    bounds.push_back((uint32_t)n);
+    return bounds;
+}
+static int upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
+    RefitState& f = r->rf;
+    std::vector<float> pos;
+    f.pos_offset.clear(); f.index_offset.clear();
+    for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
+        f.pos_offset.push_back((uint32_t)(pos.size() / 4));
+        f.index_offset.push_back(b.mesh_infos[m].index_offset);
+        pos.insert(pos.end(), b.mesh_positions[m].begin(), b.mesh_positions[m].end());
+    }
+    int rc;
+    if ((rc = upload(r, pos, &f.d_pos))) return rc;
+    if ((rc = upload(r, b.tri_slot_of, &f.d_slot_of))) return rc;
+    std::vector<uint32_t> word(4, 0u);
+    if ((rc = upload(r, word, &f.d_ext))) return rc;
+    f.device_bytes = pos.size() * 4 + b.tri_slot_of.size() * 4 + 16;
+    f.inst = b.instances;
+    f.lights = b.lights;
+    f.pair_levels = level_ranges(b.pair_nodes.size(), [&](size_t i, uint32_t* c) {
+        int k = 0;
+        for (int j = 0; j < 2; ++j) { uint32_t ref; memcpy(&ref, &b.pair_nodes[i].q[12 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
+        return k;
+    });
+    f.quad_levels = level_ranges(b.quad_nodes.size(), [&](size_t i, uint32_t* c) {
+        int k = 0;
+        for (int j = 0; j < 4; ++j) { uint32_t ref; memcpy(&ref, &b.quad_nodes[i].q[24 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
+        return k;
+    });
+    f.ok = !f.pair_levels.empty() && !f.quad_levels.empty();
+    return FRT_OK;
+}
+
 static int upload_scene(frt_renderer* r, const SceneBuilder& b) {
     SceneView& sv = r->sv;
     int rc;
@@ -257,7 +325,7 @@ static int upload_scene(frt_renderer* r, const SceneBuilder& b) {
     sv.num_lights = (uint32_t)b.lights.size();
     sv.num_nodes = (uint32_t)b.pair_nodes.size();
     sv.num_tris = (uint32_t)b.tri_slots.size();
-    return FRT_OK;
+    return upload_refit_data(r, b);
 }
 
 static void phase_rows(const frt_renderer* r, uint32_t out[8]) {
@@ -442,6 +510,11 @@ int frt_scene_build(frt_scene* s) {
     if (!s->b.built) return fail(FRT_ERR_LIMIT, "build: " + s->b.error);
     return FRT_OK;
 }
+int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null");
+    const int rc = s->b.set_instance_transforms(n, ids, m_colmajor16);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 frt_scene* frt_scene_create_cornell_box(void) {
     frt_scene* s = new frt_scene();
     scenes::create_cornell_box(s->b);
@@ -486,6 +559,8 @@ int frt_scene_get(const frt_scene* s, int which, void* out) {
     case 12: b.ensure_wide8(); memcpy(out, b.tri_slots8.data(), b.tri_slots8.size() * sizeof(TriSlot)); break;
     case 13: memcpy(out, b.tri_slots.data(), b.tri_slots.size() * sizeof(TriSlot)); break;
     case 14: b.ensure_wide8(); memcpy(out, b.wide8.child_boxes.data(), b.wide8.child_boxes.size() * 4); break;
+    case 15: memcpy(out, b.pair_nodes.data(), b.pair_nodes.size() * sizeof(PairNode)); break;
+    case 16: memcpy(out, b.instances_dev.data(), b.instances_dev.size() * sizeof(InstanceDev)); break;
     default: return fail(FRT_ERR_INVALID_ARG, "get: unknown selector");
     }
     return FRT_OK;
@@ -538,6 +613,9 @@ void frt_renderer_destroy(frt_renderer* r) {
     for (auto& t : r->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     for (hipEvent_t e : r->event_pool) (void)hipEventDestroy(e);
     for (void* p : r->scene_allocs) (void)hipFree(p);
+    if (r->rf.d_rec) (void)hipFree(r->rf.d_rec);
+    if (r->rf.h_rec) (void)hipHostFree(r->rf.h_rec);
+    if (r->rf.ev_rec) (void)hipEventDestroy(r->rf.ev_rec);
     if (r->own_arena && r->arena) (void)hipFree(r->arena);
     if (r->extras) (void)hipFree(r->extras);
     if (r->d_counters) (void)hipFree(r->d_counters);
@@ -937,6 +1015,19 @@ static int grow_queues_if_overflowed(frt_renderer* r) {
     }
     return FRT_OK;
 }
+// The speculated frames are dropped, with everything speculated behind the first: order the main stream behind the work, clear its ray counts,
+// give the physical sets back; the buffers it wrote are simply overwritten by the stages that follow.
+static int drop_speculation(frt_renderer* r) {
+    if (r->specs.empty()) return FRT_OK;
+    const frt_renderer::Spec sp = r->specs.front();
+    int rc = fence_ahead(r);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(r->d_counters + C_PENDING, 0, 4 * kPending * sizeof(unsigned long long), r->stream));
+    r->logical_phys[0] = sp.logical_before[0]; r->logical_phys[1] = sp.logical_before[1];
+    r->stats.discarded_speculations += r->specs.size();
+    r->specs.clear();
+    return FRT_OK;
+}
 static int open_frame(frt_renderer* r, const frt_camera_uniform* cam) {
     // a wave of an earlier frame found its continuation queue full: grow the queues now, between two frames (one synchronisation, at most twice in
     // a renderer's life: 0.25 -> 0.5 -> 1 slot per pixel)
@@ -960,14 +1051,8 @@ static int open_frame(frt_renderer* r, const frt_camera_uniform* cam) {
             r->cur_spec_idx = sp.idx;
             r->stats.speculated_frames += 1;
         } else {
-            // dropped, with everything speculated behind it: order the main stream behind the work, clear its ray counts, give the physical
-            // sets back; the buffers it wrote are simply overwritten by the stages that follow
-            int rc = fence_ahead(r);
+            int rc = drop_speculation(r);
             if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(r->d_counters + C_PENDING, 0, 4 * kPending * sizeof(unsigned long long), r->stream));
-            r->logical_phys[0] = sp.logical_before[0]; r->logical_phys[1] = sp.logical_before[1];
-            r->stats.discarded_speculations += r->specs.size();
-            r->specs.clear();
         }
     }
     return FRT_OK;
@@ -1235,6 +1320,113 @@ int frt_renderer_clear(frt_renderer* r) {
     r->qparity[0] = r->qparity[1] = 0; r->logical_phys[0] = 0; r->logical_phys[1] = 1;
     r->cur_slots = r->last_slots = GSlots{0, 1, 0}; r->before_last_slots = GSlots{1, 0, 0}; r->last_parity = 0;
     memset(&r->stats, 0, sizeof(r->stats));
+    return FRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ moving instances
+// Ordering: every kernel that reads the scene was enqueued by a finished frame (no frame may be open). Those on the main stream precede the update
+// on it; the edge streams' spatial launches are behind the main stream's wait for ev_edge (end of every spatial stage); the ahead stream's work
+// (a speculated next frame) is fenced, and a speculation — traced under the old geometry — is dropped as if its camera had not matched. The next
+// frame's first kernel is enqueued behind the update on the main stream, or (a new speculation) on the ahead stream behind T-merge's event.
+static int set_instance_transforms_impl(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = drop_speculation(r);
+    if (rc) return rc;
+    if (r->ahead) { r->tail_pending = true; if ((rc = fence_ahead(r))) return rc; }
+    if (n == 0) return FRT_OK;
+    // the records, in the order given (an id given twice: the later record wins, as on the host)
+    std::vector<MovedInstance> rec;
+    std::vector<int> last(f.inst.size(), -1);
+    for (uint32_t k = 0; k < n; ++k) last[ids[k]] = (int)k;
+    uint32_t work = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (last[ids[k]] != (int)k) continue;
+        InstanceRec& in = f.inst[ids[k]];
+        const float* m = mats + 16 * (size_t)k;
+        memcpy(in.m, m, sizeof(in.m));
+        MovedInstance mi;
+        memset(&mi, 0, sizeof(mi));
+        mi.id = ids[k]; mi.first_tri = in.first_tri; mi.tri_count = in.tri_count;
+        mi.index_offset = f.index_offset[in.mesh_id]; mi.pos_offset = f.pos_offset[in.mesh_id];
+        mi.work_begin = work; work += in.tri_count;
+        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) mi.m[3 * c + a] = m[4 * c + a];
+        InstanceDev d;
+        memset(&d, 0, sizeof(d));
+        d.mesh_id = in.mesh_id; d.mat_id = in.mat_id; d.first_tri = in.first_tri;
+        instance_inverse(m, d.w2o, d.flip);
+        memcpy(&mi.dev, &d, sizeof(d));
+        mi.light = 0xFFFFFFFFu;
+        if (in.light >= 0 && (size_t)in.light < f.lights.size()) {
+            Mat4 t; memcpy(t.m, m, sizeof(t.m));
+            const frt_light l = in.light_kind == 0 ? quad_light_record(t, f.lights[(size_t)in.light].emission) : sphere_light_record(t, f.lights[(size_t)in.light].emission);
+            mi.light = (uint32_t)in.light;
+            memcpy(&mi.light_rec, &l, sizeof(l));
+        }
+        rec.push_back(mi);
+    }
+    // staging: pinned, reused once the previous copy out of it has completed
+    if (!f.ev_rec) HIP_TRY(hipEventCreateWithFlags(&f.ev_rec, hipEventDisableTiming));
+    if (f.rec_pending) { HIP_TRY(hipEventSynchronize(f.ev_rec)); f.rec_pending = false; }
+    if (f.h_cap < rec.size()) {
+        if (f.h_rec) HIP_TRY(hipHostFree(f.h_rec));
+        f.h_rec = nullptr; f.h_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&f.h_rec, rec.size() * sizeof(MovedInstance)));
+        f.h_cap = rec.size();
+    }
+    if (f.d_cap < rec.size()) {
+        HIP_TRY(hipStreamSynchronize(r->stream));      // (an earlier update may still read the old records)
+        if (f.d_rec) HIP_TRY(hipFree(f.d_rec));
+        f.d_rec = nullptr; f.d_cap = 0;
+        HIP_TRY(hipMalloc((void**)&f.d_rec, rec.size() * sizeof(MovedInstance)));
+        f.d_cap = rec.size();
+    }
+    memcpy(f.h_rec, rec.data(), rec.size() * sizeof(MovedInstance));
+    HIP_TRY(hipMemcpyAsync(f.d_rec, f.h_rec, rec.size() * sizeof(MovedInstance), hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(f.ev_rec, r->stream));
+    f.rec_pending = true;
+    RefitArgs a{f.d_rec, (uint32_t)rec.size(), work, f.d_pos, f.d_slot_of, const_cast<unsigned int*>(f.d_ext)};
+    HIP_TRY(launch_instance_transform(r->sv, a, r->stream));
+    // both trees level by level, deepest first: launch k refits the k-th deepest level of each
+    const size_t lp = f.pair_levels.size() - 1, lq = f.quad_levels.size() - 1;
+    for (size_t k = 0; k < std::max(lp, lq); ++k) {
+        uint32_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
+        if (k < lp) { p0 = f.pair_levels[lp - 1 - k]; p1 = f.pair_levels[lp - k]; }
+        if (k < lq) { q0 = f.quad_levels[lq - 1 - k]; q1 = f.quad_levels[lq - k]; }
+        HIP_TRY(launch_refit_level(r->sv, f.d_ext, p0, p1, q0, q1, r->stream));
+    }
+    return FRT_OK;
+}
+int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
+    if (!r) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null");
+    if (r->failed) return fail(FRT_ERR_STATE, "set_instance_transforms: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
+    if (r->frame_open) return fail(FRT_ERR_STATE, "set_instance_transforms: a frame is open (call it between frames)");
+    if (!r->rf.ok) return fail(FRT_ERR_STATE, "set_instance_transforms: the scene's trees are not numbered breadth-first");
+#if FRT_EXPERIMENTS
+    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
+        return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: this renderer walks the 8-wide tree or the quantized pair nodes, which are not refit");
+#endif
+    const std::string bad = check_instance_transforms(n, ids, m_colmajor16, r->rf.inst.size());
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: " + bad);
+    const int rc = set_instance_transforms_impl(r, n, ids, m_colmajor16);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
+    if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
+    const SceneView& sv = r->sv;
+    const void* src = nullptr; size_t bytes = 0;
+    switch (which) {
+    case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
+    case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
+    case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
+    case 15: src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
+    case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
+    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16)");
+    }
+    FRT_DEVICE(r);
+    { int rc = sync_all(r); if (rc) return rc; }
+    if (bytes) HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return FRT_OK;
 }
 

@@ -242,21 +242,35 @@ void SceneBuilder::add_instance(uint32_t mesh_id, uint32_t mat_id, const Mat4& t
     built = false;
 }
 
-void SceneBuilder::add_quad_light(const float pos[3], const float u[3], const float v[3], const float emission[4]) {
+static frt_light make_quad_light(const float pos[3], const float u[3], const float v[3], const float emission[4]) {
     float cx = u[1] * v[2] - u[2] * v[1], cy = u[2] * v[0] - u[0] * v[2], cz = u[0] * v[1] - u[1] * v[0];
     frt_light l{};
     memcpy(l.position, pos, 12); memcpy(l.u, u, 12); memcpy(l.v, v, 12); memcpy(l.emission, emission, 16);
     l.type_ = 0;
     l.area = sqrtf(cx * cx + cy * cy + cz * cz) * 4.0f;   // |(2u) x (2v)|
-    lights.push_back(l);
+    return l;
 }
-void SceneBuilder::add_sphere_light(const float center[3], float radius, const float emission[4]) {
+static frt_light make_sphere_light(const float center[3], float radius, const float emission[4]) {
     frt_light l{};
     memcpy(l.position, center, 12); memcpy(l.emission, emission, 16);
     l.type_ = 1;
     l.area = 4.0f * 3.14159265358979323846f * radius * radius;
     l.v[0] = radius;
-    lights.push_back(l);
+    return l;
+}
+void SceneBuilder::add_quad_light(const float pos[3], const float u[3], const float v[3], const float emission[4]) { lights.push_back(make_quad_light(pos, u, v, emission)); }
+void SceneBuilder::add_sphere_light(const float center[3], float radius, const float emission[4]) { lights.push_back(make_sphere_light(center, radius, emission)); }
+frt_light quad_light_record(const Mat4& t, const float emission[4]) {
+    float u[3], v[3];
+    xform_vec3(t, 1, 0, 0, u); xform_vec3(t, 0, 0, -1, v);
+    for (int i = 0; i < 3; ++i) { u[i] *= 0.5f; v[i] *= 0.5f; }
+    return make_quad_light(&t.m[12], u, v, emission);
+}
+frt_light sphere_light_record(const Mat4& t, const float emission[4]) {
+    float x[3];
+    xform_vec3(t, 1, 0, 0, x);
+    float scale = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    return make_sphere_light(&t.m[12], scale * 0.5f, emission);
 }
 static frt_material emissive_material(size_t light_index, const float color[3], float intensity) {
     return MaterialBuilder(1, 1, 1, 1).light_index((int32_t)light_index)
@@ -265,55 +279,104 @@ static frt_material emissive_material(size_t light_index, const float color[3], 
 void SceneBuilder::register_quad_light(uint32_t mesh_id, const Mat4& t, const float color[3], float intensity) {
     uint32_t mat = add_material(emissive_material(lights.size(), color, intensity));
     add_instance(mesh_id, mat, t);
-    float u[3], v[3];
-    xform_vec3(t, 1, 0, 0, u); xform_vec3(t, 0, 0, -1, v);
-    for (int i = 0; i < 3; ++i) { u[i] *= 0.5f; v[i] *= 0.5f; }
+    instances.back().light = (int32_t)lights.size(); instances.back().light_kind = 0;
     const float em[4] = {color[0], color[1], color[2], intensity};
-    add_quad_light(&t.m[12], u, v, em);
+    lights.push_back(quad_light_record(t, em));
 }
 void SceneBuilder::register_sphere_light(uint32_t mesh_id, const Mat4& t, const float color[3], float intensity) {
     uint32_t mat = add_material(emissive_material(lights.size(), color, intensity));
     add_instance(mesh_id, mat, t);
-    float x[3];
-    xform_vec3(t, 1, 0, 0, x);
-    float scale = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    instances.back().light = (int32_t)lights.size(); instances.back().light_kind = 1;
     const float em[4] = {color[0], color[1], color[2], intensity};
-    add_sphere_light(&t.m[12], scale * 0.5f, em);
+    lights.push_back(sphere_light_record(t, em));
 }
 
 // Instances -> world-space triangles (contract): p_world = ((c0*x + c1*y) + c2*z) + c3 in f32,
 // e1 = v1 - v0, e2 = v2 - v0; world_to_object 3x3 by cofactors in double, rounded once to f32.
+static double cofactor_inverse(const float m[16], float w2o[9], uint32_t& flip) {
+    double a = m[0], b = m[4], c = m[8], d = m[1], e = m[5], f = m[9], g = m[2], h = m[6], i = m[10];
+    double k00 = e * i - f * h, k01 = f * g - d * i, k02 = d * h - e * g;
+    double det = a * k00 + b * k01 + c * k02;
+    double inv[3][3] = {{k00 / det, (c * h - b * i) / det, (b * f - c * e) / det},
+                        {k01 / det, (a * i - c * g) / det, (c * d - a * f) / det},
+                        {k02 / det, (b * g - a * h) / det, (a * e - b * d) / det}};
+    for (int col = 0; col < 3; ++col) for (int row = 0; row < 3; ++row) w2o[3 * col + row] = (float)inv[row][col];
+    flip = det < 0.0 ? 1u : 0u;
+    return det;
+}
+bool instance_inverse(const float m[16], float w2o[9], uint32_t& flip) {
+    for (int k = 0; k < 16; ++k) if (!std::isfinite(m[k])) return false;
+    float w[9]; uint32_t fl;
+    if (!(cofactor_inverse(m, w, fl) != 0.0)) return false;
+    memcpy(w2o, w, sizeof(w)); flip = fl;
+    return true;
+}
+void world_triangle(const float m[16], const float* P, const uint32_t idx[3], TriRec& t) {
+    float w[3][3];
+    for (int k = 0; k < 3; ++k) {
+        float x = P[4 * idx[k]], y = P[4 * idx[k] + 1], z = P[4 * idx[k] + 2];
+        for (int r = 0; r < 3; ++r) w[k][r] = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r];
+    }
+    for (int r = 0; r < 3; ++r) { t.v0[r] = w[0][r]; t.e1[r] = w[1][r] - w[0][r]; t.e2[r] = w[2][r] - w[0][r]; }
+}
 void SceneBuilder::flatten() {
     tris.clear(); tri_instance.clear();
     for (size_t ii = 0; ii < instances.size(); ++ii) {
         InstanceRec& in = instances[ii];
-        const float* m = in.m;
-        double a = m[0], b = m[4], c = m[8], d = m[1], e = m[5], f = m[9], g = m[2], h = m[6], i = m[10];
-        double k00 = e * i - f * h, k01 = f * g - d * i, k02 = d * h - e * g;
-        double det = a * k00 + b * k01 + c * k02;
-        double inv[3][3] = {{k00 / det, (c * h - b * i) / det, (b * f - c * e) / det},
-                            {k01 / det, (a * i - c * g) / det, (c * d - a * f) / det},
-                            {k02 / det, (b * g - a * h) / det, (a * e - b * d) / det}};
-        for (int col = 0; col < 3; ++col) for (int row = 0; row < 3; ++row) in.w2o[3 * col + row] = (float)inv[row][col];
-        in.flip = det < 0.0 ? 1u : 0u;
+        cofactor_inverse(in.m, in.w2o, in.flip);
         in.first_tri = (uint32_t)tris.size();
         const std::vector<float>& P = mesh_positions[in.mesh_id];
         const uint32_t* idx = &indices[mesh_infos[in.mesh_id].index_offset];
         uint32_t nidx = mesh_index_counts[in.mesh_id];
-        auto world = [&](uint32_t vi, float out[3]) {
-            float x = P[4 * vi], y = P[4 * vi + 1], z = P[4 * vi + 2];
-            for (int r = 0; r < 3; ++r) out[r] = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r];
-        };
         for (uint32_t k = 0; k + 2 < nidx; k += 3) {
-            float w0[3], w1[3], w2[3];
-            world(idx[k], w0); world(idx[k + 1], w1); world(idx[k + 2], w2);
             TriRec t;
-            for (int r = 0; r < 3; ++r) { t.v0[r] = w0[r]; t.e1[r] = w1[r] - w0[r]; t.e2[r] = w2[r] - w0[r]; }
+            world_triangle(in.m, P.data(), idx + k, t);
             tris.push_back(t);
             tri_instance.push_back((uint32_t)ii);
         }
         in.tri_count = (uint32_t)tris.size() - in.first_tri;
     }
+}
+
+std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats, size_t num_instances) {
+    if (n > 0 && (!ids || !mats)) return "null ids or matrices";
+    for (uint32_t k = 0; k < n; ++k) {
+        if (ids[k] >= num_instances) return "instance id " + std::to_string(ids[k]) + " out of range (" + std::to_string(num_instances) + " instances)";
+        float w2o[9]; uint32_t flip;
+        if (!instance_inverse(mats + 16 * (size_t)k, w2o, flip))
+            return "matrix " + std::to_string(k) + " (instance " + std::to_string(ids[k]) + ") has a non-finite entry or a singular 3x3";
+    }
+    return "";
+}
+
+int SceneBuilder::set_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats) {
+    if (!built) { error = "set_instance_transforms: scene is not built"; return FRT_ERR_STATE; }
+    const std::string bad = check_instance_transforms(n, ids, mats, instances.size());
+    if (!bad.empty()) { error = "set_instance_transforms: " + bad; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) {      // in order: an id given twice ends with its last matrix
+        InstanceRec& in = instances[ids[k]];
+        memcpy(in.m, mats + 16 * (size_t)k, sizeof(in.m));
+        instance_inverse(in.m, in.w2o, in.flip);
+        instances_dev[ids[k]].flip = in.flip;
+        memcpy(instances_dev[ids[k]].w2o, in.w2o, sizeof(in.w2o));
+        const float* P = mesh_positions[in.mesh_id].data();
+        const uint32_t* idx = &indices[mesh_infos[in.mesh_id].index_offset];
+        for (uint32_t j = 0; j < in.tri_count; ++j) {
+            const uint32_t id = in.first_tri + j;
+            TriRec& t = tris[id];
+            world_triangle(in.m, P, idx + 3 * j, t);
+            TriSlot& o = tri_slots[tri_slot_of[id]];      // same slot, id and instance bits
+            for (int r = 0; r < 3; ++r) { o.q[r] = t.v0[r]; o.q[4 + r] = t.e1[r]; o.q[8 + r] = t.e2[r]; }
+        }
+        if (in.light >= 0) {
+            Mat4 t; memcpy(t.m, in.m, sizeof(t.m));
+            frt_light& l = lights[(size_t)in.light];
+            float em[4]; memcpy(em, l.emission, sizeof(em));
+            l = in.light_kind == 0 ? quad_light_record(t, em) : sphere_light_record(t, em);
+        }
+    }
+    refit();
+    return FRT_OK;
 }
 
 void SceneBuilder::build() {

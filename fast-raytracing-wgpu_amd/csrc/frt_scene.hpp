@@ -54,6 +54,8 @@ struct InstanceRec {     // TLAS instance (builder.rs:181-189) + derived data
     uint32_t mesh_id, mat_id, first_tri, tri_count, flip;
     float m[16];
     float w2o[9];        // world_to_object 3x3: w2o[3*c + r]
+    int32_t light = -1;  // the light register_quad_light / register_sphere_light added with this instance (moves with it), or -1
+    uint32_t light_kind = 0;   // 0 quad, 1 sphere
 };
 
 struct TriRec { float v0[3], e1[3], e2[3]; };
@@ -90,6 +92,10 @@ public:
     uint32_t add_color_texture(const uint8_t* rgba8);  // :93
     uint32_t add_data_texture(const uint8_t* rgba8);   // :105
     void build();                                      // :431 — flatten + SAH BVH (host only)
+    // New transforms for instances of a built scene: the same tree and leaf order, the moved instances' triangles and
+    // registered lights recomputed as build() computes them, every box refit. The specification the device refit matches bit for bit.
+    // Returns an FRT_ERR_* code with `error` set, or FRT_OK.
+    int set_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats);
 
     // SceneResources-equivalent host data (src/scene/resources.rs:10-22)
     std::vector<frt_material> materials;
@@ -115,6 +121,7 @@ public:
     std::vector<uint32_t> qnode_a, qnode_b;     // quantized pair nodes, 4 words per node each (frt_trace.hpp: QBvh)
     float qmin[3] = {0, 0, 0}, qstep[3] = {1, 1, 1};
     std::vector<TriSlot> tri_slots;
+    std::vector<uint32_t> tri_slot_of;      // flattened triangle id -> its slot in tri_slots (the inverse of bvh2_tri_index)
     // The same tree as 8-wide nodes with grid boxes (frt_bvh8.hpp; frt_trace.hpp: trace8), built on first use (ensure_wide8): the product's kernels walk
     // the quad tree; the 8-wide walk is an experiment (lib/libfrt_exp.so) and its tree is otherwise read by tests and tools/bvh_quality.cpp only.
     mutable Wide8 wide8;                    // wide8.ok = false: not walkable that way (more than 65,536 nodes)
@@ -128,9 +135,21 @@ public:
 
 private:
     void flatten();
+    void refit();
     void build_bvh2();
     void build_gpu_layout();
 };
+
+// Derived data of one instance transform, as flatten() computes it: world_to_object by cofactors in double, rounded once to f32, and the
+// flip flag. False (outputs untouched) when the matrix has a non-finite entry or a singular 3x3.
+bool instance_inverse(const float m[16], float w2o[9], uint32_t& flip);
+// One world-space triangle of an instance (the contract of DESIGN.md §3): p = ((c0*x + c1*y) + c2*z) + c3 in f32, e1 = v1 - v0, e2 = v2 - v0.
+void world_triangle(const float m[16], const float* pos4, const uint32_t idx[3], TriRec& out);
+// The light record register_quad_light / register_sphere_light make for transform t (emission = (colour, intensity)).
+frt_light quad_light_record(const Mat4& t, const float emission[4]);
+frt_light sphere_light_record(const Mat4& t, const float emission[4]);
+// Argument checks shared by the scene and the renderer form of set_instance_transforms: "" when (n, ids, mats) may be applied.
+std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats, size_t num_instances);
 
 namespace scenes {
 void create_cornell_box(SceneBuilder& b);    // scenes.rs:9-130

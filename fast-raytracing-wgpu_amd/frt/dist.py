@@ -27,6 +27,9 @@ the "post" exchange grows to K + 1 rows. Reads beyond the halo are counted (stat
 the phases and the exchanges in the order described above (what bench.py --gpus N and the multi-rank tests run). Given a
 `frt.rccl.Comm` it places the transfers as grouped RCCL launches directly in the renderer's streams instead (`render_strip_frame_direct`:
 no torch stream, no event per operation — the form bench.py's ranks use on a GPU node).
+
+Moving instances: every rank calls its strip Renderer's set_instance_transforms with the same ids and matrices between
+two frames. Each replica is refit on its own device; no rows travel for it and no exchange is added.
 """
 import numpy as np
 

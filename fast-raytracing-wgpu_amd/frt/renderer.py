@@ -2,6 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM)
+from .scene import transform_args
 
 
 class Renderer:
@@ -119,6 +120,25 @@ class Renderer:
     def set_timing(self, on):
         check(lib().frt_renderer_set_timing(self._h, 1 if on else 0))
 
+    def set_instance_transforms(self, ids, transforms_colmajor):
+        """Move instances in this renderer's scene replica between frames (include/frt.h: frt_renderer_set_instance_transforms): asynchronous, on
+        the renderer's streams. The host scene is not changed (SceneBuilder.set_instance_transforms is its own call)."""
+        n, i, m = transform_args(ids, transforms_colmajor)
+        check(lib().frt_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_instance_transform(self, instance_id, transform_colmajor):
+        self.set_instance_transforms([instance_id], [transform_colmajor])
+
+    def read_scene(self, what):
+        """The device replica in SceneBuilder.get's layout: "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev" (syncs first)."""
+        n = self._scene.counts()
+        which, shape, dt = {"lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self._scene.tree_stats()["quad_nodes"], 32), np.float32),
+                            "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
+                            "instances_dev": (16, (n["instances"], 16), np.uint32)}[what]
+        out = np.zeros(shape, dt)
+        check(lib().frt_renderer_read_scene(self._h, which, out.ctypes.data))
+        return out
+
     def stats(self):
         s = Stats()
         check(lib().frt_renderer_stats(self._h, C.byref(s)))
@@ -194,6 +214,11 @@ class MultiRenderer:
         out = (C.c_uint32 * (self.ndev + 1))()
         check(lib().frt_multi_renderer_boundaries(self._h, out))
         return list(out)
+
+    def set_instance_transforms(self, ids, transforms_colmajor):
+        """Renderer.set_instance_transforms on every strip's scene replica."""
+        n, i, m = transform_args(ids, transforms_colmajor)
+        check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
 
     def read_buffer(self, buf, index=0):
         out = np.zeros((self.height, self.width, BUF_BPP[buf]), np.uint8)

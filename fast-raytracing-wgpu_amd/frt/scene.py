@@ -12,6 +12,18 @@ def material_new(base_color):
     return m
 
 
+def transform_args(ids, transforms_colmajor):
+    """(n, ids, matrices) for the *_set_instance_transforms calls: `ids` an int or a sequence, `transforms_colmajor` one column-major
+    4x4 (as frt.scenes writes them: m[4*c + r]) per id, shaped [n, 4, 4], [n, 16], [4, 4] or [16]."""
+    ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, np.int64)))
+    if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise FrtError("instance ids must be a flat list of unsigned 32-bit indices")
+    m = np.ascontiguousarray(transforms_colmajor, np.float32).reshape(-1, 16)
+    if m.shape[0] != ids.size:
+        raise FrtError(f"{ids.size} instance ids but {m.shape[0]} matrices")
+    return ids.size, ids.astype(np.uint32), m
+
+
 class SceneBuilder:
     def __init__(self, handle=None):
         self._destroy = lib().frt_scene_destroy
@@ -84,6 +96,15 @@ class SceneBuilder:
         check(lib().frt_scene_build(self._h))
         return self
 
+    # Move instances of the built scene: same tree, refit boxes (include/frt.h: frt_scene_set_instance_transforms). Host copy only.
+    def set_instance_transforms(self, ids, transforms_colmajor):
+        n, i, m = transform_args(ids, transforms_colmajor)
+        check(lib().frt_scene_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+        return self
+
+    def set_instance_transform(self, instance_id, transform_colmajor):
+        return self.set_instance_transforms([instance_id], [transform_colmajor])
+
     # ---- introspection
     def counts(self):
         c = (C.c_uint32 * 8)()
@@ -103,7 +124,7 @@ class SceneBuilder:
         n = self.counts()
         if what in ("quad_nodes", "wide8_nodes", "tri_slots8", "tri_slots"):
             t = self.tree_stats()
-            which, shape, dt = {"quad_nodes": (10, (t["quad_nodes"], 32), np.float32), "wide8_nodes": (11, (t["wide8_nodes"], 20), np.uint32),
+            which, shape, dt = {"quad_nodes": (10, (t["quad_nodes"], 32), np.float32), "wide8_nodes": (11, (t["wide8_nodes"], 32), np.uint32),
                                 "tri_slots8": (12, (t["wide8_tri_slots"], 12), np.float32), "tri_slots": (13, (n["tris"], 12), np.float32)}[what]
             out = np.zeros(shape, dt)
             check(lib().frt_scene_get(self._h, which, out.ctypes.data))
@@ -112,7 +133,8 @@ class SceneBuilder:
                 "materials": (2, (n["materials"], 16), np.uint32), "lights": (3, (n["lights"], 16), np.uint32),
                 "attributes": (4, (n["attributes"], 8), np.float32), "indices": (5, (n["indices"],), np.uint32),
                 "mesh_infos": (6, (n["meshes"], 4), np.uint32), "instances": (7, (n["instances"], 30), np.uint32),
-                "bvh2_nodes": (8, (n["bvh2_nodes"], 8), np.uint32), "bvh2_tri_index": (9, (n["tris"],), np.uint32)}[what]
+                "bvh2_nodes": (8, (n["bvh2_nodes"], 8), np.uint32), "bvh2_tri_index": (9, (n["tris"],), np.uint32),
+                "pair_nodes": (15, (self.bvh_stats()["pair_nodes"], 16), np.float32), "instances_dev": (16, (n["instances"], 16), np.uint32)}[what]
         out = np.zeros(spec[1], spec[2])
         check(lib().frt_scene_get(self._h, spec[0], out.ctypes.data))
         return out

@@ -136,10 +136,18 @@ frt_scene* frt_scene_create_gltf_scene(const char* path, const float model_trans
 int frt_scene_counts(const frt_scene* s, uint32_t counts[8]);
 /* which: 0 tris (9 f32: v0,e1,e2), 1 tri_instance (u32), 2 materials, 3 lights, 4 attributes, 5 indices, 6 mesh infos (16 B),
  * 7 instances (120 B: mesh,mat,first_tri,tri_count,flip u32; m[16]; w2o[9] f32), 8 bvh2 nodes (32 B), 9 bvh2 tri_index (u32);
- * the device forms of the tree (frt_scene_tree_stats gives the counts): 10 quad nodes (128 B), 11 8-wide compressed nodes (80 B, csrc/frt_bvh8.hpp),
+ * the device forms of the tree (frt_scene_tree_stats gives the counts): 10 quad nodes (128 B), 11 8-wide compressed nodes (128 B, csrc/frt_bvh8.hpp),
  * 12 triangle slots in the 8-wide tree's order (48 B: v0, id; e1, instance; e2, 0), 13 triangle slots in BVH2 leaf order (48 B),
- * 14 the float boxes behind the 8-wide nodes' grid boxes (192 B per node: 8 x lo.xyz, hi.xyz; host data for tools/bvh_quality.cpp) */
+ * 14 the float boxes behind the 8-wide nodes' grid boxes (192 B per node: 8 x lo.xyz, hi.xyz; host data for tools/bvh_quality.cpp),
+ * 15 pair nodes (64 B; frt_scene_bvh_stats gives the count), 16 device instance records (64 B: mesh, mat, first_tri, flip u32; w2o[9] f32; 3 pad) */
 int frt_scene_get(const frt_scene* s, int which, void* out);
+/* Move instances of a BUILT scene: instance ids[k] gets the column-major matrix m_colmajor16[16k .. 16k+15]. The tree
+ * keeps its topology and leaf order; the moved instances' triangles, their device instance records and the lights registered with them
+ * (frt_scene_register_quad_light / _sphere_light; frt_scene_add_light's lights stay) are recomputed as frt_scene_build computes them, and
+ * every box is refit. An id given twice ends with its last matrix. Host copy only: renderers created from the scene are not touched (their
+ * replica moves with frt_renderer_set_instance_transforms). FRT_ERR_STATE: scene not built; FRT_ERR_INVALID_ARG: an id out of range, a
+ * non-finite entry, a singular 3x3 (nothing is changed then). The 8-wide tree (selectors 11, 12, 14) is made again from the refit tree. */
+int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
 /* stats[8]: quad nodes, deepest traversal stack of the quad tree, 8-wide nodes (0: the scene has no 8-wide tree: more than 65,536 nodes), deepest stack of
  * the 8-wide tree, its levels, sum of its nodes' child counts, its triangle slots, how the quad tree was folded (2 surface-area programme, 1 programme where
  * the traversal-stack bound allows and the greedy fold elsewhere, 0 greedy fold) */
@@ -288,6 +296,16 @@ int frt_renderer_phase_rows(const frt_renderer* r, uint32_t out[8]);
 int frt_renderer_stats(frt_renderer* r, frt_stats* out);      /* syncs first */
 /* Switch FRT_FLAG_TIMING on or off after creation (the per-stage HIP events cost ~25 us per frame: too much for a thin strip) */
 int frt_renderer_set_timing(frt_renderer* r, int on);
+/* Move instances in this renderer's scene replica between frames: the same arguments, checks and results as
+ * frt_scene_set_instance_transforms, computed on the device by a transform kernel and a level-by-level refit. Asynchronous: enqueued behind every
+ * kernel of the renderer that reads the scene and before the next frame's first one; a next frame's G-buffer + T-trace that already ran ahead
+ * under the old geometry is dropped and redone. Accumulation and reservoirs are kept (moved objects ghost in temporal reuse until
+ * frt_renderer_reset / _clear; motion vectors stay camera-only). FRT_ERR_STATE between the phases of an open frame; FRT_ERR_INVALID_ARG for a
+ * renderer whose kernels walk a tree that is not refit (experiments build: FRT_FLAG_WALK_WIDE / _HBM with an 8-wide tree, the resident kernels). */
+int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* Read the device replica back (syncs first), in the layout of frt_scene_get: 3 lights, 10 quad nodes, 13 triangle slots, 15 pair nodes,
+ * 16 device instance records. */
+int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 
 /* ---- N GPUs behind one call (`ngpus`; section 8e) -----------------------------------------------------------------
  * In the reference one call renders one frame: Renderer::render, src/renderer.rs:349-518, called from State::render, src/state.rs:192-204.
@@ -329,6 +347,8 @@ int frt_multi_renderer_read_accum(frt_multi_renderer* m, float* rgba32f);
 int frt_multi_renderer_read_buffer(frt_multi_renderer* m, int buf, int index, void* out);         /* any target, every strip's own rows */
 int frt_multi_renderer_stats(frt_multi_renderer* m, frt_stats* out);                              /* summed over the strips */
 int frt_multi_renderer_boundaries(const frt_multi_renderer* m, uint32_t* rows_out);               /* ndev + 1 row indices; returns ndev */
+/* frt_renderer_set_instance_transforms on every strip's replica, between frames */
+int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
 
 #ifdef __cplusplus
 }
