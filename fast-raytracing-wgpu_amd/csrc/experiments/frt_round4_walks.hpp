@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel_wg(SceneView s
         ss.i = 0u; ss.n = 0u; ss.pending = false;
         const bool sp = active && spatial_begin(c, ss, pix);
         SpatialCentre centre;
-        if (sp) centre = spatial_centre(fv, pix);
+        if (sp) centre = spatial_centre(sc, fv, pix);
         for (int it = 0; it < 5; ++it) {
             AnyReq rq;
             rq.want = false; rq.o = splat3(0.0f); rq.d = splat3(1.0f); rq.tmin = 0.0001f; rq.tmax = 0.0f;

@@ -454,7 +454,7 @@ template <class Ctx>
 FRT_HD bool spatial_neighbors(Ctx& c, uint32_t pix, ReservoirView& r) {
     SpatialState ss;
     if (!spatial_begin(c, ss, pix)) return false;
-    const SpatialCentre centre = spatial_centre(c.fv, pix);
+    const SpatialCentre centre = spatial_centre(c.sc, c.fv, pix);
     while (ss.i < ss.n) {
         AnyReq req;
         req.want = false; req.o = splat3(0.0f); req.d = splat3(0.0f); req.tmin = 0.0f; req.tmax = 0.0f;

@@ -309,10 +309,15 @@ FRT_HD void temporal_merge_pixel(const SceneView& sc, const FrameView& fv, uint3
 FRT_HD void temporal_finalize(PathCtx& c, const PathState& st) { temporal_merge(c.sc, c.fv, st.pix, temporal_candidate(st.accum, st.v1_pos)); }
 
 // ================================================================================================ stage 2: restir_spatial.wgsl:857-1016
-FRT_HD bool is_valid_neighbor_spatial(const SceneView& sc, f3 cp, f3 cn, uint32_t cm, f3 pp, f3 pn, uint32_t pm, f3 cam) {   // :783-814
-    if (cm != pm) return false;
+// is_specular is a property of the CENTRE pixel's material alone (cm): the kernels read it once per pixel (spatial_centre) instead of once per neighbour,
+// where it was a dependent round trip of its own behind the neighbour's G-buffer words.
+FRT_HD bool centre_is_specular(const SceneView& sc, uint32_t cm) {
     const MaterialView& mat = sc.materials[cm];
-    bool is_specular = mat.roughness < 0.2f || mat.metallic > 0.8f || (mat.transmission > 0.01f);
+    const float roughness = mat.roughness, metallic = mat.metallic, transmission = mat.transmission;      // (read together: behind the || each is a trip of its own)
+    return roughness < 0.2f || metallic > 0.8f || (transmission > 0.01f);
+}
+FRT_HD bool is_valid_neighbor_spatial(bool is_specular, f3 cp, f3 cn, uint32_t cm, f3 pp, f3 pn, uint32_t pm, f3 cam) {   // :783-814
+    if (cm != pm) return false;
     if (is_specular) {
         if (dot(cn, pn) < 0.998f) return false;
         if (distance(cp, pp) > 0.01f) return false;
@@ -360,7 +365,8 @@ FRT_HD bool spatial_begin(PathCtx& c, SpatialState& ss, uint32_t pixel_idx) {
     ss.r = fv.res_temporal[pixel_idx];
     if (ss.r.M > 20u) { ss.r.w_sum *= 20.0f / (float)ss.r.M; ss.r.M = 20u; }
     const MaterialView& mat = sc.materials[(uint32_t)(pos_w4.w + 0.1f)];
-    ss.narrow = mat.roughness < 0.1f || mat.metallic > 0.9f || mat.transmission > 0.1f;   // :906 and :957
+    const float roughness = mat.roughness, metallic = mat.metallic, transmission = mat.transmission;      // (read together: behind the || each is a trip of its own)
+    ss.narrow = roughness < 0.1f || metallic > 0.9f || transmission > 0.1f;   // :906 and :957
     ss.n = ss.narrow ? 3u : 5u;
     ss.i = 0u;
     ss.pending = false;
@@ -369,8 +375,8 @@ FRT_HD bool spatial_begin(PathCtx& c, SpatialState& ss, uint32_t pixel_idx) {
 // One iteration of the neighbour loop up to its visibility ray (:912-982). Sets ss.pending when a candidate awaits the ray
 // result (req.want says whether a ray is actually needed).
 // The centre pixel's own G-buffer values: the same for every neighbour, decoded once per pixel by the kernels.
-struct SpatialCentre { f3 pos_w, normal, albedo, camera_pos; uint32_t mat_id; };
-FRT_HD SpatialCentre spatial_centre(const FrameView& fv, uint32_t pix) {
+struct SpatialCentre { f3 pos_w, normal, albedo, camera_pos; uint32_t mat_id; bool specular; };
+FRT_HD SpatialCentre spatial_centre(const SceneView& sc, const FrameView& fv, uint32_t pix) {
     SpatialCentre k;
     float4 pos_w4 = fv.gpos[pix];
     k.pos_w = mk3(pos_w4.x, pos_w4.y, pos_w4.z);
@@ -379,11 +385,12 @@ FRT_HD SpatialCentre spatial_centre(const FrameView& fv, uint32_t pix) {
     k.mat_id = (uint32_t)(pos_w4.w + 0.1f);
     k.albedo = xyz(unpack_rgba8(fv.galbedo[pix]));
     k.camera_pos = mk3(fv.cam.view_pos[0], fv.cam.view_pos[1], fv.cam.view_pos[2]);
+    k.specular = centre_is_specular(sc, k.mat_id);
     return k;
 }
 template <class Ctx>
 FRT_HD void spatial_neighbor_prepare(Ctx& c, SpatialState& ss, AnyReq& req, const SpatialCentre& k) {
-    const SceneView& sc = c.sc; const FrameView& fv = c.fv;
+    const FrameView& fv = c.fv;
     ss.pending = false;
     uint32_t px = ss.pix % fv.W, py = ss.pix / fv.W;
     float radius = ss.narrow ? 4.0f : 10.0f;
@@ -397,17 +404,25 @@ FRT_HD void spatial_neighbor_prepare(Ctx& c, SpatialState& ss, AnyReq& req, cons
     int nx = (int)px + (int)offset.x, ny = (int)py + (int)offset.y;   // vec2<i32>(offset) truncates toward zero
     if (nx < 0 || nx >= (int)fv.W || ny < 0 || ny >= (int)fv.H) return;
     uint32_t nidx = (uint32_t)ny * fv.W + (uint32_t)nx;
+    // Everything this iteration reads of the neighbour — a random pixel within the radius: L1 misses, the reservoir often an L2 miss — is fetched
+    // TOGETHER, before the first of the tests below: one round trip per neighbour instead of three (position; normal + albedo; reservoir). The
+    // addresses depend on nidx alone. A neighbour the tests reject costs up to 52 more bytes; the tests read the same values in the same order.
     float4 n_pos4 = fv.gpos[nidx];
+    float4 n_nrm = fv.gnormal[nidx];
+    uint32_t n_alb = fv.galbedo[nidx];
+    ReservoirView nr = fv.res_temporal[nidx];
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (left alone, the compiler sinks each load behind the test that guards its first use — the three dependent trips again; trace8 pins its node words alike)
+    asm volatile("" : "+v"(n_pos4.w), "+v"(n_nrm.x), "+v"(n_alb), "+v"(nr.y), "+v"(nr.p_hat));
+#endif
     if (n_pos4.w < 0.0f) return;
     const f3 pos_w = k.pos_w, normal = k.normal, albedo = k.albedo, camera_pos = k.camera_pos;
     const uint32_t mat_id = k.mat_id;
     f3 n_pos = mk3(n_pos4.x, n_pos4.y, n_pos4.z);
-    float4 n_nrm = fv.gnormal[nidx];
     f3 n_normal = decode_octahedral_normal(n_nrm.x, n_nrm.y);
     uint32_t n_mat_id = (uint32_t)(n_pos4.w + 0.1f);
-    f3 n_albedo = xyz(unpack_rgba8(fv.galbedo[nidx]));
-    if (!is_valid_neighbor_spatial(sc, pos_w, normal, mat_id, n_pos, n_normal, n_mat_id, camera_pos)) return;
-    ReservoirView nr = fv.res_temporal[nidx];
+    f3 n_albedo = xyz(unpack_rgba8(n_alb));
+    if (!is_valid_neighbor_spatial(k.specular, pos_w, normal, mat_id, n_pos, n_normal, n_mat_id, camera_pos)) return;
     if (nr.p_hat <= 0.0f) return;
     f3 n_s_path = mk3(nr.sx, nr.sy, nr.sz);
     float jacobian = calculate_jacobian(pos_w, normal, albedo, n_s_path, n_pos, n_normal, n_albedo);
@@ -431,7 +446,7 @@ FRT_HD void spatial_neighbor_prepare(Ctx& c, SpatialState& ss, AnyReq& req, cons
     req.want = true; req.o = pos_w; req.d = ray_dir; req.tmin = t_min; req.tmax = t_max;
 }
 FRT_HD void spatial_neighbor_prepare(PathCtx& c, SpatialState& ss, AnyReq& req) {
-    spatial_neighbor_prepare(c, ss, req, spatial_centre(c.fv, ss.pix));
+    spatial_neighbor_prepare(c, ss, req, spatial_centre(c.sc, c.fv, ss.pix));
 }
 FRT_HD void spatial_neighbor_finish(SpatialState& ss, bool visible) {
     if (ss.pending && visible)
