@@ -279,7 +279,9 @@ FRT_HD void temporal_merge(const SceneView& sc, const FrameView& fv, uint32_t pi
         f3 cam = mk3(fv.cam.view_pos[0], fv.cam.view_pos[1], fv.cam.view_pos[2]);
         if (is_valid_neighbor_temporal(mk3(pos_w.x, pos_w.y, pos_w.z), curr_normal, curr_mat_id,
                                        mk3(prev_pos.x, prev_pos.y, prev_pos.z), prev_normal, prev_mat_id, cam) && !is_specular) {
-            ReservoirView prev_r = inb ? fv.res_spatial[prev_idx] : zero_reservoir();
+            // (:855, :877) the reservoir array is indexed LINEARLY: with qx == W (prev_uv.x == 1) that is the next row's first element, not a texel out of range
+            const uint32_t lin_idx = qy * fv.W + qx;
+            ReservoirView prev_r = lin_idx < fv.W * fv.H ? fv.res_spatial[lin_idx] : zero_reservoir();
             f3 curr_albedo = xyz(unpack_rgba8(fv.galbedo[pixel_idx]));
             f3 prev_albedo = inb ? xyz(unpack_rgba8(fv.galbedo_prev[prev_idx])) : splat3(0.0f);
             float l_curr = luminance(curr_albedo) + 0.001f;

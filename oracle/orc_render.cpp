@@ -622,7 +622,8 @@ static void temporal_pixel(Ctx& c, Renderer& R, uint32_t px, uint32_t py) {
     if (prev_uv.x >= 0.0f && prev_uv.x <= 1.0f && prev_uv.y >= 0.0f && prev_uv.y <= 1.0f) {
         vec2 pf = prev_uv * size;
         uint32_t pxx = (uint32_t)pf.x, pyy = (uint32_t)pf.y;   // vec2u(): truncation; non-negative here
-        // prev_uv == 1.0 would index one past the edge; WGSL robust access returns zeros / clamps. Treated as zeros.
+        // prev_uv == 1.0 indexes one past the edge: the TEXEL reads are out of range and return zeros. The reservoir array is a storage buffer
+        // indexed linearly (:855): with pxx == W the index is the next row's first element, read as such; beyond the array it is treated as zeros.
         bool inb = pxx < R.W && pyy < R.H;
         uint32_t prev_pixel_idx = pyy * R.W + pxx;
         vec4 prev_pos_data = inb ? R.gpos[prv][prev_pixel_idx] : V4(0, 0, 0, 0);
@@ -637,7 +638,7 @@ static void temporal_pixel(Ctx& c, Renderer& R, uint32_t px, uint32_t py) {
         vec3 campos = V3(cam.view_pos[0], cam.view_pos[1], cam.view_pos[2]);
         if (is_valid_neighbor_temporal(xyz(pos_w), curr_normal, curr_mat_id, xyz(prev_pos_data), prev_normal, prev_mat_id, campos) &&
             !is_specular) {
-            Reservoir prev_r = inb ? prev_res[prev_pixel_idx] : Reservoir{};
+            Reservoir prev_r = prev_pixel_idx < R.W * R.H ? prev_res[prev_pixel_idx] : Reservoir{};
             vec3 curr_albedo = xyz(unpack_rgba8(R.galbedo[cur][pixel_idx]));
             vec3 prev_albedo = inb ? xyz(unpack_rgba8(R.galbedo[prv][prev_pixel_idx])) : V3(0.0f);
             float l_curr = luminance(curr_albedo) + 0.001f;

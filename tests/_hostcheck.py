@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 
-BPP = {0: 16, 1: 16, 2: 4, 3: 8, 4: 32, 5: 8, 6: 4, 7: 16}
+BPP = {0: 16, 1: 16, 2: 4, 3: 8, 4: 32, 5: 8, 6: 4, 7: 16, 8: 16}
 
 
 class HostCheck:
@@ -14,6 +14,8 @@ class HostCheck:
         L.hc_render.argtypes = [P, P, C.c_int]
         L.hc_read.restype = C.c_int; L.hc_read.argtypes = [P, C.c_int, C.c_int, P]
         L.hc_rays.argtypes = [P, P]
+        L.hc_write.restype = C.c_int; L.hc_write.argtypes = [P, C.c_int, C.c_int, P]
+        L.hc_reservoir_pass.restype = C.c_int; L.hc_reservoir_pass.argtypes = [P, P, U32, C.c_int, P]
         L.hc_set_jitter.argtypes = [P, C.c_float, C.c_float]
         L.hc_trace.argtypes = [P, C.c_int, U32, P, P, C.c_float, P, P, P, P, P, C.c_int]
         L.hc_quad_stats.argtypes = [P, P]
@@ -61,6 +63,24 @@ class HcRenderer:
     def read(self, buf, index=0):
         out = np.zeros((self.hgt, self.w, BPP[buf]), np.uint8)
         assert self.L.hc_read(self.h, buf, index, out.ctypes.data) == 0
+        return out
+
+    def write(self, buf, index, data):
+        """Overwrite a whole buffer (physical slot `index`): the inputs of temporal_merge / spatial_neighbors below."""
+        data = np.ascontiguousarray(data).view(np.uint8)
+        assert data.size == self.hgt * self.w * BPP[buf]
+        assert self.L.hc_write(self.h, buf, index, data.ctypes.data) == 0
+
+    def temporal_merge(self, cam, frame_count):
+        """temporal_merge_pixel over every pixel as frame `frame_count`: candidate + the other G-buffer slot + reservoirs[1] -> reservoirs[0]."""
+        cam = np.ascontiguousarray(np.frombuffer(bytes(cam), np.uint8))
+        assert self.L.hc_reservoir_pass(self.h, cam.ctypes.data, frame_count, 1, None) == 0
+
+    def spatial_neighbors(self, cam, frame_count):
+        """The neighbour loop of spatial_neighbors over every pixel: the reservoirs it leaves, (H, W, 32) bytes."""
+        cam = np.ascontiguousarray(np.frombuffer(bytes(cam), np.uint8))
+        out = np.zeros((self.hgt, self.w, 32), np.uint8)
+        assert self.L.hc_reservoir_pass(self.h, cam.ctypes.data, frame_count, 2, out.ctypes.data) == 0
         return out
 
     def rays(self):

@@ -193,7 +193,55 @@ int hc_read(void* p, int buf, int index, void* out) {
     case FRT_BUF_RAW: memcpy(out, h->raw.data(), n * 8); break;
     case FRT_BUF_DISPLAY: memcpy(out, h->display.data(), n * 4); break;
     case FRT_BUF_ACCUM: memcpy(out, h->accum[i].data(), n * 16); break;
+    case FRT_BUF_CANDIDATE: memcpy(out, h->cand.data(), n * 16); break;
     default: return -1;
+    }
+    return 0;
+}
+// probe: caller-supplied contents for the buffers the two reservoir passes read (tests/test_wgsl_f64_restir.py). index = physical slot.
+int hc_write(void* p, int buf, int index, const void* in) {
+    HostCheck* h = (HostCheck*)p;
+    size_t n = (size_t)h->W * h->H;
+    int i = index & 1;
+    switch (buf) {
+    case FRT_BUF_GPOS: memcpy(h->gpos[i].data(), in, n * 16); break;
+    case FRT_BUF_GNORMAL: memcpy(h->gnormal[i].data(), in, n * 16); break;
+    case FRT_BUF_GALBEDO: memcpy(h->galbedo[i].data(), in, n * 4); break;
+    case FRT_BUF_GMOTION: memcpy(h->gmotion.data(), in, n * 8); break;
+    case FRT_BUF_RESERVOIR: memcpy(h->res[i].data(), in, n * 32); break;
+    case FRT_BUF_CANDIDATE: memcpy(h->cand.data(), in, n * 16); break;
+    default: return -1;
+    }
+    return 0;
+}
+// probe: one reservoir pass of frame `frame_count` over the buffers as they stand, nothing else of the frame.
+//   which = 1: temporal_merge_pixel for every pixel (candidate record + previous frame's slots -> res[0]);
+//   which = 2: the neighbour loop of spatial_neighbors for every pixel; the reservoir it leaves (before trace_path) goes to `out` (32 B per pixel,
+//              the zero reservoir for a background pixel), res[1] and raw are not meaningful afterwards.
+int hc_reservoir_pass(void* p, const frt_camera_uniform* cam, uint32_t frame_count, int which, void* out) {
+    HostCheck* h = (HostCheck*)p;
+    const uint32_t cur = frame_count & 1u, prv = cur ^ 1u;
+    FrameView fv{};
+    fv.gpos = h->gpos[cur].data(); fv.gnormal = h->gnormal[cur].data(); fv.galbedo = h->galbedo[cur].data();
+    fv.gpos_prev = h->gpos[prv].data(); fv.gnormal_prev = h->gnormal[prv].data(); fv.galbedo_prev = h->galbedo[prv].data();
+    fv.gmotion = h->gmotion.data(); fv.res_temporal = h->res[0].data(); fv.res_spatial = h->res[1].data();
+    fv.cand = h->cand.data(); fv.raw = h->raw.data(); fv.display = h->display.data(); fv.history = h->accum[prv].data(); fv.accum = h->accum[cur].data();
+    fv.ray_counters = nullptr; fv.W = h->W; fv.H = h->H; fv.frame_count = frame_count; fv.max_depth = h->max_depth;
+    fv.y0 = 0; fv.y1 = h->H; fv.own_y0 = 0; fv.own_y1 = h->H; fv.prev_y0 = 0; fv.prev_y1 = h->H; fv.overflow = nullptr;
+    memcpy(&fv.cam, cam, sizeof(CameraView));
+    const uint32_t n = h->W * h->H;
+    if (which == 1) {
+        for (uint32_t pix = 0; pix < n; ++pix) temporal_merge_pixel(h->sv, fv, pix);
+        return 0;
+    }
+    if (which != 2 || !out) return -1;
+    uint32_t stack[kStackDepth];
+    ReservoirView* o = (ReservoirView*)out;
+    for (uint32_t pix = 0; pix < n; ++pix) {
+        PathCtx c(h->sv, fv, stack, 1u);
+        ReservoirView r = zero_reservoir();
+        if (!spatial_neighbors(c, pix, r)) r = zero_reservoir();
+        o[pix] = r;
     }
     return 0;
 }

@@ -5,6 +5,7 @@ import pytest
 import _wgsl_f64 as R
 import test_wgsl_f64_gbuffer as G
 import test_wgsl_f64_post as P
+import test_wgsl_f64_restir as T
 
 
 @pytest.mark.parametrize("mis,scene_name,cam_name", [("m_inv_transposed", "transforms", "static"), ("tbn_transposed", "textured", "static"),
@@ -34,3 +35,30 @@ def test_post_misreading_is_caught(frt, orc, mis, W, H, fc):
     P.check(inp, accum, display, W, H, fc, (0.0, 0.0))                              # the faithful reading agrees ...
     with pytest.raises(AssertionError):
         P.check(inp, accum, display, W, H, fc, (0.0, 0.0), mis={mis})               # ... and the misreading does not
+
+
+TEMPORAL_MIS = ["other_reservoirs", "temporal_m20", "ratio_inverted", "ris_le", "normal_0995", "prev_id_rounded"]
+SPATIAL_MIS = ["spatial_m16", "ris_le", "no_rescale", "jacobian_no_albedo", "jacobian_clamp_05_2", "offset_rounded", "third_draw_always", "tmax_dist"]
+RESTIR_CASE = ("probe", 64, 48, 0)
+
+
+@pytest.mark.parametrize("mis", TEMPORAL_MIS)
+def test_temporal_misreading_is_caught(frt, orc, mis):
+    """Each misreading of restir.wgsl:842-917 (tests/_wgsl_f64_restir.py, `mis`) on the float64 side only fails the comparison with the oracle."""
+    which, W, H, fc = RESTIR_CASE
+    _, _, _, view_pos, mats = T._setup(frt, orc, which, W, H, fc)
+    inp, out = T.oracle_temporal(frt, orc, which, W, H, fc)
+    T.check_temporal(inp, out, W, H, fc, view_pos, mats)                            # the faithful reading agrees ...
+    with pytest.raises(AssertionError, match="pixels differ from float64"):
+        T.check_temporal(inp, out, W, H, fc, view_pos, mats, mis={mis})             # ... and the misreading does not
+
+
+@pytest.mark.parametrize("mis", SPATIAL_MIS)
+def test_spatial_misreading_is_caught(frt, orc, mis):
+    """The same for restir_spatial.wgsl:857-993."""
+    which, W, H, fc = RESTIR_CASE
+    fs, _, _, view_pos, mats = T._setup(frt, orc, which, W, H, fc)
+    inp, out, raw = T.oracle_spatial(frt, orc, which, W, H, fc)
+    T.check_spatial(inp, out, raw, W, H, fc, view_pos, mats, T.tris_of(fs, which))
+    with pytest.raises(AssertionError, match="pixels differ from float64"):
+        T.check_spatial(inp, out, raw, W, H, fc, view_pos, mats, T.tris_of(fs, which), mis={mis})
