@@ -4,6 +4,7 @@
 #include "frt_scene.hpp"
 #include "frt_kernels.hpp"
 #include "frt_refit.hpp"
+#include "frt_rebuild.hpp"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cstdio>
@@ -120,6 +121,18 @@ struct RefitState {
     uint64_t device_bytes = 0;
 };
 
+// What frt_renderer_rebuild_tree adds ("Rebuild"), allocated at the first call: the scratch of the kernels, the triangle slots and the
+// id -> slot table that are NOT in use (they trade places with the replica's at every successful rebuild) and up to two quad-node buffers of
+// rebuild_max_nodes() nodes (the host-built tree's buffer may be smaller than a device tree needs, so it is never built into; the second one
+// is allocated by the second rebuild). All of it is freed with the scene replica.
+struct RebuildState {
+    RebuildScratch scratch;
+    float4* tris = nullptr; uint32_t* slot_of = nullptr;
+    float4* nodes[2] = {nullptr, nullptr};
+    bool done = false;                     // the replica's quad tree is a device rebuild: the pair tree and its quantised form are stale
+    uint64_t device_bytes = 0;
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -182,6 +195,7 @@ struct frt_renderer {
     uint32_t gsets = 2;                    // G-buffer sets in use
     uint64_t serial = 0;                   // frames finished since creation (never reset: parity of the per-frame events)
     RefitState rf;
+    RebuildState rbt;
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };
@@ -613,6 +627,7 @@ void frt_renderer_destroy(frt_renderer* r) {
     for (auto& t : r->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     for (hipEvent_t e : r->event_pool) (void)hipEventDestroy(e);
     for (void* p : r->scene_allocs) (void)hipFree(p);
+    rebuild_release(r->rbt.scratch);
     if (r->rf.d_rec) (void)hipFree(r->rf.d_rec);
     if (r->rf.h_rec) (void)hipHostFree(r->rf.h_rec);
     if (r->rf.ev_rec) (void)hipEventDestroy(r->rf.ev_rec);
@@ -1412,6 +1427,70 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
     if (rc == FRT_ERR_HIP) r->failed = true;
     return rc;
 }
+
+// ------------------------------------------------------------------------------------------------ tree rebuild ("Rebuild")
+// Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
+// frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
+// reads the buffers that left the replica; they stay allocated and are what the next rebuild builds into.
+static int rebuild_tree_impl(frt_renderer* r) {
+    RebuildState& b = r->rbt;
+    SceneView& sv = r->sv;
+    FRT_DEVICE(r);
+    if (r->ahead) { r->tail_pending = true; const int rc = fence_ahead(r); if (rc) return rc; }
+    const uint32_t N = sv.num_tris;
+    auto alloc = [&](size_t bytes, void** out) {
+        HIP_TRY(hipMalloc(out, std::max<size_t>(bytes, 16)));
+        r->scene_allocs.push_back(*out);
+        b.device_bytes += bytes;
+        return (int)FRT_OK;
+    };
+    int rc;
+    if (!b.tris) {
+        HIP_TRY(rebuild_reserve(b.scratch, N));
+        b.device_bytes += b.scratch.bytes;
+        if ((rc = alloc((size_t)N * sizeof(TriSlot), (void**)&b.tris))) return rc;
+        if ((rc = alloc((size_t)N * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
+    }
+    const int t = sv.nodes4 == b.nodes[0] ? 1 : 0;
+    if (!b.nodes[t] && (rc = alloc((size_t)rebuild_max_nodes(N) * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
+    const RebuildTarget target{b.tris, b.nodes[t], b.slot_of};
+    RebuildResult res;
+    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res));
+    if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, "rebuild_tree: the tree could not be numbered (nothing changed)");
+    // the kernels have no overflow check: the bound is hard, and it is checked before anything of the replica changes
+    if (res.stack_need > (uint32_t)kStackDepth - 1u)
+        return fail(FRT_ERR_LIMIT, "rebuild_tree: the new tree needs " + std::to_string(res.stack_need) + " traversal-stack entries, " + std::to_string(kStackDepth - 1) + " is the limit (nothing changed)");
+    b.tris = const_cast<float4*>(sv.tris); b.slot_of = const_cast<uint32_t*>(r->rf.d_slot_of);
+    sv.tris = target.tris; r->rf.d_slot_of = target.slot_of;
+    sv.nodes4 = target.nodes; sv.num_nodes4 = res.num_nodes;
+    r->rf.quad_levels = res.levels;
+    r->rf.pair_levels.assign(1, 0u);       // later refits skip the pair levels
+    r->rf.ok = true;
+    r->wg_rows = res.stack_need + 1u;
+    r->vote = res.num_nodes >= kVoteMinQuadNodes;
+    b.done = true;
+    return FRT_OK;
+}
+int frt_renderer_rebuild_tree(frt_renderer* r) {
+    if (!r) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: null");
+    if (r->failed) return fail(FRT_ERR_STATE, "rebuild_tree: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
+    if (r->frame_open) return fail(FRT_ERR_STATE, "rebuild_tree: a frame is open (call it between frames)");
+#if FRT_EXPERIMENTS
+    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
+        return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: this renderer walks the 8-wide tree or the quantized pair nodes, which are not rebuilt");
+    if ((r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill)
+        return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: this renderer's kernels walk the pair tree, which is not rebuilt");
+#endif
+    const int rc = rebuild_tree_impl(r);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+int frt_renderer_tree_stats(frt_renderer* r, uint32_t st[4]) {
+    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer tree_stats: null");
+    st[0] = r->sv.num_nodes4; st[1] = r->wg_rows > 0u ? r->wg_rows - 1u : 0u;
+    st[2] = r->rf.quad_levels.empty() ? 0u : (uint32_t)r->rf.quad_levels.size() - 1u; st[3] = r->rbt.done ? 1u : 0u;
+    return FRT_OK;
+}
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
     const SceneView& sv = r->sv;
@@ -1420,7 +1499,9 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
     case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
     case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
-    case 15: src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
+    case 15:
+        if (r->rbt.done) return fail(FRT_ERR_STATE, "read_scene: the pair tree is not rebuilt by frt_renderer_rebuild_tree and no longer describes the replica");
+        src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
     case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
     default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16)");
     }

@@ -130,6 +130,8 @@ SYMBOLS = {
     "frt_renderer_set_timing": (C.c_int, [_P, C.c_int]),
     "frt_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_read_scene": (C.c_int, [_P, C.c_int, _P]),
+    "frt_renderer_rebuild_tree": (C.c_int, [_P]),
+    "frt_renderer_tree_stats": (C.c_int, [_P, _P]),
     "frt_multi_renderer_create": (_P, [_P, _U32, _U32, _U32, _P, C.POINTER(RenderOpts)]),
     "frt_multi_renderer_destroy": (None, [_P]),
     "frt_multi_renderer_render": (C.c_int, [_P, C.POINTER(CameraUniform)]),
@@ -147,6 +149,7 @@ SYMBOLS = {
     "frt_multi_renderer_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "frt_multi_renderer_boundaries": (C.c_int, [_P, _P]),
     "frt_multi_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_multi_renderer_rebuild_tree": (C.c_int, [_P]),
 }
 
 _lib = None

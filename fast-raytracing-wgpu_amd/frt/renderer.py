@@ -129,10 +129,21 @@ class Renderer:
     def set_instance_transform(self, instance_id, transform_colmajor):
         self.set_instance_transforms([instance_id], [transform_colmajor])
 
+    def rebuild_tree(self):
+        """Build a new quad tree over the replica's triangles as they are now, on the device (include/frt.h: frt_renderer_rebuild_tree): synchronous,
+        between frames; pixels, accumulation and reservoirs are untouched. The host scene keeps its own tree."""
+        check(lib().frt_renderer_rebuild_tree(self._h))
+
+    def tree_stats(self):
+        """The replica's quad tree: nodes, traversal-stack need, levels, origin (0 host build, 1 device rebuild)."""
+        s = (C.c_uint32 * 4)()
+        check(lib().frt_renderer_tree_stats(self._h, s))
+        return {"quad_nodes": int(s[0]), "quad_stack_need": int(s[1]), "quad_levels": int(s[2]), "origin": int(s[3])}
+
     def read_scene(self, what):
         """The device replica in SceneBuilder.get's layout: "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev" (syncs first)."""
         n = self._scene.counts()
-        which, shape, dt = {"lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self._scene.tree_stats()["quad_nodes"], 32), np.float32),
+        which, shape, dt = {"lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
                             "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
                             "instances_dev": (16, (n["instances"], 16), np.uint32)}[what]
         out = np.zeros(shape, dt)
@@ -219,6 +230,10 @@ class MultiRenderer:
         """Renderer.set_instance_transforms on every strip's scene replica."""
         n, i, m = transform_args(ids, transforms_colmajor)
         check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def rebuild_tree(self):
+        """Renderer.rebuild_tree on every strip's scene replica."""
+        check(lib().frt_multi_renderer_rebuild_tree(self._h))
 
     def read_buffer(self, buf, index=0):
         out = np.zeros((self.height, self.width, BUF_BPP[buf]), np.uint8)

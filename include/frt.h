@@ -303,8 +303,22 @@ int frt_renderer_set_timing(frt_renderer* r, int on);
  * frt_renderer_reset / _clear; motion vectors stay camera-only). FRT_ERR_STATE between the phases of an open frame; FRT_ERR_INVALID_ARG for a
  * renderer whose kernels walk a tree that is not refit (experiments build: FRT_FLAG_WALK_WIDE / _HBM with an 8-wide tree, the resident kernels). */
 int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
-/* Read the device replica back (syncs first), in the layout of frt_scene_get: 3 lights, 10 quad nodes, 13 triangle slots, 15 pair nodes,
- * 16 device instance records. */
+/* Build a new quad tree over the triangle slots as they are on the device now, i.e. after any number of frt_renderer_set_instance_transforms calls, whose
+ * refit keeps the topology and so loses quality after large moves ("Rebuild"): Morton order, leaves of two adjacent slots, a binary
+ * radix tree folded into quad nodes, boxes by the refit kernel; all on the device, into a second set of buffers that is swapped in only on success. Hits are
+ * defined without reference to any tree, so pixels, ray counts, accumulation, reservoirs and frame_count are untouched. SYNCHRONOUS, unlike the instance
+ * update: the per-level node counts and the stack need come back to the host, so the call returns when the new tree is in place; call it between frames.
+ * The first call allocates the extra device memory (DESIGN.md gives the size). Afterwards frt_renderer_read_scene selectors 10 and 13 return the new tree
+ * and later frt_renderer_set_instance_transforms calls refit it. The pair tree and its quantised form are NOT rebuilt (the product's kernels walk the quad
+ * nodes only): later refits skip them and selector 15 returns FRT_ERR_STATE. The host frt_scene gets no rebuild: its tree stays the host build's.
+ * Errors, nothing changed in each case: FRT_ERR_STATE between the phases of an open frame; FRT_ERR_INVALID_ARG for a renderer whose kernels walk a tree this
+ * call does not make (experiments build: the renderers frt_renderer_set_instance_transforms refuses, and the kernel families that walk the pair tree);
+ * FRT_ERR_LIMIT if the finished tree needs more than 31 traversal-stack entries (computed on the device, checked before the swap). */
+int frt_renderer_rebuild_tree(frt_renderer* r);
+/* The quad tree of this renderer's replica: stats[4] = quad nodes, deepest traversal stack, levels, origin (0 host build, 1 device rebuild) */
+int frt_renderer_tree_stats(frt_renderer* r, uint32_t stats[4]);
+/* Read the device replica back (syncs first), in the layout of frt_scene_get: 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
+ * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 
 /* ---- N GPUs behind one call (`ngpus`; section 8e) -----------------------------------------------------------------
@@ -349,6 +363,8 @@ int frt_multi_renderer_stats(frt_multi_renderer* m, frt_stats* out);            
 int frt_multi_renderer_boundaries(const frt_multi_renderer* m, uint32_t* rows_out);               /* ndev + 1 row indices; returns ndev */
 /* frt_renderer_set_instance_transforms on every strip's replica, between frames */
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* frt_renderer_rebuild_tree on every strip's replica, between frames (synchronous) */
+int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m);
 
 #ifdef __cplusplus
 }
