@@ -460,11 +460,12 @@ int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n
 
 // Every strip rebuilds its own replica's tree (frt_renderer_rebuild_tree: synchronous per strip). The replicas hold the same triangles, so the strips
 // build the same tree. State and renderer kind are checked on the first strip before any replica changes.
-int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m) {
+int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m) { return frt_multi_renderer_rebuild_tree_ex(m, FRT_REBUILD_MORTON); }
+int frt_multi_renderer_rebuild_tree_ex(frt_multi_renderer* m, uint32_t mode) {
     if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi rebuild_tree: null");
     if (m->failed) return set_error(FRT_ERR_STATE, "multi rebuild_tree: the handle is failed; call frt_multi_renderer_clear");
     for (size_t i = 0; i < m->strips.size(); ++i) {
-        const int rc = frt_renderer_rebuild_tree(m->strips[i].r);
+        const int rc = frt_renderer_rebuild_tree_ex(m->strips[i].r, mode);
         if (rc) { if (rc == FRT_ERR_HIP) m->failed = true; return rc; }      // (a strip that refuses keeps its valid tree: the strips still agree on every pixel)
     }
     return FRT_OK;

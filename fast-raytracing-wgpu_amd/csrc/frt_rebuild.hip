@@ -12,9 +12,7 @@ namespace frt {
 static const int kRbBlock = 256;
 static const uint32_t kRbLeaf = 0x80000000u, kRbNone = 0xFFFFFFFFu;
 static const uint32_t kRbBudget = (uint32_t)kStackDepth - 1u;      // build_quad_nodes: `budget`
-// The small results (RebuildScratch::words): [0..2] min and [3..5] max of the centroids as ordered bits, [6] the size of the next frontier,
-// [8 + L] whether the binary tree has inner nodes on level L.
-enum { W_MIN = 0, W_MAX = 3, W_NEXT = 6, W_FLAGS = 8, kMaxBinaryLevels = 64, kRebuildWords = W_FLAGS + kMaxBinaryLevels + 8 };
+// (The small results, RebuildScratch::words: frt_rebuild.hpp.)
 static const int kLevelChunk = 16;      // binary levels assigned between two looks at the flags
 
 // f32 bits whose unsigned order is the order of the floats (and back).
@@ -143,31 +141,61 @@ __device__ inline bool fold_fits(const uint32_t* c, int n, uint32_t used, const 
         if (!(c[i] & kRbLeaf) && c[i] < inner && used + (uint32_t)(n - 1) + (height[c[i]] - 1u) > kRbBudget) return false;
     return true;
 }
-// 6c. One level of the fold: quad node base + t is the binary node front[t]. It takes that node's two children, then replaces inner children by
-// their own two, left to right (pass after pass), while the set still fits. Writes the whole node: far-away point boxes, the children as BINARY
-// references (quad_number_kernel turns them into quad ones), and how many of them are inner.
+// Child i of the set c[0..n) replaced by its own two children, when the larger set still fits (fold_fits).
+__device__ inline bool fold_expand(uint32_t* c, int n, int i, uint32_t used, const uint32_t* left, const uint32_t* right, const uint32_t* height, uint32_t inner) {
+    uint32_t w[4] = {c[0], c[1], c[2], c[3]};
+    for (int k = n; k > i + 1; --k) w[k] = w[k - 1];
+    w[i] = left[c[i]]; w[i + 1] = right[c[i]];
+    if (!fold_fits(w, n + 1, used, height, inner)) return false;
+    for (int k = 0; k < 4; ++k) c[k] = w[k];
+    return true;
+}
+// The plain mode's order: inner children are replaced left to right, pass after pass, while the set still fits (topological, no boxes).
+__device__ inline int fold_left_to_right(uint32_t* c, int n, uint32_t used, const uint32_t* left, const uint32_t* right, const uint32_t* height, uint32_t inner) {
+    bool grew = true, stop = false;
+    while (grew && !stop && n < 4) {
+        grew = false;
+        for (int i = 0; i < n && n < 4 && !stop;) {
+            if ((c[i] & kRbLeaf) || c[i] >= inner) { ++i; continue; }
+            if (!fold_expand(c, n, i, used, left, right, height, inner)) { stop = true; break; }
+            ++n; i += 2; grew = true;
+        }
+    }
+    return n;
+}
+// The refined mode's order, build_quad_nodes's greedy fold: the inner child with the largest half-area (nbox: one box per binary inner node) is
+// replaced first, ties to the lower child position, until nothing is left to replace or the set no longer fits.
+__device__ inline float fold_half_area(const float* nbox, uint32_t b) {
+    const float* x = nbox + (size_t)b * 6u;
+    const float dx = x[3] - x[0], dy = x[4] - x[1], dz = x[5] - x[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+__device__ inline int fold_by_area(uint32_t* c, int n, uint32_t used, const uint32_t* left, const uint32_t* right, const uint32_t* height, uint32_t inner, const float* nbox) {
+    while (n < 4) {
+        int pick = -1; float best = -1.0f;
+        for (int i = 0; i < n; ++i) {
+            if ((c[i] & kRbLeaf) || c[i] >= inner) continue;
+            const float a = fold_half_area(nbox, c[i]);
+            if (a > best) { best = a; pick = i; }
+        }
+        if (pick < 0 || !fold_expand(c, n, pick, used, left, right, height, inner)) break;
+        ++n;
+    }
+    return n;
+}
+// 6c. One level of the fold: quad node base + t is the binary node front[t]. It takes that node's two children and folds further ones in, by area
+// with `nbox`, else left to right. Writes the whole node: far-away point boxes, the children as BINARY references (quad_number_kernel turns them
+// into quad ones), and how many of them are inner.
 __global__ void __launch_bounds__(kRbBlock) quad_fold_kernel(const uint32_t* left, const uint32_t* right, const uint32_t* height, uint32_t inner, const uint32_t* front,
-                                                             const uint32_t* used, uint32_t m, uint32_t base, uint32_t cap, float4* nodes, uint32_t* cnt) {
+                                                             const uint32_t* used, uint32_t m, uint32_t base, uint32_t cap, float4* nodes, uint32_t* cnt, const float* nbox) {
     const uint32_t t = blockIdx.x * (uint32_t)kRbBlock + threadIdx.x;
     if (t >= m || base + t >= cap) return;
     const uint32_t b = front[t], u = used[t];
     uint32_t c[4] = {kRbNone, kRbNone, kRbNone, kRbNone};
     int n = 0;
     if (b < inner) {
-        c[0] = left[b]; c[1] = right[b]; n = 2;
-        bool grew = true, stop = false;
-        while (grew && !stop && n < 4) {
-            grew = false;
-            for (int i = 0; i < n && n < 4 && !stop;) {
-                if ((c[i] & kRbLeaf) || c[i] >= inner) { ++i; continue; }
-                uint32_t w[4] = {c[0], c[1], c[2], c[3]};
-                for (int k = n; k > i + 1; --k) w[k] = w[k - 1];
-                w[i] = left[c[i]]; w[i + 1] = right[c[i]];
-                if (!fold_fits(w, n + 1, u, height, inner)) { stop = true; break; }
-                for (int k = 0; k < 4; ++k) c[k] = w[k];
-                ++n; i += 2; grew = true;
-            }
-        }
+        c[0] = left[b]; c[1] = right[b];
+        n = nbox ? fold_by_area(c, 2, u, left, right, height, inner, nbox) : fold_left_to_right(c, 2, u, left, right, height, inner);
     }
     uint32_t k_inner = 0;
     for (int i = 0; i < n; ++i) if (!(c[i] & kRbLeaf)) ++k_inner;
@@ -232,6 +260,7 @@ static inline size_t align256(size_t n) { return (n + 255u) & ~(size_t)255u; }
 
 void rebuild_release(RebuildScratch& s) {
     if (s.base) (void)hipFree(s.base);
+    if (s.ploc.base) (void)hipFree(s.ploc.base);
     if (s.h_words) (void)hipHostFree(s.h_words);
     s = RebuildScratch{};
 }
@@ -261,29 +290,17 @@ hipError_t rebuild_reserve(RebuildScratch& s, uint32_t num_tris) {
 
 #define RB_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
-// The small results, on the host, once everything enqueued so far has run.
-static hipError_t fetch_words(RebuildScratch& s, hipStream_t stream) {
+hipError_t rebuild_fetch_words(RebuildScratch& s, hipStream_t stream) {
     RB_TRY(hipMemcpyAsync(s.h_words, s.words, kRebuildWords * 4u, hipMemcpyDeviceToHost, stream));
     return hipStreamSynchronize(stream);
 }
 
-hipError_t rebuild_tree(RebuildScratch& s, const SceneView& cur, const uint32_t* slot_of, const RebuildTarget& out, unsigned int* ext, hipStream_t stream, RebuildResult& res) {
-    res = RebuildResult{};
-    const uint32_t N = cur.num_tris;
-    if (N == 0 || N > s.cap_tris) return hipErrorInvalidValue;
-    const uint32_t leaves = (N + 1u) / 2u, inner = leaves - 1u, cap = rebuild_max_nodes(N);
-    // 1-4: bounds, keys, sort, gather
-    RB_TRY(hipMemsetAsync(s.words, 0, kRebuildWords * 4u, stream));
-    RB_TRY(hipMemsetAsync(s.words + W_MIN, 0xFF, 3u * 4u, stream));
-    hipLaunchKernelGGL(centroid_bounds_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, s.words);
-    hipLaunchKernelGGL(morton_keys_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, s.words, s.keys[0]);
-    RB_TRY(hipGetLastError());
-    rocprim::double_buffer<unsigned long long> kb(s.keys[0], s.keys[1]);
-    size_t sort_bytes = s.sort_bytes;
-    RB_TRY(rocprim::radix_sort_keys(s.sort_tmp, sort_bytes, kb, (size_t)N, 0u, 64u, stream));
-    const unsigned long long* keys = kb.current();
-    hipLaunchKernelGGL(gather_slots_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, slot_of, keys, out.tris, out.slot_of);
-    RB_TRY(hipGetLastError());
+// 5 - 8 for one topology: `sah` builds the refined binary tree (frt_ploc.hip; its root is the last inner node made) and folds by area, else
+// Karras's radix tree (root: inner node 0) and the left-to-right fold. res.num_nodes == 0: the tree could not be numbered; res.fell_back != 0
+// (refined mode only): this topology must not be used.
+static hipError_t build_nodes(RebuildScratch& s, const SceneView& cur, const unsigned long long* keys, const RebuildTarget& out, unsigned int* ext, hipStream_t stream, bool sah, RebuildResult& res) {
+    const uint32_t N = cur.num_tris, leaves = (N + 1u) / 2u, inner = leaves - 1u, cap = rebuild_max_nodes(N);
+    res.num_nodes = 0; res.stack_need = 0;
     res.levels.assign(1, 0u);
     uint32_t total = 0;
     if (inner == 0) {
@@ -292,37 +309,45 @@ hipError_t rebuild_tree(RebuildScratch& s, const SceneView& cur, const uint32_t*
         total = 1; res.levels.push_back(1u);
     } else {
         // 5: binary topology
-        hipLaunchKernelGGL(radix_tree_kernel, grid_for(inner), dim3(kRbBlock), 0, stream, keys, leaves, s.left, s.right);
+        uint32_t root = 0;
+        if (sah) {
+            bool ok = false;
+            RB_TRY(ploc_topology(s, out.tris, N, stream, res.iterations, ok));
+            if (!ok) { res.fell_back = 1u; return hipSuccess; }
+            root = inner - 1u;
+        } else
+            hipLaunchKernelGGL(radix_tree_kernel, grid_for(inner), dim3(kRbBlock), 0, stream, keys, leaves, s.left, s.right);
         // 6a: levels, a chunk of launches between two looks at the flags
         RB_TRY(hipMemsetAsync(s.level, 0xFF, (size_t)inner * 4u, stream));
-        RB_TRY(hipMemsetAsync(s.level, 0, 4u, stream));
+        RB_TRY(hipMemsetAsync(s.level + root, 0, 4u, stream));
         uint32_t blevels = 0;
         for (uint32_t c0 = 0; c0 < (uint32_t)kMaxBinaryLevels && blevels == 0; c0 += (uint32_t)kLevelChunk) {
             for (uint32_t l = c0; l < c0 + (uint32_t)kLevelChunk; ++l)
                 hipLaunchKernelGGL(binary_level_kernel, grid_for(inner), dim3(kRbBlock), 0, stream, s.left, s.right, inner, l, s.level, s.words);
             RB_TRY(hipGetLastError());
-            RB_TRY(fetch_words(s, stream));
+            RB_TRY(rebuild_fetch_words(s, stream));
             for (uint32_t l = c0 + 1u; l <= c0 + (uint32_t)kLevelChunk; ++l)
                 if (!s.h_words[W_FLAGS + l]) { blevels = l; break; }
         }
-        if (blevels == 0) return hipSuccess;      // deeper than 64-bit keys allow: res.num_nodes stays 0
+        if (blevels == 0) { if (sah) res.fell_back = 2u; return hipSuccess; }      // deeper than 64 levels (Morton: than 64-bit keys allow): res.num_nodes stays 0
         // 6b: heights, deepest level first
         for (uint32_t l = blevels; l-- > 0;)
             hipLaunchKernelGGL(binary_height_kernel, grid_for(inner), dim3(kRbBlock), 0, stream, s.left, s.right, s.level, inner, l, s.height);
         RB_TRY(hipGetLastError());
-        // 6c, 6d: the fold, one quad level per round; the root is binary node 0 with nothing pushed above it
-        RB_TRY(hipMemsetAsync(s.front[0], 0, 4u, stream));
+        // 6c, 6d: the fold, one quad level per round; the root has nothing pushed above it
+        RB_TRY(hipMemsetD32Async((hipDeviceptr_t)s.front[0], (int)root, 1u, stream));
         RB_TRY(hipMemsetAsync(s.used[0], 0, 4u, stream));
         uint32_t m = 1, base = 0; int f = 0;
         while (m > 0) {
             if (base + m > cap) return hipSuccess;
-            hipLaunchKernelGGL(quad_fold_kernel, grid_for(m), dim3(kRbBlock), 0, stream, s.left, s.right, s.height, inner, s.front[f], s.used[f], m, base, cap, out.nodes, s.cnt);
+            hipLaunchKernelGGL(quad_fold_kernel, grid_for(m), dim3(kRbBlock), 0, stream, s.left, s.right, s.height, inner, s.front[f], s.used[f], m, base, cap, out.nodes, s.cnt,
+                               sah ? (const float*)s.ploc.nbox : (const float*)nullptr);
             RB_TRY(hipGetLastError());
             size_t scan_bytes = s.scan_bytes;
             RB_TRY(rocprim::exclusive_scan(s.scan_tmp, scan_bytes, s.cnt, s.off, 0u, (size_t)m, rocprim::plus<uint32_t>(), stream));
             hipLaunchKernelGGL(quad_number_kernel, grid_for(m), dim3(kRbBlock), 0, stream, s.used[f], s.cnt, s.off, m, base, cap, N, out.nodes, s.front[f ^ 1], s.used[f ^ 1], s.cap_inner, s.words);
             RB_TRY(hipGetLastError());
-            RB_TRY(fetch_words(s, stream));
+            RB_TRY(rebuild_fetch_words(s, stream));
             base += m; res.levels.push_back(base);
             m = s.h_words[W_NEXT]; f ^= 1;
         }
@@ -343,6 +368,35 @@ hipError_t rebuild_tree(RebuildScratch& s, const SceneView& cur, const uint32_t*
     RB_TRY(hipStreamSynchronize(stream));
     res.stack_need = s.h_words[0];
     res.num_nodes = total;
+    return hipSuccess;
+}
+
+hipError_t rebuild_tree(RebuildScratch& s, const SceneView& cur, const uint32_t* slot_of, const RebuildTarget& out, unsigned int* ext, hipStream_t stream, RebuildResult& res, uint32_t mode) {
+    res = RebuildResult{};
+    const uint32_t N = cur.num_tris;
+    if (N == 0 || N > s.cap_tris) return hipErrorInvalidValue;
+    // 1-4: bounds, keys, sort, gather
+    RB_TRY(hipMemsetAsync(s.words, 0, kRebuildWords * 4u, stream));
+    RB_TRY(hipMemsetAsync(s.words + W_MIN, 0xFF, 3u * 4u, stream));
+    hipLaunchKernelGGL(centroid_bounds_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, s.words);
+    hipLaunchKernelGGL(morton_keys_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, s.words, s.keys[0]);
+    RB_TRY(hipGetLastError());
+    rocprim::double_buffer<unsigned long long> kb(s.keys[0], s.keys[1]);
+    size_t sort_bytes = s.sort_bytes;
+    RB_TRY(rocprim::radix_sort_keys(s.sort_tmp, sort_bytes, kb, (size_t)N, 0u, 64u, stream));
+    const unsigned long long* keys = kb.current();
+    hipLaunchKernelGGL(gather_slots_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, slot_of, keys, out.tris, out.slot_of);
+    RB_TRY(hipGetLastError());
+    if (mode != 0u && N > 2u) {
+        // the refined tree; it is kept when it is complete and fits the traversal stack
+        RB_TRY(build_nodes(s, cur, keys, out, ext, stream, true, res));
+        if (!res.fell_back && res.num_nodes > 0 && res.stack_need > kRbBudget) res.fell_back = 2u;
+        if (!res.fell_back && res.num_nodes > 0) { res.origin = 2u; return hipSuccess; }
+        if (!res.fell_back) res.fell_back = 2u;
+        RB_TRY(hipMemsetAsync(s.words + W_NEXT, 0, (kRebuildWords - W_NEXT) * 4u, stream));      // the level flags and the frontier size, as a Morton-mode call finds them
+    }
+    RB_TRY(build_nodes(s, cur, keys, out, ext, stream, false, res));
+    res.origin = mode != 0u && N <= 2u ? 2u : 1u;      // (a lone leaf is one node in either mode)
     return hipSuccess;
 }
 

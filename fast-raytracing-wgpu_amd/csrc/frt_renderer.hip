@@ -130,6 +130,8 @@ struct RebuildState {
     float4* tris = nullptr; uint32_t* slot_of = nullptr;
     float4* nodes[2] = {nullptr, nullptr};
     bool done = false;                     // the replica's quad tree is a device rebuild: the pair tree and its quantised form are stale
+    uint32_t origin = 0;                   // frt_renderer_tree_stats: 1 the Morton tree, 2 the refined tree
+    uint32_t last[4] = {0, 0, 0, 0};       // frt_renderer_rebuild_stats
     uint64_t device_bytes = 0;
 };
 
@@ -1432,7 +1434,7 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
 // Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
 // frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
 // reads the buffers that left the replica; they stay allocated and are what the next rebuild builds into.
-static int rebuild_tree_impl(frt_renderer* r) {
+static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
     RebuildState& b = r->rbt;
     SceneView& sv = r->sv;
     FRT_DEVICE(r);
@@ -1451,11 +1453,17 @@ static int rebuild_tree_impl(frt_renderer* r) {
         if ((rc = alloc((size_t)N * sizeof(TriSlot), (void**)&b.tris))) return rc;
         if ((rc = alloc((size_t)N * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
     }
+    if (mode == FRT_REBUILD_SAH && N > 2u) {      // the refined mode's own scratch, at its first call only
+        const size_t had = b.scratch.ploc.bytes;
+        HIP_TRY(ploc_reserve(b.scratch, N));
+        b.device_bytes += b.scratch.ploc.bytes - had;
+    }
     const int t = sv.nodes4 == b.nodes[0] ? 1 : 0;
     if (!b.nodes[t] && (rc = alloc((size_t)rebuild_max_nodes(N) * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
     const RebuildTarget target{b.tris, b.nodes[t], b.slot_of};
     RebuildResult res;
-    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res));
+    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res, mode));
+    b.last[0] = mode; b.last[1] = res.iterations; b.last[2] = res.fell_back; b.last[3] = (uint32_t)((b.scratch.ploc.bytes + 1023u) >> 10);
     if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, "rebuild_tree: the tree could not be numbered (nothing changed)");
     // the kernels have no overflow check: the bound is hard, and it is checked before anything of the replica changes
     if (res.stack_need > (uint32_t)kStackDepth - 1u)
@@ -1468,10 +1476,11 @@ static int rebuild_tree_impl(frt_renderer* r) {
     r->rf.ok = true;
     r->wg_rows = res.stack_need + 1u;
     r->vote = res.num_nodes >= kVoteMinQuadNodes;
-    b.done = true;
+    b.done = true; b.origin = res.origin;
     return FRT_OK;
 }
-int frt_renderer_rebuild_tree(frt_renderer* r) {
+int frt_renderer_rebuild_tree(frt_renderer* r) { return frt_renderer_rebuild_tree_ex(r, FRT_REBUILD_MORTON); }
+int frt_renderer_rebuild_tree_ex(frt_renderer* r, uint32_t mode) {
     if (!r) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: null");
     if (r->failed) return fail(FRT_ERR_STATE, "rebuild_tree: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
     if (r->frame_open) return fail(FRT_ERR_STATE, "rebuild_tree: a frame is open (call it between frames)");
@@ -1481,14 +1490,20 @@ int frt_renderer_rebuild_tree(frt_renderer* r) {
     if ((r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill)
         return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: this renderer's kernels walk the pair tree, which is not rebuilt");
 #endif
-    const int rc = rebuild_tree_impl(r);
+    if (mode != FRT_REBUILD_MORTON && mode != FRT_REBUILD_SAH) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: unknown mode (FRT_REBUILD_MORTON, FRT_REBUILD_SAH)");
+    const int rc = rebuild_tree_impl(r, mode);
     if (rc == FRT_ERR_HIP) r->failed = true;
     return rc;
 }
 int frt_renderer_tree_stats(frt_renderer* r, uint32_t st[4]) {
     if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer tree_stats: null");
     st[0] = r->sv.num_nodes4; st[1] = r->wg_rows > 0u ? r->wg_rows - 1u : 0u;
-    st[2] = r->rf.quad_levels.empty() ? 0u : (uint32_t)r->rf.quad_levels.size() - 1u; st[3] = r->rbt.done ? 1u : 0u;
+    st[2] = r->rf.quad_levels.empty() ? 0u : (uint32_t)r->rf.quad_levels.size() - 1u; st[3] = r->rbt.done ? r->rbt.origin : 0u;
+    return FRT_OK;
+}
+int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t st[4]) {
+    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer rebuild_stats: null");
+    for (int k = 0; k < 4; ++k) st[k] = r->rbt.last[k];
     return FRT_OK;
 }
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {

@@ -131,6 +131,8 @@ SYMBOLS = {
     "frt_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_read_scene": (C.c_int, [_P, C.c_int, _P]),
     "frt_renderer_rebuild_tree": (C.c_int, [_P]),
+    "frt_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
+    "frt_renderer_rebuild_stats": (C.c_int, [_P, _P]),
     "frt_renderer_tree_stats": (C.c_int, [_P, _P]),
     "frt_multi_renderer_create": (_P, [_P, _U32, _U32, _U32, _P, C.POINTER(RenderOpts)]),
     "frt_multi_renderer_destroy": (None, [_P]),
@@ -150,6 +152,7 @@ SYMBOLS = {
     "frt_multi_renderer_boundaries": (C.c_int, [_P, _P]),
     "frt_multi_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
     "frt_multi_renderer_rebuild_tree": (C.c_int, [_P]),
+    "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
 }
 
 _lib = None

@@ -5,6 +5,15 @@ from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_B
 from .scene import transform_args
 
 
+REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
+
+
+def rebuild_mode(quality):
+    if quality not in REBUILD_MODES:
+        raise ValueError(f"rebuild_tree: quality must be one of {sorted(REBUILD_MODES)}, not {quality!r}")
+    return REBUILD_MODES[quality]
+
+
 class Renderer:
     def __init__(self, scene, width, height, max_depth=8, device=0, stream=None, rows=None, arena=None, arena_bytes=0, flags=0, motion_halo=0,
                  queue_capacity=0, cuts=None):
@@ -129,13 +138,24 @@ class Renderer:
     def set_instance_transform(self, instance_id, transform_colmajor):
         self.set_instance_transforms([instance_id], [transform_colmajor])
 
-    def rebuild_tree(self):
+    def rebuild_tree(self, quality="morton"):
         """Build a new quad tree over the replica's triangles as they are now, on the device (include/frt.h: frt_renderer_rebuild_tree): synchronous,
-        between frames; pixels, accumulation and reservoirs are untouched. The host scene keeps its own tree."""
-        check(lib().frt_renderer_rebuild_tree(self._h))
+        between frames; pixels, accumulation and reservoirs are untouched. The host scene keeps its own tree. quality: "morton", the plain
+        Morton-order tree, or "sah", the tree refined by surface area (frt_renderer_rebuild_tree_ex)."""
+        if quality == "morton":
+            check(lib().frt_renderer_rebuild_tree(self._h))
+        else:
+            check(lib().frt_renderer_rebuild_tree_ex(self._h, rebuild_mode(quality)))
+
+    def rebuild_stats(self):
+        """The last rebuild_tree that reached the device: mode asked for, clustering iterations ("sah"), why the Morton tree was built instead
+        (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added."""
+        s = (C.c_uint32 * 4)()
+        check(lib().frt_renderer_rebuild_stats(self._h, s))
+        return {"mode": int(s[0]), "iterations": int(s[1]), "fell_back": int(s[2]), "refined_scratch_kib": int(s[3])}
 
     def tree_stats(self):
-        """The replica's quad tree: nodes, traversal-stack need, levels, origin (0 host build, 1 device rebuild)."""
+        """The replica's quad tree: nodes, traversal-stack need, levels, origin (0 host build, 1 device Morton tree, 2 device refined tree)."""
         s = (C.c_uint32 * 4)()
         check(lib().frt_renderer_tree_stats(self._h, s))
         return {"quad_nodes": int(s[0]), "quad_stack_need": int(s[1]), "quad_levels": int(s[2]), "origin": int(s[3])}
@@ -231,9 +251,12 @@ class MultiRenderer:
         n, i, m = transform_args(ids, transforms_colmajor)
         check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
 
-    def rebuild_tree(self):
+    def rebuild_tree(self, quality="morton"):
         """Renderer.rebuild_tree on every strip's scene replica."""
-        check(lib().frt_multi_renderer_rebuild_tree(self._h))
+        if quality == "morton":
+            check(lib().frt_multi_renderer_rebuild_tree(self._h))
+        else:
+            check(lib().frt_multi_renderer_rebuild_tree_ex(self._h, rebuild_mode(quality)))
 
     def read_buffer(self, buf, index=0):
         out = np.zeros((self.height, self.width, BUF_BPP[buf]), np.uint8)

@@ -1,8 +1,10 @@
 """Cost and worth of rebuilding a renderer's tree on the device (include/frt.h: frt_renderer_rebuild_tree; DESIGN.md section 11, "Rebuild") on the Cornell
 Box, the 82k-triangle blob and the 246k-triangle colonnade (tests/_scenes.py), 1920x1080, depth 8, two-stream schedule. Per scene, in a strongly moved
 pose: the wall time of rebuild_tree() (first call, which allocates, and the median of 20 more), the device memory the first call takes, the host
-rebuild + renderer re-create the call replaces, and the frame time over three trees measured alternately in one session: (i) a scene freshly
-host-built in the moved pose, (ii) the original tree refit, (iii) refit + device rebuild. One JSON line per scene.
+rebuild + renderer re-create the call replaces, and the frame time over four trees measured alternately in one session: (i) a scene freshly
+host-built in the moved pose, (ii) the original tree refit, (iii) refit + device rebuild, (iv) refit + refined device rebuild (quality="sah":
+its call times, the device memory of its first call, its clustering iterations). node_term of all four trees by tests/_tree_cost.py. One JSON
+line per scene.
 Usage: python tools/tree_rebuild_time.py [cornell blob colonnade]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,6 +14,7 @@ import torch
 import frt
 from _oracle import Oracle
 from instance_update_time import frame_ms
+from _tree_cost import tree_cost
 
 
 def _ry(a):
@@ -80,10 +83,11 @@ def main(names):
         r_fresh = frt.Renderer(fresh, W, H, flags=frt.FLAG_PIPELINE)
         r_fresh.sync()
         host_s = time.perf_counter() - t0                                                 # what a user without the call pays: host build + re-create
-        r_refit, r_rebuilt = frt.Renderer(fs, W, H, flags=frt.FLAG_PIPELINE), frt.Renderer(fs, W, H, flags=frt.FLAG_PIPELINE)
+        r_refit, r_rebuilt, r_sah = (frt.Renderer(fs, W, H, flags=frt.FLAG_PIPELINE) for _ in range(3))
         ms_rest = frame_ms(r_refit, W, H, fs.num_lights)
-        r_refit.set_instance_transforms(ids, mats); r_rebuilt.set_instance_transforms(ids, mats)
-        r_rebuilt.sync(); torch.cuda.synchronize()
+        for r in (r_refit, r_rebuilt, r_sah):
+            r.set_instance_transforms(ids, mats)
+        r_rebuilt.sync(); r_sah.sync(); torch.cuda.synchronize()
         free0 = torch.cuda.mem_get_info()[0]
         t0 = time.perf_counter(); r_rebuilt.rebuild_tree(); first_ms = (time.perf_counter() - t0) * 1e3
         free1 = torch.cuda.mem_get_info()[0]
@@ -91,8 +95,15 @@ def main(names):
         for _ in range(20):
             t0 = time.perf_counter(); r_rebuilt.rebuild_tree(); calls.append((time.perf_counter() - t0) * 1e3)
         free2 = torch.cuda.mem_get_info()[0]
+        t0 = time.perf_counter(); r_sah.rebuild_tree("sah"); sah_first_ms = (time.perf_counter() - t0) * 1e3
+        free3 = torch.cuda.mem_get_info()[0]
+        sah_calls = []
+        for _ in range(20):
+            t0 = time.perf_counter(); r_sah.rebuild_tree("sah"); sah_calls.append((time.perf_counter() - t0) * 1e3)
+        sah_ms = float(np.median(sah_calls))
         assert r_rebuilt.read_scene("tri_slots").shape == fresh.get("tri_slots").shape
-        trees = {"fresh": r_fresh, "refit": r_refit, "rebuilt": r_rebuilt}
+        trees = {"fresh": r_fresh, "refit": r_refit, "rebuilt": r_rebuilt, "sah": r_sah}
+        node_term = {k: round(tree_cost(r.read_scene("quad_nodes"))["node_term"], 4) for k, r in trees.items()}
         ms = {k: [] for k in trees}
         for _ in range(5):                                                                # alternately, one session
             for k, r in trees.items():
@@ -105,8 +116,12 @@ def main(names):
                           "ms_frame_rest_pose": round(ms_rest, 3),
                           "ms_frame": {k: round(float(np.median(v)), 3) for k, v in ms.items()}, "ms_frame_runs": {k: [round(x, 3) for x in v] for k, v in ms.items()},
                           "tree_fresh": {k: fresh.tree_stats()[k] for k in ("quad_nodes", "quad_stack_need")}, "tree_refit": r_refit.tree_stats(),
-                          "tree_rebuilt": r_rebuilt.tree_stats()}), flush=True)
-        del trees, r_fresh, r_refit, r_rebuilt
+                          "tree_rebuilt": r_rebuilt.tree_stats(), "tree_sah": r_sah.tree_stats(),
+                          "ms_sah_first_call": round(sah_first_ms, 3), "ms_sah_call": round(sah_ms, 3), "ms_sah_call_min_max": [round(min(sah_calls), 3), round(max(sah_calls), 3)],
+                          "sah_over_morton_call": round(sah_ms / call_ms, 2), "bytes_sah_first_call": int(free2 - free3),
+                          "sah_refined_scratch_kib": r_sah.rebuild_stats()["refined_scratch_kib"], "sah_iterations": r_sah.rebuild_stats()["iterations"],
+                          "sah_fell_back": r_sah.rebuild_stats()["fell_back"], "node_term": node_term}), flush=True)
+        del trees, r_fresh, r_refit, r_rebuilt, r_sah
 
 
 if __name__ == "__main__":
