@@ -294,6 +294,29 @@ void SceneBuilder::ensure_wide8() const {
     wide8_built = true;
 }
 
+void decoded_vertex_normal(const frt_vertex_attr& a, float out[3]) {
+    const f3 n = decode_octahedral_normal(a.normal[0], a.normal[1]);   // same function the kernels would run per hit
+    out[0] = n.x; out[1] = n.y; out[2] = n.z;
+}
+
+void SceneBuilder::write_shade_tri(uint32_t id) {
+    const InstanceRec& in = instances[tri_instance[id]];
+    const MeshInfo& mi = mesh_infos[in.mesh_id];
+    uint32_t prim = id - in.first_tri;
+    ShadeTri o{};
+    for (int k = 0; k < 3; ++k) {
+        const frt_vertex_attr& a = attributes[indices[mi.index_offset + prim * 3u + k] + mi.vertex_offset];
+        decoded_vertex_normal(a, &o.q[4 * k]);
+        o.q[12 + 4 * k] = a.tangent[0]; o.q[12 + 4 * k + 1] = a.tangent[1]; o.q[12 + 4 * k + 2] = a.tangent[2];
+        // uvs: (uv0.x, uv0.y, uv1.x, uv1.y, uv2.x, uv2.y) in the .w lanes of q0..q5
+        o.q[4 * (2 * k) + 3] = a.uv[0]; o.q[4 * (2 * k + 1) + 3] = a.uv[1];
+        if (k == 0) o.q[24] = a.tangent[3];
+    }
+    uint32_t mat = in.mat_id;
+    memcpy(&o.q[25], &mat, 4);
+    shade_tris[id] = o;
+}
+
 void SceneBuilder::build_gpu_layout() {
     pair_nodes.clear(); tri_slots.clear(); tri_slot_of.clear(); instances_dev.clear(); shade_tris.clear();
     if (!error.empty()) return;
@@ -359,23 +382,7 @@ void SceneBuilder::build_gpu_layout() {
     wide8 = Wide8{}; tri_slots8.clear(); wide8_built = false;      // (built on first use: ensure_wide8)
     // shading records: the instance -> mesh -> index -> attribute chain of gbuffer.wgsl:129-145, flattened per triangle
     shade_tris.assign(tris.size(), ShadeTri{});
-    for (size_t id = 0; id < tris.size(); ++id) {
-        const InstanceRec& in = instances[tri_instance[id]];
-        const MeshInfo& mi = mesh_infos[in.mesh_id];
-        uint32_t prim = (uint32_t)id - in.first_tri;
-        ShadeTri& o = shade_tris[id];
-        for (int k = 0; k < 3; ++k) {
-            const frt_vertex_attr& a = attributes[indices[mi.index_offset + prim * 3u + k] + mi.vertex_offset];
-            f3 n = decode_octahedral_normal(a.normal[0], a.normal[1]);   // same function the kernels would run per hit
-            o.q[4 * k] = n.x; o.q[4 * k + 1] = n.y; o.q[4 * k + 2] = n.z;
-            o.q[12 + 4 * k] = a.tangent[0]; o.q[12 + 4 * k + 1] = a.tangent[1]; o.q[12 + 4 * k + 2] = a.tangent[2];
-            // uvs: (uv0.x, uv0.y, uv1.x, uv1.y, uv2.x, uv2.y) in the .w lanes of q0..q5
-            o.q[4 * (2 * k) + 3] = a.uv[0]; o.q[4 * (2 * k + 1) + 3] = a.uv[1];
-            if (k == 0) o.q[24] = a.tangent[3];
-        }
-        uint32_t mat = in.mat_id;
-        memcpy(&o.q[25], &mat, 4);
-    }
+    for (size_t id = 0; id < tris.size(); ++id) write_shade_tri((uint32_t)id);
     instances_dev.resize(instances.size());
     for (size_t i = 0; i < instances.size(); ++i) {
         InstanceDev& d = instances_dev[i];

@@ -458,6 +458,17 @@ int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n
     return FRT_OK;
 }
 
+// Every strip deforms its own replica (frt_renderer_set_mesh_vertices), as above: arguments are checked on the first strip before any replica changes.
+int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_mesh_vertices: null");
+    if (m->failed) return set_error(FRT_ERR_STATE, "multi set_mesh_vertices: the handle is failed; call frt_multi_renderer_clear");
+    for (size_t i = 0; i < m->strips.size(); ++i) {
+        const int rc = frt_renderer_set_mesh_vertices(m->strips[i].r, mesh_id, pos4, attrs, nverts);
+        if (rc) { if (i > 0) m->failed = true; return rc; }      // (a later strip can only fail in HIP: the replicas now differ)
+    }
+    return FRT_OK;
+}
+
 // Every strip rebuilds its own replica's tree (frt_renderer_rebuild_tree: synchronous per strip). The replicas hold the same triangles, so the strips
 // build the same tree. State and renderer kind are checked on the first strip before any replica changes.
 int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m) { return frt_multi_renderer_rebuild_tree_ex(m, FRT_REBUILD_MORTON); }

@@ -62,9 +62,13 @@ __global__ void __launch_bounds__(kRefitBlock) scene_extent_kernel(SceneView sc,
 hipError_t launch_instance_transform(const SceneView& sc, const RefitArgs& a, hipStream_t stream) {
     const uint32_t n = a.work > a.nrec ? a.work : a.nrec;
     if (n > 0) hipLaunchKernelGGL(instance_transform_kernel, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, stream, sc, a);
-    hipError_t e = hipMemsetAsync(a.ext, 0, sizeof(unsigned int), stream);
+    return launch_scene_extent(sc, a.ext, stream);
+}
+
+hipError_t launch_scene_extent(const SceneView& sc, unsigned int* ext, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(ext, 0, sizeof(unsigned int), stream);
     if (e != hipSuccess) return e;
-    if (sc.num_tris > 0) hipLaunchKernelGGL(scene_extent_kernel, dim3((sc.num_tris + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, stream, sc, a.ext);
+    if (sc.num_tris > 0) hipLaunchKernelGGL(scene_extent_kernel, dim3((sc.num_tris + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, stream, sc, ext);
     return hipGetLastError();
 }
 

@@ -32,6 +32,8 @@ struct RefitArgs {
 
 // Transform + record scatter, then the scene-box reduction (ext zeroed first), all on `stream`.
 hipError_t launch_instance_transform(const SceneView& sc, const RefitArgs& a, hipStream_t stream);
+// The scene-box reduction alone (what launch_instance_transform ends with): `ext` zeroed, then max |coordinate| over every triangle slot.
+hipError_t launch_scene_extent(const SceneView& sc, unsigned int* ext, hipStream_t stream);
 // One refit level: pair nodes [p0, p1) and quad nodes [q0, q1) (each range one level of its tree, every deeper level already refit).
 hipError_t launch_refit_level(const SceneView& sc, const unsigned int* ext, uint32_t p0, uint32_t p1, uint32_t q0, uint32_t q1, hipStream_t stream);
 

@@ -5,6 +5,7 @@
 #include "frt_kernels.hpp"
 #include "frt_refit.hpp"
 #include "frt_rebuild.hpp"
+#include "frt_deform.hpp"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cstdio>
@@ -118,6 +119,12 @@ struct RefitState {
     MovedInstance* d_rec = nullptr; size_t d_cap = 0;
     MovedInstance* h_rec = nullptr; size_t h_cap = 0;   // pinned staging of the records
     hipEvent_t ev_rec = nullptr; bool rec_pending = false;   // the last copy out of h_rec
+    // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; pinned staging of one call's positions,
+    // attributes, instance records and decoded normals; the device buffer of the last two. Both grow on demand and are never shrunk.
+    std::vector<uint32_t> vert_count, attr_offset;
+    uint8_t* h_def = nullptr; size_t h_def_cap = 0;
+    uint8_t* d_def = nullptr; size_t d_def_cap = 0;
+    hipEvent_t ev_def = nullptr; bool def_pending = false;   // the last copy out of h_def
     uint64_t device_bytes = 0;
 };
 
@@ -252,10 +259,12 @@ static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
 static int upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
     RefitState& f = r->rf;
     std::vector<float> pos;
-    f.pos_offset.clear(); f.index_offset.clear();
+    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear();
     for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
         f.pos_offset.push_back((uint32_t)(pos.size() / 4));
         f.index_offset.push_back(b.mesh_infos[m].index_offset);
+        f.vert_count.push_back((uint32_t)(b.mesh_positions[m].size() / 4));
+        f.attr_offset.push_back(b.mesh_infos[m].vertex_offset);
         pos.insert(pos.end(), b.mesh_positions[m].begin(), b.mesh_positions[m].end());
     }
     int rc;
@@ -531,6 +540,11 @@ int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* 
     const int rc = s->b.set_instance_transforms(n, ids, m_colmajor16);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null");
+    const int rc = s->b.set_mesh_vertices(mesh_id, pos4, attrs, nverts);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 frt_scene* frt_scene_create_cornell_box(void) {
     frt_scene* s = new frt_scene();
     scenes::create_cornell_box(s->b);
@@ -577,6 +591,7 @@ int frt_scene_get(const frt_scene* s, int which, void* out) {
     case 14: b.ensure_wide8(); memcpy(out, b.wide8.child_boxes.data(), b.wide8.child_boxes.size() * 4); break;
     case 15: memcpy(out, b.pair_nodes.data(), b.pair_nodes.size() * sizeof(PairNode)); break;
     case 16: memcpy(out, b.instances_dev.data(), b.instances_dev.size() * sizeof(InstanceDev)); break;
+    case 17: memcpy(out, b.shade_tris.data(), b.shade_tris.size() * sizeof(ShadeTri)); break;
     default: return fail(FRT_ERR_INVALID_ARG, "get: unknown selector");
     }
     return FRT_OK;
@@ -633,6 +648,9 @@ void frt_renderer_destroy(frt_renderer* r) {
     if (r->rf.d_rec) (void)hipFree(r->rf.d_rec);
     if (r->rf.h_rec) (void)hipHostFree(r->rf.h_rec);
     if (r->rf.ev_rec) (void)hipEventDestroy(r->rf.ev_rec);
+    if (r->rf.d_def) (void)hipFree(r->rf.d_def);
+    if (r->rf.h_def) (void)hipHostFree(r->rf.h_def);
+    if (r->rf.ev_def) (void)hipEventDestroy(r->rf.ev_def);
     if (r->own_arena && r->arena) (void)hipFree(r->arena);
     if (r->extras) (void)hipFree(r->extras);
     if (r->d_counters) (void)hipFree(r->d_counters);
@@ -1345,6 +1363,18 @@ int frt_renderer_clear(frt_renderer* r) {
 // on it; the edge streams' spatial launches are behind the main stream's wait for ev_edge (end of every spatial stage); the ahead stream's work
 // (a speculated next frame) is fenced, and a speculation — traced under the old geometry — is dropped as if its camera had not matched. The next
 // frame's first kernel is enqueued behind the update on the main stream, or (a new speculation) on the ahead stream behind T-merge's event.
+// Both trees level by level, deepest first: launch k refits the k-th deepest level of each (after a rebuild the pair tree has no levels left).
+static int refit_levels(frt_renderer* r) {
+    const RefitState& f = r->rf;
+    const size_t lp = f.pair_levels.size() - 1, lq = f.quad_levels.size() - 1;
+    for (size_t k = 0; k < std::max(lp, lq); ++k) {
+        uint32_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
+        if (k < lp) { p0 = f.pair_levels[lp - 1 - k]; p1 = f.pair_levels[lp - k]; }
+        if (k < lq) { q0 = f.quad_levels[lq - 1 - k]; q1 = f.quad_levels[lq - k]; }
+        HIP_TRY(launch_refit_level(r->sv, f.d_ext, p0, p1, q0, q1, r->stream));
+    }
+    return FRT_OK;
+}
 static int set_instance_transforms_impl(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats) {
     RefitState& f = r->rf;
     FRT_DEVICE(r);
@@ -1404,15 +1434,7 @@ static int set_instance_transforms_impl(frt_renderer* r, uint32_t n, const uint3
     f.rec_pending = true;
     RefitArgs a{f.d_rec, (uint32_t)rec.size(), work, f.d_pos, f.d_slot_of, const_cast<unsigned int*>(f.d_ext)};
     HIP_TRY(launch_instance_transform(r->sv, a, r->stream));
-    // both trees level by level, deepest first: launch k refits the k-th deepest level of each
-    const size_t lp = f.pair_levels.size() - 1, lq = f.quad_levels.size() - 1;
-    for (size_t k = 0; k < std::max(lp, lq); ++k) {
-        uint32_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
-        if (k < lp) { p0 = f.pair_levels[lp - 1 - k]; p1 = f.pair_levels[lp - k]; }
-        if (k < lq) { q0 = f.quad_levels[lq - 1 - k]; q1 = f.quad_levels[lq - k]; }
-        HIP_TRY(launch_refit_level(r->sv, f.d_ext, p0, p1, q0, q1, r->stream));
-    }
-    return FRT_OK;
+    return refit_levels(r);
 }
 int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
     if (!r) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null");
@@ -1426,6 +1448,83 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
     const std::string bad = check_instance_transforms(n, ids, m_colmajor16, r->rf.inst.size());
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: " + bad);
     const int rc = set_instance_transforms_impl(r, n, ids, m_colmajor16);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
+// Ordering as the instance update's. One pinned block holds what a call uploads: [positions | attributes | instance records | decoded normals];
+// the first two are copied into the replica (the object-space positions the instance update reads, SceneView::attributes), the last two into a
+// device buffer of this call's own. The block is reused once the previous call's copies out of it have completed (ev_def); the device buffer is
+// reused in stream order and replaced, after a wait for the stream, only when it has to grow.
+static int set_mesh_vertices_impl(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = drop_speculation(r);
+    if (rc) return rc;
+    if (r->ahead) { r->tail_pending = true; if ((rc = fence_ahead(r))) return rc; }
+    std::vector<DeformInstance> rec;
+    uint32_t work = 0;
+    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
+        const InstanceRec& in = f.inst[i];
+        if (in.mesh_id != mesh_id) continue;
+        DeformInstance d;
+        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
+        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
+        rec.push_back(d);
+    }
+    const size_t pos_bytes = (size_t)nverts * 16, attr_bytes = attrs ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
+    const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = attrs ? (size_t)nverts * 16 : 0;
+    const size_t up_bytes = rec_bytes + nrm_bytes, all_bytes = pos_bytes + attr_bytes + up_bytes;
+    if (!f.ev_def) HIP_TRY(hipEventCreateWithFlags(&f.ev_def, hipEventDisableTiming));
+    if (f.def_pending) { HIP_TRY(hipEventSynchronize(f.ev_def)); f.def_pending = false; }
+    if (f.h_def_cap < all_bytes) {
+        if (f.h_def) HIP_TRY(hipHostFree(f.h_def));
+        f.h_def = nullptr; f.h_def_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&f.h_def, all_bytes));
+        f.h_def_cap = all_bytes;
+    }
+    if (f.d_def_cap < up_bytes) {
+        HIP_TRY(hipStreamSynchronize(r->stream));      // (an earlier update may still read the old buffer)
+        if (f.d_def) HIP_TRY(hipFree(f.d_def));
+        f.d_def = nullptr; f.d_def_cap = 0;
+        HIP_TRY(hipMalloc((void**)&f.d_def, up_bytes));
+        f.d_def_cap = up_bytes;
+    }
+    uint8_t* h_pos = f.h_def; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes;
+    memcpy(h_pos, pos4, pos_bytes);
+    if (attrs) {
+        memcpy(h_attr, attrs, attr_bytes);
+        float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
+        for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
+    }
+    if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
+    if (attrs) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
+    if (up_bytes) HIP_TRY(hipMemcpyAsync(f.d_def, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipEventRecord(f.ev_def, r->stream));
+    f.def_pending = true;
+    if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
+    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.d_def), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+                 f.d_pos, attrs ? reinterpret_cast<const float4*>(f.d_def + rec_bytes) : nullptr, f.d_slot_of};
+    HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
+    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
+    return refit_levels(r);
+}
+int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    if (!r) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null");
+    if (r->failed) return fail(FRT_ERR_STATE, "set_mesh_vertices: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
+    if (r->frame_open) return fail(FRT_ERR_STATE, "set_mesh_vertices: a frame is open (call it between frames)");
+    if (!r->rf.ok) return fail(FRT_ERR_STATE, "set_mesh_vertices: the scene's trees are not numbered breadth-first");
+#if FRT_EXPERIMENTS
+    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: this renderer walks the 8-wide tree or the quantized pair nodes, which are not refit");
+#endif
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
+    const int rc = set_mesh_vertices_impl(r, mesh_id, pos4, attrs, nverts);
     if (rc == FRT_ERR_HIP) r->failed = true;
     return rc;
 }
@@ -1518,7 +1617,8 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
         if (r->rbt.done) return fail(FRT_ERR_STATE, "read_scene: the pair tree is not rebuilt by frt_renderer_rebuild_tree and no longer describes the replica");
         src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
     case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16)");
+    case 17: src = sv.shade_tris; bytes = (size_t)sv.num_tris * sizeof(ShadeTri); break;
+    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16, 17)");
     }
     FRT_DEVICE(r);
     { int rc = sync_all(r); if (rc) return rc; }

@@ -379,6 +379,41 @@ int SceneBuilder::set_instance_transforms(uint32_t n, const uint32_t* ids, const
     return FRT_OK;
 }
 
+std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t mesh_nverts) {
+    if (!pos4) return "null positions";
+    if (nverts != mesh_nverts) return std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(mesh_nverts) + " (the topology is fixed)";
+    for (size_t k = 0; k < (size_t)nverts * 4; ++k) if (!std::isfinite(pos4[k])) return "position of vertex " + std::to_string(k / 4) + " is not finite";
+    if (attrs) {
+        const float* a = reinterpret_cast<const float*>(attrs);
+        for (size_t k = 0; k < (size_t)nverts * 8; ++k) if (!std::isfinite(a[k])) return "attributes of vertex " + std::to_string(k / 8) + " are not finite";
+    }
+    return "";
+}
+
+int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    if (!built) { error = "set_mesh_vertices: scene is not built"; return FRT_ERR_STATE; }
+    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    const std::string bad = check_mesh_vertices(pos4, attrs, nverts, (uint32_t)(mesh_positions[mesh_id].size() / 4));
+    if (!bad.empty()) { error = "set_mesh_vertices: " + bad; return FRT_ERR_INVALID_ARG; }
+    mesh_positions[mesh_id].assign(pos4, pos4 + (size_t)nverts * 4);
+    if (attrs) std::copy(attrs, attrs + nverts, attributes.begin() + mesh_infos[mesh_id].vertex_offset);
+    const float* P = mesh_positions[mesh_id].data();
+    const uint32_t* idx = &indices[mesh_infos[mesh_id].index_offset];
+    for (InstanceRec& in : instances) {      // in instance order, under each instance's current matrix
+        if (in.mesh_id != mesh_id) continue;
+        for (uint32_t j = 0; j < in.tri_count; ++j) {
+            const uint32_t id = in.first_tri + j;
+            TriRec& t = tris[id];
+            world_triangle(in.m, P, idx + 3 * j, t);
+            TriSlot& o = tri_slots[tri_slot_of[id]];      // same slot, id and instance bits
+            for (int r = 0; r < 3; ++r) { o.q[r] = t.v0[r]; o.q[4 + r] = t.e1[r]; o.q[8 + r] = t.e2[r]; }
+            if (attrs) write_shade_tri(id);
+        }
+    }
+    refit();
+    return FRT_OK;
+}
+
 void SceneBuilder::build() {
     error.clear();
     // Texture layers and light indices reach the kernels unchecked (sample_layer: base + layer * 4 MiB): validate them here, once.

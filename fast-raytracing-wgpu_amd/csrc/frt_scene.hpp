@@ -96,6 +96,10 @@ public:
     // registered lights recomputed as build() computes them, every box refit. The specification the device refit matches bit for bit.
     // Returns an FRT_ERR_* code with `error` set, or FRT_OK.
     int set_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats);
+    // New vertices for one mesh of a built scene ("Deforming meshes"): the same topology, tree and leaf order; the triangles of
+    // every instance of the mesh recomputed under its current matrix and, when `attrs` is given, their shading records as build() computes them;
+    // every box refit. attrs == nullptr keeps the attributes and the shading records. The specification the device path matches bit for bit.
+    int set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
 
     // SceneResources-equivalent host data (src/scene/resources.rs:10-22)
     std::vector<frt_material> materials;
@@ -138,6 +142,7 @@ private:
     void refit();
     void build_bvh2();
     void build_gpu_layout();
+    void write_shade_tri(uint32_t id);      // shade_tris[id] from the attributes of its three corners and its instance's material
 };
 
 // Derived data of one instance transform, as flatten() computes it: world_to_object by cofactors in double, rounded once to f32, and the
@@ -150,6 +155,11 @@ frt_light quad_light_record(const Mat4& t, const float emission[4]);
 frt_light sphere_light_record(const Mat4& t, const float emission[4]);
 // Argument checks shared by the scene and the renderer form of set_instance_transforms: "" when (n, ids, mats) may be applied.
 std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const float* mats, size_t num_instances);
+// Argument checks shared by the scene and the renderer form of set_mesh_vertices: "" when the vertices may be applied to a mesh of
+// `mesh_nverts` vertices (mesh_id < num_meshes is checked by the caller, which looks that count up).
+std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t mesh_nverts);
+// The decoded normal a shading record holds for a vertex with these attributes (frt_shade.hpp: decode_octahedral_normal, compiled for the host).
+void decoded_vertex_normal(const frt_vertex_attr& a, float out[3]);
 
 namespace scenes {
 void create_cornell_box(SceneBuilder& b);    // scenes.rs:9-130

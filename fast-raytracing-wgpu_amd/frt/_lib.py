@@ -101,6 +101,7 @@ SYMBOLS = {
     "frt_scene_bvh_stats": (C.c_int, [_P, _P]),
     "frt_scene_tree_stats": (C.c_int, [_P, _P]),
     "frt_scene_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_scene_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_camera_default": (None, [C.c_float, _U32, _U32, C.POINTER(CameraUniform)]),
     "frt_camera_build_uniform": (C.c_int, [_P, C.c_float, C.c_float, _P, C.c_float, _U32, _U32, _P, C.POINTER(CameraUniform), _P]),
     "frt_camera_halton_jitter": (None, [_U32, _U32, _U32, C.c_float, _P]),
@@ -129,6 +130,7 @@ SYMBOLS = {
     "frt_renderer_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "frt_renderer_set_timing": (C.c_int, [_P, C.c_int]),
     "frt_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_renderer_read_scene": (C.c_int, [_P, C.c_int, _P]),
     "frt_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
@@ -151,6 +153,7 @@ SYMBOLS = {
     "frt_multi_renderer_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "frt_multi_renderer_boundaries": (C.c_int, [_P, _P]),
     "frt_multi_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_multi_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
 }

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM)
-from .scene import transform_args
+from .scene import transform_args, mesh_vertex_args
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -138,6 +138,12 @@ class Renderer:
     def set_instance_transform(self, instance_id, transform_colmajor):
         self.set_instance_transforms([instance_id], [transform_colmajor])
 
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
+        """Deform one mesh in this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_vertices): asynchronous, on the
+        renderer's streams; the arrays are copied during the call. The host scene is not changed (SceneBuilder.set_mesh_vertices is its own call)."""
+        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
+        check(lib().frt_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+
     def rebuild_tree(self, quality="morton"):
         """Build a new quad tree over the replica's triangles as they are now, on the device (include/frt.h: frt_renderer_rebuild_tree): synchronous,
         between frames; pixels, accumulation and reservoirs are untouched. The host scene keeps its own tree. quality: "morton", the plain
@@ -161,11 +167,11 @@ class Renderer:
         return {"quad_nodes": int(s[0]), "quad_stack_need": int(s[1]), "quad_levels": int(s[2]), "origin": int(s[3])}
 
     def read_scene(self, what):
-        """The device replica in SceneBuilder.get's layout: "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev" (syncs first)."""
+        """The device replica in SceneBuilder.get's layout: "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev", "shade_tris" (syncs first)."""
         n = self._scene.counts()
         which, shape, dt = {"lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
                             "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
-                            "instances_dev": (16, (n["instances"], 16), np.uint32)}[what]
+                            "instances_dev": (16, (n["instances"], 16), np.uint32), "shade_tris": (17, (n["tris"], 32), np.float32)}[what]
         out = np.zeros(shape, dt)
         check(lib().frt_renderer_read_scene(self._h, which, out.ctypes.data))
         return out
@@ -250,6 +256,11 @@ class MultiRenderer:
         """Renderer.set_instance_transforms on every strip's scene replica."""
         n, i, m = transform_args(ids, transforms_colmajor)
         check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
+        """Renderer.set_mesh_vertices on every strip's scene replica."""
+        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
+        check(lib().frt_multi_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
 
     def rebuild_tree(self, quality="morton"):
         """Renderer.rebuild_tree on every strip's scene replica."""

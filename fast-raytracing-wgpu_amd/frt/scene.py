@@ -24,6 +24,22 @@ def transform_args(ids, transforms_colmajor):
     return ids.size, ids.astype(np.uint32), m
 
 
+def mesh_vertex_args(mesh_id, positions, attributes):
+    """(mesh id, positions, attributes or None, vertex count) for the *_set_mesh_vertices calls: `positions` [n, 4] (xyzw, as frt.geometry
+    writes them), `attributes` [n, 8] (octahedral normal, uv, tangent) or None to keep the mesh's attributes."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    pos = np.ascontiguousarray(positions, np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 4:
+        raise FrtError("positions must be shaped [n, 4]")
+    att = None
+    if attributes is not None:
+        att = np.ascontiguousarray(attributes, np.float32).reshape(-1, 8)
+        if att.shape[0] != pos.shape[0]:
+            raise FrtError(f"{pos.shape[0]} positions but {att.shape[0]} attribute records")
+    return int(mesh_id), pos, att, pos.shape[0]
+
+
 class SceneBuilder:
     def __init__(self, handle=None):
         self._destroy = lib().frt_scene_destroy
@@ -105,6 +121,12 @@ class SceneBuilder:
     def set_instance_transform(self, instance_id, transform_colmajor):
         return self.set_instance_transforms([instance_id], [transform_colmajor])
 
+    # Deform one mesh of the built scene: same topology and tree, refit boxes (include/frt.h: frt_scene_set_mesh_vertices). Host copy only.
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
+        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
+        check(lib().frt_scene_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+        return self
+
     # ---- introspection
     def counts(self):
         c = (C.c_uint32 * 8)()
@@ -134,7 +156,8 @@ class SceneBuilder:
                 "attributes": (4, (n["attributes"], 8), np.float32), "indices": (5, (n["indices"],), np.uint32),
                 "mesh_infos": (6, (n["meshes"], 4), np.uint32), "instances": (7, (n["instances"], 30), np.uint32),
                 "bvh2_nodes": (8, (n["bvh2_nodes"], 8), np.uint32), "bvh2_tri_index": (9, (n["tris"],), np.uint32),
-                "pair_nodes": (15, (self.bvh_stats()["pair_nodes"], 16), np.float32), "instances_dev": (16, (n["instances"], 16), np.uint32)}[what]
+                "pair_nodes": (15, (self.bvh_stats()["pair_nodes"], 16), np.float32), "instances_dev": (16, (n["instances"], 16), np.uint32),
+                "shade_tris": (17, (n["tris"], 32), np.float32)}[what]
         out = np.zeros(spec[1], spec[2])
         check(lib().frt_scene_get(self._h, spec[0], out.ctypes.data))
         return out

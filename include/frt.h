@@ -139,7 +139,9 @@ int frt_scene_counts(const frt_scene* s, uint32_t counts[8]);
  * the device forms of the tree (frt_scene_tree_stats gives the counts): 10 quad nodes (128 B), 11 8-wide compressed nodes (128 B, csrc/frt_bvh8.hpp),
  * 12 triangle slots in the 8-wide tree's order (48 B: v0, id; e1, instance; e2, 0), 13 triangle slots in BVH2 leaf order (48 B),
  * 14 the float boxes behind the 8-wide nodes' grid boxes (192 B per node: 8 x lo.xyz, hi.xyz; host data for tools/bvh_quality.cpp),
- * 15 pair nodes (64 B; frt_scene_bvh_stats gives the count), 16 device instance records (64 B: mesh, mat, first_tri, flip u32; w2o[9] f32; 3 pad) */
+ * 15 pair nodes (64 B; frt_scene_bvh_stats gives the count), 16 device instance records (64 B: mesh, mat, first_tri, flip u32; w2o[9] f32; 3 pad),
+ * 17 shading records (128 B per flattened triangle id, 8 x float4: (n0.xyz, uv0.x) (n1.xyz, uv0.y) (n2.xyz, uv1.x) (t0.xyz, uv1.y) (t1.xyz, uv2.x)
+ * (t2.xyz, uv2.y) (tangent sign, material id, 0, 0) (0, 0, 0, 0); normals decoded from their octahedral form) */
 int frt_scene_get(const frt_scene* s, int which, void* out);
 /* Move instances of a BUILT scene: instance ids[k] gets the column-major matrix m_colmajor16[16k .. 16k+15]. The tree
  * keeps its topology and leaf order; the moved instances' triangles, their device instance records and the lights registered with them
@@ -148,6 +150,14 @@ int frt_scene_get(const frt_scene* s, int which, void* out);
  * replica moves with frt_renderer_set_instance_transforms). FRT_ERR_STATE: scene not built; FRT_ERR_INVALID_ARG: an id out of range, a
  * non-finite entry, a singular 3x3 (nothing is changed then). The 8-wide tree (selectors 11, 12, 14) is made again from the refit tree. */
 int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* Deform one mesh of a BUILT scene ("Deforming meshes"): new object-space positions (xyzw per vertex) and, unless attrs is
+ * NULL, new attributes for every vertex of mesh `mesh_id`. The topology is fixed: nverts must be the mesh's vertex count, the indices stay. The
+ * triangles of every instance of the mesh are recomputed under the instance's current matrix, in their slots; with attrs their shading records
+ * (selector 17) are recomputed as frt_scene_build computes them, with attrs == NULL attributes and shading records stay as they are. Every box is
+ * refit; instance records and lights do not change (a registered light follows its transform, not its mesh). Afterwards the scene equals one
+ * built from scratch with the new vertices. Host copy only, as frt_scene_set_instance_transforms. FRT_ERR_STATE: scene not built;
+ * FRT_ERR_INVALID_ARG, nothing changed: mesh id out of range, nverts not the mesh's count, pos4 NULL, a non-finite position or attribute float. */
+int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
 /* stats[8]: quad nodes, deepest traversal stack of the quad tree, 8-wide nodes (0: the scene has no 8-wide tree: more than 65,536 nodes), deepest stack of
  * the 8-wide tree, its levels, sum of its nodes' child counts, its triangle slots, how the quad tree was folded (2 surface-area programme, 1 programme where
  * the traversal-stack bound allows and the greedy fold elsewhere, 0 greedy fold) */
@@ -303,6 +313,13 @@ int frt_renderer_set_timing(frt_renderer* r, int on);
  * frt_renderer_reset / _clear; motion vectors stay camera-only). FRT_ERR_STATE between the phases of an open frame; FRT_ERR_INVALID_ARG for a
  * renderer whose kernels walk a tree that is not refit (experiments build: FRT_FLAG_WALK_WIDE / _HBM with an 8-wide tree, the resident kernels). */
 int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* Deform one mesh of this renderer's scene replica between two frames: arguments, checks and result of frt_scene_set_mesh_vertices, computed on the
+ * device (the new vertices copied up, one kernel that rewrites the triangle slots and shading records of every instance of the mesh, the refit of
+ * frt_renderer_set_instance_transforms). The inputs are copied during the call (the caller's arrays may be reused at once). Ordering, state rules
+ * and refused renderers are those of frt_renderer_set_instance_transforms: asynchronous, behind every kernel that reads the scene, FRT_ERR_STATE
+ * while a frame is open, a frame that ran ahead under the old geometry dropped and redone, accumulation, reservoirs and frame_count kept. Works on
+ * a tree made by frt_renderer_rebuild_tree too, and later frt_renderer_set_instance_transforms calls transform the new vertices. */
+int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
 /* Build a new quad tree over the triangle slots as they are on the device now, i.e. after any number of frt_renderer_set_instance_transforms calls, whose
  * refit keeps the topology and so loses quality after large moves ("Rebuild"): Morton order, leaves of two adjacent slots, a binary
  * radix tree folded into quad nodes, boxes by the refit kernel; all on the device, into a second set of buffers that is swapped in only on success. Hits are
@@ -331,7 +348,7 @@ int frt_renderer_tree_stats(frt_renderer* r, uint32_t stats[4]);
  * built instead (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added. Zeros before any rebuild. */
 int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t stats[4]);
 /* Read the device replica back (syncs first), in the layout of frt_scene_get: 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
- * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records. */
+ * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 
 /* ---- N GPUs behind one call (`ngpus`; section 8e) -----------------------------------------------------------------
@@ -376,6 +393,8 @@ int frt_multi_renderer_stats(frt_multi_renderer* m, frt_stats* out);            
 int frt_multi_renderer_boundaries(const frt_multi_renderer* m, uint32_t* rows_out);               /* ndev + 1 row indices; returns ndev */
 /* frt_renderer_set_instance_transforms on every strip's replica, between frames */
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* frt_renderer_set_mesh_vertices on every strip's replica, between frames */
+int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
 /* frt_renderer_rebuild_tree on every strip's replica, between frames (synchronous) */
 int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m);
 /* frt_renderer_rebuild_tree_ex on every strip's replica */
