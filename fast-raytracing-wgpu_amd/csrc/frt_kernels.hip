@@ -49,15 +49,7 @@ __device__ __forceinline__ void flush_ray_counters(const FrameView& fv, uint32_t
     }
 }
 
-// The top of the quad tree — nodes 0 .. kLdsTopNodes - 1: the root and, numbered breadth-first, its children — copied into the workgroup's LDS, in the
-// row of the stack array that no stack entry reaches (behind the shared words): the first two node steps of every walk read it there (frt_trace.hpp:
-// trace4). Call before the workgroup's first barrier; null for a tree too small to have those nodes.
-__device__ __forceinline__ const uint32_t* stage_top_nodes(const SceneView& sc, uint32_t* s_cnt) {
-    uint32_t* const s_top = s_cnt + 32;      // (128-byte aligned)
-    if (sc.num_nodes4 < (uint32_t)kLdsTopNodes) return nullptr;
-    if (threadIdx.x < (uint32_t)kLdsTopNodes * 32u) s_top[threadIdx.x] = reinterpret_cast<const uint32_t*>(sc.nodes4)[threadIdx.x];
-    return s_top;
-}
+// (stage_top_nodes, the LDS copy of the quad tree's top that the quad walks read, is in frt_kernels.hpp: the ray-query kernels stage it too)
 
 // The whole 8-wide tree copied into the workgroup's dynamic LDS (kWalkWideLds): every node step of every walk then reads its node at the LDS's
 // latency and leaves the L1 to the triangles. Call before the workgroup's first barrier.

@@ -32,6 +32,16 @@ struct TraceLaunch {
     uint32_t* work;   // 2 x (1 + kMaxCuts) words: {next, ticket} of the pixel launch, then of each continuation launch; zero between launches
 #endif
 };
+// The top of the quad tree — nodes 0 .. kLdsTopNodes - 1: the root and, numbered breadth-first, its children — copied into the workgroup's LDS, in the
+// row of the stack array that no stack entry reaches (behind the shared words): the first two node steps of every walk read it there (frt_trace.hpp:
+// trace4). Call before the workgroup's first barrier; null for a tree too small to have those nodes.
+__device__ __forceinline__ const uint32_t* stage_top_nodes(const SceneView& sc, uint32_t* s_cnt) {
+    uint32_t* const s_top = s_cnt + 32;      // (128-byte aligned)
+    if (sc.num_nodes4 < (uint32_t)kLdsTopNodes) return nullptr;
+    if (threadIdx.x < (uint32_t)kLdsTopNodes * 32u) s_top[threadIdx.x] = reinterpret_cast<const uint32_t*>(sc.nodes4)[threadIdx.x];
+    return s_top;
+}
+
 // All launches are asynchronous on `stream` and cover rows [fv.y0, fv.y1).
 hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t walk = kWalkQuad);      // walk: kWalkQuad or kWalkWide (primary rays are coherent: their nodes stay in HBM / L1)
 hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream, const TraceLaunch& L);

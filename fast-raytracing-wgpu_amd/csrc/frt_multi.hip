@@ -490,6 +490,26 @@ int frt_multi_renderer_set_jitter(frt_multi_renderer* m, float jx, float jy) {
     return frt_renderer_set_jitter(m->strips[0].r, jx, jy);
 }
 
+// Ray queries: every strip's replica is the whole scene and all are equal, so the first strip answers. Host-pointer form only.
+static int multi_query_check(const frt_multi_renderer* m, uint32_t flags, const char* what) {
+    if (!m || m->strips.empty()) return set_error(FRT_ERR_INVALID_ARG, std::string(what) + ": null");
+    if (flags != 0u) return set_error(FRT_ERR_INVALID_ARG, std::string(what) + ": only the host-pointer form (flags = 0) is offered on a multi renderer");
+    if (m->failed) return set_error(FRT_ERR_STATE, std::string(what) + ": the handle is failed; call frt_multi_renderer_clear");
+    return FRT_OK;
+}
+int frt_multi_renderer_trace_closest(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags) {
+    const int rc = multi_query_check(m, flags, "multi trace_closest");
+    return rc ? rc : frt_renderer_trace_closest(m->strips[0].r, n, rays, out, 0u);
+}
+int frt_multi_renderer_trace_any(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags) {
+    const int rc = multi_query_check(m, flags, "multi trace_any");
+    return rc ? rc : frt_renderer_trace_any(m->strips[0].r, n, rays, occluded_out, 0u);
+}
+int frt_multi_renderer_pick(frt_multi_renderer* m, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags) {
+    const int rc = multi_query_check(m, flags, "multi pick");
+    return rc ? rc : frt_renderer_pick(m->strips[0].r, cam, n, xy, out, 0u);
+}
+
 int frt_multi_renderer_inject_failure(frt_multi_renderer* m, uint32_t strip, int step) {
     if (!m || strip >= m->strips.size() || (step != 0 && step != 1)) return set_error(FRT_ERR_INVALID_ARG, "multi inject_failure: bad arguments");
     m->inject_strip = (int)strip; m->inject_step = step;

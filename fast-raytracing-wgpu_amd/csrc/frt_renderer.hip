@@ -6,6 +6,7 @@
 #include "frt_refit.hpp"
 #include "frt_rebuild.hpp"
 #include "frt_deform.hpp"
+#include "frt_query.hpp"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cstdio>
@@ -142,6 +143,13 @@ struct RebuildState {
     uint64_t device_bytes = 0;
 };
 
+// Staging of the host-pointer ray queries: one pinned block and one device block, each [input | output] of a call; grown on demand,
+// never shrunk. A host-pointer call is synchronous, so neither needs an event: the last call's copies are done when the next one starts.
+struct QueryState {
+    uint8_t* h = nullptr; size_t h_cap = 0;
+    uint8_t* d = nullptr; size_t d_cap = 0;
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -205,6 +213,7 @@ struct frt_renderer {
     uint64_t serial = 0;                   // frames finished since creation (never reset: parity of the per-frame events)
     RefitState rf;
     RebuildState rbt;
+    QueryState qry;
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };
@@ -651,6 +660,8 @@ void frt_renderer_destroy(frt_renderer* r) {
     if (r->rf.d_def) (void)hipFree(r->rf.d_def);
     if (r->rf.h_def) (void)hipHostFree(r->rf.h_def);
     if (r->rf.ev_def) (void)hipEventDestroy(r->rf.ev_def);
+    if (r->qry.d) (void)hipFree(r->qry.d);
+    if (r->qry.h) (void)hipHostFree(r->qry.h);
     if (r->own_arena && r->arena) (void)hipFree(r->arena);
     if (r->extras) (void)hipFree(r->extras);
     if (r->d_counters) (void)hipFree(r->d_counters);
@@ -1594,6 +1605,80 @@ int frt_renderer_rebuild_tree_ex(frt_renderer* r, uint32_t mode) {
     if (rc == FRT_ERR_HIP) r->failed = true;
     return rc;
 }
+// ------------------------------------------------------------------------------------------------ ray queries
+// Ordering: a query is enqueued on the main stream and only reads the scene replica. Every writer of the replica is on that stream too: the instance
+// update and the deformation (their copies, kernels and refit levels; the ahead stream is fenced into the main stream before them), and the rebuild,
+// whose kernels run there and which waits for the stream before it swaps the buffers — so the buffers a rebuild builds into are the ones that left the
+// replica at the previous rebuild's wait, behind which no query can read them, and a query enqueued after the swap reads the new ones. The frame's
+// own kernels on the other streams read the scene as well and write none of it. Nothing here touches frame state, counters, queues or a speculation.
+enum { kQueryClosest = 0, kQueryAny = 1, kQueryPick = 2 };
+static int query_impl(frt_renderer* r, int kind, const frt_camera_uniform* cam, uint32_t n, const void* in, void* out, uint32_t flags, const char* what) {
+    const std::string w(what);
+    if (!r) return fail(FRT_ERR_INVALID_ARG, w + ": null renderer");
+    if (flags & ~FRT_QUERY_DEVICE) return fail(FRT_ERR_INVALID_ARG, w + ": unknown flag (FRT_QUERY_DEVICE)");
+    if (n > kQueryMaxRays) return fail(FRT_ERR_INVALID_ARG, w + ": more than 2^26 rays in one call");
+#if FRT_EXPERIMENTS
+    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident || (r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill)
+        return fail(FRT_ERR_INVALID_ARG, w + ": this renderer's kernels do not walk the quad tree, which is the tree a query walks");
+#endif
+    if (n == 0) return FRT_OK;
+    if (!in || !out || (kind == kQueryPick && !cam)) return fail(FRT_ERR_INVALID_ARG, w + ": null pointer");
+    if (r->failed) return fail(FRT_ERR_STATE, w + ": an earlier frame failed in the middle of its stages; call frt_renderer_clear");
+    const size_t in_bytes = (size_t)n * (kind == kQueryPick ? 8u : 32u), out_bytes = (size_t)n * (kind == kQueryAny ? 1u : 32u);
+    CameraView cv{};
+    if (kind == kQueryPick) memcpy(&cv, cam, sizeof(cv));
+    auto launch = [&](const void* d_in, void* d_out) {
+        // (vote and wg_rows as they are NOW: a rebuild changes both with the tree)
+        if (kind == kQueryClosest) return launch_query_closest(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
+        if (kind == kQueryAny) return launch_query_any(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
+        return launch_query_pick(r->sv, r->vote, r->wg_rows, cv, r->W, r->H, n, d_in, d_out, r->stream);
+    };
+    if (flags & FRT_QUERY_DEVICE) {
+        if (((uintptr_t)in & 15u) || (kind != kQueryAny && ((uintptr_t)out & 15u))) return fail(FRT_ERR_INVALID_ARG, w + ": device pointers must be 16-byte aligned");
+        FRT_DEVICE(r);
+        HIP_TRY(launch(in, out));
+        return FRT_OK;
+    }
+    if (kind == kQueryPick) {
+        const uint32_t* xy = static_cast<const uint32_t*>(in);
+        for (uint32_t k = 0; k < n; ++k)
+            if (xy[2 * (size_t)k] >= r->W || xy[2 * (size_t)k + 1] >= r->H)
+                return fail(FRT_ERR_INVALID_ARG, w + ": pixel (" + std::to_string(xy[2 * (size_t)k]) + ", " + std::to_string(xy[2 * (size_t)k + 1]) + ") is outside the " +
+                                                     std::to_string(r->W) + " x " + std::to_string(r->H) + " frame");
+    }
+    FRT_DEVICE(r);
+    QueryState& q = r->qry;
+    const size_t out_at = (in_bytes + 255u) & ~(size_t)255u, all_bytes = out_at + out_bytes;
+    if (q.h_cap < all_bytes) {
+        if (q.h) HIP_TRY(hipHostFree(q.h));
+        q.h = nullptr; q.h_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&q.h, all_bytes));
+        q.h_cap = all_bytes;
+    }
+    if (q.d_cap < all_bytes) {
+        if (q.d) HIP_TRY(hipFree(q.d));
+        q.d = nullptr; q.d_cap = 0;
+        HIP_TRY(hipMalloc((void**)&q.d, all_bytes));
+        q.d_cap = all_bytes;
+    }
+    memcpy(q.h, in, in_bytes);
+    HIP_TRY(hipMemcpyAsync(q.d, q.h, in_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch(q.d, q.d + out_at));
+    HIP_TRY(hipMemcpyAsync(q.h + out_at, q.d + out_at, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    memcpy(out, q.h + out_at, out_bytes);
+    return FRT_OK;
+}
+int frt_renderer_trace_closest(frt_renderer* r, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags) {
+    return query_impl(r, kQueryClosest, nullptr, n, rays, out, flags, "trace_closest");
+}
+int frt_renderer_trace_any(frt_renderer* r, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags) {
+    return query_impl(r, kQueryAny, nullptr, n, rays, occluded_out, flags, "trace_any");
+}
+int frt_renderer_pick(frt_renderer* r, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags) {
+    return query_impl(r, kQueryPick, cam, n, xy, out, flags, "pick");
+}
+
 int frt_renderer_tree_stats(frt_renderer* r, uint32_t st[4]) {
     if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer tree_stats: null");
     st[0] = r->sv.num_nodes4; st[1] = r->wg_rows > 0u ? r->wg_rows - 1u : 0u;

@@ -360,19 +360,27 @@ FRT_HD ReservoirView zero_reservoir() { ReservoirView r; r.y = 0u; r.w_sum = 0.0
 
 // ================================================================================================ stage 0
 // gbuffer.wgsl:91-255
+// The primary ray of pixel (px, py) of a W x H frame, gbuffer.wgsl:96-106. Shared by the G-buffer stage and frt_renderer_pick (frt_query.hip), which
+// trace it over the same range, so that a picked hit IS the G-buffer's hit.
+static constexpr float kPrimaryTmin = 0.001f, kPrimaryTmax = 1000.0f;   // gbuffer.wgsl:108
+FRT_HD void primary_ray(const CameraView& cam, uint32_t W, uint32_t H, uint32_t px, uint32_t py, f3& origin, f3& direction) {
+    f2 size = mk2((float)W, (float)H);
+    f2 uv = (mk2((float)px, (float)py) + mk2(0.5f, 0.5f)) / size;
+    f2 ndc = mk2(uv.x * 2.0f - 1.0f, 1.0f - uv.y * 2.0f);
+    m4 view_inv = load_m4(cam.view_inverse), proj_inv = load_m4(cam.proj_inverse);
+    origin = xyz(view_inv.c[3]);
+    f4 target = mul(mul(view_inv, proj_inv), mk4(ndc.x, ndc.y, 1.0f, 1.0f));   // (view_inv * proj_inv) * v, :104
+    direction = normalize(xyz(target) / target.w - origin);
+}
+
 template <class Ctx>
 FRT_HD void gbuffer_pixel(Ctx& c, uint32_t px, uint32_t py) {
     const SceneView& sc = c.sc; const FrameView& fv = c.fv;
     uint32_t pix = py * fv.W + px;
-    f2 size = mk2((float)fv.W, (float)fv.H);
-    f2 uv = (mk2((float)px, (float)py) + mk2(0.5f, 0.5f)) / size;
-    f2 ndc = mk2(uv.x * 2.0f - 1.0f, 1.0f - uv.y * 2.0f);
-    m4 view_inv = load_m4(fv.cam.view_inverse), proj_inv = load_m4(fv.cam.proj_inverse);
-    f3 origin = xyz(view_inv.c[3]);
-    f4 target = mul(mul(view_inv, proj_inv), mk4(ndc.x, ndc.y, 1.0f, 1.0f));   // (view_inv * proj_inv) * v, :104
-    f3 direction = normalize(xyz(target) / target.w - origin);
+    f3 origin, direction;
+    primary_ray(fv.cam, fv.W, fv.H, px, py, origin, direction);
     HitRec h;
-    c.closest(origin, direction, 0.001f, 1000.0f, h);
+    c.closest(origin, direction, kPrimaryTmin, kPrimaryTmax, h);
     if (h.tri == 0xFFFFFFFFu) {
         fv.gpos[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         fv.gnormal[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);

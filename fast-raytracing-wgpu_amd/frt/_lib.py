@@ -45,6 +45,16 @@ class Stats(C.Structure):
                 ("speculated_frames", C.c_uint64), ("discarded_speculations", C.c_uint64), ("queue_bytes", C.c_uint64)]
 
 
+class Ray(C.Structure):             # include/frt.h: frt_ray
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("dir", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class RayHit(C.Structure):          # include/frt.h: frt_ray_hit
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("tri", C.c_uint32), ("instance", C.c_uint32), ("material", C.c_uint32),
+                ("primitive", C.c_uint32), ("front", C.c_uint32)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(VertexAttr) == 32 and C.sizeof(Material) == 64 and C.sizeof(Light) == 64 and C.sizeof(CameraUniform) == 288
 
 FLAG_TIMING = 1
@@ -56,6 +66,8 @@ FLAG_WALK_WIDE = 32
 FLAG_WALK_WIDE_HBM = 64
 FLAG_WG_TRACE = 128
 FLAG_OVERLAP_POST = FLAG_PIPELINE      # round-1 name
+QUERY_DEVICE = 1                       # include/frt.h: FRT_QUERY_DEVICE
+QUERY_MAX_RAYS = 1 << 26
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
 PHASE_SPATIAL_INNER, PHASE_SPATIAL_EDGE = 16, 32
 BUF_GPOS, BUF_GNORMAL, BUF_GALBEDO, BUF_GMOTION, BUF_RESERVOIR, BUF_RAW, BUF_DISPLAY, BUF_ACCUM, BUF_CANDIDATE = range(9)
@@ -102,6 +114,8 @@ SYMBOLS = {
     "frt_scene_tree_stats": (C.c_int, [_P, _P]),
     "frt_scene_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_scene_trace_closest": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_scene_trace_any": (C.c_int, [_P, _U32, _P, _P]),
     "frt_camera_default": (None, [C.c_float, _U32, _U32, C.POINTER(CameraUniform)]),
     "frt_camera_build_uniform": (C.c_int, [_P, C.c_float, C.c_float, _P, C.c_float, _U32, _U32, _P, C.POINTER(CameraUniform), _P]),
     "frt_camera_halton_jitter": (None, [_U32, _U32, _U32, C.c_float, _P]),
@@ -136,6 +150,9 @@ SYMBOLS = {
     "frt_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
     "frt_renderer_rebuild_stats": (C.c_int, [_P, _P]),
     "frt_renderer_tree_stats": (C.c_int, [_P, _P]),
+    "frt_renderer_trace_closest": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_renderer_trace_any": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_renderer_pick": (C.c_int, [_P, C.POINTER(CameraUniform), _U32, _P, _P, _U32]),
     "frt_multi_renderer_create": (_P, [_P, _U32, _U32, _U32, _P, C.POINTER(RenderOpts)]),
     "frt_multi_renderer_destroy": (None, [_P]),
     "frt_multi_renderer_render": (C.c_int, [_P, C.POINTER(CameraUniform)]),
@@ -156,6 +173,9 @@ SYMBOLS = {
     "frt_multi_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
+    "frt_multi_renderer_trace_closest": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_multi_renderer_trace_any": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_multi_renderer_pick": (C.c_int, [_P, C.POINTER(CameraUniform), _U32, _P, _P, _U32]),
 }
 
 _lib = None

@@ -1,8 +1,8 @@
 """Renderer mirror (src/renderer.rs) over frt_renderer_*. Every pixel is produced by the HIP kernels in libfrt.so."""
 import ctypes as C
 import numpy as np
-from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM)
-from .scene import transform_args, mesh_vertex_args
+from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
+from .scene import transform_args, mesh_vertex_args, ray_args, hits_dict, pixel_args, HIT_FIELDS
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -14,7 +14,47 @@ def rebuild_mode(quality):
     return REBUILD_MODES[quality]
 
 
-class Renderer:
+def _is_device_tensor(x):
+    """A torch tensor in device memory (torch is only imported by callers that pass one)."""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "is_cuda") and x.is_cuda
+
+
+class _HostQueries:
+    """trace_closest / trace_any / pick over a handle's host-pointer entry points (numpy in, numpy out); Renderer and MultiRenderer name theirs."""
+    _trace_closest = _trace_any = _pick = None
+
+    def _host_trace_closest(self, origins, dirs, tmin, tmax):
+        rays = ray_args(origins, dirs, tmin, tmax)
+        out = np.zeros((rays.shape[0], 8), np.uint32)
+        check(getattr(lib(), self._trace_closest)(self._h, rays.shape[0], rays.ctypes.data, out.ctypes.data, 0))
+        return hits_dict(out)
+
+    def _host_trace_any(self, origins, dirs, tmin, tmax):
+        rays = ray_args(origins, dirs, tmin, tmax)
+        out = np.zeros(rays.shape[0], np.uint8)
+        check(getattr(lib(), self._trace_any)(self._h, rays.shape[0], rays.ctypes.data, out.ctypes.data, 0))
+        return out.astype(bool)
+
+    def _host_pick(self, camera_uniform, xy):
+        p = pixel_args(xy, self.width, self.height)
+        out = np.zeros((p.shape[0], 8), np.uint32)
+        check(getattr(lib(), self._pick)(self._h, C.byref(camera_uniform), p.shape[0], p.ctypes.data, out.ctypes.data, 0))
+        return hits_dict(out)
+
+
+def _hit_views(hits):
+    """Named views of an [n, 8] int32 tensor of frt_ray_hit records (no copies, no kernels beyond torch's view bookkeeping)."""
+    import torch
+    f = hits.view(torch.float32)
+    d = {"hits": hits}
+    for k, name in enumerate(HIT_FIELDS):
+        d[name] = (f if k < 3 else hits)[:, k]
+    return d
+
+
+class Renderer(_HostQueries):
+    _trace_closest, _trace_any, _pick = "frt_renderer_trace_closest", "frt_renderer_trace_any", "frt_renderer_pick"
+
     def __init__(self, scene, width, height, max_depth=8, device=0, stream=None, rows=None, arena=None, arena_bytes=0, flags=0, motion_halo=0,
                  queue_capacity=0, cuts=None):
         """Renderer::new (renderer.rs:206). rows=(begin,end) restricts this renderer to an image strip; motion_halo = rows of
@@ -34,6 +74,7 @@ class Renderer:
         if arena is not None:
             o.device_arena, o.arena_bytes = arena, arena_bytes
         self.width, self.height = width, height
+        self.device = device
         self._scene = scene     # keep the scene alive
         self._destroy = lib().frt_renderer_destroy
         self._h = lib().frt_renderer_create(scene._h, width, height, C.byref(o))
@@ -144,6 +185,67 @@ class Renderer:
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
 
+    # ---- ray queries against the replica as it is now (include/frt.h: frt_renderer_trace_closest / _trace_any / _pick)
+    def _torch_stream(self, torch, dev):
+        h = self.stream_handle(0)
+        return torch.cuda.ExternalStream(h, device=dev) if h else torch.cuda.default_stream(dev)
+
+    def _device_rays(self, torch, origins, dirs, tmin, tmax):
+        dev = origins.device
+        o = origins.reshape(-1, 3)
+        rays = torch.empty((o.shape[0], 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3] = o
+        rays[:, 4:7] = torch.as_tensor(dirs, device=dev).reshape(-1, 3)
+        rays[:, 3] = tmin if isinstance(tmin, (int, float)) else torch.as_tensor(tmin, dtype=torch.float32, device=dev)
+        rays[:, 7] = tmax if isinstance(tmax, (int, float)) else torch.as_tensor(tmax, dtype=torch.float32, device=dev)
+        return rays
+
+    def _device_query(self, anchor, build_input, call, out_shape, out_dtype):
+        """Enqueue one query on the renderer's main stream behind the caller's current stream (a stream-level wait, no host wait): `build_input`
+        makes the input tensor there, `call` gets (n, input pointer, output pointer). Returns the output tensor; reads are the caller's to order."""
+        import torch
+        dev = anchor.device
+        if dev.index != self.device:
+            raise FrtError(f"the tensor is on {dev}, the renderer on device {self.device}")
+        s = self._torch_stream(torch, dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            inp = build_input(torch)
+            n = inp.shape[0]
+            out = torch.empty((n,) + out_shape, dtype=getattr(torch, out_dtype), device=dev)
+            check(call(n, inp.data_ptr() if n else None, out.data_ptr() if n else None))
+        return out
+
+    def trace_closest(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        """Closest hits against the device replica. numpy (or anything array-like) in: synchronous, a dict of numpy arrays as
+        SceneBuilder.trace_closest. A torch tensor on the renderer's device in: the rays are assembled on the device, the call is only enqueued on
+        the renderer's stream (stream_handle(0)) and the result is a dict of device tensors — "hits", the [n, 8] int32 records, and a view per
+        field (t, u, v float32) — that the caller reads behind that stream; nothing waits."""
+        if not _is_device_tensor(origins):
+            return self._host_trace_closest(origins, dirs, tmin, tmax)
+        hits = self._device_query(origins, lambda torch: self._device_rays(torch, origins, dirs, tmin, tmax),
+                                  lambda n, i, o: lib().frt_renderer_trace_closest(self._h, n, i, o, QUERY_DEVICE), (8,), "int32")
+        return _hit_views(hits)
+
+    def trace_any(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        """Is the segment blocked? numpy in: a bool array; a device tensor in: a bool device tensor, enqueued as trace_closest."""
+        if not _is_device_tensor(origins):
+            return self._host_trace_any(origins, dirs, tmin, tmax)
+        import torch
+        occ = self._device_query(origins, lambda torch: self._device_rays(torch, origins, dirs, tmin, tmax),
+                                 lambda n, i, o: lib().frt_renderer_trace_any(self._h, n, i, o, QUERY_DEVICE), (), "uint8")
+        return occ.view(torch.bool)
+
+    def pick(self, camera_uniform, xy):
+        """What is under these pixels? The closest hit of the primary ray of every pixel (x, y) of `xy` ([n, 2]) under `camera_uniform`: the hit the
+        G-buffer stage finds there. numpy in: synchronous, a dict of arrays, FrtError for a pixel outside the frame; an integer device tensor in:
+        enqueued, a dict of device tensors as trace_closest, a pixel outside the frame a miss."""
+        if not _is_device_tensor(xy):
+            return self._host_pick(camera_uniform, xy)
+        hits = self._device_query(xy, lambda torch: xy.reshape(-1, 2).to(torch.int32).contiguous(),
+                                  lambda n, i, o: lib().frt_renderer_pick(self._h, C.byref(camera_uniform), n, i, o, QUERY_DEVICE), (8,), "int32")
+        return _hit_views(hits)
+
     def rebuild_tree(self, quality="morton"):
         """Build a new quad tree over the replica's triangles as they are now, on the device (include/frt.h: frt_renderer_rebuild_tree): synchronous,
         between frames; pixels, accumulation and reservoirs are untouched. The host scene keeps its own tree. quality: "morton", the plain
@@ -194,9 +296,10 @@ def _stats_dict(s):
             "speculated_frames": int(s.speculated_frames), "discarded_speculations": int(s.discarded_speculations)}
 
 
-class MultiRenderer:
+class MultiRenderer(_HostQueries):
     """Renderer::new / render (renderer.rs:206, :349) for several GPUs of one node through frt_multi_renderer_*: ONE process, one call per
     frame; strips, halo copies and the gather are inside libfrt.so. `devices`: HIP ordinals, repeats allowed (several strips on one GPU)."""
+    _trace_closest, _trace_any, _pick = "frt_multi_renderer_trace_closest", "frt_multi_renderer_trace_any", "frt_multi_renderer_pick"
 
     def __init__(self, scene, width, height, devices, max_depth=8, motion_halo=0, flags=0, queue_capacity=0):
         o = RenderOpts()
@@ -261,6 +364,17 @@ class MultiRenderer:
         """Renderer.set_mesh_vertices on every strip's scene replica."""
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_multi_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+
+    def trace_closest(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        """Renderer.trace_closest on the first strip's replica (all are equal); host arrays only."""
+        return self._host_trace_closest(origins, dirs, tmin, tmax)
+
+    def trace_any(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        return self._host_trace_any(origins, dirs, tmin, tmax)
+
+    def pick(self, camera_uniform, xy):
+        """Renderer.pick in the full frame, on the first strip's replica; host arrays only."""
+        return self._host_pick(camera_uniform, xy)
 
     def rebuild_tree(self, quality="morton"):
         """Renderer.rebuild_tree on every strip's scene replica."""

@@ -40,6 +40,41 @@ def mesh_vertex_args(mesh_id, positions, attributes):
     return int(mesh_id), pos, att, pos.shape[0]
 
 
+HIT_FIELDS = ("t", "u", "v", "tri", "instance", "material", "primitive", "front")      # include/frt.h: frt_ray_hit, one 32-bit word each
+
+
+def ray_args(origins, dirs, tmin, tmax):
+    """The [n, 8] float32 ray records (include/frt.h: frt_ray) of the *_trace_* calls: `origins` and `dirs` shaped [n, 3] (or [3]), `tmin` / `tmax`
+    scalars or one value per ray."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(dirs, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise FrtError(f"{o.shape[0]} ray origins but {d.shape[0]} directions")
+    rays = np.empty((o.shape[0], 8), np.float32)
+    rays[:, 0:3] = o
+    rays[:, 4:7] = d
+    try:
+        rays[:, 3] = np.asarray(tmin, np.float32)
+        rays[:, 7] = np.asarray(tmax, np.float32)
+    except ValueError:
+        raise FrtError("tmin / tmax must be scalars or hold one value per ray") from None
+    return rays
+
+
+def hits_dict(raw):
+    """An [n, 8] uint32 array of frt_ray_hit records as a dict of arrays: t, u, v float32; tri (0xFFFFFFFF = miss), instance, material, primitive,
+    front uint32."""
+    f = raw.view(np.float32)
+    return {name: (f if k < 3 else raw)[:, k].copy() for k, name in enumerate(HIT_FIELDS)}
+
+
+def pixel_args(xy, width, height):
+    p = np.asarray(xy, np.int64).reshape(-1, 2)
+    if p.size and (p.min() < 0 or p.max() > 0xFFFFFFFF):
+        raise FrtError("pixel coordinates must be unsigned 32-bit integers")
+    return np.ascontiguousarray(p.astype(np.uint32))
+
+
 class SceneBuilder:
     def __init__(self, handle=None):
         self._destroy = lib().frt_scene_destroy
@@ -126,6 +161,22 @@ class SceneBuilder:
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_scene_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
         return self
+
+    # ---- ray queries on the host copy of the built scene (include/frt.h: frt_scene_trace_closest / _any): the specification of Renderer.trace_*
+    def trace_closest(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        """Closest hit of every ray origin + t * dir, tmin < t < tmax: a dict of arrays (t, u, v, tri, instance, material, primitive, front);
+        tri == 0xFFFFFFFF is a miss (t = -1, the other fields 0)."""
+        rays = ray_args(origins, dirs, tmin, tmax)
+        out = np.zeros((rays.shape[0], 8), np.uint32)
+        check(lib().frt_scene_trace_closest(self._h, rays.shape[0], rays.ctypes.data, out.ctypes.data))
+        return hits_dict(out)
+
+    def trace_any(self, origins, dirs, tmin=0.0, tmax=3.0e38):
+        """Is the segment blocked? A bool per ray: some triangle is hit at tmin < t < tmax."""
+        rays = ray_args(origins, dirs, tmin, tmax)
+        out = np.zeros(rays.shape[0], np.uint8)
+        check(lib().frt_scene_trace_any(self._h, rays.shape[0], rays.ctypes.data, out.ctypes.data))
+        return out.astype(bool)
 
     # ---- introspection
     def counts(self):

@@ -165,6 +165,21 @@ int frt_scene_tree_stats(const frt_scene* s, uint32_t stats[8]);
 /* bvh stats[4]: max depth, leaves, max leaf size, wide-node count */
 int frt_scene_bvh_stats(const frt_scene* s, uint32_t stats[4]);
 
+/* ---- ray queries: caller-supplied rays against the scene, what the reference gets from the Vulkan ray query ----------
+ * A ray is origin + t * dir for tmin < t < tmax (both exclusive, as everywhere in this library); dir is used as given, so t is in units of its
+ * length. A hit is defined without reference to any tree: the closest hit is the smallest t, ties going to the smallest
+ * flattened triangle id. A ray with a non-finite origin or direction component, an all-zero direction or a NaN tmin / tmax is a miss (unoccluded),
+ * decided before any walk. */
+typedef struct frt_ray { float origin[3]; float tmin; float dir[3]; float tmax; } frt_ray;                      /* 32 B */
+/* tri: flattened triangle id, 0xFFFFFFFF = miss (then t = -1 and every other word is 0); instance: id in add_instance order; material: the
+ * instance's material id; primitive = tri - the instance's first triangle, i.e. the triangle's index within its mesh; front: 0 or 1 */
+typedef struct frt_ray_hit { float t, u, v; uint32_t tri, instance, material, primitive, front; } frt_ray_hit;   /* 32 B */
+#define FRT_QUERY_MAX_RAYS (1u << 26)
+/* The host form, the specification of the renderer calls below: a walk of the host copy's quad tree, single-threaded. n == 0: FRT_OK, nothing
+ * touched. FRT_ERR_INVALID_ARG: a null pointer with n > 0, n > FRT_QUERY_MAX_RAYS; FRT_ERR_STATE: scene not built. */
+int frt_scene_trace_closest(const frt_scene* s, uint32_t n, const frt_ray* rays, frt_ray_hit* out);
+int frt_scene_trace_any(const frt_scene* s, uint32_t n, const frt_ray* rays, uint8_t* occluded_out);             /* 1 = some triangle is hit */
+
 /* ---- camera: src/camera.rs:207-256 build_uniform at the initial pose (:40-42), jitter 0 (:202-203) ------------ */
 void frt_camera_default(float aspect, uint32_t frame_count, uint32_t num_lights, frt_camera_uniform* out);
 /* CameraController::build_uniform, src/camera.rs:207-256, for any pose (position, yaw, pitch: the controller's state, :38-56), jitter
@@ -351,6 +366,24 @@ int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t stats[4]);
  * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 
+/* Ray queries against this renderer's scene replica AS IT IS NOW on the device: after every frt_renderer_set_instance_transforms,
+ * frt_renderer_set_mesh_vertices and frt_renderer_rebuild_tree so far. Results equal frt_scene_trace_closest / _any over a scene in the same state bit for bit.
+ * flags == 0: the pointers are host memory and the call is synchronous (copy up, one kernel, copy down; it returns when `out` is filled).
+ * FRT_QUERY_DEVICE: the pointers are 16-byte aligned device memory on the renderer's device; the call only enqueues on the renderer's main stream
+ * (frt_renderer_stream(r, 0)) and returns, and the caller orders its reads behind that stream. Allowed at any time, also between the phases of an open
+ * frame: a query only reads the scene, and every writer of the scene is on (or fenced into) the main stream. Queries are not counted in frt_stats and
+ * touch no frame state. n == 0: FRT_OK, nothing touched. FRT_ERR_INVALID_ARG: null handle, a null pointer with n > 0, n > FRT_QUERY_MAX_RAYS, an
+ * unknown flag bit, a misaligned device pointer, and (experiments build) the renderers frt_renderer_rebuild_tree refuses, which do not walk the quad tree. */
+#define FRT_QUERY_DEVICE 1u
+int frt_renderer_trace_closest(frt_renderer* r, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags);
+int frt_renderer_trace_any(frt_renderer* r, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags);
+/* Picking: the closest hit of the primary ray of pixels (xy[2k], xy[2k + 1]) of the renderer's full width x height frame under `cam` (a strip renderer
+ * picks in the full frame too: its replica is the whole scene). The ray is made on the device by the code the G-buffer stage uses and traced over its
+ * range (0.001, 1000), so a picked hit is the G-buffer's hit: origin + dir * t is FRT_BUF_GPOS.xyz and `material` is its w for that pixel. `cam` is
+ * host memory in both forms (copied during the call). A pixel outside the frame: FRT_ERR_INVALID_ARG in the host-pointer form, before anything is
+ * enqueued; a miss record under FRT_QUERY_DEVICE. */
+int frt_renderer_pick(frt_renderer* r, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags);
+
 /* ---- N GPUs behind one call (`ngpus`; section 8e) -----------------------------------------------------------------
  * In the reference one call renders one frame: Renderer::render, src/renderer.rs:349-518, called from State::render, src/state.rs:192-204.
  * frt_multi_renderer is that call for a node with several GPUs: ONE process, `ndev` strip renderers (two-stream schedule), the scene
@@ -399,6 +432,10 @@ int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id
 int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m);
 /* frt_renderer_rebuild_tree_ex on every strip's replica */
 int frt_multi_renderer_rebuild_tree_ex(frt_multi_renderer* m, uint32_t mode);
+/* The three ray-query calls on the first strip's replica (all replicas are equal). Host-pointer form only: flags must be 0. */
+int frt_multi_renderer_trace_closest(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags);
+int frt_multi_renderer_trace_any(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags);
+int frt_multi_renderer_pick(frt_multi_renderer* m, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags);
 
 #ifdef __cplusplus
 }
