@@ -24,25 +24,12 @@
 //   step A  incoming "post" / "pre" copies (their source events were recorded in the previous frame) | G-buffer + T-trace + T-merge | record ev_tm
 //   step B  incoming "mid" copies | spatial interior | edge stream waits for the copies | spatial edge + continuations | post | records | end of frame
 // frt_multi_renderer_render returns when every strip's frame is ENQUEUED (the GPUs run behind, as with frt_renderer_render).
-#include "frt_scene.hpp"
-#include <hip/hip_runtime.h>
+#include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cmath>
 #include <condition_variable>
-#include <cstring>
 #include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
-
-namespace frt { int set_error(int code, const std::string& msg); }
-using frt::set_error;
-
-#define HIPM_TRY(expr)                                                                                       \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return set_error(FRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 static const uint32_t kHaloReservoir = 12;   // spatial radius 10 + 2 rows of redundant spatial work (frt_renderer.hip: kHaloGbuffer)
 static const uint32_t kHaloHistory = 1;      // post reads the previous accumulation within +-1 row (post.wgsl:196-199)
@@ -82,12 +69,6 @@ struct frt_multi_renderer {
 };
 
 namespace {
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 // Strip boundaries of equal WORK (the ceiling strip of a Cornell Box is far cheaper than the floor strip): a quarter-resolution probe
 // rendered band by band, exact device ray counters per band, cost = rays + 4 per pixel (frt/dist.py::balanced_boundaries, same numbers).
 int balanced_boundaries(const frt_scene* scene, uint32_t W, uint32_t H, uint32_t world, uint32_t max_depth, int device, uint32_t min_rows, std::vector<uint32_t>& out) {
@@ -149,8 +130,8 @@ int copy_rows(frt_multi_renderer* m, Strip& src, Strip& dst, int buf, int index,
     const void* ps = buf == FRT_BUF_RESERVOIR ? src.p_res[index & 1] : src.p_acc[index & 1];
     void* pd = buf == FRT_BUF_RESERVOIR ? dst.p_res[index & 1] : dst.p_acc[index & 1];
     const size_t pitch = (size_t)m->W * bpp, off = pitch * y0, bytes = pitch * (y1 - y0);
-    if (src.device == dst.device) HIPM_TRY(hipMemcpyAsync((uint8_t*)pd + off, (const uint8_t*)ps + off, bytes, hipMemcpyDeviceToDevice, dst.copy));
-    else HIPM_TRY(hipMemcpyPeerAsync((uint8_t*)pd + off, dst.device, (const uint8_t*)ps + off, src.device, bytes, dst.copy));
+    if (src.device == dst.device) HIP_TRY(hipMemcpyAsync((uint8_t*)pd + off, (const uint8_t*)ps + off, bytes, hipMemcpyDeviceToDevice, dst.copy));
+    else HIP_TRY(hipMemcpyPeerAsync((uint8_t*)pd + off, dst.device, (const uint8_t*)ps + off, src.device, bytes, dst.copy));
     return FRT_OK;
 }
 
@@ -162,21 +143,21 @@ enum Which { PRE, MID, POST };
 int exchange_into(frt_multi_renderer* m, size_t k, Which which, int buf, int index, uint32_t rows) {
     const size_t n = m->strips.size();
     Strip& d = m->strips[k];
-    DevGuard g(d.device);
+    DeviceGuard g(d.device);
     hipEvent_t own = which == MID ? d.ev_tm : (which == PRE ? d.ev_spatial : d.ev_post);
     hipEvent_t done = which == MID ? d.ev_copy_mid : (which == PRE ? d.ev_copy_pre : d.ev_copy_post);
-    HIPM_TRY(hipStreamWaitEvent(d.copy, own, 0));
+    HIP_TRY(hipStreamWaitEvent(d.copy, own, 0));
     for (int side = 0; side < 2; ++side) {
         if ((side == 0 && k == 0) || (side == 1 && k + 1 == n)) continue;
         Strip& s = m->strips[side == 0 ? k - 1 : k + 1];
         hipEvent_t produced = which == MID ? s.ev_tm : (which == PRE ? s.ev_spatial : s.ev_post);
-        HIPM_TRY(hipStreamWaitEvent(d.copy, produced, 0));
+        HIP_TRY(hipStreamWaitEvent(d.copy, produced, 0));
         // the upper neighbour's last `rows` rows land in [rb - rows, rb); the lower neighbour's first `rows` rows in [re, re + rows)
         const uint32_t y0 = side == 0 ? d.rb - rows : d.re, y1 = side == 0 ? d.rb : d.re + rows;
         const int rc = copy_rows(m, s, d, buf, index, y0, y1);
         if (rc) return rc;
     }
-    HIPM_TRY(hipEventRecord(done, d.copy));
+    HIP_TRY(hipEventRecord(done, d.copy));
     return FRT_OK;
 }
 
@@ -191,21 +172,21 @@ int strip_step(frt_multi_renderer* m, size_t k, int step) {
     // (restir.wgsl:846-900 uses frame_count for the seed only). Post ignores its history at frame_count 0 (post.wgsl:187).
     const bool prev_pre = m->serial > 0, prev_post = m->serial > 0 && m->frame > 0;
     if ((int)k == m->inject_strip && step == m->inject_step) return set_error(FRT_ERR_HIP, "injected failure (frt_multi_renderer_inject_failure)");
-    DevGuard g(s.device);
+    DeviceGuard g(s.device);
     hipStream_t q = (hipStream_t)frt_renderer_stream(s.r, 0);
     hipStream_t qe = (hipStream_t)frt_renderer_stream(s.r, 2);
     // rule (c): this strip's next writer of rows a neighbour copies waits for that neighbour's copy event
     auto wait_neighbours = [&](hipStream_t st, hipEvent_t Strip::*ev) -> int {
-        if (k > 0) HIPM_TRY(hipStreamWaitEvent(st, m->strips[k - 1].*ev, 0));
-        if (k + 1 < n) HIPM_TRY(hipStreamWaitEvent(st, m->strips[k + 1].*ev, 0));
+        if (k > 0) HIP_TRY(hipStreamWaitEvent(st, m->strips[k - 1].*ev, 0));
+        if (k + 1 < n) HIP_TRY(hipStreamWaitEvent(st, m->strips[k + 1].*ev, 0));
         return FRT_OK;
     };
     int rc;
     // rows a gather may still be copying (frt_multi_renderer_gather with a caller's stream): this frame's first writers wait for the copy
     auto wait_gather = [&]() -> int {
         if (!s.gather_pending) return FRT_OK;
-        HIPM_TRY(hipStreamWaitEvent(q, s.ev_gather, 0));
-        if (qe != q) HIPM_TRY(hipStreamWaitEvent(qe, s.ev_gather, 0));
+        HIP_TRY(hipStreamWaitEvent(q, s.ev_gather, 0));
+        if (qe != q) HIP_TRY(hipStreamWaitEvent(qe, s.ev_gather, 0));
         s.gather_pending = false;
         return FRT_OK;
     };
@@ -218,13 +199,13 @@ int strip_step(frt_multi_renderer* m, size_t k, int step) {
         if (prev_pre && K) {
             rc = exchange_into(m, k, PRE, FRT_BUF_RESERVOIR, 1, K);
             if (rc) return rc;
-            HIPM_TRY(hipStreamWaitEvent(q, s.ev_copy_pre, 0));
+            HIP_TRY(hipStreamWaitEvent(q, s.ev_copy_pre, 0));
         }
         // T-merge(f) rewrites reservoir_buffers[0]: behind the neighbours' "mid" copies of frame f-1 (recorded in that frame's step B)
         if (m->serial > 0 && (rc = wait_neighbours(q, &Strip::ev_copy_mid))) return rc;
         rc = frt_renderer_render_phases(s.r, cam, FRT_PHASE_GBUFFER | FRT_PHASE_TEMPORAL);      // T-merge (G-buffer + T-trace normally ran ahead of the frame)
         if (rc) return rc;
-        HIPM_TRY(hipEventRecord(s.ev_tm, q));
+        HIP_TRY(hipEventRecord(s.ev_tm, q));
         return FRT_OK;
     }
     rc = exchange_into(m, k, MID, FRT_BUF_RESERVOIR, 0, kHaloReservoir);      // behind this strip's and its neighbours' T-merge
@@ -238,19 +219,19 @@ int strip_step(frt_multi_renderer* m, size_t k, int step) {
     if ((rc = wait_gather())) return rc;      // ... and raw / spatial reservoirs / display rows a gather may still be copying
     rc = frt_renderer_render_phases(s.r, cam, FRT_PHASE_SPATIAL_INNER);       // interior rows: need nothing from a neighbour
     if (rc) return rc;
-    HIPM_TRY(hipStreamWaitEvent(qe, s.ev_copy_mid, 0));      // the edge rows' stream waits for the neighbours' reservoirs
+    HIP_TRY(hipStreamWaitEvent(qe, s.ev_copy_mid, 0));      // the edge rows' stream waits for the neighbours' reservoirs
     rc = frt_renderer_render_phases(s.r, cam, FRT_PHASE_SPATIAL_EDGE);
     if (rc) return rc;
-    HIPM_TRY(hipEventRecord(s.ev_spatial, q));
+    HIP_TRY(hipEventRecord(s.ev_spatial, q));
     if (prev_post) {
-        HIPM_TRY(hipStreamWaitEvent(q, s.ev_copy_post, 0));
+        HIP_TRY(hipStreamWaitEvent(q, s.ev_copy_post, 0));
         // post(f) rewrites the accumulation slot the neighbours' "post" copies of frame f-1 read; their copies of THIS frame (step A, same copy
         // streams, behind those) are what the events now stand for: waiting for them covers both
         if ((rc = wait_neighbours(q, &Strip::ev_copy_post))) return rc;
     }
     rc = frt_renderer_render_phases(s.r, cam, FRT_PHASE_POST);
     if (rc) return rc;
-    HIPM_TRY(hipEventRecord(s.ev_post, q));
+    HIP_TRY(hipEventRecord(s.ev_post, q));
     return frt_renderer_end_frame(s.r);
 }
 
@@ -290,6 +271,18 @@ int run_step(frt_multi_renderer* m, int step) {
     for (Strip& s : m->strips) if (s.status) return set_error(s.status, s.message);
     return FRT_OK;
 }
+
+// One edit of the scene on every strip's own replica, in strip order. Arguments are checked on the first strip before any replica changes.
+template <class Edit>
+int edit_every_replica(frt_multi_renderer* m, const char* what, Edit edit) {
+    if (!m) return set_error(FRT_ERR_INVALID_ARG, std::string(what) + ": null");
+    if (m->failed) return set_error(FRT_ERR_STATE, std::string(what) + ": the handle is failed; call frt_multi_renderer_clear");
+    for (size_t i = 0; i < m->strips.size(); ++i) {
+        const int rc = edit(m->strips[i].r);
+        if (rc) { if (i > 0) m->failed = true; return rc; }      // (a later strip can only fail in HIP: the replicas now differ)
+    }
+    return FRT_OK;
+}
 }   // namespace
 
 extern "C" {
@@ -323,7 +316,7 @@ frt_multi_renderer* frt_multi_renderer_create(const frt_scene* scene, uint32_t w
         if (ndev > 1) { o.row_begin = s.rb; o.row_end = s.re; o.motion_halo_rows = K; }
         s.r = frt_renderer_create(scene, width, height, &o);
         if (!s.r) { frt_multi_renderer_destroy(m); return nullptr; }
-        DevGuard g(s.device);
+        DeviceGuard g(s.device);
         bool ok = hipStreamCreateWithFlags(&s.copy, hipStreamNonBlocking) == hipSuccess;
         for (hipEvent_t* e : {&s.ev_tm, &s.ev_spatial, &s.ev_post, &s.ev_copy_pre, &s.ev_copy_mid, &s.ev_copy_post, &s.ev_src, &s.ev_gather})
             ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
@@ -344,7 +337,7 @@ frt_multi_renderer* frt_multi_renderer_create(const frt_scene* scene, uint32_t w
         int can = 0, both = 0;
         auto enable = [&](int from, int to) {
             if (hipDeviceCanAccessPeer(&can, from, to) != hipSuccess || !can) return;
-            DevGuard g(from);
+            DeviceGuard g(from);
             const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
             if (e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled) both += 1;
         };
@@ -364,17 +357,17 @@ void frt_multi_renderer_destroy(frt_multi_renderer* m) {
     m->cv_post.notify_all();
     for (Strip& s : m->strips) if (s.worker.joinable()) s.worker.join();
     for (Strip& s : m->strips) {      // every strip idle before any strip's buffers go away (a neighbour's incoming copy reads them)
-        DevGuard g(s.device);
+        DeviceGuard g(s.device);
         if (s.r) (void)frt_renderer_sync(s.r);
         if (s.copy) (void)hipStreamSynchronize(s.copy);
     }
     for (Strip& s : m->strips) {
-        DevGuard g(s.device);
+        DeviceGuard g(s.device);
         if (s.copy) (void)hipStreamDestroy(s.copy);
         for (hipEvent_t e : {s.ev_tm, s.ev_spatial, s.ev_post, s.ev_copy_pre, s.ev_copy_mid, s.ev_copy_post, s.ev_src, s.ev_gather}) if (e) (void)hipEventDestroy(e);
         if (s.r) frt_renderer_destroy(s.r);
     }
-    if (m->gather_buf && !m->strips.empty()) { DevGuard g(m->strips[0].device); (void)hipFree(m->gather_buf); }
+    if (m->gather_buf && !m->strips.empty()) { DeviceGuard g(m->strips[0].device); (void)hipFree(m->gather_buf); }
     delete m;
 }
 
@@ -385,8 +378,8 @@ int frt_multi_renderer_render(frt_multi_renderer* m, const frt_camera_uniform* c
     if (m->strips.size() == 1) {
         Strip& s0 = m->strips[0];
         if (s0.gather_pending) {      // a gather on the caller's stream may still be copying the rows this frame rewrites
-            DevGuard g(s0.device);
-            HIPM_TRY(hipStreamWaitEvent((hipStream_t)frt_renderer_stream(s0.r, 0), s0.ev_gather, 0));
+            DeviceGuard g(s0.device);
+            HIP_TRY(hipStreamWaitEvent((hipStream_t)frt_renderer_stream(s0.r, 0), s0.ev_gather, 0));
             s0.gather_pending = false;
         }
         int rc = m->inject_strip == 0 ? set_error(FRT_ERR_HIP, "injected failure (frt_multi_renderer_inject_failure)") : frt_renderer_render(s0.r, cam);
@@ -411,8 +404,8 @@ int frt_multi_renderer_sync(frt_multi_renderer* m) {
     for (Strip& s : m->strips) {
         int rc = frt_renderer_sync(s.r);
         if (rc) return rc;
-        DevGuard g(s.device);
-        HIPM_TRY(hipStreamSynchronize(s.copy));
+        DeviceGuard g(s.device);
+        HIP_TRY(hipStreamSynchronize(s.copy));
     }
     return FRT_OK;
 }
@@ -433,7 +426,7 @@ int frt_multi_renderer_clear(frt_multi_renderer* m) {
     if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi clear: null");
     int first = FRT_OK;
     for (Strip& s : m->strips) {
-        DevGuard g(s.device);
+        DeviceGuard g(s.device);
         (void)hipStreamSynchronize(s.copy);
         const int rc = frt_renderer_clear(s.r);      // syncs the strip's streams, zeroes its targets and counters, closes an open frame, clears `failed`
         if (rc && !first) first = rc;
@@ -447,26 +440,13 @@ int frt_multi_renderer_clear(frt_multi_renderer* m) {
 }
 
 // Every strip moves its own replica (frt_renderer_set_instance_transforms: ordered on the strip's streams). The copy streams move reservoir and
-// accumulation rows only, never scene data. Arguments are checked on the first strip before any replica changes.
+// accumulation rows only, never scene data.
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
-    if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_instance_transforms: null");
-    if (m->failed) return set_error(FRT_ERR_STATE, "multi set_instance_transforms: the handle is failed; call frt_multi_renderer_clear");
-    for (size_t i = 0; i < m->strips.size(); ++i) {
-        const int rc = frt_renderer_set_instance_transforms(m->strips[i].r, n, ids, m_colmajor16);
-        if (rc) { if (i > 0) m->failed = true; return rc; }      // (a later strip can only fail in HIP: the replicas now differ)
-    }
-    return FRT_OK;
+    return edit_every_replica(m, "multi set_instance_transforms", [&](frt_renderer* r) { return frt_renderer_set_instance_transforms(r, n, ids, m_colmajor16); });
 }
-
-// Every strip deforms its own replica (frt_renderer_set_mesh_vertices), as above: arguments are checked on the first strip before any replica changes.
+// Every strip deforms its own replica (frt_renderer_set_mesh_vertices), as above.
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
-    if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_mesh_vertices: null");
-    if (m->failed) return set_error(FRT_ERR_STATE, "multi set_mesh_vertices: the handle is failed; call frt_multi_renderer_clear");
-    for (size_t i = 0; i < m->strips.size(); ++i) {
-        const int rc = frt_renderer_set_mesh_vertices(m->strips[i].r, mesh_id, pos4, attrs, nverts);
-        if (rc) { if (i > 0) m->failed = true; return rc; }      // (a later strip can only fail in HIP: the replicas now differ)
-    }
-    return FRT_OK;
+    return edit_every_replica(m, "multi set_mesh_vertices", [&](frt_renderer* r) { return frt_renderer_set_mesh_vertices(r, mesh_id, pos4, attrs, nverts); });
 }
 
 // Every strip rebuilds its own replica's tree (frt_renderer_rebuild_tree: synchronous per strip). The replicas hold the same triangles, so the strips
@@ -544,20 +524,20 @@ int frt_multi_renderer_gather(frt_multi_renderer* m, int buf, int index, int32_t
         if (rc) return rc;
         rc = frt_renderer_fence(s.r);
         if (rc) return rc;
-        DevGuard g(s.device);
+        DeviceGuard g(s.device);
         hipStream_t q = (hipStream_t)frt_renderer_stream(s.r, 0);
-        HIPM_TRY(hipEventRecord(s.ev_src, q));
-        HIPM_TRY(hipStreamWaitEvent(s.copy, s.ev_src, 0));
+        HIP_TRY(hipEventRecord(s.ev_src, q));
+        HIP_TRY(hipStreamWaitEvent(s.copy, s.ev_src, 0));
         const size_t off = pitch * s.rb, bytes = pitch * (s.re - s.rb);
-        if (s.device == device) HIPM_TRY(hipMemcpyAsync((uint8_t*)dst + off, (const uint8_t*)src + off, bytes, hipMemcpyDeviceToDevice, s.copy));
-        else HIPM_TRY(hipMemcpyPeerAsync((uint8_t*)dst + off, device, (const uint8_t*)src + off, s.device, bytes, s.copy));
-        HIPM_TRY(hipEventRecord(s.ev_gather, s.copy));
+        if (s.device == device) HIP_TRY(hipMemcpyAsync((uint8_t*)dst + off, (const uint8_t*)src + off, bytes, hipMemcpyDeviceToDevice, s.copy));
+        else HIP_TRY(hipMemcpyPeerAsync((uint8_t*)dst + off, device, (const uint8_t*)src + off, s.device, bytes, s.copy));
+        HIP_TRY(hipEventRecord(s.ev_gather, s.copy));
         s.gather_pending = true;
     }
-    DevGuard g(device);
+    DeviceGuard g(device);
     for (Strip& s : m->strips) {
-        if (stream) HIPM_TRY(hipStreamWaitEvent((hipStream_t)stream, s.ev_gather, 0));
-        else HIPM_TRY(hipEventSynchronize(s.ev_gather));
+        if (stream) HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, s.ev_gather, 0));
+        else HIP_TRY(hipEventSynchronize(s.ev_gather));
     }
     return FRT_OK;
 }
@@ -569,16 +549,16 @@ int frt_multi_renderer_read_buffer(frt_multi_renderer* m, int buf, int index, vo
     if (!m || !out || !bpp) return set_error(FRT_ERR_INVALID_ARG, "multi read_buffer: bad arguments");
     const size_t bytes = (size_t)m->W * m->H * bpp;
     const int dev = m->strips[0].device;
-    DevGuard g(dev);
+    DeviceGuard g(dev);
     if (m->gather_bytes < bytes) {
         if (m->gather_buf) (void)hipFree(m->gather_buf);
         m->gather_buf = nullptr; m->gather_bytes = 0;
-        HIPM_TRY(hipMalloc(&m->gather_buf, bytes));
+        HIP_TRY(hipMalloc(&m->gather_buf, bytes));
         m->gather_bytes = bytes;
     }
     int rc = frt_multi_renderer_gather(m, buf, index, dev, m->gather_buf, nullptr);
     if (rc) return rc;
-    HIPM_TRY(hipMemcpy(out, m->gather_buf, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, m->gather_buf, bytes, hipMemcpyDeviceToHost));
     return FRT_OK;
 }
 int frt_multi_renderer_read_display(frt_multi_renderer* m, uint8_t* rgba8) { return frt_multi_renderer_read_buffer(m, FRT_BUF_DISPLAY, 0, rgba8); }

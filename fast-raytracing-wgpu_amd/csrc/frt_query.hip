@@ -9,6 +9,7 @@
 // (index past n, a degenerate ray, a pixel outside the frame) walks a ray that no box admits instead of leaving: every lane reaches the barrier and
 // takes part in the ballots of the staged-top loop and of the voting walk.
 #include "frt_query.hpp"
+#include "frt_renderer_state.hpp"      // frt::set_error
 
 namespace frt {
 
@@ -124,8 +125,6 @@ void scene_trace_any(const SceneBuilder& b, uint32_t n, const frt_ray* rays, uin
         occluded[i] = h.tri != 0xFFFFFFFFu ? 1 : 0;
     }
 }
-
-int set_error(int code, const std::string& msg);      // frt_renderer.hip
 
 } // namespace frt
 

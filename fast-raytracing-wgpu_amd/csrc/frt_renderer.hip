@@ -1,45 +1,8 @@
 // frt_renderer.hip — C ABI (include/frt.h) + the renderer object: per-pixel buffers in HBM, scene replica upload,
 // per-frame stage launches. Mirrors Renderer / RenderTargets of src/renderer.rs:26-170, :206-336, :349-518 and the
 // ping-pong wiring of src/passes/{gbuffer,restir,restir_spatial,post}.rs. There is no CPU path in this file.
-#include "frt_scene.hpp"
-#include "frt_kernels.hpp"
-#include "frt_refit.hpp"
-#include "frt_rebuild.hpp"
-#include "frt_deform.hpp"
-#include "frt_query.hpp"
-#include <hip/hip_runtime.h>
-#include <cstring>
-#include <cstdio>
-#include <string>
-#include <vector>
-#include <cstdlib>
-
-#ifndef FRT_EXPERIMENTS
-#define FRT_EXPERIMENTS 0      // 1: lib/libfrt_exp.so (`make experiments`): the measured-and-not-kept kernel designs and their FRT_* environment knobs
-#endif
-
-using namespace frt;
-
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-namespace frt { int set_error(int code, const std::string& msg) { return fail(code, msg); } }   // for the other translation units of the ABI
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(FRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// Every entry point that touches the device makes the renderer's device current and gives the caller's back on return (a host that
-// drives several devices from one thread — frt_multi_renderer does — must not find its current device changed by a call).
-struct DeviceGuard {
-    int prev = -1; bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-#define FRT_DEVICE(r) DeviceGuard guard_((r)->device); if (!guard_.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed")
+// State structs: frt_renderer_state.hpp; edits and reads of the scene replica between frames: frt_scene_edit.hip; scene, camera, geometry: frt_scene_abi.cpp.
+#include "frt_renderer_state.hpp"
 
 static_assert(sizeof(frt_vertex_attr) == 32 && sizeof(frt_material) == 64 && sizeof(frt_light) == 64, "ABI struct sizes");
 static_assert(sizeof(frt_camera_uniform) == 288 && sizeof(frt_reservoir) == 32 && sizeof(frt_bvh2_node) == 32, "ABI struct sizes");
@@ -52,171 +15,9 @@ static const uint32_t kHaloGbuffer = 12;   // spatial reuse radius 10 (restir_sp
 static const uint32_t kHaloSpatial = 2;    // post reads raw radiance within +-2 rows (post.wgsl:93)
 static const uint32_t kReuseRadius = 10;   // rows of temporal reservoirs a spatial pixel may read above / below itself
 
-// G-buffer, motion and candidate targets exist kGSets = kSpecDepth + 1 times. With one frame running ahead (the default) that is the
-// reference's two ping-pong slots (gbuffer.rs:299): G-buffer(f+1) overwrites the set of frame f-1, whose last readers are done by then.
-// Two frames ahead (kSpecDepth = 2, a third set: +60 B per pixel) was built and measured: 2.204 vs 2.208 ms — the ahead stream is in
-// order, so frame f+2 cannot start before f+1's latency-bound tail has drained — and is therefore not compiled in. Which physical set
-// holds which of the reference's two logical slots is tracked per frame (GSlots below), so any kSpecDepth works.
-static const int kSpecDepth = 1;             // frames whose G-buffer + T-trace may run ahead
-static const int kGSets = 3;                 // physical G-buffer sets addressable; a renderer owns `gsets` of them (2, strips under the pipeline 3)
-enum { B_GPOS0 = 0, B_GNRM0 = B_GPOS0 + kGSets, B_GALB0 = B_GNRM0 + kGSets, B_GMOT0 = B_GALB0 + kGSets, B_CAND0 = B_GMOT0 + kGSets,
-       B_RES0 = B_CAND0 + kGSets, B_RES1, B_RAW, B_DISP, B_ACC0, B_ACC1, B_COUNT };
-// Buffers outside the arena (frt_renderer_arena_bytes stays 228 B per pixel): the third G-buffer set. Only strip renderers under the pipeline
-// allocate them (frt_renderer::extras): with a third set the next frame's G-buffer + T-trace need not wait for this frame's T-merge.
-static bool is_extra(int b) { return b < B_RES0 && (b % kGSets) == 2; }
-static uint32_t bpp_of(int b) {
-    if (b < B_GALB0) return 16u;        // gpos, gnormal
-    if (b < B_GMOT0) return 4u;         // galbedo
-    if (b < B_CAND0) return 8u;         // gmotion
-    if (b < B_RES0) return 16u;         // candidate
-    if (b <= B_RES1) return 32u;
-    if (b == B_RAW) return 8u;
-    if (b == B_DISP) return 4u;
-    return 16u;                         // accumulation
-}
-struct GSlots { uint32_t g, gprev, aux; };   // physical sets: this frame's G-buffer, the previous logical slot's, and motion / candidate (= g under the pipeline)
-
-// Device counters (unsigned long long each): [0..7] committed rays per stage {closest, any}; [8] halo overflow;
-// [9..12] PENDING rays of a G-buffer + T-trace pair that ran ahead of its frame (committed by its T-merge, dropped with a discarded speculation)
-static const int kPending = 2;               // pending ray-count sets / T-trace events: consecutive speculated frames alternate (with three G-buffer sets
-                                             // T-trace(f+1) may start before T-merge(f) has committed the counts of T-trace(f))
-enum { C_STAGE = 0, C_HALO = 8, C_PENDING = 9, C_COUNT = 9 + 4 * kPending };   // a pending set of four per speculated frame in flight
 #if FRT_EXPERIMENTS
 static const int kTileStateWords = 8;      // per traced stage (experiments/frt_experiment_kernels.hpp: TileOrder uses 6)
 #endif
-
-#if FRT_EXPERIMENTS
-// Everything the measured-and-not-kept kernel designs (csrc/experiments/frt_experiment_kernels.hpp) need in a renderer: their state, their FRT_*
-// environment knobs, their allocations. Compiled into lib/libfrt_exp.so only (`make experiments`); the product library has none of it.
-struct ExpState {
-    int spec_depth = kSpecDepth;           // frames speculated ahead (FRT_SPEC_DEPTH, 0 .. kSpecDepth)
-    long cont_grid = -1;                   // FRT_CONT_GRID: slots the spatial continuation grids cover at least (-1: half the stage's pixels)
-    uint32_t* d_tiles = nullptr;           // per traced stage kTileStateWords words of sweep-direction state (FRT_TILE_ORDER=1), or null
-    bool wg_park = true;                   // pixel kernels reserve queue slots once per workgroup (FRT_WG_PARK=0: once per wave)
-    bool wavefront = false;                // ray-level wavefront (FRT_WAVEFRONT=1): per bounce depth a trace launch and a shade launch
-    uint32_t* d_wf_words[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint32_t* d_wf_items[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    uint32_t* d_wf_hits[2] = {nullptr, nullptr}; uint32_t* d_wf_counts = nullptr;   // per stage: records x 2, item lists x 2, hit buffer; 2 x 96 counters
-    bool stream_mode = false; uint32_t shade_min = 32, stream_slice = 8;   // stream kernel (resumable traversal) instead of continuation launches
-    bool refill = false; uint32_t refill_min = 16;   // bounce kernel with lane refill (single cut) instead of continuation launches
-    bool resident = false;                 // traced stages through the resident kernels (BVH cached in LDS, persistent workgroups)
-    uint32_t res_nodes = 0; bool res_tris = false; uint32_t num_cus = 0, res_batch = 0;
-    uint32_t* d_work = nullptr;            // work counters of the resident launches: [stage 1|2][launch slot][2]
-};
-#endif
-
-// What frt_renderer_set_instance_transforms needs beside the scene replica, made at create. Device: the object-space positions of every
-// mesh (16 B per vertex), the slot of every flattened triangle (4 B per triangle), one word for the scene extent and the moved-instance records
-// (208 B each, grown on demand). Host: per instance what its record needs, the registered lights' emission, the level ranges of both trees.
-struct RefitState {
-    bool ok = false;                       // level ranges found (both trees are numbered breadth-first: frt_bvh.cpp)
-    const float4* d_pos = nullptr;
-    const uint32_t* d_slot_of = nullptr;
-    const unsigned int* d_ext = nullptr;
-    std::vector<uint32_t> pos_offset;      // per mesh: its first vertex in d_pos
-    std::vector<InstanceRec> inst;         // mesh, first_tri, tri_count, light link
-    std::vector<frt_light> lights;         // the scene's lights as uploaded (emission of the registered ones)
-    std::vector<uint32_t> index_offset;    // per mesh
-    std::vector<uint32_t> pair_levels, quad_levels;   // level L of a tree = nodes [levels[L], levels[L + 1])
-    MovedInstance* d_rec = nullptr; size_t d_cap = 0;
-    MovedInstance* h_rec = nullptr; size_t h_cap = 0;   // pinned staging of the records
-    hipEvent_t ev_rec = nullptr; bool rec_pending = false;   // the last copy out of h_rec
-    // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; pinned staging of one call's positions,
-    // attributes, instance records and decoded normals; the device buffer of the last two. Both grow on demand and are never shrunk.
-    std::vector<uint32_t> vert_count, attr_offset;
-    uint8_t* h_def = nullptr; size_t h_def_cap = 0;
-    uint8_t* d_def = nullptr; size_t d_def_cap = 0;
-    hipEvent_t ev_def = nullptr; bool def_pending = false;   // the last copy out of h_def
-    uint64_t device_bytes = 0;
-};
-
-// What frt_renderer_rebuild_tree adds ("Rebuild"), allocated at the first call: the scratch of the kernels, the triangle slots and the
-// id -> slot table that are NOT in use (they trade places with the replica's at every successful rebuild) and up to two quad-node buffers of
-// rebuild_max_nodes() nodes (the host-built tree's buffer may be smaller than a device tree needs, so it is never built into; the second one
-// is allocated by the second rebuild). All of it is freed with the scene replica.
-struct RebuildState {
-    RebuildScratch scratch;
-    float4* tris = nullptr; uint32_t* slot_of = nullptr;
-    float4* nodes[2] = {nullptr, nullptr};
-    bool done = false;                     // the replica's quad tree is a device rebuild: the pair tree and its quantised form are stale
-    uint32_t origin = 0;                   // frt_renderer_tree_stats: 1 the Morton tree, 2 the refined tree
-    uint32_t last[4] = {0, 0, 0, 0};       // frt_renderer_rebuild_stats
-    uint64_t device_bytes = 0;
-};
-
-// Staging of the host-pointer ray queries: one pinned block and one device block, each [input | output] of a call; grown on demand,
-// never shrunk. A host-pointer call is synchronous, so neither needs an event: the last call's copies are done when the next one starts.
-struct QueryState {
-    uint8_t* h = nullptr; size_t h_cap = 0;
-    uint8_t* d = nullptr; size_t d_cap = 0;
-};
-
-struct frt_renderer {
-    int device = 0;
-    hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
-    bool own_stream = false;
-    hipStream_t ahead = nullptr;           // FRT_FLAG_PIPELINE: G-buffer(f+1), T-trace(f+1)
-    hipStream_t edge = nullptr;            // FRT_FLAG_PIPELINE, strips: the spatial pixel launches of the halo-dependent edge rows (beside the interior launch)
-    hipStream_t edge2 = nullptr;           // ... the second edge of a middle strip: its launch runs beside the first one's instead of behind it
-    hipEvent_t ev_spix = nullptr, ev_tt[kPending] = {}, ev_tail = nullptr, ev_tm[2] = {nullptr, nullptr}, ev_edge = nullptr, ev_edge2 = nullptr, ev_edge_ready = nullptr;
-    bool tail_pending = false;             // work enqueued on `ahead` that the main stream has not been ordered behind yet
-    bool edge_in_flight = false, edge2_in_flight = false;
-    uint32_t W = 0, H = 0, max_depth = 8, rb = 0, re = 0, flags = 0, motion_halo = 0;
-    uint32_t frame_count = 0;
-    float jitter[2] = {0.0f, 0.0f};        // PostParams.jitter of the next post stage
-    SceneView sv{};
-    std::vector<void*> scene_allocs;
-    uint8_t* arena = nullptr;
-    bool own_arena = false;
-    size_t arena_bytes = 0;
-    size_t off[B_COUNT] = {};
-    unsigned long long* d_counters = nullptr;
-    // continuation queues: per traced stage one word buffer per path segment parity (the second only with two cuts or more)
-    uint32_t* d_qwords[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    uint32_t qcap = 0, qcap_max = 0;       // slots per queue; upper bound = every traced pixel parks
-    uint32_t qslots[2][2] = {{0, 0}, {0, 0}};   // slots of each word buffer [stage][first | second buffer], derived from qcap (alloc_queues)
-    uint64_t qbytes = 0;                   // device bytes of the word buffers
-    bool qcap_fixed = false;               // capacity given by the caller: never grown
-    uint32_t* d_qcount = nullptr;          // [stage 1|2][launch parity 0|1][kMaxCuts + 1] counters, then [stage] overflow counters
-    uint32_t* h_qseen = nullptr; uint32_t* d_qseen = nullptr;   // one word of mapped host memory: set by a wave that found its queue full (ContQueue::seen)
-    uint32_t qparity[2] = {0, 0};
-    uint32_t ncuts = 2, cuts[kMaxCuts] = {3, 4, 0, 0};   // measured best on the Cornell Box
-    bool vote = false;                     // traced kernels with the voting BVH walk (set from the size of the scene's quad tree, upload_scene)
-    uint32_t walk = kWalkQuad, wide_lds_bytes = 0, wg_rows = 0;      // which tree the traced kernels walk and how (frt_kernels.hpp: kWalk*; upload_scene)
-#if FRT_EXPERIMENTS
-    ExpState x;                            // lib/libfrt_exp.so only: state and FRT_* knobs of the measured-and-not-kept kernel designs (csrc/experiments/)
-#endif
-    frt_stats stats{};
-    struct Timed { hipEvent_t a, b; int slot; };
-    std::vector<Timed> pending;
-    std::vector<hipEvent_t> event_pool;
-    // frame in progress
-    bool failed = false;                   // a HIP call failed in the middle of a frame: the stage flags and stream order are no longer trustworthy; render calls
-                                           // return FRT_ERR_STATE until frt_renderer_clear
-    bool frame_open = false, g_done = false, tt_done = false, tm_done = false, s_started = false, s_inner_done = false, s_edge_done = false;
-    bool from_speculation = false;
-    Timed s_timer{};
-    bool s_timed = false;
-    // which physical G set holds the reference's logical slot 0 / 1 (frame_count % 2) for the NEXT G-buffer launch, the sets of the frame in
-    // progress and of the last finished frames (what reads through the ABI see)
-    uint32_t logical_phys[2] = {0, 1};
-    GSlots cur_slots{0, 1, 0}, last_slots{0, 1, 0}, before_last_slots{1, 0, 0};
-    uint32_t last_parity = 0;              // frame_count % 2 of the frame that recorded last_slots (the counter may move without a frame: end_frame, reset)
-    // speculation: G-buffer + T-trace of the next frames, enqueued on `ahead` under the cameras a static scene will present
-    struct Spec { frt_camera_uniform cam; uint32_t frame; GSlots slots; uint32_t logical_before[2]; int idx; };
-    std::vector<Spec> specs;               // oldest first, at most kSpecDepth
-    int spec_next_idx = 0, cur_spec_idx = 0;
-    bool camera_static = false;
-    frt_camera_uniform last_cam{}, cur_cam{};
-    bool have_last_cam = false;
-    uint8_t* extras = nullptr; size_t extras_bytes = 0;      // the buffers of is_extra(), when this renderer has them
-    uint32_t gsets = 2;                    // G-buffer sets in use
-    uint64_t serial = 0;                   // frames finished since creation (never reset: parity of the per-frame events)
-    RefitState rf;
-    RebuildState rbt;
-    QueryState qry;
-    void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
-    bool pipeline() const { return ahead != nullptr; }
-};
 
 static size_t arena_layout(uint32_t W, uint32_t H, size_t off[B_COUNT], bool extras = false) {
     size_t n = (size_t)W * H, cur = 0;
@@ -228,76 +29,12 @@ static size_t arena_layout(uint32_t W, uint32_t H, size_t off[B_COUNT], bool ext
     return cur;
 }
 
-template <class T, class D>
-static int upload(frt_renderer* r, const std::vector<T>& v, const D** out) {
-    void* d = nullptr;
-    size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-    HIP_TRY(hipMalloc(&d, bytes));
-    r->scene_allocs.push_back(d);
-    if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = reinterpret_cast<const D*>(d);
-    return FRT_OK;
-}
-
-#ifndef FRT_VOTE_MIN_NODES
-#define FRT_VOTE_MIN_NODES 32768      // (4 MiB of quad nodes; A/B builds: 0 = every scene votes, a huge value = none does)
-#endif
-static const size_t kVoteMinQuadNodes = FRT_VOTE_MIN_NODES;
 #if FRT_EXPERIMENTS
 #ifndef FRT_WIDE_LDS_MAX
 #define FRT_WIDE_LDS_MAX 28672      // bytes of 8-wide nodes a traced workgroup may hold in LDS beside its 9 KiB of stack words: 4 workgroups per CU (A/B builds)
 #endif
 static const size_t kWideLdsMaxBytes = FRT_WIDE_LDS_MAX;
 #endif
-// Level ranges of a breadth-first tree whose node i has `kids(i, out)` inner children: boundaries of the levels, or empty if the numbering is not
-// breadth-first (then the renderer cannot refit).
-template <class Kids>
-static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
-    std::vector<uint32_t> level(n, 0u), bounds(1, 0u);
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t c[4]; const int k = kids(i, c);
-        for (int j = 0; j < k; ++j) { if (c[j] <= i || c[j] >= n) return {}; level[c[j]] = level[i] + 1u; }
-    }
-    for (size_t i = 1; i < n; ++i) {
-        if (level[i] < level[i - 1]) return {};
-        if (level[i] != level[i - 1]) bounds.push_back((uint32_t)i);
-    }
-    bounds.push_back((uint32_t)n);
-    return bounds;
-}
-static int upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
-    RefitState& f = r->rf;
-    std::vector<float> pos;
-    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear();
-    for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
-        f.pos_offset.push_back((uint32_t)(pos.size() / 4));
-        f.index_offset.push_back(b.mesh_infos[m].index_offset);
-        f.vert_count.push_back((uint32_t)(b.mesh_positions[m].size() / 4));
-        f.attr_offset.push_back(b.mesh_infos[m].vertex_offset);
-        pos.insert(pos.end(), b.mesh_positions[m].begin(), b.mesh_positions[m].end());
-    }
-    int rc;
-    if ((rc = upload(r, pos, &f.d_pos))) return rc;
-    if ((rc = upload(r, b.tri_slot_of, &f.d_slot_of))) return rc;
-    std::vector<uint32_t> word(4, 0u);
-    if ((rc = upload(r, word, &f.d_ext))) return rc;
-    f.device_bytes = pos.size() * 4 + b.tri_slot_of.size() * 4 + 16;
-    f.inst = b.instances;
-    f.lights = b.lights;
-    f.pair_levels = level_ranges(b.pair_nodes.size(), [&](size_t i, uint32_t* c) {
-        int k = 0;
-        for (int j = 0; j < 2; ++j) { uint32_t ref; memcpy(&ref, &b.pair_nodes[i].q[12 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
-        return k;
-    });
-    f.quad_levels = level_ranges(b.quad_nodes.size(), [&](size_t i, uint32_t* c) {
-        int k = 0;
-        for (int j = 0; j < 4; ++j) { uint32_t ref; memcpy(&ref, &b.quad_nodes[i].q[24 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
-        return k;
-    });
-    f.ok = !f.pair_levels.empty() && !f.quad_levels.empty();
-    return FRT_OK;
-}
-
 static int upload_scene(frt_renderer* r, const SceneBuilder& b) {
     SceneView& sv = r->sv;
     int rc;
@@ -407,7 +144,7 @@ static void fill_frame_view(const frt_renderer* r, const frt_camera_uniform* cam
 }
 
 // Stream-level fence: the main stream waits for everything enqueued on the `ahead` stream (no host wait).
-static int fence_ahead(frt_renderer* r) {
+int frt::fence_ahead(frt_renderer* r) {
     if (r->ahead && r->tail_pending) {
         HIP_TRY(hipEventRecord(r->ev_tail, r->ahead));
         HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_tail, 0));
@@ -415,7 +152,7 @@ static int fence_ahead(frt_renderer* r) {
     }
     return FRT_OK;
 }
-static int sync_all(frt_renderer* r) {
+int frt::sync_all(frt_renderer* r) {
     HIP_TRY(hipStreamSynchronize(r->stream));
     if (r->edge) HIP_TRY(hipStreamSynchronize(r->edge));
     if (r->edge2) HIP_TRY(hipStreamSynchronize(r->edge2));
@@ -453,182 +190,27 @@ static int resolve_timing(frt_renderer* r) {
     return FRT_OK;
 }
 
-extern "C" {
+// The speculated frames are dropped, with everything speculated behind the first: order the main stream behind the work, clear its ray counts,
+// give the physical sets back; the buffers it wrote are simply overwritten by the stages that follow.
+int frt::drop_speculation(frt_renderer* r) {
+    if (r->specs.empty()) return FRT_OK;
+    const frt_renderer::Spec sp = r->specs.front();
+    int rc = fence_ahead(r);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(r->d_counters + C_PENDING, 0, 4 * kPending * sizeof(unsigned long long), r->stream));
+    r->logical_phys[0] = sp.logical_before[0]; r->logical_phys[1] = sp.logical_before[1];
+    r->stats.discarded_speculations += r->specs.size();
+    r->specs.clear();
+    return FRT_OK;
+}
 
-const char* frt_last_error(void) { return g_err.c_str(); }
+extern "C" {
 
 int frt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-// ------------------------------------------------------------------------------------------------ geometry / materials
-int frt_geometry_create(int which, uint32_t subdiv, uint32_t* nverts, uint32_t* nidx, float* pos4, frt_vertex_attr* attrs, uint32_t* idx) {
-    Geometry g;
-    switch (which) {
-    case 0: g = geometry::create_plane(); break;
-    case 1: g = geometry::create_cube(); break;
-    case 2: if (subdiv > 8) return fail(FRT_ERR_INVALID_ARG, "icosphere subdivisions > 8"); g = geometry::create_sphere(subdiv); break;
-    case 3: g = geometry::create_crystal(); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "unknown geometry kind");
-    }
-    if (nverts) *nverts = (uint32_t)g.attributes.size();
-    if (nidx) *nidx = (uint32_t)g.indices.size();
-    if (pos4) memcpy(pos4, g.positions.data(), g.positions.size() * 4);
-    if (attrs) memcpy(attrs, g.attributes.data(), g.attributes.size() * sizeof(frt_vertex_attr));
-    if (idx) memcpy(idx, g.indices.data(), g.indices.size() * 4);
-    return FRT_OK;
-}
-void frt_encode_octahedral_normal(const float n[3], float out[2]) { geometry::encode_octahedral_normal(n, out); }
-void frt_material_default(const float c[4], frt_material* out) { *out = MaterialBuilder(c[0], c[1], c[2], c[3]); }
-
-// ------------------------------------------------------------------------------------------------ scene
-frt_scene* frt_scene_create(void) { return new frt_scene(); }
-void frt_scene_destroy(frt_scene* s) { delete s; }
-
-int frt_scene_add_mesh(frt_scene* s, const float* pos4, uint32_t nverts, const frt_vertex_attr* attrs, const uint32_t* idx, uint32_t nidx) {
-    if (!s || !pos4 || !attrs || !idx || nverts == 0 || nidx == 0 || nidx % 3 != 0) return fail(FRT_ERR_INVALID_ARG, "add_mesh: bad arguments");
-    for (uint32_t i = 0; i < nidx; ++i) if (idx[i] >= nverts) return fail(FRT_ERR_INVALID_ARG, "add_mesh: index out of range");
-    Geometry g;
-    g.positions.assign(pos4, pos4 + (size_t)nverts * 4);
-    g.attributes.assign(attrs, attrs + nverts);
-    g.indices.assign(idx, idx + nidx);
-    return (int)s->b.add_mesh(g);
-}
-int frt_scene_add_material(frt_scene* s, const frt_material* m) {
-    if (!s || !m) return fail(FRT_ERR_INVALID_ARG, "add_material: null");
-    if (s->b.materials.size() >= 0xFFFFu) return fail(FRT_ERR_LIMIT, "more than 65535 materials (custom index packs 16 bits, builder.rs:184)");
-    return (int)s->b.add_material(*m);
-}
-static int check_instance(frt_scene* s, uint32_t mesh_id, uint32_t mat_id, const float* m) {
-    if (!s || !m) return fail(FRT_ERR_INVALID_ARG, "instance: null");
-    if (mesh_id >= s->b.mesh_infos.size()) return fail(FRT_ERR_INVALID_ARG, "instance: unknown mesh id");
-    if (mat_id != 0xFFFFFFFFu && mat_id >= s->b.materials.size()) return fail(FRT_ERR_INVALID_ARG, "instance: unknown material id");
-    return FRT_OK;
-}
-int frt_scene_add_instance(frt_scene* s, uint32_t mesh_id, uint32_t mat_id, const float m[16]) {
-    int rc = check_instance(s, mesh_id, mat_id, m);
-    if (rc) return rc;
-    Mat4 t; memcpy(t.m, m, 64);
-    s->b.add_instance(mesh_id, mat_id, t);
-    return FRT_OK;
-}
-int frt_scene_add_light(frt_scene* s, const frt_light* l) {
-    if (!s || !l) return fail(FRT_ERR_INVALID_ARG, "add_light: null");
-    return (int)s->b.add_light(*l);
-}
-int frt_scene_register_quad_light(frt_scene* s, uint32_t mesh_id, const float m[16], const float color[3], float intensity) {
-    int rc = check_instance(s, mesh_id, 0xFFFFFFFFu, m);
-    if (rc) return rc;
-    Mat4 t; memcpy(t.m, m, 64);
-    s->b.register_quad_light(mesh_id, t, color, intensity);
-    return FRT_OK;
-}
-int frt_scene_register_sphere_light(frt_scene* s, uint32_t mesh_id, const float m[16], const float color[3], float intensity) {
-    int rc = check_instance(s, mesh_id, 0xFFFFFFFFu, m);
-    if (rc) return rc;
-    Mat4 t; memcpy(t.m, m, 64);
-    s->b.register_sphere_light(mesh_id, t, color, intensity);
-    return FRT_OK;
-}
-int frt_scene_add_texture(frt_scene* s, int kind, const uint8_t* rgba8) {
-    if (!s || !rgba8 || (kind != 0 && kind != 1)) return fail(FRT_ERR_INVALID_ARG, "add_texture: bad arguments");
-    auto& v = kind == 0 ? s->b.color_textures : s->b.data_textures;
-    if (v.size() >= 0xFFFFu) return fail(FRT_ERR_LIMIT, "too many texture layers");
-    return (int)(kind == 0 ? s->b.add_color_texture(rgba8) : s->b.add_data_texture(rgba8));
-}
-int frt_scene_build(frt_scene* s) {
-    if (!s) return fail(FRT_ERR_INVALID_ARG, "build: null");
-    s->b.build();
-    if (!s->b.built) return fail(FRT_ERR_LIMIT, "build: " + s->b.error);
-    return FRT_OK;
-}
-int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
-    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null");
-    const int rc = s->b.set_instance_transforms(n, ids, m_colmajor16);
-    return rc ? fail(rc, s->b.error) : FRT_OK;
-}
-int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
-    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null");
-    const int rc = s->b.set_mesh_vertices(mesh_id, pos4, attrs, nverts);
-    return rc ? fail(rc, s->b.error) : FRT_OK;
-}
-frt_scene* frt_scene_create_cornell_box(void) {
-    frt_scene* s = new frt_scene();
-    scenes::create_cornell_box(s->b);
-    if (!s->b.built) { g_err = s->b.error; delete s; return nullptr; }
-    return s;
-}
-frt_scene* frt_scene_create_restir_scene(void) {
-    frt_scene* s = new frt_scene();
-    scenes::create_restir_scene(s->b);
-    if (!s->b.built) { g_err = s->b.error; delete s; return nullptr; }
-    return s;
-}
-int frt_scene_counts(const frt_scene* s, uint32_t c[8]) {
-    if (!s || !c) return fail(FRT_ERR_INVALID_ARG, "counts: null");
-    const SceneBuilder& b = s->b;
-    c[0] = (uint32_t)b.tris.size(); c[1] = (uint32_t)b.instances.size(); c[2] = (uint32_t)b.materials.size(); c[3] = (uint32_t)b.lights.size();
-    c[4] = (uint32_t)b.mesh_infos.size(); c[5] = (uint32_t)b.attributes.size(); c[6] = (uint32_t)b.indices.size(); c[7] = (uint32_t)b.bvh2.size();
-    return FRT_OK;
-}
-int frt_scene_get(const frt_scene* s, int which, void* out) {
-    if (!s || !out) return fail(FRT_ERR_INVALID_ARG, "get: null");
-    const SceneBuilder& b = s->b;
-    switch (which) {
-    case 0: memcpy(out, b.tris.data(), b.tris.size() * sizeof(TriRec)); break;
-    case 1: memcpy(out, b.tri_instance.data(), b.tri_instance.size() * 4); break;
-    case 2: memcpy(out, b.materials.data(), b.materials.size() * 64); break;
-    case 3: memcpy(out, b.lights.data(), b.lights.size() * 64); break;
-    case 4: memcpy(out, b.attributes.data(), b.attributes.size() * 32); break;
-    case 5: memcpy(out, b.indices.data(), b.indices.size() * 4); break;
-    case 6: memcpy(out, b.mesh_infos.data(), b.mesh_infos.size() * 16); break;
-    case 7: {
-        uint8_t* p = (uint8_t*)out;
-        for (const InstanceRec& in : b.instances) {
-            const uint32_t h[5] = {in.mesh_id, in.mat_id, in.first_tri, in.tri_count, in.flip};
-            memcpy(p, h, 20); memcpy(p + 20, in.m, 64); memcpy(p + 84, in.w2o, 36); p += 120;
-        }
-    } break;
-    case 8: memcpy(out, b.bvh2.data(), b.bvh2.size() * sizeof(frt_bvh2_node)); break;
-    case 9: memcpy(out, b.bvh2_tri_index.data(), b.bvh2_tri_index.size() * 4); break;
-    case 10: memcpy(out, b.quad_nodes.data(), b.quad_nodes.size() * sizeof(QuadNode)); break;
-    case 11: b.ensure_wide8(); memcpy(out, b.wide8.words.data(), b.wide8.words.size() * 4); break;
-    case 12: b.ensure_wide8(); memcpy(out, b.tri_slots8.data(), b.tri_slots8.size() * sizeof(TriSlot)); break;
-    case 13: memcpy(out, b.tri_slots.data(), b.tri_slots.size() * sizeof(TriSlot)); break;
-    case 14: b.ensure_wide8(); memcpy(out, b.wide8.child_boxes.data(), b.wide8.child_boxes.size() * 4); break;
-    case 15: memcpy(out, b.pair_nodes.data(), b.pair_nodes.size() * sizeof(PairNode)); break;
-    case 16: memcpy(out, b.instances_dev.data(), b.instances_dev.size() * sizeof(InstanceDev)); break;
-    case 17: memcpy(out, b.shade_tris.data(), b.shade_tris.size() * sizeof(ShadeTri)); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "get: unknown selector");
-    }
-    return FRT_OK;
-}
-int frt_scene_bvh_stats(const frt_scene* s, uint32_t st[4]) {
-    if (!s || !st) return fail(FRT_ERR_INVALID_ARG, "bvh_stats: null");
-    st[0] = s->b.bvh_depth; st[1] = s->b.bvh_leaves; st[2] = s->b.bvh_max_leaf; st[3] = (uint32_t)s->b.pair_nodes.size();
-    return FRT_OK;
-}
-int frt_scene_tree_stats(const frt_scene* s, uint32_t st[8]) {
-    if (!s || !st) return fail(FRT_ERR_INVALID_ARG, "tree_stats: null");
-    const SceneBuilder& b = s->b;
-    b.ensure_wide8();
-    st[0] = (uint32_t)b.quad_nodes.size(); st[1] = b.quad_stack_need;
-    st[2] = b.wide8.ok ? (uint32_t)(b.wide8.words.size() / kWide8Words) : 0u; st[3] = b.wide8.stack_need; st[4] = b.wide8.depth; st[5] = b.wide8.children;
-    st[6] = (uint32_t)b.tri_slots8.size(); st[7] = b.quad_fold;
-    return FRT_OK;
-}
-void frt_camera_default(float aspect, uint32_t frame_count, uint32_t num_lights, frt_camera_uniform* out) {
-    camera_default(aspect, frame_count, num_lights, out);
-}
-int frt_camera_build_uniform(const float position[3], float yaw, float pitch, const float* prev_view_proj, float aspect, uint32_t frame_count,
-                             uint32_t num_lights, const float jitter[2], frt_camera_uniform* out, float* unjittered_view_proj) {
-    if (!position || !out || !(aspect > 0.0f)) return fail(FRT_ERR_INVALID_ARG, "camera_build_uniform: bad arguments");
-    camera_build_uniform(position, yaw, pitch, prev_view_proj, aspect, frame_count, num_lights, jitter ? jitter[0] : 0.0f, jitter ? jitter[1] : 0.0f, out, unjittered_view_proj);
-    return FRT_OK;
-}
-void frt_camera_halton_jitter(uint32_t index, uint32_t width, uint32_t height, float scale, float out[2]) { camera_halton_jitter(index, width, height, scale, out); }
 
 // ------------------------------------------------------------------------------------------------ renderer
 uint64_t frt_renderer_arena_bytes(uint32_t width, uint32_t height) { return arena_layout(width, height, nullptr); }
@@ -654,14 +236,7 @@ void frt_renderer_destroy(frt_renderer* r) {
     for (hipEvent_t e : r->event_pool) (void)hipEventDestroy(e);
     for (void* p : r->scene_allocs) (void)hipFree(p);
     rebuild_release(r->rbt.scratch);
-    if (r->rf.d_rec) (void)hipFree(r->rf.d_rec);
-    if (r->rf.h_rec) (void)hipHostFree(r->rf.h_rec);
-    if (r->rf.ev_rec) (void)hipEventDestroy(r->rf.ev_rec);
-    if (r->rf.d_def) (void)hipFree(r->rf.d_def);
-    if (r->rf.h_def) (void)hipHostFree(r->rf.h_def);
-    if (r->rf.ev_def) (void)hipEventDestroy(r->rf.ev_def);
-    if (r->qry.d) (void)hipFree(r->qry.d);
-    if (r->qry.h) (void)hipHostFree(r->qry.h);
+    for (Staging* st : {&r->rf.rec, &r->rf.def, &r->qry}) st->release();
     if (r->own_arena && r->arena) (void)hipFree(r->arena);
     if (r->extras) (void)hipFree(r->extras);
     if (r->d_counters) (void)hipFree(r->d_counters);
@@ -925,7 +500,7 @@ frt_renderer* frt_renderer_create(const frt_scene* s, uint32_t width, uint32_t h
         delete r; return nullptr;
     }
 #endif
-    if (renderer_init(r, s, o) != FRT_OK) { std::string keep = g_err; frt_renderer_destroy(r); g_err = keep; return nullptr; }
+    if (renderer_init(r, s, o) != FRT_OK) { const std::string keep = frt_last_error(); frt_renderer_destroy(r); fail(FRT_ERR_HIP, keep); return nullptr; }
     return r;
 }
 
@@ -1059,19 +634,6 @@ static int grow_queues_if_overflowed(frt_renderer* r) {
             if (rc) return rc;
         }
     }
-    return FRT_OK;
-}
-// The speculated frames are dropped, with everything speculated behind the first: order the main stream behind the work, clear its ray counts,
-// give the physical sets back; the buffers it wrote are simply overwritten by the stages that follow.
-static int drop_speculation(frt_renderer* r) {
-    if (r->specs.empty()) return FRT_OK;
-    const frt_renderer::Spec sp = r->specs.front();
-    int rc = fence_ahead(r);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(r->d_counters + C_PENDING, 0, 4 * kPending * sizeof(unsigned long long), r->stream));
-    r->logical_phys[0] = sp.logical_before[0]; r->logical_phys[1] = sp.logical_before[1];
-    r->stats.discarded_speculations += r->specs.size();
-    r->specs.clear();
     return FRT_OK;
 }
 static int open_frame(frt_renderer* r, const frt_camera_uniform* cam) {
@@ -1366,348 +928,6 @@ int frt_renderer_clear(frt_renderer* r) {
     r->qparity[0] = r->qparity[1] = 0; r->logical_phys[0] = 0; r->logical_phys[1] = 1;
     r->cur_slots = r->last_slots = GSlots{0, 1, 0}; r->before_last_slots = GSlots{1, 0, 0}; r->last_parity = 0;
     memset(&r->stats, 0, sizeof(r->stats));
-    return FRT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ moving instances
-// Ordering: every kernel that reads the scene was enqueued by a finished frame (no frame may be open). Those on the main stream precede the update
-// on it; the edge streams' spatial launches are behind the main stream's wait for ev_edge (end of every spatial stage); the ahead stream's work
-// (a speculated next frame) is fenced, and a speculation — traced under the old geometry — is dropped as if its camera had not matched. The next
-// frame's first kernel is enqueued behind the update on the main stream, or (a new speculation) on the ahead stream behind T-merge's event.
-// Both trees level by level, deepest first: launch k refits the k-th deepest level of each (after a rebuild the pair tree has no levels left).
-static int refit_levels(frt_renderer* r) {
-    const RefitState& f = r->rf;
-    const size_t lp = f.pair_levels.size() - 1, lq = f.quad_levels.size() - 1;
-    for (size_t k = 0; k < std::max(lp, lq); ++k) {
-        uint32_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
-        if (k < lp) { p0 = f.pair_levels[lp - 1 - k]; p1 = f.pair_levels[lp - k]; }
-        if (k < lq) { q0 = f.quad_levels[lq - 1 - k]; q1 = f.quad_levels[lq - k]; }
-        HIP_TRY(launch_refit_level(r->sv, f.d_ext, p0, p1, q0, q1, r->stream));
-    }
-    return FRT_OK;
-}
-static int set_instance_transforms_impl(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats) {
-    RefitState& f = r->rf;
-    FRT_DEVICE(r);
-    int rc = drop_speculation(r);
-    if (rc) return rc;
-    if (r->ahead) { r->tail_pending = true; if ((rc = fence_ahead(r))) return rc; }
-    if (n == 0) return FRT_OK;
-    // the records, in the order given (an id given twice: the later record wins, as on the host)
-    std::vector<MovedInstance> rec;
-    std::vector<int> last(f.inst.size(), -1);
-    for (uint32_t k = 0; k < n; ++k) last[ids[k]] = (int)k;
-    uint32_t work = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        if (last[ids[k]] != (int)k) continue;
-        InstanceRec& in = f.inst[ids[k]];
-        const float* m = mats + 16 * (size_t)k;
-        memcpy(in.m, m, sizeof(in.m));
-        MovedInstance mi;
-        memset(&mi, 0, sizeof(mi));
-        mi.id = ids[k]; mi.first_tri = in.first_tri; mi.tri_count = in.tri_count;
-        mi.index_offset = f.index_offset[in.mesh_id]; mi.pos_offset = f.pos_offset[in.mesh_id];
-        mi.work_begin = work; work += in.tri_count;
-        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) mi.m[3 * c + a] = m[4 * c + a];
-        InstanceDev d;
-        memset(&d, 0, sizeof(d));
-        d.mesh_id = in.mesh_id; d.mat_id = in.mat_id; d.first_tri = in.first_tri;
-        instance_inverse(m, d.w2o, d.flip);
-        memcpy(&mi.dev, &d, sizeof(d));
-        mi.light = 0xFFFFFFFFu;
-        if (in.light >= 0 && (size_t)in.light < f.lights.size()) {
-            Mat4 t; memcpy(t.m, m, sizeof(t.m));
-            const frt_light l = in.light_kind == 0 ? quad_light_record(t, f.lights[(size_t)in.light].emission) : sphere_light_record(t, f.lights[(size_t)in.light].emission);
-            mi.light = (uint32_t)in.light;
-            memcpy(&mi.light_rec, &l, sizeof(l));
-        }
-        rec.push_back(mi);
-    }
-    // staging: pinned, reused once the previous copy out of it has completed
-    if (!f.ev_rec) HIP_TRY(hipEventCreateWithFlags(&f.ev_rec, hipEventDisableTiming));
-    if (f.rec_pending) { HIP_TRY(hipEventSynchronize(f.ev_rec)); f.rec_pending = false; }
-    if (f.h_cap < rec.size()) {
-        if (f.h_rec) HIP_TRY(hipHostFree(f.h_rec));
-        f.h_rec = nullptr; f.h_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&f.h_rec, rec.size() * sizeof(MovedInstance)));
-        f.h_cap = rec.size();
-    }
-    if (f.d_cap < rec.size()) {
-        HIP_TRY(hipStreamSynchronize(r->stream));      // (an earlier update may still read the old records)
-        if (f.d_rec) HIP_TRY(hipFree(f.d_rec));
-        f.d_rec = nullptr; f.d_cap = 0;
-        HIP_TRY(hipMalloc((void**)&f.d_rec, rec.size() * sizeof(MovedInstance)));
-        f.d_cap = rec.size();
-    }
-    memcpy(f.h_rec, rec.data(), rec.size() * sizeof(MovedInstance));
-    HIP_TRY(hipMemcpyAsync(f.d_rec, f.h_rec, rec.size() * sizeof(MovedInstance), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(f.ev_rec, r->stream));
-    f.rec_pending = true;
-    RefitArgs a{f.d_rec, (uint32_t)rec.size(), work, f.d_pos, f.d_slot_of, const_cast<unsigned int*>(f.d_ext)};
-    HIP_TRY(launch_instance_transform(r->sv, a, r->stream));
-    return refit_levels(r);
-}
-int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
-    if (!r) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null");
-    if (r->failed) return fail(FRT_ERR_STATE, "set_instance_transforms: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
-    if (r->frame_open) return fail(FRT_ERR_STATE, "set_instance_transforms: a frame is open (call it between frames)");
-    if (!r->rf.ok) return fail(FRT_ERR_STATE, "set_instance_transforms: the scene's trees are not numbered breadth-first");
-#if FRT_EXPERIMENTS
-    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
-        return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: this renderer walks the 8-wide tree or the quantized pair nodes, which are not refit");
-#endif
-    const std::string bad = check_instance_transforms(n, ids, m_colmajor16, r->rf.inst.size());
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: " + bad);
-    const int rc = set_instance_transforms_impl(r, n, ids, m_colmajor16);
-    if (rc == FRT_ERR_HIP) r->failed = true;
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
-// Ordering as the instance update's. One pinned block holds what a call uploads: [positions | attributes | instance records | decoded normals];
-// the first two are copied into the replica (the object-space positions the instance update reads, SceneView::attributes), the last two into a
-// device buffer of this call's own. The block is reused once the previous call's copies out of it have completed (ev_def); the device buffer is
-// reused in stream order and replaced, after a wait for the stream, only when it has to grow.
-static int set_mesh_vertices_impl(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
-    RefitState& f = r->rf;
-    FRT_DEVICE(r);
-    int rc = drop_speculation(r);
-    if (rc) return rc;
-    if (r->ahead) { r->tail_pending = true; if ((rc = fence_ahead(r))) return rc; }
-    std::vector<DeformInstance> rec;
-    uint32_t work = 0;
-    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
-        const InstanceRec& in = f.inst[i];
-        if (in.mesh_id != mesh_id) continue;
-        DeformInstance d;
-        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
-        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
-        rec.push_back(d);
-    }
-    const size_t pos_bytes = (size_t)nverts * 16, attr_bytes = attrs ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
-    const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = attrs ? (size_t)nverts * 16 : 0;
-    const size_t up_bytes = rec_bytes + nrm_bytes, all_bytes = pos_bytes + attr_bytes + up_bytes;
-    if (!f.ev_def) HIP_TRY(hipEventCreateWithFlags(&f.ev_def, hipEventDisableTiming));
-    if (f.def_pending) { HIP_TRY(hipEventSynchronize(f.ev_def)); f.def_pending = false; }
-    if (f.h_def_cap < all_bytes) {
-        if (f.h_def) HIP_TRY(hipHostFree(f.h_def));
-        f.h_def = nullptr; f.h_def_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&f.h_def, all_bytes));
-        f.h_def_cap = all_bytes;
-    }
-    if (f.d_def_cap < up_bytes) {
-        HIP_TRY(hipStreamSynchronize(r->stream));      // (an earlier update may still read the old buffer)
-        if (f.d_def) HIP_TRY(hipFree(f.d_def));
-        f.d_def = nullptr; f.d_def_cap = 0;
-        HIP_TRY(hipMalloc((void**)&f.d_def, up_bytes));
-        f.d_def_cap = up_bytes;
-    }
-    uint8_t* h_pos = f.h_def; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes;
-    memcpy(h_pos, pos4, pos_bytes);
-    if (attrs) {
-        memcpy(h_attr, attrs, attr_bytes);
-        float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
-        for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
-    }
-    if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
-    HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
-    if (attrs) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
-    if (up_bytes) HIP_TRY(hipMemcpyAsync(f.d_def, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipEventRecord(f.ev_def, r->stream));
-    f.def_pending = true;
-    if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
-    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.d_def), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
-                 f.d_pos, attrs ? reinterpret_cast<const float4*>(f.d_def + rec_bytes) : nullptr, f.d_slot_of};
-    HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
-    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
-    return refit_levels(r);
-}
-int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
-    if (!r) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null");
-    if (r->failed) return fail(FRT_ERR_STATE, "set_mesh_vertices: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
-    if (r->frame_open) return fail(FRT_ERR_STATE, "set_mesh_vertices: a frame is open (call it between frames)");
-    if (!r->rf.ok) return fail(FRT_ERR_STATE, "set_mesh_vertices: the scene's trees are not numbered breadth-first");
-#if FRT_EXPERIMENTS
-    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: this renderer walks the 8-wide tree or the quantized pair nodes, which are not refit");
-#endif
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
-    const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
-    const int rc = set_mesh_vertices_impl(r, mesh_id, pos4, attrs, nverts);
-    if (rc == FRT_ERR_HIP) r->failed = true;
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------------ tree rebuild ("Rebuild")
-// Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
-// frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
-// reads the buffers that left the replica; they stay allocated and are what the next rebuild builds into.
-static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
-    RebuildState& b = r->rbt;
-    SceneView& sv = r->sv;
-    FRT_DEVICE(r);
-    if (r->ahead) { r->tail_pending = true; const int rc = fence_ahead(r); if (rc) return rc; }
-    const uint32_t N = sv.num_tris;
-    auto alloc = [&](size_t bytes, void** out) {
-        HIP_TRY(hipMalloc(out, std::max<size_t>(bytes, 16)));
-        r->scene_allocs.push_back(*out);
-        b.device_bytes += bytes;
-        return (int)FRT_OK;
-    };
-    int rc;
-    if (!b.tris) {
-        HIP_TRY(rebuild_reserve(b.scratch, N));
-        b.device_bytes += b.scratch.bytes;
-        if ((rc = alloc((size_t)N * sizeof(TriSlot), (void**)&b.tris))) return rc;
-        if ((rc = alloc((size_t)N * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
-    }
-    if (mode == FRT_REBUILD_SAH && N > 2u) {      // the refined mode's own scratch, at its first call only
-        const size_t had = b.scratch.ploc.bytes;
-        HIP_TRY(ploc_reserve(b.scratch, N));
-        b.device_bytes += b.scratch.ploc.bytes - had;
-    }
-    const int t = sv.nodes4 == b.nodes[0] ? 1 : 0;
-    if (!b.nodes[t] && (rc = alloc((size_t)rebuild_max_nodes(N) * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
-    const RebuildTarget target{b.tris, b.nodes[t], b.slot_of};
-    RebuildResult res;
-    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res, mode));
-    b.last[0] = mode; b.last[1] = res.iterations; b.last[2] = res.fell_back; b.last[3] = (uint32_t)((b.scratch.ploc.bytes + 1023u) >> 10);
-    if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, "rebuild_tree: the tree could not be numbered (nothing changed)");
-    // the kernels have no overflow check: the bound is hard, and it is checked before anything of the replica changes
-    if (res.stack_need > (uint32_t)kStackDepth - 1u)
-        return fail(FRT_ERR_LIMIT, "rebuild_tree: the new tree needs " + std::to_string(res.stack_need) + " traversal-stack entries, " + std::to_string(kStackDepth - 1) + " is the limit (nothing changed)");
-    b.tris = const_cast<float4*>(sv.tris); b.slot_of = const_cast<uint32_t*>(r->rf.d_slot_of);
-    sv.tris = target.tris; r->rf.d_slot_of = target.slot_of;
-    sv.nodes4 = target.nodes; sv.num_nodes4 = res.num_nodes;
-    r->rf.quad_levels = res.levels;
-    r->rf.pair_levels.assign(1, 0u);       // later refits skip the pair levels
-    r->rf.ok = true;
-    r->wg_rows = res.stack_need + 1u;
-    r->vote = res.num_nodes >= kVoteMinQuadNodes;
-    b.done = true; b.origin = res.origin;
-    return FRT_OK;
-}
-int frt_renderer_rebuild_tree(frt_renderer* r) { return frt_renderer_rebuild_tree_ex(r, FRT_REBUILD_MORTON); }
-int frt_renderer_rebuild_tree_ex(frt_renderer* r, uint32_t mode) {
-    if (!r) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: null");
-    if (r->failed) return fail(FRT_ERR_STATE, "rebuild_tree: an earlier frame failed in the middle of its stages; call frt_renderer_clear");
-    if (r->frame_open) return fail(FRT_ERR_STATE, "rebuild_tree: a frame is open (call it between frames)");
-#if FRT_EXPERIMENTS
-    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident)
-        return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: this renderer walks the 8-wide tree or the quantized pair nodes, which are not rebuilt");
-    if ((r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill)
-        return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: this renderer's kernels walk the pair tree, which is not rebuilt");
-#endif
-    if (mode != FRT_REBUILD_MORTON && mode != FRT_REBUILD_SAH) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: unknown mode (FRT_REBUILD_MORTON, FRT_REBUILD_SAH)");
-    const int rc = rebuild_tree_impl(r, mode);
-    if (rc == FRT_ERR_HIP) r->failed = true;
-    return rc;
-}
-// ------------------------------------------------------------------------------------------------ ray queries
-// Ordering: a query is enqueued on the main stream and only reads the scene replica. Every writer of the replica is on that stream too: the instance
-// update and the deformation (their copies, kernels and refit levels; the ahead stream is fenced into the main stream before them), and the rebuild,
-// whose kernels run there and which waits for the stream before it swaps the buffers — so the buffers a rebuild builds into are the ones that left the
-// replica at the previous rebuild's wait, behind which no query can read them, and a query enqueued after the swap reads the new ones. The frame's
-// own kernels on the other streams read the scene as well and write none of it. Nothing here touches frame state, counters, queues or a speculation.
-enum { kQueryClosest = 0, kQueryAny = 1, kQueryPick = 2 };
-static int query_impl(frt_renderer* r, int kind, const frt_camera_uniform* cam, uint32_t n, const void* in, void* out, uint32_t flags, const char* what) {
-    const std::string w(what);
-    if (!r) return fail(FRT_ERR_INVALID_ARG, w + ": null renderer");
-    if (flags & ~FRT_QUERY_DEVICE) return fail(FRT_ERR_INVALID_ARG, w + ": unknown flag (FRT_QUERY_DEVICE)");
-    if (n > kQueryMaxRays) return fail(FRT_ERR_INVALID_ARG, w + ": more than 2^26 rays in one call");
-#if FRT_EXPERIMENTS
-    if (r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident || (r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill)
-        return fail(FRT_ERR_INVALID_ARG, w + ": this renderer's kernels do not walk the quad tree, which is the tree a query walks");
-#endif
-    if (n == 0) return FRT_OK;
-    if (!in || !out || (kind == kQueryPick && !cam)) return fail(FRT_ERR_INVALID_ARG, w + ": null pointer");
-    if (r->failed) return fail(FRT_ERR_STATE, w + ": an earlier frame failed in the middle of its stages; call frt_renderer_clear");
-    const size_t in_bytes = (size_t)n * (kind == kQueryPick ? 8u : 32u), out_bytes = (size_t)n * (kind == kQueryAny ? 1u : 32u);
-    CameraView cv{};
-    if (kind == kQueryPick) memcpy(&cv, cam, sizeof(cv));
-    auto launch = [&](const void* d_in, void* d_out) {
-        // (vote and wg_rows as they are NOW: a rebuild changes both with the tree)
-        if (kind == kQueryClosest) return launch_query_closest(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
-        if (kind == kQueryAny) return launch_query_any(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
-        return launch_query_pick(r->sv, r->vote, r->wg_rows, cv, r->W, r->H, n, d_in, d_out, r->stream);
-    };
-    if (flags & FRT_QUERY_DEVICE) {
-        if (((uintptr_t)in & 15u) || (kind != kQueryAny && ((uintptr_t)out & 15u))) return fail(FRT_ERR_INVALID_ARG, w + ": device pointers must be 16-byte aligned");
-        FRT_DEVICE(r);
-        HIP_TRY(launch(in, out));
-        return FRT_OK;
-    }
-    if (kind == kQueryPick) {
-        const uint32_t* xy = static_cast<const uint32_t*>(in);
-        for (uint32_t k = 0; k < n; ++k)
-            if (xy[2 * (size_t)k] >= r->W || xy[2 * (size_t)k + 1] >= r->H)
-                return fail(FRT_ERR_INVALID_ARG, w + ": pixel (" + std::to_string(xy[2 * (size_t)k]) + ", " + std::to_string(xy[2 * (size_t)k + 1]) + ") is outside the " +
-                                                     std::to_string(r->W) + " x " + std::to_string(r->H) + " frame");
-    }
-    FRT_DEVICE(r);
-    QueryState& q = r->qry;
-    const size_t out_at = (in_bytes + 255u) & ~(size_t)255u, all_bytes = out_at + out_bytes;
-    if (q.h_cap < all_bytes) {
-        if (q.h) HIP_TRY(hipHostFree(q.h));
-        q.h = nullptr; q.h_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&q.h, all_bytes));
-        q.h_cap = all_bytes;
-    }
-    if (q.d_cap < all_bytes) {
-        if (q.d) HIP_TRY(hipFree(q.d));
-        q.d = nullptr; q.d_cap = 0;
-        HIP_TRY(hipMalloc((void**)&q.d, all_bytes));
-        q.d_cap = all_bytes;
-    }
-    memcpy(q.h, in, in_bytes);
-    HIP_TRY(hipMemcpyAsync(q.d, q.h, in_bytes, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(launch(q.d, q.d + out_at));
-    HIP_TRY(hipMemcpyAsync(q.h + out_at, q.d + out_at, out_bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    memcpy(out, q.h + out_at, out_bytes);
-    return FRT_OK;
-}
-int frt_renderer_trace_closest(frt_renderer* r, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags) {
-    return query_impl(r, kQueryClosest, nullptr, n, rays, out, flags, "trace_closest");
-}
-int frt_renderer_trace_any(frt_renderer* r, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags) {
-    return query_impl(r, kQueryAny, nullptr, n, rays, occluded_out, flags, "trace_any");
-}
-int frt_renderer_pick(frt_renderer* r, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags) {
-    return query_impl(r, kQueryPick, cam, n, xy, out, flags, "pick");
-}
-
-int frt_renderer_tree_stats(frt_renderer* r, uint32_t st[4]) {
-    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer tree_stats: null");
-    st[0] = r->sv.num_nodes4; st[1] = r->wg_rows > 0u ? r->wg_rows - 1u : 0u;
-    st[2] = r->rf.quad_levels.empty() ? 0u : (uint32_t)r->rf.quad_levels.size() - 1u; st[3] = r->rbt.done ? r->rbt.origin : 0u;
-    return FRT_OK;
-}
-int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t st[4]) {
-    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer rebuild_stats: null");
-    for (int k = 0; k < 4; ++k) st[k] = r->rbt.last[k];
-    return FRT_OK;
-}
-int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
-    if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
-    const SceneView& sv = r->sv;
-    const void* src = nullptr; size_t bytes = 0;
-    switch (which) {
-    case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
-    case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
-    case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
-    case 15:
-        if (r->rbt.done) return fail(FRT_ERR_STATE, "read_scene: the pair tree is not rebuilt by frt_renderer_rebuild_tree and no longer describes the replica");
-        src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
-    case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
-    case 17: src = sv.shade_tris; bytes = (size_t)sv.num_tris * sizeof(ShadeTri); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16, 17)");
-    }
-    FRT_DEVICE(r);
-    { int rc = sync_all(r); if (rc) return rc; }
-    if (bytes) HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     return FRT_OK;
 }
 

@@ -1,0 +1,393 @@
+// frt_scene_edit.hip — what edits or reads a renderer's scene replica between frames (include/frt.h): moving instances,
+// deforming meshes, the tree rebuild, the ray queries, frt_renderer_read_scene and the tree statistics. Host code only: the kernels are in
+// frt_refit.hip, frt_deform.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
+#include "frt_renderer_state.hpp"
+
+// Level ranges of a breadth-first tree whose node i has `kids(i, out)` inner children: boundaries of the levels, or empty if the numbering is not
+// breadth-first (then the renderer cannot refit).
+template <class Kids>
+static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
+    std::vector<uint32_t> level(n, 0u), bounds(1, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t c[4]; const int k = kids(i, c);
+        for (int j = 0; j < k; ++j) { if (c[j] <= i || c[j] >= n) return {}; level[c[j]] = level[i] + 1u; }
+    }
+    for (size_t i = 1; i < n; ++i) {
+        if (level[i] < level[i - 1]) return {};
+        if (level[i] != level[i - 1]) bounds.push_back((uint32_t)i);
+    }
+    bounds.push_back((uint32_t)n);
+    return bounds;
+}
+int frt::upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
+    RefitState& f = r->rf;
+    std::vector<float> pos;
+    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear();
+    for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
+        f.pos_offset.push_back((uint32_t)(pos.size() / 4));
+        f.index_offset.push_back(b.mesh_infos[m].index_offset);
+        f.vert_count.push_back((uint32_t)(b.mesh_positions[m].size() / 4));
+        f.attr_offset.push_back(b.mesh_infos[m].vertex_offset);
+        pos.insert(pos.end(), b.mesh_positions[m].begin(), b.mesh_positions[m].end());
+    }
+    int rc;
+    if ((rc = upload(r, pos, &f.d_pos))) return rc;
+    if ((rc = upload(r, b.tri_slot_of, &f.d_slot_of))) return rc;
+    std::vector<uint32_t> word(4, 0u);
+    if ((rc = upload(r, word, &f.d_ext))) return rc;
+    f.device_bytes = pos.size() * 4 + b.tri_slot_of.size() * 4 + 16;
+    f.inst = b.instances;
+    f.lights = b.lights;
+    f.pair_levels = level_ranges(b.pair_nodes.size(), [&](size_t i, uint32_t* c) {
+        int k = 0;
+        for (int j = 0; j < 2; ++j) { uint32_t ref; memcpy(&ref, &b.pair_nodes[i].q[12 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
+        return k;
+    });
+    f.quad_levels = level_ranges(b.quad_nodes.size(), [&](size_t i, uint32_t* c) {
+        int k = 0;
+        for (int j = 0; j < 4; ++j) { uint32_t ref; memcpy(&ref, &b.quad_nodes[i].q[24 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
+        return k;
+    });
+    f.ok = !f.pair_levels.empty() && !f.quad_levels.empty();
+    return FRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ staging
+// The ray queries never synchronised their stream before they replaced their device block (a host-pointer query is synchronous: nothing of an earlier
+// one is in flight); here they do, as the two edit calls always did: one wait on an idle stream, and only at a call that grows the block.
+int Staging::reserve(size_t h_bytes, size_t d_bytes, hipStream_t stream) {
+    if (pending) { HIP_TRY(hipEventSynchronize(ev)); pending = false; }
+    if (h_cap < h_bytes) {
+        if (h) { HIP_TRY(hipHostFree(h)); h = nullptr; h_cap = 0; }
+        HIP_TRY(hipHostMalloc((void**)&h, h_bytes));
+        h_cap = h_bytes;
+    }
+    if (d_cap < d_bytes) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (d) { HIP_TRY(hipFree(d)); d = nullptr; d_cap = 0; }
+        HIP_TRY(hipMalloc((void**)&d, d_bytes));
+        d_cap = d_bytes;
+    }
+    return FRT_OK;
+}
+int Staging::mark(hipStream_t stream) {
+    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ev, stream));
+    pending = true;
+    return FRT_OK;
+}
+void Staging::release() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    if (ev) (void)hipEventDestroy(ev);
+    *this = Staging();
+}
+
+// ------------------------------------------------------------------------------------------------ entry checks, stream order
+#if FRT_EXPERIMENTS
+// lib/libfrt_exp.so only: do this renderer's kernels walk the product's quad tree? That is the tree a refit, a rebuild and a query work on; the 8-wide tree,
+// the quantized pair nodes of the resident kernels and the pair tree of the compacting, wavefront, stream and refill kernels are not kept up with it.
+static bool walks_quad_tree(const frt_renderer* r) {
+    return !(r->walk == kWalkWide || r->walk == kWalkWideLds || r->x.resident || (r->flags & FRT_FLAG_COMPACTION) || r->x.wavefront || r->x.stream_mode || r->x.refill);
+}
+#endif
+// What a call `what` refuses before it looks at its own arguments, in this order: a null handle, then the `parts` it asks for.
+enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditChecks = kNotFailed | kBetweenFrames | kQuadTree };
+static int check_entry(const frt_renderer* r, const std::string& what, unsigned parts) {
+    if (!r) return fail(FRT_ERR_INVALID_ARG, what + ": null");
+    if ((parts & kNotFailed) && r->failed) return fail(FRT_ERR_STATE, what + ": an earlier frame failed in the middle of its stages; call frt_renderer_clear");
+    if ((parts & kBetweenFrames) && r->frame_open) return fail(FRT_ERR_STATE, what + ": a frame is open (call it between frames)");
+    if ((parts & kRefit) && !r->rf.ok) return fail(FRT_ERR_STATE, what + ": the scene's trees are not numbered breadth-first");
+#if FRT_EXPERIMENTS
+    if ((parts & kQuadTree) && !walks_quad_tree(r)) return fail(FRT_ERR_INVALID_ARG, what + ": this renderer's kernels do not walk the quad tree, the only tree this call keeps up or reads");
+#endif
+    return FRT_OK;
+}
+
+// The stream order of a call that writes the scene replica (`drop`: and changes its geometry), on the main stream.
+// Ordering: every kernel that reads the scene was enqueued by a finished frame (no frame may be open). Those on the main stream precede the update
+// on it; the edge streams' spatial launches are behind the main stream's wait for ev_edge (end of every spatial stage); the ahead stream's work
+// (a speculated next frame) is fenced, and a speculation — traced under the old geometry — is dropped as if its camera had not matched. The next
+// frame's first kernel is enqueued behind the update on the main stream, or (a new speculation) on the ahead stream behind T-merge's event.
+// The fence is unconditional (tail_pending is set first): whatever the ahead stream holds, the main stream waits for it.
+static int order_behind_frames(frt_renderer* r, bool drop) {
+    if (drop) { const int rc = drop_speculation(r); if (rc) return rc; }
+    if (r->ahead) { r->tail_pending = true; return fence_ahead(r); }
+    return FRT_OK;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ moving instances
+// Ordering: order_behind_frames, the speculation dropped.
+// Both trees level by level, deepest first: launch k refits the k-th deepest level of each (after a rebuild the pair tree has no levels left).
+static int refit_levels(frt_renderer* r) {
+    const RefitState& f = r->rf;
+    const size_t lp = f.pair_levels.size() - 1, lq = f.quad_levels.size() - 1;
+    for (size_t k = 0; k < std::max(lp, lq); ++k) {
+        uint32_t p0 = 0, p1 = 0, q0 = 0, q1 = 0;
+        if (k < lp) { p0 = f.pair_levels[lp - 1 - k]; p1 = f.pair_levels[lp - k]; }
+        if (k < lq) { q0 = f.quad_levels[lq - 1 - k]; q1 = f.quad_levels[lq - k]; }
+        HIP_TRY(launch_refit_level(r->sv, f.d_ext, p0, p1, q0, q1, r->stream));
+    }
+    return FRT_OK;
+}
+static int set_instance_transforms_impl(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    if (n == 0) return FRT_OK;
+    // the records, in the order given (an id given twice: the later record wins, as on the host)
+    std::vector<MovedInstance> rec;
+    std::vector<int> last(f.inst.size(), -1);
+    for (uint32_t k = 0; k < n; ++k) last[ids[k]] = (int)k;
+    uint32_t work = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (last[ids[k]] != (int)k) continue;
+        InstanceRec& in = f.inst[ids[k]];
+        const float* m = mats + 16 * (size_t)k;
+        memcpy(in.m, m, sizeof(in.m));
+        MovedInstance mi;
+        memset(&mi, 0, sizeof(mi));
+        mi.id = ids[k]; mi.first_tri = in.first_tri; mi.tri_count = in.tri_count;
+        mi.index_offset = f.index_offset[in.mesh_id]; mi.pos_offset = f.pos_offset[in.mesh_id];
+        mi.work_begin = work; work += in.tri_count;
+        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) mi.m[3 * c + a] = m[4 * c + a];
+        InstanceDev d;
+        memset(&d, 0, sizeof(d));
+        d.mesh_id = in.mesh_id; d.mat_id = in.mat_id; d.first_tri = in.first_tri;
+        instance_inverse(m, d.w2o, d.flip);
+        memcpy(&mi.dev, &d, sizeof(d));
+        mi.light = 0xFFFFFFFFu;
+        if (in.light >= 0 && (size_t)in.light < f.lights.size()) {
+            Mat4 t; memcpy(t.m, m, sizeof(t.m));
+            const frt_light l = in.light_kind == 0 ? quad_light_record(t, f.lights[(size_t)in.light].emission) : sphere_light_record(t, f.lights[(size_t)in.light].emission);
+            mi.light = (uint32_t)in.light;
+            memcpy(&mi.light_rec, &l, sizeof(l));
+        }
+        rec.push_back(mi);
+    }
+    // staging: pinned, reused once the previous copy out of it has completed
+    const size_t rec_bytes = rec.size() * sizeof(MovedInstance);
+    if ((rc = f.rec.reserve(rec_bytes, rec_bytes, r->stream))) return rc;
+    memcpy(f.rec.h, rec.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(f.rec.d, f.rec.h, rec_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = f.rec.mark(r->stream))) return rc;
+    RefitArgs a{reinterpret_cast<const MovedInstance*>(f.rec.d), (uint32_t)rec.size(), work, f.d_pos, f.d_slot_of, const_cast<unsigned int*>(f.d_ext)};
+    HIP_TRY(launch_instance_transform(r->sv, a, r->stream));
+    return refit_levels(r);
+}
+int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
+    if (const int rc = check_entry(r, "set_instance_transforms", kEditChecks | kRefit)) return rc;
+    const std::string bad = check_instance_transforms(n, ids, m_colmajor16, r->rf.inst.size());
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: " + bad);
+    const int rc = set_instance_transforms_impl(r, n, ids, m_colmajor16);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
+// Ordering as the instance update's. One pinned block holds what a call uploads: [positions | attributes | instance records | decoded normals];
+// the first two are copied into the replica (the object-space positions the instance update reads, SceneView::attributes), the last two into a
+// device buffer of this call's own. The block is reused once the previous call's copies out of it have completed (Staging::ev); the device buffer is
+// reused in stream order and replaced, after a wait for the stream, only when it has to grow.
+static int set_mesh_vertices_impl(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    std::vector<DeformInstance> rec;
+    uint32_t work = 0;
+    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
+        const InstanceRec& in = f.inst[i];
+        if (in.mesh_id != mesh_id) continue;
+        DeformInstance d;
+        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
+        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
+        rec.push_back(d);
+    }
+    const size_t pos_bytes = (size_t)nverts * 16, attr_bytes = attrs ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
+    const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = attrs ? (size_t)nverts * 16 : 0;
+    const size_t up_bytes = rec_bytes + nrm_bytes, all_bytes = pos_bytes + attr_bytes + up_bytes;
+    if ((rc = f.def.reserve(all_bytes, up_bytes, r->stream))) return rc;
+    uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes;
+    memcpy(h_pos, pos4, pos_bytes);
+    if (attrs) {
+        memcpy(h_attr, attrs, attr_bytes);
+        float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
+        for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
+    }
+    if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
+    if (attrs) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
+    if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = f.def.mark(r->stream))) return rc;
+    if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
+    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+                 f.d_pos, attrs ? reinterpret_cast<const float4*>(f.def.d + rec_bytes) : nullptr, f.d_slot_of};
+    HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
+    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
+    return refit_levels(r);
+}
+int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    if (const int rc = check_entry(r, "set_mesh_vertices", kEditChecks | kRefit)) return rc;
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
+    const int rc = set_mesh_vertices_impl(r, mesh_id, pos4, attrs, nverts);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ tree rebuild ("Rebuild")
+// Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
+// frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
+// reads the buffers that left the replica; they stay allocated and are what the next rebuild builds into.
+static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
+    RebuildState& b = r->rbt;
+    SceneView& sv = r->sv;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, false);
+    if (rc) return rc;
+    const uint32_t N = sv.num_tris;
+    auto alloc = [&](size_t bytes, void** out) {
+        HIP_TRY(hipMalloc(out, std::max<size_t>(bytes, 16)));
+        r->scene_allocs.push_back(*out);
+        b.device_bytes += bytes;
+        return (int)FRT_OK;
+    };
+    if (!b.tris) {
+        HIP_TRY(rebuild_reserve(b.scratch, N));
+        b.device_bytes += b.scratch.bytes;
+        if ((rc = alloc((size_t)N * sizeof(TriSlot), (void**)&b.tris))) return rc;
+        if ((rc = alloc((size_t)N * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
+    }
+    if (mode == FRT_REBUILD_SAH && N > 2u) {      // the refined mode's own scratch, at its first call only
+        const size_t had = b.scratch.ploc.bytes;
+        HIP_TRY(ploc_reserve(b.scratch, N));
+        b.device_bytes += b.scratch.ploc.bytes - had;
+    }
+    const int t = sv.nodes4 == b.nodes[0] ? 1 : 0;
+    if (!b.nodes[t] && (rc = alloc((size_t)rebuild_max_nodes(N) * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
+    const RebuildTarget target{b.tris, b.nodes[t], b.slot_of};
+    RebuildResult res;
+    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res, mode));
+    b.last[0] = mode; b.last[1] = res.iterations; b.last[2] = res.fell_back; b.last[3] = (uint32_t)((b.scratch.ploc.bytes + 1023u) >> 10);
+    if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, "rebuild_tree: the tree could not be numbered (nothing changed)");
+    // the kernels have no overflow check: the bound is hard, and it is checked before anything of the replica changes
+    if (res.stack_need > (uint32_t)kStackDepth - 1u)
+        return fail(FRT_ERR_LIMIT, "rebuild_tree: the new tree needs " + std::to_string(res.stack_need) + " traversal-stack entries, " + std::to_string(kStackDepth - 1) + " is the limit (nothing changed)");
+    b.tris = const_cast<float4*>(sv.tris); b.slot_of = const_cast<uint32_t*>(r->rf.d_slot_of);
+    sv.tris = target.tris; r->rf.d_slot_of = target.slot_of;
+    sv.nodes4 = target.nodes; sv.num_nodes4 = res.num_nodes;
+    r->rf.quad_levels = res.levels;
+    r->rf.pair_levels.assign(1, 0u);       // later refits skip the pair levels
+    r->rf.ok = true;
+    r->wg_rows = res.stack_need + 1u;
+    r->vote = res.num_nodes >= kVoteMinQuadNodes;
+    b.done = true; b.origin = res.origin;
+    return FRT_OK;
+}
+int frt_renderer_rebuild_tree(frt_renderer* r) { return frt_renderer_rebuild_tree_ex(r, FRT_REBUILD_MORTON); }
+int frt_renderer_rebuild_tree_ex(frt_renderer* r, uint32_t mode) {
+    if (const int rc = check_entry(r, "rebuild_tree", kEditChecks)) return rc;
+    if (mode != FRT_REBUILD_MORTON && mode != FRT_REBUILD_SAH) return fail(FRT_ERR_INVALID_ARG, "rebuild_tree: unknown mode (FRT_REBUILD_MORTON, FRT_REBUILD_SAH)");
+    const int rc = rebuild_tree_impl(r, mode);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+// ------------------------------------------------------------------------------------------------ ray queries
+// Ordering: a query is enqueued on the main stream and only reads the scene replica. Every writer of the replica is on that stream too: the instance
+// update and the deformation (their copies, kernels and refit levels; the ahead stream is fenced into the main stream before them), and the rebuild,
+// whose kernels run there and which waits for the stream before it swaps the buffers — so the buffers a rebuild builds into are the ones that left the
+// replica at the previous rebuild's wait, behind which no query can read them, and a query enqueued after the swap reads the new ones. The frame's
+// own kernels on the other streams read the scene as well and write none of it. Nothing here touches frame state, counters, queues or a speculation.
+enum { kQueryClosest = 0, kQueryAny = 1, kQueryPick = 2 };
+static int query_impl(frt_renderer* r, int kind, const frt_camera_uniform* cam, uint32_t n, const void* in, void* out, uint32_t flags, const char* what) {
+    const std::string w(what);
+    if (!r) return fail(FRT_ERR_INVALID_ARG, w + ": null renderer");
+    if (flags & ~FRT_QUERY_DEVICE) return fail(FRT_ERR_INVALID_ARG, w + ": unknown flag (FRT_QUERY_DEVICE)");
+    if (n > kQueryMaxRays) return fail(FRT_ERR_INVALID_ARG, w + ": more than 2^26 rays in one call");
+    if (const int rc = check_entry(r, w, kQuadTree)) return rc;
+    if (n == 0) return FRT_OK;
+    if (!in || !out || (kind == kQueryPick && !cam)) return fail(FRT_ERR_INVALID_ARG, w + ": null pointer");
+    if (const int rc = check_entry(r, w, kNotFailed)) return rc;      // (a query may run while a frame is open, and needs no level ranges)
+    const size_t in_bytes = (size_t)n * (kind == kQueryPick ? 8u : 32u), out_bytes = (size_t)n * (kind == kQueryAny ? 1u : 32u);
+    CameraView cv{};
+    if (kind == kQueryPick) memcpy(&cv, cam, sizeof(cv));
+    auto launch = [&](const void* d_in, void* d_out) {
+        // (vote and wg_rows as they are NOW: a rebuild changes both with the tree)
+        if (kind == kQueryClosest) return launch_query_closest(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
+        if (kind == kQueryAny) return launch_query_any(r->sv, r->vote, r->wg_rows, n, d_in, d_out, r->stream);
+        return launch_query_pick(r->sv, r->vote, r->wg_rows, cv, r->W, r->H, n, d_in, d_out, r->stream);
+    };
+    if (flags & FRT_QUERY_DEVICE) {
+        if (((uintptr_t)in & 15u) || (kind != kQueryAny && ((uintptr_t)out & 15u))) return fail(FRT_ERR_INVALID_ARG, w + ": device pointers must be 16-byte aligned");
+        FRT_DEVICE(r);
+        HIP_TRY(launch(in, out));
+        return FRT_OK;
+    }
+    if (kind == kQueryPick) {
+        const uint32_t* xy = static_cast<const uint32_t*>(in);
+        for (uint32_t k = 0; k < n; ++k)
+            if (xy[2 * (size_t)k] >= r->W || xy[2 * (size_t)k + 1] >= r->H)
+                return fail(FRT_ERR_INVALID_ARG, w + ": pixel (" + std::to_string(xy[2 * (size_t)k]) + ", " + std::to_string(xy[2 * (size_t)k + 1]) + ") is outside the " +
+                                                     std::to_string(r->W) + " x " + std::to_string(r->H) + " frame");
+    }
+    FRT_DEVICE(r);
+    Staging& q = r->qry;
+    const size_t out_at = (in_bytes + 255u) & ~(size_t)255u, all_bytes = out_at + out_bytes;
+    if (const int rc = q.reserve(all_bytes, all_bytes, r->stream)) return rc;      // (never marked: the call waits for its own copies below)
+    memcpy(q.h, in, in_bytes);
+    HIP_TRY(hipMemcpyAsync(q.d, q.h, in_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(launch(q.d, q.d + out_at));
+    HIP_TRY(hipMemcpyAsync(q.h + out_at, q.d + out_at, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    memcpy(out, q.h + out_at, out_bytes);
+    return FRT_OK;
+}
+int frt_renderer_trace_closest(frt_renderer* r, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags) {
+    return query_impl(r, kQueryClosest, nullptr, n, rays, out, flags, "trace_closest");
+}
+int frt_renderer_trace_any(frt_renderer* r, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags) {
+    return query_impl(r, kQueryAny, nullptr, n, rays, occluded_out, flags, "trace_any");
+}
+int frt_renderer_pick(frt_renderer* r, const frt_camera_uniform* cam, uint32_t n, const uint32_t* xy, frt_ray_hit* out, uint32_t flags) {
+    return query_impl(r, kQueryPick, cam, n, xy, out, flags, "pick");
+}
+
+int frt_renderer_tree_stats(frt_renderer* r, uint32_t st[4]) {
+    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer tree_stats: null");
+    st[0] = r->sv.num_nodes4; st[1] = r->wg_rows > 0u ? r->wg_rows - 1u : 0u;
+    st[2] = r->rf.quad_levels.empty() ? 0u : (uint32_t)r->rf.quad_levels.size() - 1u; st[3] = r->rbt.done ? r->rbt.origin : 0u;
+    return FRT_OK;
+}
+int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t st[4]) {
+    if (!r || !st) return fail(FRT_ERR_INVALID_ARG, "renderer rebuild_stats: null");
+    for (int k = 0; k < 4; ++k) st[k] = r->rbt.last[k];
+    return FRT_OK;
+}
+int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
+    if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
+    const SceneView& sv = r->sv;
+    const void* src = nullptr; size_t bytes = 0;
+    switch (which) {
+    case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
+    case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
+    case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
+    case 15:
+        if (r->rbt.done) return fail(FRT_ERR_STATE, "read_scene: the pair tree is not rebuilt by frt_renderer_rebuild_tree and no longer describes the replica");
+        src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
+    case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
+    case 17: src = sv.shade_tris; bytes = (size_t)sv.num_tris * sizeof(ShadeTri); break;
+    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16, 17)");
+    }
+    FRT_DEVICE(r);
+    { int rc = sync_all(r); if (rc) return rc; }
+    if (bytes) HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+
+} // extern "C"

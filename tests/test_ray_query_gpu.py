@@ -16,7 +16,7 @@ from test_ray_query import family, degenerate_rays, MISS, RANGES, INVALID_ARG
 pytestmark = pytest.mark.gpu
 W, H = 32, 24
 FIELDS = ("t", "u", "v", "tri", "instance", "material", "primitive", "front")
-VOTE_MIN_QUAD_NODES = 32768      # csrc/frt_renderer.hip: kVoteMinQuadNodes — trees of at least this many quad nodes are walked by the voting loop
+VOTE_MIN_QUAD_NODES = 32768      # csrc/frt_renderer_state.hpp: kVoteMinQuadNodes — trees of at least this many quad nodes are walked by the voting loop
 
 
 def words(h):
