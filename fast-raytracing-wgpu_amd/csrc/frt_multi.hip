@@ -448,6 +448,19 @@ int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
     return edit_every_replica(m, "multi set_mesh_vertices", [&](frt_renderer* r) { return frt_renderer_set_mesh_vertices(r, mesh_id, pos4, attrs, nverts); });
 }
+// The material, light and texture edits on every strip's replica, as above.
+int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials) {
+    return edit_every_replica(m, "multi set_materials", [&](frt_renderer* r) { return frt_renderer_set_materials(r, n, ids, materials); });
+}
+int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids) {
+    return edit_every_replica(m, "multi set_instance_materials", [&](frt_renderer* r) { return frt_renderer_set_instance_materials(r, n, instance_ids, material_ids); });
+}
+int frt_multi_renderer_set_light_emission(frt_multi_renderer* m, uint32_t light, const float color[3], float intensity) {
+    return edit_every_replica(m, "multi set_light_emission", [&](frt_renderer* r) { return frt_renderer_set_light_emission(r, light, color, intensity); });
+}
+int frt_multi_renderer_set_texture(frt_multi_renderer* m, int kind, uint32_t layer, const uint8_t* rgba8) {
+    return edit_every_replica(m, "multi set_texture", [&](frt_renderer* r) { return frt_renderer_set_texture(r, kind, layer, rgba8); });
+}
 
 // Every strip rebuilds its own replica's tree (frt_renderer_rebuild_tree: synchronous per strip). The replicas hold the same triangles, so the strips
 // build the same tree. State and renderer kind are checked on the first strip before any replica changes.

@@ -4,6 +4,7 @@
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
+#include "frt_material_edit.hpp"
 #include "frt_query.hpp"        // (frt_scene.hpp, frt_kernels.hpp)
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -117,6 +118,7 @@ struct RefitState {
     // [positions | attributes | instance records | decoded normals], on the device the last two.
     std::vector<uint32_t> vert_count, attr_offset;
     Staging def;
+    uint32_t color_layers = 0, data_layers = 0;   // texture layers of the replica (the material and texture edits check against them)
     uint64_t device_bytes = 0;
 };
 
@@ -200,6 +202,8 @@ struct frt_renderer {
     // The host-pointer ray queries: both blocks [input | output] of a call. Such a call is synchronous — the last call's copies are done
     // when the next one starts — so this one is never marked: no event is created, recorded or waited for.
     Staging qry;
+    // The material, light and texture edits: the pinned block of one call and, for frt_renderer_set_instance_materials, its records on the device.
+    Staging look;
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };

@@ -192,7 +192,7 @@ MaterialBuilder::MaterialBuilder(float r, float g, float b, float a) {
 }
 
 // ---------------------------------------------------------------------------------------------- builder.rs
-static const size_t kTexBytes = 1024u * 1024u * 4u;   // src/scene/mod.rs:12-13
+static const size_t kTexBytes = kTextureLayerBytes;
 
 static std::vector<uint8_t> make_texture(uint8_t (*fn)(uint32_t, uint32_t, int)) {
     std::vector<uint8_t> t(kTexBytes);
@@ -272,9 +272,13 @@ frt_light sphere_light_record(const Mat4& t, const float emission[4]) {
     float scale = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
     return make_sphere_light(&t.m[12], scale * 0.5f, emission);
 }
+void light_emissive_factor(const float color[3], float intensity, float out[3]) {
+    for (int k = 0; k < 3; ++k) out[k] = color[k] * intensity;
+}
 static frt_material emissive_material(size_t light_index, const float color[3], float intensity) {
-    return MaterialBuilder(1, 1, 1, 1).light_index((int32_t)light_index)
-        .emissive_factor(color[0] * intensity, color[1] * intensity, color[2] * intensity).texture(0);
+    float e[3];
+    light_emissive_factor(color, intensity, e);
+    return MaterialBuilder(1, 1, 1, 1).light_index((int32_t)light_index).emissive_factor(e[0], e[1], e[2]).texture(0);
 }
 void SceneBuilder::register_quad_light(uint32_t mesh_id, const Mat4& t, const float color[3], float intensity) {
     uint32_t mat = add_material(emissive_material(lights.size(), color, intensity));
@@ -414,21 +418,95 @@ int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const f
     return FRT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- materials, lights, textures
+std::string check_material(const frt_material& m, size_t color_layers, size_t data_layers, size_t num_lights) {
+    std::string bad;
+    const struct { uint32_t id; size_t layers; const char* what; } slots[5] = {
+        {m.tex_info_0 & 0xFFFFu, color_layers, "base colour"}, {m.tex_info_0 >> 16, data_layers, "normal"},
+        {m.tex_info_1 & 0xFFFFu, data_layers, "occlusion"}, {m.tex_info_1 >> 16, color_layers, "emissive"},
+        {m.tex_info_2 & 0xFFFFu, data_layers, "metallic-roughness"}};
+    for (const auto& t : slots)
+        if (t.id != 0xFFFFu && t.id >= t.layers)
+            bad = std::string(t.what) + " texture layer " + std::to_string(t.id) + " does not exist (" + std::to_string(t.layers) + " layers)";
+    if (m.light_index >= 0 && (size_t)m.light_index >= num_lights)
+        bad = "light_index " + std::to_string(m.light_index) + " does not exist (" + std::to_string(num_lights) + " lights)";
+    return bad;
+}
+std::string check_set_materials(uint32_t n, const uint32_t* ids, const frt_material* mats, size_t num_materials, size_t color_layers, size_t data_layers, size_t num_lights) {
+    if (n > 0 && (!ids || !mats)) return "null ids or materials";
+    for (uint32_t k = 0; k < n; ++k) {
+        if (ids[k] >= num_materials) return "material id " + std::to_string(ids[k]) + " out of range (" + std::to_string(num_materials) + " materials)";
+        const std::string bad = check_material(mats[k], color_layers, data_layers, num_lights);
+        if (!bad.empty()) return "material " + std::to_string(ids[k]) + ": " + bad;
+    }
+    return "";
+}
+std::string check_set_instance_materials(uint32_t n, const uint32_t* iids, const uint32_t* mids, const std::vector<InstanceRec>& instances, size_t num_materials) {
+    if (n > 0 && (!iids || !mids)) return "null instance or material ids";
+    for (uint32_t k = 0; k < n; ++k) {
+        if (iids[k] >= instances.size()) return "instance id " + std::to_string(iids[k]) + " out of range (" + std::to_string(instances.size()) + " instances)";
+        if (mids[k] >= num_materials) return "material id " + std::to_string(mids[k]) + " out of range (" + std::to_string(num_materials) + " materials)";
+        if (instances[iids[k]].light >= 0)
+            return "instance " + std::to_string(iids[k]) + " was registered with light " + std::to_string(instances[iids[k]].light) + ": its material carries the light link (set_light_emission edits it)";
+    }
+    return "";
+}
+std::string check_set_texture(int kind, uint32_t layer, const uint8_t* rgba8, size_t color_layers, size_t data_layers) {
+    if (kind != 0 && kind != 1) return "kind must be 0 (colour) or 1 (data)";
+    if (!rgba8) return "null pixels";
+    const size_t layers = kind == 0 ? color_layers : data_layers;
+    if (layer >= layers) return std::string(kind == 0 ? "colour" : "data") + " layer " + std::to_string(layer) + " does not exist (" + std::to_string(layers) + " layers)";
+    return "";
+}
+int light_instance(const std::vector<InstanceRec>& instances, uint32_t light) {
+    for (size_t i = 0; i < instances.size(); ++i) if (instances[i].light >= 0 && (uint32_t)instances[i].light == light) return (int)i;
+    return -1;
+}
+
+int SceneBuilder::set_materials(uint32_t n, const uint32_t* ids, const frt_material* mats) {
+    if (!built) { error = "set_materials: scene is not built"; return FRT_ERR_STATE; }
+    const std::string bad = check_set_materials(n, ids, mats, materials.size(), color_textures.size(), data_textures.size(), lights.size());
+    if (!bad.empty()) { error = "set_materials: " + bad; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) materials[ids[k]] = mats[k];      // in order: an id given twice ends with its last value
+    return FRT_OK;
+}
+int SceneBuilder::set_instance_materials(uint32_t n, const uint32_t* iids, const uint32_t* mids) {
+    if (!built) { error = "set_instance_materials: scene is not built"; return FRT_ERR_STATE; }
+    const std::string bad = check_set_instance_materials(n, iids, mids, instances, materials.size());
+    if (!bad.empty()) { error = "set_instance_materials: " + bad; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) {      // in order, as above
+        InstanceRec& in = instances[iids[k]];
+        in.mat_id = mids[k];
+        instances_dev[iids[k]].mat_id = mids[k];
+        for (uint32_t j = 0; j < in.tri_count; ++j) memcpy(&shade_tris[in.first_tri + j].q[25], &mids[k], 4);      // the word write_shade_tri writes
+    }
+    return FRT_OK;
+}
+int SceneBuilder::set_light_emission(uint32_t light, const float color[3], float intensity) {
+    if (!built) { error = "set_light_emission: scene is not built"; return FRT_ERR_STATE; }
+    if (!color) { error = "set_light_emission: null colour"; return FRT_ERR_INVALID_ARG; }
+    if (light >= lights.size()) { error = "set_light_emission: light " + std::to_string(light) + " out of range (" + std::to_string(lights.size()) + " lights)"; return FRT_ERR_INVALID_ARG; }
+    const float em[4] = {color[0], color[1], color[2], intensity};
+    memcpy(lights[light].emission, em, sizeof(em));
+    const int i = light_instance(instances, light);
+    if (i >= 0 && instances[(size_t)i].mat_id < materials.size()) light_emissive_factor(color, intensity, materials[instances[(size_t)i].mat_id].emissive_factor);
+    return FRT_OK;
+}
+int SceneBuilder::set_texture(int kind, uint32_t layer, const uint8_t* rgba8) {
+    if (!built) { error = "set_texture: scene is not built"; return FRT_ERR_STATE; }
+    const std::string bad = check_set_texture(kind, layer, rgba8, color_textures.size(), data_textures.size());
+    if (!bad.empty()) { error = "set_texture: " + bad; return FRT_ERR_INVALID_ARG; }
+    (kind == 0 ? color_textures : data_textures)[layer].assign(rgba8, rgba8 + kTexBytes);
+    return FRT_OK;
+}
+
 void SceneBuilder::build() {
     error.clear();
     // Texture layers and light indices reach the kernels unchecked (sample_layer: base + layer * 4 MiB): validate them here, once.
     // wgpu would reject an out-of-range layer at bind time / clamp the fetch; here it would be an out-of-bounds read on the GPU.
     for (size_t i = 0; i < materials.size() && error.empty(); ++i) {
-        const frt_material& m = materials[i];
-        const struct { uint32_t id; size_t layers; const char* what; } slots[5] = {
-            {m.tex_info_0 & 0xFFFFu, color_textures.size(), "base colour"}, {m.tex_info_0 >> 16, data_textures.size(), "normal"},
-            {m.tex_info_1 & 0xFFFFu, data_textures.size(), "occlusion"}, {m.tex_info_1 >> 16, color_textures.size(), "emissive"},
-            {m.tex_info_2 & 0xFFFFu, data_textures.size(), "metallic-roughness"}};
-        for (const auto& t : slots)
-            if (t.id != 0xFFFFu && t.id >= t.layers)
-                error = "material " + std::to_string(i) + ": " + t.what + " texture layer " + std::to_string(t.id) + " does not exist (" + std::to_string(t.layers) + " layers)";
-        if (m.light_index >= 0 && (size_t)m.light_index >= lights.size())
-            error = "material " + std::to_string(i) + ": light_index " + std::to_string(m.light_index) + " does not exist (" + std::to_string(lights.size()) + " lights)";
+        const std::string bad = check_material(materials[i], color_textures.size(), data_textures.size(), lights.size());
+        if (!bad.empty()) error = "material " + std::to_string(i) + ": " + bad;
     }
     if (!error.empty()) { built = false; return; }
     flatten();

@@ -100,6 +100,18 @@ public:
     // every instance of the mesh recomputed under its current matrix and, when `attrs` is given, their shading records as build() computes them;
     // every box refit. attrs == nullptr keeps the attributes and the shading records. The specification the device path matches bit for bit.
     int set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+    // What a built scene LOOKS like: no triangle, slot or box moves. Each is the specification its device form matches bit for bit,
+    // validates everything before it applies anything, and leaves the scene equal to one built from scratch with the edited values.
+    // Material ids[k] becomes mats[k], under the checks build() makes on a material (check_material).
+    int set_materials(uint32_t n, const uint32_t* ids, const frt_material* mats);
+    // Instance instance_ids[k] uses material material_ids[k]: its record, its device record and word 25 of its triangles' shading records. An instance
+    // that register_*_light created is refused: its material carries the light link that set_light_emission relies on.
+    int set_instance_materials(uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
+    // lights[light].emission = (colour, intensity); a light registered with an instance also gets that instance's material re-emitted as
+    // register_*_light makes it (emissive_factor = colour * intensity).
+    int set_light_emission(uint32_t light, const float color[3], float intensity);
+    // Overwrite one existing texture layer (kind 0 colour, 1 data).
+    int set_texture(int kind, uint32_t layer, const uint8_t* rgba8);
 
     // SceneResources-equivalent host data (src/scene/resources.rs:10-22)
     std::vector<frt_material> materials;
@@ -158,6 +170,18 @@ std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const flo
 // Argument checks shared by the scene and the renderer form of set_mesh_vertices: "" when the vertices may be applied to a mesh of
 // `mesh_nverts` vertices (mesh_id < num_meshes is checked by the caller, which looks that count up).
 std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t mesh_nverts);
+// What build() and set_materials check on a material, whose texture layers and light index reach the kernels unchecked: "" when all five layers exist
+// (or are 0xFFFF) and light_index < num_lights (or is negative).
+std::string check_material(const frt_material& m, size_t color_layers, size_t data_layers, size_t num_lights);
+// Argument checks shared by the scene and the renderer forms of the material edits: "" when the call may be applied.
+std::string check_set_materials(uint32_t n, const uint32_t* ids, const frt_material* mats, size_t num_materials, size_t color_layers, size_t data_layers, size_t num_lights);
+std::string check_set_instance_materials(uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids, const std::vector<InstanceRec>& instances, size_t num_materials);
+std::string check_set_texture(int kind, uint32_t layer, const uint8_t* rgba8, size_t color_layers, size_t data_layers);
+// emissive_factor of the material register_*_light makes for (colour, intensity): colour[k] * intensity in f32.
+void light_emissive_factor(const float color[3], float intensity, float out[3]);
+// The instance a light was registered with, or -1 (a light of add_light / add_*_light).
+int light_instance(const std::vector<InstanceRec>& instances, uint32_t light);
+static const size_t kTextureLayerBytes = 1024u * 1024u * 4u;   // src/scene/mod.rs:12-13
 // The decoded normal a shading record holds for a vertex with these attributes (frt_shade.hpp: decode_octahedral_normal, compiled for the host).
 void decoded_vertex_normal(const frt_vertex_attr& a, float out[3]);
 

@@ -100,6 +100,26 @@ int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos
     const int rc = s->b.set_mesh_vertices(mesh_id, pos4, attrs, nverts);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_materials: null");
+    const int rc = s->b.set_materials(n, ids, materials);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_instance_materials(frt_scene* s, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_instance_materials: null");
+    const int rc = s->b.set_instance_materials(n, instance_ids, material_ids);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_light_emission(frt_scene* s, uint32_t light, const float color[3], float intensity) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_light_emission: null");
+    const int rc = s->b.set_light_emission(light, color, intensity);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_texture(frt_scene* s, int kind, uint32_t layer, const uint8_t* rgba8) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_texture: null");
+    const int rc = s->b.set_texture(kind, layer, rgba8);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 frt_scene* frt_scene_create_cornell_box(void) {
     frt_scene* s = new frt_scene();
     scenes::create_cornell_box(s->b);

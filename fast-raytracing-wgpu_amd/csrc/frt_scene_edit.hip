@@ -1,7 +1,9 @@
 // frt_scene_edit.hip — what edits or reads a renderer's scene replica between frames (include/frt.h): moving instances,
-// deforming meshes, the tree rebuild, the ray queries, frt_renderer_read_scene and the tree statistics. Host code only: the kernels are in
-// frt_refit.hip, frt_deform.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
+// deforming meshes, the material, light and texture edits (§13), the tree rebuild, the ray queries, frt_renderer_read_scene and the tree statistics.
+// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
 #include "frt_renderer_state.hpp"
+#include <algorithm>
+#include <cstddef>
 
 // Level ranges of a breadth-first tree whose node i has `kids(i, out)` inner children: boundaries of the levels, or empty if the numbering is not
 // breadth-first (then the renderer cannot refit).
@@ -38,6 +40,7 @@ int frt::upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
     f.device_bytes = pos.size() * 4 + b.tri_slot_of.size() * 4 + 16;
     f.inst = b.instances;
     f.lights = b.lights;
+    f.color_layers = (uint32_t)b.color_textures.size(); f.data_layers = (uint32_t)b.data_textures.size();
     f.pair_levels = level_ranges(b.pair_nodes.size(), [&](size_t i, uint32_t* c) {
         int k = 0;
         for (int j = 0; j < 2; ++j) { uint32_t ref; memcpy(&ref, &b.pair_nodes[i].q[12 + j], 4); if (!(ref & kLeafFlag)) c[k++] = ref; }
@@ -92,7 +95,8 @@ static bool walks_quad_tree(const frt_renderer* r) {
 }
 #endif
 // What a call `what` refuses before it looks at its own arguments, in this order: a null handle, then the `parts` it asks for.
-enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditChecks = kNotFailed | kBetweenFrames | kQuadTree };
+enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditChecks = kNotFailed | kBetweenFrames | kQuadTree,
+       kLookChecks = kNotFailed | kBetweenFrames };      // (the edits of §13 involve no tree: every renderer takes them)
 static int check_entry(const frt_renderer* r, const std::string& what, unsigned parts) {
     if (!r) return fail(FRT_ERR_INVALID_ARG, what + ": null");
     if ((parts & kNotFailed) && r->failed) return fail(FRT_ERR_STATE, what + ": an earlier frame failed in the middle of its stages; call frt_renderer_clear");
@@ -241,6 +245,122 @@ int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const floa
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------ materials, lights, textures
+// Ordering as the instance update's (order_behind_frames, the speculation dropped: its G-buffer and T-trace have read the materials). All four calls
+// stage through r->look: what a call uploads is written into the pinned block and copied from there, on the main stream, into the replica's tables
+// (or, for the instance records of set_instance_materials, into the device block its one kernel reads). The pinned block is reused once the
+// previous call's copies out of it have completed (Staging::ev).
+static int set_materials_impl(frt_renderer* r, uint32_t n, const uint32_t* ids, const frt_material* mats) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    // ascending ids, of an id given twice its last value: no two copies overlap, and a run of consecutive ids is one copy
+    std::vector<std::pair<uint32_t, uint32_t>> e(n);
+    for (uint32_t k = 0; k < n; ++k) e[k] = {ids[k], k};
+    std::sort(e.begin(), e.end());
+    size_t m = 0;
+    for (size_t k = 0; k < e.size(); ++k) if (k + 1 == e.size() || e[k + 1].first != e[k].first) e[m++] = e[k];
+    e.resize(m);
+    if ((rc = r->look.reserve(m * sizeof(frt_material), 0, r->stream))) return rc;
+    for (size_t k = 0; k < m; ++k) memcpy(r->look.h + k * sizeof(frt_material), mats + e[k].second, sizeof(frt_material));
+    for (size_t k = 0; k < m;) {
+        size_t run = 1;
+        while (k + run < m && e[k + run].first == e[k].first + (uint32_t)run) ++run;
+        HIP_TRY(hipMemcpyAsync(const_cast<MaterialView*>(r->sv.materials) + e[k].first, r->look.h + k * sizeof(frt_material), run * sizeof(frt_material), hipMemcpyHostToDevice, r->stream));
+        k += run;
+    }
+    return r->look.mark(r->stream);
+}
+int frt_renderer_set_materials(frt_renderer* r, uint32_t n, const uint32_t* ids, const frt_material* materials) {
+    if (const int rc = check_entry(r, "set_materials", kLookChecks)) return rc;
+    const std::string bad = check_set_materials(n, ids, materials, r->sv.num_materials, r->rf.color_layers, r->rf.data_layers, r->sv.num_lights);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_materials: " + bad);
+    if (n == 0) return FRT_OK;
+    const int rc = set_materials_impl(r, n, ids, materials);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int set_instance_materials_impl(frt_renderer* r, uint32_t n, const uint32_t* iids, const uint32_t* mids) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    // one record per distinct instance (an id given twice: its last value), so that no two threads of the kernel store the same word
+    std::vector<MaterialEditInstance> rec;
+    std::vector<int> last(f.inst.size(), -1);
+    for (uint32_t k = 0; k < n; ++k) last[iids[k]] = (int)k;
+    uint32_t work = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (last[iids[k]] != (int)k) continue;
+        InstanceRec& in = f.inst[iids[k]];
+        in.mat_id = mids[k];      // (the record a later set_instance_transforms re-creates carries it)
+        rec.push_back(MaterialEditInstance{in.first_tri, work, iids[k], mids[k]});
+        work += in.tri_count;
+    }
+    const size_t rec_bytes = rec.size() * sizeof(MaterialEditInstance);
+    if ((rc = r->look.reserve(rec_bytes, rec_bytes, r->stream))) return rc;
+    memcpy(r->look.h, rec.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(r->look.d, r->look.h, rec_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = r->look.mark(r->stream))) return rc;
+    const MaterialEditArgs a{reinterpret_cast<const MaterialEditInstance*>(r->look.d), (uint32_t)rec.size(), work, (uint32_t)f.inst.size()};
+    HIP_TRY(launch_instance_materials(r->sv, a, r->stream));
+    return FRT_OK;
+}
+int frt_renderer_set_instance_materials(frt_renderer* r, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids) {
+    if (const int rc = check_entry(r, "set_instance_materials", kLookChecks)) return rc;
+    const std::string bad = check_set_instance_materials(n, instance_ids, material_ids, r->rf.inst, r->sv.num_materials);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_instance_materials: " + bad);
+    if (n == 0) return FRT_OK;
+    const int rc = set_instance_materials_impl(r, n, instance_ids, material_ids);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int set_light_emission_impl(frt_renderer* r, uint32_t light, const float color[3], float intensity) {
+    RefitState& f = r->rf;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    float up[8] = {color[0], color[1], color[2], intensity, 0.0f, 0.0f, 0.0f, 0.0f};      // [emission | emissive_factor]
+    light_emissive_factor(color, intensity, up + 4);
+    memcpy(f.lights[light].emission, up, 16);      // the mirror a later set_instance_transforms re-creates a moved light's record from
+    if ((rc = r->look.reserve(sizeof(up), 0, r->stream))) return rc;
+    memcpy(r->look.h, up, sizeof(up));
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint8_t*>(const_cast<LightView*>(r->sv.lights) + light) + offsetof(LightView, emission), r->look.h, 16, hipMemcpyHostToDevice, r->stream));
+    const int i = light_instance(f.inst, light);
+    if (i >= 0 && f.inst[(size_t)i].mat_id < r->sv.num_materials)
+        HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint8_t*>(const_cast<MaterialView*>(r->sv.materials) + f.inst[(size_t)i].mat_id) + offsetof(MaterialView, emissive_factor), r->look.h + 16, 12, hipMemcpyHostToDevice, r->stream));
+    return r->look.mark(r->stream);
+}
+int frt_renderer_set_light_emission(frt_renderer* r, uint32_t light, const float color[3], float intensity) {
+    if (const int rc = check_entry(r, "set_light_emission", kLookChecks)) return rc;
+    if (!color) return fail(FRT_ERR_INVALID_ARG, "set_light_emission: null colour");
+    if (light >= r->sv.num_lights) return fail(FRT_ERR_INVALID_ARG, "set_light_emission: light " + std::to_string(light) + " out of range (" + std::to_string(r->sv.num_lights) + " lights)");
+    const int rc = set_light_emission_impl(r, light, color, intensity);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int set_texture_impl(frt_renderer* r, int kind, uint32_t layer, const uint8_t* rgba8) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    if ((rc = r->look.reserve(kTextureLayerBytes, 0, r->stream))) return rc;
+    memcpy(r->look.h, rgba8, kTextureLayerBytes);
+    uint8_t* dst = const_cast<uint8_t*>(kind == 0 ? r->sv.color_tex : r->sv.data_tex) + (size_t)layer * kTextureLayerBytes;
+    HIP_TRY(hipMemcpyAsync(dst, r->look.h, kTextureLayerBytes, hipMemcpyHostToDevice, r->stream));
+    return r->look.mark(r->stream);
+}
+int frt_renderer_set_texture(frt_renderer* r, int kind, uint32_t layer, const uint8_t* rgba8) {
+    if (const int rc = check_entry(r, "set_texture", kLookChecks)) return rc;
+    const std::string bad = check_set_texture(kind, layer, rgba8, r->rf.color_layers, r->rf.data_layers);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_texture: " + bad);
+    const int rc = set_texture_impl(r, kind, layer, rgba8);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------ tree rebuild ("Rebuild")
 // Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
 // frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
@@ -374,6 +494,7 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     const SceneView& sv = r->sv;
     const void* src = nullptr; size_t bytes = 0;
     switch (which) {
+    case 2: src = sv.materials; bytes = (size_t)sv.num_materials * sizeof(MaterialView); break;
     case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
     case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
     case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
@@ -382,7 +503,7 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
         src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
     case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
     case 17: src = sv.shade_tris; bytes = (size_t)sv.num_tris * sizeof(ShadeTri); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (3, 10, 13, 15, 16, 17)");
+    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (2, 3, 10, 13, 15, 16, 17)");
     }
     FRT_DEVICE(r);
     { int rc = sync_all(r); if (rc) return rc; }

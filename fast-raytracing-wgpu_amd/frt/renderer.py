@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
-from .scene import transform_args, mesh_vertex_args, ray_args, hits_dict, pixel_args, HIT_FIELDS
+from .scene import transform_args, mesh_vertex_args, material_args, id_pair_args, emission_args, texture_args, ray_args, hits_dict, pixel_args, HIT_FIELDS
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -185,6 +185,29 @@ class Renderer(_HostQueries):
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
 
+    # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it): asynchronous,
+    # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).
+    # The host scene is not changed (SceneBuilder has the same four methods).
+    def set_materials(self, ids, materials):
+        """Material ids[k] of this renderer's scene replica becomes materials[k]."""
+        n, i, m = material_args(ids, materials)
+        check(lib().frt_renderer_set_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_instance_materials(self, instance_ids, material_ids):
+        """Instance instance_ids[k] uses material material_ids[k]; pick and trace_closest report it at once."""
+        n, i, m = id_pair_args(instance_ids, material_ids)
+        check(lib().frt_renderer_set_instance_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_light_emission(self, light, color, intensity):
+        """Light `light` emits (color, intensity); a light registered with an instance also gets that instance's emissive material updated."""
+        l, c, i = emission_args(light, color, intensity)
+        check(lib().frt_renderer_set_light_emission(self._h, l, c.ctypes.data, i))
+
+    def set_texture(self, kind, layer, rgba8):
+        """Replace one existing texture layer: kind "color" (0) or "data" (1), rgba8 1024 x 1024 x 4 bytes."""
+        k, l, t = texture_args(kind, layer, rgba8)
+        check(lib().frt_renderer_set_texture(self._h, k, l, t.ctypes.data))
+
     # ---- ray queries against the replica as it is now (include/frt.h: frt_renderer_trace_closest / _trace_any / _pick; DESIGN.md section 12)
     def _torch_stream(self, torch, dev):
         h = self.stream_handle(0)
@@ -269,9 +292,9 @@ class Renderer(_HostQueries):
         return {"quad_nodes": int(s[0]), "quad_stack_need": int(s[1]), "quad_levels": int(s[2]), "origin": int(s[3])}
 
     def read_scene(self, what):
-        """The device replica in SceneBuilder.get's layout: "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev", "shade_tris" (syncs first)."""
+        """The device replica in SceneBuilder.get's layout: "materials", "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev", "shade_tris" (syncs first)."""
         n = self._scene.counts()
-        which, shape, dt = {"lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
+        which, shape, dt = {"materials": (2, (n["materials"], 16), np.uint32), "lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
                             "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
                             "instances_dev": (16, (n["instances"], 16), np.uint32), "shade_tris": (17, (n["tris"], 32), np.float32)}[what]
         out = np.zeros(shape, dt)
@@ -364,6 +387,29 @@ class MultiRenderer(_HostQueries):
         """Renderer.set_mesh_vertices on every strip's scene replica."""
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_multi_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+
+    # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it; DESIGN.md section 13): asynchronous,
+    # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).
+    # The host scene is not changed (SceneBuilder has the same four methods).
+    def set_materials(self, ids, materials):
+        """Material ids[k] of every strip's scene replica becomes materials[k]."""
+        n, i, m = material_args(ids, materials)
+        check(lib().frt_multi_renderer_set_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_instance_materials(self, instance_ids, material_ids):
+        """Instance instance_ids[k] uses material material_ids[k]; pick and trace_closest report it at once."""
+        n, i, m = id_pair_args(instance_ids, material_ids)
+        check(lib().frt_multi_renderer_set_instance_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+
+    def set_light_emission(self, light, color, intensity):
+        """Light `light` emits (color, intensity); a light registered with an instance also gets that instance's emissive material updated."""
+        l, c, i = emission_args(light, color, intensity)
+        check(lib().frt_multi_renderer_set_light_emission(self._h, l, c.ctypes.data, i))
+
+    def set_texture(self, kind, layer, rgba8):
+        """Replace one existing texture layer: kind "color" (0) or "data" (1), rgba8 1024 x 1024 x 4 bytes."""
+        k, l, t = texture_args(kind, layer, rgba8)
+        check(lib().frt_multi_renderer_set_texture(self._h, k, l, t.ctypes.data))
 
     def trace_closest(self, origins, dirs, tmin=0.0, tmax=3.0e38):
         """Renderer.trace_closest on the first strip's replica (all are equal); host arrays only."""

@@ -40,6 +40,54 @@ def mesh_vertex_args(mesh_id, positions, attributes):
     return int(mesh_id), pos, att, pos.shape[0]
 
 
+def material_args(ids, materials):
+    """(n, ids, [n, 16] uint32 material records) for the *_set_materials calls: `ids` an int or a sequence, `materials` one frt.Material (or a 64-byte
+    row of get("materials")) per id."""
+    ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, np.int64)))
+    if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise FrtError("material ids must be a flat list of unsigned 32-bit indices")
+    if isinstance(materials, Material):
+        materials = [materials]
+    rows = [np.frombuffer(bytes(m), np.uint32) if isinstance(m, Material) else np.ascontiguousarray(m).view(np.uint32).reshape(-1) for m in materials]
+    if any(r.size != 16 for r in rows):
+        raise FrtError("a material is 64 bytes")
+    if len(rows) != ids.size:
+        raise FrtError(f"{ids.size} material ids but {len(rows)} materials")
+    m = np.ascontiguousarray(np.stack(rows), np.uint32) if rows else np.zeros((0, 16), np.uint32)
+    return ids.size, ids.astype(np.uint32), m
+
+
+def id_pair_args(instance_ids, material_ids):
+    """(n, instance ids, material ids) for the *_set_instance_materials calls."""
+    a = np.ascontiguousarray(np.atleast_1d(np.asarray(instance_ids, np.int64)))
+    b = np.ascontiguousarray(np.atleast_1d(np.asarray(material_ids, np.int64)))
+    if a.ndim != 1 or b.ndim != 1 or a.size != b.size:
+        raise FrtError(f"{a.size} instance ids but {b.size} material ids")
+    if a.size and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) > 0xFFFFFFFF):
+        raise FrtError("instance and material ids must be unsigned 32-bit indices")
+    return a.size, a.astype(np.uint32), b.astype(np.uint32)
+
+
+def emission_args(light, color, intensity):
+    if not 0 <= int(light) <= 0xFFFFFFFF:
+        raise FrtError("light must be an unsigned 32-bit index")
+    c = np.ascontiguousarray(color, np.float32).reshape(-1)
+    if c.size != 3:
+        raise FrtError("color must hold three values")
+    return int(light), c, float(intensity)
+
+
+def texture_args(kind, layer, rgba8):
+    """(kind, layer, pixels) for the *_set_texture calls: kind 0 / "color" or 1 / "data", `rgba8` 1024 x 1024 x 4 bytes."""
+    kind = {"color": 0, "colour": 0, "data": 1}.get(kind, kind)
+    if not 0 <= int(layer) <= 0xFFFFFFFF:
+        raise FrtError("layer must be an unsigned 32-bit index")
+    t = np.ascontiguousarray(rgba8, np.uint8)
+    if t.size != 1024 * 1024 * 4:
+        raise FrtError("a texture layer is 1024 x 1024 RGBA8")
+    return int(kind), int(layer), t
+
+
 HIT_FIELDS = ("t", "u", "v", "tri", "instance", "material", "primitive", "front")      # include/frt.h: frt_ray_hit, one 32-bit word each
 
 
@@ -160,6 +208,27 @@ class SceneBuilder:
     def set_mesh_vertices(self, mesh_id, positions, attributes=None):
         mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
         check(lib().frt_scene_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+        return self
+
+    # ---- what the built scene looks like (include/frt.h: frt_scene_set_materials and the three calls after it). Host copy only.
+    def set_materials(self, ids, materials):
+        n, i, m = material_args(ids, materials)
+        check(lib().frt_scene_set_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+        return self
+
+    def set_instance_materials(self, instance_ids, material_ids):
+        n, i, m = id_pair_args(instance_ids, material_ids)
+        check(lib().frt_scene_set_instance_materials(self._h, n, i.ctypes.data, m.ctypes.data))
+        return self
+
+    def set_light_emission(self, light, color, intensity):
+        l, c, i = emission_args(light, color, intensity)
+        check(lib().frt_scene_set_light_emission(self._h, l, c.ctypes.data, i))
+        return self
+
+    def set_texture(self, kind, layer, rgba8):
+        k, l, t = texture_args(kind, layer, rgba8)
+        check(lib().frt_scene_set_texture(self._h, k, l, t.ctypes.data))
         return self
 
     # ---- ray queries on the host copy of the built scene (include/frt.h: frt_scene_trace_closest / _any): the specification of Renderer.trace_*

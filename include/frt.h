@@ -158,6 +158,23 @@ int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* 
  * built from scratch with the new vertices. Host copy only, as frt_scene_set_instance_transforms. FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG, nothing changed: mesh id out of range, nverts not the mesh's count, pos4 NULL, a non-finite position or attribute float. */
 int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* What a BUILT scene looks like: four edits that move no triangle, slot or box. Common rules: FRT_ERR_STATE: scene not built;
+ * FRT_ERR_INVALID_ARG: an id or layer out of range, a null pointer with n > 0, a failed check; everything is validated before anything is applied, so
+ * a refused call changes nothing. n == 0: FRT_OK. An id given twice ends with its last value. Afterwards the scene equals one built from scratch
+ * with the edited values. Host copy only: a renderer's replica is edited by the frt_renderer_* calls of the same names.
+ * set_materials: material ids[k] becomes materials[k], under the checks frt_scene_build makes on a material: each of its five texture layers
+ * exists or is 0xFFFF, light_index < the number of lights (or negative). */
+int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials);
+/* Instance instance_ids[k] uses material material_ids[k]: the instance record (selector 7), the device instance record (16) and word 25 of the shading
+ * record (17) of every triangle of the instance. An instance made by frt_scene_register_quad_light / _sphere_light is refused: its material
+ * carries the link to its light, which frt_scene_set_light_emission relies on (edit that material with frt_scene_set_materials instead). */
+int frt_scene_set_instance_materials(frt_scene* s, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
+/* The brightness edit: light `light` emits (color, intensity). A light made by frt_scene_register_quad_light / _sphere_light also gets its
+ * instance's material re-emitted as that call makes it (emissive_factor = color * intensity, in f32); a light of frt_scene_add_light only
+ * gets the record change. */
+int frt_scene_set_light_emission(frt_scene* s, uint32_t light, const float color[3], float intensity);
+/* Replace one EXISTING texture layer; kind and pixels as frt_scene_add_texture. */
+int frt_scene_set_texture(frt_scene* s, int kind /*0 colour (sRGB), 1 data*/, uint32_t layer, const uint8_t* rgba8_1024x1024);
 /* stats[8]: quad nodes, deepest traversal stack of the quad tree, 8-wide nodes (0: the scene has no 8-wide tree: more than 65,536 nodes), deepest stack of
  * the 8-wide tree, its levels, sum of its nodes' child counts, its triangle slots, how the quad tree was folded (2 surface-area programme, 1 programme where
  * the traversal-stack bound allows and the greedy fold elsewhere, 0 greedy fold) */
@@ -335,6 +352,19 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
  * while a frame is open, a frame that ran ahead under the old geometry dropped and redone, accumulation, reservoirs and frame_count kept. Works on
  * a tree made by frt_renderer_rebuild_tree too, and later frt_renderer_set_instance_transforms calls transform the new vertices. */
 int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
+ * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
+ * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
+ * are copied during the call. Ordering and state rules are those of frt_renderer_set_instance_transforms: asynchronous, behind every kernel that
+ * reads the scene and before the next frame's first one, FRT_ERR_STATE while a frame is open, a next frame's G-buffer + T-trace that ran ahead under
+ * the old values dropped and redone. Accumulation, reservoirs, frame_count and the tree are kept: an edited surface converges to its new look only
+ * through frt_renderer_reset / _clear (until then temporal reuse and the accumulated frame still carry the old one). No tree is involved, so every
+ * renderer takes these calls, those of the experiments build that the other edit calls refuse included. frt_renderer_pick and _trace_closest
+ * report the material of the instance record, so they see set_instance_materials at once. */
+int frt_renderer_set_materials(frt_renderer* r, uint32_t n, const uint32_t* ids, const frt_material* materials);
+int frt_renderer_set_instance_materials(frt_renderer* r, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
+int frt_renderer_set_light_emission(frt_renderer* r, uint32_t light, const float color[3], float intensity);
+int frt_renderer_set_texture(frt_renderer* r, int kind, uint32_t layer, const uint8_t* rgba8_1024x1024);
 /* Build a new quad tree over the triangle slots as they are on the device now, i.e. after any number of frt_renderer_set_instance_transforms calls, whose
  * refit keeps the topology and so loses quality after large moves ("Rebuild"): Morton order, leaves of two adjacent slots, a binary
  * radix tree folded into quad nodes, boxes by the refit kernel; all on the device, into a second set of buffers that is swapped in only on success. Hits are
@@ -362,7 +392,7 @@ int frt_renderer_tree_stats(frt_renderer* r, uint32_t stats[4]);
 /* The last rebuild call that reached the device: stats[4] = mode asked for, clustering iterations run (FRT_REBUILD_SAH), why the Morton tree was
  * built instead (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added. Zeros before any rebuild. */
 int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t stats[4]);
-/* Read the device replica back (syncs first), in the layout of frt_scene_get: 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
+/* Read the device replica back (syncs first), in the layout of frt_scene_get: 2 materials, 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
  * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 
@@ -428,6 +458,11 @@ int frt_multi_renderer_boundaries(const frt_multi_renderer* m, uint32_t* rows_ou
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
 /* frt_renderer_set_mesh_vertices on every strip's replica, between frames */
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* frt_renderer_set_materials, _set_instance_materials, _set_light_emission and _set_texture on every strip's replica, between frames */
+int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials);
+int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
+int frt_multi_renderer_set_light_emission(frt_multi_renderer* m, uint32_t light, const float color[3], float intensity);
+int frt_multi_renderer_set_texture(frt_multi_renderer* m, int kind, uint32_t layer, const uint8_t* rgba8_1024x1024);
 /* frt_renderer_rebuild_tree on every strip's replica, between frames (synchronous) */
 int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m);
 /* frt_renderer_rebuild_tree_ex on every strip's replica */
