@@ -28,6 +28,18 @@ struct DeformArgs {
     const uint32_t* slot_of;                          // flattened triangle id -> triangle slot
 };
 
+// Words 0..23 of a shading record (frt_shade.hpp: fetch_hit_geometry), shared with frt_instance_edit.hip: a gather, no arithmetic.
+//   q0 (n0.xyz, uv0.x) q1 (n1.xyz, uv0.y) q2 (n2.xyz, uv1.x) q3 (t0.xyz, uv1.y) q4 (t1.xyz, uv2.x) q5 (t2.xyz, uv2.y); q6 = (tangent sign of corner 0, mat_id, 0, 0)
+// `n`: the decoded normals of the three corners; `nu`, `tg`: the two float4 of their attributes, (normal.xy, uv.xy) and (tangent.xyzw).
+__device__ inline void store_shade_corners(float4* rec, const float4 n[3], const float4 nu[3], const float4 tg[3]) {
+    rec[0] = make_float4(n[0].x, n[0].y, n[0].z, nu[0].z);
+    rec[1] = make_float4(n[1].x, n[1].y, n[1].z, nu[0].w);
+    rec[2] = make_float4(n[2].x, n[2].y, n[2].z, nu[1].z);
+    rec[3] = make_float4(tg[0].x, tg[0].y, tg[0].z, nu[1].w);
+    rec[4] = make_float4(tg[1].x, tg[1].y, tg[1].z, nu[2].z);
+    rec[5] = make_float4(tg[2].x, tg[2].y, tg[2].z, nu[2].w);
+}
+
 // The triangle (and shading record) rewrite on `stream`. Launches nothing when there is no work.
 hipError_t launch_mesh_deform(const SceneView& sc, const DeformArgs& a, hipStream_t stream);
 

@@ -475,6 +475,21 @@ int frt_multi_renderer_rebuild_tree_ex(frt_multi_renderer* m, uint32_t mode) {
     return FRT_OK;
 }
 
+// Every strip adds to / removes from its own replica (frt_renderer_add_instances / _remove_instances: synchronous per strip). The replicas
+// hold the same scene, so every strip makes the same buffers and the same tree; the first strip's refusal leaves every replica as it was.
+int frt_multi_renderer_add_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode) {
+    int first = 0;
+    const int rc = edit_every_replica(m, "multi add_instances", [&](frt_renderer* r) {
+        const int id = frt_renderer_add_instances(r, n, mesh_ids, mat_ids, m_colmajor16, rebuild_mode);
+        if (id >= 0) first = id;
+        return id < 0 ? id : (int)FRT_OK;
+    });
+    return rc ? rc : first;
+}
+int frt_multi_renderer_remove_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode) {
+    return edit_every_replica(m, "multi remove_instances", [&](frt_renderer* r) { return frt_renderer_remove_instances(r, n, ids, rebuild_mode); });
+}
+
 int frt_multi_renderer_set_jitter(frt_multi_renderer* m, float jx, float jy) {
     if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_jitter: null");
     if (m->strips.size() > 1 && (jx != 0.0f || jy != 0.0f))

@@ -4,6 +4,7 @@
 // The only atomics are the min / max of the centroid bounds, which are exact and order-independent. No box arithmetic is written here: the boxes
 // are the refit kernel's (frt_refit.hip), so every box is the padded union DESIGN.md §11 defines.
 #include "frt_rebuild.hpp"
+#include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -271,7 +272,13 @@ hipError_t rebuild_reserve(RebuildScratch& s, uint32_t num_tris) {
     const uint32_t inner = rebuild_max_nodes(num_tris);
     hipError_t e;
     rocprim::double_buffer<unsigned long long> kb(nullptr, nullptr);
-    if ((e = rocprim::radix_sort_keys(nullptr, s.sort_bytes, kb, (size_t)num_tris, 0u, 64u, (hipStream_t) nullptr)) != hipSuccess) return e;
+    // (the scratch may serve scenes of fewer triangles than it was reserved for, DESIGN.md §14, and the sort picks its algorithm by size: room for the
+    // largest need at every halving down from num_tris; rebuild_tree checks the need of the size it sorts against this before it sorts)
+    for (size_t n = num_tris; n > 0; n /= 2) {
+        size_t need = 0;
+        if ((e = rocprim::radix_sort_keys(nullptr, need, kb, n, 0u, 64u, (hipStream_t) nullptr)) != hipSuccess) return e;
+        s.sort_bytes = std::max(s.sort_bytes, need);
+    }
     if ((e = rocprim::exclusive_scan(nullptr, s.scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)inner, rocprim::plus<uint32_t>(), (hipStream_t) nullptr)) != hipSuccess) return e;
     const size_t kbytes = align256((size_t)num_tris * 8u), ibytes = align256((size_t)inner * 4u);
     const size_t total = 2u * kbytes + align256(s.sort_bytes) + align256(s.scan_bytes) + 11u * ibytes + align256(kRebuildWords * 4u);
@@ -382,7 +389,10 @@ hipError_t rebuild_tree(RebuildScratch& s, const SceneView& cur, const uint32_t*
     hipLaunchKernelGGL(morton_keys_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, s.words, s.keys[0]);
     RB_TRY(hipGetLastError());
     rocprim::double_buffer<unsigned long long> kb(s.keys[0], s.keys[1]);
-    size_t sort_bytes = s.sort_bytes;
+    size_t sort_bytes = 0;
+    RB_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, kb, (size_t)N, 0u, 64u, stream));
+    if (sort_bytes > s.sort_bytes) return hipErrorOutOfMemory;      // (never seen: rebuild_reserve)
+    sort_bytes = s.sort_bytes;
     RB_TRY(rocprim::radix_sort_keys(s.sort_tmp, sort_bytes, kb, (size_t)N, 0u, 64u, stream));
     const unsigned long long* keys = kb.current();
     hipLaunchKernelGGL(gather_slots_kernel, grid_for(N), dim3(kRbBlock), 0, stream, cur, slot_of, keys, out.tris, out.slot_of);

@@ -9,8 +9,6 @@ namespace frt {
 static const int kRefitBlock = 256;
 static const uint32_t kRefitLeaf = 0x80000000u, kRefitNone = 0xFFFFFFFFu;
 
-__device__ inline float4 mkf4(float x, float y, float z, uint32_t wbits) { return make_float4(x, y, z, __uint_as_float(wbits)); }
-
 // Threads [0, work): one triangle of a moved instance each, written into its slot (same id and instance bits). Threads [0, nrec): the moved
 // instances' device records and registered lights.
 __global__ void __launch_bounds__(kRefitBlock) instance_transform_kernel(SceneView sc, RefitArgs a) {
@@ -26,18 +24,13 @@ __global__ void __launch_bounds__(kRefitBlock) instance_transform_kernel(SceneVi
     const MovedInstance& r = a.rec[lo];
     const uint32_t j = g - r.work_begin;
     if (j >= r.tri_count) return;
-    const float* m = r.m;
+    float4 p[3];
     float w[3][3];
-    for (int k = 0; k < 3; ++k) {
-        const float4 p = a.pos[r.pos_offset + sc.indices[r.index_offset + 3u * j + (uint32_t)k]];
-        for (int c = 0; c < 3; ++c) w[k][c] = ((m[c] * p.x + m[3 + c] * p.y) + m[6 + c] * p.z) + m[9 + c];
-    }
+    for (int k = 0; k < 3; ++k) p[k] = a.pos[r.pos_offset + sc.indices[r.index_offset + 3u * j + (uint32_t)k]];
+    instance_world_vertices(r.m, p, w);
     const uint32_t id = r.first_tri + j, slot = a.slot_of[id];
     if (slot >= sc.num_tris) return;
-    float4* t = const_cast<float4*>(sc.tris) + (size_t)slot * 3u;
-    t[0] = mkf4(w[0][0], w[0][1], w[0][2], id);
-    t[1] = mkf4(w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2], r.id);
-    t[2] = mkf4(w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2], 0u);
+    store_tri_slot(const_cast<float4*>(sc.tris) + (size_t)slot * 3u, w, id, r.id);
 }
 
 // max |coordinate| over the bounds of every triangle slot (v0, v0 + e1, v0 + e2): build_bvh2's `ext`. Non-negative f32 bits order as unsigned.

@@ -30,6 +30,20 @@ struct RefitArgs {
     unsigned int* ext;                               // max |coordinate| over all triangle bounds, as f32 bits (one word)
 };
 
+// The device functions the kernels that write triangle slots share (frt_refit.hip, frt_deform.hip, frt_instance_edit.hip). Contract flags: no
+// contraction, no hand-written fma, so every operation is world_triangle's (frt_scene.cpp), in its order.
+// Vertex k of a triangle under the 3x4 `m` (columns 0..3, xyz each: m[3c + r]): w[k] = ((c0*x + c1*y) + c2*z) + c3.
+__device__ inline void instance_world_vertices(const float* m, const float4 p[3], float w[3][3]) {
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) w[k][c] = ((m[c] * p[k].x + m[3 + c] * p[k].y) + m[6 + c] * p[k].z) + m[9 + c];
+}
+// The whole triangle slot (build_gpu_layout): (v0, id bits) (e1 = v1 - v0, instance bits) (e2 = v2 - v0, 0).
+__device__ inline void store_tri_slot(float4* t, const float w[3][3], uint32_t id, uint32_t inst) {
+    t[0] = make_float4(w[0][0], w[0][1], w[0][2], __uint_as_float(id));
+    t[1] = make_float4(w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2], __uint_as_float(inst));
+    t[2] = make_float4(w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2], 0.0f);
+}
+
 // Transform + record scatter, then the scene-box reduction (ext zeroed first), all on `stream`.
 hipError_t launch_instance_transform(const SceneView& sc, const RefitArgs& a, hipStream_t stream);
 // The scene-box reduction alone (what launch_instance_transform ends with): `ext` zeroed, then max |coordinate| over every triangle slot.

@@ -4,6 +4,7 @@
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
+#include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
 #include "frt_query.hpp"        // (frt_scene.hpp, frt_kernels.hpp)
 #include <hip/hip_runtime.h>
@@ -117,6 +118,7 @@ struct RefitState {
     // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; staging of one call: pinned
     // [positions | attributes | instance records | decoded normals], on the device the last two.
     std::vector<uint32_t> vert_count, attr_offset;
+    std::vector<uint32_t> mesh_tris;       // per mesh: its triangles (what an added instance of it brings)
     Staging def;
     uint32_t color_layers = 0, data_layers = 0;   // texture layers of the replica (the material and texture edits check against them)
     uint64_t device_bytes = 0;
@@ -130,10 +132,23 @@ struct RebuildState {
     RebuildScratch scratch;
     float4* tris = nullptr; uint32_t* slot_of = nullptr;
     float4* nodes[2] = {nullptr, nullptr};
+    uint32_t cap_tris = 0, nodes_cap[2] = {0, 0};      // triangles `tris` / `slot_of` have room for, quad nodes each of `nodes` has (capacities)
     bool done = false;                     // the replica's quad tree is a device rebuild: the pair tree and its quantised form are stale
     uint32_t origin = 0;                   // frt_renderer_tree_stats: 1 the Morton tree, 2 the refined tree
     uint32_t last[4] = {0, 0, 0, 0};       // frt_renderer_rebuild_stats
     uint64_t device_bytes = 0;
+};
+
+// What frt_renderer_add_instances / _remove_instances add, allocated at the first call and freed with the scene replica. From then on
+// every buffer of the replica that is sized by triangles or instances has a capacity apart from its count: capacities grow geometrically, are never
+// shrunk, and a growth is a new allocation plus a device-to-device copy of what is in use.
+struct InstanceEditState {
+    uint32_t cap_tris = 0, cap_inst = 0;   // 0: the replica's buffers are as uploaded, exactly as large as their counts
+    float4* tris = nullptr; uint32_t* slot_of = nullptr;      // what an edit writes and its rebuild reads: never part of the replica
+    float4* shade_tris = nullptr; InstanceView* instances = nullptr;   // written by an edit; they trade places with the replica's when its rebuild succeeds
+    const float4* d_normals = nullptr;     // the decoded normal of every vertex (xyz, 0), indexed as SceneView::attributes; set_mesh_vertices keeps it up
+    Staging rec;                           // the records of one call (AppendInstance / RemovedRange)
+    uint32_t growths = 0;                  // calls that had to grow a capacity
 };
 
 struct frt_renderer {
@@ -199,6 +214,7 @@ struct frt_renderer {
     uint64_t serial = 0;                   // frames finished since creation (never reset: parity of the per-frame events)
     RefitState rf;
     RebuildState rbt;
+    InstanceEditState ie;
     // The host-pointer ray queries: both blocks [input | output] of a call. Such a call is synchronous — the last call's copies are done
     // when the next one starts — so this one is never marked: no event is created, recorded or waited for.
     Staging qry;

@@ -500,6 +500,85 @@ int SceneBuilder::set_texture(int kind, uint32_t layer, const uint8_t* rgba8) {
     return FRT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- adding and removing instances
+int check_add_instances(uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats, const std::vector<uint32_t>& mesh_tris, size_t num_materials,
+                        uint64_t num_tris, std::string& why) {
+    if (n > 0 && (!mesh_ids || !mat_ids || !mats)) { why = "null mesh ids, material ids or matrices"; return FRT_ERR_INVALID_ARG; }
+    uint64_t total = num_tris;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (mesh_ids[k] >= mesh_tris.size()) { why = "mesh id " + std::to_string(mesh_ids[k]) + " out of range (" + std::to_string(mesh_tris.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+        if (mat_ids[k] >= num_materials) { why = "material id " + std::to_string(mat_ids[k]) + " out of range (" + std::to_string(num_materials) + " materials)"; return FRT_ERR_INVALID_ARG; }
+        float w2o[9]; uint32_t flip;
+        if (!instance_inverse(mats + 16 * (size_t)k, w2o, flip)) { why = "matrix " + std::to_string(k) + " has a non-finite entry or a singular 3x3"; return FRT_ERR_INVALID_ARG; }
+        total += mesh_tris[mesh_ids[k]];
+    }
+    if (total > kMaxSceneTris) { why = std::to_string(total) + " triangles would result, " + std::to_string(kMaxSceneTris) + " is the limit"; return FRT_ERR_LIMIT; }
+    return FRT_OK;
+}
+int check_remove_instances(uint32_t n, const uint32_t* ids, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why) {
+    removed.clear();
+    if (n > 0 && !ids) { why = "null ids"; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) {
+        if (ids[k] >= instances.size()) { why = "instance id " + std::to_string(ids[k]) + " out of range (" + std::to_string(instances.size()) + " instances)"; return FRT_ERR_INVALID_ARG; }
+        if (instances[ids[k]].light >= 0) {
+            why = "instance " + std::to_string(ids[k]) + " was registered with light " + std::to_string(instances[ids[k]].light) + ": its material and its light record carry links to it";
+            return FRT_ERR_INVALID_ARG;
+        }
+    }
+    removed.assign(ids, ids + n);
+    std::sort(removed.begin(), removed.end());
+    removed.erase(std::unique(removed.begin(), removed.end()), removed.end());
+    if (n > 0 && removed.size() == instances.size()) { removed.clear(); why = "every instance would be removed (a scene without triangles cannot be built)"; return FRT_ERR_INVALID_ARG; }
+    return FRT_OK;
+}
+
+int SceneBuilder::add_instances(uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats) {
+    if (!built) { error = "add_instances: scene is not built"; return FRT_ERR_STATE; }
+    std::vector<uint32_t> mesh_tris(mesh_index_counts.size());
+    for (size_t m = 0; m < mesh_tris.size(); ++m) mesh_tris[m] = mesh_index_counts[m] / 3u;
+    std::string why;
+    if (const int rc = check_add_instances(n, mesh_ids, mat_ids, mats, mesh_tris, materials.size(), tris.size(), why)) { error = "add_instances: " + why; return rc; }
+    const size_t first = instances.size();
+    if (n == 0) return (int)first;
+    for (uint32_t k = 0; k < n; ++k) {
+        Mat4 t; memcpy(t.m, mats + 16 * (size_t)k, sizeof(t.m));
+        add_instance(mesh_ids[k], mat_ids[k], t);
+    }
+    build();
+    if (!built) {      // (a tree the builder refuses: back to the list as it was, built the same way it had been)
+        const std::string why_not = error;
+        instances.resize(first);
+        build();
+        error = "add_instances: " + why_not + " (nothing changed)";
+        return FRT_ERR_LIMIT;
+    }
+    return (int)first;
+}
+
+int SceneBuilder::remove_instances(uint32_t n, const uint32_t* ids) {
+    if (!built) { error = "remove_instances: scene is not built"; return FRT_ERR_STATE; }
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_instances(n, ids, instances, gone, why)) { error = "remove_instances: " + why; return rc; }
+    if (gone.empty()) return FRT_OK;
+    const std::vector<InstanceRec> before = instances;
+    size_t g = 0, w = 0;
+    for (size_t i = 0; i < before.size(); ++i) {      // the survivors in their order (each keeps its light link: lights are not renumbered)
+        if (g < gone.size() && gone[g] == i) { ++g; continue; }
+        instances[w++] = before[i];
+    }
+    instances.resize(w);
+    build();
+    if (!built) {
+        const std::string why_not = error;
+        instances = before;
+        build();
+        error = "remove_instances: " + why_not + " (nothing changed)";
+        return FRT_ERR_LIMIT;
+    }
+    return FRT_OK;
+}
+
 void SceneBuilder::build() {
     error.clear();
     // Texture layers and light indices reach the kernels unchecked (sample_layer: base + layer * 4 MiB): validate them here, once.

@@ -112,6 +112,13 @@ public:
     int set_light_emission(uint32_t light, const float color[3], float intensity);
     // Overwrite one existing texture layer (kind 0 colour, 1 data).
     int set_texture(int kind, uint32_t layer, const uint8_t* rgba8);
+    // How many instances a built scene holds. Each validates everything before it applies anything and leaves the scene equal, selector
+    // for selector, to one built from scratch with the resulting instance list: the list is edited and build() runs again. The specification the
+    // device forms match. add_instances appends in argument order and returns the id of the first new instance (the instance count when n == 0).
+    int add_instances(uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats);
+    // The instances `ids` leave (an id given twice leaves once); ids and flattened triangle ids above them shift down, as in a from-scratch build. An
+    // instance that register_*_light created is refused, and so is removing every instance.
+    int remove_instances(uint32_t n, const uint32_t* ids);
 
     // SceneResources-equivalent host data (src/scene/resources.rs:10-22)
     std::vector<frt_material> materials;
@@ -177,6 +184,12 @@ std::string check_material(const frt_material& m, size_t color_layers, size_t da
 std::string check_set_materials(uint32_t n, const uint32_t* ids, const frt_material* mats, size_t num_materials, size_t color_layers, size_t data_layers, size_t num_lights);
 std::string check_set_instance_materials(uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids, const std::vector<InstanceRec>& instances, size_t num_materials);
 std::string check_set_texture(int kind, uint32_t layer, const uint8_t* rgba8, size_t color_layers, size_t data_layers);
+// Argument checks shared by the scene and the renderer forms of add_instances / remove_instances: FRT_OK, or the code with `why` set.
+// `mesh_tris`: triangles per mesh; `num_tris`: flattened triangles now. remove: `removed` receives the distinct ids, ascending.
+static const uint64_t kMaxSceneTris = 0xFFFFFFFEull;
+int check_add_instances(uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats, const std::vector<uint32_t>& mesh_tris, size_t num_materials,
+                        uint64_t num_tris, std::string& why);
+int check_remove_instances(uint32_t n, const uint32_t* ids, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why);
 // emissive_factor of the material register_*_light makes for (colour, intensity): colour[k] * intensity in f32.
 void light_emissive_factor(const float color[3], float intensity, float out[3]);
 // The instance a light was registered with, or -1 (a light of add_light / add_*_light).

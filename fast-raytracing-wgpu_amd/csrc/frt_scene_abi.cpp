@@ -120,6 +120,16 @@ int frt_scene_set_texture(frt_scene* s, int kind, uint32_t layer, const uint8_t*
     const int rc = s->b.set_texture(kind, layer, rgba8);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_add_instances(frt_scene* s, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "add_instances: null");
+    const int rc = s->b.add_instances(n, mesh_ids, mat_ids, m_colmajor16);
+    return rc < 0 ? fail(rc, s->b.error) : rc;
+}
+int frt_scene_remove_instances(frt_scene* s, uint32_t n, const uint32_t* ids) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "remove_instances: null");
+    const int rc = s->b.remove_instances(n, ids);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 frt_scene* frt_scene_create_cornell_box(void) {
     frt_scene* s = new frt_scene();
     scenes::create_cornell_box(s->b);

@@ -1,6 +1,7 @@
 // frt_scene_edit.hip — what edits or reads a renderer's scene replica between frames (include/frt.h): moving instances,
-// deforming meshes, the material, light and texture edits (§13), the tree rebuild, the ray queries, frt_renderer_read_scene and the tree statistics.
-// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
+// deforming meshes, the material, light and texture edits (§13), the tree rebuild, adding and removing instances (§14), the ray queries,
+// frt_renderer_read_scene and the tree statistics.
+// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -24,12 +25,13 @@ static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
 int frt::upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
     RefitState& f = r->rf;
     std::vector<float> pos;
-    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear();
+    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear(); f.mesh_tris.clear();
     for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
         f.pos_offset.push_back((uint32_t)(pos.size() / 4));
         f.index_offset.push_back(b.mesh_infos[m].index_offset);
         f.vert_count.push_back((uint32_t)(b.mesh_positions[m].size() / 4));
         f.attr_offset.push_back(b.mesh_infos[m].vertex_offset);
+        f.mesh_tris.push_back(b.mesh_index_counts[m] / 3u);
         pos.insert(pos.end(), b.mesh_positions[m].begin(), b.mesh_positions[m].end());
     }
     int rc;
@@ -226,6 +228,8 @@ static int set_mesh_vertices_impl(frt_renderer* r, uint32_t mesh_id, const float
     HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
     if (attrs) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
     if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
+    if (attrs && r->ie.d_normals)      // (what a later frt_renderer_add_instances of this mesh reads, §14)
+        HIP_TRY(hipMemcpyAsync(const_cast<float4*>(r->ie.d_normals) + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
     if ((rc = f.def.mark(r->stream))) return rc;
     if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
     DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
@@ -365,40 +369,75 @@ int frt_renderer_set_texture(frt_renderer* r, int kind, uint32_t layer, const ui
 // Ordering: as the instance update, the ahead stream is fenced into the main stream (the edge streams already are, behind ev_edge). A speculated
 // frame that ran ahead on the old tree is kept: both trees give the same hits. The call waits for the main stream, so when it returns no kernel
 // reads the buffers that left the replica; they stay allocated and are what the next rebuild builds into.
-static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
+// Scene allocations that may be replaced while the renderer lives (they are freed with the scene replica otherwise).
+static int scene_alloc(frt_renderer* r, size_t bytes, void** out) {
+    HIP_TRY(hipMalloc(out, std::max<size_t>(bytes, 16)));
+    r->scene_allocs.push_back(*out);
+    return FRT_OK;
+}
+static void scene_free(frt_renderer* r, const void* p) {
+    if (!p) return;
+    auto it = std::find(r->scene_allocs.begin(), r->scene_allocs.end(), const_cast<void*>(p));
+    if (it != r->scene_allocs.end()) r->scene_allocs.erase(it);
+    (void)hipFree(const_cast<void*>(p));
+}
+// Triangles the replica's triangle-sized buffers have room for: their count until an instance edit gave them a capacity.
+static uint32_t tri_capacity(const frt_renderer* r) { return r->ie.cap_tris ? r->ie.cap_tris : r->sv.num_tris; }
+
+// The buffers a rebuild builds into, with room for a tree over tri_capacity() triangles: the scratch, the spare triangle slots and id -> slot table, and
+// the quad-node buffer that is not in use. Each is (re)allocated only when it is too small; none of them is part of the replica, and no kernel of an
+// earlier call still uses them (every rebuild waits for its stream).
+static int rebuild_prepare(frt_renderer* r, uint32_t num_tris, uint32_t mode, RebuildTarget& target) {
     RebuildState& b = r->rbt;
-    SceneView& sv = r->sv;
-    FRT_DEVICE(r);
-    int rc = order_behind_frames(r, false);
-    if (rc) return rc;
-    const uint32_t N = sv.num_tris;
-    auto alloc = [&](size_t bytes, void** out) {
-        HIP_TRY(hipMalloc(out, std::max<size_t>(bytes, 16)));
-        r->scene_allocs.push_back(*out);
-        b.device_bytes += bytes;
-        return (int)FRT_OK;
-    };
-    if (!b.tris) {
-        HIP_TRY(rebuild_reserve(b.scratch, N));
-        b.device_bytes += b.scratch.bytes;
-        if ((rc = alloc((size_t)N * sizeof(TriSlot), (void**)&b.tris))) return rc;
-        if ((rc = alloc((size_t)N * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
+    const uint32_t cap = std::max(tri_capacity(r), num_tris);
+    int rc;
+    if (b.cap_tris < cap) {
+        const size_t had = b.scratch.bytes + b.scratch.ploc.bytes;
+        HIP_TRY(rebuild_reserve(b.scratch, cap));
+        b.device_bytes += b.scratch.bytes + b.scratch.ploc.bytes; b.device_bytes -= had;
+        scene_free(r, b.tris); scene_free(r, b.slot_of);
+        b.device_bytes -= (uint64_t)b.cap_tris * (sizeof(TriSlot) + sizeof(uint32_t));
+        b.tris = nullptr; b.slot_of = nullptr; b.cap_tris = 0;
+        if ((rc = scene_alloc(r, (size_t)cap * sizeof(TriSlot), (void**)&b.tris))) return rc;
+        if ((rc = scene_alloc(r, (size_t)cap * sizeof(uint32_t), (void**)&b.slot_of))) return rc;
+        b.cap_tris = cap;
+        b.device_bytes += (uint64_t)cap * (sizeof(TriSlot) + sizeof(uint32_t));
     }
-    if (mode == FRT_REBUILD_SAH && N > 2u) {      // the refined mode's own scratch, at its first call only
+    if (mode == FRT_REBUILD_SAH && num_tris > 2u) {      // the refined mode's own scratch, at its first call (and after a growth) only
         const size_t had = b.scratch.ploc.bytes;
-        HIP_TRY(ploc_reserve(b.scratch, N));
+        HIP_TRY(ploc_reserve(b.scratch, cap));
         b.device_bytes += b.scratch.ploc.bytes - had;
     }
-    const int t = sv.nodes4 == b.nodes[0] ? 1 : 0;
-    if (!b.nodes[t] && (rc = alloc((size_t)rebuild_max_nodes(N) * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
-    const RebuildTarget target{b.tris, b.nodes[t], b.slot_of};
-    RebuildResult res;
-    HIP_TRY(rebuild_tree(b.scratch, sv, r->rf.d_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res, mode));
+    const int t = r->sv.nodes4 == b.nodes[0] ? 1 : 0;
+    const uint32_t need = rebuild_max_nodes(cap);
+    if (b.nodes_cap[t] < need) {
+        scene_free(r, b.nodes[t]);
+        b.device_bytes -= (uint64_t)b.nodes_cap[t] * sizeof(QuadNode);
+        b.nodes[t] = nullptr; b.nodes_cap[t] = 0;
+        if ((rc = scene_alloc(r, (size_t)need * sizeof(QuadNode), (void**)&b.nodes[t]))) return rc;
+        b.nodes_cap[t] = need;
+        b.device_bytes += (uint64_t)need * sizeof(QuadNode);
+    }
+    target = RebuildTarget{b.tris, b.nodes[t], b.slot_of};
+    return FRT_OK;
+}
+// The tree of `src` (its tris and num_tris; `src_slot_of` its id -> slot table) into the buffers of rebuild_prepare, and the checks every caller makes before
+// anything of the replica changes. Waits for the main stream.
+static int rebuild_into(frt_renderer* r, const SceneView& src, const uint32_t* src_slot_of, uint32_t mode, const char* what, RebuildTarget& target, RebuildResult& res) {
+    RebuildState& b = r->rbt;
+    if (const int rc = rebuild_prepare(r, src.num_tris, mode, target)) return rc;
+    HIP_TRY(rebuild_tree(b.scratch, src, src_slot_of, target, const_cast<unsigned int*>(r->rf.d_ext), r->stream, res, mode));
     b.last[0] = mode; b.last[1] = res.iterations; b.last[2] = res.fell_back; b.last[3] = (uint32_t)((b.scratch.ploc.bytes + 1023u) >> 10);
-    if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, "rebuild_tree: the tree could not be numbered (nothing changed)");
+    if (res.num_nodes == 0) return fail(FRT_ERR_LIMIT, std::string(what) + ": the tree could not be numbered (nothing changed)");
     // the kernels have no overflow check: the bound is hard, and it is checked before anything of the replica changes
     if (res.stack_need > (uint32_t)kStackDepth - 1u)
-        return fail(FRT_ERR_LIMIT, "rebuild_tree: the new tree needs " + std::to_string(res.stack_need) + " traversal-stack entries, " + std::to_string(kStackDepth - 1) + " is the limit (nothing changed)");
+        return fail(FRT_ERR_LIMIT, std::string(what) + ": the new tree needs " + std::to_string(res.stack_need) + " traversal-stack entries, " + std::to_string(kStackDepth - 1) + " is the limit (nothing changed)");
+    return FRT_OK;
+}
+// The finished tree enters the replica; the buffers that leave it are what the next rebuild builds into.
+static void rebuild_swap(frt_renderer* r, const RebuildTarget& target, const RebuildResult& res) {
+    RebuildState& b = r->rbt;
+    SceneView& sv = r->sv;
     b.tris = const_cast<float4*>(sv.tris); b.slot_of = const_cast<uint32_t*>(r->rf.d_slot_of);
     sv.tris = target.tris; r->rf.d_slot_of = target.slot_of;
     sv.nodes4 = target.nodes; sv.num_nodes4 = res.num_nodes;
@@ -408,6 +447,15 @@ static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
     r->wg_rows = res.stack_need + 1u;
     r->vote = res.num_nodes >= kVoteMinQuadNodes;
     b.done = true; b.origin = res.origin;
+}
+static int rebuild_tree_impl(frt_renderer* r, uint32_t mode) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, false);
+    if (rc) return rc;
+    RebuildTarget target;
+    RebuildResult res;
+    if ((rc = rebuild_into(r, r->sv, r->rf.d_slot_of, mode, "rebuild_tree", target, res))) return rc;
+    rebuild_swap(r, target, res);
     return FRT_OK;
 }
 int frt_renderer_rebuild_tree(frt_renderer* r) { return frt_renderer_rebuild_tree_ex(r, FRT_REBUILD_MORTON); }
@@ -418,6 +466,218 @@ int frt_renderer_rebuild_tree_ex(frt_renderer* r, uint32_t mode) {
     if (rc == FRT_ERR_HIP) r->failed = true;
     return rc;
 }
+// ------------------------------------------------------------------------------------------------ adding and removing instances
+// Ordering: as the instance update's (order_behind_frames, the speculation dropped: it was traced on the old geometry). The kernels of
+// frt_instance_edit.hip write buffers that are not part of the replica (InstanceEditState); the scene-extent pass and the rebuild follow them on the
+// main stream and read only those; the rebuild waits for the stream, and only then — the tree is known to fit the traversal stack — do the new
+// triangles, shading records, instance records, id -> slot table and tree enter the replica in one step, with the host bookkeeping (RefitState::inst).
+// A call that is refused or fails before that step leaves the replica as it was (the extent word is made again from the replica's triangles).
+
+// Room for `need_tris` triangles and `need_inst` instances in every buffer sized by them: the replica's (triangle slots, id -> slot table, shading
+// records, instance records: new allocation + device-to-device copy of what is in use) and the edit's own; the rebuild's buffers follow in
+// rebuild_prepare. Capacities double (at least), are never shrunk, and nothing happens while they suffice.
+// (`elem`: bytes per element; `live` / `own` point at the caller's pointer of whatever type)
+static int grow_live(frt_renderer* r, const void* live_ptr, size_t elem, size_t used, size_t cap) {
+    const void** live = static_cast<const void**>(const_cast<void*>(live_ptr));
+    void* d = nullptr;
+    if (const int rc = scene_alloc(r, cap * elem, &d)) return rc;
+    if (used) HIP_TRY(hipMemcpy(d, *live, used * elem, hipMemcpyDeviceToDevice));
+    scene_free(r, *live);
+    *live = d;
+    return FRT_OK;
+}
+static int regrow_own(frt_renderer* r, void* own_ptr, size_t elem, size_t cap) {
+    void** own = static_cast<void**>(own_ptr);
+    scene_free(r, *own); *own = nullptr;
+    return scene_alloc(r, cap * elem, own);
+}
+static int reserve_edit(frt_renderer* r, uint32_t need_tris, uint32_t need_inst) {
+    InstanceEditState& e = r->ie;
+    SceneView& sv = r->sv;
+    const uint32_t have_tris = tri_capacity(r), have_inst = e.cap_inst ? e.cap_inst : (uint32_t)r->rf.inst.size();
+    const bool first = e.tris == nullptr, more_tris = need_tris > have_tris, more_inst = need_inst > have_inst;
+    if (!first && !more_tris && !more_inst) return FRT_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));      // (the ahead stream is fenced into it: no kernel reads what is replaced below)
+    int rc;
+    if (first || more_tris) {
+        const uint32_t cap = more_tris ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need_tris, 2ull * have_tris), kMaxSceneTris) : have_tris;
+        if (more_tris) {
+            if ((rc = grow_live(r, &sv.tris, sizeof(TriSlot), sv.num_tris, cap))) return rc;
+            if ((rc = grow_live(r, &sv.shade_tris, sizeof(ShadeTri), sv.num_tris, cap))) return rc;
+            if ((rc = grow_live(r, &r->rf.d_slot_of, sizeof(uint32_t), sv.num_tris, cap))) return rc;
+        }
+        if ((rc = regrow_own(r, &e.tris, sizeof(TriSlot), cap))) return rc;
+        if ((rc = regrow_own(r, &e.shade_tris, sizeof(ShadeTri), cap))) return rc;
+        if ((rc = regrow_own(r, &e.slot_of, sizeof(uint32_t), cap))) return rc;
+        e.cap_tris = cap;
+    }
+    if (first || more_inst) {
+        const uint32_t cap = more_inst ? std::max(need_inst, 2u * have_inst) : have_inst;
+        if (more_inst && (rc = grow_live(r, &sv.instances, sizeof(InstanceView), r->rf.inst.size(), cap))) return rc;
+        if ((rc = regrow_own(r, &e.instances, sizeof(InstanceView), cap))) return rc;
+        e.cap_inst = cap;
+    }
+    if (more_tris || more_inst) ++e.growths;
+    return FRT_OK;
+}
+// The decoded normal of every vertex of the replica, made once, at the first call that adds an instance: the attributes come back from the device (a
+// deformation may have replaced them) and are decoded by the function build_gpu_layout uses.
+static int ensure_normals(frt_renderer* r) {
+    if (r->ie.d_normals) return FRT_OK;
+    const RefitState& f = r->rf;
+    const size_t nverts = f.attr_offset.empty() ? 0 : (size_t)f.attr_offset.back() + f.vert_count.back();
+    std::vector<frt_vertex_attr> attrs(nverts);
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (nverts) HIP_TRY(hipMemcpy(attrs.data(), r->sv.attributes, nverts * sizeof(frt_vertex_attr), hipMemcpyDeviceToHost));
+    std::vector<float> nrm(4 * nverts, 0.0f);
+    for (size_t v = 0; v < nverts; ++v) decoded_vertex_normal(attrs[v], &nrm[4 * v]);
+    void* d = nullptr;
+    if (const int rc = scene_alloc(r, nrm.size() * sizeof(float), &d)) return rc;
+    if (nverts) HIP_TRY(hipMemcpy(d, nrm.data(), nrm.size() * sizeof(float), hipMemcpyHostToDevice));
+    r->ie.d_normals = static_cast<const float4*>(d);
+    return FRT_OK;
+}
+// What both calls end with: the extent and the tree of the triangles the edit wrote, then everything enters the replica together.
+static int commit_instance_edit(frt_renderer* r, uint32_t num_tris, std::vector<InstanceRec>& inst, uint32_t mode, const char* what) {
+    InstanceEditState& e = r->ie;
+    SceneView& sv = r->sv;
+    unsigned int* ext = const_cast<unsigned int*>(r->rf.d_ext);
+    SceneView nv = sv;
+    nv.tris = e.tris; nv.shade_tris = e.shade_tris; nv.instances = e.instances; nv.num_tris = num_tris;
+    HIP_TRY(launch_scene_extent(nv, ext, r->stream));
+    RebuildTarget target;
+    RebuildResult res;
+    const int rc = rebuild_into(r, nv, e.slot_of, mode, what, target, res);
+    if (rc) {
+        if (rc != FRT_ERR_HIP) {      // refused: the extent word of the replica's own triangles again (fail()'s message is kept)
+            HIP_TRY(launch_scene_extent(sv, ext, r->stream));
+            HIP_TRY(hipStreamSynchronize(r->stream));
+        }
+        return rc;
+    }
+    rebuild_swap(r, target, res);      // (what left the replica there are the spare slots and table of the next rebuild)
+    { float4* was = const_cast<float4*>(sv.shade_tris); sv.shade_tris = e.shade_tris; e.shade_tris = was; }
+    { InstanceView* was = const_cast<InstanceView*>(sv.instances); sv.instances = e.instances; e.instances = was; }
+    sv.num_tris = num_tris;
+    r->rf.inst.swap(inst);
+    return FRT_OK;
+}
+
+static int add_instances_impl(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats, uint32_t mode) {
+    RefitState& f = r->rf;
+    InstanceEditState& e = r->ie;
+    SceneView& sv = r->sv;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old_tris = sv.num_tris, old_inst = (uint32_t)f.inst.size();
+    std::vector<InstanceRec> inst = f.inst;
+    std::vector<AppendInstance> rec(n);
+    uint32_t work = 0;
+    for (uint32_t k = 0; k < n; ++k) {      // in argument order: the next instance ids, the next flattened triangle ids
+        const float* m = mats + 16 * (size_t)k;
+        InstanceRec in{};
+        in.mesh_id = mesh_ids[k]; in.mat_id = mat_ids[k]; in.first_tri = old_tris + work; in.tri_count = f.mesh_tris[mesh_ids[k]];
+        memcpy(in.m, m, sizeof(in.m));
+        instance_inverse(m, in.w2o, in.flip);
+        AppendInstance& a = rec[k];
+        memset(&a, 0, sizeof(a));
+        a.id = old_inst + k; a.first_tri = in.first_tri; a.tri_count = in.tri_count; a.work_begin = work;
+        a.index_offset = f.index_offset[in.mesh_id]; a.pos_offset = f.pos_offset[in.mesh_id]; a.attr_offset = f.attr_offset[in.mesh_id];
+        for (int c = 0; c < 4; ++c) for (int x = 0; x < 3; ++x) a.m[3 * c + x] = m[4 * c + x];
+        a.dev.mesh_id = in.mesh_id; a.dev.mat_id = in.mat_id; a.dev.first_tri = in.first_tri; a.dev.flip = in.flip;
+        memcpy(a.dev.w2o, in.w2o, sizeof(in.w2o));
+        work += in.tri_count;
+        inst.push_back(in);
+    }
+    const uint32_t num_tris = old_tris + work, num_inst = old_inst + n;
+    if ((rc = reserve_edit(r, num_tris, num_inst))) return rc;
+    if ((rc = ensure_normals(r))) return rc;
+    const size_t rec_bytes = rec.size() * sizeof(AppendInstance);
+    if ((rc = e.rec.reserve(rec_bytes, rec_bytes, r->stream))) return rc;
+    memcpy(e.rec.h, rec.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(e.rec.d, e.rec.h, rec_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = e.rec.mark(r->stream))) return rc;
+    // what stays: the old slots where they are (and their table), the old shading and instance records
+    HIP_TRY(hipMemcpyAsync(e.tris, sv.tris, (size_t)old_tris * sizeof(TriSlot), hipMemcpyDeviceToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(e.slot_of, f.d_slot_of, (size_t)old_tris * sizeof(uint32_t), hipMemcpyDeviceToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(e.shade_tris, sv.shade_tris, (size_t)old_tris * sizeof(ShadeTri), hipMemcpyDeviceToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(e.instances, sv.instances, (size_t)old_inst * sizeof(InstanceView), hipMemcpyDeviceToDevice, r->stream));
+    const AppendArgs a{reinterpret_cast<const AppendInstance*>(e.rec.d), n, work, f.d_pos, e.d_normals, num_tris, num_inst, InstanceEditTarget{e.tris, e.slot_of, e.shade_tris, e.instances}};
+    HIP_TRY(launch_instances_append(sv, a, r->stream));
+    if ((rc = commit_instance_edit(r, num_tris, inst, mode, "add_instances"))) return rc;
+    return (int)old_inst;
+}
+
+static int remove_instances_impl(frt_renderer* r, const std::vector<uint32_t>& gone, uint32_t mode) {
+    RefitState& f = r->rf;
+    InstanceEditState& e = r->ie;
+    SceneView& sv = r->sv;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old_tris = sv.num_tris, old_inst = (uint32_t)f.inst.size();
+    std::vector<RemovedRange> rng;
+    std::vector<InstanceRec> inst;
+    uint32_t tris_gone = 0;
+    size_t g = 0;
+    for (uint32_t i = 0; i < old_inst; ++i) {
+        if (g < gone.size() && gone[g] == i) {
+            const uint32_t before = tris_gone;
+            tris_gone += f.inst[i].tri_count;
+            rng.push_back(RemovedRange{f.inst[i].first_tri - before, tris_gone, i - (uint32_t)g, 0u});
+            ++g;
+            continue;
+        }
+        InstanceRec in = f.inst[i];
+        in.first_tri -= tris_gone;
+        inst.push_back(in);
+    }
+    const uint32_t num_tris = old_tris - tris_gone, num_inst = (uint32_t)inst.size();
+    if (num_tris == 0) return fail(FRT_ERR_INVALID_ARG, "remove_instances: no triangle would be left (nothing changed)");
+    if ((rc = reserve_edit(r, num_tris, num_inst))) return rc;
+    const size_t rec_bytes = rng.size() * sizeof(RemovedRange);
+    if ((rc = e.rec.reserve(rec_bytes, rec_bytes, r->stream))) return rc;
+    memcpy(e.rec.h, rng.data(), rec_bytes);
+    HIP_TRY(hipMemcpyAsync(e.rec.d, e.rec.h, rec_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = e.rec.mark(r->stream))) return rc;
+    const RemoveArgs a{reinterpret_cast<const RemovedRange*>(e.rec.d), (uint32_t)rng.size(), f.d_slot_of, old_tris, old_inst, num_tris, num_inst,
+                       InstanceEditTarget{e.tris, e.slot_of, e.shade_tris, e.instances}};
+    HIP_TRY(launch_instances_remove(sv, a, r->stream));
+    return commit_instance_edit(r, num_tris, inst, mode, "remove_instances");
+}
+
+static int check_rebuild_mode(const char* what, uint32_t mode) {
+    if (mode != FRT_REBUILD_MORTON && mode != FRT_REBUILD_SAH) return fail(FRT_ERR_INVALID_ARG, std::string(what) + ": unknown rebuild mode (FRT_REBUILD_MORTON, FRT_REBUILD_SAH)");
+    return FRT_OK;
+}
+int frt_renderer_add_instances(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode) {
+    if (const int rc = check_entry(r, "add_instances", kEditChecks)) return rc;
+    if (const int rc = check_rebuild_mode("add_instances", rebuild_mode)) return rc;
+    std::string why;
+    if (const int rc = check_add_instances(n, mesh_ids, mat_ids, m_colmajor16, r->rf.mesh_tris, r->sv.num_materials, r->sv.num_tris, why)) return fail(rc, "add_instances: " + why);
+    if (n == 0) return (int)r->rf.inst.size();
+    const int rc = add_instances_impl(r, n, mesh_ids, mat_ids, m_colmajor16, rebuild_mode);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+int frt_renderer_remove_instances(frt_renderer* r, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode) {
+    if (const int rc = check_entry(r, "remove_instances", kEditChecks)) return rc;
+    if (const int rc = check_rebuild_mode("remove_instances", rebuild_mode)) return rc;
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_instances(n, ids, r->rf.inst, gone, why)) return fail(rc, "remove_instances: " + why);
+    if (gone.empty()) return FRT_OK;
+    const int rc = remove_instances_impl(r, gone, rebuild_mode);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+int frt_renderer_scene_counts(frt_renderer* r, uint32_t counts[4]) {
+    if (!r || !counts) return fail(FRT_ERR_INVALID_ARG, "renderer scene_counts: null");
+    counts[0] = r->sv.num_tris; counts[1] = (uint32_t)r->rf.inst.size(); counts[2] = r->sv.num_materials; counts[3] = r->sv.num_lights;
+    return FRT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ ray queries
 // Ordering: a query is enqueued on the main stream and only reads the scene replica. Every writer of the replica is on that stream too: the instance
 // update and the deformation (their copies, kernels and refit levels; the ahead stream is fenced into the main stream before them), and the rebuild,

@@ -118,6 +118,8 @@ SYMBOLS = {
     "frt_scene_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),
     "frt_scene_set_texture": (C.c_int, [_P, C.c_int, _U32, _P]),
+    "frt_scene_add_instances": (C.c_int, [_P, _U32, _P, _P, _P]),
+    "frt_scene_remove_instances": (C.c_int, [_P, _U32, _P]),
     "frt_scene_trace_closest": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_trace_any": (C.c_int, [_P, _U32, _P, _P]),
     "frt_camera_default": (None, [C.c_float, _U32, _U32, C.POINTER(CameraUniform)]),
@@ -154,6 +156,9 @@ SYMBOLS = {
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),
     "frt_renderer_set_texture": (C.c_int, [_P, C.c_int, _U32, _P]),
     "frt_renderer_read_scene": (C.c_int, [_P, C.c_int, _P]),
+    "frt_renderer_scene_counts": (C.c_int, [_P, _P]),
+    "frt_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
+    "frt_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
     "frt_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
     "frt_renderer_rebuild_stats": (C.c_int, [_P, _P]),
@@ -185,6 +190,8 @@ SYMBOLS = {
     "frt_multi_renderer_set_texture": (C.c_int, [_P, C.c_int, _U32, _P]),
     "frt_multi_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
+    "frt_multi_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
+    "frt_multi_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
     "frt_multi_renderer_trace_closest": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_trace_any": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_pick": (C.c_int, [_P, C.POINTER(CameraUniform), _U32, _P, _P, _U32]),

@@ -2,7 +2,8 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
-from .scene import transform_args, mesh_vertex_args, material_args, id_pair_args, emission_args, texture_args, ray_args, hits_dict, pixel_args, HIT_FIELDS
+from .scene import (transform_args, mesh_vertex_args, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
+                    pixel_args, HIT_FIELDS)
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -278,6 +279,25 @@ class Renderer(_HostQueries):
         else:
             check(lib().frt_renderer_rebuild_tree_ex(self._h, rebuild_mode(quality)))
 
+    # ---- how many instances the replica holds (include/frt.h: frt_renderer_add_instances / _remove_instances): synchronous, between
+    # frames, ending in the device tree rebuild `quality` names; accumulation, reservoirs and frame_count are kept. The host scene is not changed
+    # (SceneBuilder has the same two methods).
+    def add_instances(self, mesh_ids, mat_ids, transforms_colmajor, quality="sah"):
+        """Append instances of existing meshes and materials to this renderer's scene replica; returns the id of the first new instance."""
+        n, me, ma, m = instance_add_args(mesh_ids, mat_ids, transforms_colmajor)
+        return check(lib().frt_renderer_add_instances(self._h, n, me.ctypes.data, ma.ctypes.data, m.ctypes.data, rebuild_mode(quality)))
+
+    def remove_instances(self, ids, quality="sah"):
+        """Remove instances from this renderer's scene replica (an id given twice once); the ids above them shift down."""
+        n, i = instance_id_args(ids)
+        check(lib().frt_renderer_remove_instances(self._h, n, i.ctypes.data, rebuild_mode(quality)))
+
+    def scene_counts(self):
+        """Triangles, instances, materials and lights of the replica as it is now."""
+        c = (C.c_uint32 * 4)()
+        check(lib().frt_renderer_scene_counts(self._h, c))
+        return dict(zip(("tris", "instances", "materials", "lights"), (int(v) for v in c)))
+
     def rebuild_stats(self):
         """The last rebuild_tree that reached the device: mode asked for, clustering iterations ("sah"), why the Morton tree was built instead
         (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added."""
@@ -293,7 +313,7 @@ class Renderer(_HostQueries):
 
     def read_scene(self, what):
         """The device replica in SceneBuilder.get's layout: "materials", "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev", "shade_tris" (syncs first)."""
-        n = self._scene.counts()
+        n = self.scene_counts()      # (the replica's own counts: after add_instances / remove_instances they differ from the host scene's)
         which, shape, dt = {"materials": (2, (n["materials"], 16), np.uint32), "lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
                             "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
                             "instances_dev": (16, (n["instances"], 16), np.uint32), "shade_tris": (17, (n["tris"], 32), np.float32)}[what]
@@ -428,6 +448,16 @@ class MultiRenderer(_HostQueries):
             check(lib().frt_multi_renderer_rebuild_tree(self._h))
         else:
             check(lib().frt_multi_renderer_rebuild_tree_ex(self._h, rebuild_mode(quality)))
+
+    def add_instances(self, mesh_ids, mat_ids, transforms_colmajor, quality="sah"):
+        """Renderer.add_instances on every strip's scene replica."""
+        n, me, ma, m = instance_add_args(mesh_ids, mat_ids, transforms_colmajor)
+        return check(lib().frt_multi_renderer_add_instances(self._h, n, me.ctypes.data, ma.ctypes.data, m.ctypes.data, rebuild_mode(quality)))
+
+    def remove_instances(self, ids, quality="sah"):
+        """Renderer.remove_instances on every strip's scene replica."""
+        n, i = instance_id_args(ids)
+        check(lib().frt_multi_renderer_remove_instances(self._h, n, i.ctypes.data, rebuild_mode(quality)))
 
     def read_buffer(self, buf, index=0):
         out = np.zeros((self.height, self.width, BUF_BPP[buf]), np.uint8)

@@ -68,6 +68,24 @@ def id_pair_args(instance_ids, material_ids):
     return a.size, a.astype(np.uint32), b.astype(np.uint32)
 
 
+def instance_add_args(mesh_ids, mat_ids, transforms_colmajor):
+    """(n, mesh ids, material ids, matrices) for the *_add_instances calls: one mesh id, one material id and one column-major 4x4 per new instance
+    (ints and a single matrix for one instance)."""
+    n, me, ma = id_pair_args(mesh_ids, mat_ids)
+    m = np.ascontiguousarray(transforms_colmajor, np.float32).reshape(-1, 16)
+    if m.shape[0] != n:
+        raise FrtError(f"{n} mesh ids but {m.shape[0]} matrices")
+    return n, me, ma, m
+
+
+def instance_id_args(ids):
+    """(n, ids) for the *_remove_instances calls: `ids` an int or a sequence."""
+    ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, np.int64)))
+    if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise FrtError("instance ids must be a flat list of unsigned 32-bit indices")
+    return ids.size, ids.astype(np.uint32)
+
+
 def emission_args(light, color, intensity):
     if not 0 <= int(light) <= 0xFFFFFFFF:
         raise FrtError("light must be an unsigned 32-bit index")
@@ -229,6 +247,19 @@ class SceneBuilder:
     def set_texture(self, kind, layer, rgba8):
         k, l, t = texture_args(kind, layer, rgba8)
         check(lib().frt_scene_set_texture(self._h, k, l, t.ctypes.data))
+        return self
+
+    # ---- how many instances the built scene holds (include/frt.h: frt_scene_add_instances / _remove_instances). Host copy only:
+    # each costs a host build and leaves the scene equal to one built from scratch with the resulting instance list.
+    def add_instances(self, mesh_ids, mat_ids, transforms_colmajor):
+        """Append instances of existing meshes and materials; returns the id of the first new instance."""
+        n, me, ma, m = instance_add_args(mesh_ids, mat_ids, transforms_colmajor)
+        return check(lib().frt_scene_add_instances(self._h, n, me.ctypes.data, ma.ctypes.data, m.ctypes.data))
+
+    def remove_instances(self, ids):
+        """Remove instances (an id given twice once); the ids above them shift down."""
+        n, i = instance_id_args(ids)
+        check(lib().frt_scene_remove_instances(self._h, n, i.ctypes.data))
         return self
 
     # ---- ray queries on the host copy of the built scene (include/frt.h: frt_scene_trace_closest / _any): the specification of Renderer.trace_*

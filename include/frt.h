@@ -175,6 +175,18 @@ int frt_scene_set_instance_materials(frt_scene* s, uint32_t n, const uint32_t* i
 int frt_scene_set_light_emission(frt_scene* s, uint32_t light, const float color[3], float intensity);
 /* Replace one EXISTING texture layer; kind and pixels as frt_scene_add_texture. */
 int frt_scene_set_texture(frt_scene* s, int kind /*0 colour (sRGB), 1 data*/, uint32_t layer, const uint8_t* rgba8_1024x1024);
+/* How many instances a BUILT scene holds. Afterwards the scene equals, selector for selector of frt_scene_get (the trees included),
+ * a scene built from scratch with the resulting instance list: the call costs a host build. Host copy only; a renderer's replica follows with
+ * frt_renderer_add_instances / _remove_instances. Everything is validated before anything is applied; a refused call changes nothing.
+ * add: n instances of EXISTING meshes and materials, one column-major 4x4 each, appended in argument order with the next instance ids and the next
+ * flattened triangle ids. Returns the id of the first new instance (n == 0: the instance count).
+ * remove: the instances `ids` leave, an id given twice once. Ids stay dense: instance ids above a removed one and flattened triangle ids above its
+ * triangles shift down; a registered light keeps its link to its (renumbered) instance.
+ * FRT_ERR_STATE: scene not built. FRT_ERR_INVALID_ARG: a null pointer with n > 0; an id, mesh id or material id out of range; a non-finite matrix entry or
+ * a singular 3x3; removing an instance made by frt_scene_register_quad_light / _sphere_light (its material and light record carry links to it); removing
+ * every instance. FRT_ERR_LIMIT: more than 0xFFFFFFFE triangles would result, or the builder refuses the new tree. */
+int frt_scene_add_instances(frt_scene* s, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16);
+int frt_scene_remove_instances(frt_scene* s, uint32_t n, const uint32_t* ids);
 /* stats[8]: quad nodes, deepest traversal stack of the quad tree, 8-wide nodes (0: the scene has no 8-wide tree: more than 65,536 nodes), deepest stack of
  * the 8-wide tree, its levels, sum of its nodes' child counts, its triangle slots, how the quad tree was folded (2 surface-area programme, 1 programme where
  * the traversal-stack bound allows and the greedy fold elsewhere, 0 greedy fold) */
@@ -395,6 +407,20 @@ int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t stats[4]);
 /* Read the device replica back (syncs first), in the layout of frt_scene_get: 2 materials, 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
  * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
+/* counts[4]: triangles, instances, materials, lights of the replica AS IT IS NOW (what sizes the arrays of frt_renderer_read_scene). */
+int frt_renderer_scene_counts(frt_renderer* r, uint32_t counts[4]);
+/* frt_scene_add_instances / _remove_instances on this renderer's scene replica, on the device: the same arguments, checks and results.
+ * The new triangles, shading records, instance records and id -> slot table are written out of place and the call ends with the device tree rebuild of
+ * frt_renderer_rebuild_tree_ex in `rebuild_mode` (FRT_REBUILD_MORTON, FRT_REBUILD_SAH); all of it enters the replica together, on success only. Synchronous,
+ * between frames. Afterwards selectors 2, 3, 16 and 17 of frt_renderer_read_scene equal, byte for byte, those of a freshly built scene with the same instance
+ * list, selector 13 holds the same triangle records in the device tree's order, and every frame equals that scene's bit for bit. A next frame's G-buffer +
+ * T-trace that ran ahead is dropped and redone; accumulation, reservoirs and frame_count are kept (the change ghosts until frt_renderer_reset / _clear).
+ * The host frt_scene is not changed. Device buffers grow geometrically and are never shrunk; the per-pixel arena is untouched.
+ * Errors, nothing changed in each case: those of the host calls (the scene is always "built"); FRT_ERR_STATE between the phases of an open frame;
+ * FRT_ERR_INVALID_ARG for an unknown rebuild_mode or a renderer frt_renderer_rebuild_tree refuses; FRT_ERR_LIMIT if the new tree needs more than 31
+ * traversal-stack entries. FRT_ERR_HIP leaves the renderer failed (frt_renderer_clear). */
+int frt_renderer_add_instances(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode);
+int frt_renderer_remove_instances(frt_renderer* r, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
 
 /* Ray queries against this renderer's scene replica AS IT IS NOW on the device: after every frt_renderer_set_instance_transforms,
  * frt_renderer_set_mesh_vertices and frt_renderer_rebuild_tree so far. Results equal frt_scene_trace_closest / _any over a scene in the same state bit for bit.
@@ -467,6 +493,10 @@ int frt_multi_renderer_set_texture(frt_multi_renderer* m, int kind, uint32_t lay
 int frt_multi_renderer_rebuild_tree(frt_multi_renderer* m);
 /* frt_renderer_rebuild_tree_ex on every strip's replica */
 int frt_multi_renderer_rebuild_tree_ex(frt_multi_renderer* m, uint32_t mode);
+/* frt_renderer_add_instances / _remove_instances on every strip's replica (synchronous). A strip that fails after the first one has changed leaves the
+ * handle failed, as a failed render does. */
+int frt_multi_renderer_add_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode);
+int frt_multi_renderer_remove_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
 /* The three ray-query calls on the first strip's replica (all replicas are equal). Host-pointer form only: flags must be 0. */
 int frt_multi_renderer_trace_closest(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags);
 int frt_multi_renderer_trace_any(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags);
