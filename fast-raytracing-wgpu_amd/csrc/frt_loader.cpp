@@ -17,6 +17,7 @@
 #include <map>
 #include <tuple>
 #include <fstream>
+#include <functional>
 #include <sstream>
 
 namespace frt {
@@ -958,12 +959,12 @@ bool load_model(const std::string& path, LoadedModel& out, std::string& err) {
 }
 
 // ================================================================================================ builder.rs:191-314
-std::vector<uint32_t> add_gltf_materials(SceneBuilder& b, const LoadedModel& m) {
+std::vector<frt_material> remap_gltf_materials(const LoadedModel& m, const std::function<uint32_t(uint32_t)>& add_color, const std::function<uint32_t(uint32_t)>& add_data) {
     const size_t ni = m.images.size();
     std::vector<int64_t> color_map(ni, -1), data_map(ni, -1);
-    std::vector<uint32_t> ids;
-    auto color = [&](uint32_t img) -> uint32_t { if (color_map[img] < 0) color_map[img] = b.add_color_texture(m.images[img].data()); return (uint32_t)color_map[img]; };
-    auto data = [&](uint32_t img) -> uint32_t { if (data_map[img] < 0) data_map[img] = b.add_data_texture(m.images[img].data()); return (uint32_t)data_map[img]; };
+    std::vector<frt_material> out;
+    auto color = [&](uint32_t img) -> uint32_t { if (color_map[img] < 0) color_map[img] = add_color(img); return (uint32_t)color_map[img]; };
+    auto data = [&](uint32_t img) -> uint32_t { if (data_map[img] < 0) data_map[img] = add_data(img); return (uint32_t)data_map[img]; };
     for (frt_material mat : m.materials) {
         // order as in the reference: base colour (colour array), normal, occlusion (data array), emissive (colour), metallic-roughness (data)
         uint32_t t = mat.tex_info_0 & 0xFFFFu;
@@ -976,8 +977,16 @@ std::vector<uint32_t> add_gltf_materials(SceneBuilder& b, const LoadedModel& m) 
         if (t != 0xFFFFu && t < ni) mat.tex_info_1 = pack16(mat.tex_info_1, color(t), true);
         t = mat.tex_info_2 & 0xFFFFu;
         if (t != 0xFFFFu && t < ni) mat.tex_info_2 = pack16(mat.tex_info_2, data(t), false);
-        ids.push_back(b.add_material(mat));
+        out.push_back(mat);
     }
+    return out;
+}
+std::vector<uint32_t> add_gltf_materials(SceneBuilder& b, const LoadedModel& m) {
+    std::vector<uint32_t> ids;
+    // (textures and materials go to different arrays: adding the materials after the layers numbers both as adding them in turn does)
+    for (const frt_material& mat : remap_gltf_materials(m, [&](uint32_t img) { return b.add_color_texture(m.images[img].data()); },
+                                                        [&](uint32_t img) { return b.add_data_texture(m.images[img].data()); }))
+        ids.push_back(b.add_material(mat));
     return ids;
 }
 std::vector<uint32_t> add_gltf_meshes(SceneBuilder& b, const LoadedModel& m) {
@@ -1077,6 +1086,16 @@ int frt_scene_add_gltf_materials(frt_scene* s, const frt_model* m, uint32_t* mat
     s->b.built = false;
     if (mat_ids) memcpy(mat_ids, ids.data(), ids.size() * sizeof(uint32_t));
     return (int)ids.size();
+}
+int frt_model_layer_plan(const frt_model* m, uint32_t color_layers, uint32_t data_layers, frt_material* materials_out, uint32_t* color_images, uint32_t* data_images, uint32_t counts[2]) {
+    if (!m || !counts || (!m->m.materials.empty() && !materials_out) || (!m->m.images.empty() && (!color_images || !data_images))) return set_error(FRT_ERR_INVALID_ARG, "model_layer_plan: null");
+    if ((uint64_t)color_layers + m->m.images.size() >= 0xFFFFu || (uint64_t)data_layers + m->m.images.size() >= 0xFFFFu) return set_error(FRT_ERR_LIMIT, "too many texture layers");
+    uint32_t nc = 0, nd = 0;
+    const std::vector<frt_material> mats = remap_gltf_materials(m->m, [&](uint32_t img) { color_images[nc] = img; return color_layers + nc++; },
+                                                                [&](uint32_t img) { data_images[nd] = img; return data_layers + nd++; });
+    if (!mats.empty()) memcpy(materials_out, mats.data(), mats.size() * sizeof(frt_material));
+    counts[0] = nc; counts[1] = nd;
+    return FRT_OK;
 }
 int frt_scene_add_gltf_meshes(frt_scene* s, const frt_model* m, uint32_t* mesh_ids) {
     if (!s || !m) return set_error(FRT_ERR_INVALID_ARG, "add_gltf_meshes: null");

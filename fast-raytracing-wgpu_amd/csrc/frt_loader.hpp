@@ -4,6 +4,7 @@
 // has no OBJ path) so that the usual Bunny / Sponza distributions load. Host only; nothing here touches the GPU.
 #pragma once
 #include "frt_scene.hpp"
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -29,6 +30,9 @@ bool decode_png(const uint8_t* data, size_t size, std::vector<uint8_t>& pixels, 
 // Huffman JPEG (baseline and progressive, 8-bit, 3-component) -> RGB8
 bool decode_jpeg(const uint8_t* data, size_t size, std::vector<uint8_t>& rgb, uint32_t& w, uint32_t& h, std::string& why);
 
+// builder.rs:191-292 without the builder: the model's materials with every image index remapped to the layer id `add_color` / `add_data` returns for
+// that image (each is called once per image it is asked about, in the reference's order). What add_gltf_materials and frt_model_layer_plan share.
+std::vector<frt_material> remap_gltf_materials(const LoadedModel& m, const std::function<uint32_t(uint32_t)>& add_color, const std::function<uint32_t(uint32_t)>& add_data);
 // builder.rs:191-314
 std::vector<uint32_t> add_gltf_materials(SceneBuilder& b, const LoadedModel& m);
 std::vector<uint32_t> add_gltf_meshes(SceneBuilder& b, const LoadedModel& m);

@@ -283,6 +283,17 @@ int edit_every_replica(frt_multi_renderer* m, const char* what, Edit edit) {
     }
     return FRT_OK;
 }
+// ... for a call that returns an id (>= 0) instead of FRT_OK: the first strip's id (the replicas hold the same scene, so every strip hands out the same).
+template <class Add>
+int add_to_every_replica(frt_multi_renderer* m, const char* what, Add add) {
+    int first = 0;
+    const int rc = edit_every_replica(m, what, [&](frt_renderer* r) {
+        const int id = add(r);
+        if (id >= 0) first = id;
+        return id < 0 ? id : (int)FRT_OK;
+    });
+    return rc ? rc : first;
+}
 }   // namespace
 
 extern "C" {
@@ -488,6 +499,27 @@ int frt_multi_renderer_add_instances(frt_multi_renderer* m, uint32_t n, const ui
 }
 int frt_multi_renderer_remove_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode) {
     return edit_every_replica(m, "multi remove_instances", [&](frt_renderer* r) { return frt_renderer_remove_instances(r, n, ids, rebuild_mode); });
+}
+
+// New meshes, materials, texture layers and lights on every strip's replica, as above: the replicas hold the same scene, so every strip
+// hands out the same ids; the first strip's refusal leaves every replica as it was.
+int frt_multi_renderer_add_meshes(frt_multi_renderer* m, uint32_t n, const frt_mesh_data* meshes) {
+    return add_to_every_replica(m, "multi add_meshes", [&](frt_renderer* r) { return frt_renderer_add_meshes(r, n, meshes); });
+}
+int frt_multi_renderer_add_materials(frt_multi_renderer* m, uint32_t n, const frt_material* materials) {
+    return add_to_every_replica(m, "multi add_materials", [&](frt_renderer* r) { return frt_renderer_add_materials(r, n, materials); });
+}
+int frt_multi_renderer_add_texture(frt_multi_renderer* m, int kind, const uint8_t* rgba8) {
+    return add_to_every_replica(m, "multi add_texture", [&](frt_renderer* r) { return frt_renderer_add_texture(r, kind, rgba8); });
+}
+int frt_multi_renderer_add_lights(frt_multi_renderer* m, uint32_t n, const frt_light* lights) {
+    return add_to_every_replica(m, "multi add_lights", [&](frt_renderer* r) { return frt_renderer_add_lights(r, n, lights); });
+}
+int frt_multi_renderer_register_quad_light(frt_multi_renderer* m, uint32_t mesh_id, const float mat[16], const float color[3], float intensity, uint32_t rebuild_mode) {
+    return add_to_every_replica(m, "multi register_quad_light", [&](frt_renderer* r) { return frt_renderer_register_quad_light(r, mesh_id, mat, color, intensity, rebuild_mode); });
+}
+int frt_multi_renderer_register_sphere_light(frt_multi_renderer* m, uint32_t mesh_id, const float mat[16], const float color[3], float intensity, uint32_t rebuild_mode) {
+    return add_to_every_replica(m, "multi register_sphere_light", [&](frt_renderer* r) { return frt_renderer_register_sphere_light(r, mesh_id, mat, color, intensity, rebuild_mode); });
 }
 
 int frt_multi_renderer_set_jitter(frt_multi_renderer* m, float jx, float jy) {

@@ -6,6 +6,7 @@
 #include "frt_deform.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
+#include "frt_mesh_edit.hpp"
 #include "frt_query.hpp"        // (frt_scene.hpp, frt_kernels.hpp)
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -151,6 +152,17 @@ struct InstanceEditState {
     uint32_t growths = 0;                  // calls that had to grow a capacity
 };
 
+// What frt_renderer_add_meshes / _add_materials / _add_texture / _add_lights / _register_*_light add. From the first such call on, the
+// replica's buffers that are sized by vertices, indices, meshes, materials, lights and texture layers have a capacity apart from their count, under the
+// rules of §14: a capacity at least doubles when it grows (the texture arrays, 4 MiB a layer: by max(4, count / 2) layers), is never shrunk, and a
+// growth is a new allocation plus a device-to-device copy behind a wait for the stream. A renderer that never makes such a call allocates nothing.
+enum { kPoolVerts = 0, kPoolIndices, kPoolMeshes, kPoolMaterials, kPoolLights, kPoolColor, kPoolData, kPoolCount };
+struct MeshEditState {
+    uint32_t cap[kPoolCount] = {};         // 0: the pool is as uploaded, exactly as large as its count
+    uint32_t growths = 0;                  // calls that had to grow a capacity
+    Staging up;                            // what one call uploads: the pinned block and, for add_meshes, the device block its kernel reads
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -215,6 +227,7 @@ struct frt_renderer {
     RefitState rf;
     RebuildState rbt;
     InstanceEditState ie;
+    MeshEditState me;
     // The host-pointer ray queries: both blocks [input | output] of a call. Such a call is synchronous — the last call's copies are done
     // when the next one starts — so this one is never marked: no event is created, recorded or waited for.
     Staging qry;

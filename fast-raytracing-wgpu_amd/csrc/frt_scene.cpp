@@ -275,20 +275,20 @@ frt_light sphere_light_record(const Mat4& t, const float emission[4]) {
 void light_emissive_factor(const float color[3], float intensity, float out[3]) {
     for (int k = 0; k < 3; ++k) out[k] = color[k] * intensity;
 }
-static frt_material emissive_material(size_t light_index, const float color[3], float intensity) {
+frt_material light_emissive_material(size_t light_index, const float color[3], float intensity) {
     float e[3];
     light_emissive_factor(color, intensity, e);
     return MaterialBuilder(1, 1, 1, 1).light_index((int32_t)light_index).emissive_factor(e[0], e[1], e[2]).texture(0);
 }
 void SceneBuilder::register_quad_light(uint32_t mesh_id, const Mat4& t, const float color[3], float intensity) {
-    uint32_t mat = add_material(emissive_material(lights.size(), color, intensity));
+    uint32_t mat = add_material(light_emissive_material(lights.size(), color, intensity));
     add_instance(mesh_id, mat, t);
     instances.back().light = (int32_t)lights.size(); instances.back().light_kind = 0;
     const float em[4] = {color[0], color[1], color[2], intensity};
     lights.push_back(quad_light_record(t, em));
 }
 void SceneBuilder::register_sphere_light(uint32_t mesh_id, const Mat4& t, const float color[3], float intensity) {
-    uint32_t mat = add_material(emissive_material(lights.size(), color, intensity));
+    uint32_t mat = add_material(light_emissive_material(lights.size(), color, intensity));
     add_instance(mesh_id, mat, t);
     instances.back().light = (int32_t)lights.size(); instances.back().light_kind = 1;
     const float em[4] = {color[0], color[1], color[2], intensity};
@@ -578,6 +578,62 @@ int SceneBuilder::remove_instances(uint32_t n, const uint32_t* ids) {
     }
     return FRT_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- new meshes, materials, layers, lights
+int check_add_meshes(uint32_t n, const frt_mesh_data* meshes, uint64_t num_verts, uint64_t num_indices, std::string& why) {
+    if (n > 0 && !meshes) { why = "null meshes"; return FRT_ERR_INVALID_ARG; }
+    uint64_t verts = num_verts, indices = num_indices;
+    for (uint32_t k = 0; k < n; ++k) {
+        const frt_mesh_data& m = meshes[k];
+        const std::string which = "mesh " + std::to_string(k) + ": ";
+        if (!m.pos4 || !m.attrs || !m.idx) { why = which + "null positions, attributes or indices"; return FRT_ERR_INVALID_ARG; }
+        if (m.nverts == 0) { why = which + "no vertices"; return FRT_ERR_INVALID_ARG; }
+        if (m.nidx == 0 || m.nidx % 3u != 0u) { why = which + std::to_string(m.nidx) + " indices (a positive multiple of 3 is needed)"; return FRT_ERR_INVALID_ARG; }
+        for (uint32_t i = 0; i < m.nidx; ++i)
+            if (m.idx[i] >= m.nverts) { why = which + "index " + std::to_string(i) + " is " + std::to_string(m.idx[i]) + ", the mesh has " + std::to_string(m.nverts) + " vertices"; return FRT_ERR_INVALID_ARG; }
+        const std::string bad = check_mesh_vertices(m.pos4, m.attrs, m.nverts, m.nverts);
+        if (!bad.empty()) { why = which + bad; return FRT_ERR_INVALID_ARG; }
+        verts += m.nverts; indices += m.nidx;      // (n < 2^32 terms of less than 2^32 each: no overflow in 64 bits)
+    }
+    if (verts > kMaxPoolElems) { why = std::to_string(verts) + " vertices would result, " + std::to_string(kMaxPoolElems) + " is the limit"; return FRT_ERR_LIMIT; }
+    if (indices > kMaxPoolElems) { why = std::to_string(indices) + " indices would result, " + std::to_string(kMaxPoolElems) + " is the limit"; return FRT_ERR_LIMIT; }
+    return FRT_OK;
+}
+int check_add_materials(uint32_t n, const frt_material* mats, size_t num_materials, size_t color_layers, size_t data_layers, size_t num_lights, std::string& why) {
+    if (n > 0 && !mats) { why = "null materials"; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string bad = check_material(mats[k], color_layers, data_layers, num_lights);
+        if (!bad.empty()) { why = "material " + std::to_string(k) + ": " + bad; return FRT_ERR_INVALID_ARG; }
+    }
+    if ((uint64_t)num_materials + n > kMaxMaterials) { why = "more than 65535 materials (custom index packs 16 bits, builder.rs:184)"; return FRT_ERR_LIMIT; }
+    return FRT_OK;
+}
+int check_add_texture(int kind, const uint8_t* rgba8, size_t color_layers, size_t data_layers, std::string& why) {
+    if (kind != 0 && kind != 1) { why = "kind must be 0 (colour) or 1 (data)"; return FRT_ERR_INVALID_ARG; }
+    if (!rgba8) { why = "null pixels"; return FRT_ERR_INVALID_ARG; }
+    if ((kind == 0 ? color_layers : data_layers) >= kMaxTextureLayers) { why = "too many texture layers"; return FRT_ERR_LIMIT; }
+    return FRT_OK;
+}
+int check_add_lights(uint32_t n, const frt_light* lights, std::string& why) {
+    if (n > 0 && !lights) { why = "null lights"; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k) {
+        const frt_light& l = lights[k];
+        const float f[14] = {l.position[0], l.position[1], l.position[2], l.u[0], l.u[1], l.u[2], l.area, l.v[0], l.v[1], l.v[2], l.emission[0], l.emission[1], l.emission[2], l.emission[3]};
+        for (float x : f) if (!std::isfinite(x)) { why = "light " + std::to_string(k) + " has a non-finite field"; return FRT_ERR_INVALID_ARG; }
+        if (!(l.area > 0.0f)) { why = "light " + std::to_string(k) + " has no area"; return FRT_ERR_INVALID_ARG; }
+    }
+    return FRT_OK;
+}
+void pack_mesh_appends(uint32_t n, const frt_mesh_data* meshes, uint32_t num_verts, uint32_t num_indices, std::vector<MeshAppend>& rec, uint32_t& new_verts, uint32_t& new_indices) {
+    rec.assign(n, MeshAppend{});
+    new_verts = new_indices = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        rec[k] = MeshAppend{num_verts + new_verts, num_indices + new_indices, meshes[k].nverts, meshes[k].nidx, new_verts, new_indices, {0u, 0u}};
+        new_verts += meshes[k].nverts; new_indices += meshes[k].nidx;
+    }
+}
+uint32_t grown_capacity(uint64_t have, uint64_t need, uint64_t limit) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 2ull * have), limit); }
+uint32_t grown_layer_capacity(uint64_t have, uint64_t need) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, have + std::max<uint64_t>(4, have / 2)), kMaxTextureLayers); }
 
 void SceneBuilder::build() {
     error.clear();

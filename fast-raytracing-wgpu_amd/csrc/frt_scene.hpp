@@ -192,6 +192,27 @@ int check_add_instances(uint32_t n, const uint32_t* mesh_ids, const uint32_t* ma
 int check_remove_instances(uint32_t n, const uint32_t* ids, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why);
 // emissive_factor of the material register_*_light makes for (colour, intensity): colour[k] * intensity in f32.
 void light_emissive_factor(const float color[3], float intensity, float out[3]);
+// The material register_*_light makes for its instance: white, emissive, linked to light `light_index`.
+frt_material light_emissive_material(size_t light_index, const float color[3], float intensity);
+// Argument checks of the calls that add meshes, materials, texture layers and lights to a renderer's replica: FRT_OK, or the code with
+// `why` set. The counts are the replica's as they are; nothing here knows a device, so a stand-alone host program can call them.
+static const uint64_t kMaxPoolElems = 0xFFFFFFFFull;      // vertices and indices are addressed with 32 bits
+static const size_t kMaxMaterials = 0xFFFFu;            // (frt_scene_add_material)
+static const size_t kMaxTextureLayers = 0xFFFEu;        // a texture array of a replica: a 65,535th layer is refused (0xFFFF means "none" in tex_info_*)
+int check_add_meshes(uint32_t n, const frt_mesh_data* meshes, uint64_t num_verts, uint64_t num_indices, std::string& why);
+int check_add_materials(uint32_t n, const frt_material* mats, size_t num_materials, size_t color_layers, size_t data_layers, size_t num_lights, std::string& why);
+int check_add_texture(int kind, const uint8_t* rgba8, size_t color_layers, size_t data_layers, std::string& why);
+int check_add_lights(uint32_t n, const frt_light* lights, std::string& why);
+// One appended mesh of a call, 32 B, as mesh_append_kernel reads it (frt_mesh_edit.hpp): where its vertices and indices go in the replica's pools, how
+// many there are, and where they begin among the call's staged vertices and indices (prefix sums over the meshes before it).
+struct MeshAppend { uint32_t vert_base, index_base, nverts, nidx, vert_begin, index_begin, pad[2]; };
+static_assert(sizeof(MeshAppend) == 32, "MeshAppend layout");
+// The records of a call that passed check_add_meshes, for pools that hold num_verts vertices and num_indices indices; returns the call's totals.
+void pack_mesh_appends(uint32_t n, const frt_mesh_data* meshes, uint32_t num_verts, uint32_t num_indices, std::vector<MeshAppend>& rec, uint32_t& new_verts, uint32_t& new_indices);
+// The capacity a pool of `have` elements gets when `need` no longer fit: at least twice as many, never beyond `limit`.
+uint32_t grown_capacity(uint64_t have, uint64_t need, uint64_t limit);
+// ... and a texture array, whose layers are 4 MiB each: max(4, have / 2) layers more, or what is needed.
+uint32_t grown_layer_capacity(uint64_t have, uint64_t need);
 // The instance a light was registered with, or -1 (a light of add_light / add_*_light).
 int light_instance(const std::vector<InstanceRec>& instances, uint32_t light);
 static const size_t kTextureLayerBytes = 1024u * 1024u * 4u;   // src/scene/mod.rs:12-13

@@ -1,7 +1,8 @@
 // frt_scene_edit.hip — what edits or reads a renderer's scene replica between frames (include/frt.h): moving instances,
-// deforming meshes, the material, light and texture edits (§13), the tree rebuild, adding and removing instances (§14), the ray queries,
+// deforming meshes, the material, light and texture edits (§13), the tree rebuild, adding and removing instances (§14), new meshes, materials, texture
+// layers and lights (§15), the ray queries,
 // frt_renderer_read_scene and the tree statistics.
-// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
+// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -563,7 +564,8 @@ static int commit_instance_edit(frt_renderer* r, uint32_t num_tris, std::vector<
     return FRT_OK;
 }
 
-static int add_instances_impl(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats, uint32_t mode) {
+// (`light` >= 0, register_*_light of §15: the first new instance carries the link to that light, of kind `light_kind`)
+static int add_instances_impl(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* mats, uint32_t mode, int32_t light = -1, uint32_t light_kind = 0) {
     RefitState& f = r->rf;
     InstanceEditState& e = r->ie;
     SceneView& sv = r->sv;
@@ -588,6 +590,7 @@ static int add_instances_impl(frt_renderer* r, uint32_t n, const uint32_t* mesh_
         a.dev.mesh_id = in.mesh_id; a.dev.mat_id = in.mat_id; a.dev.first_tri = in.first_tri; a.dev.flip = in.flip;
         memcpy(a.dev.w2o, in.w2o, sizeof(in.w2o));
         work += in.tri_count;
+        if (k == 0 && light >= 0) { in.light = light; in.light_kind = light_kind; }
         inst.push_back(in);
     }
     const uint32_t num_tris = old_tris + work, num_inst = old_inst + n;
@@ -678,6 +681,260 @@ int frt_renderer_scene_counts(frt_renderer* r, uint32_t counts[4]) {
     return FRT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ new meshes, materials, layers, lights
+// Ordering: as the edits of §13 (order_behind_frames, the speculation dropped). What a call uploads is written into the pinned block of r->me.up and
+// copied from there, on the main stream: materials, lights and texture layers straight into the replica's pools, the vertices and indices of new meshes
+// into the device block mesh_append_kernel reads. A pool that is too small grows first (reserve_pools): behind a wait for the stream, by a new
+// allocation and a device-to-device copy of what is in use. The host bookkeeping (RefitState) and the counts of the SceneView follow when everything
+// is enqueued, so that the edits of §11 - §14 accept the new ids.
+static uint32_t pool_verts(const frt_renderer* r) { const RefitState& f = r->rf; return f.attr_offset.empty() ? 0u : f.attr_offset.back() + f.vert_count.back(); }
+static uint32_t pool_indices(const frt_renderer* r) { const RefitState& f = r->rf; return f.index_offset.empty() ? 0u : f.index_offset.back() + 3u * f.mesh_tris.back(); }
+static uint32_t pool_count(const frt_renderer* r, int pool) {
+    switch (pool) {
+    case kPoolVerts: return pool_verts(r);
+    case kPoolIndices: return pool_indices(r);
+    case kPoolMeshes: return (uint32_t)r->rf.mesh_tris.size();
+    case kPoolMaterials: return r->sv.num_materials;
+    case kPoolLights: return r->sv.num_lights;
+    case kPoolColor: return r->rf.color_layers;
+    default: return r->rf.data_layers;
+    }
+}
+// grow_live for a pool: an allocation that fails is a limit, not a broken device (nothing has changed then).
+static int grow_pool(frt_renderer* r, const void* live_ptr, size_t elem, size_t used, size_t cap) {
+    const void** live = static_cast<const void**>(const_cast<void*>(live_ptr));
+    void* d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(cap * elem, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FRT_ERR_LIMIT, "no device memory for " + std::to_string(cap * elem) + " bytes (nothing changed)");
+    }
+    r->scene_allocs.push_back(d);
+    if (used) HIP_TRY(hipMemcpy(d, *live, used * elem, hipMemcpyDeviceToDevice));
+    scene_free(r, *live);
+    *live = d;
+    return FRT_OK;
+}
+// Room for `need[pool]` elements in every pool (0: the pool is not asked about). A pool's capacity is its count until it first grows.
+static int reserve_pools(frt_renderer* r, const uint32_t need[kPoolCount]) {
+    MeshEditState& e = r->me;
+    SceneView& sv = r->sv;
+    bool synced = false, grew = false;
+    for (int p = 0; p < kPoolCount; ++p) {
+        const uint32_t used = pool_count(r, p), have = e.cap[p] ? e.cap[p] : used;
+        if (need[p] <= have) continue;
+        if (!synced) { HIP_TRY(hipStreamSynchronize(r->stream)); synced = true; }      // (the ahead stream is fenced into it: no kernel reads what is replaced below)
+        const uint32_t cap = p == kPoolColor || p == kPoolData ? grown_layer_capacity(have, need[p])
+                           : grown_capacity(have, need[p], p == kPoolMaterials ? kMaxMaterials : kMaxPoolElems);
+        int rc = FRT_OK;
+        switch (p) {
+        case kPoolVerts:
+            if ((rc = grow_pool(r, &r->rf.d_pos, sizeof(float4), used, cap))) return rc;
+            if ((rc = grow_pool(r, &sv.attributes, sizeof(VertexAttrView), used, cap))) return rc;
+            if ((rc = grow_pool(r, &r->ie.d_normals, sizeof(float4), used, cap))) return rc;
+            break;
+        case kPoolIndices: rc = grow_pool(r, &sv.indices, sizeof(uint32_t), used, cap); break;
+        case kPoolMeshes: rc = grow_pool(r, &sv.mesh_infos, sizeof(MeshInfoView), used, cap); break;
+        case kPoolMaterials: rc = grow_pool(r, &sv.materials, sizeof(MaterialView), used, cap); break;
+        case kPoolLights: rc = grow_pool(r, &sv.lights, sizeof(LightView), used, cap); break;
+        case kPoolColor: rc = grow_pool(r, &sv.color_tex, kTextureLayerBytes, used, cap); break;
+        default: rc = grow_pool(r, &sv.data_tex, kTextureLayerBytes, used, cap); break;
+        }
+        if (rc) return rc;
+        e.cap[p] = cap;
+        grew = true;
+    }
+    if (grew) ++e.growths;
+    return FRT_OK;
+}
+// `bytes` from `src` through the pinned block at `h_off` to `dst`, on the main stream (the caller has reserved the block and marks it afterwards).
+static int staged_copy(frt_renderer* r, size_t h_off, const void* src, void* dst, size_t bytes) {
+    memcpy(r->me.up.h + h_off, src, bytes);
+    HIP_TRY(hipMemcpyAsync(dst, r->me.up.h + h_off, bytes, hipMemcpyHostToDevice, r->stream));
+    return FRT_OK;
+}
+
+static int add_meshes_impl(frt_renderer* r, uint32_t n, const frt_mesh_data* meshes) {
+    RefitState& f = r->rf;
+    MeshEditState& e = r->me;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old_meshes = (uint32_t)f.mesh_tris.size(), old_verts = pool_verts(r), old_indices = pool_indices(r);
+    std::vector<MeshAppend> rec;
+    uint32_t nv = 0, ni = 0;
+    pack_mesh_appends(n, meshes, old_verts, old_indices, rec, nv, ni);
+    if ((rc = ensure_normals(r))) return rc;      // (at the replica's present size; the pool of the vertices grows with the others below)
+    uint32_t need[kPoolCount] = {};
+    need[kPoolVerts] = old_verts + nv; need[kPoolIndices] = old_indices + ni; need[kPoolMeshes] = old_meshes + n;
+    if ((rc = reserve_pools(r, need))) return rc;
+    // one block: [records | positions | attributes | indices], each part 16-byte aligned (32 n, 16 nv and 32 nv bytes in front of the indices)
+    const size_t rec_bytes = (size_t)n * sizeof(MeshAppend), pos_bytes = (size_t)nv * 16, attr_bytes = (size_t)nv * sizeof(frt_vertex_attr), idx_bytes = (size_t)ni * 4;
+    const size_t pos_at = rec_bytes, attr_at = pos_at + pos_bytes, idx_at = attr_at + attr_bytes, all_bytes = idx_at + idx_bytes;
+    if ((rc = e.up.reserve(all_bytes, all_bytes, r->stream))) return rc;
+    memcpy(e.up.h, rec.data(), rec_bytes);
+    for (uint32_t k = 0; k < n; ++k) {
+        memcpy(e.up.h + pos_at + (size_t)rec[k].vert_begin * 16, meshes[k].pos4, (size_t)meshes[k].nverts * 16);
+        memcpy(e.up.h + attr_at + (size_t)rec[k].vert_begin * sizeof(frt_vertex_attr), meshes[k].attrs, (size_t)meshes[k].nverts * sizeof(frt_vertex_attr));
+        memcpy(e.up.h + idx_at + (size_t)rec[k].index_begin * 4, meshes[k].idx, (size_t)meshes[k].nidx * 4);
+    }
+    HIP_TRY(hipMemcpyAsync(e.up.d, e.up.h, all_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = e.up.mark(r->stream))) return rc;
+    MeshAppendArgs a{};
+    a.rec = reinterpret_cast<const MeshAppend*>(e.up.d); a.nrec = n; a.nverts = nv; a.nidx = ni;
+    a.pos = reinterpret_cast<const float4*>(e.up.d + pos_at); a.attrs = reinterpret_cast<const float4*>(e.up.d + attr_at); a.idx = reinterpret_cast<const uint32_t*>(e.up.d + idx_at);
+    a.out_pos = const_cast<float4*>(f.d_pos); a.out_attrs = reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes));
+    a.out_normals = const_cast<float4*>(r->ie.d_normals); a.out_idx = const_cast<uint32_t*>(r->sv.indices); a.out_infos = const_cast<MeshInfoView*>(r->sv.mesh_infos);
+    a.mesh_base = old_meshes;
+    a.cap_verts = e.cap[kPoolVerts] ? e.cap[kPoolVerts] : old_verts; a.cap_indices = e.cap[kPoolIndices] ? e.cap[kPoolIndices] : old_indices;
+    a.cap_meshes = e.cap[kPoolMeshes] ? e.cap[kPoolMeshes] : old_meshes;
+    HIP_TRY(launch_mesh_append(a, r->stream));
+    for (uint32_t k = 0; k < n; ++k) {
+        f.pos_offset.push_back(rec[k].vert_base); f.attr_offset.push_back(rec[k].vert_base); f.index_offset.push_back(rec[k].index_base);
+        f.vert_count.push_back(rec[k].nverts); f.mesh_tris.push_back(rec[k].nidx / 3u);
+    }
+    return (int)old_meshes;
+}
+int frt_renderer_add_meshes(frt_renderer* r, uint32_t n, const frt_mesh_data* meshes) {
+    if (const int rc = check_entry(r, "add_meshes", kLookChecks)) return rc;
+    const RefitState& f = r->rf;
+    const uint64_t pos_verts = f.pos_offset.empty() ? 0u : (uint64_t)f.pos_offset.back() + f.vert_count.back();
+    if (pos_verts != pool_verts(r)) return fail(FRT_ERR_STATE, "add_meshes: the replica's positions and attributes are not numbered alike");
+    std::string why;
+    if (const int rc = check_add_meshes(n, meshes, pool_verts(r), pool_indices(r), why)) return fail(rc, "add_meshes: " + why);
+    if (n == 0) return (int)f.mesh_tris.size();
+    uint64_t work = 0;
+    for (uint32_t k = 0; k < n; ++k) work += (uint64_t)meshes[k].nverts + meshes[k].nidx;
+    if (work > 0xFFFFFF00ull || (uint64_t)f.mesh_tris.size() + n > 0x7FFFFFFFull) return fail(FRT_ERR_LIMIT, "add_meshes: too many vertices and indices, or meshes, in one call");
+    const int rc = add_meshes_impl(r, n, meshes);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int add_materials_impl(frt_renderer* r, uint32_t n, const frt_material* mats) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old = r->sv.num_materials;
+    uint32_t need[kPoolCount] = {};
+    need[kPoolMaterials] = old + n;
+    if ((rc = reserve_pools(r, need))) return rc;
+    const size_t bytes = (size_t)n * sizeof(frt_material);
+    if ((rc = r->me.up.reserve(bytes, 0, r->stream))) return rc;
+    if ((rc = staged_copy(r, 0, mats, const_cast<MaterialView*>(r->sv.materials) + old, bytes))) return rc;
+    if ((rc = r->me.up.mark(r->stream))) return rc;
+    r->sv.num_materials = old + n;
+    return (int)old;
+}
+int frt_renderer_add_materials(frt_renderer* r, uint32_t n, const frt_material* materials) {
+    if (const int rc = check_entry(r, "add_materials", kLookChecks)) return rc;
+    std::string why;
+    if (const int rc = check_add_materials(n, materials, r->sv.num_materials, r->rf.color_layers, r->rf.data_layers, r->sv.num_lights, why)) return fail(rc, "add_materials: " + why);
+    if (n == 0) return (int)r->sv.num_materials;
+    const int rc = add_materials_impl(r, n, materials);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int add_texture_impl(frt_renderer* r, int kind, const uint8_t* rgba8) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    uint32_t& layers = kind == 0 ? r->rf.color_layers : r->rf.data_layers;
+    uint32_t need[kPoolCount] = {};
+    need[kind == 0 ? kPoolColor : kPoolData] = layers + 1u;
+    if ((rc = reserve_pools(r, need))) return rc;
+    if ((rc = r->me.up.reserve(kTextureLayerBytes, 0, r->stream))) return rc;
+    uint8_t* dst = const_cast<uint8_t*>(kind == 0 ? r->sv.color_tex : r->sv.data_tex) + (size_t)layers * kTextureLayerBytes;
+    if ((rc = staged_copy(r, 0, rgba8, dst, kTextureLayerBytes))) return rc;
+    if ((rc = r->me.up.mark(r->stream))) return rc;
+    return (int)layers++;
+}
+int frt_renderer_add_texture(frt_renderer* r, int kind, const uint8_t* rgba8) {
+    if (const int rc = check_entry(r, "add_texture", kLookChecks)) return rc;
+    std::string why;
+    if (const int rc = check_add_texture(kind, rgba8, r->rf.color_layers, r->rf.data_layers, why)) return fail(rc, "add_texture: " + why);
+    const int rc = add_texture_impl(r, kind, rgba8);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int add_lights_impl(frt_renderer* r, uint32_t n, const frt_light* lights) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old = r->sv.num_lights;
+    uint32_t need[kPoolCount] = {};
+    need[kPoolLights] = old + n;
+    if ((rc = reserve_pools(r, need))) return rc;
+    const size_t bytes = (size_t)n * sizeof(frt_light);
+    if ((rc = r->me.up.reserve(bytes, 0, r->stream))) return rc;
+    if ((rc = staged_copy(r, 0, lights, const_cast<LightView*>(r->sv.lights) + old, bytes))) return rc;
+    if ((rc = r->me.up.mark(r->stream))) return rc;
+    r->rf.lights.insert(r->rf.lights.end(), lights, lights + n);
+    r->sv.num_lights = old + n;
+    return (int)old;
+}
+int frt_renderer_add_lights(frt_renderer* r, uint32_t n, const frt_light* lights) {
+    if (const int rc = check_entry(r, "add_lights", kLookChecks)) return rc;
+    std::string why;
+    if (const int rc = check_add_lights(n, lights, why)) return fail(rc, "add_lights: " + why);
+    if ((uint64_t)r->sv.num_lights + n > 0x7FFFFFFFull) return fail(FRT_ERR_LIMIT, "add_lights: a material's light_index is a signed 32-bit number");
+    if (n == 0) return (int)r->sv.num_lights;
+    const int rc = add_lights_impl(r, n, lights);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// register_quad_light / register_sphere_light of the builder (frt_scene.cpp) on the replica: the material and the light record are made by the builder's
+// own functions; the pools get their room first (a refusal there changes nothing), then the instance goes through add_instances_impl with the ids the
+// material and the light are about to get, and only when its tree is in place do the two records follow and the counts move.
+static int register_light_impl(frt_renderer* r, uint32_t mesh_id, const float* m, const frt_material& mat, const frt_light& light, uint32_t kind, uint32_t mode) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t mat_id = r->sv.num_materials, light_id = r->sv.num_lights;
+    uint32_t need[kPoolCount] = {};
+    need[kPoolMaterials] = mat_id + 1u; need[kPoolLights] = light_id + 1u;
+    if ((rc = reserve_pools(r, need))) return rc;
+    if ((rc = r->me.up.reserve(sizeof(mat) + sizeof(light), 0, r->stream))) return rc;
+    if ((rc = add_instances_impl(r, 1, &mesh_id, &mat_id, m, mode, (int32_t)light_id, kind)) < 0) return rc;
+    if ((rc = staged_copy(r, 0, &mat, const_cast<MaterialView*>(r->sv.materials) + mat_id, sizeof(mat)))) return rc;
+    if ((rc = staged_copy(r, sizeof(mat), &light, const_cast<LightView*>(r->sv.lights) + light_id, sizeof(light)))) return rc;
+    if ((rc = r->me.up.mark(r->stream))) return rc;
+    r->rf.lights.push_back(light);
+    r->sv.num_materials = mat_id + 1u; r->sv.num_lights = light_id + 1u;
+    return (int)light_id;
+}
+static int register_light(frt_renderer* r, uint32_t mesh_id, const float* m, const float* color, float intensity, uint32_t mode, uint32_t kind, const char* what) {
+    if (const int rc = check_entry(r, what, kEditChecks)) return rc;
+    if (const int rc = check_rebuild_mode(what, mode)) return rc;
+    if (!m || !color) return fail(FRT_ERR_INVALID_ARG, std::string(what) + ": null matrix or colour");
+    const uint32_t mat_id = r->sv.num_materials;
+    std::string why;
+    if (mat_id >= kMaxMaterials) return fail(FRT_ERR_LIMIT, std::string(what) + ": more than 65535 materials");
+    if (const int rc = check_add_instances(1, &mesh_id, &mat_id, m, r->rf.mesh_tris, (size_t)mat_id + 1u, r->sv.num_tris, why)) return fail(rc, std::string(what) + ": " + why);
+    Mat4 t; memcpy(t.m, m, sizeof(t.m));
+    const float em[4] = {color[0], color[1], color[2], intensity};
+    const frt_light light = kind == 0 ? quad_light_record(t, em) : sphere_light_record(t, em);
+    if (const int rc = check_add_lights(1, &light, why)) return fail(rc, std::string(what) + ": the light this transform, colour and intensity make: " + why);
+    const frt_material mat = light_emissive_material(r->sv.num_lights, color, intensity);
+    const int rc = register_light_impl(r, mesh_id, m, mat, light, kind, mode);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+int frt_renderer_register_quad_light(frt_renderer* r, uint32_t mesh_id, const float m[16], const float color[3], float intensity, uint32_t rebuild_mode) {
+    return register_light(r, mesh_id, m, color, intensity, rebuild_mode, 0u, "register_quad_light");
+}
+int frt_renderer_register_sphere_light(frt_renderer* r, uint32_t mesh_id, const float m[16], const float color[3], float intensity, uint32_t rebuild_mode) {
+    return register_light(r, mesh_id, m, color, intensity, rebuild_mode, 1u, "register_sphere_light");
+}
+int frt_renderer_pool_counts(frt_renderer* r, uint32_t counts[6]) {
+    if (!r || !counts) return fail(FRT_ERR_INVALID_ARG, "renderer pool_counts: null");
+    counts[0] = pool_count(r, kPoolMeshes); counts[1] = pool_verts(r); counts[2] = pool_indices(r);
+    counts[3] = r->rf.color_layers; counts[4] = r->rf.data_layers; counts[5] = r->me.growths;
+    return FRT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ ray queries
 // Ordering: a query is enqueued on the main stream and only reads the scene replica. Every writer of the replica is on that stream too: the instance
 // update and the deformation (their copies, kernels and refit levels; the ahead stream is fenced into the main stream before them), and the rebuild,
@@ -756,6 +1013,15 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     switch (which) {
     case 2: src = sv.materials; bytes = (size_t)sv.num_materials * sizeof(MaterialView); break;
     case 3: src = sv.lights; bytes = (size_t)sv.num_lights * sizeof(LightView); break;
+    case 4: src = sv.attributes; bytes = (size_t)pool_verts(r) * sizeof(VertexAttrView); break;
+    case 5: src = sv.indices; bytes = (size_t)pool_indices(r) * sizeof(uint32_t); break;
+    case 6: src = sv.mesh_infos; bytes = r->rf.mesh_tris.size() * sizeof(MeshInfoView); break;
+    case 18: {      // (made at the first call that needs them: frt_renderer_add_instances, _add_meshes, or this one)
+        FRT_DEVICE(r);
+        if (const int rc = sync_all(r)) return rc;
+        if (const int rc = ensure_normals(r)) return rc;
+        src = r->ie.d_normals; bytes = (size_t)pool_verts(r) * sizeof(float4);
+    } break;
     case 10: src = sv.nodes4; bytes = (size_t)sv.num_nodes4 * sizeof(QuadNode); break;
     case 13: src = sv.tris; bytes = (size_t)sv.num_tris * sizeof(TriSlot); break;
     case 15:
@@ -763,7 +1029,7 @@ int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
         src = sv.nodes; bytes = (size_t)sv.num_nodes * sizeof(PairNode); break;
     case 16: src = sv.instances; bytes = r->rf.inst.size() * sizeof(InstanceDev); break;
     case 17: src = sv.shade_tris; bytes = (size_t)sv.num_tris * sizeof(ShadeTri); break;
-    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (2, 3, 10, 13, 15, 16, 17)");
+    default: return fail(FRT_ERR_INVALID_ARG, "read_scene: unknown selector (2 - 6, 10, 13, 15 - 18)");
     }
     FRT_DEVICE(r);
     { int rc = sync_all(r); if (rc) return rc; }

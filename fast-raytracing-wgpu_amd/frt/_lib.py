@@ -25,6 +25,10 @@ class Light(C.Structure):           # src/scene/light.rs:1-16
                 ("v", C.c_float * 3), ("pad", C.c_uint32), ("emission", C.c_float * 4)]
 
 
+class MeshData(C.Structure):        # include/frt.h: frt_mesh_data
+    _fields_ = [("pos4", C.c_void_p), ("attrs", C.c_void_p), ("idx", C.c_void_p), ("nverts", C.c_uint32), ("nidx", C.c_uint32)]
+
+
 class CameraUniform(C.Structure):   # src/camera.rs:4-15
     _fields_ = [("view_proj", C.c_float * 16), ("view_inverse", C.c_float * 16), ("proj_inverse", C.c_float * 16),
                 ("view_pos", C.c_float * 4), ("prev_view_proj", C.c_float * 16),
@@ -106,6 +110,7 @@ SYMBOLS = {
     "frt_model_warning": (C.c_char_p, [_P, _U32]),
     "frt_scene_add_gltf_materials": (C.c_int, [_P, _P, _P]),
     "frt_scene_add_gltf_meshes": (C.c_int, [_P, _P, _P]),
+    "frt_model_layer_plan": (C.c_int, [_P, _U32, _U32, _P, _P, _P, _P]),
     "frt_scene_add_gltf_instances": (C.c_int, [_P, _P, _P, _U32, _P, _U32, _P]),
     "frt_scene_create_gltf_scene": (_P, [C.c_char_p, _P, _P]),
     "frt_scene_counts": (C.c_int, [_P, _P]),
@@ -159,6 +164,13 @@ SYMBOLS = {
     "frt_renderer_scene_counts": (C.c_int, [_P, _P]),
     "frt_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
     "frt_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_renderer_add_meshes": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_add_materials": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_add_texture": (C.c_int, [_P, C.c_int, _P]),
+    "frt_renderer_add_lights": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_register_quad_light": (C.c_int, [_P, _U32, _P, _P, C.c_float, _U32]),
+    "frt_renderer_register_sphere_light": (C.c_int, [_P, _U32, _P, _P, C.c_float, _U32]),
+    "frt_renderer_pool_counts": (C.c_int, [_P, _P]),
     "frt_renderer_rebuild_tree": (C.c_int, [_P]),
     "frt_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
     "frt_renderer_rebuild_stats": (C.c_int, [_P, _P]),
@@ -192,6 +204,12 @@ SYMBOLS = {
     "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
     "frt_multi_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
     "frt_multi_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_multi_renderer_add_meshes": (C.c_int, [_P, _U32, _P]),
+    "frt_multi_renderer_add_materials": (C.c_int, [_P, _U32, _P]),
+    "frt_multi_renderer_add_texture": (C.c_int, [_P, C.c_int, _P]),
+    "frt_multi_renderer_add_lights": (C.c_int, [_P, _U32, _P]),
+    "frt_multi_renderer_register_quad_light": (C.c_int, [_P, _U32, _P, _P, C.c_float, _U32]),
+    "frt_multi_renderer_register_sphere_light": (C.c_int, [_P, _U32, _P, _P, C.c_float, _U32]),
     "frt_multi_renderer_trace_closest": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_trace_any": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_pick": (C.c_int, [_P, C.POINTER(CameraUniform), _U32, _P, _P, _U32]),

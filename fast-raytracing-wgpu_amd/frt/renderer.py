@@ -3,7 +3,7 @@ import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
 from .scene import (transform_args, mesh_vertex_args, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
-                    pixel_args, HIT_FIELDS)
+                    pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan)
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -53,8 +53,50 @@ def _hit_views(hits):
     return d
 
 
-class Renderer(_HostQueries):
+class _SceneGrowth:
+    """New meshes, materials, texture layers and lights for the scene replica(s) of a running renderer (include/frt.h: frt_renderer_add_meshes and the
+    calls after it): between frames, the arguments copied during the call; accumulation, reservoirs and frame_count are kept. The
+    new ids are accepted at once by add_instances and the set_* edits; pass the new light count to build_uniform from the next frame on. The host scene
+    is not changed (its route is SceneBuilder.add_* followed by build()). Renderer and MultiRenderer name their entry points in `_grow`."""
+    _grow = None
+
+    def _grow_call(self, name, *args):
+        return check(getattr(lib(), self._grow + name)(self._h, *args))
+
+    def add_meshes(self, geometries):
+        """Append meshes (one or a sequence of objects with .positions / .attributes / .indices); returns the id of the first new mesh."""
+        n, recs, _keep = mesh_add_args(geometries)
+        return self._grow_call("add_meshes", n, C.cast(recs, C.c_void_p))
+
+    def add_materials(self, materials):
+        """Append materials (they may name layers and lights added before); returns the id of the first new material."""
+        n, m = material_add_args(materials)
+        return self._grow_call("add_materials", n, m.ctypes.data)
+
+    def add_texture(self, kind, rgba8):
+        """Append one texture layer: kind "color" (0) or "data" (1), rgba8 1024 x 1024 x 4 bytes; returns its layer id."""
+        k, t = texture_add_args(kind, rgba8)
+        return self._grow_call("add_texture", k, t.ctypes.data)
+
+    def add_lights(self, lights):
+        """Append light records as SceneBuilder.add_light takes them (no instance, no link); returns the index of the first new light."""
+        n, l = light_add_args(lights)
+        return self._grow_call("add_lights", n, l.ctypes.data)
+
+    def register_quad_light(self, mesh_id, transform_colmajor, color, intensity, quality="sah"):
+        """SceneBuilder.register_quad_light on the replica: an emissive material, an instance of `mesh_id` and a light linked to it, then the device
+        tree rebuild `quality` names (synchronous). Returns the light index."""
+        me, m, c, i = light_register_args(mesh_id, transform_colmajor, color, intensity)
+        return self._grow_call("register_quad_light", me, m.ctypes.data, c.ctypes.data, i, rebuild_mode(quality))
+
+    def register_sphere_light(self, mesh_id, transform_colmajor, color, intensity, quality="sah"):
+        me, m, c, i = light_register_args(mesh_id, transform_colmajor, color, intensity)
+        return self._grow_call("register_sphere_light", me, m.ctypes.data, c.ctypes.data, i, rebuild_mode(quality))
+
+
+class Renderer(_HostQueries, _SceneGrowth):
     _trace_closest, _trace_any, _pick = "frt_renderer_trace_closest", "frt_renderer_trace_any", "frt_renderer_pick"
+    _grow = "frt_renderer_"
 
     def __init__(self, scene, width, height, max_depth=8, device=0, stream=None, rows=None, arena=None, arena_bytes=0, flags=0, motion_halo=0,
                  queue_capacity=0, cuts=None):
@@ -298,6 +340,32 @@ class Renderer(_HostQueries):
         check(lib().frt_renderer_scene_counts(self._h, c))
         return dict(zip(("tris", "instances", "materials", "lights"), (int(v) for v in c)))
 
+    def pool_counts(self):
+        """Meshes, vertices, indices and texture layers of the replica as it is now, and the add_* / register_* calls that had to grow a capacity."""
+        c = (C.c_uint32 * 6)()
+        check(lib().frt_renderer_pool_counts(self._h, c))
+        return dict(zip(("meshes", "vertices", "indices", "color_layers", "data_layers", "growths"), (int(v) for v in c)))
+
+    def add_gltf(self, model, transform_colmajor, quality="sah"):
+        """Import a loaded model (frt.loader.load_gltf) into the running renderer, as SceneBuilder.add_gltf_materials / _meshes / _instances import it
+        into a scene: its images become texture layers, its materials (slots remapped to those layers by the library's own remapping) and its meshes
+        are appended, and one instance per primitive is added under `transform_colmajor`. Returns (mesh ids, material ids, id of the first instance)."""
+        pc = self.pool_counts()
+        mats, color_images, data_images = gltf_layer_plan(model, pc["color_layers"], pc["data_layers"])
+        for img in color_images:
+            self.add_texture(0, model.image(img))
+        for img in data_images:
+            self.add_texture(1, model.image(img))
+        n = model.counts()["geometries"]
+        geos = [model.geometry(i) for i in range(n)]
+        mat0 = self.add_materials(mats)
+        mat_ids = np.arange(mat0, mat0 + len(mats), dtype=np.uint32)
+        mesh0 = self.add_meshes([g for g, _ in geos])
+        mesh_ids = np.arange(mesh0, mesh0 + n, dtype=np.uint32)
+        use = [int(mat_ids[mi]) if mi < len(mat_ids) else 0 for _, mi in geos]      # (builder.rs:294-307: a primitive without a known material uses material 0)
+        m = np.tile(np.ascontiguousarray(transform_colmajor, np.float32).reshape(1, 16), (n, 1))
+        return mesh_ids, mat_ids, self.add_instances(mesh_ids, use, m, quality=quality)
+
     def rebuild_stats(self):
         """The last rebuild_tree that reached the device: mode asked for, clustering iterations ("sah"), why the Morton tree was built instead
         (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added."""
@@ -312,8 +380,16 @@ class Renderer(_HostQueries):
         return {"quad_nodes": int(s[0]), "quad_stack_need": int(s[1]), "quad_levels": int(s[2]), "origin": int(s[3])}
 
     def read_scene(self, what):
-        """The device replica in SceneBuilder.get's layout: "materials", "lights", "quad_nodes", "tri_slots", "pair_nodes", "instances_dev", "shade_tris" (syncs first)."""
+        """The device replica in SceneBuilder.get's layout: "materials", "lights", "attributes", "indices", "mesh_infos", "quad_nodes", "tri_slots", "pair_nodes",
+        "instances_dev", "shade_tris"; and "normals", the decoded normal of every vertex ([vertices, 4]: xyz, 0). Syncs first."""
         n = self.scene_counts()      # (the replica's own counts: after add_instances / remove_instances they differ from the host scene's)
+        if what in ("attributes", "indices", "mesh_infos", "normals"):
+            p = self.pool_counts()
+            which, shape, dt = {"attributes": (4, (p["vertices"], 8), np.float32), "indices": (5, (p["indices"],), np.uint32), "mesh_infos": (6, (p["meshes"], 4), np.uint32),
+                                "normals": (18, (p["vertices"], 4), np.float32)}[what]
+            out = np.zeros(shape, dt)
+            check(lib().frt_renderer_read_scene(self._h, which, out.ctypes.data))
+            return out
         which, shape, dt = {"materials": (2, (n["materials"], 16), np.uint32), "lights": (3, (n["lights"], 16), np.uint32), "quad_nodes": (10, (self.tree_stats()["quad_nodes"], 32), np.float32),
                             "tri_slots": (13, (n["tris"], 12), np.float32), "pair_nodes": (15, (self._scene.bvh_stats()["pair_nodes"], 16), np.float32),
                             "instances_dev": (16, (n["instances"], 16), np.uint32), "shade_tris": (17, (n["tris"], 32), np.float32)}[what]
@@ -339,10 +415,11 @@ def _stats_dict(s):
             "speculated_frames": int(s.speculated_frames), "discarded_speculations": int(s.discarded_speculations)}
 
 
-class MultiRenderer(_HostQueries):
+class MultiRenderer(_HostQueries, _SceneGrowth):
     """Renderer::new / render (renderer.rs:206, :349) for several GPUs of one node through frt_multi_renderer_*: ONE process, one call per
     frame; strips, halo copies and the gather are inside libfrt.so. `devices`: HIP ordinals, repeats allowed (several strips on one GPU)."""
     _trace_closest, _trace_any, _pick = "frt_multi_renderer_trace_closest", "frt_multi_renderer_trace_any", "frt_multi_renderer_pick"
+    _grow = "frt_multi_renderer_"
 
     def __init__(self, scene, width, height, devices, max_depth=8, motion_halo=0, flags=0, queue_capacity=0):
         o = RenderOpts()

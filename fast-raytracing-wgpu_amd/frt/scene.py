@@ -1,7 +1,7 @@
 """SceneBuilder mirror (src/scene/builder.rs) over frt_scene_*."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, Material, Light, FrtError
+from ._lib import lib, check, Material, Light, MeshData, FrtError
 
 
 def material_new(base_color):
@@ -104,6 +104,101 @@ def texture_args(kind, layer, rgba8):
     if t.size != 1024 * 1024 * 4:
         raise FrtError("a texture layer is 1024 x 1024 RGBA8")
     return int(kind), int(layer), t
+
+
+# ---- the calls that add meshes, materials, texture layers and lights to a renderer's replica (include/frt.h: frt_renderer_add_meshes ...; DESIGN.md
+# section 15). A wrong shape or dtype is a ValueError here, before the library sees anything.
+def _exact(a, dtype, what):
+    """`a` as a contiguous array of `dtype`; an array of another kind (floats for indices, integers for pixels) is refused, not converted."""
+    a = np.asarray(a)
+    want = np.dtype(dtype)
+    if a.dtype != want and not (a.dtype.kind in "iu" and want.kind in "iu") and not (a.dtype.kind == "f" and want.kind == "f"):
+        raise ValueError(f"{what} must be {want.name}, not {a.dtype.name}")
+    if a.dtype.kind in "iu" and a.size and (a.min() < 0 or a.max() > np.iinfo(want).max):
+        raise ValueError(f"{what} must fit {want.name}")
+    return np.ascontiguousarray(a, want)
+
+
+def mesh_add_args(geometries):
+    """(n, frt_mesh_data array, the arrays it points into) for the *_add_meshes calls: anything with .positions [v, 4] float, .attributes [v, 8] float
+    and .indices [3 t] integer per mesh, as SceneBuilder.add_mesh takes it; one such object or a sequence."""
+    if hasattr(geometries, "positions"):
+        geometries = [geometries]
+    geometries = list(geometries)
+    recs, keep = (MeshData * max(len(geometries), 1))(), []
+    for k, g in enumerate(geometries):
+        pos, att, idx = _exact(g.positions, np.float32, "positions"), _exact(g.attributes, np.float32, "attributes"), _exact(g.indices, np.uint32, "indices")
+        if pos.ndim != 2 or pos.shape[1] != 4:
+            raise ValueError(f"mesh {k}: positions must be shaped [n, 4]")
+        if att.size != pos.shape[0] * 8:
+            raise ValueError(f"mesh {k}: {pos.shape[0]} positions but {att.size / 8:g} attribute records of 8 floats")
+        if idx.ndim != 1:
+            raise ValueError(f"mesh {k}: indices must be a flat array")
+        keep.append((pos, att, idx))
+        recs[k] = MeshData(pos.ctypes.data, att.ctypes.data, idx.ctypes.data, pos.shape[0], idx.size)
+    return len(geometries), recs, keep
+
+
+def material_add_args(materials):
+    """(n, [n, 16] uint32 records) for the *_add_materials calls: one frt.Material (or a 64-byte row of get("materials")) or a sequence of them."""
+    if isinstance(materials, Material):
+        materials = [materials]
+    rows = []
+    for m in materials:
+        r = np.frombuffer(bytes(m), np.uint32) if isinstance(m, Material) else np.ascontiguousarray(m).view(np.uint32).reshape(-1)
+        if r.size != 16:
+            raise ValueError("a material is 64 bytes")
+        rows.append(r)
+    return len(rows), (np.ascontiguousarray(np.stack(rows), np.uint32) if rows else np.zeros((0, 16), np.uint32))
+
+
+def light_add_args(lights):
+    """(n, [n, 16] uint32 records) for the *_add_lights calls: one frt.Light (or a 64-byte row of get("lights")) or a sequence of them."""
+    if isinstance(lights, Light):
+        lights = [lights]
+    rows = []
+    for l in lights:
+        r = np.frombuffer(bytes(l), np.uint32) if isinstance(l, Light) else np.ascontiguousarray(l).view(np.uint32).reshape(-1)
+        if r.size != 16:
+            raise ValueError("a light is 64 bytes")
+        rows.append(r)
+    return len(rows), (np.ascontiguousarray(np.stack(rows), np.uint32) if rows else np.zeros((0, 16), np.uint32))
+
+
+def texture_add_args(kind, rgba8):
+    """(kind, pixels) for the *_add_texture calls: kind 0 / "color" or 1 / "data", `rgba8` 1024 x 1024 x 4 bytes of uint8."""
+    k = {"color": 0, "colour": 0, "data": 1}.get(kind, kind)
+    if k not in (0, 1):
+        raise ValueError(f'kind must be "color" (0) or "data" (1), not {kind!r}')
+    t = np.asarray(rgba8)
+    if t.dtype != np.uint8:
+        raise ValueError(f"a texture layer is uint8, not {t.dtype.name}")
+    if t.size != 1024 * 1024 * 4:
+        raise ValueError("a texture layer is 1024 x 1024 RGBA8")
+    return int(k), np.ascontiguousarray(t)
+
+
+def light_register_args(mesh_id, transform_colmajor, color, intensity):
+    """(mesh id, matrix, colour, intensity) for the *_register_quad_light / _sphere_light calls."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise ValueError("mesh id must be an unsigned 32-bit index")
+    m = np.ascontiguousarray(transform_colmajor, np.float32).reshape(-1)
+    c = np.ascontiguousarray(color, np.float32).reshape(-1)
+    if m.size != 16:
+        raise ValueError("the transform is one column-major 4x4")
+    if c.size != 3:
+        raise ValueError("color must hold three values")
+    return int(mesh_id), m, c, float(intensity)
+
+
+def gltf_layer_plan(model, color_layers, data_layers):
+    """What SceneBuilder.add_gltf_materials would add to a scene with that many texture layers (include/frt.h: frt_model_layer_plan; the library's own
+    remapping): (materials with their slots remapped to layer ids, images that become the next colour layers, images that become the next data layers)."""
+    n = model.counts()
+    mats = np.zeros((max(n["materials"], 1), 16), np.uint32)
+    ci, di, c = np.zeros(max(n["images"], 1), np.uint32), np.zeros(max(n["images"], 1), np.uint32), (C.c_uint32 * 2)()
+    check(lib().frt_model_layer_plan(model._h, color_layers, data_layers, mats.ctypes.data, ci.ctypes.data, di.ctypes.data, c))
+    return mats[:n["materials"]], [int(i) for i in ci[:c[0]]], [int(i) for i in di[:c[1]]]
 
 
 HIT_FIELDS = ("t", "u", "v", "tri", "instance", "material", "primitive", "front")      # include/frt.h: frt_ray_hit, one 32-bit word each

@@ -404,8 +404,10 @@ int frt_renderer_tree_stats(frt_renderer* r, uint32_t stats[4]);
 /* The last rebuild call that reached the device: stats[4] = mode asked for, clustering iterations run (FRT_REBUILD_SAH), why the Morton tree was
  * built instead (0 it was not, 1 iteration bound, 2 traversal stack), KiB of device memory the refined mode has added. Zeros before any rebuild. */
 int frt_renderer_rebuild_stats(frt_renderer* r, uint32_t stats[4]);
-/* Read the device replica back (syncs first), in the layout of frt_scene_get: 2 materials, 3 lights, 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle
- * slots, 15 pair nodes (FRT_ERR_STATE after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records. */
+/* Read the device replica back (syncs first), in the layout of frt_scene_get: 2 materials, 3 lights, 4 attributes, 5 indices, 6 mesh infos
+ * (frt_renderer_pool_counts gives their counts), 10 quad nodes (frt_renderer_tree_stats gives the count), 13 triangle slots, 15 pair nodes (FRT_ERR_STATE
+ * after frt_renderer_rebuild_tree), 16 device instance records, 17 shading records; and 18: the decoded normal of every vertex (16 B: xyz, 0; indexed
+ * as the attributes), which frt_renderer_add_instances builds its shading records from. */
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out);
 /* counts[4]: triangles, instances, materials, lights of the replica AS IT IS NOW (what sizes the arrays of frt_renderer_read_scene). */
 int frt_renderer_scene_counts(frt_renderer* r, uint32_t counts[4]);
@@ -421,6 +423,41 @@ int frt_renderer_scene_counts(frt_renderer* r, uint32_t counts[4]);
  * traversal-stack entries. FRT_ERR_HIP leaves the renderer failed (frt_renderer_clear). */
 int frt_renderer_add_instances(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode);
 int frt_renderer_remove_instances(frt_renderer* r, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
+/* New meshes, materials, texture layers and lights for this renderer's scene replica between frames. The specification is the host
+ * route on a built scene: frt_scene_add_mesh / _add_material / _add_texture / _add_light / _register_*_light followed by frt_scene_build. After any sequence
+ * of these calls and the edits above the replica holds what a scene built from scratch with the same builder calls holds: ids, flattened triangle ids,
+ * mesh infos and offsets, material and light records, layer numbering; frt_renderer_read_scene selectors 2 - 6, 16 and 17 equal it byte for byte, 13 as a
+ * set of records, and every frame equals that scene's bit for bit. Everything is validated before anything is applied, a refused call changes nothing,
+ * n == 0 is FRT_OK (the add calls: the current count), FRT_ERR_STATE while a frame is open, a next frame's G-buffer + T-trace that ran ahead is dropped and
+ * redone, accumulation, reservoirs and frame_count are kept. The inputs are copied during the call. The new ids are accepted at once by
+ * frt_renderer_add_instances, _set_mesh_vertices, _set_materials, _set_instance_materials, _set_light_emission and _set_texture; the caller passes the new
+ * light count in frt_camera_uniform.num_lights from the next frame on. Nothing can be removed: per-pixel history holds light indices and material ids.
+ * add_meshes / _materials / _texture / _lights add no triangle: no rebuild, asynchronous on the renderer's stream; they wait for the stream only when a
+ * capacity grows (capacities at least double, texture arrays grow by max(4, count / 2) layers, and are never shrunk). Returns: the id of the first new
+ * mesh / material, the layer id, the index of the first new light (lights as frt_scene_add_light takes them: no instance, no link).
+ * register_quad_light / _sphere_light: what frt_scene_register_quad_light / _sphere_light make: a new emissive material, a new instance of `mesh_id` and
+ * a new light record linked to it, then the device rebuild of frt_renderer_add_instances in `rebuild_mode` (synchronous). Returns the light index. The
+ * instance then behaves as any registered light's: frt_renderer_set_instance_transforms moves the light, _set_light_emission edits it, _remove_instances
+ * and _set_instance_materials refuse it.
+ * FRT_ERR_INVALID_ARG: a null pointer with n > 0; nverts == 0; nidx == 0 or not a multiple of 3; an index >= nverts; a non-finite position or attribute
+ * float; a material that fails frt_scene_build's check against the replica's layers and lights as they are; a light with a non-finite field or
+ * area <= 0; kind not 0 or 1; mesh_id out of range, a non-finite or singular matrix, an unknown rebuild_mode. FRT_ERR_LIMIT: vertex or index totals
+ * beyond 32 bits, more than 65,535 materials, a 65,535th texture layer, a failed allocation, a new tree beyond 31 traversal-stack entries. */
+typedef struct frt_mesh_data { const float* pos4; const frt_vertex_attr* attrs; const uint32_t* idx; uint32_t nverts, nidx; } frt_mesh_data;
+int frt_renderer_add_meshes(frt_renderer* r, uint32_t n, const frt_mesh_data* meshes);
+int frt_renderer_add_materials(frt_renderer* r, uint32_t n, const frt_material* materials);
+int frt_renderer_add_texture(frt_renderer* r, int kind /*0 colour (sRGB), 1 data*/, const uint8_t* rgba8_1024x1024);
+int frt_renderer_add_lights(frt_renderer* r, uint32_t n, const frt_light* lights);
+int frt_renderer_register_quad_light(frt_renderer* r, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
+int frt_renderer_register_sphere_light(frt_renderer* r, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
+/* counts[6]: meshes, vertices, indices, colour layers, data layers of the replica AS IT IS NOW (with frt_renderer_scene_counts what sizes the arrays of
+ * frt_renderer_read_scene), and the calls above that had to grow a capacity so far. */
+int frt_renderer_pool_counts(frt_renderer* r, uint32_t counts[6]);
+/* For an importer (frt/renderer.py: add_gltf): what frt_scene_add_gltf_materials would add to a scene that has `color_layers` / `data_layers` texture
+ * layers, without adding it. materials_out ([materials] of frt_model_counts): the model's materials with their image indices remapped to layer ids;
+ * color_images / data_images ([images] each): the image that becomes layer color_layers + k / data_layers + k; counts[2]: how many of each. */
+int frt_model_layer_plan(const frt_model* m, uint32_t color_layers, uint32_t data_layers, frt_material* materials_out, uint32_t* color_images, uint32_t* data_images,
+                         uint32_t counts[2]);
 
 /* Ray queries against this renderer's scene replica AS IT IS NOW on the device: after every frt_renderer_set_instance_transforms,
  * frt_renderer_set_mesh_vertices and frt_renderer_rebuild_tree so far. Results equal frt_scene_trace_closest / _any over a scene in the same state bit for bit.
@@ -497,6 +534,14 @@ int frt_multi_renderer_rebuild_tree_ex(frt_multi_renderer* m, uint32_t mode);
  * handle failed, as a failed render does. */
 int frt_multi_renderer_add_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16, uint32_t rebuild_mode);
 int frt_multi_renderer_remove_instances(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
+/* frt_renderer_add_meshes, _add_materials, _add_texture, _add_lights and _register_quad_light / _sphere_light on every strip's replica. The first strip's
+ * refusal leaves every replica as it was; a strip that fails after the first one has changed leaves the handle failed. */
+int frt_multi_renderer_add_meshes(frt_multi_renderer* m, uint32_t n, const frt_mesh_data* meshes);
+int frt_multi_renderer_add_materials(frt_multi_renderer* m, uint32_t n, const frt_material* materials);
+int frt_multi_renderer_add_texture(frt_multi_renderer* m, int kind, const uint8_t* rgba8_1024x1024);
+int frt_multi_renderer_add_lights(frt_multi_renderer* m, uint32_t n, const frt_light* lights);
+int frt_multi_renderer_register_quad_light(frt_multi_renderer* m, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
+int frt_multi_renderer_register_sphere_light(frt_multi_renderer* m, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
 /* The three ray-query calls on the first strip's replica (all replicas are equal). Host-pointer form only: flags must be 0. */
 int frt_multi_renderer_trace_closest(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags);
 int frt_multi_renderer_trace_any(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags);
