@@ -522,6 +522,20 @@ int frt_multi_renderer_register_sphere_light(frt_multi_renderer* m, uint32_t mes
     return add_to_every_replica(m, "multi register_sphere_light", [&](frt_renderer* r) { return frt_renderer_register_sphere_light(r, mesh_id, mat, color, intensity, rebuild_mode); });
 }
 
+// Removing meshes, materials, layers and lights on every strip's replica, as above.
+int frt_multi_renderer_remove_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids) {
+    return edit_every_replica(m, "multi remove_materials", [&](frt_renderer* r) { return frt_renderer_remove_materials(r, n, ids); });
+}
+int frt_multi_renderer_remove_meshes(frt_multi_renderer* m, uint32_t n, const uint32_t* ids) {
+    return edit_every_replica(m, "multi remove_meshes", [&](frt_renderer* r) { return frt_renderer_remove_meshes(r, n, ids); });
+}
+int frt_multi_renderer_remove_lights(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode) {
+    return edit_every_replica(m, "multi remove_lights", [&](frt_renderer* r) { return frt_renderer_remove_lights(r, n, ids, rebuild_mode); });
+}
+int frt_multi_renderer_remove_texture(frt_multi_renderer* m, int kind, uint32_t layer) {
+    return edit_every_replica(m, "multi remove_texture", [&](frt_renderer* r) { return frt_renderer_remove_texture(r, kind, layer); });
+}
+
 int frt_multi_renderer_set_jitter(frt_multi_renderer* m, float jx, float jy) {
     if (!m) return set_error(FRT_ERR_INVALID_ARG, "multi set_jitter: null");
     if (m->strips.size() > 1 && (jx != 0.0f || jy != 0.0f))

@@ -7,6 +7,7 @@
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
 #include "frt_mesh_edit.hpp"
+#include "frt_scene_remove.hpp"
 #include "frt_query.hpp"        // (frt_scene.hpp, frt_kernels.hpp)
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -163,6 +164,17 @@ struct MeshEditState {
     Staging up;                            // what one call uploads: the pinned block and, for add_meshes, the device block its kernel reads
 };
 
+// What frt_renderer_remove_materials / _meshes / _lights / _texture add, allocated at the first such call and freed with the scene replica.
+// A pool that closes up is compacted out of place into its `spare`, which then trades places with the replica's buffer: what left the replica is what
+// the next removal from that pool writes, behind every kernel that read it (the same stream). A spare has room for its pool's capacity. From the first
+// removal on a pool has a capacity apart from its count (MeshEditState::cap), as after a growth: counts move, capacities are never shrunk.
+enum { kSparePos = 0, kSpareAttrs, kSpareNormals, kSpareIndices, kSpareMeshInfos, kSpareMaterials, kSpareLights, kSpareCount };
+struct RemoveState {
+    void* spare[kSpareCount] = {};
+    size_t spare_bytes[kSpareCount] = {};
+    Staging tab;                           // the tables of one call: old -> new ids and removed spans
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -228,6 +240,7 @@ struct frt_renderer {
     RebuildState rbt;
     InstanceEditState ie;
     MeshEditState me;
+    RemoveState rm;
     // The host-pointer ray queries: both blocks [input | output] of a call. Such a call is synchronous — the last call's copies are done
     // when the next one starts — so this one is never marked: no event is created, recorded or waited for.
     Staging qry;

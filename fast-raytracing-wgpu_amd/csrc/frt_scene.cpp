@@ -635,6 +635,194 @@ void pack_mesh_appends(uint32_t n, const frt_mesh_data* meshes, uint32_t num_ver
 uint32_t grown_capacity(uint64_t have, uint64_t need, uint64_t limit) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 2ull * have), limit); }
 uint32_t grown_layer_capacity(uint64_t have, uint64_t need) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, have + std::max<uint64_t>(4, have / 2)), kMaxTextureLayers); }
 
+// ---------------------------------------------------------------------------------------------- removing materials, meshes, lights, layers
+std::vector<uint32_t> removal_map(size_t count, const std::vector<uint32_t>& removed) {
+    std::vector<uint32_t> map(count);
+    size_t g = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (g < removed.size() && removed[g] == i) { map[i] = kGone; ++g; }
+        else map[i] = (uint32_t)(i - g);
+    }
+    return map;
+}
+// The distinct ids of a call, ascending; false (with `why`) for a null pointer or an id out of range.
+static bool distinct_ids(uint32_t n, const uint32_t* ids, size_t count, const char* what, std::vector<uint32_t>& out, std::string& why) {
+    out.clear();
+    if (n > 0 && !ids) { why = "null ids"; return false; }
+    for (uint32_t k = 0; k < n; ++k)
+        if (ids[k] >= count) { why = std::string(what) + " id " + std::to_string(ids[k]) + " out of range (" + std::to_string(count) + ")"; return false; }
+    out.assign(ids, ids + n);
+    std::sort(out.begin(), out.end());
+    out.erase(std::unique(out.begin(), out.end()), out.end());
+    return true;
+}
+int check_remove_materials(uint32_t n, const uint32_t* ids, size_t num_materials, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why) {
+    if (!distinct_ids(n, ids, num_materials, "material", removed, why)) return FRT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < instances.size(); ++i) {
+        const InstanceRec& in = instances[i];
+        if (!std::binary_search(removed.begin(), removed.end(), in.mat_id)) continue;
+        if (in.light >= 0) why = "material " + std::to_string(in.mat_id) + " was made with light " + std::to_string(in.light) + " by register_*_light: remove the light instead";
+        else why = "instance " + std::to_string(i) + " still uses material " + std::to_string(in.mat_id);
+        removed.clear();
+        return FRT_ERR_INVALID_ARG;
+    }
+    return FRT_OK;
+}
+int check_remove_meshes(uint32_t n, const uint32_t* ids, size_t num_meshes, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why) {
+    if (!distinct_ids(n, ids, num_meshes, "mesh", removed, why)) return FRT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < instances.size(); ++i)
+        if (std::binary_search(removed.begin(), removed.end(), instances[i].mesh_id)) {
+            why = "instance " + std::to_string(i) + " still uses mesh " + std::to_string(instances[i].mesh_id);
+            removed.clear();
+            return FRT_ERR_INVALID_ARG;
+        }
+    return FRT_OK;
+}
+int check_remove_lights(uint32_t n, const uint32_t* ids, size_t num_lights, const frt_material* materials, size_t num_materials, const std::vector<InstanceRec>& instances,
+                        LightRemoval& out, std::string& why) {
+    out = LightRemoval();
+    if (!distinct_ids(n, ids, num_lights, "light", out.lights, why)) return FRT_ERR_INVALID_ARG;
+    if (out.lights.empty()) return FRT_OK;
+    if (!materials && num_materials > 0) { out = LightRemoval(); why = "null materials"; return FRT_ERR_INVALID_ARG; }
+    auto refuse = [&](const std::string& w) { why = w; out = LightRemoval(); return (int)FRT_ERR_INVALID_ARG; };
+    for (size_t i = 0; i < instances.size(); ++i) {      // the composites register_*_light made: the instance and its material leave with the light
+        const InstanceRec& in = instances[i];
+        if (in.light < 0 || !std::binary_search(out.lights.begin(), out.lights.end(), (uint32_t)in.light)) continue;
+        out.instances.push_back((uint32_t)i);
+        if (in.mat_id < num_materials) out.materials.push_back(in.mat_id);
+    }
+    std::sort(out.materials.begin(), out.materials.end());
+    out.materials.erase(std::unique(out.materials.begin(), out.materials.end()), out.materials.end());
+    if (!out.instances.empty() && out.instances.size() == instances.size()) return refuse("every instance would be removed (a scene without triangles cannot be built)");
+    for (size_t i = 0; i < instances.size(); ++i) {
+        if (std::binary_search(out.instances.begin(), out.instances.end(), (uint32_t)i)) continue;
+        if (std::binary_search(out.materials.begin(), out.materials.end(), instances[i].mat_id))
+            return refuse("instance " + std::to_string(i) + " still uses material " + std::to_string(instances[i].mat_id) + ", which a removed light was registered with");
+    }
+    for (size_t m = 0; m < num_materials; ++m) {
+        if (std::binary_search(out.materials.begin(), out.materials.end(), (uint32_t)m)) continue;
+        const int32_t li = materials[m].light_index;
+        if (li >= 0 && std::binary_search(out.lights.begin(), out.lights.end(), (uint32_t)li))
+            return refuse("light_index of material " + std::to_string(m) + " still names light " + std::to_string(li));
+    }
+    return FRT_OK;
+}
+int check_remove_texture(int kind, uint32_t layer, size_t color_layers, size_t data_layers, const frt_material* materials, size_t num_materials, std::string& why) {
+    if (kind != 0 && kind != 1) { why = "kind must be 0 (colour) or 1 (data)"; return FRT_ERR_INVALID_ARG; }
+    const size_t layers = kind == 0 ? color_layers : data_layers;
+    const std::string name = std::string(kind == 0 ? "colour" : "data") + " layer " + std::to_string(layer);
+    if (layer >= layers) { why = name + " does not exist (" + std::to_string(layers) + " layers)"; return FRT_ERR_INVALID_ARG; }
+    if (layer < kBuilderLayers) { why = name + " is one of the layers every scene starts with"; return FRT_ERR_INVALID_ARG; }
+    if (!materials && num_materials > 0) { why = "null materials"; return FRT_ERR_INVALID_ARG; }
+    for (size_t m = 0; m < num_materials; ++m) {
+        const frt_material& a = materials[m];
+        const uint32_t color[2] = {a.tex_info_0 & 0xFFFFu, a.tex_info_1 >> 16}, data[3] = {a.tex_info_0 >> 16, a.tex_info_1 & 0xFFFFu, a.tex_info_2 & 0xFFFFu};
+        bool used = false;
+        if (kind == 0) for (uint32_t s : color) used |= s == layer;
+        else for (uint32_t s : data) used |= s == layer;
+        if (used) { why = "material " + std::to_string(m) + " still names " + name; return FRT_ERR_INVALID_ARG; }
+    }
+    return FRT_OK;
+}
+static uint32_t slot_without(uint32_t slot, uint32_t layer) { return slot != 0xFFFFu && layer != kGone && slot > layer ? slot - 1u : slot; }
+void remap_material(frt_material& m, const std::vector<uint32_t>& light_map, uint32_t color_layer, uint32_t data_layer) {
+    if (m.light_index >= 0 && (size_t)m.light_index < light_map.size() && light_map[(size_t)m.light_index] != kGone) m.light_index = (int32_t)light_map[(size_t)m.light_index];
+    m.tex_info_0 = slot_without(m.tex_info_0 & 0xFFFFu, color_layer) | (slot_without(m.tex_info_0 >> 16, data_layer) << 16);
+    m.tex_info_1 = slot_without(m.tex_info_1 & 0xFFFFu, data_layer) | (slot_without(m.tex_info_1 >> 16, color_layer) << 16);
+    m.tex_info_2 = slot_without(m.tex_info_2 & 0xFFFFu, data_layer) | (m.tex_info_2 & 0xFFFF0000u);
+}
+void pack_mesh_removal(const std::vector<uint32_t>& removed, const std::vector<uint32_t>& vert_offset, const std::vector<uint32_t>& vert_count,
+                       const std::vector<uint32_t>& index_offset, const std::vector<uint32_t>& index_count,
+                       std::vector<RemovedSpan>& meshes, std::vector<RemovedSpan>& verts, std::vector<RemovedSpan>& indices) {
+    meshes.clear(); verts.clear(); indices.clear();
+    uint32_t vgone = 0, igone = 0;
+    for (size_t k = 0; k < removed.size(); ++k) {
+        const uint32_t m = removed[k];
+        meshes.push_back(RemovedSpan{m - (uint32_t)k, (uint32_t)k + 1u});
+        verts.push_back(RemovedSpan{vert_offset[m] - vgone, vgone + vert_count[m]});
+        indices.push_back(RemovedSpan{index_offset[m] - igone, igone + index_count[m]});
+        vgone += vert_count[m]; igone += index_count[m];
+    }
+}
+
+// The four host forms share their end: build() over the edited lists; a tree the builder refuses puts the lists back as `undo` holds them.
+namespace {
+struct Lists {
+    std::vector<frt_material> materials; std::vector<frt_vertex_attr> attributes; std::vector<uint32_t> indices; std::vector<MeshInfo> mesh_infos; std::vector<frt_light> lights;
+    std::vector<std::vector<float>> mesh_positions; std::vector<uint32_t> mesh_index_counts; std::vector<InstanceRec> instances;
+};
+Lists lists_of(const SceneBuilder& b) { return Lists{b.materials, b.attributes, b.indices, b.mesh_infos, b.lights, b.mesh_positions, b.mesh_index_counts, b.instances}; }
+int rebuild_or_undo(SceneBuilder& b, Lists& undo, const char* what) {
+    b.build();
+    if (b.built) return FRT_OK;
+    const std::string why_not = b.error;
+    b.materials.swap(undo.materials); b.attributes.swap(undo.attributes); b.indices.swap(undo.indices); b.mesh_infos.swap(undo.mesh_infos); b.lights.swap(undo.lights);
+    b.mesh_positions.swap(undo.mesh_positions); b.mesh_index_counts.swap(undo.mesh_index_counts); b.instances.swap(undo.instances);
+    b.build();
+    b.error = std::string(what) + ": " + why_not + " (nothing changed)";
+    return FRT_ERR_LIMIT;
+}
+}
+
+int SceneBuilder::remove_materials(uint32_t n, const uint32_t* ids) {
+    if (!built) { error = "remove_materials: scene is not built"; return FRT_ERR_STATE; }
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_materials(n, ids, materials.size(), instances, gone, why)) { error = "remove_materials: " + why; return rc; }
+    if (gone.empty()) return FRT_OK;
+    Lists undo = lists_of(*this);
+    const std::vector<uint32_t> map = removal_map(materials.size(), gone);
+    remove_elements(materials, gone);
+    for (InstanceRec& in : instances) if (in.mat_id < map.size()) in.mat_id = map[in.mat_id];
+    return rebuild_or_undo(*this, undo, "remove_materials");
+}
+int SceneBuilder::remove_meshes(uint32_t n, const uint32_t* ids) {
+    if (!built) { error = "remove_meshes: scene is not built"; return FRT_ERR_STATE; }
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_meshes(n, ids, mesh_infos.size(), instances, gone, why)) { error = "remove_meshes: " + why; return rc; }
+    if (gone.empty()) return FRT_OK;
+    Lists undo = lists_of(*this);
+    const std::vector<uint32_t> map = removal_map(mesh_infos.size(), gone);
+    std::vector<frt_vertex_attr> attrs; std::vector<uint32_t> idx; std::vector<MeshInfo> infos;
+    for (size_t m = 0; m < mesh_infos.size(); ++m) {      // the pools as add_mesh lays the surviving meshes out
+        if (map[m] == kGone) continue;
+        const size_t nv = mesh_positions[m].size() / 4, ni = mesh_index_counts[m];
+        infos.push_back(MeshInfo{(uint32_t)attrs.size(), (uint32_t)idx.size(), {0, 0}});
+        attrs.insert(attrs.end(), attributes.begin() + mesh_infos[m].vertex_offset, attributes.begin() + mesh_infos[m].vertex_offset + nv);
+        idx.insert(idx.end(), indices.begin() + mesh_infos[m].index_offset, indices.begin() + mesh_infos[m].index_offset + ni);
+    }
+    attributes.swap(attrs); indices.swap(idx); mesh_infos.swap(infos);
+    remove_elements(mesh_positions, gone); remove_elements(mesh_index_counts, gone);
+    for (InstanceRec& in : instances) in.mesh_id = map[in.mesh_id];
+    return rebuild_or_undo(*this, undo, "remove_meshes");
+}
+int SceneBuilder::remove_lights(uint32_t n, const uint32_t* ids) {
+    if (!built) { error = "remove_lights: scene is not built"; return FRT_ERR_STATE; }
+    LightRemoval rem;
+    std::string why;
+    if (const int rc = check_remove_lights(n, ids, lights.size(), materials.data(), materials.size(), instances, rem, why)) { error = "remove_lights: " + why; return rc; }
+    if (rem.lights.empty()) return FRT_OK;
+    Lists undo = lists_of(*this);
+    const std::vector<uint32_t> light_map = removal_map(lights.size(), rem.lights), mat_map = removal_map(materials.size(), rem.materials);
+    remove_elements(instances, rem.instances); remove_elements(materials, rem.materials); remove_elements(lights, rem.lights);
+    for (InstanceRec& in : instances) {
+        if (in.mat_id < mat_map.size()) in.mat_id = mat_map[in.mat_id];
+        if (in.light >= 0 && (size_t)in.light < light_map.size()) in.light = (int32_t)light_map[(size_t)in.light];
+    }
+    for (frt_material& m : materials) remap_material(m, light_map, kGone, kGone);
+    return rebuild_or_undo(*this, undo, "remove_lights");
+}
+int SceneBuilder::remove_texture(int kind, uint32_t layer) {
+    if (!built) { error = "remove_texture: scene is not built"; return FRT_ERR_STATE; }
+    std::string why;
+    if (const int rc = check_remove_texture(kind, layer, color_textures.size(), data_textures.size(), materials.data(), materials.size(), why)) { error = "remove_texture: " + why; return rc; }
+    auto& layers = kind == 0 ? color_textures : data_textures;
+    layers.erase(layers.begin() + layer);
+    for (frt_material& m : materials) remap_material(m, {}, kind == 0 ? layer : kGone, kind == 1 ? layer : kGone);      // (nothing build() derives names a layer)
+    return FRT_OK;
+}
+
 void SceneBuilder::build() {
     error.clear();
     // Texture layers and light indices reach the kernels unchecked (sample_layer: base + layer * 4 MiB): validate them here, once.

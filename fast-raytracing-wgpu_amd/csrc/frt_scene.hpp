@@ -119,6 +119,18 @@ public:
     // The instances `ids` leave (an id given twice leaves once); ids and flattened triangle ids above them shift down, as in a from-scratch build. An
     // instance that register_*_light created is refused, and so is removing every instance.
     int remove_instances(uint32_t n, const uint32_t* ids);
+    // What a built scene no longer holds. Each validates everything before it applies anything, edits the builder's lists and runs build()
+    // again: the scene then equals, selector for selector, one built from scratch with the surviving builder calls. Ids stay dense: everything above a
+    // removed id shifts down, an id given twice leaves once. The specifications the device forms match.
+    // Materials no instance uses (a material register_*_light made leaves with its light); the material word of every instance follows.
+    int remove_materials(uint32_t n, const uint32_t* ids);
+    // Meshes no instance uses: the vertex, index and mesh-info lists close up, the mesh word of every instance follows.
+    int remove_meshes(uint32_t n, const uint32_t* ids);
+    // Lights: a light of add_light loses its record; a light of register_*_light leaves as the composite that call made (record, instance, emissive
+    // material). light_index of every material and the light link of every instance follow.
+    int remove_lights(uint32_t n, const uint32_t* ids);
+    // One texture layer (kind 0 colour, 1 data) no material slot of that kind names; the slots above it follow.
+    int remove_texture(int kind, uint32_t layer);
 
     // SceneResources-equivalent host data (src/scene/resources.rs:10-22)
     std::vector<frt_material> materials;
@@ -216,6 +228,45 @@ uint32_t grown_layer_capacity(uint64_t have, uint64_t need);
 // The instance a light was registered with, or -1 (a light of add_light / add_*_light).
 int light_instance(const std::vector<InstanceRec>& instances, uint32_t light);
 static const size_t kTextureLayerBytes = 1024u * 1024u * 4u;   // src/scene/mod.rs:12-13
+// Removing materials, meshes, lights and texture layers: the argument checks and the renumbering shared by the scene forms, the renderer
+// forms and a stand-alone host program. Nothing here knows a device. The checks return FRT_OK or the code with `why` set; `removed` receives the distinct
+// ids, ascending.
+static const uint32_t kGone = 0xFFFFFFFFu;             // in an old -> new table: the id left
+static const uint32_t kBuilderLayers = 3u;             // the layers of each kind SceneBuilder() makes itself: never removed
+static const float kGoneMaterialWord = 65535.0f;       // gpos.w of a pixel whose material left: no valid id (kMaxMaterials ids: 0 .. 65,534)
+// old -> new ids of `count` dense ids after the ascending, distinct ids `removed` left.
+std::vector<uint32_t> removal_map(size_t count, const std::vector<uint32_t>& removed);
+// `list` without the elements `removed` names (ascending, distinct), the survivors in their order.
+template <class T>
+void remove_elements(std::vector<T>& list, const std::vector<uint32_t>& removed) {
+    size_t g = 0, w = 0;
+    for (size_t i = 0; i < list.size(); ++i) {
+        if (g < removed.size() && removed[g] == i) { ++g; continue; }
+        if (w != i) list[w] = std::move(list[i]);
+        ++w;
+    }
+    list.resize(w);
+}
+int check_remove_materials(uint32_t n, const uint32_t* ids, size_t num_materials, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why);
+int check_remove_meshes(uint32_t n, const uint32_t* ids, size_t num_meshes, const std::vector<InstanceRec>& instances, std::vector<uint32_t>& removed, std::string& why);
+// What a call of remove_lights takes out: the lights, the instances registered with them and those instances' materials (each ascending, distinct).
+struct LightRemoval { std::vector<uint32_t> lights, instances, materials; };
+// `materials`: the scene's or the replica's material records as they are (their light_index is what the check reads).
+int check_remove_lights(uint32_t n, const uint32_t* ids, size_t num_lights, const frt_material* materials, size_t num_materials, const std::vector<InstanceRec>& instances,
+                        LightRemoval& out, std::string& why);
+int check_remove_texture(int kind, uint32_t layer, size_t color_layers, size_t data_layers, const frt_material* materials, size_t num_materials, std::string& why);
+// One material record under new light indices (`light_map`: old -> new, or empty) and without layer `color_layer` / `data_layer` (kGone: none left):
+// light_index >= 0 and the five 16-bit slots follow, 0xFFFF and negative indices stay. What remap_material_words_kernel does word by word.
+void remap_material(frt_material& m, const std::vector<uint32_t>& light_map, uint32_t color_layer, uint32_t data_layer);
+// One removed mesh in one of the three pools it occupies (meshes, vertices, indices), 8 B; a table is sorted by mesh id. `new_begin`: elements that survive
+// in front of the range; `through`: elements removed up to and including it. The element at new index g was at g + through of the last span with
+// new_begin <= g (frt_scene_remove.hpp: removed_in_front).
+struct RemovedSpan { uint32_t new_begin, through; };
+// The three tables of a call that passed check_remove_meshes, one span per removed mesh each, for pools laid out by (vert_offset, vert_count,
+// index_offset, index_count) per mesh.
+void pack_mesh_removal(const std::vector<uint32_t>& removed, const std::vector<uint32_t>& vert_offset, const std::vector<uint32_t>& vert_count,
+                       const std::vector<uint32_t>& index_offset, const std::vector<uint32_t>& index_count,
+                       std::vector<RemovedSpan>& meshes, std::vector<RemovedSpan>& verts, std::vector<RemovedSpan>& indices);
 // The decoded normal a shading record holds for a vertex with these attributes (frt_shade.hpp: decode_octahedral_normal, compiled for the host).
 void decoded_vertex_normal(const frt_vertex_attr& a, float out[3]);
 

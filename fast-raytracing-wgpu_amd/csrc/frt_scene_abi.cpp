@@ -130,6 +130,26 @@ int frt_scene_remove_instances(frt_scene* s, uint32_t n, const uint32_t* ids) {
     const int rc = s->b.remove_instances(n, ids);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_remove_materials(frt_scene* s, uint32_t n, const uint32_t* ids) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "remove_materials: null");
+    const int rc = s->b.remove_materials(n, ids);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_remove_meshes(frt_scene* s, uint32_t n, const uint32_t* ids) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "remove_meshes: null");
+    const int rc = s->b.remove_meshes(n, ids);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_remove_lights(frt_scene* s, uint32_t n, const uint32_t* ids) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "remove_lights: null");
+    const int rc = s->b.remove_lights(n, ids);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_remove_texture(frt_scene* s, int kind, uint32_t layer) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "remove_texture: null");
+    const int rc = s->b.remove_texture(kind, layer);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 frt_scene* frt_scene_create_cornell_box(void) {
     frt_scene* s = new frt_scene();
     scenes::create_cornell_box(s->b);

@@ -1,8 +1,8 @@
 // frt_scene_edit.hip — what edits or reads a renderer's scene replica between frames (include/frt.h): moving instances,
 // deforming meshes, the material, light and texture edits (§13), the tree rebuild, adding and removing instances (§14), new meshes, materials, texture
-// layers and lights (§15), the ray queries,
+// layers and lights (§15), removing meshes, materials, layers and lights (§16), the ray queries,
 // frt_renderer_read_scene and the tree statistics.
-// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
+// Host code only: the kernels are in frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip, frt_ploc.hip and frt_query.hip.
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -532,8 +532,8 @@ static int ensure_normals(frt_renderer* r) {
     if (nverts) HIP_TRY(hipMemcpy(attrs.data(), r->sv.attributes, nverts * sizeof(frt_vertex_attr), hipMemcpyDeviceToHost));
     std::vector<float> nrm(4 * nverts, 0.0f);
     for (size_t v = 0; v < nverts; ++v) decoded_vertex_normal(attrs[v], &nrm[4 * v]);
-    void* d = nullptr;
-    if (const int rc = scene_alloc(r, nrm.size() * sizeof(float), &d)) return rc;
+    void* d = nullptr;      // (with room for the vertex pool's capacity, which a growth or a removal has set apart from its count)
+    if (const int rc = scene_alloc(r, std::max<size_t>(nverts, r->me.cap[kPoolVerts]) * sizeof(float4), &d)) return rc;
     if (nverts) HIP_TRY(hipMemcpy(d, nrm.data(), nrm.size() * sizeof(float), hipMemcpyHostToDevice));
     r->ie.d_normals = static_cast<const float4*>(d);
     return FRT_OK;
@@ -933,6 +933,246 @@ int frt_renderer_pool_counts(frt_renderer* r, uint32_t counts[6]) {
     counts[0] = pool_count(r, kPoolMeshes); counts[1] = pool_verts(r); counts[2] = pool_indices(r);
     counts[3] = r->rf.color_layers; counts[4] = r->rf.data_layers; counts[5] = r->me.growths;
     return FRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ removing meshes, materials, layers, lights
+// Ordering: as the edits of §13 (order_behind_frames, the speculation dropped: it has read the ids that change). The tables of a call (old -> new ids,
+// removed spans) are staged through r->rm.tab. A pool that closes up is compacted by a kernel into its spare buffer (RemoveState), which enters the
+// replica on the host once every launch of the call is enqueued; the buffer that left is the next removal's spare, and the next kernel that writes it
+// is behind this call's readers on the same stream. Surviving records are renumbered in place, one word per thread, and so is gpos.w of every G-buffer
+// set the renderer owns. Nothing waits for the device unless a spare has to be (re)allocated, except the two checks that read the material table back.
+static uint32_t pool_cap(const frt_renderer* r, int p) { return r->me.cap[p] ? r->me.cap[p] : pool_count(r, p); }
+static void pin_capacity(frt_renderer* r, int p) { if (!r->me.cap[p]) r->me.cap[p] = pool_count(r, p); }      // before the count moves: the buffer keeps its room
+static int spare_for(frt_renderer* r, int slot, size_t bytes, void** out) {
+    RemoveState& s = r->rm;
+    if (!s.spare[slot] || s.spare_bytes[slot] < bytes) {
+        HIP_TRY(hipStreamSynchronize(r->stream));      // (a kernel of an earlier call may still read what is freed)
+        scene_free(r, s.spare[slot]);
+        s.spare[slot] = nullptr; s.spare_bytes[slot] = 0;
+        if (const int rc = scene_alloc(r, bytes, &s.spare[slot])) return rc;
+        s.spare_bytes[slot] = std::max<size_t>(bytes, 16);
+    }
+    *out = s.spare[slot];
+    return FRT_OK;
+}
+// The replica's buffer `live` and the spare of `slot` trade places (`live_bytes`: what the buffer that leaves has room for).
+static void swap_spare(frt_renderer* r, int slot, const void* live_ptr, size_t live_bytes) {
+    const void** live = static_cast<const void**>(const_cast<void*>(live_ptr));
+    RemoveState& s = r->rm;
+    void* was = const_cast<void*>(*live);
+    *live = s.spare[slot];
+    s.spare[slot] = was; s.spare_bytes[slot] = std::max<size_t>(live_bytes, 16);
+}
+static int stage_words(frt_renderer* r, const std::vector<uint32_t>& w, const uint32_t** d) {
+    const size_t bytes = std::max<size_t>(w.size() * 4, 16);
+    Staging& t = r->rm.tab;
+    if (const int rc = t.reserve(bytes, bytes, r->stream)) return rc;
+    memcpy(t.h, w.data(), w.size() * 4);
+    HIP_TRY(hipMemcpyAsync(t.d, t.h, bytes, hipMemcpyHostToDevice, r->stream));
+    if (const int rc = t.mark(r->stream)) return rc;
+    *d = reinterpret_cast<const uint32_t*>(t.d);
+    return FRT_OK;
+}
+// [map of `count` ids | one span per removed id] for a pool of single records.
+static std::vector<uint32_t> id_tables(size_t count, const std::vector<uint32_t>& gone, std::vector<uint32_t>& map) {
+    map = removal_map(count, gone);
+    std::vector<uint32_t> w = map;
+    for (size_t k = 0; k < gone.size(); ++k) { w.push_back(gone[k] - (uint32_t)k); w.push_back((uint32_t)k + 1u); }
+    return w;
+}
+// gpos.w of every G-buffer set this renderer owns, over all its rows.
+static int remap_history(frt_renderer* r, const uint32_t* d_map, uint32_t n) {
+    for (uint32_t g = 0; g < r->gsets && g < (uint32_t)kGSets; ++g) {
+        const int b = B_GPOS0 + (int)g;
+        if (is_extra(b) && !r->extras) continue;
+        HIP_TRY(launch_remap_history(static_cast<float4*>(r->buf(b)), r->W * r->H, d_map, n, r->stream));
+    }
+    return FRT_OK;
+}
+// The material table as it is on the device (the checks of remove_lights and remove_texture read light_index and the texture slots): waits for the device.
+static int read_materials(frt_renderer* r, std::vector<frt_material>& out) {
+    FRT_DEVICE(r);
+    if (const int rc = sync_all(r)) return rc;
+    out.resize(r->sv.num_materials);
+    if (!out.empty()) HIP_TRY(hipMemcpy(out.data(), r->sv.materials, out.size() * sizeof(frt_material), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+
+// The materials `gone` (checked, not empty) leave the table; instance records, shading records and the per-pixel history follow. The caller has ordered the stream.
+static int remove_materials_device(frt_renderer* r, const std::vector<uint32_t>& gone) {
+    SceneView& sv = r->sv;
+    const uint32_t old = sv.num_materials, left = old - (uint32_t)gone.size();
+    std::vector<uint32_t> map;
+    const std::vector<uint32_t> words = id_tables(old, gone, map);
+    pin_capacity(r, kPoolMaterials);
+    const size_t cap_bytes = (size_t)pool_cap(r, kPoolMaterials) * sizeof(MaterialView);
+    void* dst = nullptr;
+    int rc;
+    if ((rc = spare_for(r, kSpareMaterials, cap_bytes, &dst))) return rc;
+    const uint32_t* d = nullptr;
+    if ((rc = stage_words(r, words, &d))) return rc;
+    const RemovedSpan* spans = reinterpret_cast<const RemovedSpan*>(d + old);
+    HIP_TRY(launch_compact_vec4(reinterpret_cast<const float4*>(sv.materials), static_cast<float4*>(dst), left, 4u, spans, (uint32_t)gone.size(), r->stream));
+    HIP_TRY(launch_remap_words(reinterpret_cast<uint32_t*>(const_cast<float4*>(sv.shade_tris)), sv.num_tris, 32u, 25u, d, old, r->stream));
+    HIP_TRY(launch_remap_words(reinterpret_cast<uint32_t*>(const_cast<InstanceView*>(sv.instances)), (uint32_t)r->rf.inst.size(), 16u, 1u, d, old, r->stream));
+    if ((rc = remap_history(r, d, old))) return rc;
+    swap_spare(r, kSpareMaterials, &sv.materials, cap_bytes);
+    for (InstanceRec& in : r->rf.inst) if (in.mat_id < old && map[in.mat_id] != kGone) in.mat_id = map[in.mat_id];
+    sv.num_materials = left;
+    return FRT_OK;
+}
+// The light records `gone` (checked, not empty) leave the table; light_index of every material and the light link of every instance follow.
+static int remove_light_records_device(frt_renderer* r, const std::vector<uint32_t>& gone) {
+    SceneView& sv = r->sv;
+    const uint32_t old = sv.num_lights, left = old - (uint32_t)gone.size();
+    std::vector<uint32_t> map;
+    const std::vector<uint32_t> words = id_tables(old, gone, map);
+    pin_capacity(r, kPoolLights);
+    const size_t cap_bytes = (size_t)pool_cap(r, kPoolLights) * sizeof(LightView);
+    void* dst = nullptr;
+    int rc;
+    if ((rc = spare_for(r, kSpareLights, cap_bytes, &dst))) return rc;
+    const uint32_t* d = nullptr;
+    if ((rc = stage_words(r, words, &d))) return rc;
+    const RemovedSpan* spans = reinterpret_cast<const RemovedSpan*>(d + old);
+    HIP_TRY(launch_compact_vec4(reinterpret_cast<const float4*>(sv.lights), static_cast<float4*>(dst), left, 4u, spans, (uint32_t)gone.size(), r->stream));
+    HIP_TRY(launch_remap_materials(const_cast<MaterialView*>(sv.materials), sv.num_materials, d, old, kGone, kGone, r->stream));
+    swap_spare(r, kSpareLights, &sv.lights, cap_bytes);
+    remove_elements(r->rf.lights, gone);
+    for (InstanceRec& in : r->rf.inst) if (in.light >= 0 && (uint32_t)in.light < old && map[(size_t)in.light] != kGone) in.light = (int32_t)map[(size_t)in.light];
+    sv.num_lights = left;
+    return FRT_OK;
+}
+
+static int remove_materials_impl(frt_renderer* r, const std::vector<uint32_t>& gone) {
+    FRT_DEVICE(r);
+    if (const int rc = order_behind_frames(r, true)) return rc;
+    return remove_materials_device(r, gone);
+}
+int frt_renderer_remove_materials(frt_renderer* r, uint32_t n, const uint32_t* ids) {
+    if (const int rc = check_entry(r, "remove_materials", kLookChecks)) return rc;
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_materials(n, ids, r->sv.num_materials, r->rf.inst, gone, why)) return fail(rc, "remove_materials: " + why);
+    if (gone.empty()) return FRT_OK;
+    const int rc = remove_materials_impl(r, gone);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+static int remove_meshes_impl(frt_renderer* r, const std::vector<uint32_t>& gone) {
+    RefitState& f = r->rf;
+    SceneView& sv = r->sv;
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    const uint32_t old_meshes = (uint32_t)f.mesh_tris.size(), old_verts = pool_verts(r), old_indices = pool_indices(r);
+    std::vector<uint32_t> index_count(old_meshes);
+    for (uint32_t m = 0; m < old_meshes; ++m) index_count[m] = 3u * f.mesh_tris[m];
+    std::vector<RemovedSpan> sm, sve, si;
+    pack_mesh_removal(gone, f.attr_offset, f.vert_count, f.index_offset, index_count, sm, sve, si);
+    const uint32_t ns = (uint32_t)gone.size(), verts = old_verts - sve.back().through, indices = old_indices - si.back().through, meshes = old_meshes - ns;
+    const std::vector<uint32_t> map = removal_map(old_meshes, gone);
+    std::vector<uint32_t> words(6u * ns);      // [mesh spans | vertex spans | index spans | old -> new mesh ids]
+    memcpy(words.data(), sm.data(), 8u * ns); memcpy(words.data() + 2u * ns, sve.data(), 8u * ns); memcpy(words.data() + 4u * ns, si.data(), 8u * ns);
+    words.insert(words.end(), map.begin(), map.end());
+    pin_capacity(r, kPoolVerts); pin_capacity(r, kPoolIndices); pin_capacity(r, kPoolMeshes);
+    const size_t cv = pool_cap(r, kPoolVerts), ci = pool_cap(r, kPoolIndices), cm = pool_cap(r, kPoolMeshes);
+    void *pos = nullptr, *attrs = nullptr, *nrm = nullptr, *idx = nullptr, *infos = nullptr;
+    if ((rc = spare_for(r, kSparePos, cv * sizeof(float4), &pos))) return rc;
+    if ((rc = spare_for(r, kSpareAttrs, cv * sizeof(VertexAttrView), &attrs))) return rc;
+    if (r->ie.d_normals && (rc = spare_for(r, kSpareNormals, cv * sizeof(float4), &nrm))) return rc;
+    if ((rc = spare_for(r, kSpareIndices, ci * sizeof(uint32_t), &idx))) return rc;
+    if ((rc = spare_for(r, kSpareMeshInfos, cm * sizeof(MeshInfoView), &infos))) return rc;
+    const uint32_t* d = nullptr;
+    if ((rc = stage_words(r, words, &d))) return rc;
+    const RemovedSpan *dm = reinterpret_cast<const RemovedSpan*>(d), *dv = dm + ns, *di = dv + ns;
+    HIP_TRY(launch_compact_vec4(f.d_pos, static_cast<float4*>(pos), verts, 1u, dv, ns, r->stream));
+    HIP_TRY(launch_compact_vec4(reinterpret_cast<const float4*>(sv.attributes), static_cast<float4*>(attrs), verts, 2u, dv, ns, r->stream));
+    if (nrm) HIP_TRY(launch_compact_vec4(r->ie.d_normals, static_cast<float4*>(nrm), verts, 1u, dv, ns, r->stream));
+    HIP_TRY(launch_compact_u32(sv.indices, static_cast<uint32_t*>(idx), indices, di, ns, r->stream));
+    HIP_TRY(launch_compact_mesh_infos(sv.mesh_infos, static_cast<MeshInfoView*>(infos), meshes, dm, dv, di, ns, r->stream));
+    HIP_TRY(launch_remap_words(reinterpret_cast<uint32_t*>(const_cast<InstanceView*>(sv.instances)), (uint32_t)f.inst.size(), 16u, 0u, d + 6u * ns, old_meshes, r->stream));
+    // everything is enqueued: the new pools enter the replica together, with the host bookkeeping
+    swap_spare(r, kSparePos, &f.d_pos, cv * sizeof(float4));
+    swap_spare(r, kSpareAttrs, &sv.attributes, cv * sizeof(VertexAttrView));
+    if (nrm) swap_spare(r, kSpareNormals, &r->ie.d_normals, cv * sizeof(float4));
+    swap_spare(r, kSpareIndices, &sv.indices, ci * sizeof(uint32_t));
+    swap_spare(r, kSpareMeshInfos, &sv.mesh_infos, cm * sizeof(MeshInfoView));
+    std::vector<uint32_t> vo, io, vc, mt;
+    uint32_t v = 0, i = 0;
+    for (uint32_t m = 0; m < old_meshes; ++m) {      // the offsets a scratch build gives the survivors
+        if (map[m] == kGone) continue;
+        vo.push_back(v); io.push_back(i); vc.push_back(f.vert_count[m]); mt.push_back(f.mesh_tris[m]);
+        v += f.vert_count[m]; i += index_count[m];
+    }
+    f.pos_offset = vo; f.attr_offset.swap(vo); f.index_offset.swap(io); f.vert_count.swap(vc); f.mesh_tris.swap(mt);
+    for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];
+    return FRT_OK;
+}
+int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids) {
+    if (const int rc = check_entry(r, "remove_meshes", kLookChecks)) return rc;
+    const RefitState& f = r->rf;
+    if (f.pos_offset != f.attr_offset) return fail(FRT_ERR_STATE, "remove_meshes: the replica's positions and attributes are not numbered alike");
+    std::vector<uint32_t> gone;
+    std::string why;
+    if (const int rc = check_remove_meshes(n, ids, f.mesh_tris.size(), f.inst, gone, why)) return fail(rc, "remove_meshes: " + why);
+    if (gone.empty()) return FRT_OK;
+    if (2ull * pool_verts(r) > 0xFFFFFF00ull || pool_indices(r) > 0xFFFFFF00u) return fail(FRT_ERR_LIMIT, "remove_meshes: too many vertices or indices for one compaction launch");
+    const int rc = remove_meshes_impl(r, gone);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// A registered light leaves as the composite register_*_light made: its instance first (remove_instances_impl: the one step that can be refused, by the
+// tree; nothing has changed then), then its material, then the record.
+static int remove_lights_impl(frt_renderer* r, const LightRemoval& rem, uint32_t mode) {
+    FRT_DEVICE(r);
+    int rc = order_behind_frames(r, true);
+    if (rc) return rc;
+    if (!rem.instances.empty() && (rc = remove_instances_impl(r, rem.instances, mode))) return rc;
+    if (!rem.materials.empty() && (rc = remove_materials_device(r, rem.materials))) return rc;      // (from here on only a HIP call can fail: the renderer is then failed)
+    return remove_light_records_device(r, rem.lights);
+}
+int frt_renderer_remove_lights(frt_renderer* r, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode) {
+    if (const int rc = check_entry(r, "remove_lights", kEditChecks)) return rc;
+    if (const int rc = check_rebuild_mode("remove_lights", rebuild_mode)) return rc;
+    if (n == 0) return FRT_OK;
+    std::vector<frt_material> mats;
+    if (const int rc = read_materials(r, mats)) { if (rc == FRT_ERR_HIP) r->failed = true; return rc; }
+    LightRemoval rem;
+    std::string why;
+    if (const int rc = check_remove_lights(n, ids, r->sv.num_lights, mats.data(), mats.size(), r->rf.inst, rem, why)) return fail(rc, "remove_lights: " + why);
+    if (rem.lights.empty()) return FRT_OK;
+    const int rc = remove_lights_impl(r, rem, rebuild_mode);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
+}
+
+// The layers above the removed one move down, one device-to-device copy each in ascending order (source and destination of a copy are different layers;
+// a copy's destination is the source of the copy before it, which the stream has finished by then).
+static int remove_texture_impl(frt_renderer* r, int kind, uint32_t layer) {
+    FRT_DEVICE(r);
+    if (const int rc = order_behind_frames(r, true)) return rc;
+    pin_capacity(r, kind == 0 ? kPoolColor : kPoolData);
+    uint32_t& layers = kind == 0 ? r->rf.color_layers : r->rf.data_layers;
+    uint8_t* base = const_cast<uint8_t*>(kind == 0 ? r->sv.color_tex : r->sv.data_tex);
+    for (uint32_t l = layer; l + 1u < layers; ++l)
+        HIP_TRY(hipMemcpyAsync(base + (size_t)l * kTextureLayerBytes, base + (size_t)(l + 1u) * kTextureLayerBytes, kTextureLayerBytes, hipMemcpyDeviceToDevice, r->stream));
+    HIP_TRY(launch_remap_materials(const_cast<MaterialView*>(r->sv.materials), r->sv.num_materials, nullptr, 0u, kind == 0 ? layer : kGone, kind == 1 ? layer : kGone, r->stream));
+    --layers;
+    return FRT_OK;
+}
+int frt_renderer_remove_texture(frt_renderer* r, int kind, uint32_t layer) {
+    if (const int rc = check_entry(r, "remove_texture", kLookChecks)) return rc;
+    std::string why;
+    if (const int rc = check_remove_texture(kind, layer, r->rf.color_layers, r->rf.data_layers, nullptr, 0, why)) return fail(rc, "remove_texture: " + why);      // (what needs no device first)
+    std::vector<frt_material> mats;
+    if (const int rc = read_materials(r, mats)) { if (rc == FRT_ERR_HIP) r->failed = true; return rc; }
+    if (const int rc = check_remove_texture(kind, layer, r->rf.color_layers, r->rf.data_layers, mats.data(), mats.size(), why)) return fail(rc, "remove_texture: " + why);
+    const int rc = remove_texture_impl(r, kind, layer);
+    if (rc == FRT_ERR_HIP) r->failed = true;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------ ray queries

@@ -125,6 +125,10 @@ SYMBOLS = {
     "frt_scene_set_texture": (C.c_int, [_P, C.c_int, _U32, _P]),
     "frt_scene_add_instances": (C.c_int, [_P, _U32, _P, _P, _P]),
     "frt_scene_remove_instances": (C.c_int, [_P, _U32, _P]),
+    "frt_scene_remove_materials": (C.c_int, [_P, _U32, _P]),
+    "frt_scene_remove_meshes": (C.c_int, [_P, _U32, _P]),
+    "frt_scene_remove_lights": (C.c_int, [_P, _U32, _P]),
+    "frt_scene_remove_texture": (C.c_int, [_P, C.c_int, _U32]),
     "frt_scene_trace_closest": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_trace_any": (C.c_int, [_P, _U32, _P, _P]),
     "frt_camera_default": (None, [C.c_float, _U32, _U32, C.POINTER(CameraUniform)]),
@@ -164,6 +168,10 @@ SYMBOLS = {
     "frt_renderer_scene_counts": (C.c_int, [_P, _P]),
     "frt_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
     "frt_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_renderer_remove_materials": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_remove_meshes": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_remove_lights": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_renderer_remove_texture": (C.c_int, [_P, C.c_int, _U32]),
     "frt_renderer_add_meshes": (C.c_int, [_P, _U32, _P]),
     "frt_renderer_add_materials": (C.c_int, [_P, _U32, _P]),
     "frt_renderer_add_texture": (C.c_int, [_P, C.c_int, _P]),
@@ -204,6 +212,10 @@ SYMBOLS = {
     "frt_multi_renderer_rebuild_tree_ex": (C.c_int, [_P, C.c_uint32]),
     "frt_multi_renderer_add_instances": (C.c_int, [_P, _U32, _P, _P, _P, _U32]),
     "frt_multi_renderer_remove_instances": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_multi_renderer_remove_materials": (C.c_int, [_P, _U32, _P]),
+    "frt_multi_renderer_remove_meshes": (C.c_int, [_P, _U32, _P]),
+    "frt_multi_renderer_remove_lights": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_multi_renderer_remove_texture": (C.c_int, [_P, C.c_int, _U32]),
     "frt_multi_renderer_add_meshes": (C.c_int, [_P, _U32, _P]),
     "frt_multi_renderer_add_materials": (C.c_int, [_P, _U32, _P]),
     "frt_multi_renderer_add_texture": (C.c_int, [_P, C.c_int, _P]),

@@ -3,7 +3,7 @@ import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
 from .scene import (transform_args, mesh_vertex_args, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
-                    pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan)
+                    pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
 
 REBUILD_MODES = {"morton": 0, "sah": 1}      # include/frt.h: FRT_REBUILD_MORTON, FRT_REBUILD_SAH
@@ -92,6 +92,30 @@ class _SceneGrowth:
     def register_sphere_light(self, mesh_id, transform_colmajor, color, intensity, quality="sah"):
         me, m, c, i = light_register_args(mesh_id, transform_colmajor, color, intensity)
         return self._grow_call("register_sphere_light", me, m.ctypes.data, c.ctypes.data, i, rebuild_mode(quality))
+
+
+    # ---- and out again (include/frt.h: frt_renderer_remove_materials and the three calls after it): ids stay dense, those above a
+    # removed one shift down, and the material id every pixel keeps in BUF_GPOS.w follows (65535.0 where the material left).
+    def remove_materials(self, ids):
+        """Remove materials no instance uses from the replica(s)."""
+        n, i = id_list_args(ids, "material")
+        self._grow_call("remove_materials", n, i.ctypes.data)
+
+    def remove_meshes(self, ids):
+        """Remove meshes no instance uses from the replica(s); the vertex and index pools close up."""
+        n, i = id_list_args(ids, "mesh")
+        self._grow_call("remove_meshes", n, i.ctypes.data)
+
+    def remove_lights(self, ids, quality="sah"):
+        """Remove lights from the replica(s): an add_lights light loses its record; a registered light leaves with its instance and its emissive material,
+        which ends in the device tree rebuild `quality` names (synchronous). Pass the new light count to build_uniform from the next frame on."""
+        n, i = id_list_args(ids, "light")
+        self._grow_call("remove_lights", n, i.ctypes.data, rebuild_mode(quality))
+
+    def remove_texture(self, kind, layer):
+        """Remove one texture layer no material names: kind "color" (0) or "data" (1); the layers above it shift down."""
+        k, l = layer_args(kind, layer)
+        self._grow_call("remove_texture", k, l)
 
 
 class Renderer(_HostQueries, _SceneGrowth):

@@ -86,6 +86,24 @@ def instance_id_args(ids):
     return ids.size, ids.astype(np.uint32)
 
 
+def id_list_args(ids, what):
+    """(n, ids) for the *_remove_materials / _meshes / _lights calls: `ids` an int or a sequence."""
+    ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, np.int64)))
+    if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise FrtError(f"{what} ids must be a flat list of unsigned 32-bit indices")
+    return ids.size, ids.astype(np.uint32)
+
+
+def layer_args(kind, layer):
+    """(kind, layer) for the *_remove_texture calls: kind 0 / "color" or 1 / "data"."""
+    k = {"color": 0, "colour": 0, "data": 1}.get(kind, kind)
+    if k not in (0, 1):
+        raise ValueError(f'kind must be "color" (0) or "data" (1), not {kind!r}')
+    if not 0 <= int(layer) <= 0xFFFFFFFF:
+        raise FrtError("layer must be an unsigned 32-bit index")
+    return int(k), int(layer)
+
+
 def emission_args(light, color, intensity):
     if not 0 <= int(light) <= 0xFFFFFFFF:
         raise FrtError("light must be an unsigned 32-bit index")
@@ -355,6 +373,32 @@ class SceneBuilder:
         """Remove instances (an id given twice once); the ids above them shift down."""
         n, i = instance_id_args(ids)
         check(lib().frt_scene_remove_instances(self._h, n, i.ctypes.data))
+        return self
+
+    # ---- what the built scene no longer holds (include/frt.h: frt_scene_remove_materials and the three calls after it; DESIGN.md section 16). Host copy
+    # only: ids stay dense (those above a removed one shift down), and the scene equals one built from scratch with the surviving builder calls.
+    def remove_materials(self, ids):
+        """Remove materials no instance uses; the material ids above them shift down."""
+        n, i = id_list_args(ids, "material")
+        check(lib().frt_scene_remove_materials(self._h, n, i.ctypes.data))
+        return self
+
+    def remove_meshes(self, ids):
+        """Remove meshes no instance uses; the mesh ids above them shift down and the vertex and index lists close up."""
+        n, i = id_list_args(ids, "mesh")
+        check(lib().frt_scene_remove_meshes(self._h, n, i.ctypes.data))
+        return self
+
+    def remove_lights(self, ids):
+        """Remove lights: an add_light light loses its record, a registered light leaves with its instance and its emissive material."""
+        n, i = id_list_args(ids, "light")
+        check(lib().frt_scene_remove_lights(self._h, n, i.ctypes.data))
+        return self
+
+    def remove_texture(self, kind, layer):
+        """Remove one texture layer no material names: kind "color" (0) or "data" (1); the layers above it shift down."""
+        k, l = layer_args(kind, layer)
+        check(lib().frt_scene_remove_texture(self._h, k, l))
         return self
 
     # ---- ray queries on the host copy of the built scene (include/frt.h: frt_scene_trace_closest / _any): the specification of Renderer.trace_*

@@ -187,6 +187,27 @@ int frt_scene_set_texture(frt_scene* s, int kind /*0 colour (sRGB), 1 data*/, ui
  * every instance. FRT_ERR_LIMIT: more than 0xFFFFFFFE triangles would result, or the builder refuses the new tree. */
 int frt_scene_add_instances(frt_scene* s, uint32_t n, const uint32_t* mesh_ids, const uint32_t* mat_ids, const float* m_colmajor16);
 int frt_scene_remove_instances(frt_scene* s, uint32_t n, const uint32_t* ids);
+/* What a BUILT scene no longer holds. Ids stay dense: everything above a removed id shifts down, an id given twice is removed once.
+ * Afterwards the scene equals, selector for selector of frt_scene_get (the trees included), a scene built from scratch with the surviving builder calls:
+ * the lists are edited and the scene is built again. Host copy only; a renderer's replica follows with frt_renderer_remove_*. Everything is validated before
+ * anything is applied; a refused call changes nothing. n == 0: FRT_OK.
+ * materials: the material word of every instance follows. Refused: a material an instance still uses; a material frt_scene_register_quad_light /
+ *   _sphere_light made (remove the light instead).
+ * meshes: the vertex, index and mesh-info lists close up as a from-scratch build lays them out, the mesh word of every instance follows. Refused: a mesh
+ *   an instance still uses.
+ * lights: a light of frt_scene_add_light loses its record; a light of frt_scene_register_quad_light / _sphere_light leaves as the composite that call
+ *   made: its record, its instance and its emissive material (instance and material ids shift as after _remove_instances and _remove_materials).
+ *   light_index >= 0 of every material and the light link of every instance follow. Refused: a light that the light_index of a surviving material names;
+ *   a registered light whose material another instance uses; removing every instance. A scene may be left without lights.
+ * texture: one layer (kind 0 colour, 1 data); the 16-bit slots of that kind above it in every material's tex_info_* follow (colour: base colour and
+ *   emissive; data: normal, occlusion, metallic-roughness; 0xFFFF stays). Refused: a layer a material slot of that kind names; layers 0 - 2 of either
+ *   kind, which every scene starts with.
+ * FRT_ERR_STATE: scene not built. FRT_ERR_INVALID_ARG: a null pointer with n > 0, an id or layer out of range, kind not 0 or 1, the refusals above.
+ * FRT_ERR_LIMIT: the builder refuses the new tree (lights). */
+int frt_scene_remove_materials(frt_scene* s, uint32_t n, const uint32_t* ids);
+int frt_scene_remove_meshes(frt_scene* s, uint32_t n, const uint32_t* ids);
+int frt_scene_remove_lights(frt_scene* s, uint32_t n, const uint32_t* ids);
+int frt_scene_remove_texture(frt_scene* s, int kind /*0 colour, 1 data*/, uint32_t layer);
 /* stats[8]: quad nodes, deepest traversal stack of the quad tree, 8-wide nodes (0: the scene has no 8-wide tree: more than 65,536 nodes), deepest stack of
  * the 8-wide tree, its levels, sum of its nodes' child counts, its triangle slots, how the quad tree was folded (2 surface-area programme, 1 programme where
  * the traversal-stack bound allows and the greedy fold elsewhere, 0 greedy fold) */
@@ -431,7 +452,7 @@ int frt_renderer_remove_instances(frt_renderer* r, uint32_t n, const uint32_t* i
  * n == 0 is FRT_OK (the add calls: the current count), FRT_ERR_STATE while a frame is open, a next frame's G-buffer + T-trace that ran ahead is dropped and
  * redone, accumulation, reservoirs and frame_count are kept. The inputs are copied during the call. The new ids are accepted at once by
  * frt_renderer_add_instances, _set_mesh_vertices, _set_materials, _set_instance_materials, _set_light_emission and _set_texture; the caller passes the new
- * light count in frt_camera_uniform.num_lights from the next frame on. Nothing can be removed: per-pixel history holds light indices and material ids.
+ * light count in frt_camera_uniform.num_lights from the next frame on. What was added can be taken out again: frt_renderer_remove_* below.
  * add_meshes / _materials / _texture / _lights add no triangle: no rebuild, asynchronous on the renderer's stream; they wait for the stream only when a
  * capacity grows (capacities at least double, texture arrays grow by max(4, count / 2) layers, and are never shrunk). Returns: the id of the first new
  * mesh / material, the layer id, the index of the first new light (lights as frt_scene_add_light takes them: no instance, no link).
@@ -453,6 +474,24 @@ int frt_renderer_register_sphere_light(frt_renderer* r, uint32_t mesh_id, const 
 /* counts[6]: meshes, vertices, indices, colour layers, data layers of the replica AS IT IS NOW (with frt_renderer_scene_counts what sizes the arrays of
  * frt_renderer_read_scene), and the calls above that had to grow a capacity so far. */
 int frt_renderer_pool_counts(frt_renderer* r, uint32_t counts[6]);
+/* frt_scene_remove_materials / _meshes / _lights / _texture on this renderer's scene replica, on the device: the same arguments, checks
+ * and refusals, under the contract of the add calls above: after any sequence of these calls and every other edit the replica holds what a scene built from
+ * scratch with the surviving builder calls holds (frt_renderer_read_scene selectors 2 - 6, 16 and 17 byte for byte, 13 as a set of records, every frame bit
+ * for bit); everything is validated first, a refused call changes nothing, n == 0 is FRT_OK, FRT_ERR_STATE while a frame is open; a next frame's G-buffer +
+ * T-trace that ran ahead is dropped and redone; accumulation, both reservoir buffers and frame_count are kept. Counts move (frt_renderer_scene_counts,
+ * _pool_counts), capacities are never shrunk. The removed ids' successors are accepted at once by every other call under their new ids; the caller passes
+ * the new light count in frt_camera_uniform.num_lights from the next frame on.
+ * Per-pixel history: the one id a pixel keeps between frames is the material id in FRT_BUF_GPOS.w, which temporal reprojection compares. Whenever materials
+ * are renumbered (remove_materials; remove_lights of a registered light) that word is renumbered in every G-buffer set the renderer owns: a hit's id follows,
+ * an id that left becomes 65535.0 (no valid id: such a pixel restarts its reservoir), the miss word -1 stays. Nothing else per pixel changes.
+ * remove_materials, _meshes, _texture, and remove_lights of lights that have no instance add no triangle work and are only enqueued on the renderer's stream
+ * (remove_lights and remove_texture wait for the device once: their checks read the material table back). remove_lights of a registered light removes its
+ * instance as frt_renderer_remove_instances does, with the device rebuild in `rebuild_mode`, and is synchronous; a tree that is refused (FRT_ERR_LIMIT)
+ * leaves everything as it was. FRT_ERR_INVALID_ARG also for an unknown rebuild_mode. FRT_ERR_HIP leaves the renderer failed (frt_renderer_clear). */
+int frt_renderer_remove_materials(frt_renderer* r, uint32_t n, const uint32_t* ids);
+int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids);
+int frt_renderer_remove_lights(frt_renderer* r, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
+int frt_renderer_remove_texture(frt_renderer* r, int kind /*0 colour, 1 data*/, uint32_t layer);
 /* For an importer (frt/renderer.py: add_gltf): what frt_scene_add_gltf_materials would add to a scene that has `color_layers` / `data_layers` texture
  * layers, without adding it. materials_out ([materials] of frt_model_counts): the model's materials with their image indices remapped to layer ids;
  * color_images / data_images ([images] each): the image that becomes layer color_layers + k / data_layers + k; counts[2]: how many of each. */
@@ -542,6 +581,12 @@ int frt_multi_renderer_add_texture(frt_multi_renderer* m, int kind, const uint8_
 int frt_multi_renderer_add_lights(frt_multi_renderer* m, uint32_t n, const frt_light* lights);
 int frt_multi_renderer_register_quad_light(frt_multi_renderer* m, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
 int frt_multi_renderer_register_sphere_light(frt_multi_renderer* m, uint32_t mesh_id, const float m_colmajor[16], const float color[3], float intensity, uint32_t rebuild_mode);
+/* frt_renderer_remove_materials, _remove_meshes, _remove_lights and _remove_texture on every strip's replica. The first strip's refusal leaves every replica
+ * as it was; a strip that fails after the first one has changed leaves the handle failed. */
+int frt_multi_renderer_remove_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids);
+int frt_multi_renderer_remove_meshes(frt_multi_renderer* m, uint32_t n, const uint32_t* ids);
+int frt_multi_renderer_remove_lights(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, uint32_t rebuild_mode);
+int frt_multi_renderer_remove_texture(frt_multi_renderer* m, int kind, uint32_t layer);
 /* The three ray-query calls on the first strip's replica (all replicas are equal). Host-pointer form only: flags must be 0. */
 int frt_multi_renderer_trace_closest(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, frt_ray_hit* out, uint32_t flags);
 int frt_multi_renderer_trace_any(frt_multi_renderer* m, uint32_t n, const frt_ray* rays, uint8_t* occluded_out, uint32_t flags);
