@@ -1,6 +1,7 @@
 // frt_renderer_state.hpp — private to the translation units of the renderer's C ABI (frt_renderer.hip: create, destroy and the frame loop;
-// frt_scene_edit.hip: everything that edits or reads the scene replica between frames; frt_multi.hip; frt_scene_abi.cpp; frt_query.hip): the error and
-// device helpers, the layout of the per-pixel buffers, the renderer's state structs and the few functions more than one of those files calls.
+// frt_scene_edit.hip: everything that edits the scene replica between frames; frt_scene_read.hip: everything that only reads it; frt_multi.hip;
+// frt_scene_abi.cpp): the error and device helpers, the layout of the per-pixel buffers, the renderer's state structs and the few functions more than
+// one of those files calls.
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
@@ -90,8 +91,11 @@ struct ExpState {
 };
 #endif
 
-// What a call that edits or queries the scene replica stages its data through (frt_scene_edit.hip): one pinned host block and one device block, each
-// grown on demand and never shrunk, and the event behind the last copy out of the pinned block.
+// The state of the scene edits (frt_scene_edit.hip) is made of three things: Staging blocks for what a call uploads, OwnedBuf for the
+// device buffers a call writes beside the replica, and one capacity record (PoolState) for every buffer of the replica that is sized by a count.
+
+// What a call that edits or queries the scene replica stages its data through: one pinned host block and one device block, each grown on demand and
+// never shrunk, and the event behind the last copy out of the pinned block.
 struct Staging {
     uint8_t* h = nullptr; size_t h_cap = 0;
     uint8_t* d = nullptr; size_t d_cap = 0;
@@ -100,7 +104,20 @@ struct Staging {
     // The device block is replaced only after a wait for `stream`, whose kernels of an earlier call may still read it.
     int reserve(size_t h_bytes, size_t d_bytes, hipStream_t stream);
     int mark(hipStream_t stream);          // the copies out of the pinned block are enqueued: record `ev` (created here, at the first call)
+    int upload(const void* src, size_t bytes, hipStream_t stream);      // reserve, `src` -> pinned block -> device block on `stream`, mark
     void release();
+};
+
+// A device buffer the renderer owns beside the scene replica: what a call builds into, and what then trades places with a buffer of the replica. It is
+// allocated among the replica's allocations (frt_renderer::scene_allocs), so whichever side of a trade it ends on it is freed with the replica.
+struct OwnedBuf {
+    void* p = nullptr; size_t bytes = 0;
+    // Room for `need` bytes: nothing when it is large enough; otherwise a wait for the main stream (a kernel of an earlier call may still use the
+    // buffer), then it is freed and allocated anew (its contents are not kept).
+    int ensure(frt_renderer* r, size_t need);
+    // This buffer enters the replica as `live`; the one that leaves (with room for `live_bytes`) is what the next call builds into.
+    template <class T> void trade(const T*& live, size_t live_bytes) { void* was = const_cast<T*>(live); live = static_cast<const T*>(p); p = was; bytes = live_bytes; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
 // What frt_renderer_set_instance_transforms needs beside the scene replica, made at create. Device: the object-space positions of every
@@ -123,55 +140,52 @@ struct RefitState {
     std::vector<uint32_t> mesh_tris;       // per mesh: its triangles (what an added instance of it brings)
     Staging def;
     uint32_t color_layers = 0, data_layers = 0;   // texture layers of the replica (the material and texture edits check against them)
-    uint64_t device_bytes = 0;
 };
 
 // What frt_renderer_rebuild_tree adds ("Rebuild"), allocated at the first call: the scratch of the kernels, the triangle slots and the
 // id -> slot table that are NOT in use (they trade places with the replica's at every successful rebuild) and up to two quad-node buffers of
-// rebuild_max_nodes() nodes (the host-built tree's buffer may be smaller than a device tree needs, so it is never built into; the second one
-// is allocated by the second rebuild). All of it is freed with the scene replica.
+// rebuild_max_nodes() nodes, built into in turn (the host-built tree's buffer may be smaller than a device tree needs, so it is never built into;
+// the second one is allocated by the second rebuild). Each has room for a tree over the triangle capacity.
 struct RebuildState {
     RebuildScratch scratch;
-    float4* tris = nullptr; uint32_t* slot_of = nullptr;
-    float4* nodes[2] = {nullptr, nullptr};
-    uint32_t cap_tris = 0, nodes_cap[2] = {0, 0};      // triangles `tris` / `slot_of` have room for, quad nodes each of `nodes` has (capacities)
+    OwnedBuf tris, slot_of;
+    OwnedBuf nodes[2];
     bool done = false;                     // the replica's quad tree is a device rebuild: the pair tree and its quantised form are stale
     uint32_t origin = 0;                   // frt_renderer_tree_stats: 1 the Morton tree, 2 the refined tree
     uint32_t last[4] = {0, 0, 0, 0};       // frt_renderer_rebuild_stats
-    uint64_t device_bytes = 0;
 };
 
-// What frt_renderer_add_instances / _remove_instances add, allocated at the first call and freed with the scene replica. From then on
-// every buffer of the replica that is sized by triangles or instances has a capacity apart from its count: capacities grow geometrically, are never
-// shrunk, and a growth is a new allocation plus a device-to-device copy of what is in use.
+// What frt_renderer_add_instances / _remove_instances add, allocated at the first call, each with room for the triangle or instance
+// capacity: an edit writes them, and its rebuild reads them.
 struct InstanceEditState {
-    uint32_t cap_tris = 0, cap_inst = 0;   // 0: the replica's buffers are as uploaded, exactly as large as their counts
-    float4* tris = nullptr; uint32_t* slot_of = nullptr;      // what an edit writes and its rebuild reads: never part of the replica
-    float4* shade_tris = nullptr; InstanceView* instances = nullptr;   // written by an edit; they trade places with the replica's when its rebuild succeeds
-    const float4* d_normals = nullptr;     // the decoded normal of every vertex (xyz, 0), indexed as SceneView::attributes; set_mesh_vertices keeps it up
+    OwnedBuf tris, slot_of;                // never part of the replica: the rebuild makes the replica's next slots and table out of them
+    OwnedBuf shade_tris, instances;        // they trade places with the replica's when the edit's rebuild succeeds
     Staging rec;                           // the records of one call (AppendInstance / RemovedRange)
-    uint32_t growths = 0;                  // calls that had to grow a capacity
 };
 
-// What frt_renderer_add_meshes / _add_materials / _add_texture / _add_lights / _register_*_light add. From the first such call on, the
-// replica's buffers that are sized by vertices, indices, meshes, materials, lights and texture layers have a capacity apart from their count, under the
-// rules of §14: a capacity at least doubles when it grows (the texture arrays, 4 MiB a layer: by max(4, count / 2) layers), is never shrunk, and a
-// growth is a new allocation plus a device-to-device copy behind a wait for the stream. A renderer that never makes such a call allocates nothing.
-enum { kPoolVerts = 0, kPoolIndices, kPoolMeshes, kPoolMaterials, kPoolLights, kPoolColor, kPoolData, kPoolCount };
-struct MeshEditState {
+// The one capacity record. Every buffer of the replica that is sized by a count belongs to one of these pools; pool_count() tells how many elements of a
+// pool are in use, cap[] how many its buffers have room for. A renderer's pools are as uploaded, exactly as large as their counts (cap 0), until a
+// call gives one a capacity apart from its count: a growth (frt_renderer_add_*, _register_*_light: DESIGN.md §14, §15) or, before a count goes down, a
+// removal (§14, §16). A capacity at least doubles when it grows (the texture arrays, 4 MiB a layer: by max(4, count / 2) layers), is never shrunk, and
+// a growth is a new allocation plus a device-to-device copy behind a wait for the stream. A renderer that never makes such a call allocates nothing.
+enum { kPoolVerts = 0, kPoolIndices, kPoolMeshes, kPoolMaterials, kPoolLights, kPoolColor, kPoolData,      // §15, §16
+       kPoolTris, kPoolInstances,                                                                           // §14
+       kPoolCount };
+struct PoolState {
     uint32_t cap[kPoolCount] = {};         // 0: the pool is as uploaded, exactly as large as its count
-    uint32_t growths = 0;                  // calls that had to grow a capacity
-    Staging up;                            // what one call uploads: the pinned block and, for add_meshes, the device block its kernel reads
+    uint32_t growths = 0;                  // calls that had to grow a pool of §15 (frt_renderer_pool_counts)
+    // The decoded normal of every vertex (xyz, 0), indexed as SceneView::attributes: a buffer of the vertex pool that is not part of the SceneView, made
+    // at the first call that needs it (ensure_normals); set_mesh_vertices keeps it up, add_instances reads it.
+    const float4* d_normals = nullptr;
+    Staging up;                            // what one call of §15 uploads: the pinned block and, for add_meshes, the device block its kernel reads
 };
 
-// What frt_renderer_remove_materials / _meshes / _lights / _texture add, allocated at the first such call and freed with the scene replica.
-// A pool that closes up is compacted out of place into its `spare`, which then trades places with the replica's buffer: what left the replica is what
-// the next removal from that pool writes, behind every kernel that read it (the same stream). A spare has room for its pool's capacity. From the first
-// removal on a pool has a capacity apart from its count (MeshEditState::cap), as after a growth: counts move, capacities are never shrunk.
+// What frt_renderer_remove_materials / _meshes / _lights / _texture add, allocated at the first such call. A pool that closes up is
+// compacted out of place into its `spare`, which then trades places with the replica's buffer: what left the replica is what the next removal from that
+// pool writes, behind every kernel that read it (the same stream). A spare has room for its pool's capacity.
 enum { kSparePos = 0, kSpareAttrs, kSpareNormals, kSpareIndices, kSpareMeshInfos, kSpareMaterials, kSpareLights, kSpareCount };
 struct RemoveState {
-    void* spare[kSpareCount] = {};
-    size_t spare_bytes[kSpareCount] = {};
+    OwnedBuf spare[kSpareCount];
     Staging tab;                           // the tables of one call: old -> new ids and removed spans
 };
 
@@ -239,7 +253,7 @@ struct frt_renderer {
     RefitState rf;
     RebuildState rbt;
     InstanceEditState ie;
-    MeshEditState me;
+    PoolState pools;
     RemoveState rm;
     // The host-pointer ray queries: both blocks [input | output] of a call. Such a call is synchronous — the last call's copies are done
     // when the next one starts — so this one is never marked: no event is created, recorded or waited for.
@@ -271,4 +285,10 @@ int fence_ahead(frt_renderer* r);                                  // frt_render
 int sync_all(frt_renderer* r);
 int drop_speculation(frt_renderer* r);
 int upload_refit_data(frt_renderer* r, const SceneBuilder& b);    // frt_scene_edit.hip
+// What a call `what` refuses before it looks at its own arguments, in this order: a null handle, then the `parts` it asks for.
+enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditChecks = kNotFailed | kBetweenFrames | kQuadTree,
+       kLookChecks = kNotFailed | kBetweenFrames };      // (the edits of §13, §15 and §16 involve no tree: every renderer takes them)
+int check_entry(const frt_renderer* r, const std::string& what, unsigned parts);
+uint32_t pool_count(const frt_renderer* r, int pool);             // elements of a pool (PoolState) in use
+int ensure_normals(frt_renderer* r);                              // PoolState::d_normals exists afterwards
 }

@@ -261,6 +261,72 @@ def test_round_trip(gpu, orc):
     frames_of_list(frt, orc, r, lst, first, cfg, "round trip", frames=3, oracle=False)
 
 
+def decoded_normals(frt, attrs):
+    """What the host's decoded_vertex_normal makes of the attribute records `attrs`, (xyz, 0) per vertex: host_normals over one mesh that holds them (a
+    shading record's normals do not depend on the positions)."""
+    from test_scene_grow_gpu import host_normals
+    n = len(attrs)
+    v = np.arange(n, dtype=np.float32)
+    pos = np.stack([np.cos(v), np.sin(v), 0.01 * v, np.ones(n, np.float32)], axis=1).astype(np.float32)
+    return host_normals(frt, [frt.geometry.Geometry(pos, np.ascontiguousarray(attrs, np.float32).reshape(n, 8), np.arange(3, dtype=np.uint32))])
+
+
+def test_capacities_across_edit_families(gpu):
+    """One renderer through the orders in which the capacities of the edit families hand over to each other: a removal on pools that never grew, growth from
+    the pinned capacities, a deformation and a rebuild on the grown buffers, removal again (spares smaller than their pools), and an addition that fits."""
+    from test_scene_grow_gpu import pyramid, new_materials, new_transforms
+    frt = gpu
+    cfg = "pipeline"
+    lst = cornell_list(frt)
+    lst.materials.append(frt.material_new([0.1, 0.2, 0.3, 1.0]))      # 6: no instance uses it (the registered lights' materials are 7 and 8 then)
+    calls = Calls.of_list(lst)
+    r = renderer(frt, calls.build(frt), cfg)
+
+    def check(what, origin):
+        fresh = calls.build(frt)
+        check_all(frt, r, fresh, what, origin=origin)
+        assert r.read_scene("normals").tobytes() == decoded_normals(frt, r.read_scene("attributes")).tobytes(), f"{what}: normals"
+        return fresh
+
+    # 1. removal first: the pools are pinned at their counts
+    r.remove_materials(6)
+    r.remove_meshes(4)      # the one-triangle mesh
+    calls = calls.without_materials([6]).without_meshes([4])
+    assert r.pool_counts()["growths"] == 0
+    # 2. growth from a pinned capacity
+    me, ma, m = [4, 4, 4], [8, 9, 8], new_transforms(frt)
+    light = {"kind": "quad", "mesh": 0, "m": trs(frt, (0.4, 0.6, 0.2), 0.3, 0.2), "color": (1.0, 0.8, 0.6), "intensity": 4.0}
+    assert r.add_meshes([frt.geometry.create_sphere(1), pyramid(frt)]) == 4      # (more vertices than the 3 the removed mesh left room for)
+    assert r.add_materials(new_materials(frt)) == 8
+    assert r.add_instances(me, ma, m) == 9
+    assert r.register_quad_light(light["mesh"], light["m"], light["color"], light["intensity"]) == 2
+    assert r.pool_counts()["growths"] >= 1
+    calls = calls.plus({"kind": "mesh", "geo": frt.geometry.create_sphere(1)}, {"kind": "mesh", "geo": pyramid(frt)}, *[{"kind": "material", "mat": x} for x in new_materials(frt)],
+                       *[{"kind": "inst", "mesh": a, "mat": b, "m": c} for a, b, c in zip(me, ma, m)], light)
+    check("growth from a pinned capacity", origin=2)
+    # 3. a mesh from before step 1 deformed (its decoded normals live in a grown, once-compacted buffer), then a rebuild
+    cube = frt.geometry.create_cube()
+    pos = np.array(cube.positions, np.float32); pos[:, 0] *= 1.0 + 0.3 * pos[:, 1]
+    att = np.array(cube.attributes, np.float32); att[:, 2:4] = att[:, 2:4] * 0.5 + 0.25
+    att[:, 0:2] = att[::-1, 0:2].copy()      # (other normals too: valid encodings, each another vertex's)
+    r.set_mesh_vertices(1, pos, att)
+    r.rebuild_tree(quality="sah")
+    calls.calls[calls._made_by(("mesh",))[1]]["geo"] = frt.geometry.Geometry(pos, att, cube.indices)
+    # 4. removal again: the light of step 2, two of its instances, its unused mesh (whose spares are smaller than the pools by now)
+    r.remove_lights(2)
+    r.remove_instances([10, 11])
+    r.remove_meshes(5)
+    calls = calls.without_lights([2]).without_instances([10, 11]).without_meshes([5])
+    check("removal after growth", origin=2)
+    # 5. step 2's instances once more: they fit
+    growths = r.pool_counts()["growths"]
+    assert r.add_instances(me, ma, m) == 10
+    assert r.pool_counts()["growths"] == growths
+    calls = calls.plus(*[{"kind": "inst", "mesh": a, "mat": b, "m": c} for a, b, c in zip(me, ma, m)])
+    fresh = check("an addition that fits", origin=2)
+    check_frames(frt, None, r, calls, fresh, cfg, "capacities across the edit families", frames=2, oracle=False)
+
+
 def test_refusals_change_nothing(gpu):
     frt = gpu
     L = frt.lib()
