@@ -2,7 +2,7 @@
 //
 // Launch shape: one wave64 owns an 8x8 pixel tile (the reference's @workgroup_size(8,8), gbuffer.rs:302), four waves
 // per 256-thread workgroup = a 16x16 block. Each lane's BVH traversal stack is a column of an LDS array
-// (kStackDepth x 256 words = 32 KiB per workgroup; lane-consecutive addresses -> conflict-free ds_read/ds_write_b32).
+// (one 256-word row per stack entry the scene's tree needs; lane-consecutive addresses -> conflict-free ds_read/ds_write_b32).
 // Scene data (quad nodes 128 B, triangle slots 48 B: frt_trace.hpp) is read with 16-byte loads; per-pixel buffers are pixel-linear
 // float4 / 8-byte / 4-byte streams, so every wave-level access is a set of full 128-byte row segments.
 #include "frt_mono.hpp"
@@ -12,19 +12,21 @@
 namespace frt {
 
 static constexpr int kBlock = 256;
-// LDS of a traced workgroup = the stack array and nothing else: exactly 32 KiB, five workgroups per CU by LDS. The quad tree of any scene the
-// builder accepts needs at most kStackDepth - 1 entries per lane (frt_bvh.cpp: build_quad_nodes folds only within that budget; a plain binary
-// subtree is at most kMaxBvhDepth = 30 deep), so the LAST row of the array is never a stack entry: the workgroup's few shared words (ray-count
-// partial sums, the queue reservation scratch) live there.
-static constexpr int kMiscRow = kStackDepth - 1;
+// LDS of a quad-walk workgroup is DYNAMIC, sized at launch from the scene's tree (frt_kernels.hpp: walk_lds_plan): `stack_rows` rows of kBlock words
+// — the tree's stack need; the builder accepts no tree that needs more than kStackDepth - 1 entries per lane (frt_bvh.cpp: build_quad_nodes folds only
+// within that budget; a plain binary subtree is at most kMaxBvhDepth = 30 deep) — then the workgroup's few shared words (ray-count partial sums, the
+// queue reservation scratch: 128 bytes) and behind them the copy of the tree's top (stage_top_nodes). The traced kernels' budget is 40 KiB (four
+// workgroups per CU, all their 128 VGPRs allow): the Cornell Box's 24 rows leave room for 127 of its 326 quad nodes.
+extern __shared__ __attribute__((aligned(128))) uint32_t s_walk[];
+struct WalkArgs { uint32_t stack_rows, top_nodes; };      // kernel argument: WalkLdsPlan without the byte count
 // Kernels that walk the 8-wide tree (WALK >= kWalkWide; frt_trace.hpp: trace8) need one stack word per level: kStack8 rows + one row for the shared
 // words = 9 KiB, and — kWalkWideLds — the whole tree behind them in dynamic LDS (128 bytes per node: 27 KiB for the Cornell Box's 216 nodes).
-template <int WALK> struct WalkLds { static constexpr int kRows = kStackDepth, kMisc = kMiscRow; };
+template <int WALK> struct WalkLds;
 template <> struct WalkLds<kWalkWide> { static constexpr int kRows = kStack8 + 1, kMisc = kStack8; };
 template <> struct WalkLds<kWalkWideLds> { static constexpr int kRows = kStack8 + 1, kMisc = kStack8; };
 extern __shared__ uint4 s_wide_nodes[];      // dynamic LDS of the kWalkWideLds kernels
 #ifndef FRT_WAVES
-#define FRT_WAVES 4      // waves per SIMD the traced kernels are built for (A/B builds: 5 needs <= 96 VGPRs and <= 32 KiB of LDS per workgroup)
+#define FRT_WAVES 4      // waves per SIMD the traced kernels are built for (A/B builds: 5 needs <= 96 VGPRs and five workgroups per CU, 160 KiB / 5 = 32 KiB of LDS each at the most)
 #endif
 
 __device__ __forceinline__ bool tile_pixel_at(const FrameView& fv, uint32_t tx, uint32_t ty, uint32_t& px, uint32_t& py) {
@@ -66,20 +68,30 @@ template <> struct CtxOf<kWalkWideLds> { typedef Wide8PathCtx type; };
 // Workgroup prologue shared by the traced kernels: clears the shared words, stages the tree's top (quad walk) or the whole tree (kWalkWideLds) in LDS,
 // returns the context's tree pointer set up. One barrier inside.
 template <int WALK, class Ctx>
-__device__ __forceinline__ void walk_prologue(const SceneView& sc, uint32_t* s_cnt, Ctx& c) {
+__device__ __forceinline__ void walk_prologue(const SceneView& sc, uint32_t* s_cnt, Ctx& c, const WalkArgs& wa) {
     if (threadIdx.x < 2u) s_cnt[threadIdx.x] = 0u;
     if constexpr (WALK == kWalkWideLds) { stage_wide_nodes(sc); c.nb = reinterpret_cast<const char*>(s_wide_nodes); }
-    else if constexpr (WALK < kWalkWide) c.lds_top = stage_top_nodes(sc, s_cnt);
+    else if constexpr (WALK < kWalkWide) { c.lds_top = stage_top_nodes(sc, s_cnt, wa.top_nodes); c.lds_n = wa.top_nodes; }
     __syncthreads();
+}
+// The workgroup's stack array and its shared words: dynamic LDS for the quad walks, a static array of kStack8 + 1 rows for the 8-wide ones.
+template <int WALK>
+__device__ __forceinline__ uint32_t* walk_stack(const WalkArgs& wa, uint32_t*& s_cnt) {
+    if constexpr (WALK < kWalkWide) { s_cnt = s_walk + wa.stack_rows * (uint32_t)kBlock; return s_walk; }
+    else {
+        __shared__ uint32_t s_stack[WalkLds<WALK>::kRows * kBlock];
+        s_cnt = &s_stack[WalkLds<WALK>::kMisc * kBlock];
+        return s_stack;
+    }
 }
 
 // G-buffer: one primary ray per pixel, coherent within the 8x8 tile (lane utilisation 96 %): plain thread-per-pixel launch.
 template <int WALK>
-__global__ void __launch_bounds__(kBlock) gbuffer_kernel(SceneView sc, FrameView fv) {
-    __shared__ uint32_t s_stack[WalkLds<WALK>::kRows * kBlock];
-    uint32_t* const s_cnt = &s_stack[WalkLds<WALK>::kMisc * kBlock];
+__global__ void __launch_bounds__(kBlock) gbuffer_kernel(SceneView sc, FrameView fv, WalkArgs wa) {
+    uint32_t* s_cnt;
+    uint32_t* const s_stack = walk_stack<WALK>(wa, s_cnt);
     typename CtxOf<WALK>::type c(sc, fv, &s_stack[threadIdx.x], (uint32_t)kBlock);
-    walk_prologue<WALK>(sc, s_cnt, c);
+    walk_prologue<WALK>(sc, s_cnt, c, wa);
     uint32_t px, py;
     bool active = tile_pixel(fv, px, py);
     if (active) gbuffer_pixel(c, px, py);
@@ -160,13 +172,13 @@ __device__ __forceinline__ bool run_segment_and_park(Ctx& c, LoopState& s, uint3
 }
 
 template <int STAGE, int WALK>
-__global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, FrameView fv, ContQueue q, uint32_t cut, uint32_t* zero_counts, bool wg_park) {
+__global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, FrameView fv, ContQueue q, uint32_t cut, uint32_t* zero_counts, bool wg_park, WalkArgs wa) {
     constexpr int THREADS = kBlock;
-    __shared__ uint32_t s_stack[WalkLds<WALK>::kRows * THREADS];
-    uint32_t* const s_cnt = &s_stack[WalkLds<WALK>::kMisc * THREADS];
+    uint32_t* s_cnt;
+    uint32_t* const s_stack = walk_stack<WALK>(wa, s_cnt);
     uint32_t* const s_tmp = s_cnt + 8;
     typename CtxOf<WALK>::type c(sc, fv, &s_stack[threadIdx.x], (uint32_t)THREADS);
-    walk_prologue<WALK>(sc, s_cnt, c);
+    walk_prologue<WALK>(sc, s_cnt, c, wa);
     constexpr int VARIANT = STAGE == 1 ? 0 : 1;
     // the queue counters this stage's NEXT launch will use (the other set of the pair) are cleared here instead of by a memset
     if (zero_counts && blockIdx.x == 0u && blockIdx.y == 0u && threadIdx.x <= (uint32_t)kMaxCuts) zero_counts[threadIdx.x] = 0u;
@@ -210,10 +222,10 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, 
 
 // Resumes parked paths for bounces [d0, d1); survivors are parked again in `qout` (d1 < MAX_DEPTH) or finished here.
 template <int STAGE, int WALK>
-__global__ void __launch_bounds__(kBlock, FRT_WAVES) continue_kernel(SceneView sc, FrameView fv, ContQueue qin, ContQueue qout, uint32_t d0, uint32_t d1) {
+__global__ void __launch_bounds__(kBlock, FRT_WAVES) continue_kernel(SceneView sc, FrameView fv, ContQueue qin, ContQueue qout, uint32_t d0, uint32_t d1, WalkArgs wa) {
     constexpr int THREADS = kBlock;
-    __shared__ uint32_t s_stack[WalkLds<WALK>::kRows * THREADS];
-    uint32_t* const s_cnt = &s_stack[WalkLds<WALK>::kMisc * THREADS];
+    uint32_t* s_cnt;
+    uint32_t* const s_stack = walk_stack<WALK>(wa, s_cnt);
     const uint32_t filled = *qin.count;
     const uint32_t n = filled < qin.capacity ? filled : qin.capacity;
     // The launch that parked these paths ran out of slots (its counter ran past the capacity; the surplus paths were finished in place): tell the
@@ -226,7 +238,7 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) continue_kernel(SceneView s
     if (blockIdx.x * (uint32_t)THREADS >= n) return;   // uniform per workgroup
     constexpr int VARIANT = STAGE == 1 ? 0 : 1;
     typename CtxOf<WALK>::type c(sc, fv, &s_stack[threadIdx.x], (uint32_t)THREADS);
-    walk_prologue<WALK>(sc, s_cnt, c);
+    walk_prologue<WALK>(sc, s_cnt, c, wa);
     uint32_t cnt_closest = 0u, cnt_any = 0u;
     // stride loop: one trip with the grid of launch_trace_continuations; uniform per workgroup for any grid
     for (uint32_t base = blockIdx.x * (uint32_t)THREADS; base < n; base += gridDim.x * (uint32_t)THREADS) {
@@ -335,13 +347,14 @@ static ContQueue queue_of(const TraceLaunch& L, uint32_t k) {
 }
 static uint32_t first_cut(const TraceLaunch& L, const FrameView& fv) { return L.ncuts ? L.cuts[0] : fv.max_depth; }
 
-hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t walk) {
+hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t wg_rows, uint32_t walk) {
     if (empty_rows(fv)) return hipSuccess;
 #if FRT_EXPERIMENTS
-    if (walk == (uint32_t)kWalkWide || walk == (uint32_t)kWalkWideLds) { hipLaunchKernelGGL(gbuffer_kernel<kWalkWide>, grid_for(fv), dim3(kBlock), 0, stream, sc, fv); return hipGetLastError(); }
+    if (walk == (uint32_t)kWalkWide || walk == (uint32_t)kWalkWideLds) { hipLaunchKernelGGL(gbuffer_kernel<kWalkWide>, grid_for(fv), dim3(kBlock), 0, stream, sc, fv, WalkArgs{0u, 0u}); return hipGetLastError(); }
 #endif
     (void)walk;
-    hipLaunchKernelGGL(gbuffer_kernel<kWalkQuad>, grid_for(fv), dim3(kBlock), 0, stream, sc, fv);
+    const WalkLdsPlan p = walk_lds_plan(wg_rows, sc.num_nodes4, gbuffer_lds_budget(wg_rows));
+    hipLaunchKernelGGL(gbuffer_kernel<kWalkQuad>, grid_for(fv), dim3(kBlock), p.bytes, stream, sc, fv, WalkArgs{p.stack_rows, p.top_nodes});
     return hipGetLastError();
 }
 hipError_t launch_post(const FrameView& fv, hipStream_t stream) {
@@ -370,7 +383,9 @@ hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& 
 #if FRT_EXPERIMENTS
     if (L.resident) return exp_launch_resident_pixels(stage, sc, fv, stream, L);
 #endif
-    auto go = [&](auto kernel, uint32_t lds = 0u) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, 0), first_cut(L, fv), L.zero_counts, L.wg_park); };
+    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
+    const WalkArgs wa{plan.stack_rows, plan.top_nodes};
+    auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, 0), first_cut(L, fv), L.zero_counts, L.wg_park, wa); };
 #if FRT_EXPERIMENTS
     if (L.walk == (uint32_t)kWalkQuadWg) {      // collective walks: dynamic LDS = stack rows + exchange rows
         const uint32_t lds = (L.wg_rows + (uint32_t)kXRows) * (uint32_t)kBlock * 4u;
@@ -380,10 +395,10 @@ hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& 
         return hipGetLastError();
     }
     if (L.walk == (uint32_t)kWalkWideLds) { if (stage == 1) go(pixel_kernel<1, kWalkWideLds>, L.wide_lds_bytes); else go(pixel_kernel<2, kWalkWideLds>, L.wide_lds_bytes); return hipGetLastError(); }
-    if (L.walk == (uint32_t)kWalkWide) { if (stage == 1) go(pixel_kernel<1, kWalkWide>); else go(pixel_kernel<2, kWalkWide>); return hipGetLastError(); }
+    if (L.walk == (uint32_t)kWalkWide) { if (stage == 1) go(pixel_kernel<1, kWalkWide>, 0u); else go(pixel_kernel<2, kWalkWide>, 0u); return hipGetLastError(); }
 #endif
-    if (stage == 1) { if (L.vote) go(pixel_kernel<1, 1>); else go(pixel_kernel<1, 0>); }
-    else { if (L.vote) go(pixel_kernel<2, 1>); else go(pixel_kernel<2, 0>); }
+    if (stage == 1) { if (L.vote) go(pixel_kernel<1, 1>, plan.bytes); else go(pixel_kernel<1, 0>, plan.bytes); }
+    else { if (L.vote) go(pixel_kernel<2, 1>, plan.bytes); else go(pixel_kernel<2, 0>, plan.bytes); }
     return hipGetLastError();
 }
 bool trace_has_continuations(const TraceLaunch& L, uint32_t max_depth) { return L.ncuts > 0 && L.cuts[0] < max_depth; }
@@ -394,11 +409,13 @@ hipError_t launch_trace_continuations(int stage, const SceneView& sc, const Fram
 #if FRT_EXPERIMENTS
     { hipError_t e_; if (exp_launch_continuations(stage, sc, fv, stream, L, e_)) return e_; }      // wavefront / stream / refill / resident forms
 #endif
+    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
+    const WalkArgs wa{plan.stack_rows, plan.top_nodes};
     for (uint32_t k = 0; k < L.ncuts && L.cuts[k] < fv.max_depth; ++k) {
         const uint32_t gslots = std::max(queue_of(L, k).capacity, L.grid_min_slots);   // (workgroups beyond the queue's fill retire at once)
         const dim3 cgrid((gslots + (uint32_t)kBlock - 1u) / (uint32_t)kBlock);
         const uint32_t d0 = L.cuts[k], d1 = (k + 1 < L.ncuts && L.cuts[k + 1] < fv.max_depth) ? L.cuts[k + 1] : fv.max_depth;
-        auto go = [&](auto kernel, uint32_t lds = 0u) { hipLaunchKernelGGL(kernel, cgrid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, k), queue_of(L, k + 1), d0, d1); };
+        auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, cgrid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, k), queue_of(L, k + 1), d0, d1, wa); };
 #if FRT_EXPERIMENTS
         if (L.walk == (uint32_t)kWalkQuadWg) {
             const uint32_t lds = (L.wg_rows + (uint32_t)kXRows) * (uint32_t)kBlock * 4u;
@@ -408,10 +425,10 @@ hipError_t launch_trace_continuations(int stage, const SceneView& sc, const Fram
             continue;
         }
         if (L.walk == (uint32_t)kWalkWideLds) { if (stage == 1) go(continue_kernel<1, kWalkWideLds>, L.wide_lds_bytes); else go(continue_kernel<2, kWalkWideLds>, L.wide_lds_bytes); continue; }
-        if (L.walk == (uint32_t)kWalkWide) { if (stage == 1) go(continue_kernel<1, kWalkWide>); else go(continue_kernel<2, kWalkWide>); continue; }
+        if (L.walk == (uint32_t)kWalkWide) { if (stage == 1) go(continue_kernel<1, kWalkWide>, 0u); else go(continue_kernel<2, kWalkWide>, 0u); continue; }
 #endif
-        if (stage == 1) { if (L.vote) go(continue_kernel<1, 1>); else go(continue_kernel<1, 0>); }
-        else { if (L.vote) go(continue_kernel<2, 1>); else go(continue_kernel<2, 0>); }
+        if (stage == 1) { if (L.vote) go(continue_kernel<1, 1>, plan.bytes); else go(continue_kernel<1, 0>, plan.bytes); }
+        else { if (L.vote) go(continue_kernel<2, 1>, plan.bytes); else go(continue_kernel<2, 0>, plan.bytes); }
     }
     return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // frt_kernels.hpp — host-callable launch entry points of frt_kernels.hip.
 #pragma once
 #include "frt_mono.hpp"
+#include <algorithm>
 
 namespace frt {
 // How to launch a traced stage (1 = T-trace, 2 = spatial + shade): pixel kernel cut at cuts[0] + one continuation launch per further
@@ -21,7 +22,7 @@ struct TraceLaunch {
     bool vote;      // the kernels whose BVH walk votes for its next step (frt_trace.hpp: trace4<ANY, VOTE>): scenes with a deep tree
     uint32_t walk;  // which tree the traced kernels walk: kWalkQuad (trace4; `vote` picks its loop), kWalkWide (trace8, nodes read from HBM), kWalkWideLds (trace8, the whole 8-wide tree copied into every workgroup's LDS: wide_lds_bytes of dynamic LDS)
     uint32_t wide_lds_bytes;
-    uint32_t wg_rows;   // kWalkQuadWg: stack rows of a workgroup's dynamic LDS (the quad tree's stack need + the shared row)
+    uint32_t wg_rows;   // rows of a quad-walk workgroup's dynamic LDS: the quad tree's stack need + the shared row (walk_lds_plan below; kWalkQuadWg adds its exchange rows)
 #if FRT_EXPERIMENTS
     // lib/libfrt_exp.so only (csrc/experiments/frt_experiment_kernels.hpp): the measured-and-not-kept kernel designs
     uint32_t* tile_state;   // the stage's sweep-direction state (TileOrder) or null = tile rows top to bottom
@@ -32,18 +33,50 @@ struct TraceLaunch {
     uint32_t* work;   // 2 x (1 + kMaxCuts) words: {next, ticket} of the pixel launch, then of each continuation launch; zero between launches
 #endif
 };
-// The top of the quad tree — nodes 0 .. kLdsTopNodes - 1: the root and, numbered breadth-first, its children — copied into the workgroup's LDS, in the
-// row of the stack array that no stack entry reaches (behind the shared words): the first two node steps of every walk read it there (frt_trace.hpp:
-// trace4). Call before the workgroup's first barrier; null for a tree too small to have those nodes.
+// The top of the quad tree — nodes 0 .. n - 1; the tree is numbered breadth-first — copied into the workgroup's LDS behind the shared words of the row
+// that follows the stack rows, 16 bytes per lane and coalesced. The
+// node steps of a walk whose whole wave is among these nodes read them there. Call before the workgroup's first barrier; null for n = 0.
+// Without `n`: the five nodes that fit the shared row itself (the ray-query kernels), none for a smaller tree.
+static constexpr uint32_t kLdsSharedWords = 32u;      // words of the shared row in front of the node copy (ray-count sums, reservation scratch): 128 bytes
+__device__ __forceinline__ const uint32_t* stage_top_nodes(const SceneView& sc, uint32_t* s_cnt, uint32_t n) {
+    uint4* const s_top = reinterpret_cast<uint4*>(s_cnt + kLdsSharedWords);      // (128-byte aligned)
+    if (n == 0u) return nullptr;
+    const uint4* const src = reinterpret_cast<const uint4*>(sc.nodes4);
+    for (uint32_t i = threadIdx.x; i < n * 8u; i += blockDim.x) s_top[i] = src[i];
+    return reinterpret_cast<const uint32_t*>(s_top);
+}
 __device__ __forceinline__ const uint32_t* stage_top_nodes(const SceneView& sc, uint32_t* s_cnt) {
-    uint32_t* const s_top = s_cnt + 32;      // (128-byte aligned)
-    if (sc.num_nodes4 < (uint32_t)kLdsTopNodes) return nullptr;
-    if (threadIdx.x < (uint32_t)kLdsTopNodes * 32u) s_top[threadIdx.x] = reinterpret_cast<const uint32_t*>(sc.nodes4)[threadIdx.x];
-    return s_top;
+    return stage_top_nodes(sc, s_cnt, sc.num_nodes4 < (uint32_t)kLdsTopNodes ? 0u : (uint32_t)kLdsTopNodes);
+}
+// LDS of a workgroup of the quad-walk frame kernels (dynamic, sized per launch): one 1 KiB row per stack entry the tree needs, the shared words, then
+// the node copy — as many of the tree's first nodes as `budget` bytes leave room for, never fewer than the kLdsTopNodes (or the whole tree) that
+// the shared row itself would hold. `bytes` is rounded up to the hardware's allocation granule.
+struct WalkLdsPlan { uint32_t stack_rows, top_nodes, bytes; };
+static constexpr uint32_t kLdsGranule = 512u;                   // LDS is allocated in 128-dword granules (the kernel descriptor's granulated size field)
+static constexpr uint32_t kLdsPerCu = 160u * 1024u;
+static constexpr uint32_t kLdsTracedBudget = kLdsPerCu / 4u;    // four workgroups per CU: the traced kernels' 128 VGPRs allow no more
+#ifndef FRT_LDS_TOP_MAX
+#define FRT_LDS_TOP_MAX 0xFFFFFFFFu      // (A/B builds only: a cap on the cached nodes)
+#endif
+// The G-buffer kernel's registers allow six and more waves per SIMD: its budget is the smallest share of a CU's LDS (a sixth, a fifth, a quarter,
+// in whole granules) that holds the stack rows and the shared row.
+inline uint32_t gbuffer_lds_budget(uint32_t wg_rows) {
+    const uint32_t least = (wg_rows < 2u ? 2u : wg_rows) * 1024u;
+    for (uint32_t wgs = 6u; wgs > 4u; --wgs) { const uint32_t b = kLdsPerCu / wgs / kLdsGranule * kLdsGranule; if (b >= least) return b; }
+    return kLdsTracedBudget;
+}
+inline WalkLdsPlan walk_lds_plan(uint32_t wg_rows, uint32_t num_nodes4, uint32_t budget) {
+    WalkLdsPlan p;
+    p.stack_rows = wg_rows < 2u ? 1u : wg_rows - 1u;      // (wg_rows = stack need + 1; a one-node tree still gets a row to point at)
+    const uint32_t fixed = p.stack_rows * 1024u + kLdsSharedWords * 4u;
+    const uint32_t room = budget > fixed ? (budget - fixed) / 128u : 0u;
+    p.top_nodes = std::min(std::min(num_nodes4, (uint32_t)FRT_LDS_TOP_MAX), std::max(room, (uint32_t)kLdsTopNodes));
+    p.bytes = (std::max(fixed + p.top_nodes * 128u, (p.stack_rows + 1u) * 1024u) + kLdsGranule - 1u) / kLdsGranule * kLdsGranule;
+    return p;
 }
 
 // All launches are asynchronous on `stream` and cover rows [fv.y0, fv.y1).
-hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t walk = kWalkQuad);      // walk: kWalkQuad or kWalkWide (primary rays are coherent: their nodes stay in HBM / L1)
+hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t wg_rows, uint32_t walk = kWalkQuad);      // wg_rows: TraceLaunch::wg_rows; walk: kWalkQuad or kWalkWide (primary rays are coherent: their nodes stay in HBM / L1)
 hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream, const TraceLaunch& L);
 bool trace_has_continuations(const TraceLaunch& L, uint32_t max_depth);
 hipError_t launch_trace_continuations(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream, const TraceLaunch& L);

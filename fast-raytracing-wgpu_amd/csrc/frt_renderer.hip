@@ -561,7 +561,7 @@ static int launch_g_and_trace(frt_renderer* r, FrameView fv, hipStream_t q, bool
         fv.ray_counters = r->d_counters + (pending ? C_PENDING + 4 * pending_set : C_STAGE);
         frt_renderer::Timed t{};
         if (timed) { int rc = timer_begin(r, t, 0, q); if (rc) return rc; }
-        HIP_TRY(launch_gbuffer(r->sv, fv, q, r->walk == kWalkQuadWg ? (uint32_t)kWalkQuad : r->walk));      // (primary rays are coherent: plain walks)
+        HIP_TRY(launch_gbuffer(r->sv, fv, q, r->wg_rows, r->walk == kWalkQuadWg ? (uint32_t)kWalkQuad : r->walk));      // (primary rays are coherent: plain walks)
         if (timed) { int rc = timer_end(r, t, q); if (rc) return rc; }
         r->stats.launches[0] += 1;
     }

@@ -52,7 +52,8 @@ struct PathCtx {
     const SceneView& sc;
     const FrameView& fv;
     uint32_t* stk; uint32_t stride;
-    const uint32_t* lds_top = nullptr;   // the workgroup's LDS copy of quad nodes 0 .. 4 (frt_kernels.hip: stage_top_nodes), or null: trace4 then reads them like any node
+    const uint32_t* lds_top = nullptr;   // the workgroup's LDS copy of quad nodes 0 .. lds_n - 1 (frt_kernels.hpp: stage_top_nodes), or null: trace4 then reads them like any node
+    uint32_t lds_n = (uint32_t)kLdsTopNodes;
     uint32_t rng;               // var<private> rng_seed, restir.wgsl:130
     uint32_t n_closest, n_any;  // rays issued by this lane
     FRT_HD PathCtx(const SceneView& s, const FrameView& f, uint32_t* st, uint32_t sd) : sc(s), fv(f), stk(st), stride(sd), rng(0), n_closest(0), n_any(0) {}
@@ -69,9 +70,9 @@ struct PathCtx {
     template <bool ANY, bool VOTE>
     FRT_HD void walk(f3 o, f3 d, float tmin, float tmax, HitRec& h) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        if (FRT_DBG_TWICE & (ANY ? 2 : 1)) { HitRec h2; f3 o2 = o; asm volatile("" : "+v"(o2.x)); trace4<ANY, VOTE>(sc, o2, d, tmin, tmax, stk, stride, h2, lds_top); asm volatile("" :: "v"(h2.t), "v"(h2.tri)); }
+        if (FRT_DBG_TWICE & (ANY ? 2 : 1)) { HitRec h2; f3 o2 = o; asm volatile("" : "+v"(o2.x)); trace4<ANY, VOTE>(sc, o2, d, tmin, tmax, stk, stride, h2, lds_top, lds_n); asm volatile("" :: "v"(h2.t), "v"(h2.tri)); }
 #endif
-        trace4<ANY, VOTE>(sc, o, d, tmin, tmax, stk, stride, h, lds_top);
+        trace4<ANY, VOTE>(sc, o, d, tmin, tmax, stk, stride, h, lds_top, lds_n);
     }
     FRT_HD void closest(f3 o, f3 d, float tmin, float tmax, HitRec& h) { n_closest++; walk<false, false>(o, d, tmin, tmax, h); }
     FRT_HD bool any(f3 o, f3 d, float tmin, float tmax) { HitRec h; n_any++; walk<true, false>(o, d, tmin, tmax, h); return h.tri != 0xFFFFFFFFu; }

@@ -13,7 +13,7 @@
 
 namespace frt {
 
-static const int kLdsTopNodes = 5;      // quad nodes 0 .. 4 (the root and, numbered breadth-first, its children) are copied into a workgroup's LDS (trace4)
+static const int kLdsTopNodes = 5;      // the least of a quad tree's top that a workgroup's LDS holds (trace4): nodes 0 .. 4, the root and, numbered breadth-first, its children — what fits the shared row
 #ifndef FRT_STACK
 #define FRT_STACK 32      // (A/B builds only: a shallower LDS stack for scenes whose quad tree needs no more)
 #endif
@@ -231,8 +231,23 @@ FRT_HD uint32_t wave_count(bool b) {      // lanes of the wave for which b holds
     return b ? 1u : 0u;
 #endif
 }
+// LDS copy of the tree's top (frt_kernels.hpp: stage_top_nodes): quad nodes 0 .. lds_n - 1 — the tree is numbered breadth-first, so these are its upper
+// levels — sit in the workgroup's LDS behind the stack rows, `lds_n` chosen per launch from what the stack rows leave of the workgroup's LDS budget.
+// A node step reads its node there when EVERY lane of the wave that takes the step holds a node < lds_n (one wave-uniform test per trip, never a per-lane
+// choice: a mixed trip would issue both load groups, and a 16-byte vector load holds the L1 for its 16 cycles whatever the lane count), so such a
+// step leaves the L1 alone. Two forms of the test (profiles/r9_experiments/lds_top.md):
+//   leading    only the first steps of a walk, while every lane is still up there (the VOTE walk);
+//   re-entrant any step of the walk, also after a pop has brought the whole wave back to the top (the while-while walk).
+// Same hits either way: a node's bytes are the same wherever they are read (hit semantics at the top of this file).
+// A cached node is laid out as in HBM. (Rotating each node's eight 16-byte words against LDS bank conflicts — lanes on different nodes read the same word
+// of nodes 128 bytes apart, two 16-byte bank groups of the LDS's sixteen — was built and measured at nothing on the Cornell Box, whose walks stay among
+// some twenty nodes: profiles/r9_experiments/lds_top.md.)
+#ifndef FRT_LDS_REENTRANT
+#define FRT_LDS_REENTRANT 1   // (A/B builds only: 0 = the leading form in every walk)
+#endif
 template <bool ANY, bool VOTE = false>
-FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint32_t* stk, uint32_t stride, HitRec& hit, const uint32_t* lds_top = nullptr) {
+FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint32_t* stk, uint32_t stride, HitRec& hit, const uint32_t* lds_top = nullptr,
+                   uint32_t lds_n = (uint32_t)kLdsTopNodes) {
     hit.t = tmax; hit.tri = 0xFFFFFFFFu; hit.u = 0.0f; hit.v = 0.0f; hit.inst = 0u; hit.front = false;
     float best_det = 0.0f;
     f3 inv = mk3(prune_rcp(d.x), prune_rcp(d.y), prune_rcp(d.z));
@@ -250,57 +265,43 @@ FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint
         const uint32_t nn = wave_count(at_node), nl = wave_count(!at_node && cur != kDone);
         return nn != 0u && nn >= nl;
     };
-#if defined(__HIP_DEVICE_COMPILE__)
-    // The first steps of every walk — the root, then one of its children (quad nodes 1 .. 4: the tree is numbered breadth-first) — read their node from
-    // the workgroup's LDS copy of nodes 0 .. 4 while EVERY lane of the wave is still up there (wave-uniform test): two of a walk's ten node steps
-    // leave the L1 alone and see the LDS's latency instead: Cornell Box 1.560 -> 1.537 ms per frame (8 more VGPRs, still four waves per SIMD).
-    if (lds_top) {
-        while (__ballot(cur >= (uint32_t)kLdsTopNodes) == 0ull) {
-            const uint32_t noff = cur << 7;
-            const char* nb = reinterpret_cast<const char*>(lds_top);
-            const float4 rf = *reinterpret_cast<const float4*>(nb + (noff + 96u));
-            float t[4]; bool h[4];
-            slab4(nb, noff | sx, noff | sy, noff | sz, inv, oinv, tmin, ANY ? tmax : hit.t, t, h);
-            uint32_t r[4] = {f2u(rf.x), f2u(rf.y), f2u(rf.z), f2u(rf.w)};
-            float k[4];
+    // One node step: the node's four boxes behind `nb` (the HBM array or the LDS copy; byte offsets of the reference word and of this lane's near planes
+    // on each axis) tested against the ray, the hit children sorted near to far, the nearest entered and the others stacked.
+    auto node_step = [&](const char* nb, uint32_t oref, uint32_t ox, uint32_t oy, uint32_t oz) {
+        const float4 rf = *reinterpret_cast<const float4*>(nb + oref);
+        float t[4]; bool h[4];
+        slab4(nb, ox, oy, oz, inv, oinv, tmin, ANY ? tmax : hit.t, t, h);
+        uint32_t r[4] = {f2u(rf.x), f2u(rf.y), f2u(rf.z), f2u(rf.w)};
+        // (an empty slot holds a far-away degenerate box: it never passes the slab test, no reference check needed)
+        float k[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) k[c] = h[c] ? t[c] : kFar;
+        for (int c = 0; c < 4; ++c) k[c] = h[c] ? t[c] : kFar;
 #define FRT_CE(a, b) { const bool s_ = k[b] < k[a]; const float ka_ = s_ ? k[b] : k[a], kb_ = s_ ? k[a] : k[b]; \
                        const uint32_t ra_ = s_ ? r[b] : r[a], rb_ = s_ ? r[a] : r[b]; k[a] = ka_; k[b] = kb_; r[a] = ra_; r[b] = rb_; }
-            FRT_CE(0, 1) FRT_CE(2, 3) FRT_CE(0, 2) FRT_CE(1, 3) FRT_CE(1, 2)
+        FRT_CE(0, 1) FRT_CE(2, 3) FRT_CE(0, 2) FRT_CE(1, 3) FRT_CE(1, 2)
 #undef FRT_CE
-            if (k[3] < kFar) { *top = r[3]; top += stride; }
-            if (k[2] < kFar) { *top = r[2]; top += stride; }
-            if (k[1] < kFar) { *top = r[1]; top += stride; }
-            if (k[0] < kFar) cur = r[0];
-            else if (top == stk) cur = kDone;
-            else { top -= stride; cur = *top; }
-        }
+        if (k[3] < kFar) { *top = r[3]; top += stride; }
+        if (k[2] < kFar) { *top = r[2]; top += stride; }
+        if (k[1] < kFar) { *top = r[1]; top += stride; }
+        if (k[0] < kFar) cur = r[0];
+        else if (top == stk) cur = kDone;
+        else { top -= stride; cur = *top; }
+    };
+    const char* const nb4 = reinterpret_cast<const char*>(sc.nodes4);
+    auto step_at = [&](const char* nb) { const uint32_t noff = cur << 7; node_step(nb, noff + 96u, noff | sx, noff | sy, noff | sz); };
+    const char* const nbl = reinterpret_cast<const char*>(lds_top);
+    constexpr bool kReentrant = FRT_LDS_REENTRANT && !VOTE;
+    // Leading form: the first steps of every walk — the root, then its children, ... — while EVERY lane of the wave is still among the cached nodes
+    // (five cached nodes, two of a walk's ten node steps: Cornell Box 1.560 -> 1.537 ms per frame, 8 more VGPRs, still four waves per SIMD).
+    if (!kReentrant && lds_top) {
+        while (wave_count(cur >= lds_n) == 0u) step_at(nbl);
     }
-#endif
     for (;;) {
         while (node_phase()) {
             if (VOTE && (cur & 0x80000000u)) continue;      // this lane holds a leaf (or is done): it sits the node step out
-            const uint32_t noff = cur << 7;
-            const char* nb = reinterpret_cast<const char*>(sc.nodes4);
-            const float4 rf = *reinterpret_cast<const float4*>(nb + (noff + 96u));
-            float t[4]; bool h[4];
-            slab4(nb, noff | sx, noff | sy, noff | sz, inv, oinv, tmin, ANY ? tmax : hit.t, t, h);
-            uint32_t r[4] = {f2u(rf.x), f2u(rf.y), f2u(rf.z), f2u(rf.w)};
-            // (an empty slot holds a far-away degenerate box: it never passes the slab test, no reference check needed)
-            float k[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) k[c] = h[c] ? t[c] : kFar;
-#define FRT_CE(a, b) { const bool s_ = k[b] < k[a]; const float ka_ = s_ ? k[b] : k[a], kb_ = s_ ? k[a] : k[b]; \
-                       const uint32_t ra_ = s_ ? r[b] : r[a], rb_ = s_ ? r[a] : r[b]; k[a] = ka_; k[b] = kb_; r[a] = ra_; r[b] = rb_; }
-            FRT_CE(0, 1) FRT_CE(2, 3) FRT_CE(0, 2) FRT_CE(1, 3) FRT_CE(1, 2)
-#undef FRT_CE
-            if (k[3] < kFar) { *top = r[3]; top += stride; }
-            if (k[2] < kFar) { *top = r[2]; top += stride; }
-            if (k[1] < kFar) { *top = r[1]; top += stride; }
-            if (k[0] < kFar) cur = r[0];
-            else if (top == stk) cur = kDone;
-            else { top -= stride; cur = *top; }
+            // re-entrant form: only lanes that hold a node are active here, so the count is over exactly the lanes that take this step
+            if (kReentrant && lds_top && wave_count(cur >= lds_n) == 0u) { step_at(nbl); continue; }
+            step_at(nb4);
         }
         if (cur == kDone) break;
         if (VOTE && !(cur & 0x80000000u)) continue;      // this lane still holds a node: it sits the leaf step out

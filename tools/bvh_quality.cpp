@@ -171,7 +171,13 @@ struct Lane {
         pop();
     }
 };
-struct WaveCost { uint64_t checksum = 0, rays = 0, lane_nodes = 0, lane_tris = 0, wave_rays = 0, wave_nodes = 0, wave_leaves = 0, wave_tri_tests = 0, max_lane_nodes = 0; };
+// LDS copy of the tree's top (frt_trace.hpp: trace4, nodes 0 .. N - 1 of the breadth-first numbering): wave-level node steps in which EVERY lane that
+// takes the step holds a node < N, for the cache sizes g_topn — top_lead: only the leading steps of a walk (the count stops at the walk's first
+// step that is not covered, or at its first leaf step); top_re: any step, tested per trip (the re-entrant form).
+static const int kTopN = 4;
+static uint32_t g_topn[kTopN] = {0, 0, 0, 0};      // (argv[14] = the largest N switches the report on)
+struct WaveCost { uint64_t checksum = 0, rays = 0, lane_nodes = 0, lane_tris = 0, wave_rays = 0, wave_nodes = 0, wave_leaves = 0, wave_tri_tests = 0, max_lane_nodes = 0;
+                  uint64_t top_lead[kTopN] = {0, 0, 0, 0}, top_re[kTopN] = {0, 0, 0, 0}; };
 static uint32_t leaf_count(uint32_t ref) { return (ref >> 24) & 0x7F; }
 static int g_policy = 0;      // 0: while-while (trace4); 1: majority (the step more lanes wait for); 2: leaf step as soon as fewer than g_thresh lanes hold a node
 static int g_thresh = 16;
@@ -181,17 +187,27 @@ static void run_wave(const Tree& T, std::vector<Lane>& L, const std::vector<char
     if (!anyact) return;
     ++w.wave_rays;
     if (g_policy == 0) {
+        bool leading[kTopN] = {true, true, true, true};
         for (;;) {
             for (;;) {
                 bool stepped = false;
-                for (auto& l : L) if (l.at_node()) { l.node_step(T); stepped = true; }
+                uint32_t deepest = 0;      // the largest node index among the lanes that take this step
+                for (auto& l : L) if (l.at_node()) { deepest = std::max(deepest, l.cur); stepped = true; }
                 if (!stepped) break;
+                for (int k = 0; k < kTopN; ++k) {
+                    const bool in = deepest < g_topn[k];
+                    if (in) ++w.top_re[k];
+                    leading[k] = leading[k] && in;
+                    if (leading[k]) ++w.top_lead[k];
+                }
+                for (auto& l : L) if (l.at_node()) l.node_step(T);
                 ++w.wave_nodes;
             }
             bool leaf = false; uint32_t mc = 0;
             for (auto& l : L) if (l.at_leaf()) { mc = std::max(mc, leaf_count(l.cur)); l.leaf_step(T); leaf = true; }
             if (!leaf) break;
             ++w.wave_leaves; w.wave_tri_tests += mc;
+            for (int k = 0; k < kTopN; ++k) leading[k] = false;      // (trace4's leading loop ends for good when the first lane holds a leaf)
         }
     } else {
         for (;;) {
@@ -517,6 +533,11 @@ static void report(const char* name, const WaveCost& w) {
            (double)w.wave_leaves / w.wave_rays, (double)w.wave_tri_tests / w.wave_rays, (double)w.max_lane_nodes / w.wave_rays,
            (110.0 * w.wave_nodes + 20.0 * w.wave_leaves + 75.0 * w.wave_tri_tests) / w.wave_rays,
            (110.0 * w.wave_nodes + 20.0 * w.wave_leaves + 75.0 * w.wave_tri_tests) / w.rays * 64.0);      // VALU + SALU per step, from the ISA of trace4
+    if (g_topn[kTopN - 1] && w.wave_nodes) {
+        printf("  %-10s share of wave node steps read from an LDS copy of nodes 0 .. N-1:", "");
+        for (int k = 0; k < kTopN; ++k) printf("  N=%u leading %.3f re-entrant %.3f", g_topn[k], (double)w.top_lead[k] / w.wave_nodes, (double)w.top_re[k] / w.wave_nodes);
+        printf("\n");
+    }
 }
 
 int main(int argc, char** argv) {
@@ -545,6 +566,7 @@ int main(int argc, char** argv) {
     g_unified = argc > 11 ? atoi(argv[11]) : 0;
     g_precise = argc > 12 ? atoi(argv[12]) : 0;
     const int sort256 = argc > 13 ? atoi(argv[13]) : 0;
+    if (argc > 14 && atoi(argv[14]) > 0) { g_topn[0] = 5; g_topn[1] = 21; g_topn[2] = 85; g_topn[3] = (uint32_t)atoi(argv[14]); }
     // the 8-wide compressed tree as the product built it (csrc/frt_bvh8.hpp), decoded from its device form
     WideTree WT;
     {
@@ -717,7 +739,7 @@ int main(int argc, char** argv) {
     if (!g_chain) { WaveCost sum = shadow; sum.wave_nodes += bounce1.wave_nodes; sum.wave_leaves += bounce1.wave_leaves; sum.wave_tri_tests += bounce1.wave_tri_tests; sum.rays += bounce1.rays;
                     sum.lane_nodes += bounce1.lane_nodes; sum.lane_tris += bounce1.lane_tris; sum.max_lane_nodes += bounce1.max_lane_nodes; sum.wave_rays = bounce1.wave_rays; report("sh + b1", sum); }
     WaveCost all;
-    for (const WaveCost* w : {&shadow, &bounce1, &bounce2}) { all.rays += w->rays; all.lane_nodes += w->lane_nodes; all.lane_tris += w->lane_tris; all.wave_rays += w->wave_rays; all.wave_nodes += w->wave_nodes; all.wave_leaves += w->wave_leaves; all.wave_tri_tests += w->wave_tri_tests; all.max_lane_nodes += w->max_lane_nodes; }
+    for (const WaveCost* w : {&shadow, &bounce1, &bounce2}) { for (int k = 0; k < kTopN; ++k) { all.top_lead[k] += w->top_lead[k]; all.top_re[k] += w->top_re[k]; } all.rays += w->rays; all.lane_nodes += w->lane_nodes; all.lane_tris += w->lane_tris; all.wave_rays += w->wave_rays; all.wave_nodes += w->wave_nodes; all.wave_leaves += w->wave_leaves; all.wave_tri_tests += w->wave_tri_tests; all.max_lane_nodes += w->max_lane_nodes; }
     report("incoherent", all);
     // what the rays hit does not depend on the schedule, the helpers or the tree: occluded shadow rays + sum of (hit triangle id + 1) over the bounce rays
     printf("hits checksum %llu %llu %llu\n", (unsigned long long)shadow.checksum, (unsigned long long)bounce1.checksum, (unsigned long long)bounce2.checksum);
