@@ -26,7 +26,45 @@ struct DeformArgs {
     const float4* pos;                                // object-space positions of every mesh, xyzw (already the new ones)
     const float4* normals;                            // decoded normal of every vertex of the mesh (xyz, 0), or null: shading records stay
     const uint32_t* slot_of;                          // flattened triangle id -> triangle slot
+    const uint32_t* reject = nullptr;                 // a device-input call's flag word (DeformInput), or null: set, the kernel returns at once
 };
+
+// ---- Recomputed normals and device input ("Recomputed normals" and "Vertices from device memory") ----
+// All three kernels below: one thread per vertex or word, consecutive threads on consecutive elements, vector loads and stores, no LDS, nothing passed
+// between the blocks of a launch. They run on the renderer's main stream in this order, in front of mesh_deform_kernel; what one launch writes the
+// next reads behind the kernel boundary. Every destination is checked against the vertex pool's capacity before it is stored.
+
+// The normal pass (frt_vertex_normal.hpp: recomputed_vertex_normal, the host specification's own function). Thread v: vertex v of the mesh. It stores
+// the 8-byte encoded normal into SceneView::attributes unless the vertex keeps its normal, then decodes what the attribute now holds and stores that
+// into `block` (what mesh_deform_kernel reads as DeformArgs::normals) and, when there is one, into the pool of decoded normals.
+struct NormalArgs {
+    const uint32_t* adj_offsets;      // [nverts + 1]: the mesh's vertex -> corner adjacency (build_vertex_corners), cached per mesh by the renderer
+    const uint32_t* adj_corners;      // [nidx]
+    uint32_t nverts, nidx;
+    uint32_t index_offset, pos_offset, attr_offset;   // of the mesh in SceneView::indices, `pos`, SceneView::attributes
+    uint32_t cap_verts, cap_indices;                  // capacities of the vertex and index pools
+    const float4* pos;                // object-space positions of every mesh (already the new ones)
+    float4* block;                    // [nverts] decoded normals of this call
+    float4* pool_normals;             // PoolState::d_normals, or null
+    const uint32_t* reject;           // as DeformArgs::reject
+    // lib/libfrt_exp.so only (FRT_NORMALS_TRI_PASS=1), the design that was measured and not kept: a first launch, one thread per triangle, writes the
+    // triangle's normal here ([nidx / 3], call-owned scratch) and the vertex threads gather 16 bytes per corner instead of recomputing. Null in the product.
+    float4* tri_scratch = nullptr;
+};
+hipError_t launch_vertex_normals(const SceneView& sc, const NormalArgs& a, hipStream_t stream);
+
+// Device input: the caller's positions (and attributes) are device memory. `reject`: [0] the flag of this call, zeroed on the stream in front of the
+// validation launch; [1] the calls rejected so far. The validation launch (one thread per float4 of the input) raises the flag for a non-finite float;
+// the copy-in launch (one thread per vertex) returns at once when it is raised — its first thread then counts the rejection — and otherwise copies the
+// vertex into the pools and, when `block` is given (attributes without FRT_DEFORM_RECOMPUTE_NORMALS), decodes its normal as mesh_append_kernel does.
+struct DeformInput {
+    const float4* pos; const float4* attrs;           // the caller's: [nverts] and [2 nverts] (or null)
+    uint32_t nverts, pos_offset, attr_offset, cap_verts;
+    float4* out_pos; float4* out_attrs;               // the replica's pools
+    float4* block; float4* pool_normals;              // decoded normals, as NormalArgs (both may be null)
+    uint32_t* reject;
+};
+hipError_t launch_deform_input(const DeformInput& a, hipStream_t stream);      // zeroes the flag, validates, copies in
 
 // Words 0..23 of a shading record (frt_shade.hpp: fetch_hit_geometry), shared with frt_instance_edit.hip: a gather, no arithmetic.
 //   q0 (n0.xyz, uv0.x) q1 (n1.xyz, uv0.y) q2 (n2.xyz, uv1.x) q3 (t0.xyz, uv1.y) q4 (t1.xyz, uv2.x) q5 (t2.xyz, uv2.y); q6 = (tangent sign of corner 0, mat_id, 0, 0)

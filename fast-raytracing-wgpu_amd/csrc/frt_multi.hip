@@ -456,8 +456,12 @@ int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n
     return edit_every_replica(m, "multi set_instance_transforms", [&](frt_renderer* r) { return frt_renderer_set_instance_transforms(r, n, ids, m_colmajor16); });
 }
 // Every strip deforms its own replica (frt_renderer_set_mesh_vertices), as above.
+int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
+    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_vertices: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    return edit_every_replica(m, "multi set_mesh_vertices", [&](frt_renderer* r) { return frt_renderer_set_mesh_vertices_ex(r, mesh_id, pos4, attrs, nverts, flags); });
+}
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
-    return edit_every_replica(m, "multi set_mesh_vertices", [&](frt_renderer* r) { return frt_renderer_set_mesh_vertices(r, mesh_id, pos4, attrs, nverts); });
+    return frt_multi_renderer_set_mesh_vertices_ex(m, mesh_id, pos4, attrs, nverts, 0u);
 }
 // The material, light and texture edits on every strip's replica, as above.
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials) {

@@ -139,6 +139,14 @@ struct RefitState {
     std::vector<uint32_t> vert_count, attr_offset;
     std::vector<uint32_t> mesh_tris;       // per mesh: its triangles (what an added instance of it brings)
     Staging def;
+    // FRT_DEFORM_RECOMPUTE_NORMALS: per mesh its vertex -> corner adjacency on the device, [offsets: vert_count + 1 | corners: 3 mesh_tris] (null: not made
+    // yet; ensure_adjacency makes it at the mesh's first such call). Mesh-local numbers: a pool that moves or grows leaves it valid, remove_meshes renumbers it.
+    std::vector<const uint32_t*> adj;
+    // FRT_DEFORM_DEVICE: [0] the flag of the call in flight, [1] the calls rejected so far (frt_deform.hpp: DeformInput); made at the first such call.
+    uint32_t* d_reject = nullptr;
+#if FRT_EXPERIMENTS
+    OwnedBuf tri_normals;                  // lib/libfrt_exp.so, FRT_NORMALS_TRI_PASS=1: the scratch of the triangle pass (NormalArgs::tri_scratch)
+#endif
     uint32_t color_layers = 0, data_layers = 0;   // texture layers of the replica (the material and texture edits check against them)
 };
 

@@ -2,6 +2,7 @@
 // Mirrors src/geometry.rs, src/scene/{builder,material,scenes}.rs, src/camera.rs; matrix helpers follow glam 0.30.9
 // (Cargo.lock:876), f32 throughout.
 #include "frt_scene.hpp"
+#include "frt_vertex_normal.hpp"      // encode_vertex_normal, recomputed_vertex_normal: shared with the device
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -62,16 +63,9 @@ static void v3_normalize_glam(float v[3]) {   // Vec3::normalize = v * (1 / leng
 // ---------------------------------------------------------------------------------------------- geometry.rs
 namespace geometry {
 
-void encode_octahedral_normal(const float n[3], float out[2]) {   // geometry.rs:56-76
-    float l1 = fabsf(n[0]) + fabsf(n[1]) + fabsf(n[2]);
-    float rx = 0.0f, ry = 0.0f;
-    if (l1 > 0.0f) { rx = n[0] / l1; ry = n[1] / l1; }
-    if (n[2] < 0.0f) {
-        float fx = (1.0f - fabsf(ry)) * (rx >= 0.0f ? 1.0f : -1.0f);
-        float fy = (1.0f - fabsf(rx)) * (ry >= 0.0f ? 1.0f : -1.0f);
-        rx = fx; ry = fy;
-    }
-    out[0] = rx; out[1] = ry;
+void encode_octahedral_normal(const float n[3], float out[2]) {   // geometry.rs:56-76 (frt_vertex_normal.hpp: the same function runs on the device)
+    const f2 e = encode_vertex_normal(mk3(n[0], n[1], n[2]));
+    out[0] = e.x; out[1] = e.y;
 }
 
 static void push_vertex(Geometry& g, float x, float y, float z, const float nrm[3], float u, float v, const float tan[4]) {
@@ -394,15 +388,39 @@ std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs,
     return "";
 }
 
-int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, std::vector<uint32_t>& offsets, std::vector<uint32_t>& corners) {
+    offsets.assign((size_t)nverts + 1u, 0u);
+    corners.assign(nidx, 0u);
+    for (uint32_t c = 0; c < nidx; ++c) if (idx[c] < nverts) ++offsets[(size_t)idx[c] + 1u];
+    for (uint32_t v = 0; v < nverts; ++v) offsets[(size_t)v + 1u] += offsets[v];
+    std::vector<uint32_t> next(offsets.begin(), offsets.end() - 1);
+    for (uint32_t c = 0; c < nidx; ++c) if (idx[c] < nverts) corners[next[idx[c]]++] = c;      // ascending c per vertex: a counting sort is stable
+}
+
+int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
     if (!built) { error = "set_mesh_vertices: scene is not built"; return FRT_ERR_STATE; }
+    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_vertices: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_vertices_ex only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_vertices: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
     if (mesh_id >= mesh_positions.size()) { error = "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
     const std::string bad = check_mesh_vertices(pos4, attrs, nverts, (uint32_t)(mesh_positions[mesh_id].size() / 4));
     if (!bad.empty()) { error = "set_mesh_vertices: " + bad; return FRT_ERR_INVALID_ARG; }
+    const bool recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
     mesh_positions[mesh_id].assign(pos4, pos4 + (size_t)nverts * 4);
     if (attrs) std::copy(attrs, attrs + nverts, attributes.begin() + mesh_infos[mesh_id].vertex_offset);
     const float* P = mesh_positions[mesh_id].data();
     const uint32_t* idx = &indices[mesh_infos[mesh_id].index_offset];
+    if (recompute) {      // after the attributes of the call: uv and tangent are the caller's, the normal is the mesh's (a vertex that keeps its normal keeps the caller's)
+        struct P4 { float x, y, z, w; };
+        const uint32_t nidx = mesh_index_counts[mesh_id];
+        std::vector<uint32_t> off, corners;
+        build_vertex_corners(idx, nidx, nverts, off, corners);
+        for (uint32_t v = 0; v < nverts; ++v) {
+            f2 e;
+            if (!recomputed_vertex_normal(corners.data(), off[v], off[v + 1u], idx, nidx, reinterpret_cast<const P4*>(P), nverts, e)) continue;
+            frt_vertex_attr& a = attributes[(size_t)mesh_infos[mesh_id].vertex_offset + v];
+            a.normal[0] = e.x; a.normal[1] = e.y;
+        }
+    }
     for (InstanceRec& in : instances) {      // in instance order, under each instance's current matrix
         if (in.mesh_id != mesh_id) continue;
         for (uint32_t j = 0; j < in.tri_count; ++j) {
@@ -411,7 +429,7 @@ int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const f
             world_triangle(in.m, P, idx + 3 * j, t);
             TriSlot& o = tri_slots[tri_slot_of[id]];      // same slot, id and instance bits
             for (int r = 0; r < 3; ++r) { o.q[r] = t.v0[r]; o.q[4 + r] = t.e1[r]; o.q[8 + r] = t.e2[r]; }
-            if (attrs) write_shade_tri(id);
+            if (attrs || recompute) write_shade_tri(id);
         }
     }
     refit();

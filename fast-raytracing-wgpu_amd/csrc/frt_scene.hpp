@@ -99,7 +99,9 @@ public:
     // New vertices for one mesh of a built scene ("Deforming meshes"): the same topology, tree and leaf order; the triangles of
     // every instance of the mesh recomputed under its current matrix and, when `attrs` is given, their shading records as build() computes them;
     // every box refit. attrs == nullptr keeps the attributes and the shading records. The specification the device path matches bit for bit.
-    int set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+    // flags (include/frt.h): FRT_DEFORM_RECOMPUTE_NORMALS replaces the normal of every vertex by the normalised sum of the area-weighted normals of the
+    // triangles around it, in the new positions (frt_vertex_normal.hpp: recomputed_vertex_normal), and recomputes the shading records as if `attrs` had held it.
+    int set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags = 0);
     // What a built scene LOOKS like: no triangle, slot or box moves. Each is the specification its device form matches bit for bit,
     // validates everything before it applies anything, and leaves the scene equal to one built from scratch with the edited values.
     // Material ids[k] becomes mats[k], under the checks build() makes on a material (check_material).
@@ -189,6 +191,9 @@ std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const flo
 // Argument checks shared by the scene and the renderer form of set_mesh_vertices: "" when the vertices may be applied to a mesh of
 // `mesh_nverts` vertices (mesh_id < num_meshes is checked by the caller, which looks that count up).
 std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t mesh_nverts);
+// The vertex -> corner adjacency of one mesh in CSR form: corners[offsets[v] .. offsets[v + 1]) are the corners 3 * triangle + k whose index is v,
+// ascending. offsets has nverts + 1 entries, corners nidx (an index out of range, which the checks let into no mesh, names no vertex).
+void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, std::vector<uint32_t>& offsets, std::vector<uint32_t>& corners);
 // What build() and set_materials check on a material, whose texture layers and light index reach the kernels unchecked: "" when all five layers exist
 // (or are 0xFFFF) and light_index < num_lights (or is negative).
 std::string check_material(const frt_material& m, size_t color_layers, size_t data_layers, size_t num_lights);

@@ -95,10 +95,13 @@ int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* 
     const int rc = s->b.set_instance_transforms(n, ids, m_colmajor16);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
-int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null");
-    const int rc = s->b.set_mesh_vertices(mesh_id, pos4, attrs, nverts);
+    const int rc = s->b.set_mesh_vertices(mesh_id, pos4, attrs, nverts, flags);
     return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    return frt_scene_set_mesh_vertices_ex(s, mesh_id, pos4, attrs, nverts, 0u);
 }
 int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_materials: null");

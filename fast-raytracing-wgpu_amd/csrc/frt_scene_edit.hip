@@ -35,7 +35,7 @@ static std::vector<uint32_t> level_ranges(size_t n, Kids kids) {
 int frt::upload_refit_data(frt_renderer* r, const SceneBuilder& b) {
     RefitState& f = r->rf;
     std::vector<float> pos;
-    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear(); f.mesh_tris.clear();
+    f.pos_offset.clear(); f.index_offset.clear(); f.vert_count.clear(); f.attr_offset.clear(); f.mesh_tris.clear(); f.adj.clear();
     for (size_t m = 0; m < b.mesh_positions.size(); ++m) {
         f.pos_offset.push_back((uint32_t)(pos.size() / 4));
         f.index_offset.push_back(b.mesh_infos[m].index_offset);
@@ -321,15 +321,62 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
 }
 
 // ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
-// One pinned block holds what a call uploads: [positions | attributes | instance records | decoded normals]; the first two are copied into the replica
-// (the object-space positions the instance update reads, SceneView::attributes), the last two into the device block of RefitState::def, which is
-// reused in stream order and replaced, after a wait for the stream, only when it has to grow.
-int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+// The vertex -> corner adjacency of mesh `m` is on the device afterwards (RefitState::adj). Made once per mesh from the replica's own indices: a wait for
+// the stream and one read-back, as ensure_normals; frt_renderer_remove_meshes keeps the list in step with the mesh ids.
+static int ensure_adjacency(frt_renderer* r, uint32_t m) {
+    RefitState& f = r->rf;
+    if (f.adj.size() < f.mesh_tris.size()) f.adj.resize(f.mesh_tris.size(), nullptr);
+    if (f.adj[m]) return FRT_OK;
+    const uint32_t nidx = 3u * f.mesh_tris[m], nverts = f.vert_count[m];
+    std::vector<uint32_t> idx(nidx), off, corners;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (nidx) HIP_TRY(hipMemcpy(idx.data(), r->sv.indices + f.index_offset[m], (size_t)nidx * 4, hipMemcpyDeviceToHost));
+    build_vertex_corners(idx.data(), nidx, nverts, off, corners);
+    off.insert(off.end(), corners.begin(), corners.end());
+    void* d = nullptr;
+    if (const int rc = scene_alloc(r, off.size() * 4, &d)) return rc;
+    HIP_TRY(hipMemcpy(d, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    f.adj[m] = static_cast<const uint32_t*>(d);
+    return FRT_OK;
+}
+// Is `p` device memory of the renderer's device, 16-byte aligned, with `bytes` bytes of its allocation behind it? (What a kernel would otherwise find out by faulting.)
+static int check_device_pointer(const frt_renderer* r, const void* p, size_t bytes, const char* what) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + " are not device memory (FRT_DEFORM_DEVICE)"); }
+    if (at.type != hipMemoryTypeDevice || at.device != r->device)
+        return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + " are not memory of the renderer's device " + std::to_string(r->device) + " (FRT_DEFORM_DEVICE)");
+    if ((uintptr_t)p & 15u) return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": device pointers must be 16-byte aligned");
+    hipDeviceptr_t base = nullptr; size_t size = 0;      // the allocation around p holds `bytes` from p on
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": no device allocation holds the pointer"); }
+    const size_t before = (size_t)((const uint8_t*)p - (const uint8_t*)base);
+    if (before > size || size - before < bytes)
+        return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": the device allocation holds " + std::to_string(size - std::min(before, size)) + " bytes from the pointer on, " + std::to_string(bytes) + " are needed");
+    return FRT_OK;
+}
+// Host input: one pinned block holds what a call uploads, [positions | attributes | instance records | decoded normals]; the first two are copied into the
+// replica (the object-space positions the instance update reads, SceneView::attributes), the last two into the device block of RefitState::def, which is
+// reused in stream order and replaced, after a wait for the stream, only when it has to grow. With FRT_DEFORM_RECOMPUTE_NORMALS the host decodes nothing:
+// the normal pass writes the decoded normals into the device block. Device input (FRT_DEFORM_DEVICE): only the instance records are staged; the
+// vertices reach the replica through the validation and copy-in launches of frt_deform.hpp.
+int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
     if (const int rc = check_entry(r, "set_mesh_vertices", kEditChecks | kRefit)) return rc;
+    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: unknown flag bits");
     if (mesh_id >= r->rf.vert_count.size())
         return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
-    const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    if (!dev) {
+        const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
+        if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
+    } else {      // what check_mesh_vertices checks without reading the vertices; their finiteness is the validation launch's to check
+        if (!pos4) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null positions");
+        if (nverts != r->rf.vert_count[mesh_id])
+            return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(r->rf.vert_count[mesh_id]) + " (the topology is fixed)");
+        DeviceGuard guard(r->device);
+        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+        if (const int rc = check_device_pointer(r, pos4, (size_t)nverts * 16, "positions")) return rc;
+        if (attrs) if (const int rc = check_device_pointer(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), "attributes")) return rc;
+    }
     return edit_frame(r, true, [&]() -> int {
         RefitState& f = r->rf;
         std::vector<DeformInstance> rec;
@@ -342,32 +389,70 @@ int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const floa
             for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
             rec.push_back(d);
         }
-        const size_t pos_bytes = (size_t)nverts * 16, attr_bytes = attrs ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
-        const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = attrs ? (size_t)nverts * 16 : 0;
-        const size_t up_bytes = rec_bytes + nrm_bytes, all_bytes = pos_bytes + attr_bytes + up_bytes;
+        const bool shade = attrs || recompute;            // the shading records are written again: the device block holds the decoded normals
+        const bool host_decode = attrs && !recompute && !dev;
+        const size_t pos_bytes = dev ? 0 : (size_t)nverts * 16, attr_bytes = attrs && !dev ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
+        const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = shade ? (size_t)nverts * 16 : 0;
+        const size_t up_bytes = rec_bytes + (host_decode ? nrm_bytes : 0);      // what is copied into the device block
         int rc;
-        if ((rc = f.def.reserve(all_bytes, up_bytes, r->stream))) return rc;
+        if (recompute && (rc = ensure_adjacency(r, mesh_id))) return rc;
+        if (dev && !f.d_reject) {
+            void* d = nullptr;
+            if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
+            HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
+            f.d_reject = static_cast<uint32_t*>(d);
+        }
+        if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes, rec_bytes + nrm_bytes, r->stream))) return rc;
         uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes;
-        memcpy(h_pos, pos4, pos_bytes);
-        if (attrs) {
-            memcpy(h_attr, attrs, attr_bytes);
+        float4* block = shade ? reinterpret_cast<float4*>(f.def.d + rec_bytes) : nullptr;
+        float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
+        const uint32_t cap_verts = pool_cap(r, kPoolVerts);
+        if ((uint64_t)f.pos_offset[mesh_id] + nverts > cap_verts || (uint64_t)f.attr_offset[mesh_id] + nverts > cap_verts)
+            return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the vertex pool");
+        if ((uint64_t)f.index_offset[mesh_id] + 3ull * f.mesh_tris[mesh_id] > pool_cap(r, kPoolIndices))
+            return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the index pool");
+        if (!dev) memcpy(h_pos, pos4, pos_bytes);
+        if (attr_bytes) memcpy(h_attr, attrs, attr_bytes);
+        if (host_decode) {
             float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
             for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
         }
         if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
-        HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
-        if (attrs) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
+        if (!dev) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
+        if (attr_bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
         if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
-        if (attrs && r->pools.d_normals)      // (what a later frt_renderer_add_instances of this mesh reads, §14)
-            HIP_TRY(hipMemcpyAsync(const_cast<float4*>(r->pools.d_normals) + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
+        if (host_decode && pool_normals)
+            HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
         if ((rc = f.def.mark(r->stream))) return rc;
+        const uint32_t* reject = dev ? f.d_reject : nullptr;      // (host input was validated above: there is no flag to look at)
+        if (dev) {
+            DeformInput in{reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(attrs), nverts, f.pos_offset[mesh_id], f.attr_offset[mesh_id], cap_verts,
+                           const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
+                           attrs && !recompute ? block : nullptr, attrs && !recompute ? pool_normals : nullptr, f.d_reject};
+            HIP_TRY(launch_deform_input(in, r->stream));
+        }
+        if (recompute) {
+            NormalArgs na{f.adj[mesh_id], f.adj[mesh_id] + (nverts + 1u), nverts, 3u * f.mesh_tris[mesh_id], f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+                          cap_verts, pool_cap(r, kPoolIndices), f.d_pos, block, pool_normals, reject};
+#if FRT_EXPERIMENTS
+            const char* tri_pass = getenv("FRT_NORMALS_TRI_PASS");
+            if (tri_pass && atoi(tri_pass) != 0) {
+                if ((rc = f.tri_normals.ensure(r, (size_t)f.mesh_tris[mesh_id] * sizeof(float4)))) return rc;
+                na.tri_scratch = f.tri_normals.as<float4>();
+            }
+#endif
+            HIP_TRY(launch_vertex_normals(r->sv, na, r->stream));
+        }
         if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
         DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
-                     f.d_pos, attrs ? reinterpret_cast<const float4*>(f.def.d + rec_bytes) : nullptr, f.d_slot_of};
+                     f.d_pos, block, f.d_slot_of, reject};
         HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
         HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
         return refit_levels(r);
     });
+}
+int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
+    return frt_renderer_set_mesh_vertices_ex(r, mesh_id, pos4, attrs, nverts, 0u);
 }
 
 // ------------------------------------------------------------------------------------------------ materials, lights, textures
@@ -968,6 +1053,15 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             v += f.vert_count[m]; i += index_count[m];
         }
         f.pos_offset = vo; f.attr_offset.swap(vo); f.index_offset.swap(io); f.vert_count.swap(vc); f.mesh_tris.swap(mt);
+        // the adjacency of a mesh that leaves is freed (behind a wait: a deformation's kernel may still read it), the survivors' follow their new ids
+        f.adj.resize(old_meshes, nullptr);
+        bool waited = false;
+        for (uint32_t g : gone) {
+            if (!f.adj[g]) continue;
+            if (!waited) { HIP_TRY(hipStreamSynchronize(r->stream)); waited = true; }
+            scene_free(r, f.adj[g]);
+        }
+        remove_elements(f.adj, gone);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];
         return FRT_OK;
     });

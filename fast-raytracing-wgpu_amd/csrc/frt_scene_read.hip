@@ -88,6 +88,15 @@ int frt_renderer_pool_counts(frt_renderer* r, uint32_t counts[6]) {
     counts[3] = r->rf.color_layers; counts[4] = r->rf.data_layers; counts[5] = r->pools.growths;
     return FRT_OK;
 }
+int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out) {
+    if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "deform_rejects: null");
+    *out = 0u;
+    if (!r->rf.d_reject) return FRT_OK;      // no device-input deformation yet
+    FRT_DEVICE(r);
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(out, r->rf.d_reject + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
     const SceneView& sv = r->sv;

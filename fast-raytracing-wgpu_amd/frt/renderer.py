@@ -1,8 +1,8 @@
 """Renderer mirror (src/renderer.rs) over frt_renderer_*. Every pixel is produced by the HIP kernels in libfrt.so."""
 import ctypes as C
 import numpy as np
-from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE)
-from .scene import (transform_args, mesh_vertex_args, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
+from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE)
+from .scene import (transform_args, set_mesh_vertices_call, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
                     pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
 
@@ -143,6 +143,7 @@ class Renderer(_HostQueries, _SceneGrowth):
         self.width, self.height = width, height
         self.device = device
         self._scene = scene     # keep the scene alive
+        self._held = []         # device tensors of set_mesh_vertices calls the stream may not have passed yet: (event behind the call, tensors)
         self._destroy = lib().frt_renderer_destroy
         self._h = lib().frt_renderer_create(scene._h, width, height, C.byref(o))
         if not self._h:
@@ -165,6 +166,7 @@ class Renderer(_HostQueries, _SceneGrowth):
         return int(lib().frt_renderer_frame_count(self._h))
 
     def render(self, camera_uniform, jitter=None):      # renderer.rs:349 (jitter -> PostParams.jitter, :361-379)
+        self._release_held()
         if jitter is None:
             check(lib().frt_renderer_render(self._h, C.byref(camera_uniform)))
         else:
@@ -192,6 +194,7 @@ class Renderer(_HostQueries, _SceneGrowth):
 
     def sync(self):
         check(lib().frt_renderer_sync(self._h))
+        self._release_held(all_done=True)
 
     def reset(self):             # state.rs:152 / renderer.rs:346
         check(lib().frt_renderer_reset(self._h))
@@ -246,11 +249,55 @@ class Renderer(_HostQueries, _SceneGrowth):
     def set_instance_transform(self, instance_id, transform_colmajor):
         self.set_instance_transforms([instance_id], [transform_colmajor])
 
-    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
-        """Deform one mesh in this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_vertices): asynchronous, on the
-        renderer's streams; the arrays are copied during the call. The host scene is not changed (SceneBuilder.set_mesh_vertices is its own call)."""
-        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
-        check(lib().frt_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None, normals="keep"):
+        """Deform one mesh in this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_vertices_ex): asynchronous, on the
+        renderer's streams. The host scene is not changed (SceneBuilder.set_mesh_vertices is its own call). normals="recompute": the vertex normals
+        are computed on the device from the new positions (uv and tangent from `attributes`, or kept).
+        numpy (or array-like) in: the arrays are checked and copied during the call. Contiguous float32 torch tensors on the renderer's device in
+        (positions [n, 4], attributes [n, 8]; not one of each kind): nothing is copied to the host and nothing waits — the renderer's stream
+        (stream_handle(0)) waits for the caller's current stream, the call is enqueued there, and the renderer keeps a reference to the tensors
+        until that stream has passed the call (an event behind it, looked at by the next such call, by render() and by sync()), so the caching allocator cannot hand their
+        memory out early. (Tensor.record_stream would say the same to the allocator, but it makes the allocator record an event on the renderer's
+        stream when the tensor is freed, and a tensor may outlive the renderer that owns that stream.) A non-finite float then rejects the call
+        on the device: nothing is applied and deform_rejects() counts it."""
+        dev_in = [_is_device_tensor(x) for x in (positions, attributes) if x is not None]
+        if not any(dev_in):
+            return set_mesh_vertices_call("frt_renderer_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
+        if not all(dev_in):
+            raise FrtError("set_mesh_vertices: positions and attributes must both be host arrays or both be device tensors")
+        import torch
+        flags = deform_flags(normals) | DEFORM_DEVICE
+        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+            raise FrtError("mesh id must be an unsigned 32-bit index")
+        for name, t, cols in (("positions", positions, 4), ("attributes", attributes, 8)):
+            if t is None:
+                continue
+            if t.device.index != self.device:
+                raise FrtError(f"set_mesh_vertices: {name} are on {t.device}, the renderer on device {self.device}")
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+                raise FrtError(f"set_mesh_vertices: device {name} must be a contiguous float32 tensor shaped [n, {cols}]")
+        if attributes is not None and attributes.shape[0] != positions.shape[0]:
+            raise FrtError(f"{positions.shape[0]} positions but {attributes.shape[0]} attribute records")
+        dev = positions.device
+        s = self._torch_stream(torch, dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        check(lib().frt_renderer_set_mesh_vertices_ex(self._h, int(mesh_id), positions.data_ptr(), attributes.data_ptr() if attributes is not None else None,
+                                                      positions.shape[0], flags))
+        done = torch.cuda.Event()
+        done.record(s)
+        self._release_held()
+        self._held.append((done, positions, attributes))
+
+    def _release_held(self, all_done=False):
+        """Drop the references to device tensors whose call the stream has passed (all of them after a sync)."""
+        if self._held:
+            self._held = [] if all_done else [h for h in self._held if not h[0].query()]
+
+    def deform_rejects(self):
+        """Device-tensor set_mesh_vertices calls rejected so far for a non-finite float (nothing of them was applied). Waits for the renderer's stream."""
+        n = C.c_uint32()
+        check(lib().frt_renderer_deform_rejects(self._h, C.byref(n)))
+        return int(n.value)
 
     # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it; DESIGN.md section 13): asynchronous,
     # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).
@@ -504,10 +551,11 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         n, i, m = transform_args(ids, transforms_colmajor)
         check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
 
-    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
-        """Renderer.set_mesh_vertices on every strip's scene replica."""
-        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
-        check(lib().frt_multi_renderer_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None, normals="keep"):
+        """Renderer.set_mesh_vertices on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
+        if any(_is_device_tensor(x) for x in (positions, attributes)):
+            raise FrtError("set_mesh_vertices: a MultiRenderer takes host arrays only (its replicas live on different devices)")
+        set_mesh_vertices_call("frt_multi_renderer_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
 
     # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it; DESIGN.md section 13): asynchronous,
     # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).

@@ -1,7 +1,7 @@
 """SceneBuilder mirror (src/scene/builder.rs) over frt_scene_*."""
 import ctypes as C
 import numpy as np
-from ._lib import lib, check, Material, Light, MeshData, FrtError
+from ._lib import lib, check, Material, Light, MeshData, FrtError, DEFORM_RECOMPUTE_NORMALS
 
 
 def material_new(base_color):
@@ -38,6 +38,25 @@ def mesh_vertex_args(mesh_id, positions, attributes):
         if att.shape[0] != pos.shape[0]:
             raise FrtError(f"{pos.shape[0]} positions but {att.shape[0]} attribute records")
     return int(mesh_id), pos, att, pos.shape[0]
+
+
+def deform_flags(normals):
+    """The flags of the *_set_mesh_vertices_ex calls for `normals`: "keep" (the attributes' normals stay) or "recompute" (every vertex normal is
+    computed from the new positions: the normalised sum of the area-weighted normals of the triangles around the vertex)."""
+    if normals not in ("keep", "recompute"):
+        raise FrtError(f'set_mesh_vertices: normals must be "keep" or "recompute", not {normals!r}')
+    return DEFORM_RECOMPUTE_NORMALS if normals == "recompute" else 0
+
+
+def set_mesh_vertices_call(name, handle, mesh_id, positions, attributes, normals):
+    """One host-array deformation through the entry point `name` (its _ex form when a flag is set)."""
+    flags = deform_flags(normals)
+    mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
+    a = att.ctypes.data if att is not None else None
+    if flags:
+        check(getattr(lib(), name + "_ex")(handle, mid, pos.ctypes.data, a, n, flags))
+    else:
+        check(getattr(lib(), name)(handle, mid, pos.ctypes.data, a, n))
 
 
 def material_args(ids, materials):
@@ -336,9 +355,9 @@ class SceneBuilder:
         return self.set_instance_transforms([instance_id], [transform_colmajor])
 
     # Deform one mesh of the built scene: same topology and tree, refit boxes (include/frt.h: frt_scene_set_mesh_vertices). Host copy only.
-    def set_mesh_vertices(self, mesh_id, positions, attributes=None):
-        mid, pos, att, n = mesh_vertex_args(mesh_id, positions, attributes)
-        check(lib().frt_scene_set_mesh_vertices(self._h, mid, pos.ctypes.data, att.ctypes.data if att is not None else None, n))
+    # normals="recompute": the vertex normals are computed from the new positions (frt_scene_set_mesh_vertices_ex, FRT_DEFORM_RECOMPUTE_NORMALS).
+    def set_mesh_vertices(self, mesh_id, positions, attributes=None, normals="keep"):
+        set_mesh_vertices_call("frt_scene_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
         return self
 
     # ---- what the built scene looks like (include/frt.h: frt_scene_set_materials and the three calls after it). Host copy only.

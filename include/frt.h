@@ -158,6 +158,18 @@ int frt_scene_set_instance_transforms(frt_scene* s, uint32_t n, const uint32_t* 
  * built from scratch with the new vertices. Host copy only, as frt_scene_set_instance_transforms. FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG, nothing changed: mesh id out of range, nverts not the mesh's count, pos4 NULL, a non-finite position or attribute float. */
 int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* The same call with flags ("Recomputed normals"); flags == 0 is frt_scene_set_mesh_vertices.
+ * FRT_DEFORM_RECOMPUTE_NORMALS: the normal of every vertex of the mesh is computed from the new positions. For triangle j with indices (i0, i1, i2),
+ * c_j = (p1 - p0) x (p2 - p0) (area-weighted, not normalised); for vertex v, s = ((0 + c_a) + c_b) + ... over every triangle corner that names v, in
+ * ascending 3 j + corner (a triangle that names v twice counts twice); d = (s.x s.x + s.y s.y) + s.z s.z; n = s * (1 / sqrt(d)), all in f32 without
+ * contraction; the attribute's `normal` becomes the octahedral encoding of n that the geometry generators use. A vertex no triangle names, or whose d
+ * is zero or not finite, keeps its normal. With attrs, uv and tangent (and the normal of a vertex that keeps it) come from attrs; with attrs == NULL
+ * they stay. Tangents are not re-orthogonalised against the new normal. The shading records of every instance of the mesh are recomputed, and the
+ * scene then equals one built from scratch whose mesh carries the new positions and these attributes.
+ * FRT_DEFORM_DEVICE: frt_renderer_set_mesh_vertices_ex only. FRT_ERR_INVALID_ARG, nothing changed: an unknown flag bit, FRT_DEFORM_DEVICE here. */
+#define FRT_DEFORM_RECOMPUTE_NORMALS 1u
+#define FRT_DEFORM_DEVICE 2u
+int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
 /* What a BUILT scene looks like: four edits that move no triangle, slot or box. Common rules: FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG: an id or layer out of range, a null pointer with n > 0, a failed check; everything is validated before anything is applied, so
  * a refused call changes nothing. n == 0: FRT_OK. An id given twice ends with its last value. Afterwards the scene equals one built from scratch
@@ -385,6 +397,23 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
  * while a frame is open, a frame that ran ahead under the old geometry dropped and redone, accumulation, reservoirs and frame_count kept. Works on
  * a tree made by frt_renderer_rebuild_tree too, and later frt_renderer_set_instance_transforms calls transform the new vertices. */
 int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* The same call with flags; flags == 0 is frt_renderer_set_mesh_vertices.
+ * FRT_DEFORM_RECOMPUTE_NORMALS: as frt_scene_set_mesh_vertices_ex, bit for bit, by a kernel with one thread per vertex that gathers through the mesh's
+ * vertex -> corner adjacency. The adjacency is built on the host from the replica's indices at the first such call for a mesh (one read-back behind a
+ * wait for the stream), kept on the device (4 (nverts + 1 + nidx) bytes per mesh) and follows frt_renderer_remove_meshes.
+ * FRT_DEFORM_DEVICE: pos4 and attrs (if not NULL) are 16-byte aligned device memory on the renderer's device. The call checks what the host can see
+ * (state, mesh id, vertex count, flags, that the pointers are device memory of this device inside an allocation that holds nverts records from them
+ * on), enqueues everything on the renderer's main stream
+ * (frt_renderer_stream(r, 0): order it behind the producer of the vertices first) and returns: no host copy of the vertices and no wait for this
+ * call's work. The one wait a deformation of either kind may make is for the PREVIOUS deformation's small copies out of the pinned staging block
+ * (its 64-byte instance records): a second call issued back to back blocks the host until the stream has reached the first one's copy, hence until
+ * the work the stream was ordered behind for the first one has run. The caller keeps the memory alive
+ * and unchanged until that stream has passed the call. The finiteness check runs on the device: a call with a non-finite position or attribute float
+ * changes nothing of the replica (its kernels return at once; the refit that follows reproduces the same boxes) and adds one to a counter that
+ * frt_renderer_deform_rejects reads. With attrs == NULL and FRT_DEFORM_RECOMPUTE_NORMALS no attribute is read from the caller. */
+int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
+/* Device-input deformations this renderer has rejected since it was created (non-finite input). Waits for the main stream. */
+int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
@@ -560,6 +589,8 @@ int frt_multi_renderer_boundaries(const frt_multi_renderer* m, uint32_t* rows_ou
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
 /* frt_renderer_set_mesh_vertices on every strip's replica, between frames */
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
+/* ... with flags. FRT_DEFORM_DEVICE is refused (FRT_ERR_INVALID_ARG): the strips' replicas live on different devices. */
+int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
 /* frt_renderer_set_materials, _set_instance_materials, _set_light_emission and _set_texture on every strip's replica, between frames */
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials);
 int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);

@@ -3,6 +3,9 @@
 microseconds per call with and without attributes (HIP events on the renderer's stream, median of 20; the call's host part, which copies the
 vertices into pinned memory, is reported beside it), the set_instance_transforms call for the same instances, the frame time before and after
 (1920x1080, two-stream schedule), and the host rebuild + renderer re-create the call replaces.
+Then the routes to correct normals and to device-resident vertices ("Recomputed normals", "Vertices from device memory"), each
+timed the same way with the frame time after it: (a) smooth normals computed on the host in numpy, encoded, and passed as attributes — the only route
+before normals="recompute"; (b) host positions with normals="recompute"; (c) device tensors, normals="keep"; (d) device tensors, normals="recompute".
 One JSON line per scene. Usage: python tools/mesh_update_time.py [cornell blob colonnade]"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,6 +37,23 @@ def deformed(geo, phase):
     pos[:, :3] = p * (np.float32(1.0) + np.float32(0.05) * np.sin(np.float32(7.0) * p[:, 1:2] + np.float32(3.0) * p[:, 0:1] + np.float32(phase)))
     att[:, 2:4] += np.float32(0.01 * phase)
     return pos, att
+
+
+def numpy_normals(pos, att, idx):
+    """Route (a): area-weighted smooth normals in numpy (float32; np.add.at sums in index order), octahedral-encoded into a copy of `att`."""
+    p = pos[:, :3]
+    tri = idx.reshape(-1, 3)
+    c = np.cross(p[tri[:, 1]] - p[tri[:, 0]], p[tri[:, 2]] - p[tri[:, 0]]).astype(np.float32)
+    s = np.zeros_like(p)
+    for k in range(3):
+        np.add.at(s, tri[:, k], c)
+    n = s / np.maximum(np.linalg.norm(s, axis=1, keepdims=True), np.float32(1e-30))
+    e = n[:, 0:2] / np.maximum(np.abs(n).sum(axis=1, keepdims=True), np.float32(1e-30))
+    low = n[:, 2] < 0
+    f = (np.float32(1.0) - np.abs(e[:, ::-1])) * np.where(e >= 0, np.float32(1.0), np.float32(-1.0))
+    out = att.copy()
+    out[:, 0:2] = np.where(low[:, None], f, e)
+    return out
 
 
 def call_us(r, call, reps=20):
@@ -73,6 +93,24 @@ def main(names):
         posonly, pos_host = call_us(r, positions_only)
         moved, _ = call_us(r, lambda: r.set_instance_transforms(ids, mats))
         after = frame_ms(r, W, H, fs.num_lights)
+        # the routes to correct normals / from device memory
+        idx = np.asarray(geo.indices, np.uint32)
+        dev = torch.device("cuda", r.device)
+        tens = [tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in sh) for sh in shapes]
+        def route_a():
+            k[0] ^= 1; p, a = shapes[k[0]]; r.set_mesh_vertices(mesh, p, numpy_normals(p, a, idx))
+        def route_b():
+            k[0] ^= 1; r.set_mesh_vertices(mesh, shapes[k[0]][0], normals="recompute")
+        def route_c():
+            k[0] ^= 1; r.set_mesh_vertices(mesh, *tens[k[0]])
+        def route_d():
+            k[0] ^= 1; r.set_mesh_vertices(mesh, tens[k[0]][0], normals="recompute")
+        routes = {}
+        route_b(); r.sync()      # (the one-time adjacency build is not part of a call's steady cost)
+        for key, fn in (("a_host_numpy_normals", route_a), ("b_host_recompute", route_b), ("c_device_keep", route_c), ("d_device_recompute", route_d)):
+            us, host = call_us(r, fn)
+            routes[key] = {"us": round(us, 1), "us_host": round(host, 1), "ms_frame_after": round(frame_ms(r, W, H, fs.num_lights), 3)}
+        rejects = r.deform_rejects()
         t0 = time.perf_counter()
         fs2 = rebuild()
         r2 = frt.Renderer(fs2, W, H, flags=frt.FLAG_PIPELINE)
@@ -83,7 +121,8 @@ def main(names):
                           "us_with_attributes": round(full, 1), "us_host_with_attributes": round(full_host, 1),
                           "us_positions_only": round(posonly, 1), "us_host_positions_only": round(pos_host, 1),
                           "us_set_instance_transforms_same_instances": round(moved, 1),
-                          "ms_frame_before": round(before, 3), "ms_frame_after": round(after, 3), "s_rebuild_and_recreate": round(rebuild_s, 3)}), flush=True)
+                          "ms_frame_before": round(before, 3), "ms_frame_after": round(after, 3), "s_rebuild_and_recreate": round(rebuild_s, 3),
+                          "routes": routes, "deform_rejects": rejects}), flush=True)
         del r, r2
 
 
