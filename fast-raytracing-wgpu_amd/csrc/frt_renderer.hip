@@ -44,7 +44,7 @@ static int upload_scene(frt_renderer* r, const SceneBuilder& b) {
     // where they are short. Per frame, never / always voting, with the leaf step that fetches both triangles together (before it the 25k-node scene
     // still gained 2 %): 74k quad nodes (246k triangles, 4K, 16 bounces) 20.98 / 19.79 ms; 25k (82k triangles) 2.948 / 2.987 ms; 9.5k (32k triangles)
     // 1.279 / 1.340 ms; 390 (the Cornell Box) 1.565 / 1.611 ms.
-    r->vote = b.quad_nodes.size() >= kVoteMinQuadNodes;
+    r->vote = walk_votes(b.quad_nodes.size());
     if ((rc = upload(r, b.tri_slots, &sv.tris))) return rc;
     sv.nodes8 = nullptr; sv.tris8 = nullptr; sv.num_nodes8 = 0u; sv.stack_need8 = 0u;
     r->walk = kWalkQuad; r->wide_lds_bytes = 0u;

@@ -287,6 +287,12 @@ static int upload(frt_renderer* r, const std::vector<T>& v, const D** out) {
 #define FRT_VOTE_MIN_NODES 32768      // (4 MiB of quad nodes; A/B builds: 0 = every scene votes, a huge value = none does)
 #endif
 static const size_t kVoteMinQuadNodes = FRT_VOTE_MIN_NODES;
+// The walk of a tree of `quad_nodes` nodes: the voting loop from kVoteMinQuadNodes on. FRT_WALK_VOTE=0|1 in the environment overrides the size rule
+// (tests run both walks over one small scene; tools time both over one scene).
+static inline bool walk_votes(size_t quad_nodes) {
+    if (const char* e = getenv("FRT_WALK_VOTE")) return atoi(e) != 0;
+    return quad_nodes >= kVoteMinQuadNodes;
+}
 
 namespace frt {
 int fence_ahead(frt_renderer* r);                                  // frt_renderer.hip

@@ -587,7 +587,7 @@ static void rebuild_swap(frt_renderer* r, const RebuildTarget& target, const Reb
     r->rf.pair_levels.assign(1, 0u);       // later refits skip the pair levels
     r->rf.ok = true;
     r->wg_rows = res.stack_need + 1u;
-    r->vote = res.num_nodes >= kVoteMinQuadNodes;
+    r->vote = walk_votes(res.num_nodes);
     b.done = true; b.origin = res.origin;
 }
 int frt_renderer_rebuild_tree(frt_renderer* r) { return frt_renderer_rebuild_tree_ex(r, FRT_REBUILD_MORTON); }

@@ -183,8 +183,13 @@ FRT_HD void trace(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint3
 // ---- quad nodes -----------------------------------------------------------------------------------------------------------------
 // Four child boxes per node (frt_bvh.cpp: build_quad_nodes): one dependent fetch (7 x 16 B) decides two levels of the binary tree, so a
 // ray takes about half as many node steps, each with four independent slab tests. Closest-hit rays visit the hit children near to far
-// (a five-exchange sorting network on (entry distance, reference)) — any-hit rays too: which triangles are hit does not depend on the
-// order (hit semantics above), but near-first finds an occluder sooner (slot order measured 10 % slower per traced stage).
+// (a five-exchange sorting network on (entry distance, reference)): their interval shrinks with every hit, so the order prunes. An any-hit
+// ray's interval never shrinks and which triangles it hits does not depend on the order (hit semantics above); the order only decides how
+// soon an occluder is found. It enters the NEAREST hit child (a tournament: three compare / select pairs) and stacks the others in slot
+// order, the highest slot on top — about half of the network's 33 VALU (15 fewer selects per step in the ISA). In the host model of a wave's lockstep walk (tools/bvh_quality.cpp,
+// profiles/r10_experiments/anyhit_order.md) that costs a shadow wave-ray 5.33 + 1.62 node + leaf steps on the Cornell Box against the full
+// sort's 5.43 + 1.67, and 18.74 + 5.77 against 18.33 + 5.63 on the ReSTIR scene; the others popped lowest slot first: 6.84 + 2.16 on the
+// Cornell Box; slot order throughout: 30.7 + 6.5 (measured 10 % slower per traced stage in round 2).
 // Near / far planes are picked by the sign of the ray direction: the near planes of a child are its lo planes for a positive direction
 // component and its hi planes for a negative one, so no min / max per axis is needed (4 instead of 10 instructions per child; fma is
 // monotonic, so these are the values min / max would select). `n` is the uniform base of the node array and sx, sy, sz the 32-bit byte
@@ -266,7 +271,7 @@ FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint
         return nn != 0u && nn >= nl;
     };
     // One node step: the node's four boxes behind `nb` (the HBM array or the LDS copy; byte offsets of the reference word and of this lane's near planes
-    // on each axis) tested against the ray, the hit children sorted near to far, the nearest entered and the others stacked.
+    // on each axis) tested against the ray, the nearest hit child entered and the others stacked — near to far for a closest-hit ray, in slot order for an any-hit ray.
     auto node_step = [&](const char* nb, uint32_t oref, uint32_t ox, uint32_t oy, uint32_t oz) {
         const float4 rf = *reinterpret_cast<const float4*>(nb + oref);
         float t[4]; bool h[4];
@@ -276,6 +281,20 @@ FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint
         float k[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) k[c] = h[c] ? t[c] : kFar;
+        if constexpr (ANY) {
+            // no sort: a tournament of three compare / select pairs finds the nearest hit child (ties: the lower slot), which is entered; the other hit
+            // children are stacked in slot order. Two children of a node never share a reference, so "not the one entered" is a compare of references.
+            const bool s01 = k[1] < k[0], s23 = k[3] < k[2];
+            const float ka = s01 ? k[1] : k[0], kb = s23 ? k[3] : k[2];
+            const uint32_t ra = s01 ? r[1] : r[0], rb = s23 ? r[3] : r[2];
+            const uint32_t rn = kb < ka ? rb : ra;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) if (h[c] && r[c] != rn) { *top = r[c]; top += stride; }
+            if (h[0] || h[1] || h[2] || h[3]) cur = rn;
+            else if (top == stk) cur = kDone;
+            else { top -= stride; cur = *top; }
+            return;
+        }
 #define FRT_CE(a, b) { const bool s_ = k[b] < k[a]; const float ka_ = s_ ? k[b] : k[a], kb_ = s_ ? k[a] : k[b]; \
                        const uint32_t ra_ = s_ ? r[b] : r[a], rb_ = s_ ? r[a] : r[b]; k[a] = ka_; k[b] = kb_; r[a] = ra_; r[b] = rb_; }
         FRT_CE(0, 1) FRT_CE(2, 3) FRT_CE(0, 2) FRT_CE(1, 3) FRT_CE(1, 2)

@@ -1,7 +1,7 @@
 // bvh_quality.cpp — offline measure of what a BVH costs the traced kernels, on the host (no GPU).
 //
 //   g++ -O2 -std=c++17 tools/bvh_quality.cpp -Iinclude -Lfast-raytracing-wgpu_amd/lib -lfrt -Wl,-rpath,$PWD/fast-raytracing-wgpu_amd/lib -o tools/_build/bvh_quality
-//   tools/_build/bvh_quality [cornell|restir] [tiles] [insertion passes] [policy 0|1|2] [threshold] [presence 0..1] [split 0|1] [chain 0|1]
+//   tools/_build/bvh_quality [cornell|restir] [tiles] [insertion passes] [policy 0|1|2] [threshold] [presence 0..1] [split 0|1] [chain 0|1] ... [any-hit order 0..3] (argument 15)
 //
 // Takes the canonical BVH2 the product built (frt_scene_get), folds it into quad nodes the way frt_bvh.cpp: build_quad_nodes does, and walks it
 // with the rays of the workload — 8x8 pixel tiles of primary rays from the benchmark camera, then from every primary hit a cosine-distributed
@@ -33,6 +33,8 @@ struct Tri { V3 v0, e1, e2; };
 static uint64_t g_dbg[2][4];      // any-hit rays: [quad | 8-wide][unoccluded rays, their triangle tests, occluded rays, theirs]
 struct Quad { float lo[3][4], hi[3][4]; uint32_t ref[4]; int n; };
 static const uint32_t kLeaf = 0x80000000u, kNone = 0xFFFFFFFFu;
+static int g_anyorder = 0;      // any-hit rays in the quad tree: 0 = the hit children near to far (the full sort); 1 = the nearest first, the others in slot order
+                                // (ascending); 2 = the same, the others in descending slot order; 3 = slot order throughout
 
 struct Tree {
     std::vector<frt_bvh2_node> t;
@@ -136,6 +138,15 @@ struct Lane {
                 tn = std::max(tn, std::min(t0, t1)); tf = std::min(tf, std::max(t0, t1));
             }
             key[c] = tn <= tf ? tn : 3e38f; r[c] = q.ref[c];
+        }
+        if (any && g_anyorder) {      // no sort: a tournament for the nearest hit child (ties -> the lower slot), the others wait on the stack in slot order
+            int m = 0;
+            if (g_anyorder != 3) { for (int c = 1; c < 4; ++c) if (key[c] < key[m]) m = c; }
+            else { while (m < 3 && !(key[m] < 3e38f)) ++m; }
+            if (g_anyorder == 2) { for (int c = 0; c < 4; ++c) if (c != m && key[c] < 3e38f) stk.push_back(r[c]); }
+            else for (int c = 3; c >= 0; --c) if (c != m && key[c] < 3e38f) stk.push_back(r[c]);
+            if (key[m] < 3e38f) cur = r[m]; else pop();
+            return;
         }
         auto ce = [&](int a, int b) { if (key[b] < key[a]) { std::swap(key[a], key[b]); std::swap(r[a], r[b]); } };
         ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
@@ -566,6 +577,7 @@ int main(int argc, char** argv) {
     g_unified = argc > 11 ? atoi(argv[11]) : 0;
     g_precise = argc > 12 ? atoi(argv[12]) : 0;
     const int sort256 = argc > 13 ? atoi(argv[13]) : 0;
+    g_anyorder = argc > 15 ? atoi(argv[15]) : 0;
     if (argc > 14 && atoi(argv[14]) > 0) { g_topn[0] = 5; g_topn[1] = 21; g_topn[2] = 85; g_topn[3] = (uint32_t)atoi(argv[14]); }
     // the 8-wide compressed tree as the product built it (csrc/frt_bvh8.hpp), decoded from its device form
     WideTree WT;
