@@ -5,6 +5,7 @@
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
+#include "frt_refit_device.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
 #include "frt_mesh_edit.hpp"
@@ -123,8 +124,20 @@ struct OwnedBuf {
 // What frt_renderer_set_instance_transforms needs beside the scene replica, made at create. Device: the object-space positions of every
 // mesh (16 B per vertex), the slot of every flattened triangle (4 B per triangle), one word for the scene extent and the moved-instance records
 // (208 B each, staged through `rec`). Host: per instance what its record needs, the registered lights' emission, the level ranges of both trees.
+// What frt_renderer_set_instance_transforms_ex adds for FRT_TRANSFORM_DEVICE ("Transforms from device memory"; frt_refit_device.hpp), made
+// at the first such call, each with room for the instance capacity. `consts` restates the host's per-instance bookkeeping: an edit that changes what it
+// holds only clears consts_ok, and the next device call uploads it again (through `up`). `m` holds every instance's matrix and is the truth from the
+// first device call on: RefitState::inst[].m (with .w2o and .flip) is then a mirror that may be stale, and a call that reads it reads `m` back first.
+// mirror_stale implies m_ok; m_ok is cleared only while the mirror is current (then the next device call uploads the mirror).
+struct DeviceTransformState {
+    OwnedBuf consts, m, last;              // [InstanceConst], [4 float4], [uint32_t] per instance
+    Staging up;                            // the pinned block the two tables are uploaded through
+    bool consts_ok = false, m_ok = false, mirror_stale = false;
+    uint32_t* d_reject = nullptr;          // [0] the flag of the call in flight, [1] the calls rejected so far (TransformInput::reject)
+};
+
 struct RefitState {
-    bool ok = false;                       // level ranges found (both trees are numbered breadth-first: frt_bvh.cpp)
+    bool ok = false;                      // level ranges found (both trees are numbered breadth-first: frt_bvh.cpp)
     const float4* d_pos = nullptr;
     const uint32_t* d_slot_of = nullptr;
     const unsigned int* d_ext = nullptr;
@@ -144,8 +157,9 @@ struct RefitState {
     std::vector<const uint32_t*> adj;
     // FRT_DEFORM_DEVICE: [0] the flag of the call in flight, [1] the calls rejected so far (frt_deform.hpp: DeformInput); made at the first such call.
     uint32_t* d_reject = nullptr;
+    DeviceTransformState xf;               // FRT_TRANSFORM_DEVICE
 #if FRT_EXPERIMENTS
-    OwnedBuf tri_normals;                  // lib/libfrt_exp.so, FRT_NORMALS_TRI_PASS=1: the scratch of the triangle pass (NormalArgs::tri_scratch)
+    OwnedBuf tri_normals;                 // lib/libfrt_exp.so, FRT_NORMALS_TRI_PASS=1: the scratch of the triangle pass (NormalArgs::tri_scratch)
 #endif
     uint32_t color_layers = 0, data_layers = 0;   // texture layers of the replica (the material and texture edits check against them)
 };

@@ -5,7 +5,7 @@
 //   new meshes, materials, texture layers and lights                        §15
 //   removing meshes, materials, layers and lights                           §16
 // The calls that only read the replica (the ray queries, frt_renderer_read_scene, the statistics and counts) are in frt_scene_read.hip; the kernels in
-// frt_refit.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
+// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
 //
 // All edits share one scheme:
 //   - the call frame (edit_frame): the device guard, the stream order behind the finished frames, the body, `failed` on a HIP error;
@@ -261,9 +261,94 @@ int frt::ensure_normals(frt_renderer* r) {
     return FRT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ the tables of the device-input transforms
+// RefitState::inst[].m, .w2o and .flip are current afterwards: after a device-input set_instance_transforms the truth is the matrix table on the device,
+// which is read back here, once, behind a wait for the stream. Every call that reads a mirrored matrix (or is about to replace the tables) begins with this.
+static int sync_matrix_mirror(frt_renderer* r) {
+    RefitState& f = r->rf;
+    DeviceTransformState& x = f.xf;
+    if (!x.mirror_stale) return FRT_OK;
+    std::vector<float> m(16 * f.inst.size());
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (!m.empty()) HIP_TRY(hipMemcpy(m.data(), x.m.p, m.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < f.inst.size(); ++i) {
+        InstanceRec& in = f.inst[i];
+        if (!memcmp(in.m, &m[16 * i], sizeof(in.m))) continue;
+        memcpy(in.m, &m[16 * i], sizeof(in.m));
+        instance_inverse(in.m, in.w2o, in.flip);
+    }
+    x.mirror_stale = false;
+    return FRT_OK;
+}
+// An edit has changed what the table of per-instance constants restates (`matrices`: and the mirror, which is current, no longer equals the matrix table):
+// the next device-input call uploads them again.
+static void drop_transform_tables(frt_renderer* r, bool matrices) {
+    r->rf.xf.consts_ok = false;
+    if (matrices) r->rf.xf.m_ok = false;
+}
+// The tables of a device-input call exist and are current afterwards; what is not is uploaded from the host's bookkeeping on the main stream.
+static int ensure_transform_tables(frt_renderer* r) {
+    RefitState& f = r->rf;
+    DeviceTransformState& x = f.xf;
+    int rc;
+    if (!x.d_reject) {
+        void* d = nullptr;
+        if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
+        HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
+        x.d_reject = static_cast<uint32_t*>(d);
+    }
+    if (x.consts_ok && x.m_ok) return FRT_OK;
+    const size_t ni = f.inst.size(), cap = std::max<size_t>(pool_cap(r, kPoolInstances), ni);
+    if (x.m.bytes < cap * 64u) {      // (a table that is replaced loses its contents: the matrices come from the mirror)
+        if ((rc = sync_matrix_mirror(r))) return rc;
+        x.m_ok = false;
+    }
+    if ((rc = x.consts.ensure(r, cap * sizeof(InstanceConst)))) return rc;
+    if ((rc = x.m.ensure(r, cap * 64u))) return rc;
+    if ((rc = x.last.ensure(r, cap * sizeof(uint32_t)))) return rc;
+    const size_t const_bytes = x.consts_ok ? 0 : ni * sizeof(InstanceConst), m_bytes = x.m_ok ? 0 : ni * 64u;
+    if ((rc = x.up.reserve(const_bytes + m_bytes, 0, r->stream))) return rc;
+    if (const_bytes) {
+        InstanceConst* c = reinterpret_cast<InstanceConst*>(x.up.h);
+        for (size_t i = 0; i < ni; ++i) {
+            const InstanceRec& in = f.inst[i];
+            memset(&c[i], 0, sizeof(c[i]));
+            c[i].first_tri = in.first_tri; c[i].tri_count = in.tri_count; c[i].index_offset = f.index_offset[in.mesh_id]; c[i].pos_offset = f.pos_offset[in.mesh_id];
+            c[i].mesh_id = in.mesh_id; c[i].mat_id = in.mat_id; c[i].light = 0xFFFFFFFFu; c[i].light_kind = in.light_kind;
+            if (in.light >= 0 && (size_t)in.light < f.lights.size()) { c[i].light = (uint32_t)in.light; memcpy(c[i].emission, f.lights[(size_t)in.light].emission, 16); }
+        }
+        HIP_TRY(hipMemcpyAsync(x.consts.p, x.up.h, const_bytes, hipMemcpyHostToDevice, r->stream));
+    }
+    if (m_bytes) {
+        float* m = reinterpret_cast<float*>(x.up.h + const_bytes);
+        for (size_t i = 0; i < ni; ++i) memcpy(m + 16 * i, f.inst[i].m, 64);
+        HIP_TRY(hipMemcpyAsync(x.m.p, x.up.h + const_bytes, m_bytes, hipMemcpyHostToDevice, r->stream));
+    }
+    if (const_bytes + m_bytes) if ((rc = x.up.mark(r->stream))) return rc;
+    x.consts_ok = x.m_ok = true;
+    return FRT_OK;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ moving instances
+// Is `p` device memory of the renderer's device, `align`-byte aligned, with `bytes` bytes of its allocation behind it? (What a kernel would otherwise
+// find out by faulting.) `call`, `flag`: the names the message begins and ends with.
+static int check_device_pointer(const frt_renderer* r, const void* p, size_t bytes, size_t align, const char* call, const char* what, const char* flag) {
+    const std::string w = std::string(call) + ": " + what;
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, w + " are not device memory (" + flag + ")"); }
+    if (at.type != hipMemoryTypeDevice || at.device != r->device)
+        return fail(FRT_ERR_INVALID_ARG, w + " are not memory of the renderer's device " + std::to_string(r->device) + " (" + flag + ")");
+    if ((uintptr_t)p & (align - 1u)) return fail(FRT_ERR_INVALID_ARG, w + ": device pointers must be " + std::to_string(align) + "-byte aligned");
+    hipDeviceptr_t base = nullptr; size_t size = 0;      // the allocation around p holds `bytes` from p on
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, w + ": no device allocation holds the pointer"); }
+    const size_t before = (size_t)((const uint8_t*)p - (const uint8_t*)base);
+    if (before > size || size - before < bytes)
+        return fail(FRT_ERR_INVALID_ARG, w + ": the device allocation holds " + std::to_string(size - std::min(before, size)) + " bytes from the pointer on, " + std::to_string(bytes) + " are needed");
+    return FRT_OK;
+}
 // Both trees level by level, deepest first: launch k refits the k-th deepest level of each (after a rebuild the pair tree has no levels left).
 static int refit_levels(frt_renderer* r) {
     const RefitState& f = r->rf;
@@ -283,6 +368,8 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
     return edit_frame(r, true, [&]() -> int {
         RefitState& f = r->rf;
         if (n == 0) return FRT_OK;      // (behind the fence: an empty call still drops the speculation)
+        if (const int rc = sync_matrix_mirror(r)) return rc;      // (after device-input calls: the mirror written below is the truth again)
+        f.xf.m_ok = false;
         // the records, in the order given (an id given twice: the later record wins, as on the host)
         std::vector<MovedInstance> rec;
         std::vector<int> last(f.inst.size(), -1);
@@ -319,6 +406,34 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
         return refit_levels(r);
     });
 }
+// Device input (FRT_TRANSFORM_DEVICE): nothing of the call's data is seen by the host. The entry checks, the stream order and the dropped speculation are
+// the host form's; the kernels of frt_refit_device.hpp do the rest from the renderer's device tables, and the host's mirror of the matrices goes stale.
+static const uint32_t kMaxDeviceTransforms = 1u << 26;
+int frt_renderer_set_instance_transforms_ex(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats, uint32_t flags) {
+    if (const int rc = check_entry(r, "set_instance_transforms", kEditChecks | kRefit)) return rc;
+    if (flags & ~FRT_TRANSFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: unknown flag bits");
+    if (!(flags & FRT_TRANSFORM_DEVICE)) return frt_renderer_set_instance_transforms(r, n, ids, mats);
+    if (n > 0 && (!ids || !mats)) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null ids or matrices");
+    if (n > kMaxDeviceTransforms) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: more than 2^26 records in one device-input call");
+    if (n > 0) {
+        DeviceGuard guard(r->device);
+        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+        if (const int rc = check_device_pointer(r, ids, (size_t)n * 4, 4, "set_instance_transforms", "ids", "FRT_TRANSFORM_DEVICE")) return rc;
+        if (const int rc = check_device_pointer(r, mats, (size_t)n * 64, 16, "set_instance_transforms", "matrices", "FRT_TRANSFORM_DEVICE")) return rc;
+    }
+    return edit_frame(r, true, [&]() -> int {
+        RefitState& f = r->rf;
+        if (n == 0) return FRT_OK;
+        if (const int rc = ensure_transform_tables(r)) return rc;
+        DeviceTransformState& x = f.xf;
+        const TransformInput a{ids, reinterpret_cast<const float4*>(mats), n, (uint32_t)f.inst.size(), x.consts.as<InstanceConst>(), x.m.as<float4>(), x.last.as<uint32_t>(), x.d_reject,
+                               f.d_pos, f.d_slot_of, pool_cap(r, kPoolVerts), pool_cap(r, kPoolIndices)};
+        HIP_TRY(launch_device_transforms(r->sv, a, r->stream));
+        x.mirror_stale = true;      // (a rejected call leaves the table as it was: reading it back then changes nothing)
+        HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
+        return refit_levels(r);
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
 // The vertex -> corner adjacency of mesh `m` is on the device afterwards (RefitState::adj). Made once per mesh from the replica's own indices: a wait for
@@ -337,21 +452,6 @@ static int ensure_adjacency(frt_renderer* r, uint32_t m) {
     if (const int rc = scene_alloc(r, off.size() * 4, &d)) return rc;
     HIP_TRY(hipMemcpy(d, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     f.adj[m] = static_cast<const uint32_t*>(d);
-    return FRT_OK;
-}
-// Is `p` device memory of the renderer's device, 16-byte aligned, with `bytes` bytes of its allocation behind it? (What a kernel would otherwise find out by faulting.)
-static int check_device_pointer(const frt_renderer* r, const void* p, size_t bytes, const char* what) {
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + " are not device memory (FRT_DEFORM_DEVICE)"); }
-    if (at.type != hipMemoryTypeDevice || at.device != r->device)
-        return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + " are not memory of the renderer's device " + std::to_string(r->device) + " (FRT_DEFORM_DEVICE)");
-    if ((uintptr_t)p & 15u) return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": device pointers must be 16-byte aligned");
-    hipDeviceptr_t base = nullptr; size_t size = 0;      // the allocation around p holds `bytes` from p on
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": no device allocation holds the pointer"); }
-    const size_t before = (size_t)((const uint8_t*)p - (const uint8_t*)base);
-    if (before > size || size - before < bytes)
-        return fail(FRT_ERR_INVALID_ARG, std::string("set_mesh_vertices: ") + what + ": the device allocation holds " + std::to_string(size - std::min(before, size)) + " bytes from the pointer on, " + std::to_string(bytes) + " are needed");
     return FRT_OK;
 }
 // Host input: one pinned block holds what a call uploads, [positions | attributes | instance records | decoded normals]; the first two are copied into the
@@ -374,11 +474,12 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
             return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(r->rf.vert_count[mesh_id]) + " (the topology is fixed)");
         DeviceGuard guard(r->device);
         if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, pos4, (size_t)nverts * 16, "positions")) return rc;
-        if (attrs) if (const int rc = check_device_pointer(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), "attributes")) return rc;
+        if (const int rc = check_device_pointer(r, pos4, (size_t)nverts * 16, 16, "set_mesh_vertices", "positions", "FRT_DEFORM_DEVICE")) return rc;
+        if (attrs) if (const int rc = check_device_pointer(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), 16, "set_mesh_vertices", "attributes", "FRT_DEFORM_DEVICE")) return rc;
     }
     return edit_frame(r, true, [&]() -> int {
         RefitState& f = r->rf;
+        if (const int rc = sync_matrix_mirror(r)) return rc;      // (the instances' matrices are read below)
         std::vector<DeformInstance> rec;
         uint32_t work = 0;
         for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
@@ -491,6 +592,7 @@ int frt_renderer_set_instance_materials(frt_renderer* r, uint32_t n, const uint3
     if (n == 0) return FRT_OK;
     return edit_frame(r, true, [&]() -> int {
         RefitState& f = r->rf;
+        drop_transform_tables(r, false);
         // one record per distinct instance (an id given twice: its last value), so that no two threads of the kernel store the same word
         std::vector<MaterialEditInstance> rec;
         std::vector<int> last(f.inst.size(), -1);
@@ -519,6 +621,7 @@ int frt_renderer_set_light_emission(frt_renderer* r, uint32_t light, const float
         float up[8] = {color[0], color[1], color[2], intensity, 0.0f, 0.0f, 0.0f, 0.0f};      // [emission | emissive_factor]
         light_emissive_factor(color, intensity, up + 4);
         memcpy(f.lights[light].emission, up, 16);      // the mirror a later set_instance_transforms re-creates a moved light's record from
+        drop_transform_tables(r, false);
         if (const int rc = r->look.reserve(sizeof(up), 0, r->stream)) return rc;
         memcpy(r->look.h, up, sizeof(up));
         HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint8_t*>(const_cast<LightView*>(r->sv.lights) + light) + offsetof(LightView, emission), r->look.h, 16, hipMemcpyHostToDevice, r->stream));
@@ -661,6 +764,8 @@ static int add_instances(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, 
     InstanceEditState& e = r->ie;
     SceneView& sv = r->sv;
     const uint32_t old_tris = sv.num_tris, old_inst = (uint32_t)f.inst.size();
+    if (const int rc0 = sync_matrix_mirror(r)) return rc0;      // (the old instances' records are copied below, matrices included)
+    drop_transform_tables(r, true);
     std::vector<InstanceRec> inst = f.inst;
     std::vector<AppendInstance> rec(n);
     uint32_t work = 0;
@@ -704,6 +809,8 @@ static int remove_instances(frt_renderer* r, const std::vector<uint32_t>& gone, 
     InstanceEditState& e = r->ie;
     SceneView& sv = r->sv;
     const uint32_t old_tris = sv.num_tris, old_inst = (uint32_t)f.inst.size();
+    if (const int rc0 = sync_matrix_mirror(r)) return rc0;      // (the survivors' records are copied below, matrices included)
+    drop_transform_tables(r, true);
     std::vector<RemovedRange> rng;
     std::vector<InstanceRec> inst;
     uint32_t tris_gone = 0;
@@ -791,6 +898,7 @@ int frt_renderer_add_meshes(frt_renderer* r, uint32_t n, const frt_mesh_data* me
     if (total > 0xFFFFFF00ull || (uint64_t)old_meshes + n > 0x7FFFFFFFull) return fail(FRT_ERR_LIMIT, "add_meshes: too many vertices and indices, or meshes, in one call");
     return edit_frame(r, true, [&]() -> int {
         Staging& up = r->pools.up;
+        drop_transform_tables(r, false);
         std::vector<MeshAppend> rec;
         uint32_t nv = 0, ni = 0;
         pack_mesh_appends(n, meshes, old_verts, old_indices, rec, nv, ni);
@@ -893,6 +1001,7 @@ static int register_light(frt_renderer* r, uint32_t mesh_id, const float* m, con
         if ((rc = staged_copy(r, sizeof(mat), &light, const_cast<LightView*>(r->sv.lights) + light_id, sizeof(light)))) return rc;
         if ((rc = r->pools.up.mark(r->stream))) return rc;
         r->rf.lights.push_back(light);
+        drop_transform_tables(r, false);      // (the new instance's light record is in the mirror only now)
         r->sv.num_materials = mat_id + 1u; r->sv.num_lights = light_id + 1u;
         return (int)light_id;
     });
@@ -969,6 +1078,7 @@ static int remove_materials(frt_renderer* r, const std::vector<uint32_t>& gone) 
     HIP_TRY(launch_remap_words(reinterpret_cast<uint32_t*>(const_cast<InstanceView*>(sv.instances)), (uint32_t)r->rf.inst.size(), 16u, 1u, d, old, r->stream));
     if ((rc = remap_history(r, d, old))) return rc;
     spare.trade(sv.materials, (size_t)pool_cap(r, kPoolMaterials) * sizeof(MaterialView));
+    drop_transform_tables(r, false);
     for (InstanceRec& in : r->rf.inst) if (in.mat_id < old && map[in.mat_id] != kGone) in.mat_id = map[in.mat_id];
     sv.num_materials = old - (uint32_t)gone.size();
     return FRT_OK;
@@ -984,6 +1094,7 @@ static int remove_light_records(frt_renderer* r, const std::vector<uint32_t>& go
     HIP_TRY(launch_remap_materials(const_cast<MaterialView*>(sv.materials), sv.num_materials, d, old, kGone, kGone, r->stream));
     spare.trade(sv.lights, (size_t)pool_cap(r, kPoolLights) * sizeof(LightView));
     remove_elements(r->rf.lights, gone);
+    drop_transform_tables(r, false);
     for (InstanceRec& in : r->rf.inst) if (in.light >= 0 && (uint32_t)in.light < old && map[(size_t)in.light] != kGone) in.light = (int32_t)map[(size_t)in.light];
     sv.num_lights = old - (uint32_t)gone.size();
     return FRT_OK;
@@ -1062,6 +1173,7 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             scene_free(r, f.adj[g]);
         }
         remove_elements(f.adj, gone);
+        drop_transform_tables(r, false);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];
         return FRT_OK;
     });

@@ -97,6 +97,15 @@ int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out) {
     HIP_TRY(hipMemcpy(out, r->rf.d_reject + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
     return FRT_OK;
 }
+int frt_renderer_transform_rejects(frt_renderer* r, uint32_t* out) {
+    if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "transform_rejects: null");
+    *out = 0u;
+    if (!r->rf.xf.d_reject) return FRT_OK;      // no device-input transform call yet
+    FRT_DEVICE(r);
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(out, r->rf.xf.d_reject + 1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
 int frt_renderer_read_scene(frt_renderer* r, int which, void* out) {
     if (!r || !out) return fail(FRT_ERR_INVALID_ARG, "read_scene: null");
     const SceneView& sv = r->sv;

@@ -73,6 +73,7 @@ FLAG_OVERLAP_POST = FLAG_PIPELINE      # round-1 name
 QUERY_DEVICE = 1                       # include/frt.h: FRT_QUERY_DEVICE
 QUERY_MAX_RAYS = 1 << 26
 DEFORM_RECOMPUTE_NORMALS, DEFORM_DEVICE = 1, 2      # include/frt.h: FRT_DEFORM_*
+TRANSFORM_DEVICE = 1                                # include/frt.h: FRT_TRANSFORM_DEVICE
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
 PHASE_SPATIAL_INNER, PHASE_SPATIAL_EDGE = 16, 32
 BUF_GPOS, BUF_GNORMAL, BUF_GALBEDO, BUF_GMOTION, BUF_RESERVOIR, BUF_RAW, BUF_DISPLAY, BUF_ACCUM, BUF_CANDIDATE = range(9)
@@ -161,6 +162,8 @@ SYMBOLS = {
     "frt_renderer_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "frt_renderer_set_timing": (C.c_int, [_P, C.c_int]),
     "frt_renderer_set_instance_transforms": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_renderer_set_instance_transforms_ex": (C.c_int, [_P, _U32, _P, _P, _U32]),
+    "frt_renderer_transform_rejects": (C.c_int, [_P, C.POINTER(_U32)]),
     "frt_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_renderer_set_mesh_vertices_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
     "frt_renderer_deform_rejects": (C.c_int, [_P, C.POINTER(_U32)]),

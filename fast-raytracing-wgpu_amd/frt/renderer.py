@@ -1,7 +1,7 @@
 """Renderer mirror (src/renderer.rs) over frt_renderer_*. Every pixel is produced by the HIP kernels in libfrt.so."""
 import ctypes as C
 import numpy as np
-from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE)
+from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE, TRANSFORM_DEVICE)
 from .scene import (transform_args, set_mesh_vertices_call, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
                     pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
@@ -18,6 +18,22 @@ def rebuild_mode(quality):
 def _is_device_tensor(x):
     """A torch tensor in device memory (torch is only imported by callers that pass one)."""
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "is_cuda") and x.is_cuda
+
+
+def device_transform_args(torch, ids, mats, device):
+    """The record count of a device-tensor set_instance_transforms call on HIP device `device`, or FrtError: `ids` contiguous int32 [n], `mats`
+    contiguous float32 [n, 16] or [n, 4, 4] (column-major, as the host form), both on that device. Looks at the tensors' descriptions only."""
+    for name, t in (("ids", ids), ("matrices", mats)):
+        if t.device.index != device:
+            raise FrtError(f"set_instance_transforms: {name} are on {t.device}, the renderer on device {device}")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise FrtError("set_instance_transforms: device ids must be a contiguous int32 tensor shaped [n]")
+    shape = tuple(mats.shape)
+    if mats.dtype != torch.float32 or not (shape[1:] == (16,) or shape[1:] == (4, 4)) or len(shape) < 2 or not mats.is_contiguous():
+        raise FrtError("set_instance_transforms: device matrices must be a contiguous float32 tensor shaped [n, 16] or [n, 4, 4]")
+    if shape[0] != ids.shape[0]:
+        raise FrtError(f"{ids.shape[0]} instance ids but {shape[0]} matrices")
+    return int(ids.shape[0])
 
 
 class _HostQueries:
@@ -143,7 +159,7 @@ class Renderer(_HostQueries, _SceneGrowth):
         self.width, self.height = width, height
         self.device = device
         self._scene = scene     # keep the scene alive
-        self._held = []         # device tensors of set_mesh_vertices calls the stream may not have passed yet: (event behind the call, tensors)
+        self._held = []         # device tensors of set_mesh_vertices / set_instance_transforms calls the stream may not have passed yet: (event behind the call, tensors)
         self._destroy = lib().frt_renderer_destroy
         self._h = lib().frt_renderer_create(scene._h, width, height, C.byref(o))
         if not self._h:
@@ -242,9 +258,36 @@ class Renderer(_HostQueries, _SceneGrowth):
 
     def set_instance_transforms(self, ids, transforms_colmajor):
         """Move instances in this renderer's scene replica between frames (include/frt.h: frt_renderer_set_instance_transforms): asynchronous, on
-        the renderer's streams. The host scene is not changed (SceneBuilder.set_instance_transforms is its own call)."""
-        n, i, m = transform_args(ids, transforms_colmajor)
-        check(lib().frt_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+        the renderer's streams. The host scene is not changed (SceneBuilder.set_instance_transforms is its own call).
+        numpy (or array-like) in: the arrays are checked and copied during the call. Torch tensors on the renderer's device in (ids contiguous int32
+        [n], matrices contiguous float32 [n, 16] or [n, 4, 4]; not one of each kind): frt_renderer_set_instance_transforms_ex with
+        FRT_TRANSFORM_DEVICE, under the rules of the device form of set_mesh_vertices — the renderer's stream waits for the caller's current stream,
+        the call is only enqueued, the renderer keeps a reference to the tensors until that stream has passed the call, nothing waits on the host.
+        A bad id, a non-finite entry or a singular 3x3 then rejects the whole call on the device: nothing is applied and transform_rejects()
+        counts it."""
+        dev_in = [_is_device_tensor(x) for x in (ids, transforms_colmajor)]
+        if not any(dev_in):
+            n, i, m = transform_args(ids, transforms_colmajor)
+            return check(lib().frt_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
+        if not all(dev_in):
+            raise FrtError("set_instance_transforms: ids and matrices must both be host arrays or both be device tensors")
+        import torch
+        n = device_transform_args(torch, ids, transforms_colmajor, self.device)
+        dev = transforms_colmajor.device
+        s = self._torch_stream(torch, dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        check(lib().frt_renderer_set_instance_transforms_ex(self._h, n, ids.data_ptr() if n else None, transforms_colmajor.data_ptr() if n else None, TRANSFORM_DEVICE))
+        done = torch.cuda.Event()
+        done.record(s)
+        self._release_held()
+        self._held.append((done, ids, transforms_colmajor))
+
+    def transform_rejects(self):
+        """Device-tensor set_instance_transforms calls rejected so far (a bad id, a non-finite entry, a singular 3x3; nothing of them was applied).
+        Waits for the renderer's stream."""
+        n = C.c_uint32()
+        check(lib().frt_renderer_transform_rejects(self._h, C.byref(n)))
+        return int(n.value)
 
     def set_instance_transform(self, instance_id, transform_colmajor):
         self.set_instance_transforms([instance_id], [transform_colmajor])
@@ -547,7 +590,9 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         return list(out)
 
     def set_instance_transforms(self, ids, transforms_colmajor):
-        """Renderer.set_instance_transforms on every strip's scene replica."""
+        """Renderer.set_instance_transforms on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
+        if any(_is_device_tensor(x) for x in (ids, transforms_colmajor)):
+            raise FrtError("set_instance_transforms: a MultiRenderer takes host arrays only (its replicas live on different devices)")
         n, i, m = transform_args(ids, transforms_colmajor)
         check(lib().frt_multi_renderer_set_instance_transforms(self._h, n, i.ctypes.data, m.ctypes.data))
 

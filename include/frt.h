@@ -390,6 +390,24 @@ int frt_renderer_set_timing(frt_renderer* r, int on);
  * frt_renderer_reset / _clear; motion vectors stay camera-only). FRT_ERR_STATE between the phases of an open frame; FRT_ERR_INVALID_ARG for a
  * renderer whose kernels walk a tree that is not refit (experiments build: FRT_FLAG_WALK_WIDE / _HBM with an 8-wide tree, the resident kernels). */
 int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16);
+/* The same call with flags; flags == 0 is frt_renderer_set_instance_transforms.
+ * FRT_TRANSFORM_DEVICE: ids (uint32[n], 4-byte aligned) and m_colmajor16 (float[16 n], 16-byte aligned) are device memory on the renderer's device, at
+ * most 2^26 records. The call checks what the host can see (state, flags, that the pointers are device memory of this device inside an allocation that
+ * holds n records from them on), enqueues everything on the renderer's main stream (frt_renderer_stream(r, 0): order it behind the producer of the
+ * matrices first) and returns: no host copy of the ids or matrices and no wait for this call's work. The caller keeps the memory alive and unchanged
+ * until that stream has passed the call. Ordering, state rules and refused renderers are the host form's, and so is the result, bit for bit: an id given
+ * twice ends with its last matrix, world_to_object and flip come from the same cofactor formula in double, a registered light moves with its instance.
+ * The checks of the data run on the device, all or nothing: a call with an id at or beyond the instance count, a non-finite matrix entry or a 3x3 whose
+ * determinant is zero changes nothing of the replica (its kernels return at once; the refit that follows reproduces the same boxes) and adds one to a
+ * counter that frt_renderer_transform_rejects reads; no kernel uses such an id as an index. The kernels read per-instance tables the renderer keeps on
+ * the device (112 bytes + 4 per instance, uploaded at the first such call and again after an edit that changes what they restate), and the triangle
+ * launch covers every triangle of the scene, since the host cannot know which instances move. From the first such call on the matrices live in a device
+ * table: a later call that needs them on the host (the host form of this call, frt_renderer_set_mesh_vertices*, _add_instances, _remove_instances,
+ * _register_*_light, _remove_lights) first waits for the main stream and reads the table back, once. */
+#define FRT_TRANSFORM_DEVICE 1u
+int frt_renderer_set_instance_transforms_ex(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* m_colmajor16, uint32_t flags);
+/* Device-input transform calls this renderer has rejected since it was created (a bad id, a non-finite entry, a singular 3x3). Waits for the main stream. */
+int frt_renderer_transform_rejects(frt_renderer* r, uint32_t* out);
 /* Deform one mesh of this renderer's scene replica between two frames: arguments, checks and result of frt_scene_set_mesh_vertices, computed on the
  * device (the new vertices copied up, one kernel that rewrites the triangle slots and shading records of every instance of the mesh, the refit of
  * frt_renderer_set_instance_transforms). The inputs are copied during the call (the caller's arrays may be reused at once). Ordering, state rules
