@@ -32,6 +32,76 @@ FRT_HD f2 operator*(f2 a, float s) { return mk2(a.x * s, a.y * s); }
 FRT_HD f2 operator*(f2 a, f2 b) { return mk2(a.x * b.x, a.y * b.y); }
 FRT_HD f2 operator/(f2 a, f2 b) { return mk2(a.x / b.x, a.y / b.y); }
 
+FRT_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
+FRT_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
+
+// ---- 1 / x, sqrt(x), 1 / sqrt(x): correctly rounded (the contract), without the compiler's range scaffolding on the device ----------------
+// The compiler's expansions of `1.0f / x` and `__builtin_sqrtf(x)` (-fhip-fp32-correctly-rounded-divide-sqrt, denormals kept) are 11 and about
+// 15 VALU: the hardware estimate and its fma corrections wrapped in v_div_scale / v_div_fmas / v_div_fixup (division) or an input scale, a result
+// scale and a class select (square root), which only matter when the operand, the result or an intermediate leaves the normal range. The device
+// forms below take the estimate and the corrections alone when the operand lies in a range in which that is exact, and the compiler's own
+// expression otherwise (zero, inf, NaN, denormal operands or results, negative operands of sqrt: a rarely taken branch). "Exact" is not argued, it
+// is counted: tools/exact_div_sqrt_check.hip compares each form with the compiler's expansion for all 2^32 operands on the chip
+// (tests/test_exact_div_sqrt_gpu.py; profiles/r11_experiments/exact_div_sqrt.md has the forms that were tried and their mismatch counts).
+// The host branch is the plain expression (tests/hostcheck, tests/test_exact_div_sqrt.py).
+FRT_HD bool rcp_fast_range(float x) { return __builtin_fabsf(x) >= 0x1p-126f && __builtin_fabsf(x) < 0x1p+126f; }      // x and 1 / x both normal
+FRT_HD bool sqrt_fast_range(float x) { return x >= 0x1p-96f && x < 0x1p+126f; }      // (sqrt(x) is then in [2^-48, 2^63): inside rcp_fast_range)
+#if defined(__HIP_DEVICE_COMPILE__)
+// v_rcp_f32 (1 ulp) and ONE Newton step: r + r * (1 - x * r), residual and update each one fma. Equal to the compiler's 1.0f / x for every x of
+// rcp_fast_range (2 x 252 x 2^23 operands counted); outside it v_rcp_f32 flushes the denormal operand or result.
+__device__ __forceinline__ float rcp_fast_(float x) {      // requires rcp_fast_range(x)
+    const float r = __builtin_amdgcn_rcpf(x);
+    const float e = __builtin_fmaf(-x, r, 1.0f);
+    return __builtin_fmaf(e, r, r);
+}
+// v_rsq_f32 (1 ulp): s = x * y estimates the root, h = y / 2 the slope 1 / (2 sqrt(x)); one step s + (x - s * s) * h with the residual in one fma.
+// Equal to the compiler's __builtin_sqrtf(x) for every x >= 2^-102 counted on the chip (below that the residual is rounded: it is denormal).
+__device__ __forceinline__ float sqrt_fast_(float x) {      // requires sqrt_fast_range(x)
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float s = x * y, h = 0.5f * y;
+    const float d = __builtin_fmaf(-s, s, x);
+    return __builtin_fmaf(d, h, s);
+}
+#endif
+// The fast form is evaluated unconditionally (it cannot trap) and overwritten behind the range test: one skipped region, no else branch.
+FRT_HD float rcpf_(float x) {      // 1.0f / x
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_constant_p(x)) return 1.0f / x;      // (a literal divisor still folds at compile time)
+    float r = rcp_fast_(x);
+    if (__builtin_expect(!rcp_fast_range(x), 0)) r = 1.0f / x;
+    return r;
+#else
+    return 1.0f / x;
+#endif
+}
+FRT_HD float neg_rcpf_(float x) {      // -1.0f / x (= -(1 / x) in the fast range: rounding to nearest is symmetric)
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r = -rcp_fast_(x);
+    if (__builtin_expect(!rcp_fast_range(x), 0)) r = -1.0f / x;
+    return r;
+#else
+    return -1.0f / x;
+#endif
+}
+FRT_HD float sqrtf_(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r = sqrt_fast_(x);
+    if (__builtin_expect(!sqrt_fast_range(x), 0)) r = __builtin_sqrtf(x);
+    return r;
+#else
+    return __builtin_sqrtf(x);
+#endif
+}
+FRT_HD float rsqrt_exact(float x) {      // 1.0f / sqrtf_(x): one range test for both steps
+#if defined(__HIP_DEVICE_COMPILE__)
+    float r = rcp_fast_(sqrt_fast_(x));
+    if (__builtin_expect(!sqrt_fast_range(x), 0)) r = 1.0f / __builtin_sqrtf(x);
+    return r;
+#else
+    return 1.0f / __builtin_sqrtf(x);
+#endif
+}
+
 FRT_HD f3 operator+(f3 a, f3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
 FRT_HD f3 operator-(f3 a, f3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
 FRT_HD f3 operator-(f3 a) { return mk3(-a.x, -a.y, -a.z); }
@@ -39,7 +109,7 @@ FRT_HD f3 operator*(f3 a, f3 b) { return mk3(a.x * b.x, a.y * b.y, a.z * b.z); }
 FRT_HD f3 operator*(f3 a, float s) { return mk3(a.x * s, a.y * s, a.z * s); }
 FRT_HD f3 operator*(float s, f3 a) { return mk3(s * a.x, s * a.y, s * a.z); }
 // vector / scalar: one IEEE reciprocal, then three multiplies (contract; WGSL allows 2.5 ulp for division)
-FRT_HD f3 operator/(f3 a, float s) { float r = 1.0f / s; return mk3(a.x * r, a.y * r, a.z * r); }
+FRT_HD f3 operator/(f3 a, float s) { float r = rcpf_(s); return mk3(a.x * r, a.y * r, a.z * r); }
 FRT_HD f3 operator-(float s, f3 a) { return mk3(s - a.x, s - a.y, s - a.z); }
 FRT_HD f4 operator+(f4 a, f4 b) { return mk4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 FRT_HD f4 operator*(f4 a, float s) { return mk4(a.x * s, a.y * s, a.z * s, a.w * s); }
@@ -54,10 +124,8 @@ FRT_HD float smoothstepf(float e0, float e1, float x) {
     float t = clampf((x - e0) / (e1 - e0), 0.0f, 1.0f);
     return t * t * (3.0f - 2.0f * t);
 }
-FRT_HD float sqrtf_(float x) { return __builtin_sqrtf(x); }
 FRT_HD float floorf_(float x) { return __builtin_floorf(x); }
 FRT_HD float fabsf_(float x) { return __builtin_fabsf(x); }
-FRT_HD float rsqrt_exact(float x) { return 1.0f / sqrtf_(x); }
 
 FRT_HD f3 max3(f3 a, f3 b) { return mk3(fmaxn(a.x, b.x), fmaxn(a.y, b.y), fmaxn(a.z, b.z)); }
 FRT_HD f3 clamp3(f3 v, f3 lo, f3 hi) { return mk3(clampf(v.x, lo.x, hi.x), clampf(v.y, lo.y, hi.y), clampf(v.z, lo.z, hi.z)); }
@@ -67,7 +135,13 @@ FRT_HD float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 FRT_HD f3 cross(f3 a, f3 b) { return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 FRT_HD float length(f3 v) { return sqrtf_(dot(v, v)); }
 FRT_HD float length2(f2 v) { return sqrtf_(v.x * v.x + v.y * v.y); }
-FRT_HD f3 normalize(f3 v) { float r = 1.0f / length(v); return v * r; }
+FRT_HD f3 normalize(f3 v) { float r = rsqrt_exact(dot(v, v)); return v * r; }      // 1 / length(v)
+// The compiler's own forms, by name: for code whose operands are often exactly zero (the post stage), where the fallback of the device forms above
+// would be taken by whole waves on top of the fast path.
+FRT_HD float sqrt_ieee_(float x) { return __builtin_sqrtf(x); }
+FRT_HD float length_ieee_(f3 v) { return sqrt_ieee_(dot(v, v)); }
+FRT_HD float length2_ieee_(f2 v) { return sqrt_ieee_(v.x * v.x + v.y * v.y); }
+FRT_HD f3 div_ieee_(f3 a, float s) { float r = 1.0f / s; return mk3(a.x * r, a.y * r, a.z * r); }
 FRT_HD float distance(f3 a, f3 b) { return length(a - b); }
 FRT_HD f3 reflect(f3 i, f3 n) { return i - n * (2.0f * dot(n, i)); }
 FRT_HD f3 refract(f3 i, f3 n, float eta) {
@@ -81,9 +155,6 @@ struct m4 { f4 c[4]; };   // column-major
 FRT_HD f4 mul(const m4& m, f4 v) { return ((m.c[0] * v.x + m.c[1] * v.y) + m.c[2] * v.z) + m.c[3] * v.w; }
 FRT_HD m4 mul(const m4& a, const m4& b) { m4 r; for (int j = 0; j < 4; ++j) r.c[j] = mul(a, b.c[j]); return r; }
 FRT_HD m4 load_m4(const float* p) { m4 m; for (int k = 0; k < 4; ++k) m.c[k] = mk4(p[4 * k], p[4 * k + 1], p[4 * k + 2], p[4 * k + 3]); return m; }
-
-FRT_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
-FRT_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 // sin/cos: Cody–Waite pi/2 reduction + Cephes minimax polynomials (same algorithm as the checker; contract)
 FRT_HD void sincosf_(float x, float& s, float& c) {

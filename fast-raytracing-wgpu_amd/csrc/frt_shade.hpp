@@ -141,7 +141,7 @@ FRT_HD f3 decode_octahedral_normal(float ex, float ey) {   // gbuffer.wgsl:38-44
 }
 FRT_HD f2 encode_octahedral_normal(f3 n) {   // gbuffer.wgsl:46-62
     float l1 = fabsf_(n.x) + fabsf_(n.y) + fabsf_(n.z);
-    float s = 1.0f / fmaxn(l1, 1e-6f);
+    float s = rcpf_(fmaxn(l1, 1e-6f));
     f2 res = l1 > 0.0f ? mk2(n.x * s, n.y * s) : mk2(0.0f, 0.0f);
     if (n.z < 0.0f) {
         float sx = res.x >= 0.0f ? 1.0f : -1.0f, sy = res.y >= 0.0f ? 1.0f : -1.0f;
@@ -151,7 +151,7 @@ FRT_HD f2 encode_octahedral_normal(f3 n) {   // gbuffer.wgsl:46-62
 }
 FRT_HD void make_orthonormal_basis(f3 n, f3& tangent, f3& bitangent) {   // restir.wgsl:161-168
     float sign = n.z >= 0.0f ? 1.0f : -1.0f;
-    float a = -1.0f / (sign + n.z);
+    float a = neg_rcpf_(sign + n.z);
     float b = n.x * n.y * a;
     tangent = mk3(1.0f + sign * n.x * n.x * a, sign * b, -sign * n.x);
     bitangent = mk3(b, sign + n.y * n.y * a, -n.y);
@@ -214,7 +214,7 @@ FRT_HD LightSmp sample_light(PathCtx& c, uint32_t light_idx) {   // :219-245
         float sv = r2 * 2.0f - 1.0f;
         s.pos = lp + lu * su + lv * sv;
         s.normal = normalize(cross(lu, lv));
-        s.pdf = 1.0f / L.area;
+        s.pdf = rcpf_(L.area);
     } else {
         float z = 1.0f - 2.0f * r1;
         float r_xy = sqrtf_(fmaxn(0.0f, 1.0f - z * z));
@@ -224,7 +224,7 @@ FRT_HD LightSmp sample_light(PathCtx& c, uint32_t light_idx) {   // :219-245
         f3 local_dir = mk3(r_xy * cp, r_xy * sp, z);
         s.pos = lp + local_dir * L.v[0];
         s.normal = local_dir;
-        s.pdf = 1.0f / L.area;
+        s.pdf = rcpf_(L.area);
     }
     return s;
 }
@@ -275,7 +275,7 @@ FRT_HD BsdfSmp sample_bsdf(PathCtx& c, f3 wo, f3 ffnormal, bool front_face, cons
     BsdfSmp s;
     if (m.transmission > 0.01f) {
         s.pdf = 0.0f;
-        float refraction_ratio = front_face ? 1.0f / m.ior : m.ior;
+        float refraction_ratio = front_face ? rcpf_(m.ior) : m.ior;
         float cos_theta = fminn(dot(wo, ffnormal), 1.0f);
         float sin_theta = sqrtf_(1.0f - cos_theta * cos_theta);
         bool refl = refraction_ratio * sin_theta > 1.0f;
@@ -422,6 +422,8 @@ FRT_HD void gbuffer_pixel(Ctx& c, uint32_t px, uint32_t py) {
 }
 
 // ================================================================================================ stage 3
+// Division and square root of this stage are the compiler's (frt_math.hpp: *_ieee_): a still camera's motion, the centre tap's distance and a flat
+// neighbourhood's variance are exactly zero, so whole waves would run the device forms' fallback as well (post_kernel 120 -> 149 us with them).
 // post.wgsl:61-282. The centre / neighbour colour and albedo are textureSampleLevel(raw_tex / albedo_tex, smp, uv + unjitter_offset)
 // (post.wgsl:72-78, :97-109, :152-158) under the Repeat / Linear sampler of renderer.rs:240-249. Contract: with jitter == (0, 0)
 // (the shipped reference, camera.rs:202-203) the sample point is the texel centre and the sample IS the texel (what a sampler's
@@ -433,8 +435,8 @@ FRT_HD f3 rgb_to_ycocg(f3 c) {
     return mk3(c.x * 0.25f + c.y * 0.5f + c.z * 0.25f, c.x * 0.5f + c.y * 0.0f + c.z * -0.5f, c.x * -0.25f + c.y * 0.5f + c.z * -0.25f);
 }
 FRT_HD f3 ycocg_to_rgb(f3 c) { return mk3(c.x + c.y - c.z, c.x + c.z, c.x - c.y - c.z); }
-FRT_HD f3 resolve_tonemap(f3 c) { return c / (1.0f + fmaxn(c.x, fmaxn(c.y, c.z))); }
-FRT_HD f3 resolve_inverse_tonemap(f3 c) { return c / (1.0f - fmaxn(c.x, fmaxn(c.y, c.z))); }
+FRT_HD f3 resolve_tonemap(f3 c) { return div_ieee_(c, 1.0f + fmaxn(c.x, fmaxn(c.y, c.z))); }
+FRT_HD f3 resolve_inverse_tonemap(f3 c) { return div_ieee_(c, 1.0f - fmaxn(c.x, fmaxn(c.y, c.z))); }
 
 // What the 5x5 bilateral and 3x3 variance loops read of a neighbour pixel. GlobalTaps decodes it from the per-pixel buffers in
 // HBM on every tap (host check, reference form); the post kernel stages a 20x20 tile of already decoded values in LDS instead
@@ -517,22 +519,22 @@ FRT_HD void post_pixel_t(const FrameView& fv, uint32_t px, uint32_t py, const Ta
             int nx = (int)px + dx, ny = (int)py + dy;
             if (nx < 0 || ny < 0 || nx >= W || ny >= H) continue;
             const TapData t = taps.get(nx, ny);
-            float w_spatial = gauss(length2(mk2((float)dx, (float)dy)), 1.5f);
+            float w_spatial = gauss(length2_ieee_(mk2((float)dx, (float)dy)), 1.5f);
             // equal albedo (every tap on a surface of one material: most of them): gauss(length(0)) = exp2(-0) = 1 exactly (frt_math.hpp: the
             // polynomial of exp2f_ at -0 is 1), so the square root and the exponential are skipped — by the whole wave when all its lanes agree
             const f3 d_albedo = t.albedo - center_albedo;
             float w_color = 1.0f;
-            if (!(d_albedo.x == 0.0f && d_albedo.y == 0.0f && d_albedo.z == 0.0f)) w_color = gauss(length(d_albedo), 0.2f);
+            if (!(d_albedo.x == 0.0f && d_albedo.y == 0.0f && d_albedo.z == 0.0f)) w_color = gauss(length_ieee_(d_albedo), 0.2f);
             float dot_normal = clampf(dot(center_normal, t.normal), 0.0f, 1.0f);
             float w_normal = pow20_(dot_normal);
-            float w_pos = gauss(length(t.pos - center_pos), 0.1f);
+            float w_pos = gauss(length_ieee_(t.pos - center_pos), 0.1f);
             float weight = w_spatial * w_color * w_normal * w_pos;
             sum_color = sum_color + t.color * weight;
             sum_weight += weight;
         }
     }
     f3 filtered_color = center_color;
-    if (sum_weight > 0.001f) filtered_color = sum_color / sum_weight;
+    if (sum_weight > 0.001f) filtered_color = div_ieee_(sum_color, sum_weight);
     f3 m1 = splat3(0.0f), m2 = splat3(0.0f);
     f3 tm_filtered = resolve_tonemap(filtered_color);
     for (int dy = -1; dy <= 1; dy++) {
@@ -545,9 +547,9 @@ FRT_HD void post_pixel_t(const FrameView& fv, uint32_t px, uint32_t py, const Ta
             m2 = m2 + s_ycocg * s_ycocg;
         }
     }
-    m1 = m1 / 9.0f; m2 = m2 / 9.0f;
+    m1 = div_ieee_(m1, 9.0f); m2 = div_ieee_(m2, 9.0f);
     f3 var = max3(splat3(0.0f), m2 - m1 * m1);
-    f3 sigma = mk3(sqrtf_(var.x), sqrtf_(var.y), sqrtf_(var.z));
+    f3 sigma = mk3(sqrt_ieee_(var.x), sqrt_ieee_(var.y), sqrt_ieee_(var.z));
     f3 c_min = m1 - sigma * 1.2f;
     f3 c_max = m1 + sigma * 1.2f;
     f3 history_color = tm_filtered;
@@ -584,7 +586,7 @@ FRT_HD void post_pixel_t(const FrameView& fv, uint32_t px, uint32_t py, const Ta
     if (valid_history) {
         f3 clamped_history = ycocg_to_rgb(clamp3(rgb_to_ycocg(history_color), c_min, c_max));
         f2 motion_px = structure_motion * mk2((float)fv.W, (float)fv.H);
-        float speed = length2(motion_px);
+        float speed = length2_ieee_(motion_px);
         if (speed < 0.5f) {
             float accum_blend = 1.0f - (1.0f / (float)(fv.frame_count + 1u));
             final_tm = mix3(tm_filtered, history_color, clampf(accum_blend, 0.0f, 1.0f));

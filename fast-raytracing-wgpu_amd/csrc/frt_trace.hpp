@@ -68,7 +68,7 @@ FRT_HD bool intersect_tri(f3 v0, f3 e1, f3 e2, f3 o, f3 d, float tmin, float tma
     f3 p = cross(d, e2);
     float det = dot(e1, p);
     if (det == 0.0f) return false;
-    float inv = 1.0f / det;
+    float inv = rcpf_(det);
     f3 s = o - v0;
     float uu = dot(s, p) * inv;
     if (!(uu >= 0.0f && uu <= 1.0f)) return false;

@@ -32,7 +32,7 @@ FRT_HD f3 triangle_area_normal(f3 p0, f3 p1, f3 p2) {
 FRT_HD bool finish_vertex_normal(f3 s, bool has_corner, f2& enc) {
     const float d = (s.x * s.x + s.y * s.y) + s.z * s.z;
     if (!has_corner || d == 0.0f || (f2u(d) & 0x7f800000u) == 0x7f800000u) return false;
-    const float r = 1.0f / sqrtf_(d);
+    const float r = rsqrt_exact(d);
     enc = encode_vertex_normal(mk3(s.x * r, s.y * r, s.z * r));
     return true;
 }
