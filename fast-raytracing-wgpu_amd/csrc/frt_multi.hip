@@ -463,6 +463,14 @@ int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
     return frt_multi_renderer_set_mesh_vertices_ex(m, mesh_id, pos4, attrs, nverts, 0u);
 }
+// Every strip binds the skin to, and poses, its own replica (frt_renderer_set_mesh_skin, frt_renderer_set_mesh_pose).
+int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    return edit_every_replica(m, "multi set_mesh_skin", [&](frt_renderer* r) { return frt_renderer_set_mesh_skin(r, mesh_id, joints4, weights4, nverts, njoints); });
+}
+int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_pose: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose(r, mesh_id, joint_mats, njoints, flags); });
+}
 // The material, light and texture edits on every strip's replica, as above.
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     return edit_every_replica(m, "multi set_materials", [&](frt_renderer* r) { return frt_renderer_set_materials(r, n, ids, materials); });

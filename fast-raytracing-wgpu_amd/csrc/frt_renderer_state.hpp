@@ -5,6 +5,7 @@
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
+#include "frt_skin.hpp"
 #include "frt_refit_device.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
@@ -157,6 +158,13 @@ struct RefitState {
     std::vector<const uint32_t*> adj;
     // FRT_DEFORM_DEVICE: [0] the flag of the call in flight, [1] the calls rejected so far (frt_deform.hpp: DeformInput); made at the first such call.
     uint32_t* d_reject = nullptr;
+    // frt_renderer_set_mesh_skin / _set_mesh_pose ("Skinning"): per mesh its skin on the device, one buffer [bind positions 16 nverts | weights 16 nverts |
+    // joints 8 nverts] (njoints == 0: none; the list may be shorter than the mesh list); remove_meshes frees a leaving mesh's and renumbers the rest.
+    // `skin_up`: the pinned block a bind call's joints and weights go through. `skinned`: the scratch a pose call skins into, [nverts] float4.
+    struct MeshSkin { OwnedBuf buf; uint32_t njoints = 0; };
+    std::vector<MeshSkin> skins;
+    Staging skin_up;
+    OwnedBuf skinned;
     DeviceTransformState xf;               // FRT_TRANSFORM_DEVICE
 #if FRT_EXPERIMENTS
     OwnedBuf tri_normals;                 // lib/libfrt_exp.so, FRT_NORMALS_TRI_PASS=1: the scratch of the triangle pass (NormalArgs::tri_scratch)

@@ -3,6 +3,7 @@
 // (Cargo.lock:876), f32 throughout.
 #include "frt_scene.hpp"
 #include "frt_vertex_normal.hpp"      // encode_vertex_normal, recomputed_vertex_normal: shared with the device
+#include "frt_skin.hpp"               // skinned_position: shared with the device
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -436,6 +437,61 @@ int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const f
     return FRT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- skinning ("Skinning")
+std::string check_mesh_skin(const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t mesh_nverts) {
+    if (!joints4 || !weights4) return "null joints or weights";
+    if (nverts != mesh_nverts) return std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(mesh_nverts);
+    if (njoints == 0 || njoints > 0x10000u) return std::to_string(njoints) + " joints (1 to 65536: a joint index is 16 bits)";
+    for (size_t k = 0; k < (size_t)nverts * 4; ++k) {
+        if (joints4[k] >= njoints) return "vertex " + std::to_string(k / 4) + " names joint " + std::to_string(joints4[k]) + " of " + std::to_string(njoints);
+        if (!std::isfinite(weights4[k]) || weights4[k] < 0.0f) return "a weight of vertex " + std::to_string(k / 4) + " is negative or not finite";
+    }
+    return "";
+}
+std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t bound_joints, bool host_memory) {
+    if (bound_joints == 0) return "the mesh has no skin (set_mesh_skin)";
+    if (njoints != bound_joints) return std::to_string(njoints) + " joint matrices given, the skin was bound with " + std::to_string(bound_joints);
+    if (!joint_mats) return "null joint matrices";
+    for (size_t k = 0; host_memory && k < (size_t)njoints * 16; ++k) if (!std::isfinite(joint_mats[k])) return "joint matrix " + std::to_string(k / 16) + " has a non-finite entry";
+    return "";
+}
+int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    if (!built) { error = "set_mesh_skin: scene is not built"; return FRT_ERR_STATE; }
+    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_skin: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (!joints4) {
+        if (mesh_id < mesh_skins.size()) mesh_skins[mesh_id] = MeshSkin();
+        return FRT_OK;
+    }
+    const std::string bad = check_mesh_skin(joints4, weights4, nverts, njoints, (uint32_t)(mesh_positions[mesh_id].size() / 4));
+    if (!bad.empty()) { error = "set_mesh_skin: " + bad; return FRT_ERR_INVALID_ARG; }
+    if (mesh_skins.size() <= mesh_id) mesh_skins.resize((size_t)mesh_id + 1u);
+    MeshSkin& k = mesh_skins[mesh_id];
+    k.njoints = njoints;
+    k.joints.assign(joints4, joints4 + (size_t)nverts * 4);
+    k.weights.assign(weights4, weights4 + (size_t)nverts * 4);
+    k.bind = mesh_positions[mesh_id];
+    return FRT_OK;
+}
+int SceneBuilder::set_mesh_pose(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    if (!built) { error = "set_mesh_pose: scene is not built"; return FRT_ERR_STATE; }
+    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_pose: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_pose only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_pose: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
+    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u);
+    if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
+    const MeshSkin& k = mesh_skins[mesh_id];
+    const uint32_t nverts = (uint32_t)(k.bind.size() / 4);
+    std::vector<float> skinned(k.bind.size());
+    for (uint32_t v = 0; v < nverts; ++v) {
+        float m[4][16];
+        for (int s = 0; s < 4; ++s) memcpy(m[s], joint_mats + 16 * (size_t)k.joints[4 * (size_t)v + s], sizeof(m[s]));
+        skinned_position(&k.bind[4 * (size_t)v], m, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);
+    }
+    for (size_t c = 0; c < skinned.size(); ++c)
+        if (!std::isfinite(skinned[c])) { error = "set_mesh_pose: the skinned position of vertex " + std::to_string(c / 4) + " is not finite"; return FRT_ERR_INVALID_ARG; }
+    return set_mesh_vertices(mesh_id, skinned.data(), nullptr, nverts, flags);
+}
+
 // ---------------------------------------------------------------------------------------------- materials, lights, textures
 std::string check_material(const frt_material& m, size_t color_layers, size_t data_layers, size_t num_lights) {
     std::string bad;
@@ -813,7 +869,12 @@ int SceneBuilder::remove_meshes(uint32_t n, const uint32_t* ids) {
     attributes.swap(attrs); indices.swap(idx); mesh_infos.swap(infos);
     remove_elements(mesh_positions, gone); remove_elements(mesh_index_counts, gone);
     for (InstanceRec& in : instances) in.mesh_id = map[in.mesh_id];
-    return rebuild_or_undo(*this, undo, "remove_meshes");
+    const int rc = rebuild_or_undo(*this, undo, "remove_meshes");
+    if (rc == FRT_OK && !mesh_skins.empty()) {      // the skins follow the mesh ids (a call that was undone leaves them)
+        mesh_skins.resize(map.size());
+        remove_elements(mesh_skins, gone);
+    }
+    return rc;
 }
 int SceneBuilder::remove_lights(uint32_t n, const uint32_t* ids) {
     if (!built) { error = "remove_lights: scene is not built"; return FRT_ERR_STATE; }

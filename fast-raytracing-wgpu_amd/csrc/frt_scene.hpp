@@ -102,6 +102,16 @@ public:
     // flags (include/frt.h): FRT_DEFORM_RECOMPUTE_NORMALS replaces the normal of every vertex by the normalised sum of the area-weighted normals of the
     // triangles around it, in the new positions (frt_vertex_normal.hpp: recomputed_vertex_normal), and recomputes the shading records as if `attrs` had held it.
     int set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags = 0);
+    // Linear-blend skinning ("Skinning"). set_mesh_skin binds four joint indices and four weights per vertex to a mesh of a built scene; the
+    // mesh's object-space positions as they are at the call are copied and become the bind pose. No vertex and no triangle changes. joints4 == nullptr
+    // removes the skin. Refused, with nothing changed (check_mesh_skin): a vertex count that is not the mesh's, njoints == 0 or above 65,536 (a joint
+    // index is 16 bits), a joint index >= njoints, a weight that is negative or not finite.
+    int set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+    // Every vertex of the bind pose through frt_skin.hpp's skinned_position under the palette `joint_mats` (njoints column-major 4x4), then
+    // set_mesh_vertices(mesh_id, skinned, nullptr, nverts, flags). Refused, with nothing changed: a mesh without a skin, njoints that is not the bound
+    // count, a matrix entry or a skinned coordinate that is not finite, FRT_DEFORM_DEVICE, an unknown flag bit. A set_mesh_vertices on a skinned mesh
+    // leaves the bind pose as it is; remove_meshes drops the skin of a mesh that leaves and the survivors' skins follow their ids.
+    int set_mesh_pose(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags = 0);
     // What a built scene LOOKS like: no triangle, slot or box moves. Each is the specification its device form matches bit for bit,
     // validates everything before it applies anything, and leaves the scene equal to one built from scratch with the edited values.
     // Material ids[k] becomes mats[k], under the checks build() makes on a material (check_material).
@@ -144,6 +154,9 @@ public:
     std::vector<std::vector<float>> mesh_positions;
     std::vector<uint32_t> mesh_index_counts;
     std::vector<InstanceRec> instances;
+    // Per mesh its skin (set_mesh_skin); njoints == 0: none. Shorter than the mesh list while the last meshes have none.
+    struct MeshSkin { uint32_t njoints = 0; std::vector<uint16_t> joints; std::vector<float> weights, bind; };
+    std::vector<MeshSkin> mesh_skins;
     // built
     bool built = false;
     std::vector<TriRec> tris;
@@ -191,6 +204,11 @@ std::string check_instance_transforms(uint32_t n, const uint32_t* ids, const flo
 // Argument checks shared by the scene and the renderer form of set_mesh_vertices: "" when the vertices may be applied to a mesh of
 // `mesh_nverts` vertices (mesh_id < num_meshes is checked by the caller, which looks that count up).
 std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t mesh_nverts);
+// Argument checks shared by the scene and the renderer forms of set_mesh_skin and set_mesh_pose: "" when the call may be applied to a mesh of
+// `mesh_nverts` vertices, or under a skin of `bound_joints` joints (0: the mesh has no skin). Whether the skinned coordinates are finite is for the
+// caller to find out: the scene computes them, the renderer's validation launch reads them.
+std::string check_mesh_skin(const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t mesh_nverts);
+std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t bound_joints, bool host_memory = true);      // (device memory: the matrices are not read)
 // The vertex -> corner adjacency of one mesh in CSR form: corners[offsets[v] .. offsets[v + 1]) are the corners 3 * triangle + k whose index is v,
 // ascending. offsets has nverts + 1 entries, corners nidx (an index out of range, which the checks let into no mesh, names no vertex).
 void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, std::vector<uint32_t>& offsets, std::vector<uint32_t>& corners);

@@ -103,6 +103,16 @@ int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* 
 int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
     return frt_scene_set_mesh_vertices_ex(s, mesh_id, pos4, attrs, nverts, 0u);
 }
+int frt_scene_set_mesh_skin(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: null");
+    const int rc = s->b.set_mesh_skin(mesh_id, joints4, weights4, nverts, njoints);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: null");
+    const int rc = s->b.set_mesh_pose(mesh_id, joint_mats, njoints, flags);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_materials: null");
     const int rc = s->b.set_materials(n, ids, materials);

@@ -1,11 +1,11 @@
 // frt_scene_edit.hip — every call that edits a renderer's scene replica between frames (include/frt.h), host code only:
-//   moving instances, deforming meshes, the tree rebuild                    DESIGN.md §11
+//   moving instances, deforming and skinning meshes, the tree rebuild       DESIGN.md §11
 //   the material, light and texture edits                                   §13
 //   adding and removing instances                                           §14
 //   new meshes, materials, texture layers and lights                        §15
 //   removing meshes, materials, layers and lights                           §16
 // The calls that only read the replica (the ray queries, frt_renderer_read_scene, the statistics and counts) are in frt_scene_read.hip; the kernels in
-// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
+// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
 //
 // All edits share one scheme:
 //   - the call frame (edit_frame): the device guard, the stream order behind the finished frames, the body, `failed` on a HIP error;
@@ -454,6 +454,102 @@ static int ensure_adjacency(frt_renderer* r, uint32_t m) {
     f.adj[m] = static_cast<const uint32_t*>(d);
     return FRT_OK;
 }
+// What follows the checks of a deformation, inside its call frame: the staging, the launches and the refit. frt_renderer_set_mesh_vertices_ex (`pose` null)
+// and frt_renderer_set_mesh_pose run these lines. With `pose`, pos4 and attrs are ignored (no attributes): the mesh is skinned into RefitState::skinned by
+// frt_skin.hpp's kernel, and that buffer then takes the device-input route; a palette from the host rides in the call's pinned and device blocks.
+struct PoseInput { const float* mats; uint32_t njoints; bool device; };
+static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags, const PoseInput* pose) {
+    if (pose) attrs = nullptr;
+    RefitState& f = r->rf;
+    const bool dev = pose || (flags & FRT_DEFORM_DEVICE), recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    if (const int rc = sync_matrix_mirror(r)) return rc;      // (the instances' matrices are read below)
+    std::vector<DeformInstance> rec;
+    uint32_t work = 0;
+    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
+        const InstanceRec& in = f.inst[i];
+        if (in.mesh_id != mesh_id) continue;
+        DeformInstance d;
+        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
+        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
+        rec.push_back(d);
+    }
+    const bool shade = attrs || recompute;            // the shading records are written again: the device block holds the decoded normals
+    const bool host_decode = attrs && !recompute && !dev;
+    const size_t pos_bytes = dev ? 0 : (size_t)nverts * 16, attr_bytes = attrs && !dev ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
+    const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = shade ? (size_t)nverts * 16 : 0;
+    const size_t up_bytes = rec_bytes + (host_decode ? nrm_bytes : 0);      // what is copied into the device block
+    const size_t pal_bytes = pose && !pose->device ? (size_t)pose->njoints * 64 : 0;      // a host palette: behind both, in the pinned and in the device block
+    int rc;
+    if (pose) {
+        if ((rc = f.skinned.ensure(r, (size_t)nverts * 16))) return rc;
+        pos4 = f.skinned.as<float>();
+    }
+    if (recompute && (rc = ensure_adjacency(r, mesh_id))) return rc;
+    if (dev && !f.d_reject) {
+        void* d = nullptr;
+        if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
+        HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
+        f.d_reject = static_cast<uint32_t*>(d);
+    }
+    if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes + pal_bytes, rec_bytes + nrm_bytes + pal_bytes, r->stream))) return rc;
+    uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes; uint8_t* h_pal = h_up + up_bytes;
+    uint8_t* d_pal = f.def.d + rec_bytes + nrm_bytes;
+    float4* block = shade ? reinterpret_cast<float4*>(f.def.d + rec_bytes) : nullptr;
+    float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
+    const uint32_t cap_verts = pool_cap(r, kPoolVerts);
+    if ((uint64_t)f.pos_offset[mesh_id] + nverts > cap_verts || (uint64_t)f.attr_offset[mesh_id] + nverts > cap_verts)
+        return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the vertex pool");
+    if ((uint64_t)f.index_offset[mesh_id] + 3ull * f.mesh_tris[mesh_id] > pool_cap(r, kPoolIndices))
+        return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the index pool");
+    if (!dev) memcpy(h_pos, pos4, pos_bytes);
+    if (attr_bytes) memcpy(h_attr, attrs, attr_bytes);
+    if (host_decode) {
+        float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
+        for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
+    }
+    if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
+    if (pal_bytes) memcpy(h_pal, pose->mats, pal_bytes);
+    if (!dev) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
+    if (attr_bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
+    if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
+    if (host_decode && pool_normals)
+        HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
+    if (pal_bytes) HIP_TRY(hipMemcpyAsync(d_pal, h_pal, pal_bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = f.def.mark(r->stream))) return rc;
+    const uint32_t* reject = dev ? f.d_reject : nullptr;      // (host input was validated above: there is no flag to look at)
+    if (pose) {      // the skinned vertices are this call's device input: the flag is zeroed here, in front of the launch that may raise it first
+        const uint8_t* k = static_cast<const uint8_t*>(f.skins[mesh_id].buf.p);
+        HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
+        const SkinArgs sa{reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + (size_t)nverts * 16), reinterpret_cast<const uint2*>(k + (size_t)nverts * 32),
+                          pose->device ? reinterpret_cast<const float4*>(pose->mats) : reinterpret_cast<const float4*>(d_pal), f.skinned.as<float4>(),
+                          nverts, pose->njoints, (uint32_t)std::min<size_t>(f.skinned.bytes / 16, 0xFFFFFFFFu), pose->device ? 1u : 0u, f.d_reject};
+        HIP_TRY(launch_mesh_skin(sa, r->stream));
+    }
+    if (dev) {
+        DeformInput in{reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(attrs), nverts, f.pos_offset[mesh_id], f.attr_offset[mesh_id], cap_verts,
+                       const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
+                       attrs && !recompute ? block : nullptr, attrs && !recompute ? pool_normals : nullptr, f.d_reject};
+        HIP_TRY(launch_deform_input(in, r->stream, !pose));
+    }
+    if (recompute) {
+        NormalArgs na{f.adj[mesh_id], f.adj[mesh_id] + (nverts + 1u), nverts, 3u * f.mesh_tris[mesh_id], f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+                      cap_verts, pool_cap(r, kPoolIndices), f.d_pos, block, pool_normals, reject};
+#if FRT_EXPERIMENTS
+        const char* tri_pass = getenv("FRT_NORMALS_TRI_PASS");
+        if (tri_pass && atoi(tri_pass) != 0) {
+            if ((rc = f.tri_normals.ensure(r, (size_t)f.mesh_tris[mesh_id] * sizeof(float4)))) return rc;
+            na.tri_scratch = f.tri_normals.as<float4>();
+        }
+#endif
+        HIP_TRY(launch_vertex_normals(r->sv, na, r->stream));
+    }
+    if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
+    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+                 f.d_pos, block, f.d_slot_of, reject};
+    HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
+    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
+    return refit_levels(r);
+}
 // Host input: one pinned block holds what a call uploads, [positions | attributes | instance records | decoded normals]; the first two are copied into the
 // replica (the object-space positions the instance update reads, SceneView::attributes), the last two into the device block of RefitState::def, which is
 // reused in stream order and replaced, after a wait for the stream, only when it has to grow. With FRT_DEFORM_RECOMPUTE_NORMALS the host decodes nothing:
@@ -464,7 +560,7 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
     if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: unknown flag bits");
     if (mesh_id >= r->rf.vert_count.size())
         return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
-    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
     if (!dev) {
         const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
         if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + bad);
@@ -477,83 +573,73 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
         if (const int rc = check_device_pointer(r, pos4, (size_t)nverts * 16, 16, "set_mesh_vertices", "positions", "FRT_DEFORM_DEVICE")) return rc;
         if (attrs) if (const int rc = check_device_pointer(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), 16, "set_mesh_vertices", "attributes", "FRT_DEFORM_DEVICE")) return rc;
     }
-    return edit_frame(r, true, [&]() -> int {
-        RefitState& f = r->rf;
-        if (const int rc = sync_matrix_mirror(r)) return rc;      // (the instances' matrices are read below)
-        std::vector<DeformInstance> rec;
-        uint32_t work = 0;
-        for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
-            const InstanceRec& in = f.inst[i];
-            if (in.mesh_id != mesh_id) continue;
-            DeformInstance d;
-            d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
-            for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
-            rec.push_back(d);
-        }
-        const bool shade = attrs || recompute;            // the shading records are written again: the device block holds the decoded normals
-        const bool host_decode = attrs && !recompute && !dev;
-        const size_t pos_bytes = dev ? 0 : (size_t)nverts * 16, attr_bytes = attrs && !dev ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
-        const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = shade ? (size_t)nverts * 16 : 0;
-        const size_t up_bytes = rec_bytes + (host_decode ? nrm_bytes : 0);      // what is copied into the device block
-        int rc;
-        if (recompute && (rc = ensure_adjacency(r, mesh_id))) return rc;
-        if (dev && !f.d_reject) {
-            void* d = nullptr;
-            if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
-            HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
-            f.d_reject = static_cast<uint32_t*>(d);
-        }
-        if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes, rec_bytes + nrm_bytes, r->stream))) return rc;
-        uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes;
-        float4* block = shade ? reinterpret_cast<float4*>(f.def.d + rec_bytes) : nullptr;
-        float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
-        const uint32_t cap_verts = pool_cap(r, kPoolVerts);
-        if ((uint64_t)f.pos_offset[mesh_id] + nverts > cap_verts || (uint64_t)f.attr_offset[mesh_id] + nverts > cap_verts)
-            return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the vertex pool");
-        if ((uint64_t)f.index_offset[mesh_id] + 3ull * f.mesh_tris[mesh_id] > pool_cap(r, kPoolIndices))
-            return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the index pool");
-        if (!dev) memcpy(h_pos, pos4, pos_bytes);
-        if (attr_bytes) memcpy(h_attr, attrs, attr_bytes);
-        if (host_decode) {
-            float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
-            for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
-        }
-        if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
-        if (!dev) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
-        if (attr_bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
-        if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
-        if (host_decode && pool_normals)
-            HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
-        if ((rc = f.def.mark(r->stream))) return rc;
-        const uint32_t* reject = dev ? f.d_reject : nullptr;      // (host input was validated above: there is no flag to look at)
-        if (dev) {
-            DeformInput in{reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(attrs), nverts, f.pos_offset[mesh_id], f.attr_offset[mesh_id], cap_verts,
-                           const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
-                           attrs && !recompute ? block : nullptr, attrs && !recompute ? pool_normals : nullptr, f.d_reject};
-            HIP_TRY(launch_deform_input(in, r->stream));
-        }
-        if (recompute) {
-            NormalArgs na{f.adj[mesh_id], f.adj[mesh_id] + (nverts + 1u), nverts, 3u * f.mesh_tris[mesh_id], f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
-                          cap_verts, pool_cap(r, kPoolIndices), f.d_pos, block, pool_normals, reject};
-#if FRT_EXPERIMENTS
-            const char* tri_pass = getenv("FRT_NORMALS_TRI_PASS");
-            if (tri_pass && atoi(tri_pass) != 0) {
-                if ((rc = f.tri_normals.ensure(r, (size_t)f.mesh_tris[mesh_id] * sizeof(float4)))) return rc;
-                na.tri_scratch = f.tri_normals.as<float4>();
-            }
-#endif
-            HIP_TRY(launch_vertex_normals(r->sv, na, r->stream));
-        }
-        if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
-        DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
-                     f.d_pos, block, f.d_slot_of, reject};
-        HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
-        HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
-        return refit_levels(r);
-    });
+    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, mesh_id, pos4, attrs, nverts, flags, nullptr); });
 }
 int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
     return frt_renderer_set_mesh_vertices_ex(r, mesh_id, pos4, attrs, nverts, 0u);
+}
+
+// ------------------------------------------------------------------------------------------------ skinning ("Skinning")
+// The skin of mesh `m` leaves (behind a wait: a pose's kernel may still read it).
+static int drop_skin(frt_renderer* r, uint32_t m) {
+    RefitState& f = r->rf;
+    if (m >= f.skins.size() || !f.skins[m].buf.p) return FRT_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    scene_free(r, f.skins[m].buf.p);
+    f.skins[m] = RefitState::MeshSkin();
+    return FRT_OK;
+}
+// Joints and weights go through the pinned block of RefitState::skin_up into the mesh's own buffer; the bind pose is copied there from the replica's
+// object-space positions on the stream, behind every deformation enqueued so far. The speculation is kept: nothing a frame reads changes.
+int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    if (const int rc = check_entry(r, "set_mesh_skin", kEditChecks | kRefit)) return rc;
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (joints4) {
+        const std::string bad = check_mesh_skin(joints4, weights4, nverts, njoints, r->rf.vert_count[mesh_id]);
+        if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: " + bad);
+    }
+    return edit_frame(r, false, [&]() -> int {
+        RefitState& f = r->rf;
+        if (!joints4) return drop_skin(r, mesh_id);
+        if (f.skins.size() <= mesh_id) f.skins.resize((size_t)mesh_id + 1u);
+        RefitState::MeshSkin& k = f.skins[mesh_id];
+        const size_t pos_bytes = (size_t)nverts * 16, joint_bytes = (size_t)nverts * 8;
+        int rc;
+        if ((uint64_t)f.pos_offset[mesh_id] + nverts > pool_cap(r, kPoolVerts)) return fail(FRT_ERR_STATE, "set_mesh_skin: the mesh does not lie inside the vertex pool");
+        k.njoints = 0;      // (a call that fails below leaves the mesh without a skin)
+        if ((rc = k.buf.ensure(r, 2 * pos_bytes + joint_bytes))) return rc;
+        if ((rc = f.skin_up.reserve(pos_bytes + joint_bytes, 0, r->stream))) return rc;
+        memcpy(f.skin_up.h, weights4, pos_bytes);
+        memcpy(f.skin_up.h + pos_bytes, joints4, joint_bytes);
+        uint8_t* d = k.buf.as<uint8_t>();      // [bind positions | weights | joints]
+        if (nverts) {
+            HIP_TRY(hipMemcpyAsync(d, f.d_pos + f.pos_offset[mesh_id], pos_bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_TRY(hipMemcpyAsync(d + pos_bytes, f.skin_up.h, pos_bytes + joint_bytes, hipMemcpyHostToDevice, r->stream));
+        }
+        if ((rc = f.skin_up.mark(r->stream))) return rc;
+        k.njoints = njoints;
+        return FRT_OK;
+    });
+}
+// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what this call adds runs in front of the device-input route.
+int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    if (const int rc = check_entry(r, "set_mesh_pose", kEditChecks | kRefit)) return rc;
+    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: unknown flag bits");
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
+    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].njoints : 0u, !dev);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
+    if (dev) {      // the palette's finiteness is the skin launch's to check
+        DeviceGuard guard(r->device);
+        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+        if (const int rc = check_device_pointer(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices", "FRT_DEFORM_DEVICE")) return rc;
+    }
+    const PoseInput pose{joint_mats, njoints, dev};
+    return edit_frame(r, true, [&]() -> int {
+        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, &pose);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ materials, lights, textures
@@ -1173,6 +1259,12 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             scene_free(r, f.adj[g]);
         }
         remove_elements(f.adj, gone);
+        // and so do the skins
+        if (!f.skins.empty()) {
+            f.skins.resize(old_meshes);
+            for (uint32_t g : gone) if ((rc = drop_skin(r, g))) return rc;
+            remove_elements(f.skins, gone);
+        }
         drop_transform_tables(r, false);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];
         return FRT_OK;

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE, TRANSFORM_DEVICE)
-from .scene import (transform_args, set_mesh_vertices_call, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
+from .scene import (transform_args, set_mesh_vertices_call, set_mesh_skin_call, set_mesh_pose_call, _num_joints, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
                     pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
 
@@ -331,6 +331,39 @@ class Renderer(_HostQueries, _SceneGrowth):
         self._release_held()
         self._held.append((done, positions, attributes))
 
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
+        """Bind a skin to one mesh of this renderer's scene replica (include/frt.h: frt_renderer_set_mesh_skin): `joints` [n, 4] integers, `weights`
+        [n, 4] float32, copied during the call; the replica's positions of the mesh, as the renderer's stream finds them, become the bind pose.
+        joints=None removes the skin; num_joints defaults to the largest joint index + 1. The host scene is not changed."""
+        set_mesh_skin_call("frt_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
+        """Pose a skinned mesh of this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_pose): one column-major 4x4 per
+        joint, [J, 16] or [J, 4, 4]. One kernel skins the bind pose on the device; the result is applied as set_mesh_vertices applies device
+        positions. normals="recompute" (the default: a posed mesh lit with its bind-pose normals is wrong) or "keep".
+        numpy (or array-like) in: checked and copied during the call. A contiguous float32 torch tensor on the renderer's device in: the protocol of
+        the device form of set_mesh_vertices — the renderer's stream waits for the caller's current stream, the call is only enqueued, and the
+        renderer keeps a reference to the tensor until that stream has passed the call. A non-finite matrix entry of a device palette, and for
+        either kind a pose that overflows, rejects the call on the device: nothing is applied and deform_rejects() counts it."""
+        if not _is_device_tensor(joint_matrices):
+            return set_mesh_pose_call("frt_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
+        import torch
+        flags = deform_flags(normals) | DEFORM_DEVICE
+        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+            raise FrtError("mesh id must be an unsigned 32-bit index")
+        t = joint_matrices
+        if t.device.index != self.device:
+            raise FrtError(f"set_mesh_pose: joint matrices are on {t.device}, the renderer on device {self.device}")
+        if t.dtype != torch.float32 or not t.is_contiguous() or not ((t.dim() == 2 and t.shape[1] == 16) or (t.dim() == 3 and tuple(t.shape[1:]) == (4, 4))):
+            raise FrtError("set_mesh_pose: device joint matrices must be a contiguous float32 tensor shaped [J, 16] or [J, 4, 4]")
+        s = self._torch_stream(torch, t.device)
+        s.wait_stream(torch.cuda.current_stream(t.device))
+        check(lib().frt_renderer_set_mesh_pose(self._h, int(mesh_id), t.data_ptr(), t.shape[0], flags))
+        done = torch.cuda.Event()
+        done.record(s)
+        self._release_held()
+        self._held.append((done, t))
+
     def _release_held(self, all_done=False):
         """Drop the references to device tensors whose call the stream has passed (all of them after a sync)."""
         if self._held:
@@ -601,6 +634,16 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         if any(_is_device_tensor(x) for x in (positions, attributes)):
             raise FrtError("set_mesh_vertices: a MultiRenderer takes host arrays only (its replicas live on different devices)")
         set_mesh_vertices_call("frt_multi_renderer_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
+
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
+        """Renderer.set_mesh_skin on every strip's scene replica."""
+        set_mesh_skin_call("frt_multi_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
+        """Renderer.set_mesh_pose on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
+        if _is_device_tensor(joint_matrices):
+            raise FrtError("set_mesh_pose: a MultiRenderer takes host arrays only (its replicas live on different devices)")
+        set_mesh_pose_call("frt_multi_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
 
     # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it; DESIGN.md section 13): asynchronous,
     # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).

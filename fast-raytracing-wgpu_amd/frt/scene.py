@@ -59,6 +59,57 @@ def set_mesh_vertices_call(name, handle, mesh_id, positions, attributes, normals
         check(getattr(lib(), name)(handle, mid, pos.ctypes.data, a, n))
 
 
+def mesh_skin_args(mesh_id, joints, weights):
+    """(mesh id, joints, weights, vertex count) for the *_set_mesh_skin calls: `joints` [n, 4] integers (converted to uint16 after a range check),
+    `weights` [n, 4] float32."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    j = np.asarray(joints)
+    if j.ndim != 2 or j.shape[1] != 4 or j.dtype.kind not in "iu":
+        raise FrtError("set_mesh_skin: joints must be integers shaped [n, 4]")
+    if j.size and (int(j.min()) < 0 or int(j.max()) > 0xFFFF):
+        raise FrtError("set_mesh_skin: a joint index is an unsigned 16-bit number")
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.ndim != 2 or w.shape[1] != 4 or w.shape[0] != j.shape[0]:
+        raise FrtError(f"set_mesh_skin: weights must be shaped [{j.shape[0]}, 4], like the joints")
+    return int(mesh_id), np.ascontiguousarray(j.astype(np.uint16)), w, j.shape[0]
+
+
+def _num_joints(joints, num_joints):
+    """The joint count a bind call states: `num_joints`, or the largest joint index + 1."""
+    if num_joints is not None or joints is None:
+        return int(num_joints or 0)
+    j = np.asarray(joints)
+    return int(j.max()) + 1 if j.size else 0
+
+
+def set_mesh_skin_call(name, handle, mesh_id, joints, weights, njoints):
+    """One bind call through the entry point `name`; joints None removes the skin."""
+    if joints is None:
+        return check(getattr(lib(), name)(handle, int(mesh_id), None, None, 0, 0))
+    mid, j, w, n = mesh_skin_args(mesh_id, joints, weights)
+    check(getattr(lib(), name)(handle, mid, j.ctypes.data, w.ctypes.data, n, int(njoints)))
+
+
+def mesh_pose_args(mesh_id, joint_matrices):
+    """(mesh id, [J, 16] float32 matrices, J) for the host form of the *_set_mesh_pose calls: `joint_matrices` one column-major 4x4 per joint, shaped
+    [J, 16] or [J, 4, 4]."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    m = np.ascontiguousarray(joint_matrices, np.float32)
+    if not (m.ndim == 2 and m.shape[1] == 16) and not (m.ndim == 3 and m.shape[1:] == (4, 4)):
+        raise FrtError("set_mesh_pose: joint matrices must be shaped [J, 16] or [J, 4, 4]")
+    m = m.reshape(-1, 16)
+    return int(mesh_id), m, m.shape[0]
+
+
+def set_mesh_pose_call(name, handle, mesh_id, joint_matrices, normals):
+    """One host-array pose through the entry point `name`."""
+    flags = deform_flags(normals)
+    mid, m, n = mesh_pose_args(mesh_id, joint_matrices)
+    check(getattr(lib(), name)(handle, mid, m.ctypes.data, n, flags))
+
+
 def material_args(ids, materials):
     """(n, ids, [n, 16] uint32 material records) for the *_set_materials calls: `ids` an int or a sequence, `materials` one frt.Material (or a 64-byte
     row of get("materials")) per id."""
@@ -358,6 +409,17 @@ class SceneBuilder:
     # normals="recompute": the vertex normals are computed from the new positions (frt_scene_set_mesh_vertices_ex, FRT_DEFORM_RECOMPUTE_NORMALS).
     def set_mesh_vertices(self, mesh_id, positions, attributes=None, normals="keep"):
         set_mesh_vertices_call("frt_scene_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
+        return self
+
+    # Linear-blend skinning (include/frt.h: frt_scene_set_mesh_skin, frt_scene_set_mesh_pose). set_mesh_skin binds four joints and four weights per vertex;
+    # the mesh's positions at the call become the bind pose (joints=None removes the skin; num_joints defaults to the largest index + 1). set_mesh_pose
+    # skins the bind pose under one column-major 4x4 per joint and applies the result as set_mesh_vertices does. Host copy only.
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
+        set_mesh_skin_call("frt_scene_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+        return self
+
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
+        set_mesh_pose_call("frt_scene_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
         return self
 
     # ---- what the built scene looks like (include/frt.h: frt_scene_set_materials and the three calls after it). Host copy only.

@@ -170,6 +170,22 @@ int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos
 #define FRT_DEFORM_RECOMPUTE_NORMALS 1u
 #define FRT_DEFORM_DEVICE 2u
 int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
+/* Linear-blend skinning ("Skinning"). A skin is bound to a mesh of a BUILT scene once; a pose is then only the joint palette.
+ * The contract, f32 without contraction and without a hand-written fma: for vertex v with bind position p = (x, y, z, w), joint indices j[0..3], weights
+ * w[0..3] and the palette's column-major 4x4 matrices M (the layout of an instance transform; row 3 is ignored), for slot k and row r in 0..2
+ *   q_k[r] = ((M_jk[r] * x + M_jk[4 + r] * y) + M_jk[8 + r] * z) + M_jk[12 + r]            (the expression of an instance's world-space triangle)
+ *   out[r] = ((w0 * q_0[r] + w1 * q_1[r]) + w2 * q_2[r]) + w3 * q_3[r]
+ * All four terms are always evaluated (a weight of 0 is not skipped), weights are used as given (not renormalised), out.w is the bind pose's w.
+ * set_mesh_skin: joints4 [4 nverts] and weights4 [4 nverts] are copied, and so are the mesh's object-space positions as they are at the call: they
+ * become the bind pose. No vertex and no triangle changes. joints4 == NULL removes the skin. FRT_ERR_STATE: scene not built; FRT_ERR_INVALID_ARG, nothing
+ * changed: mesh id out of range, nverts not the mesh's count, njoints == 0 or above 65536, a joint index >= njoints, a weight that is negative or not finite.
+ * set_mesh_pose: every vertex by the contract from the bind pose under joint_mats [16 njoints], then exactly
+ * frt_scene_set_mesh_vertices_ex(s, mesh_id, skinned, NULL, nverts, flags & FRT_DEFORM_RECOMPUTE_NORMALS). FRT_ERR_INVALID_ARG, nothing changed: a mesh
+ * without a skin, njoints not the bound count, a non-finite matrix entry, a non-finite skinned coordinate (a finite pose can overflow), an unknown flag
+ * bit, FRT_DEFORM_DEVICE. A later frt_scene_set_mesh_vertices on a skinned mesh is allowed and leaves the bind pose untouched; frt_scene_remove_meshes
+ * drops the skin of a mesh that leaves, and the survivors' skins follow their ids. */
+int frt_scene_set_mesh_skin(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* What a BUILT scene looks like: four edits that move no triangle, slot or box. Common rules: FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG: an id or layer out of range, a null pointer with n > 0, a failed check; everything is validated before anything is applied, so
  * a refused call changes nothing. n == 0: FRT_OK. An id given twice ends with its last value. Afterwards the scene equals one built from scratch
@@ -430,6 +446,19 @@ int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const floa
  * changes nothing of the replica (its kernels return at once; the refit that follows reproduces the same boxes) and adds one to a counter that
  * frt_renderer_deform_rejects reads. With attrs == NULL and FRT_DEFORM_RECOMPUTE_NORMALS no attribute is read from the caller. */
 int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
+/* Skin a mesh of this renderer's scene replica ("Skinning"): arguments, checks and results of frt_scene_set_mesh_skin and
+ * frt_scene_set_mesh_pose, bit for bit, under the ordering and state rules of frt_renderer_set_mesh_vertices.
+ * set_mesh_skin: joints and weights are copied during the call, through pinned memory, into device buffers kept per mesh (8 + 16 bytes per vertex); the
+ * bind pose is a device-to-device copy of the replica's object-space positions as the stream finds them (16 bytes per vertex, no read-back). The buffers
+ * follow frt_renderer_remove_meshes.
+ * set_mesh_pose: flags are FRT_DEFORM_RECOMPUTE_NORMALS and FRT_DEFORM_DEVICE. Without FRT_DEFORM_DEVICE joint_mats is host memory: checked for finiteness
+ * (FRT_ERR_INVALID_ARG) and copied during the call. With it, joint_mats is 16-byte aligned device memory of the renderer's device, 64 njoints bytes, under
+ * the rules of the device form of frt_renderer_set_mesh_vertices_ex. One kernel skins the mesh into a scratch buffer of the renderer; from there the
+ * vertices take the device-input route of frt_renderer_set_mesh_vertices_ex. What the host cannot see is rejected on the device as data: a non-finite
+ * entry of a device palette (in a joint no vertex names too) and, for either kind of palette, a skinned coordinate that overflowed. Such a call changes
+ * nothing of the replica and adds one to the counter frt_renderer_deform_rejects reads. */
+int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* Device-input deformations this renderer has rejected since it was created (non-finite input). Waits for the main stream. */
 int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
@@ -609,6 +638,9 @@ int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts);
 /* ... with flags. FRT_DEFORM_DEVICE is refused (FRT_ERR_INVALID_ARG): the strips' replicas live on different devices. */
 int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
+/* frt_renderer_set_mesh_skin and frt_renderer_set_mesh_pose on every strip's replica, between frames. FRT_DEFORM_DEVICE is refused. */
+int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* frt_renderer_set_materials, _set_instance_materials, _set_light_emission and _set_texture on every strip's replica, between frames */
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials);
 int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
