@@ -130,6 +130,10 @@ void orc_trace_any(void* sp, int use_bvh, uint32_t n, const float* o, const floa
         occ_out[i] = tr.any(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmin, tmax[i], st);
 }
 
+// ---- shading probes (orc_render.hpp: shade_probe)
+int orc_shade_probe(int op, const void* lights, uint32_t nlights, const void* in, void* out, uint32_t n) { return shade_probe(op, lights, nlights, in, out, n); }
+void orc_shade_probe_sizes(uint32_t* sizes) { shade_probe_sizes(sizes); }
+
 // ---- renderer
 void* orc_renderer_create(void* scene, uint32_t w, uint32_t h, uint32_t max_depth, int use_bvh, int nthreads) {
     return new Renderer((Scene*)scene, w, h, max_depth, use_bvh != 0, nthreads);

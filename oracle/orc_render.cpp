@@ -91,6 +91,9 @@ struct HitInfo {   // restir.wgsl:81-90
 struct BsdfSample { vec3 wi; float pdf; vec3 weight; bool is_delta; };
 struct LightSample { vec3 pos, normal; float pdf; vec4 emission; };
 struct PathResult { vec3 radiance; bool valid_v1; vec3 v1_pos, v1_normal; };
+// Probe of the NEE block (shade_probe below): the shadow ray is not traced; its request is recorded and the caller's answer returned.
+// state: 0 the block was skipped, 1 a light was sampled and no ray asked for (zero term), 2 a ray was asked for, 3 lit without a ray (variant 1's early-out)
+struct ShadowProbe { bool visible; uint32_t state; vec3 o, d; float tmin, tmax; };
 
 struct Ctx {
     const Renderer& R;
@@ -100,6 +103,7 @@ struct Ctx {
     TraceStats st;
     uint32_t rng_seed = 0;      // var<private> rng_seed (restir.wgsl:130)
     int variant = 0;            // 0 = restir.wgsl, 1 = restir_spatial.wgsl
+    ShadowProbe* probe = nullptr;   // shade_probe only
     uint32_t cur;               // frame_count % 2
     Ctx(const Renderer& r, const CameraUniform& c) : R(r), S(*r.scene), tracer(*r.scene, r.use_bvh), cam(c), cur(r.frame_count % 2) {}
 
@@ -275,9 +279,9 @@ static BsdfSample sample_bsdf(Ctx& c, vec3 wo, const HitInfo& hit, const Materia
 // restir.wgsl:375-381 (variant 0) vs restir_spatial.wgsl:380-400 (variant 1)
 static bool trace_shadow_ray(Ctx& c, vec3 origin, vec3 dir, float dist) {
     float t_max = fmax_(dist * 0.999f, 0.0f);
-    if (c.variant == 0) return !c.tracer.any(origin, dir, 0.001f, t_max, c.st);
-    float t_min = 0.0001f;
-    if (t_min >= t_max) return true;
+    float t_min = c.variant == 0 ? 0.001f : 0.0001f;
+    if (c.variant == 1 && t_min >= t_max) { if (c.probe) c.probe->state = 3u; return true; }
+    if (c.probe) { c.probe->state = 2u; c.probe->o = origin; c.probe->d = dir; c.probe->tmin = t_min; c.probe->tmax = t_max; return c.probe->visible; }
     return !c.tracer.any(origin, dir, t_min, t_max, c.st);
 }
 // restir.wgsl:383-441 — attribute fetch/interpolation for a committed intersection
@@ -345,6 +349,7 @@ static vec3 nee(Ctx& c, const HitInfo& hit, vec3 wo, const Material& mat, vec3 b
     if (nl > 0u) {
         uint32_t light_idx = (uint32_t)(c.rand() * (float)nl);
         if (light_idx < nl) {
+            if (c.probe) c.probe->state = 1u;
             LightSample ls = sample_light(c, light_idx);
             float pdf_nee = ls.pdf * (1.0f / (float)nl);
             float p_bsdf = eval_pdf(hit.ffnormal, normalize(ls.pos - hit.pos), wo, mat, base_color);
@@ -354,6 +359,18 @@ static vec3 nee(Ctx& c, const HitInfo& hit, vec3 wo, const Material& mat, vec3 b
         }
     }
     return add;
+}
+// restir.wgsl:593-603: Russian roulette from depth 3 on, then the next ray's origin. false: the path ends (break).
+static bool roulette_and_origin(Ctx& c, uint32_t depth, vec3& throughput, const HitInfo& hit, vec3 next_dir, vec3& origin) {
+    if (depth >= 3u) {
+        float p = fmax_(throughput.x, fmax_(throughput.y, throughput.z));
+        float survival_prob = clamp_(p, 0.05f, 0.95f);
+        if (c.rand() > survival_prob) return false;
+        throughput /= survival_prob;
+    }
+    vec3 offset_dir = hit.ffnormal * sign_(dot(hit.ffnormal, next_dir));
+    origin = hit.pos + offset_dir * 0.001f;
+    return true;
 }
 
 // restir.wgsl:460-737 (variant 0) / restir_spatial.wgsl:480-762 (variant 1)
@@ -435,14 +452,8 @@ static PathResult trace_path(Ctx& c, int cx, int cy, uint32_t seed) {
     next_dir = sc.wi;
 
     for (uint32_t depth = 1u; depth < R.max_depth; depth++) {   // :590
-        if (depth >= 3u) {
-            float p = fmax_(throughput.x, fmax_(throughput.y, throughput.z));
-            float survival_prob = clamp_(p, 0.05f, 0.95f);
-            if (c.rand() > survival_prob) break;
-            throughput /= survival_prob;
-        }
-        vec3 offset_dir = hit.ffnormal * sign_(dot(hit.ffnormal, next_dir));
-        vec3 origin = hit.pos + offset_dir * 0.001f;
+        vec3 origin;
+        if (!roulette_and_origin(c, depth, throughput, hit, next_dir, origin)) break;
         Hit h = c.tracer.closest(origin, next_dir, 0.001f, 100.0f, c.st);
         if (!h.hit) break;
         hit = reconstruct_geometry_hit(c, h, origin, next_dir);
@@ -497,6 +508,136 @@ static PathResult trace_path(Ctx& c, int cx, int cy, uint32_t seed) {
     }
     result.radiance = accumulated_color;
     return result;
+}
+
+// ------------------------------------------------------------------ shade_probe (tests/test_wgsl_f64_shade*.py)
+// One call of one of the functions above per case, from flat input records into flat output records; the shadow ray's answer is an input. Record layouts
+// (little-endian, every field a 4-byte word, no padding; the numpy dtypes of tests/_shade_probe.py are the definition the tests compare the sizes with):
+//   light (64 B, = LightUniform)
+//   0 basis        n[3]                                                                         -> tangent[3] bitangent[3]
+//   1 fresnel      f0[3] v_dot_h                                                                -> f[3]
+//   2 reflectance  cosine ref_idx                                                               -> r
+//   3 ndf          n_dot_h roughness                                                            -> d
+//   4 g1           n_dot_v roughness                                                            -> g
+//   5 vndf         wo[3] roughness u[2]                                                         -> wm[3]
+//   6 light        light rng:u32                                                                -> pos[3] normal[3] pdf emission[4] rng:u32
+//   7 eval_pdf     n[3] wi[3] wo[3] roughness metallic transmission ior base[3]                 -> pdf
+//   8 eval_bsdf    (as eval_pdf)                                                                -> f[3]
+//   9 unit_vector  rng:u32                                                                      -> v[3] rng:u32
+//  10 sample_bsdf  wo[3] ffn[3] front:u32 roughness metallic transmission ior base[3] rng:u32   -> wi[3] pdf weight[3] rng:u32
+//  11 / 12 nee (variant 0 / 1)  num_lights:u32 pos[3] ffn[3] wo[3] roughness metallic transmission ior base[3] visible:u32 rng:u32
+//                                                                                               -> nee:u32 want:u32 o[3] d[3] tmin tmax direct[3] rng:u32
+//  13 roulette     depth:u32 throughput[3] ffn[3] next_dir[3] pos[3] rng:u32                    -> survived:u32 throughput[3] origin[3] rng:u32
+namespace {
+struct PMat { float roughness, metallic, transmission, ior; };
+struct PBasisIn { float n[3]; };                            struct PBasisOut { float t[3], b[3]; };
+struct PFresnelIn { float f0[3], v_dot_h; };                struct PVec3Out { float v[3]; };
+struct PPairIn { float a, b; };                             struct PScalarOut { float v; };
+struct PVndfIn { float wo[3], roughness, u[2]; };
+struct PLightIn { LightUniform light; uint32_t rng; };      struct PLightOut { float pos[3], normal[3], pdf, emission[4]; uint32_t rng; };
+struct PEvalIn { float n[3], wi[3], wo[3]; PMat m; float base[3]; };
+struct PUnitIn { uint32_t rng; };                           struct PUnitOut { float v[3]; uint32_t rng; };
+struct PSampleIn { float wo[3], ffn[3]; uint32_t front; PMat m; float base[3]; uint32_t rng; };
+struct PSampleOut { float wi[3], pdf, weight[3]; uint32_t rng; };
+struct PNeeIn { uint32_t num_lights; float pos[3], ffn[3], wo[3]; PMat m; float base[3]; uint32_t visible, rng; };
+struct PNeeOut { uint32_t nee, want; float o[3], d[3], tmin, tmax, direct[3]; uint32_t rng; };
+struct PRouletteIn { uint32_t depth; float throughput[3], ffn[3], next_dir[3], pos[3]; uint32_t rng; };
+struct PRouletteOut { uint32_t survived; float throughput[3], origin[3]; uint32_t rng; };
+const uint32_t kProbeSizes[SHADE_PROBE_OPS][2] = {
+    {sizeof(PBasisIn), sizeof(PBasisOut)}, {sizeof(PFresnelIn), sizeof(PVec3Out)}, {sizeof(PPairIn), sizeof(PScalarOut)}, {sizeof(PPairIn), sizeof(PScalarOut)},
+    {sizeof(PPairIn), sizeof(PScalarOut)}, {sizeof(PVndfIn), sizeof(PVec3Out)}, {sizeof(PLightIn), sizeof(PLightOut)}, {sizeof(PEvalIn), sizeof(PScalarOut)},
+    {sizeof(PEvalIn), sizeof(PVec3Out)}, {sizeof(PUnitIn), sizeof(PUnitOut)}, {sizeof(PSampleIn), sizeof(PSampleOut)}, {sizeof(PNeeIn), sizeof(PNeeOut)},
+    {sizeof(PNeeIn), sizeof(PNeeOut)}, {sizeof(PRouletteIn), sizeof(PRouletteOut)}};
+inline vec3 ld3(const float* p) { return V3(p[0], p[1], p[2]); }
+inline void st3(float* p, vec3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+inline Material probe_material(const PMat& m) {
+    Material mat{}; mat.roughness = m.roughness; mat.metallic = m.metallic; mat.transmission = m.transmission; mat.ior = m.ior; mat.light_index = -1;
+    return mat;
+}
+}
+void shade_probe_sizes(uint32_t* sizes) {
+    for (int op = 0; op < SHADE_PROBE_OPS; ++op) { sizes[2 * op] = kProbeSizes[op][0]; sizes[2 * op + 1] = kProbeSizes[op][1]; }
+}
+int shade_probe(int op, const void* lights, uint32_t nlights, const void* in_v, void* out_v, uint32_t n) {
+    if (op < 0 || op >= SHADE_PROBE_OPS) return -1;
+    Scene S;
+    if (op == 11 || op == 12) {
+        const LightUniform* L = static_cast<const LightUniform*>(lights);
+        S.lights.assign(L, L + nlights);
+        for (uint32_t i = 0; i < n; ++i) if (static_cast<const PNeeIn*>(in_v)[i].num_lights > nlights) return -1;
+    } else S.lights.resize(1);
+    Renderer R(&S, 1u, 1u, 8u, false, 1);
+    CameraUniform cam{};
+    for (uint32_t i = 0; i < n; ++i) {
+        Ctx c(R, cam);
+        switch (op) {
+        case 0: {
+            PBasisOut& o = static_cast<PBasisOut*>(out_v)[i];
+            vec3 t, b; make_orthonormal_basis(ld3(static_cast<const PBasisIn*>(in_v)[i].n), t, b); st3(o.t, t); st3(o.b, b);
+        } break;
+        case 1: {
+            const PFresnelIn& in = static_cast<const PFresnelIn*>(in_v)[i];
+            st3(static_cast<PVec3Out*>(out_v)[i].v, fresnel_schlick(ld3(in.f0), in.v_dot_h));
+        } break;
+        case 2: case 3: case 4: {
+            const PPairIn& in = static_cast<const PPairIn*>(in_v)[i];
+            static_cast<PScalarOut*>(out_v)[i].v = op == 2 ? reflectance(in.a, in.b) : op == 3 ? ndf_ggx(in.a, in.b) : geometry_schlick_ggx(in.a, in.b);
+        } break;
+        case 5: {
+            const PVndfIn& in = static_cast<const PVndfIn*>(in_v)[i];
+            st3(static_cast<PVec3Out*>(out_v)[i].v, sample_ggx_vndf(ld3(in.wo), in.roughness, V2(in.u[0], in.u[1])));
+        } break;
+        case 6: {
+            const PLightIn& in = static_cast<const PLightIn*>(in_v)[i]; PLightOut& o = static_cast<PLightOut*>(out_v)[i];
+            S.lights[0] = in.light;
+            c.rng_seed = in.rng;
+            LightSample s = sample_light(c, 0u);
+            st3(o.pos, s.pos); st3(o.normal, s.normal); o.pdf = s.pdf;
+            o.emission[0] = s.emission.x; o.emission[1] = s.emission.y; o.emission[2] = s.emission.z; o.emission[3] = s.emission.w; o.rng = c.rng_seed;
+        } break;
+        case 7: case 8: {
+            const PEvalIn& in = static_cast<const PEvalIn*>(in_v)[i];
+            Material mat = probe_material(in.m);
+            if (op == 7) static_cast<PScalarOut*>(out_v)[i].v = eval_pdf(ld3(in.n), ld3(in.wi), ld3(in.wo), mat, ld3(in.base));
+            else st3(static_cast<PVec3Out*>(out_v)[i].v, eval_bsdf(ld3(in.n), ld3(in.wi), ld3(in.wo), mat, ld3(in.base)));
+        } break;
+        case 9: {
+            PUnitOut& o = static_cast<PUnitOut*>(out_v)[i];
+            c.rng_seed = static_cast<const PUnitIn*>(in_v)[i].rng;
+            st3(o.v, c.random_unit_vector()); o.rng = c.rng_seed;
+        } break;
+        case 10: {
+            const PSampleIn& in = static_cast<const PSampleIn*>(in_v)[i]; PSampleOut& o = static_cast<PSampleOut*>(out_v)[i];
+            HitInfo hit{}; hit.ffnormal = ld3(in.ffn); hit.normal = hit.ffnormal; hit.front_face = in.front != 0u;
+            c.rng_seed = in.rng;
+            BsdfSample s = sample_bsdf(c, ld3(in.wo), hit, probe_material(in.m), ld3(in.base));
+            st3(o.wi, s.wi); o.pdf = s.pdf; st3(o.weight, s.weight); o.rng = c.rng_seed;
+        } break;
+        case 11: case 12: {
+            const PNeeIn& in = static_cast<const PNeeIn*>(in_v)[i]; PNeeOut& o = static_cast<PNeeOut*>(out_v)[i];
+            CameraUniform cam_i{}; cam_i.num_lights = in.num_lights;
+            Ctx cn(R, cam_i);
+            cn.variant = op == 11 ? 0 : 1;
+            ShadowProbe sp{}; sp.visible = in.visible != 0u; sp.o = V3(0.0f); sp.d = V3(0.0f);
+            cn.probe = &sp;
+            cn.rng_seed = in.rng;
+            HitInfo hit{}; hit.pos = ld3(in.pos); hit.ffnormal = ld3(in.ffn); hit.normal = hit.ffnormal; hit.front_face = true;
+            vec3 direct = V3(0.0f);
+            direct += nee(cn, hit, ld3(in.wo), probe_material(in.m), ld3(in.base), V3(1.0f));      // accumulated_color += ..., as trace_path adds it
+            o.nee = sp.state; o.want = sp.state == 2u ? 1u : 0u; st3(o.o, sp.o); st3(o.d, sp.d); o.tmin = sp.tmin; o.tmax = sp.tmax;
+            st3(o.direct, direct); o.rng = cn.rng_seed;
+        } break;
+        case 13: {
+            const PRouletteIn& in = static_cast<const PRouletteIn*>(in_v)[i]; PRouletteOut& o = static_cast<PRouletteOut*>(out_v)[i];
+            HitInfo hit{}; hit.pos = ld3(in.pos); hit.ffnormal = ld3(in.ffn);
+            vec3 throughput = ld3(in.throughput), origin = V3(0.0f);
+            c.rng_seed = in.rng;
+            o.survived = roulette_and_origin(c, in.depth, throughput, hit, ld3(in.next_dir), origin) ? 1u : 0u;
+            st3(o.throughput, throughput); st3(o.origin, origin); o.rng = c.rng_seed;
+        } break;
+        }
+    }
+    return 0;
 }
 
 // restir.wgsl:746-756

@@ -42,4 +42,11 @@ struct Renderer {
     void end_frame() { frame_count += 1; }
 };
 
+// Probes of the shading functions of orc_render.cpp, one call per case (tests/test_wgsl_f64_shade*.py; record layouts next to the definition).
+// op: 0 basis, 1 fresnel, 2 reflectance, 3 ndf, 4 g1, 5 vndf, 6 light, 7 eval_pdf, 8 eval_bsdf, 9 unit_vector, 10 sample_bsdf, 11 nee (restir.wgsl),
+// 12 nee (restir_spatial.wgsl's shadow ray), 13 roulette. lights / nlights: the light table of the nee operations. -1: bad operation or light count.
+enum { SHADE_PROBE_OPS = 14 };
+int shade_probe(int op, const void* lights, uint32_t nlights, const void* in, void* out, uint32_t n);
+void shade_probe_sizes(uint32_t* sizes);      // sizes[2 * op], sizes[2 * op + 1]: input and output record size
+
 } // namespace orc

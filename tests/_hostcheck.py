@@ -20,6 +20,8 @@ class HostCheck:
         L.hc_trace.argtypes = [P, C.c_int, U32, P, P, C.c_float, P, P, P, P, P, C.c_int]
         L.hc_quad_stats.argtypes = [P, P]
         L.hc_wide8_stats.argtypes = [P, P]
+        L.hc_shade_probe.restype = C.c_int; L.hc_shade_probe.argtypes = [C.c_int, P, P, P, U32]
+        L.hc_shade_probe_sizes.argtypes = [P]
 
     def renderer(self, scene, w, h, max_depth=8, nthreads=8, state_machine=False):
         return HcRenderer(self, scene, w, h, max_depth, nthreads, state_machine)

@@ -34,6 +34,7 @@ class Oracle:
             "orc_renderer_frame_count": (U32, [P]), "orc_renderer_read": (C.c_int, [P, C.c_int, C.c_int, P]),
             "orc_renderer_write_rows": (C.c_int, [P, C.c_int, C.c_int, U32, U32, P]),
             "orc_renderer_read_rows": (C.c_int, [P, C.c_int, C.c_int, U32, U32, P]),
+            "orc_shade_probe": (C.c_int, [C.c_int, P, U32, P, P, U32]), "orc_shade_probe_sizes": (None, [P]),
             "orc_renderer_stats": (None, [P, P]), "orc_renderer_time_frames": (C.c_double, [P, P, U32]),
         }
         for n, (r, a) in sig.items():

@@ -4,6 +4,7 @@
 // The kernels themselves (LDS stack columns, wave tiling, ray-counter reduction) are only exercised by the -m gpu tests.
 #include "../../fast-raytracing-wgpu_amd/csrc/frt_scene.hpp"
 #include "../../fast-raytracing-wgpu_amd/csrc/frt_mono.hpp"
+#include "frt_shade_probe.hpp"
 #include <vector>
 #include <cstring>
 #include <thread>
@@ -351,6 +352,18 @@ void hc_wide8_stats(const frt_scene* s, uint32_t out[8]) {
         }
     }
     out[5] = (uint32_t)(kids * 100u / std::max<size_t>(w.size() / kWide8Words, 1));
+}
+
+// probe: n cases of one shading operation through the probe body that tools/shade_probe.hip runs on the device (frt_shade_probe.hpp: record layouts).
+// lights: the table of 100 lights of the nee operations (ignored otherwise). -1: unknown operation or a record asking for more lights than the table holds.
+int hc_shade_probe(int op, const void* lights, const void* in, void* out, uint32_t n) {
+    if (op < 0 || op >= probe::OP_COUNT || !probe::nee_records_ok(op, in, n)) return -1;
+    for (uint32_t i = 0; i < n; ++i) probe::shade_probe_case(op, static_cast<const LightView*>(lights), in, out, i);
+    return 0;
+}
+// sizes[2 * op], sizes[2 * op + 1]: input and output record size of every operation
+void hc_shade_probe_sizes(uint32_t* sizes) {
+    for (int op = 0; op < probe::OP_COUNT; ++op) { sizes[2 * op] = probe::in_size(op); sizes[2 * op + 1] = probe::out_size(op); }
 }
 
 } // extern "C"

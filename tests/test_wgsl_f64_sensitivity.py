@@ -62,3 +62,22 @@ def test_spatial_misreading_is_caught(frt, orc, mis):
     T.check_spatial(inp, out, raw, W, H, fc, view_pos, mats, T.tris_of(fs, which))
     with pytest.raises(AssertionError, match="pixels differ from float64"):
         T.check_spatial(inp, out, raw, W, H, fc, view_pos, mats, T.tris_of(fs, which), mis={mis})
+
+
+SHADE_MIS = [("g1_alpha2", "g1"), ("prob_spec_swapped", "eval_pdf"), ("fresnel_n_dot_v", "eval_bsdf"), ("pdf_g_smith", "eval_pdf"), ("kd_no_metallic", "eval_bsdf"),
+             ("glass_ratio_swapped", "sample_bsdf"), ("glass_no_short_circuit", "sample_bsdf"), ("vndf_no_stretch_back", "vndf"), ("sphere_radius_u", "light"),
+             ("mis_power", "nee0"), ("nee_tmax_dist", "nee1"), ("nee_pdf_from_offset", "nee0"), ("roulette_ge", "roulette"), ("offset_no_sign", "roulette")]
+
+
+@pytest.mark.parametrize("mis,op", SHADE_MIS)
+def test_shading_misreading_is_caught(orc, mis, op):
+    """Each misreading of restir.wgsl:161-603 (tests/_wgsl_f64_shade.py, `mis`) on the float64 side only puts at least one case that the misread
+    float64 still decides outside its bound, or off in its draw count, against the oracle."""
+    import _shade_probe as S
+    inp, _, lights, ref, und = S.prepared(op)
+    out = S.run_oracle(orc, op, inp, lights)
+    assert not S.failures(S.compare(op, out, ref, und)).any()                      # the faithful reading agrees ...
+    bad_ref, bad_und = S.reference(op, inp, lights, mis={mis})
+    bad = S.failures(S.compare(op, out, bad_ref, bad_und))
+    assert bad.any(), f"{mis}: the comparison does not notice this misreading"   # ... and the misreading does not
+    print(f" {mis}: {int(bad.sum())} of {len(inp)} cases of {op}")
