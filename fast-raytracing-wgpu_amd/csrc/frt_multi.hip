@@ -471,6 +471,18 @@ int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, co
     if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_pose: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
     return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose(r, mesh_id, joint_mats, njoints, flags); });
 }
+// Every strip binds the morph targets to, and morphs, its own replica (frt_renderer_set_mesh_morph_targets, _set_mesh_morph_weights, _set_mesh_pose_ex).
+int frt_multi_renderer_set_mesh_morph_targets(frt_multi_renderer* m, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
+    return edit_every_replica(m, "multi set_mesh_morph_targets", [&](frt_renderer* r) { return frt_renderer_set_mesh_morph_targets(r, mesh_id, deltas3, nverts, ntargets); });
+}
+int frt_multi_renderer_set_mesh_morph_weights(frt_multi_renderer* m, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
+    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_morph_weights: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    return edit_every_replica(m, "multi set_mesh_morph_weights", [&](frt_renderer* r) { return frt_renderer_set_mesh_morph_weights(r, mesh_id, weights, ntargets, flags); });
+}
+int frt_multi_renderer_set_mesh_pose_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_pose: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, morph_weights, ntargets, flags); });
+}
 // The material, light and texture edits on every strip's replica, as above.
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     return edit_every_replica(m, "multi set_materials", [&](frt_renderer* r) { return frt_renderer_set_materials(r, n, ids, materials); });

@@ -6,6 +6,7 @@
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
 #include "frt_skin.hpp"
+#include "frt_morph.hpp"
 #include "frt_refit_device.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
@@ -165,6 +166,14 @@ struct RefitState {
     std::vector<MeshSkin> skins;
     Staging skin_up;
     OwnedBuf skinned;
+    // frt_renderer_set_mesh_morph_targets / _set_mesh_morph_weights / _set_mesh_pose_ex ("Morph targets"): per mesh its targets on the device, one buffer
+    // [base positions 16 nverts | deltas, target-major, 12 nverts ntargets] (ntargets == 0: none; the list may be shorter than the mesh list);
+    // remove_meshes frees a leaving mesh's and renumbers the rest. `morph_up`: the pinned block a bind call's deltas go through. A morph call morphs into
+    // `skinned`; the combined call morphs into `morphed`, [nverts] float4, which the skin launch then reads as its bind pose.
+    struct MeshMorph { OwnedBuf buf; uint32_t ntargets = 0; };
+    std::vector<MeshMorph> morphs;
+    Staging morph_up;
+    OwnedBuf morphed;
     DeviceTransformState xf;               // FRT_TRANSFORM_DEVICE
 #if FRT_EXPERIMENTS
     OwnedBuf tri_normals;                 // lib/libfrt_exp.so, FRT_NORMALS_TRI_PASS=1: the scratch of the triangle pass (NormalArgs::tri_scratch)

@@ -4,6 +4,7 @@
 #include "frt_scene.hpp"
 #include "frt_vertex_normal.hpp"      // encode_vertex_normal, recomputed_vertex_normal: shared with the device
 #include "frt_skin.hpp"               // skinned_position: shared with the device
+#include "frt_morph.hpp"              // morphed_position: shared with the device
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -473,19 +474,83 @@ int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const
     return FRT_OK;
 }
 int SceneBuilder::set_mesh_pose(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    return set_mesh_pose_ex(mesh_id, joint_mats, njoints, nullptr, 0u, flags);
+}
+
+// ---------------------------------------------------------------------------------------------- morph targets ("Morph targets")
+std::string check_mesh_morph_targets(const float* deltas3, uint32_t nverts, uint32_t ntargets, uint32_t mesh_nverts) {
+    if (!deltas3) return "null deltas";
+    if (nverts != mesh_nverts) return std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(mesh_nverts);
+    if (ntargets == 0 || ntargets > FRT_MAX_MORPH_TARGETS) return std::to_string(ntargets) + " targets (1 to " + std::to_string(FRT_MAX_MORPH_TARGETS) + ")";
+    for (size_t k = 0; k < (size_t)ntargets * nverts * 3; ++k)
+        if (!std::isfinite(deltas3[k])) return "a delta of target " + std::to_string(k / 3 / nverts) + ", vertex " + std::to_string(k / 3 % nverts) + " is not finite";
+    return "";
+}
+std::string check_mesh_morph_weights(const float* weights, uint32_t ntargets, uint32_t bound_targets, bool host_memory) {
+    if (bound_targets == 0) return "the mesh has no morph targets (set_mesh_morph_targets)";
+    if (ntargets != bound_targets) return std::to_string(ntargets) + " weights given, " + std::to_string(bound_targets) + " targets are bound";
+    if (!weights) return "null weights";
+    for (uint32_t t = 0; host_memory && t < ntargets; ++t) if (!std::isfinite(weights[t])) return "the weight of target " + std::to_string(t) + " is not finite";
+    return "";
+}
+int SceneBuilder::set_mesh_morph_targets(uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
+    if (!built) { error = "set_mesh_morph_targets: scene is not built"; return FRT_ERR_STATE; }
+    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_morph_targets: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (!deltas3) {
+        if (mesh_id < mesh_morphs.size()) mesh_morphs[mesh_id] = MeshMorph();
+        return FRT_OK;
+    }
+    const std::string bad = check_mesh_morph_targets(deltas3, nverts, ntargets, (uint32_t)(mesh_positions[mesh_id].size() / 4));
+    if (!bad.empty()) { error = "set_mesh_morph_targets: " + bad; return FRT_ERR_INVALID_ARG; }
+    if (mesh_morphs.size() <= mesh_id) mesh_morphs.resize((size_t)mesh_id + 1u);
+    MeshMorph& k = mesh_morphs[mesh_id];
+    k.ntargets = ntargets;
+    k.deltas.assign(deltas3, deltas3 + (size_t)ntargets * nverts * 3);
+    k.base = mesh_positions[mesh_id];
+    return FRT_OK;
+}
+// The morphed positions of mesh `mesh_id` under checked weights; "" or what is wrong with them.
+static std::string morph_mesh(const SceneBuilder::MeshMorph& k, const float* weights, std::vector<float>& morphed) {
+    const size_t nverts = k.base.size() / 4;
+    morphed.resize(k.base.size());
+    for (size_t v = 0; v < nverts; ++v) morphed_position(&k.base[4 * v], &k.deltas[3 * v], 3 * nverts, weights, k.ntargets, &morphed[4 * v]);
+    for (size_t c = 0; c < morphed.size(); ++c)
+        if (!std::isfinite(morphed[c])) return "the morphed position of vertex " + std::to_string(c / 4) + " is not finite";
+    return "";
+}
+int SceneBuilder::set_mesh_morph_weights(uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
+    if (!built) { error = "set_mesh_morph_weights: scene is not built"; return FRT_ERR_STATE; }
+    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_morph_weights: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_morph_weights only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_morph_weights: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
+    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_morph_weights: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < mesh_morphs.size() ? mesh_morphs[mesh_id].ntargets : 0u);
+    std::vector<float> morphed;
+    if (bad.empty()) bad = morph_mesh(mesh_morphs[mesh_id], weights, morphed);
+    if (!bad.empty()) { error = "set_mesh_morph_weights: " + bad; return FRT_ERR_INVALID_ARG; }
+    return set_mesh_vertices(mesh_id, morphed.data(), nullptr, (uint32_t)(morphed.size() / 4), flags);
+}
+// set_mesh_pose's checks in set_mesh_pose's order; with morph weights the morph's follow, and the morphed positions stand where the bind pose stood.
+int SceneBuilder::set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
     if (!built) { error = "set_mesh_pose: scene is not built"; return FRT_ERR_STATE; }
     if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_pose: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_pose only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
     if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_pose: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
     if (mesh_id >= mesh_positions.size()) { error = "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
-    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u);
+    std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u);
     if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
     const MeshSkin& k = mesh_skins[mesh_id];
-    const uint32_t nverts = (uint32_t)(k.bind.size() / 4);
-    std::vector<float> skinned(k.bind.size());
+    std::vector<float> morphed;
+    if (morph_weights || ntargets) {
+        bad = check_mesh_morph_weights(morph_weights, ntargets, mesh_id < mesh_morphs.size() ? mesh_morphs[mesh_id].ntargets : 0u);
+        if (bad.empty()) bad = morph_mesh(mesh_morphs[mesh_id], morph_weights, morphed);
+        if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
+    }
+    const std::vector<float>& bind = morphed.empty() ? k.bind : morphed;
+    const uint32_t nverts = (uint32_t)(bind.size() / 4);
+    std::vector<float> skinned(bind.size());
     for (uint32_t v = 0; v < nverts; ++v) {
         float m[4][16];
         for (int s = 0; s < 4; ++s) memcpy(m[s], joint_mats + 16 * (size_t)k.joints[4 * (size_t)v + s], sizeof(m[s]));
-        skinned_position(&k.bind[4 * (size_t)v], m, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);
+        skinned_position(&bind[4 * (size_t)v], m, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);
     }
     for (size_t c = 0; c < skinned.size(); ++c)
         if (!std::isfinite(skinned[c])) { error = "set_mesh_pose: the skinned position of vertex " + std::to_string(c / 4) + " is not finite"; return FRT_ERR_INVALID_ARG; }
@@ -873,6 +938,10 @@ int SceneBuilder::remove_meshes(uint32_t n, const uint32_t* ids) {
     if (rc == FRT_OK && !mesh_skins.empty()) {      // the skins follow the mesh ids (a call that was undone leaves them)
         mesh_skins.resize(map.size());
         remove_elements(mesh_skins, gone);
+    }
+    if (rc == FRT_OK && !mesh_morphs.empty()) {     // and so do the morph targets
+        mesh_morphs.resize(map.size());
+        remove_elements(mesh_morphs, gone);
     }
     return rc;
 }

@@ -112,6 +112,19 @@ public:
     // count, a matrix entry or a skinned coordinate that is not finite, FRT_DEFORM_DEVICE, an unknown flag bit. A set_mesh_vertices on a skinned mesh
     // leaves the bind pose as it is; remove_meshes drops the skin of a mesh that leaves and the survivors' skins follow their ids.
     int set_mesh_pose(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags = 0);
+    // Morph targets ("Morph targets"). set_mesh_morph_targets binds ntargets sets of per-vertex position deltas, [ntargets][nverts][3], to
+    // a mesh of a built scene; the mesh's object-space positions as they are at the call are copied and become the base. No vertex and no triangle
+    // changes. deltas3 == nullptr removes the binding. Refused, with nothing changed (check_mesh_morph_targets): a vertex count that is not the mesh's,
+    // ntargets == 0 or above FRT_MAX_MORPH_TARGETS, a delta that is not finite.
+    int set_mesh_morph_targets(uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
+    // Every vertex of the base through frt_morph.hpp's morphed_position under `weights`, then set_mesh_vertices(mesh_id, morphed, nullptr, nverts, flags).
+    // Refused, with nothing changed: a mesh with no targets, ntargets that is not the bound count, a weight or a morphed coordinate that is not finite,
+    // FRT_DEFORM_DEVICE, an unknown flag bit. A set_mesh_vertices on the mesh leaves the base as it is; remove_meshes drops the targets of a mesh that
+    // leaves and the survivors' targets follow their ids.
+    int set_mesh_morph_weights(uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags = 0);
+    // Morph, then skin: set_mesh_pose with the morphed position (from the morph base) in the place of the skin's bind pose, which is not read.
+    // morph_weights == nullptr with ntargets == 0: set_mesh_pose. Refuses what either part refuses.
+    int set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags = 0);
     // What a built scene LOOKS like: no triangle, slot or box moves. Each is the specification its device form matches bit for bit,
     // validates everything before it applies anything, and leaves the scene equal to one built from scratch with the edited values.
     // Material ids[k] becomes mats[k], under the checks build() makes on a material (check_material).
@@ -157,6 +170,9 @@ public:
     // Per mesh its skin (set_mesh_skin); njoints == 0: none. Shorter than the mesh list while the last meshes have none.
     struct MeshSkin { uint32_t njoints = 0; std::vector<uint16_t> joints; std::vector<float> weights, bind; };
     std::vector<MeshSkin> mesh_skins;
+    // Per mesh its morph targets (set_mesh_morph_targets); ntargets == 0: none. Shorter than the mesh list while the last meshes have none.
+    struct MeshMorph { uint32_t ntargets = 0; std::vector<float> deltas, base; };      // deltas [ntargets][nverts][3], base [nverts][4]
+    std::vector<MeshMorph> mesh_morphs;
     // built
     bool built = false;
     std::vector<TriRec> tris;
@@ -209,6 +225,11 @@ std::string check_mesh_vertices(const float* pos4, const frt_vertex_attr* attrs,
 // caller to find out: the scene computes them, the renderer's validation launch reads them.
 std::string check_mesh_skin(const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t mesh_nverts);
 std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t bound_joints, bool host_memory = true);      // (device memory: the matrices are not read)
+// The same for set_mesh_morph_targets and for the weights of set_mesh_morph_weights and set_mesh_pose_ex: "" when the call may be applied to a mesh of
+// `mesh_nverts` vertices, or under `bound_targets` bound targets (0: the mesh has none). Whether the morphed coordinates are finite is for the caller
+// to find out, as with a pose.
+std::string check_mesh_morph_targets(const float* deltas3, uint32_t nverts, uint32_t ntargets, uint32_t mesh_nverts);
+std::string check_mesh_morph_weights(const float* weights, uint32_t ntargets, uint32_t bound_targets, bool host_memory = true);      // (device memory: the weights are not read)
 // The vertex -> corner adjacency of one mesh in CSR form: corners[offsets[v] .. offsets[v + 1]) are the corners 3 * triangle + k whose index is v,
 // ascending. offsets has nverts + 1 entries, corners nidx (an index out of range, which the checks let into no mesh, names no vertex).
 void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, std::vector<uint32_t>& offsets, std::vector<uint32_t>& corners);

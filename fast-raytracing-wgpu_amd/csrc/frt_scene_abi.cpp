@@ -113,6 +113,21 @@ int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_m
     const int rc = s->b.set_mesh_pose(mesh_id, joint_mats, njoints, flags);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_set_mesh_morph_targets(frt_scene* s, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_targets: null");
+    const int rc = s->b.set_mesh_morph_targets(mesh_id, deltas3, nverts, ntargets);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_mesh_morph_weights(frt_scene* s, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_weights: null");
+    const int rc = s->b.set_mesh_morph_weights(mesh_id, weights, ntargets, flags);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
+int frt_scene_set_mesh_pose_ex(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: null");
+    const int rc = s->b.set_mesh_pose_ex(mesh_id, joint_mats, njoints, morph_weights, ntargets, flags);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_materials: null");
     const int rc = s->b.set_materials(n, ids, materials);

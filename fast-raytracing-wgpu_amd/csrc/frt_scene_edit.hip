@@ -1,11 +1,11 @@
 // frt_scene_edit.hip — every call that edits a renderer's scene replica between frames (include/frt.h), host code only:
-//   moving instances, deforming and skinning meshes, the tree rebuild       DESIGN.md §11
+//   moving instances, deforming, skinning and morphing meshes, the rebuild  DESIGN.md §11
 //   the material, light and texture edits                                   §13
 //   adding and removing instances                                           §14
 //   new meshes, materials, texture layers and lights                        §15
 //   removing meshes, materials, layers and lights                           §16
 // The calls that only read the replica (the ray queries, frt_renderer_read_scene, the statistics and counts) are in frt_scene_read.hip; the kernels in
-// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
+// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_morph.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
 //
 // All edits share one scheme:
 //   - the call frame (edit_frame): the device guard, the stream order behind the finished frames, the body, `failed` on a HIP error;
@@ -457,11 +457,16 @@ static int ensure_adjacency(frt_renderer* r, uint32_t m) {
 // What follows the checks of a deformation, inside its call frame: the staging, the launches and the refit. frt_renderer_set_mesh_vertices_ex (`pose` null)
 // and frt_renderer_set_mesh_pose run these lines. With `pose`, pos4 and attrs are ignored (no attributes): the mesh is skinned into RefitState::skinned by
 // frt_skin.hpp's kernel, and that buffer then takes the device-input route; a palette from the host rides in the call's pinned and device blocks.
+// frt_renderer_set_mesh_morph_weights (`morph` alone) is the same with frt_morph.hpp's kernel in the skin kernel's place, its host weights behind the
+// palette's place in the blocks. frt_renderer_set_mesh_pose_ex (both): the morph launch writes RefitState::morphed, and the skin launch, otherwise
+// unchanged, reads that buffer as its bind pose.
 struct PoseInput { const float* mats; uint32_t njoints; bool device; };
-static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags, const PoseInput* pose) {
-    if (pose) attrs = nullptr;
+struct MorphInput { const float* weights; uint32_t ntargets; bool device; };
+static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags, const PoseInput* pose,
+                       const MorphInput* morph = nullptr) {
+    if (pose || morph) attrs = nullptr;
     RefitState& f = r->rf;
-    const bool dev = pose || (flags & FRT_DEFORM_DEVICE), recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    const bool dev = pose || morph || (flags & FRT_DEFORM_DEVICE), recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
     if (const int rc = sync_matrix_mirror(r)) return rc;      // (the instances' matrices are read below)
     std::vector<DeformInstance> rec;
     uint32_t work = 0;
@@ -479,9 +484,11 @@ static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, con
     const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = shade ? (size_t)nverts * 16 : 0;
     const size_t up_bytes = rec_bytes + (host_decode ? nrm_bytes : 0);      // what is copied into the device block
     const size_t pal_bytes = pose && !pose->device ? (size_t)pose->njoints * 64 : 0;      // a host palette: behind both, in the pinned and in the device block
+    const size_t wt_bytes = morph && !morph->device ? (size_t)morph->ntargets * 4 : 0;      // host morph weights: behind the palette, in both blocks
     int rc;
-    if (pose) {
+    if (pose || morph) {
         if ((rc = f.skinned.ensure(r, (size_t)nverts * 16))) return rc;
+        if (pose && morph && (rc = f.morphed.ensure(r, (size_t)nverts * 16))) return rc;
         pos4 = f.skinned.as<float>();
     }
     if (recompute && (rc = ensure_adjacency(r, mesh_id))) return rc;
@@ -491,9 +498,9 @@ static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, con
         HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
         f.d_reject = static_cast<uint32_t*>(d);
     }
-    if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes + pal_bytes, rec_bytes + nrm_bytes + pal_bytes, r->stream))) return rc;
-    uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes; uint8_t* h_pal = h_up + up_bytes;
-    uint8_t* d_pal = f.def.d + rec_bytes + nrm_bytes;
+    if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes + pal_bytes + wt_bytes, rec_bytes + nrm_bytes + pal_bytes + wt_bytes, r->stream))) return rc;
+    uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes; uint8_t* h_pal = h_up + up_bytes; uint8_t* h_wt = h_pal + pal_bytes;
+    uint8_t* d_pal = f.def.d + rec_bytes + nrm_bytes; uint8_t* d_wt = d_pal + pal_bytes;
     float4* block = shade ? reinterpret_cast<float4*>(f.def.d + rec_bytes) : nullptr;
     float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
     const uint32_t cap_verts = pool_cap(r, kPoolVerts);
@@ -509,18 +516,29 @@ static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, con
     }
     if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
     if (pal_bytes) memcpy(h_pal, pose->mats, pal_bytes);
+    if (wt_bytes) memcpy(h_wt, morph->weights, wt_bytes);
     if (!dev) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
     if (attr_bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
     if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
     if (host_decode && pool_normals)
         HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
     if (pal_bytes) HIP_TRY(hipMemcpyAsync(d_pal, h_pal, pal_bytes, hipMemcpyHostToDevice, r->stream));
+    if (wt_bytes) HIP_TRY(hipMemcpyAsync(d_wt, h_wt, wt_bytes, hipMemcpyHostToDevice, r->stream));
     if ((rc = f.def.mark(r->stream))) return rc;
     const uint32_t* reject = dev ? f.d_reject : nullptr;      // (host input was validated above: there is no flag to look at)
-    if (pose) {      // the skinned vertices are this call's device input: the flag is zeroed here, in front of the launch that may raise it first
+    // the morphed or skinned vertices are this call's device input: the flag is zeroed here, in front of the launch that may raise it first
+    if (pose || morph) HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
+    if (morph) {
+        const uint8_t* k = static_cast<const uint8_t*>(f.morphs[mesh_id].buf.p);
+        const OwnedBuf& out = pose ? f.morphed : f.skinned;
+        const MorphArgs ma{reinterpret_cast<const float4*>(k), reinterpret_cast<const float*>(k + (size_t)nverts * 16),
+                           morph->device ? morph->weights : reinterpret_cast<const float*>(d_wt), out.as<float4>(),
+                           nverts, morph->ntargets, (uint32_t)std::min<size_t>(out.bytes / 16, 0xFFFFFFFFu), morph->device ? 1u : 0u, f.d_reject};
+        HIP_TRY(launch_mesh_morph(ma, r->stream));
+    }
+    if (pose) {
         const uint8_t* k = static_cast<const uint8_t*>(f.skins[mesh_id].buf.p);
-        HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
-        const SkinArgs sa{reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + (size_t)nverts * 16), reinterpret_cast<const uint2*>(k + (size_t)nverts * 32),
+        const SkinArgs sa{morph ? f.morphed.as<const float4>() : reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + (size_t)nverts * 16), reinterpret_cast<const uint2*>(k + (size_t)nverts * 32),
                           pose->device ? reinterpret_cast<const float4*>(pose->mats) : reinterpret_cast<const float4*>(d_pal), f.skinned.as<float4>(),
                           nverts, pose->njoints, (uint32_t)std::min<size_t>(f.skinned.bytes / 16, 0xFFFFFFFFu), pose->device ? 1u : 0u, f.d_reject};
         HIP_TRY(launch_mesh_skin(sa, r->stream));
@@ -529,7 +547,7 @@ static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, con
         DeformInput in{reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(attrs), nverts, f.pos_offset[mesh_id], f.attr_offset[mesh_id], cap_verts,
                        const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
                        attrs && !recompute ? block : nullptr, attrs && !recompute ? pool_normals : nullptr, f.d_reject};
-        HIP_TRY(launch_deform_input(in, r->stream, !pose));
+        HIP_TRY(launch_deform_input(in, r->stream, !(pose || morph)));
     }
     if (recompute) {
         NormalArgs na{f.adj[mesh_id], f.adj[mesh_id] + (nverts + 1u), nverts, 3u * f.mesh_tris[mesh_id], f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
@@ -639,6 +657,96 @@ int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* j
     const PoseInput pose{joint_mats, njoints, dev};
     return edit_frame(r, true, [&]() -> int {
         return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, &pose);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ morph targets ("Morph targets")
+// The targets of mesh `m` leave (behind a wait: a morph's kernel may still read them).
+static int drop_morph(frt_renderer* r, uint32_t m) {
+    RefitState& f = r->rf;
+    if (m >= f.morphs.size() || !f.morphs[m].buf.p) return FRT_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    scene_free(r, f.morphs[m].buf.p);
+    f.morphs[m] = RefitState::MeshMorph();
+    return FRT_OK;
+}
+// The deltas go through the pinned block of RefitState::morph_up into the mesh's own buffer, in the caller's layout (target-major); the base is copied
+// there from the replica's object-space positions on the stream, behind every deformation enqueued so far. The speculation is kept: nothing a frame
+// reads changes.
+int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
+    if (const int rc = check_entry(r, "set_mesh_morph_targets", kEditChecks | kRefit)) return rc;
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_targets: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (deltas3) {
+        const std::string bad = check_mesh_morph_targets(deltas3, nverts, ntargets, r->rf.vert_count[mesh_id]);
+        if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_targets: " + bad);
+    }
+    return edit_frame(r, false, [&]() -> int {
+        RefitState& f = r->rf;
+        if (!deltas3) return drop_morph(r, mesh_id);
+        if (f.morphs.size() <= mesh_id) f.morphs.resize((size_t)mesh_id + 1u);
+        RefitState::MeshMorph& k = f.morphs[mesh_id];
+        const size_t pos_bytes = (size_t)nverts * 16, delta_bytes = (size_t)ntargets * nverts * 12;
+        int rc;
+        if ((uint64_t)f.pos_offset[mesh_id] + nverts > pool_cap(r, kPoolVerts)) return fail(FRT_ERR_STATE, "set_mesh_morph_targets: the mesh does not lie inside the vertex pool");
+        k.ntargets = 0;      // (a call that fails below leaves the mesh without targets)
+        if ((rc = k.buf.ensure(r, pos_bytes + delta_bytes))) return rc;
+        if ((rc = f.morph_up.reserve(delta_bytes, 0, r->stream))) return rc;
+        memcpy(f.morph_up.h, deltas3, delta_bytes);
+        uint8_t* d = k.buf.as<uint8_t>();      // [base positions | deltas]
+        if (nverts) {
+            HIP_TRY(hipMemcpyAsync(d, f.d_pos + f.pos_offset[mesh_id], pos_bytes, hipMemcpyDeviceToDevice, r->stream));
+            HIP_TRY(hipMemcpyAsync(d + pos_bytes, f.morph_up.h, delta_bytes, hipMemcpyHostToDevice, r->stream));
+        }
+        if ((rc = f.morph_up.mark(r->stream))) return rc;
+        k.ntargets = ntargets;
+        return FRT_OK;
+    });
+}
+// What the two calls that take morph weights check about them, in front of the call frame; with FRT_DEFORM_DEVICE their finiteness is the morph launch's.
+static int check_morph_input(frt_renderer* r, const char* call, uint32_t mesh_id, const float* weights, uint32_t ntargets, bool dev) {
+    const std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < r->rf.morphs.size() ? r->rf.morphs[mesh_id].ntargets : 0u, !dev);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, std::string(call) + ": " + bad);
+    if (dev) {
+        DeviceGuard guard(r->device);
+        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+        if (const int rc = check_device_pointer(r, weights, (size_t)ntargets * 4, 4, call, "morph weights", "FRT_DEFORM_DEVICE")) return rc;
+    }
+    return FRT_OK;
+}
+// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what this call adds runs in front of the device-input route.
+int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = check_entry(r, "set_mesh_morph_weights", kEditChecks | kRefit)) return rc;
+    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_weights: unknown flag bits");
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_weights: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
+    if (const int rc = check_morph_input(r, "set_mesh_morph_weights", mesh_id, weights, ntargets, dev)) return rc;
+    const MorphInput morph{weights, ntargets, dev};
+    return edit_frame(r, true, [&]() -> int {
+        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, nullptr, &morph);
+    });
+}
+// frt_renderer_set_mesh_pose's checks, then the morph's; two launches in front of the device-input route.
+int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (!morph_weights && ntargets == 0) return frt_renderer_set_mesh_pose(r, mesh_id, joint_mats, njoints, flags);
+    if (const int rc = check_entry(r, "set_mesh_pose", kEditChecks | kRefit)) return rc;
+    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: unknown flag bits");
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
+    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].njoints : 0u, !dev);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
+    if (dev) {
+        DeviceGuard guard(r->device);
+        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+        if (const int rc = check_device_pointer(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices", "FRT_DEFORM_DEVICE")) return rc;
+    }
+    if (const int rc = check_morph_input(r, "set_mesh_pose", mesh_id, morph_weights, ntargets, dev)) return rc;
+    const PoseInput pose{joint_mats, njoints, dev};
+    const MorphInput morph{morph_weights, ntargets, dev};
+    return edit_frame(r, true, [&]() -> int {
+        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, &pose, &morph);
     });
 }
 
@@ -1264,6 +1372,11 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             f.skins.resize(old_meshes);
             for (uint32_t g : gone) if ((rc = drop_skin(r, g))) return rc;
             remove_elements(f.skins, gone);
+        }
+        if (!f.morphs.empty()) {      // and the morph targets
+            f.morphs.resize(old_meshes);
+            for (uint32_t g : gone) if ((rc = drop_morph(r, g))) return rc;
+            remove_elements(f.morphs, gone);
         }
         drop_transform_tables(r, false);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];

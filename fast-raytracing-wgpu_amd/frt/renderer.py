@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE, TRANSFORM_DEVICE)
-from .scene import (transform_args, set_mesh_vertices_call, set_mesh_skin_call, set_mesh_pose_call, _num_joints, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
+from .scene import (transform_args, set_mesh_vertices_call, set_mesh_skin_call, set_mesh_pose_call, set_mesh_morph_targets_call, set_mesh_morph_weights_call, _num_joints, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
                     pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
 
@@ -337,16 +337,21 @@ class Renderer(_HostQueries, _SceneGrowth):
         joints=None removes the skin; num_joints defaults to the largest joint index + 1. The host scene is not changed."""
         set_mesh_skin_call("frt_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
 
-    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
         """Pose a skinned mesh of this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_pose): one column-major 4x4 per
         joint, [J, 16] or [J, 4, 4]. One kernel skins the bind pose on the device; the result is applied as set_mesh_vertices applies device
         positions. normals="recompute" (the default: a posed mesh lit with its bind-pose normals is wrong) or "keep".
         numpy (or array-like) in: checked and copied during the call. A contiguous float32 torch tensor on the renderer's device in: the protocol of
         the device form of set_mesh_vertices — the renderer's stream waits for the caller's current stream, the call is only enqueued, and the
         renderer keeps a reference to the tensor until that stream has passed the call. A non-finite matrix entry of a device palette, and for
-        either kind a pose that overflows, rejects the call on the device: nothing is applied and deform_rejects() counts it."""
-        if not _is_device_tensor(joint_matrices):
-            return set_mesh_pose_call("frt_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
+        either kind a pose that overflows, rejects the call on the device: nothing is applied and deform_rejects() counts it.
+        morph_weights [T] (frt_renderer_set_mesh_pose_ex): the mesh is morphed from its morph base first and the morphed positions are skinned, in
+        two launches. The palette and the weights are then either both tensors or both arrays; None calls exactly what the plain pose calls."""
+        dev_in = [_is_device_tensor(x) for x in (joint_matrices, morph_weights) if x is not None]
+        if not any(dev_in):
+            return set_mesh_pose_call("frt_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals, morph_weights)
+        if not all(dev_in):
+            raise TypeError("set_mesh_pose: joint matrices and morph weights must both be host arrays or both be device tensors")
         import torch
         flags = deform_flags(normals) | DEFORM_DEVICE
         if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
@@ -356,13 +361,53 @@ class Renderer(_HostQueries, _SceneGrowth):
             raise FrtError(f"set_mesh_pose: joint matrices are on {t.device}, the renderer on device {self.device}")
         if t.dtype != torch.float32 or not t.is_contiguous() or not ((t.dim() == 2 and t.shape[1] == 16) or (t.dim() == 3 and tuple(t.shape[1:]) == (4, 4))):
             raise FrtError("set_mesh_pose: device joint matrices must be a contiguous float32 tensor shaped [J, 16] or [J, 4, 4]")
+        if morph_weights is not None:
+            self._check_device_weights(torch, "set_mesh_pose", morph_weights)
         s = self._torch_stream(torch, t.device)
         s.wait_stream(torch.cuda.current_stream(t.device))
-        check(lib().frt_renderer_set_mesh_pose(self._h, int(mesh_id), t.data_ptr(), t.shape[0], flags))
+        if morph_weights is None:
+            check(lib().frt_renderer_set_mesh_pose(self._h, int(mesh_id), t.data_ptr(), t.shape[0], flags))
+        else:
+            check(lib().frt_renderer_set_mesh_pose_ex(self._h, int(mesh_id), t.data_ptr(), t.shape[0], morph_weights.data_ptr(), morph_weights.shape[0], flags))
         done = torch.cuda.Event()
         done.record(s)
         self._release_held()
-        self._held.append((done, t))
+        self._held.append((done, t, morph_weights))
+
+    def _check_device_weights(self, torch, call, w):
+        if w.device.index != self.device:
+            raise FrtError(f"{call}: morph weights are on {w.device}, the renderer on device {self.device}")
+        if w.dtype != torch.float32 or w.dim() != 1 or not w.is_contiguous():
+            raise FrtError(f"{call}: device morph weights must be a contiguous float32 tensor shaped [T]")
+
+    def set_mesh_morph_targets(self, mesh_id, deltas):
+        """Bind morph targets to one mesh of this renderer's scene replica (include/frt.h: frt_renderer_set_mesh_morph_targets): `deltas` [T, n, 3]
+        float32, copied during the call; the replica's positions of the mesh, as the renderer's stream finds them, become the base. deltas=None
+        removes the targets. The host scene is not changed."""
+        set_mesh_morph_targets_call("frt_renderer_set_mesh_morph_targets", self._h, mesh_id, deltas)
+
+    def set_mesh_morph_weights(self, mesh_id, weights, normals="recompute"):
+        """Morph a mesh of this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_morph_weights): one weight per bound
+        target, [T]. One kernel adds the weighted deltas to the base on the device, in target order; the result is applied as set_mesh_vertices
+        applies device positions. normals="recompute" (the default) or "keep".
+        numpy (or array-like) in: checked and copied during the call. A contiguous float32 torch tensor on the renderer's device in: the protocol of
+        the device palette of set_mesh_pose — the renderer's stream waits for the caller's current stream, the call is only enqueued, and the
+        renderer keeps a reference to the tensor until that stream has passed the call. A non-finite device weight, and for either kind a morph
+        that overflows, rejects the call on the device: nothing is applied and deform_rejects() counts it."""
+        if not _is_device_tensor(weights):
+            return set_mesh_morph_weights_call("frt_renderer_set_mesh_morph_weights", self._h, mesh_id, weights, normals)
+        import torch
+        flags = deform_flags(normals) | DEFORM_DEVICE
+        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+            raise FrtError("mesh id must be an unsigned 32-bit index")
+        self._check_device_weights(torch, "set_mesh_morph_weights", weights)
+        s = self._torch_stream(torch, weights.device)
+        s.wait_stream(torch.cuda.current_stream(weights.device))
+        check(lib().frt_renderer_set_mesh_morph_weights(self._h, int(mesh_id), weights.data_ptr(), weights.shape[0], flags))
+        done = torch.cuda.Event()
+        done.record(s)
+        self._release_held()
+        self._held.append((done, weights))
 
     def _release_held(self, all_done=False):
         """Drop the references to device tensors whose call the stream has passed (all of them after a sync)."""
@@ -639,11 +684,21 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         """Renderer.set_mesh_skin on every strip's scene replica."""
         set_mesh_skin_call("frt_multi_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
 
-    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
         """Renderer.set_mesh_pose on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
-        if _is_device_tensor(joint_matrices):
+        if _is_device_tensor(joint_matrices) or _is_device_tensor(morph_weights):
             raise FrtError("set_mesh_pose: a MultiRenderer takes host arrays only (its replicas live on different devices)")
-        set_mesh_pose_call("frt_multi_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
+        set_mesh_pose_call("frt_multi_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals, morph_weights)
+
+    def set_mesh_morph_targets(self, mesh_id, deltas):
+        """Renderer.set_mesh_morph_targets on every strip's scene replica."""
+        set_mesh_morph_targets_call("frt_multi_renderer_set_mesh_morph_targets", self._h, mesh_id, deltas)
+
+    def set_mesh_morph_weights(self, mesh_id, weights, normals="recompute"):
+        """Renderer.set_mesh_morph_weights on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
+        if _is_device_tensor(weights):
+            raise FrtError("set_mesh_morph_weights: a MultiRenderer takes host arrays only (its replicas live on different devices)")
+        set_mesh_morph_weights_call("frt_multi_renderer_set_mesh_morph_weights", self._h, mesh_id, weights, normals)
 
     # ---- what the replica looks like (include/frt.h: frt_renderer_set_materials and the three calls after it; DESIGN.md section 13): asynchronous,
     # between frames, the arguments copied during the call; accumulation and reservoirs are kept (reset() / clear() to converge to the new look).

@@ -103,11 +103,50 @@ def mesh_pose_args(mesh_id, joint_matrices):
     return int(mesh_id), m, m.shape[0]
 
 
-def set_mesh_pose_call(name, handle, mesh_id, joint_matrices, normals):
-    """One host-array pose through the entry point `name`."""
+def set_mesh_pose_call(name, handle, mesh_id, joint_matrices, normals, morph_weights=None):
+    """One host-array pose through the entry point `name`; with `morph_weights` the morph-and-skin call `name`_ex."""
     flags = deform_flags(normals)
     mid, m, n = mesh_pose_args(mesh_id, joint_matrices)
-    check(getattr(lib(), name)(handle, mid, m.ctypes.data, n, flags))
+    if morph_weights is None:
+        return check(getattr(lib(), name)(handle, mid, m.ctypes.data, n, flags))
+    _, w, t = mesh_morph_weight_args(mesh_id, morph_weights)
+    check(getattr(lib(), name + "_ex")(handle, mid, m.ctypes.data, n, w.ctypes.data, t, flags))
+
+
+def mesh_morph_target_args(mesh_id, deltas):
+    """(mesh id, deltas, vertex count, target count) for the *_set_mesh_morph_targets calls: `deltas` [T, n, 3] float32, one position delta per target
+    and vertex."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    d = np.ascontiguousarray(deltas, np.float32)
+    if d.ndim != 3 or d.shape[2] != 3:
+        raise FrtError("set_mesh_morph_targets: deltas must be shaped [T, n, 3]")
+    return int(mesh_id), d, d.shape[1], d.shape[0]
+
+
+def set_mesh_morph_targets_call(name, handle, mesh_id, deltas):
+    """One bind call through the entry point `name`; deltas None removes the targets."""
+    if deltas is None:
+        return check(getattr(lib(), name)(handle, int(mesh_id), None, 0, 0))
+    mid, d, n, t = mesh_morph_target_args(mesh_id, deltas)
+    check(getattr(lib(), name)(handle, mid, d.ctypes.data, n, t))
+
+
+def mesh_morph_weight_args(mesh_id, weights):
+    """(mesh id, [T] float32 weights, T) for the host form of the calls that take morph weights."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.ndim != 1:
+        raise FrtError("morph weights must be shaped [T]")
+    return int(mesh_id), w, w.shape[0]
+
+
+def set_mesh_morph_weights_call(name, handle, mesh_id, weights, normals):
+    """One host-array morph through the entry point `name`."""
+    flags = deform_flags(normals)
+    mid, w, t = mesh_morph_weight_args(mesh_id, weights)
+    check(getattr(lib(), name)(handle, mid, w.ctypes.data, t, flags))
 
 
 def material_args(ids, materials):
@@ -418,8 +457,20 @@ class SceneBuilder:
         set_mesh_skin_call("frt_scene_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
         return self
 
-    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute"):
-        set_mesh_pose_call("frt_scene_set_mesh_pose", self._h, mesh_id, joint_matrices, normals)
+    # morph_weights: morph first, then skin the morphed positions (frt_scene_set_mesh_pose_ex); None is the plain pose.
+    def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
+        set_mesh_pose_call("frt_scene_set_mesh_pose", self._h, mesh_id, joint_matrices, normals, morph_weights)
+        return self
+
+    # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
+    # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
+    # base in target order and applies the result as set_mesh_vertices does. Host copy only.
+    def set_mesh_morph_targets(self, mesh_id, deltas):
+        set_mesh_morph_targets_call("frt_scene_set_mesh_morph_targets", self._h, mesh_id, deltas)
+        return self
+
+    def set_mesh_morph_weights(self, mesh_id, weights, normals="recompute"):
+        set_mesh_morph_weights_call("frt_scene_set_mesh_morph_weights", self._h, mesh_id, weights, normals)
         return self
 
     # ---- what the built scene looks like (include/frt.h: frt_scene_set_materials and the three calls after it). Host copy only.

@@ -186,6 +186,29 @@ int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* 
  * drops the skin of a mesh that leaves, and the survivors' skins follow their ids. */
 int frt_scene_set_mesh_skin(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
 int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
+/* Morph targets, or blend shapes ("Morph targets"). A set of per-vertex position deltas is bound to a mesh of a BUILT scene once; a
+ * morph is then only one weight per target. The contract, f32 without contraction and without a hand-written fma: for vertex v with base position
+ * b = (x, y, z, w), targets 0..T-1 with deltas d_t = (dx, dy, dz) and weights w_t, for r in 0..2
+ *   m[r] = ((...((b[r] + w_0 * d_0[r]) + w_1 * d_1[r]) ...) + w_{T-1} * d_{T-1}[r])            (in target order)
+ *   m[3] = b[3]
+ * Every term is evaluated (a weight of 0 is not skipped); weights are used as given: they may be negative or above 1 and are not normalised. Only
+ * positions are morphed; normals follow through FRT_DEFORM_RECOMPUTE_NORMALS.
+ * set_mesh_morph_targets: deltas3 [ntargets][nverts][3] is copied, and so are the mesh's object-space positions as they are at the call: they become the
+ * base. No vertex and no triangle changes. deltas3 == NULL removes the binding. FRT_ERR_STATE: scene not built; FRT_ERR_INVALID_ARG, nothing changed: mesh
+ * id out of range, nverts not the mesh's count, ntargets == 0 or above FRT_MAX_MORPH_TARGETS, a delta that is not finite.
+ * set_mesh_morph_weights: every vertex by the contract from the base under weights [ntargets], then exactly
+ * frt_scene_set_mesh_vertices_ex(s, mesh_id, morphed, NULL, nverts, flags & FRT_DEFORM_RECOMPUTE_NORMALS). FRT_ERR_INVALID_ARG, nothing changed: a mesh
+ * with no targets, ntargets not the bound count, a weight that is not finite, a morphed coordinate that is not finite (finite inputs can overflow), an
+ * unknown flag bit, FRT_DEFORM_DEVICE. A later frt_scene_set_mesh_vertices on the mesh is allowed and leaves the base untouched;
+ * frt_scene_remove_meshes drops the targets of a mesh that leaves, and the survivors' targets follow their ids.
+ * set_mesh_pose_ex: morph and skin in one call, in glTF's order: skinned_position(morphed vertex, ...), that is frt_scene_set_mesh_pose with the morphed
+ * position, computed from the morph base under morph_weights [ntargets], in the place of the skin's bind pose. The skin's own bind copy is not read in this
+ * call, so bind the targets and the skin before the first pose: both copies are then the same rest positions. With morph_weights == NULL and
+ * ntargets == 0 it is frt_scene_set_mesh_pose, bit for bit. It refuses what either part refuses. */
+#define FRT_MAX_MORPH_TARGETS 4096u
+int frt_scene_set_mesh_morph_targets(frt_scene* s, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
+int frt_scene_set_mesh_morph_weights(frt_scene* s, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
+int frt_scene_set_mesh_pose_ex(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* What a BUILT scene looks like: four edits that move no triangle, slot or box. Common rules: FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG: an id or layer out of range, a null pointer with n > 0, a failed check; everything is validated before anything is applied, so
  * a refused call changes nothing. n == 0: FRT_OK. An id given twice ends with its last value. Afterwards the scene equals one built from scratch
@@ -459,6 +482,23 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
  * nothing of the replica and adds one to the counter frt_renderer_deform_rejects reads. */
 int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
 int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
+/* Morph a mesh of this renderer's scene replica ("Morph targets"): arguments, checks and results of
+ * frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights and frt_scene_set_mesh_pose_ex, bit for bit, under the ordering and state rules of
+ * frt_renderer_set_mesh_pose.
+ * set_mesh_morph_targets: the deltas are copied during the call, through pinned memory, into a device buffer kept per mesh (12 bytes per vertex and
+ * target); the base is a device-to-device copy of the replica's object-space positions as the stream finds them (16 bytes per vertex, no read-back). The
+ * buffer follows frt_renderer_remove_meshes.
+ * set_mesh_morph_weights: flags are FRT_DEFORM_RECOMPUTE_NORMALS and FRT_DEFORM_DEVICE. Without FRT_DEFORM_DEVICE weights is host memory: checked for
+ * finiteness (FRT_ERR_INVALID_ARG) and copied during the call. With it, weights is 4-byte aligned device memory of the renderer's device, 4 ntargets bytes,
+ * under the rules of the device form of frt_renderer_set_mesh_vertices_ex. One kernel morphs the mesh into a scratch buffer of the renderer; from there the
+ * vertices take the device-input route of frt_renderer_set_mesh_vertices_ex. What the host cannot see is rejected on the device as data: a non-finite
+ * device weight (of a target whose deltas are all zero too) and, for either kind of weights, a morphed coordinate that overflowed. Such a call changes
+ * nothing of the replica and adds one to the counter frt_renderer_deform_rejects reads.
+ * set_mesh_pose_ex: the morph kernel writes a second scratch buffer, which frt_renderer_set_mesh_pose's kernel reads in the place of the skin's bind
+ * pose. FRT_DEFORM_DEVICE covers both inputs: joint_mats (16-byte aligned) and morph_weights (4-byte aligned) are then both device memory. */
+int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
+int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
+int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* Device-input deformations this renderer has rejected since it was created (non-finite input). Waits for the main stream. */
 int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
@@ -641,6 +681,11 @@ int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh
 /* frt_renderer_set_mesh_skin and frt_renderer_set_mesh_pose on every strip's replica, between frames. FRT_DEFORM_DEVICE is refused. */
 int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
 int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
+/* frt_renderer_set_mesh_morph_targets, frt_renderer_set_mesh_morph_weights and frt_renderer_set_mesh_pose_ex on every strip's replica, between frames.
+ * FRT_DEFORM_DEVICE is refused. */
+int frt_multi_renderer_set_mesh_morph_targets(frt_multi_renderer* m, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
+int frt_multi_renderer_set_mesh_morph_weights(frt_multi_renderer* m, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
+int frt_multi_renderer_set_mesh_pose_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* frt_renderer_set_materials, _set_instance_materials, _set_light_emission and _set_texture on every strip's replica, between frames */
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials);
 int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
