@@ -455,9 +455,14 @@ int frt_multi_renderer_clear(frt_multi_renderer* m) {
 int frt_multi_renderer_set_instance_transforms(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const float* m_colmajor16) {
     return edit_every_replica(m, "multi set_instance_transforms", [&](frt_renderer* r) { return frt_renderer_set_instance_transforms(r, n, ids, m_colmajor16); });
 }
+// The strips' replicas live on different devices: no call of the mesh-edit family takes device memory here.
+static int refuse_device_flag(const char* call, uint32_t flags) {
+    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, std::string("multi ") + call + ": FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    return FRT_OK;
+}
 // Every strip deforms its own replica (frt_renderer_set_mesh_vertices), as above.
 int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
-    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_vertices: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    if (const int rc = refuse_device_flag("set_mesh_vertices", flags)) return rc;
     return edit_every_replica(m, "multi set_mesh_vertices", [&](frt_renderer* r) { return frt_renderer_set_mesh_vertices_ex(r, mesh_id, pos4, attrs, nverts, flags); });
 }
 int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
@@ -468,7 +473,7 @@ int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, co
     return edit_every_replica(m, "multi set_mesh_skin", [&](frt_renderer* r) { return frt_renderer_set_mesh_skin(r, mesh_id, joints4, weights4, nverts, njoints); });
 }
 int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
-    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_pose: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    if (const int rc = refuse_device_flag("set_mesh_pose", flags)) return rc;
     return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose(r, mesh_id, joint_mats, njoints, flags); });
 }
 // Every strip binds the morph targets to, and morphs, its own replica (frt_renderer_set_mesh_morph_targets, _set_mesh_morph_weights, _set_mesh_pose_ex).
@@ -476,11 +481,11 @@ int frt_multi_renderer_set_mesh_morph_targets(frt_multi_renderer* m, uint32_t me
     return edit_every_replica(m, "multi set_mesh_morph_targets", [&](frt_renderer* r) { return frt_renderer_set_mesh_morph_targets(r, mesh_id, deltas3, nverts, ntargets); });
 }
 int frt_multi_renderer_set_mesh_morph_weights(frt_multi_renderer* m, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
-    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_morph_weights: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    if (const int rc = refuse_device_flag("set_mesh_morph_weights", flags)) return rc;
     return edit_every_replica(m, "multi set_mesh_morph_weights", [&](frt_renderer* r) { return frt_renderer_set_mesh_morph_weights(r, mesh_id, weights, ntargets, flags); });
 }
 int frt_multi_renderer_set_mesh_pose_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
-    if (flags & FRT_DEFORM_DEVICE) return fail(FRT_ERR_INVALID_ARG, "multi set_mesh_pose: FRT_DEFORM_DEVICE is refused (the strips' replicas live on different devices)");
+    if (const int rc = refuse_device_flag("set_mesh_pose", flags)) return rc;
     return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, morph_weights, ntargets, flags); });
 }
 // The material, light and texture edits on every strip's replica, as above.

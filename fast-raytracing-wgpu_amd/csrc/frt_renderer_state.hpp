@@ -149,8 +149,8 @@ struct RefitState {
     std::vector<uint32_t> index_offset;    // per mesh
     std::vector<uint32_t> pair_levels, quad_levels;   // level L of a tree = nodes [levels[L], levels[L + 1])
     Staging rec;                           // the moved-instance records of one call (MovedInstance)
-    // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; staging of one call: pinned
-    // [positions | attributes | instance records | decoded normals], on the device the last two.
+    // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; `def`: the staging of one call of the family
+    // that deforms (vertices, pose, morph weights), its sections named by frt_scene_edit.hip's DeformLayout.
     std::vector<uint32_t> vert_count, attr_offset;
     std::vector<uint32_t> mesh_tris;       // per mesh: its triangles (what an added instance of it brings)
     Staging def;
@@ -159,19 +159,19 @@ struct RefitState {
     std::vector<const uint32_t*> adj;
     // FRT_DEFORM_DEVICE: [0] the flag of the call in flight, [1] the calls rejected so far (frt_deform.hpp: DeformInput); made at the first such call.
     uint32_t* d_reject = nullptr;
-    // frt_renderer_set_mesh_skin / _set_mesh_pose ("Skinning"): per mesh its skin on the device, one buffer [bind positions 16 nverts | weights 16 nverts |
-    // joints 8 nverts] (njoints == 0: none; the list may be shorter than the mesh list); remove_meshes frees a leaving mesh's and renumbers the rest.
-    // `skin_up`: the pinned block a bind call's joints and weights go through. `skinned`: the scratch a pose call skins into, [nverts] float4.
-    struct MeshSkin { OwnedBuf buf; uint32_t njoints = 0; };
-    std::vector<MeshSkin> skins;
+    // What a bind call leaves with a mesh: one device buffer and how many joints or targets it was bound with (0: nothing bound). The lists may be
+    // shorter than the mesh list; remove_meshes frees a leaving mesh's bindings and renumbers the rest.
+    struct MeshBinding { OwnedBuf buf; uint32_t count = 0; };
+    // frt_renderer_set_mesh_skin / _set_mesh_pose ("Skinning"): a skin is [bind positions 16 nverts | weights 16 nverts | joints 8 nverts], `count` its
+    // joints. `skin_up`: the pinned block a bind call's weights and joints go through. `skinned`: the scratch a pose call skins into, [nverts] float4.
+    std::vector<MeshBinding> skins;
     Staging skin_up;
     OwnedBuf skinned;
-    // frt_renderer_set_mesh_morph_targets / _set_mesh_morph_weights / _set_mesh_pose_ex ("Morph targets"): per mesh its targets on the device, one buffer
-    // [base positions 16 nverts | deltas, target-major, 12 nverts ntargets] (ntargets == 0: none; the list may be shorter than the mesh list);
-    // remove_meshes frees a leaving mesh's and renumbers the rest. `morph_up`: the pinned block a bind call's deltas go through. A morph call morphs into
-    // `skinned`; the combined call morphs into `morphed`, [nverts] float4, which the skin launch then reads as its bind pose.
-    struct MeshMorph { OwnedBuf buf; uint32_t ntargets = 0; };
-    std::vector<MeshMorph> morphs;
+    // frt_renderer_set_mesh_morph_targets / _set_mesh_morph_weights / _set_mesh_pose_ex ("Morph targets"): targets are [base positions 16 nverts |
+    // deltas, target-major, 12 nverts per target], `count` the targets. `morph_up`: the pinned block a bind call's deltas go through (a block of its
+    // own: a morph bind does not wait for a skin bind's copies). A morph call morphs into `skinned`; the combined call morphs into `morphed`, [nverts]
+    // float4, which the skin launch then reads as its bind pose.
+    std::vector<MeshBinding> morphs;
     Staging morph_up;
     OwnedBuf morphed;
     DeviceTransformState xf;               // FRT_TRANSFORM_DEVICE

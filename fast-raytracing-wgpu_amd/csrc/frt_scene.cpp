@@ -399,11 +399,18 @@ void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, s
     for (uint32_t c = 0; c < nidx; ++c) if (idx[c] < nverts) corners[next[idx[c]]++] = c;      // ascending c per vertex: a counting sort is stable
 }
 
+// What each call of the mesh-edit family checks first, in this order: the scene is built, no FRT_DEFORM_DEVICE (`renderer_call`: the call that takes it),
+// no unknown flag bit, the mesh id. A call without flags passes 0.
+int SceneBuilder::check_mesh_call(const char* call, const char* renderer_call, uint32_t mesh_id, uint32_t flags) {
+    const std::string c(call);
+    if (!built) { error = c + ": scene is not built"; return FRT_ERR_STATE; }
+    if (flags & FRT_DEFORM_DEVICE) { error = c + ": FRT_DEFORM_DEVICE is for " + renderer_call + " only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = c + ": unknown flag bits"; return FRT_ERR_INVALID_ARG; }
+    if (mesh_id >= mesh_positions.size()) { error = c + ": mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    return FRT_OK;
+}
 int SceneBuilder::set_mesh_vertices(uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
-    if (!built) { error = "set_mesh_vertices: scene is not built"; return FRT_ERR_STATE; }
-    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_vertices: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_vertices_ex only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
-    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_vertices: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
-    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (const int rc = check_mesh_call("set_mesh_vertices", "frt_renderer_set_mesh_vertices_ex", mesh_id, flags)) return rc;
     const std::string bad = check_mesh_vertices(pos4, attrs, nverts, (uint32_t)(mesh_positions[mesh_id].size() / 4));
     if (!bad.empty()) { error = "set_mesh_vertices: " + bad; return FRT_ERR_INVALID_ARG; }
     const bool recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
@@ -457,8 +464,7 @@ std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t 
     return "";
 }
 int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
-    if (!built) { error = "set_mesh_skin: scene is not built"; return FRT_ERR_STATE; }
-    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_skin: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (const int rc = check_mesh_call("set_mesh_skin", "", mesh_id, 0u)) return rc;
     if (!joints4) {
         if (mesh_id < mesh_skins.size()) mesh_skins[mesh_id] = MeshSkin();
         return FRT_OK;
@@ -494,8 +500,7 @@ std::string check_mesh_morph_weights(const float* weights, uint32_t ntargets, ui
     return "";
 }
 int SceneBuilder::set_mesh_morph_targets(uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
-    if (!built) { error = "set_mesh_morph_targets: scene is not built"; return FRT_ERR_STATE; }
-    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_morph_targets: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (const int rc = check_mesh_call("set_mesh_morph_targets", "", mesh_id, 0u)) return rc;
     if (!deltas3) {
         if (mesh_id < mesh_morphs.size()) mesh_morphs[mesh_id] = MeshMorph();
         return FRT_OK;
@@ -519,10 +524,7 @@ static std::string morph_mesh(const SceneBuilder::MeshMorph& k, const float* wei
     return "";
 }
 int SceneBuilder::set_mesh_morph_weights(uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
-    if (!built) { error = "set_mesh_morph_weights: scene is not built"; return FRT_ERR_STATE; }
-    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_morph_weights: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_morph_weights only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
-    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_morph_weights: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
-    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_morph_weights: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (const int rc = check_mesh_call("set_mesh_morph_weights", "frt_renderer_set_mesh_morph_weights", mesh_id, flags)) return rc;
     std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < mesh_morphs.size() ? mesh_morphs[mesh_id].ntargets : 0u);
     std::vector<float> morphed;
     if (bad.empty()) bad = morph_mesh(mesh_morphs[mesh_id], weights, morphed);
@@ -531,10 +533,7 @@ int SceneBuilder::set_mesh_morph_weights(uint32_t mesh_id, const float* weights,
 }
 // set_mesh_pose's checks in set_mesh_pose's order; with morph weights the morph's follow, and the morphed positions stand where the bind pose stood.
 int SceneBuilder::set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
-    if (!built) { error = "set_mesh_pose: scene is not built"; return FRT_ERR_STATE; }
-    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_pose: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_pose only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
-    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_pose: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
-    if (mesh_id >= mesh_positions.size()) { error = "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(mesh_positions.size()) + " meshes)"; return FRT_ERR_INVALID_ARG; }
+    if (const int rc = check_mesh_call("set_mesh_pose", "frt_renderer_set_mesh_pose", mesh_id, flags)) return rc;
     std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u);
     if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
     const MeshSkin& k = mesh_skins[mesh_id];
@@ -915,6 +914,13 @@ int SceneBuilder::remove_materials(uint32_t n, const uint32_t* ids) {
     for (InstanceRec& in : instances) if (in.mat_id < map.size()) in.mat_id = map[in.mat_id];
     return rebuild_or_undo(*this, undo, "remove_materials");
 }
+// A per-mesh list of bindings (empty, or as long as the last bound mesh asks) loses the entries of the meshes `gone`: the survivors' follow their new ids.
+template <class T>
+static void bindings_follow_mesh_ids(std::vector<T>& list, size_t old_meshes, const std::vector<uint32_t>& gone) {
+    if (list.empty()) return;
+    list.resize(old_meshes);
+    remove_elements(list, gone);
+}
 int SceneBuilder::remove_meshes(uint32_t n, const uint32_t* ids) {
     if (!built) { error = "remove_meshes: scene is not built"; return FRT_ERR_STATE; }
     std::vector<uint32_t> gone;
@@ -935,13 +941,9 @@ int SceneBuilder::remove_meshes(uint32_t n, const uint32_t* ids) {
     remove_elements(mesh_positions, gone); remove_elements(mesh_index_counts, gone);
     for (InstanceRec& in : instances) in.mesh_id = map[in.mesh_id];
     const int rc = rebuild_or_undo(*this, undo, "remove_meshes");
-    if (rc == FRT_OK && !mesh_skins.empty()) {      // the skins follow the mesh ids (a call that was undone leaves them)
-        mesh_skins.resize(map.size());
-        remove_elements(mesh_skins, gone);
-    }
-    if (rc == FRT_OK && !mesh_morphs.empty()) {     // and so do the morph targets
-        mesh_morphs.resize(map.size());
-        remove_elements(mesh_morphs, gone);
+    if (rc == FRT_OK) {      // the skins and the morph targets follow the mesh ids (a call that was undone leaves them)
+        bindings_follow_mesh_ids(mesh_skins, map.size(), gone);
+        bindings_follow_mesh_ids(mesh_morphs, map.size(), gone);
     }
     return rc;
 }

@@ -173,6 +173,9 @@ public:
     // Per mesh its morph targets (set_mesh_morph_targets); ntargets == 0: none. Shorter than the mesh list while the last meshes have none.
     struct MeshMorph { uint32_t ntargets = 0; std::vector<float> deltas, base; };      // deltas [ntargets][nverts][3], base [nverts][4]
     std::vector<MeshMorph> mesh_morphs;
+private:
+    int check_mesh_call(const char* call, const char* renderer_call, uint32_t mesh_id, uint32_t flags);      // the preamble of the mesh-edit calls (frt_scene.cpp)
+public:
     // built
     bool built = false;
     std::vector<TriRec> tris;

@@ -12,6 +12,9 @@
 //   - capacities (PoolState::cap, pool_count, pool_cap, reserve_pools): every buffer of the replica that is sized by a count;
 //   - the buffers beside the replica that a call writes and that then trade places with the replica's (OwnedBuf);
 //   - staging (Staging): what a call uploads goes through a pinned block that is reused once the copies out of it have completed.
+// The seven calls on meshes are one family: one entry check (check_mesh_call), one check of a device pointer (check_device_input), one type and one
+// helper for what a bind call leaves with a mesh (RefitState::MeshBinding, bind_to_mesh), and one body for everything that deforms (deform_mesh: a
+// DeformCall says where the positions come from, a DeformLayout where each section of the call's blocks lies, and three steps stage, pose and apply).
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -286,17 +289,22 @@ static void drop_transform_tables(frt_renderer* r, bool matrices) {
     r->rf.xf.consts_ok = false;
     if (matrices) r->rf.xf.m_ok = false;
 }
+// The two words a device-input call's kernels report through exist afterwards, zeroed when made: [0] the flag of the call in flight, [1] the calls
+// rejected so far (RefitState::d_reject, DeviceTransformState::d_reject).
+static int ensure_reject_words(frt_renderer* r, uint32_t*& words) {
+    if (words) return FRT_OK;
+    void* d = nullptr;
+    if (const int rc = scene_alloc(r, 2 * sizeof(uint32_t), &d)) return rc;
+    HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
+    words = static_cast<uint32_t*>(d);
+    return FRT_OK;
+}
 // The tables of a device-input call exist and are current afterwards; what is not is uploaded from the host's bookkeeping on the main stream.
 static int ensure_transform_tables(frt_renderer* r) {
     RefitState& f = r->rf;
     DeviceTransformState& x = f.xf;
     int rc;
-    if (!x.d_reject) {
-        void* d = nullptr;
-        if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
-        HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
-        x.d_reject = static_cast<uint32_t*>(d);
-    }
+    if ((rc = ensure_reject_words(r, x.d_reject))) return rc;
     if (x.consts_ok && x.m_ok) return FRT_OK;
     const size_t ni = f.inst.size(), cap = std::max<size_t>(pool_cap(r, kPoolInstances), ni);
     if (x.m.bytes < cap * 64u) {      // (a table that is replaced loses its contents: the matrices come from the mirror)
@@ -348,6 +356,12 @@ static int check_device_pointer(const frt_renderer* r, const void* p, size_t byt
     if (before > size || size - before < bytes)
         return fail(FRT_ERR_INVALID_ARG, w + ": the device allocation holds " + std::to_string(size - std::min(before, size)) + " bytes from the pointer on, " + std::to_string(bytes) + " are needed");
     return FRT_OK;
+}
+// The same with the renderer's device current, as the pointer queries need it: what every call that takes device input asks of each of its pointers.
+static int check_device_input(const frt_renderer* r, const void* p, size_t bytes, size_t align, const char* call, const char* what, const char* flag = "FRT_DEFORM_DEVICE") {
+    DeviceGuard guard(r->device);
+    if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
+    return check_device_pointer(r, p, bytes, align, call, what, flag);
 }
 // Both trees level by level, deepest first: launch k refits the k-th deepest level of each (after a rebuild the pair tree has no levels left).
 static int refit_levels(frt_renderer* r) {
@@ -416,10 +430,8 @@ int frt_renderer_set_instance_transforms_ex(frt_renderer* r, uint32_t n, const u
     if (n > 0 && (!ids || !mats)) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: null ids or matrices");
     if (n > kMaxDeviceTransforms) return fail(FRT_ERR_INVALID_ARG, "set_instance_transforms: more than 2^26 records in one device-input call");
     if (n > 0) {
-        DeviceGuard guard(r->device);
-        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, ids, (size_t)n * 4, 4, "set_instance_transforms", "ids", "FRT_TRANSFORM_DEVICE")) return rc;
-        if (const int rc = check_device_pointer(r, mats, (size_t)n * 64, 16, "set_instance_transforms", "matrices", "FRT_TRANSFORM_DEVICE")) return rc;
+        if (const int rc = check_device_input(r, ids, (size_t)n * 4, 4, "set_instance_transforms", "ids", "FRT_TRANSFORM_DEVICE")) return rc;
+        if (const int rc = check_device_input(r, mats, (size_t)n * 64, 16, "set_instance_transforms", "matrices", "FRT_TRANSFORM_DEVICE")) return rc;
     }
     return edit_frame(r, true, [&]() -> int {
         RefitState& f = r->rf;
@@ -435,7 +447,18 @@ int frt_renderer_set_instance_transforms_ex(frt_renderer* r, uint32_t n, const u
     });
 }
 
-// ------------------------------------------------------------------------------------------------ deforming meshes ("Deforming meshes")
+// ------------------------------------------------------------------------------------------------ the mesh-edit family ("Deforming meshes", "Skinning", "Morph targets")
+// What each of the seven calls checks first, in this order: the entry, flag bits outside `allowed_flags`, the mesh id.
+static int check_mesh_call(const frt_renderer* r, const char* call, uint32_t mesh_id, uint32_t flags, uint32_t allowed_flags) {
+    const std::string c(call);
+    if (const int rc = check_entry(r, c, kEditChecks | kRefit)) return rc;
+    if (flags & ~allowed_flags) return fail(FRT_ERR_INVALID_ARG, c + ": unknown flag bits");
+    if (mesh_id >= r->rf.vert_count.size())
+        return fail(FRT_ERR_INVALID_ARG, c + ": mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    return FRT_OK;
+}
+static const uint32_t kDeformFlags = FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE;
+
 // The vertex -> corner adjacency of mesh `m` is on the device afterwards (RefitState::adj). Made once per mesh from the replica's own indices: a wait for
 // the stream and one read-back, as ensure_normals; frt_renderer_remove_meshes keeps the list in step with the mesh ids.
 static int ensure_adjacency(frt_renderer* r, uint32_t m) {
@@ -454,130 +477,168 @@ static int ensure_adjacency(frt_renderer* r, uint32_t m) {
     f.adj[m] = static_cast<const uint32_t*>(d);
     return FRT_OK;
 }
-// What follows the checks of a deformation, inside its call frame: the staging, the launches and the refit. frt_renderer_set_mesh_vertices_ex (`pose` null)
-// and frt_renderer_set_mesh_pose run these lines. With `pose`, pos4 and attrs are ignored (no attributes): the mesh is skinned into RefitState::skinned by
-// frt_skin.hpp's kernel, and that buffer then takes the device-input route; a palette from the host rides in the call's pinned and device blocks.
-// frt_renderer_set_mesh_morph_weights (`morph` alone) is the same with frt_morph.hpp's kernel in the skin kernel's place, its host weights behind the
-// palette's place in the blocks. frt_renderer_set_mesh_pose_ex (both): the morph launch writes RefitState::morphed, and the skin launch, otherwise
-// unchanged, reads that buffer as its bind pose.
-struct PoseInput { const float* mats; uint32_t njoints; bool device; };
-struct MorphInput { const float* weights; uint32_t ntargets; bool device; };
-static int deform_mesh(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags, const PoseInput* pose,
-                       const MorphInput* morph = nullptr) {
-    if (pose || morph) attrs = nullptr;
+
+// One deformation, as its C call has checked it. `source` says where the new positions come from: the caller's host memory, the caller's device memory
+// (FRT_DEFORM_DEVICE), or the renderer's scratch after a skin launch, a morph launch, or a morph launch and then a skin launch over its result. Only the
+// first two read `pos4` and may bring attributes (which live where the positions live); the others read the mesh's bindings and what they name here:
+// `palette` for a skin launch, `weights` for a morph launch, each in host memory (it rides in the call's blocks) or, `*_on_device`, in the caller's
+// device memory (the launch checks its finiteness).
+enum class PosSource { Host, Device, Skin, Morph, MorphThenSkin };
+struct DeformCall {
+    uint32_t mesh_id = 0, nverts = 0;
+    PosSource source = PosSource::Host;
+    bool recompute = false;                       // FRT_DEFORM_RECOMPUTE_NORMALS
+    const float* pos4 = nullptr;
+    const frt_vertex_attr* attrs = nullptr;
+    const float* palette = nullptr; uint32_t njoints = 0; bool palette_on_device = false;
+    const float* weights = nullptr; uint32_t ntargets = 0; bool weights_on_device = false;
+    bool skins() const { return source == PosSource::Skin || source == PosSource::MorphThenSkin; }
+    bool morphs() const { return source == PosSource::Morph || source == PosSource::MorphThenSkin; }
+    bool posed() const { return skins() || morphs(); }
+    bool device_route() const { return source != PosSource::Host; }      // the positions reach the replica through frt_deform.hpp's validation and copy-in
+    bool shade() const { return attrs || recompute; }                    // the shading records are written again: the device block holds decoded normals
+    bool host_decode() const { return attrs && !recompute && !device_route(); }      // ... which the host decodes from the call's attributes
+};
+// Where everything a call stages lies in the two blocks of RefitState::def, computed once; a section that a call does not use is empty.
+//   pinned: positions | attributes | instance records | decoded normals | palette | weights
+//   device:                          instance records | decoded normals | palette | weights
+// The first two pinned sections are copied into the replica (the object-space positions the instance update reads, SceneView::attributes). Records and
+// normals are neighbours in both blocks and go over in one copy (`h_up`); the device's normals section is there whenever shading records are written
+// (the normal pass fills it where the host did not), the pinned one only for the host's decode.
+struct Section { size_t off = 0, bytes = 0; };
+struct DeformLayout {
+    Section h_pos, h_attrs, h_rec, h_nrm, h_pal, h_wt, h_up, d_rec, d_nrm, d_pal, d_wt;
+    size_t h_total = 0, d_total = 0;
+    DeformLayout(const DeformCall& c, size_t ninstances) {
+        auto put = [](size_t& total, size_t bytes) { const Section s{total, bytes}; total += bytes; return s; };
+        const size_t n = c.nverts, rec = ninstances * sizeof(DeformInstance);
+        const size_t pal = c.skins() && !c.palette_on_device ? (size_t)c.njoints * 64 : 0, wt = c.morphs() && !c.weights_on_device ? (size_t)c.ntargets * 4 : 0;
+        h_pos = put(h_total, c.device_route() ? 0 : n * 16);
+        h_attrs = put(h_total, c.attrs && !c.device_route() ? n * sizeof(frt_vertex_attr) : 0);
+        h_rec = put(h_total, rec);
+        h_nrm = put(h_total, c.host_decode() ? n * 16 : 0);
+        h_pal = put(h_total, pal);
+        h_wt = put(h_total, wt);
+        h_up = Section{h_rec.off, h_rec.bytes + h_nrm.bytes};
+        d_rec = put(d_total, rec);
+        d_nrm = put(d_total, c.shade() ? n * 16 : 0);
+        d_pal = put(d_total, pal);
+        d_wt = put(d_total, wt);
+    }
+};
+// Step 1: the call's data into the pinned block and, in stream order, out of it. RefitState::def is reused in stream order and replaced, after a wait
+// for the stream, only when it has to grow.
+static int stage_deform(frt_renderer* r, const DeformCall& c, const DeformLayout& l, const std::vector<DeformInstance>& rec) {
     RefitState& f = r->rf;
-    const bool dev = pose || morph || (flags & FRT_DEFORM_DEVICE), recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
-    if (const int rc = sync_matrix_mirror(r)) return rc;      // (the instances' matrices are read below)
-    std::vector<DeformInstance> rec;
-    uint32_t work = 0;
-    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
-        const InstanceRec& in = f.inst[i];
-        if (in.mesh_id != mesh_id) continue;
-        DeformInstance d;
-        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
-        for (int c = 0; c < 4; ++c) for (int a = 0; a < 3; ++a) d.m[3 * c + a] = in.m[4 * c + a];
-        rec.push_back(d);
-    }
-    const bool shade = attrs || recompute;            // the shading records are written again: the device block holds the decoded normals
-    const bool host_decode = attrs && !recompute && !dev;
-    const size_t pos_bytes = dev ? 0 : (size_t)nverts * 16, attr_bytes = attrs && !dev ? (size_t)nverts * sizeof(frt_vertex_attr) : 0;
-    const size_t rec_bytes = rec.size() * sizeof(DeformInstance), nrm_bytes = shade ? (size_t)nverts * 16 : 0;
-    const size_t up_bytes = rec_bytes + (host_decode ? nrm_bytes : 0);      // what is copied into the device block
-    const size_t pal_bytes = pose && !pose->device ? (size_t)pose->njoints * 64 : 0;      // a host palette: behind both, in the pinned and in the device block
-    const size_t wt_bytes = morph && !morph->device ? (size_t)morph->ntargets * 4 : 0;      // host morph weights: behind the palette, in both blocks
-    int rc;
-    if (pose || morph) {
-        if ((rc = f.skinned.ensure(r, (size_t)nverts * 16))) return rc;
-        if (pose && morph && (rc = f.morphed.ensure(r, (size_t)nverts * 16))) return rc;
-        pos4 = f.skinned.as<float>();
-    }
-    if (recompute && (rc = ensure_adjacency(r, mesh_id))) return rc;
-    if (dev && !f.d_reject) {
-        void* d = nullptr;
-        if ((rc = scene_alloc(r, 2 * sizeof(uint32_t), &d))) return rc;
-        HIP_TRY(hipMemset(d, 0, 2 * sizeof(uint32_t)));
-        f.d_reject = static_cast<uint32_t*>(d);
-    }
-    if ((rc = f.def.reserve(pos_bytes + attr_bytes + up_bytes + pal_bytes + wt_bytes, rec_bytes + nrm_bytes + pal_bytes + wt_bytes, r->stream))) return rc;
-    uint8_t* h_pos = f.def.h; uint8_t* h_attr = h_pos + pos_bytes; uint8_t* h_up = h_attr + attr_bytes; uint8_t* h_pal = h_up + up_bytes; uint8_t* h_wt = h_pal + pal_bytes;
-    uint8_t* d_pal = f.def.d + rec_bytes + nrm_bytes; uint8_t* d_wt = d_pal + pal_bytes;
-    float4* block = shade ? reinterpret_cast<float4*>(f.def.d + rec_bytes) : nullptr;
-    float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
-    const uint32_t cap_verts = pool_cap(r, kPoolVerts);
-    if ((uint64_t)f.pos_offset[mesh_id] + nverts > cap_verts || (uint64_t)f.attr_offset[mesh_id] + nverts > cap_verts)
+    const uint32_t m = c.mesh_id, cap_verts = pool_cap(r, kPoolVerts);
+    if (const int rc = f.def.reserve(l.h_total, l.d_total, r->stream)) return rc;
+    if ((uint64_t)f.pos_offset[m] + c.nverts > cap_verts || (uint64_t)f.attr_offset[m] + c.nverts > cap_verts)
         return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the vertex pool");
-    if ((uint64_t)f.index_offset[mesh_id] + 3ull * f.mesh_tris[mesh_id] > pool_cap(r, kPoolIndices))
+    if ((uint64_t)f.index_offset[m] + 3ull * f.mesh_tris[m] > pool_cap(r, kPoolIndices))
         return fail(FRT_ERR_STATE, "set_mesh_vertices: the mesh does not lie inside the index pool");
-    if (!dev) memcpy(h_pos, pos4, pos_bytes);
-    if (attr_bytes) memcpy(h_attr, attrs, attr_bytes);
-    if (host_decode) {
-        float* nrm = reinterpret_cast<float*>(h_up + rec_bytes);
-        for (uint32_t v = 0; v < nverts; ++v) { decoded_vertex_normal(attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
+    uint8_t* h = f.def.h; uint8_t* d = f.def.d;
+    float4* pool_normals = const_cast<float4*>(r->pools.d_normals);      // (what a later frt_renderer_add_instances of this mesh reads, §14; may be null)
+    if (l.h_pos.bytes) memcpy(h + l.h_pos.off, c.pos4, l.h_pos.bytes);
+    if (l.h_attrs.bytes) memcpy(h + l.h_attrs.off, c.attrs, l.h_attrs.bytes);
+    if (c.host_decode()) {
+        float* nrm = reinterpret_cast<float*>(h + l.h_nrm.off);
+        for (uint32_t v = 0; v < c.nverts; ++v) { decoded_vertex_normal(c.attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
     }
-    if (rec_bytes) memcpy(h_up, rec.data(), rec_bytes);
-    if (pal_bytes) memcpy(h_pal, pose->mats, pal_bytes);
-    if (wt_bytes) memcpy(h_wt, morph->weights, wt_bytes);
-    if (!dev) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[mesh_id], h_pos, pos_bytes, hipMemcpyHostToDevice, r->stream));
-    if (attr_bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[mesh_id], h_attr, attr_bytes, hipMemcpyHostToDevice, r->stream));
-    if (up_bytes) HIP_TRY(hipMemcpyAsync(f.def.d, h_up, up_bytes, hipMemcpyHostToDevice, r->stream));
-    if (host_decode && pool_normals)
-        HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[mesh_id], h_up + rec_bytes, nrm_bytes, hipMemcpyHostToDevice, r->stream));
-    if (pal_bytes) HIP_TRY(hipMemcpyAsync(d_pal, h_pal, pal_bytes, hipMemcpyHostToDevice, r->stream));
-    if (wt_bytes) HIP_TRY(hipMemcpyAsync(d_wt, h_wt, wt_bytes, hipMemcpyHostToDevice, r->stream));
-    if ((rc = f.def.mark(r->stream))) return rc;
-    const uint32_t* reject = dev ? f.d_reject : nullptr;      // (host input was validated above: there is no flag to look at)
-    // the morphed or skinned vertices are this call's device input: the flag is zeroed here, in front of the launch that may raise it first
-    if (pose || morph) HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
-    if (morph) {
-        const uint8_t* k = static_cast<const uint8_t*>(f.morphs[mesh_id].buf.p);
-        const OwnedBuf& out = pose ? f.morphed : f.skinned;
-        const MorphArgs ma{reinterpret_cast<const float4*>(k), reinterpret_cast<const float*>(k + (size_t)nverts * 16),
-                           morph->device ? morph->weights : reinterpret_cast<const float*>(d_wt), out.as<float4>(),
-                           nverts, morph->ntargets, (uint32_t)std::min<size_t>(out.bytes / 16, 0xFFFFFFFFu), morph->device ? 1u : 0u, f.d_reject};
+    if (l.h_rec.bytes) memcpy(h + l.h_rec.off, rec.data(), l.h_rec.bytes);
+    if (l.h_pal.bytes) memcpy(h + l.h_pal.off, c.palette, l.h_pal.bytes);
+    if (l.h_wt.bytes) memcpy(h + l.h_wt.off, c.weights, l.h_wt.bytes);
+    if (!c.device_route()) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[m], h + l.h_pos.off, l.h_pos.bytes, hipMemcpyHostToDevice, r->stream));
+    if (l.h_attrs.bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[m], h + l.h_attrs.off, l.h_attrs.bytes, hipMemcpyHostToDevice, r->stream));
+    if (l.h_up.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_rec.off, h + l.h_up.off, l.h_up.bytes, hipMemcpyHostToDevice, r->stream));
+    if (c.host_decode() && pool_normals) HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[m], h + l.h_nrm.off, l.h_nrm.bytes, hipMemcpyHostToDevice, r->stream));
+    if (l.h_pal.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_pal.off, h + l.h_pal.off, l.h_pal.bytes, hipMemcpyHostToDevice, r->stream));
+    if (l.h_wt.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_wt.off, h + l.h_wt.off, l.h_wt.bytes, hipMemcpyHostToDevice, r->stream));
+    return f.def.mark(r->stream);
+}
+// Step 2, the posing sources only: the morph launch and/or the skin launch into the scratch buffers. Their result is this call's device input, so the
+// flag is zeroed here, in front of the launch that may raise it first. Morph then skin: the morph launch writes RefitState::morphed, and the skin
+// launch, otherwise unchanged, reads that buffer as its bind pose.
+static int pose_deform(frt_renderer* r, const DeformCall& c, const DeformLayout& l) {
+    RefitState& f = r->rf;
+    const size_t pos_bytes = (size_t)c.nverts * 16;      // (the first section of a binding's buffer: RefitState::MeshBinding)
+    HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
+    if (c.morphs()) {
+        const uint8_t* k = static_cast<const uint8_t*>(f.morphs[c.mesh_id].buf.p);
+        const OwnedBuf& out = c.skins() ? f.morphed : f.skinned;
+        const MorphArgs ma{reinterpret_cast<const float4*>(k), reinterpret_cast<const float*>(k + pos_bytes),
+                           c.weights_on_device ? c.weights : reinterpret_cast<const float*>(f.def.d + l.d_wt.off), out.as<float4>(),
+                           c.nverts, c.ntargets, (uint32_t)std::min<size_t>(out.bytes / 16, 0xFFFFFFFFu), c.weights_on_device ? 1u : 0u, f.d_reject};
         HIP_TRY(launch_mesh_morph(ma, r->stream));
     }
-    if (pose) {
-        const uint8_t* k = static_cast<const uint8_t*>(f.skins[mesh_id].buf.p);
-        const SkinArgs sa{morph ? f.morphed.as<const float4>() : reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + (size_t)nverts * 16), reinterpret_cast<const uint2*>(k + (size_t)nverts * 32),
-                          pose->device ? reinterpret_cast<const float4*>(pose->mats) : reinterpret_cast<const float4*>(d_pal), f.skinned.as<float4>(),
-                          nverts, pose->njoints, (uint32_t)std::min<size_t>(f.skinned.bytes / 16, 0xFFFFFFFFu), pose->device ? 1u : 0u, f.d_reject};
+    if (c.skins()) {
+        const uint8_t* k = static_cast<const uint8_t*>(f.skins[c.mesh_id].buf.p);
+        const SkinArgs sa{c.morphs() ? f.morphed.as<const float4>() : reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + pos_bytes), reinterpret_cast<const uint2*>(k + 2 * pos_bytes),
+                          reinterpret_cast<const float4*>(c.palette_on_device ? reinterpret_cast<const uint8_t*>(c.palette) : f.def.d + l.d_pal.off), f.skinned.as<float4>(),
+                          c.nverts, c.njoints, (uint32_t)std::min<size_t>(f.skinned.bytes / 16, 0xFFFFFFFFu), c.palette_on_device ? 1u : 0u, f.d_reject};
         HIP_TRY(launch_mesh_skin(sa, r->stream));
     }
-    if (dev) {
-        DeformInput in{reinterpret_cast<const float4*>(pos4), reinterpret_cast<const float4*>(attrs), nverts, f.pos_offset[mesh_id], f.attr_offset[mesh_id], cap_verts,
+    return FRT_OK;
+}
+// Step 3: device positions (the caller's, or the scratch of step 2) through the validation and copy-in launches of frt_deform.hpp, the normal pass,
+// the mesh's triangles under every instance of it, the scene extent and the refit. `work`: the triangles of those instances.
+static int apply_deform(frt_renderer* r, const DeformCall& c, const DeformLayout& l, uint32_t ninstances, uint32_t work) {
+    RefitState& f = r->rf;
+    const uint32_t m = c.mesh_id, cap_verts = pool_cap(r, kPoolVerts);
+    float4* block = c.shade() ? reinterpret_cast<float4*>(f.def.d + l.d_nrm.off) : nullptr;
+    float4* pool_normals = const_cast<float4*>(r->pools.d_normals);
+    const uint32_t* reject = c.device_route() ? f.d_reject : nullptr;      // (host input was validated by the call: there is no flag to look at)
+    if (c.device_route()) {
+        const bool decode = c.attrs && !c.recompute;
+        DeformInput in{c.posed() ? f.skinned.as<const float4>() : reinterpret_cast<const float4*>(c.pos4), reinterpret_cast<const float4*>(c.attrs), c.nverts, f.pos_offset[m], f.attr_offset[m], cap_verts,
                        const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
-                       attrs && !recompute ? block : nullptr, attrs && !recompute ? pool_normals : nullptr, f.d_reject};
-        HIP_TRY(launch_deform_input(in, r->stream, !(pose || morph)));
+                       decode ? block : nullptr, decode ? pool_normals : nullptr, f.d_reject};
+        HIP_TRY(launch_deform_input(in, r->stream, !c.posed()));
     }
-    if (recompute) {
-        NormalArgs na{f.adj[mesh_id], f.adj[mesh_id] + (nverts + 1u), nverts, 3u * f.mesh_tris[mesh_id], f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+    if (c.recompute) {
+        NormalArgs na{f.adj[m], f.adj[m] + (c.nverts + 1u), c.nverts, 3u * f.mesh_tris[m], f.index_offset[m], f.pos_offset[m], f.attr_offset[m],
                       cap_verts, pool_cap(r, kPoolIndices), f.d_pos, block, pool_normals, reject};
 #if FRT_EXPERIMENTS
         const char* tri_pass = getenv("FRT_NORMALS_TRI_PASS");
         if (tri_pass && atoi(tri_pass) != 0) {
-            if ((rc = f.tri_normals.ensure(r, (size_t)f.mesh_tris[mesh_id] * sizeof(float4)))) return rc;
+            if (const int rc = f.tri_normals.ensure(r, (size_t)f.mesh_tris[m] * sizeof(float4))) return rc;
             na.tri_scratch = f.tri_normals.as<float4>();
         }
 #endif
         HIP_TRY(launch_vertex_normals(r->sv, na, r->stream));
     }
     if (work == 0) return FRT_OK;      // no instance of the mesh: no triangle changes
-    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d), (uint32_t)rec.size(), work, f.index_offset[mesh_id], f.pos_offset[mesh_id], f.attr_offset[mesh_id],
+    DeformArgs a{reinterpret_cast<const DeformInstance*>(f.def.d + l.d_rec.off), ninstances, work, f.index_offset[m], f.pos_offset[m], f.attr_offset[m],
                  f.d_pos, block, f.d_slot_of, reject};
     HIP_TRY(launch_mesh_deform(r->sv, a, r->stream));
     HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
     return refit_levels(r);
 }
-// Host input: one pinned block holds what a call uploads, [positions | attributes | instance records | decoded normals]; the first two are copied into the
-// replica (the object-space positions the instance update reads, SceneView::attributes), the last two into the device block of RefitState::def, which is
-// reused in stream order and replaced, after a wait for the stream, only when it has to grow. With FRT_DEFORM_RECOMPUTE_NORMALS the host decodes nothing:
-// the normal pass writes the decoded normals into the device block. Device input (FRT_DEFORM_DEVICE): only the instance records are staged; the
-// vertices reach the replica through the validation and copy-in launches of frt_deform.hpp.
+// What follows the checks of a deformation, inside its call frame: the instance records, what the call needs beside the staging, and the three steps.
+static int deform_mesh(frt_renderer* r, const DeformCall& c) {
+    RefitState& f = r->rf;
+    int rc;
+    if ((rc = sync_matrix_mirror(r))) return rc;      // (the instances' matrices are read below)
+    std::vector<DeformInstance> rec;
+    uint32_t work = 0;
+    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
+        const InstanceRec& in = f.inst[i];
+        if (in.mesh_id != c.mesh_id) continue;
+        DeformInstance d;
+        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = work; work += in.tri_count;
+        for (int col = 0; col < 4; ++col) for (int a = 0; a < 3; ++a) d.m[3 * col + a] = in.m[4 * col + a];
+        rec.push_back(d);
+    }
+    const DeformLayout l(c, rec.size());
+    if (c.posed() && (rc = f.skinned.ensure(r, (size_t)c.nverts * 16))) return rc;
+    if (c.skins() && c.morphs() && (rc = f.morphed.ensure(r, (size_t)c.nverts * 16))) return rc;
+    if (c.recompute && (rc = ensure_adjacency(r, c.mesh_id))) return rc;
+    if (c.device_route() && (rc = ensure_reject_words(r, f.d_reject))) return rc;
+    if ((rc = stage_deform(r, c, l, rec))) return rc;
+    if (c.posed() && (rc = pose_deform(r, c, l))) return rc;
+    return apply_deform(r, c, l, (uint32_t)rec.size(), work);
+}
 int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
-    if (const int rc = check_entry(r, "set_mesh_vertices", kEditChecks | kRefit)) return rc;
-    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: unknown flag bits");
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (const int rc = check_mesh_call(r, "set_mesh_vertices", mesh_id, flags, kDeformFlags)) return rc;
     const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
     if (!dev) {
         const std::string bad = check_mesh_vertices(pos4, attrs, nverts, r->rf.vert_count[mesh_id]);
@@ -586,168 +647,112 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
         if (!pos4) return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: null positions");
         if (nverts != r->rf.vert_count[mesh_id])
             return fail(FRT_ERR_INVALID_ARG, "set_mesh_vertices: " + std::to_string(nverts) + " vertices given, the mesh has " + std::to_string(r->rf.vert_count[mesh_id]) + " (the topology is fixed)");
-        DeviceGuard guard(r->device);
-        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, pos4, (size_t)nverts * 16, 16, "set_mesh_vertices", "positions", "FRT_DEFORM_DEVICE")) return rc;
-        if (attrs) if (const int rc = check_device_pointer(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), 16, "set_mesh_vertices", "attributes", "FRT_DEFORM_DEVICE")) return rc;
+        if (const int rc = check_device_input(r, pos4, (size_t)nverts * 16, 16, "set_mesh_vertices", "positions")) return rc;
+        if (attrs) if (const int rc = check_device_input(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), 16, "set_mesh_vertices", "attributes")) return rc;
     }
-    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, mesh_id, pos4, attrs, nverts, flags, nullptr); });
+    DeformCall c;
+    c.mesh_id = mesh_id; c.nverts = nverts; c.source = dev ? PosSource::Device : PosSource::Host; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    c.pos4 = pos4; c.attrs = attrs;
+    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
 }
 int frt_renderer_set_mesh_vertices(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts) {
     return frt_renderer_set_mesh_vertices_ex(r, mesh_id, pos4, attrs, nverts, 0u);
 }
 
-// ------------------------------------------------------------------------------------------------ skinning ("Skinning")
-// The skin of mesh `m` leaves (behind a wait: a pose's kernel may still read it).
-static int drop_skin(frt_renderer* r, uint32_t m) {
-    RefitState& f = r->rf;
-    if (m >= f.skins.size() || !f.skins[m].buf.p) return FRT_OK;
+// ------------------------------------------------------------------------------------------------ binding skins and morph targets
+// The binding of mesh `m` in `list` leaves (behind a wait: a pose's or a morph's kernel may still read it).
+static int drop_binding(frt_renderer* r, std::vector<RefitState::MeshBinding>& list, uint32_t m) {
+    if (m >= list.size() || !list[m].buf.p) return FRT_OK;
     HIP_TRY(hipStreamSynchronize(r->stream));
-    scene_free(r, f.skins[m].buf.p);
-    f.skins[m] = RefitState::MeshSkin();
+    scene_free(r, list[m].buf.p);
+    list[m] = RefitState::MeshBinding();
     return FRT_OK;
 }
-// Joints and weights go through the pinned block of RefitState::skin_up into the mesh's own buffer; the bind pose is copied there from the replica's
-// object-space positions on the stream, behind every deformation enqueued so far. The speculation is kept: nothing a frame reads changes.
+// Mesh `mesh_id` gets a binding in `list`: its buffer is [the mesh's positions | the host parts, in order]. The positions are copied from the replica's
+// object-space positions on the stream, behind every deformation enqueued so far; the host parts go through the pinned block of `up`.
+struct HostPart { const void* p; size_t bytes; };
+static int bind_to_mesh(frt_renderer* r, const char* call, std::vector<RefitState::MeshBinding>& list, Staging& up, uint32_t mesh_id, uint32_t nverts,
+                        std::initializer_list<HostPart> parts, uint32_t count) {
+    RefitState& f = r->rf;
+    if (list.size() <= mesh_id) list.resize((size_t)mesh_id + 1u);
+    RefitState::MeshBinding& k = list[mesh_id];
+    const size_t pos_bytes = (size_t)nverts * 16;
+    size_t host_bytes = 0;
+    for (const HostPart& part : parts) host_bytes += part.bytes;
+    int rc;
+    if ((uint64_t)f.pos_offset[mesh_id] + nverts > pool_cap(r, kPoolVerts)) return fail(FRT_ERR_STATE, std::string(call) + ": the mesh does not lie inside the vertex pool");
+    k.count = 0;      // (a call that fails below leaves the mesh without the binding)
+    if ((rc = k.buf.ensure(r, pos_bytes + host_bytes))) return rc;
+    if ((rc = up.reserve(host_bytes, 0, r->stream))) return rc;
+    size_t at = 0;
+    for (const HostPart& part : parts) { memcpy(up.h + at, part.p, part.bytes); at += part.bytes; }
+    if (nverts) {
+        HIP_TRY(hipMemcpyAsync(k.buf.p, f.d_pos + f.pos_offset[mesh_id], pos_bytes, hipMemcpyDeviceToDevice, r->stream));
+        HIP_TRY(hipMemcpyAsync(k.buf.as<uint8_t>() + pos_bytes, up.h, host_bytes, hipMemcpyHostToDevice, r->stream));
+    }
+    if ((rc = up.mark(r->stream))) return rc;
+    k.count = count;
+    return FRT_OK;
+}
+// Skinning: [bind positions | weights | joints]. The speculation is kept: nothing a frame reads changes.
 int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
-    if (const int rc = check_entry(r, "set_mesh_skin", kEditChecks | kRefit)) return rc;
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (const int rc = check_mesh_call(r, "set_mesh_skin", mesh_id, 0u, 0u)) return rc;
     if (joints4) {
         const std::string bad = check_mesh_skin(joints4, weights4, nverts, njoints, r->rf.vert_count[mesh_id]);
         if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: " + bad);
     }
     return edit_frame(r, false, [&]() -> int {
-        RefitState& f = r->rf;
-        if (!joints4) return drop_skin(r, mesh_id);
-        if (f.skins.size() <= mesh_id) f.skins.resize((size_t)mesh_id + 1u);
-        RefitState::MeshSkin& k = f.skins[mesh_id];
-        const size_t pos_bytes = (size_t)nverts * 16, joint_bytes = (size_t)nverts * 8;
-        int rc;
-        if ((uint64_t)f.pos_offset[mesh_id] + nverts > pool_cap(r, kPoolVerts)) return fail(FRT_ERR_STATE, "set_mesh_skin: the mesh does not lie inside the vertex pool");
-        k.njoints = 0;      // (a call that fails below leaves the mesh without a skin)
-        if ((rc = k.buf.ensure(r, 2 * pos_bytes + joint_bytes))) return rc;
-        if ((rc = f.skin_up.reserve(pos_bytes + joint_bytes, 0, r->stream))) return rc;
-        memcpy(f.skin_up.h, weights4, pos_bytes);
-        memcpy(f.skin_up.h + pos_bytes, joints4, joint_bytes);
-        uint8_t* d = k.buf.as<uint8_t>();      // [bind positions | weights | joints]
-        if (nverts) {
-            HIP_TRY(hipMemcpyAsync(d, f.d_pos + f.pos_offset[mesh_id], pos_bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_TRY(hipMemcpyAsync(d + pos_bytes, f.skin_up.h, pos_bytes + joint_bytes, hipMemcpyHostToDevice, r->stream));
-        }
-        if ((rc = f.skin_up.mark(r->stream))) return rc;
-        k.njoints = njoints;
-        return FRT_OK;
+        if (!joints4) return drop_binding(r, r->rf.skins, mesh_id);
+        return bind_to_mesh(r, "set_mesh_skin", r->rf.skins, r->rf.skin_up, mesh_id, nverts, {{weights4, (size_t)nverts * 16}, {joints4, (size_t)nverts * 8}}, njoints);
     });
 }
-// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what this call adds runs in front of the device-input route.
-int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
-    if (const int rc = check_entry(r, "set_mesh_pose", kEditChecks | kRefit)) return rc;
-    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: unknown flag bits");
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
-    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
-    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].njoints : 0u, !dev);
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
-    if (dev) {      // the palette's finiteness is the skin launch's to check
-        DeviceGuard guard(r->device);
-        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices", "FRT_DEFORM_DEVICE")) return rc;
-    }
-    const PoseInput pose{joint_mats, njoints, dev};
-    return edit_frame(r, true, [&]() -> int {
-        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, &pose);
-    });
-}
-
-// ------------------------------------------------------------------------------------------------ morph targets ("Morph targets")
-// The targets of mesh `m` leave (behind a wait: a morph's kernel may still read them).
-static int drop_morph(frt_renderer* r, uint32_t m) {
-    RefitState& f = r->rf;
-    if (m >= f.morphs.size() || !f.morphs[m].buf.p) return FRT_OK;
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    scene_free(r, f.morphs[m].buf.p);
-    f.morphs[m] = RefitState::MeshMorph();
-    return FRT_OK;
-}
-// The deltas go through the pinned block of RefitState::morph_up into the mesh's own buffer, in the caller's layout (target-major); the base is copied
-// there from the replica's object-space positions on the stream, behind every deformation enqueued so far. The speculation is kept: nothing a frame
-// reads changes.
+// Morph targets: [base positions | deltas], the deltas in the caller's layout (target-major). The speculation is kept, as above.
 int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
-    if (const int rc = check_entry(r, "set_mesh_morph_targets", kEditChecks | kRefit)) return rc;
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_targets: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (const int rc = check_mesh_call(r, "set_mesh_morph_targets", mesh_id, 0u, 0u)) return rc;
     if (deltas3) {
         const std::string bad = check_mesh_morph_targets(deltas3, nverts, ntargets, r->rf.vert_count[mesh_id]);
         if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_targets: " + bad);
     }
     return edit_frame(r, false, [&]() -> int {
-        RefitState& f = r->rf;
-        if (!deltas3) return drop_morph(r, mesh_id);
-        if (f.morphs.size() <= mesh_id) f.morphs.resize((size_t)mesh_id + 1u);
-        RefitState::MeshMorph& k = f.morphs[mesh_id];
-        const size_t pos_bytes = (size_t)nverts * 16, delta_bytes = (size_t)ntargets * nverts * 12;
-        int rc;
-        if ((uint64_t)f.pos_offset[mesh_id] + nverts > pool_cap(r, kPoolVerts)) return fail(FRT_ERR_STATE, "set_mesh_morph_targets: the mesh does not lie inside the vertex pool");
-        k.ntargets = 0;      // (a call that fails below leaves the mesh without targets)
-        if ((rc = k.buf.ensure(r, pos_bytes + delta_bytes))) return rc;
-        if ((rc = f.morph_up.reserve(delta_bytes, 0, r->stream))) return rc;
-        memcpy(f.morph_up.h, deltas3, delta_bytes);
-        uint8_t* d = k.buf.as<uint8_t>();      // [base positions | deltas]
-        if (nverts) {
-            HIP_TRY(hipMemcpyAsync(d, f.d_pos + f.pos_offset[mesh_id], pos_bytes, hipMemcpyDeviceToDevice, r->stream));
-            HIP_TRY(hipMemcpyAsync(d + pos_bytes, f.morph_up.h, delta_bytes, hipMemcpyHostToDevice, r->stream));
-        }
-        if ((rc = f.morph_up.mark(r->stream))) return rc;
-        k.ntargets = ntargets;
-        return FRT_OK;
+        if (!deltas3) return drop_binding(r, r->rf.morphs, mesh_id);
+        return bind_to_mesh(r, "set_mesh_morph_targets", r->rf.morphs, r->rf.morph_up, mesh_id, nverts, {{deltas3, (size_t)ntargets * nverts * 12}}, ntargets);
     });
 }
+
+// ------------------------------------------------------------------------------------------------ posing: skin, morph, or morph then skin
 // What the two calls that take morph weights check about them, in front of the call frame; with FRT_DEFORM_DEVICE their finiteness is the morph launch's.
 static int check_morph_input(frt_renderer* r, const char* call, uint32_t mesh_id, const float* weights, uint32_t ntargets, bool dev) {
-    const std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < r->rf.morphs.size() ? r->rf.morphs[mesh_id].ntargets : 0u, !dev);
+    const std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < r->rf.morphs.size() ? r->rf.morphs[mesh_id].count : 0u, !dev);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, std::string(call) + ": " + bad);
-    if (dev) {
-        DeviceGuard guard(r->device);
-        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, weights, (size_t)ntargets * 4, 4, call, "morph weights", "FRT_DEFORM_DEVICE")) return rc;
-    }
-    return FRT_OK;
+    return dev ? check_device_input(r, weights, (size_t)ntargets * 4, 4, call, "morph weights") : FRT_OK;
 }
-// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what this call adds runs in front of the device-input route.
+// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what these calls add runs in front of the device-input route.
 int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
-    if (const int rc = check_entry(r, "set_mesh_morph_weights", kEditChecks | kRefit)) return rc;
-    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_weights: unknown flag bits");
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_morph_weights: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
+    if (const int rc = check_mesh_call(r, "set_mesh_morph_weights", mesh_id, flags, kDeformFlags)) return rc;
     const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
     if (const int rc = check_morph_input(r, "set_mesh_morph_weights", mesh_id, weights, ntargets, dev)) return rc;
-    const MorphInput morph{weights, ntargets, dev};
-    return edit_frame(r, true, [&]() -> int {
-        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, nullptr, &morph);
-    });
+    DeformCall c;
+    c.mesh_id = mesh_id; c.nverts = r->rf.vert_count[mesh_id]; c.source = PosSource::Morph; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    c.weights = weights; c.ntargets = ntargets; c.weights_on_device = dev;
+    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
 }
-// frt_renderer_set_mesh_pose's checks, then the morph's; two launches in front of the device-input route.
+// The pose's checks, the palette's device pointer, then (with morph weights or a target count) the morph's; the palette's finiteness is the skin launch's
+// to check when it is device memory.
 int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
-    if (!morph_weights && ntargets == 0) return frt_renderer_set_mesh_pose(r, mesh_id, joint_mats, njoints, flags);
-    if (const int rc = check_entry(r, "set_mesh_pose", kEditChecks | kRefit)) return rc;
-    if (flags & ~(FRT_DEFORM_RECOMPUTE_NORMALS | FRT_DEFORM_DEVICE)) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: unknown flag bits");
-    if (mesh_id >= r->rf.vert_count.size())
-        return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: mesh id " + std::to_string(mesh_id) + " out of range (" + std::to_string(r->rf.vert_count.size()) + " meshes)");
-    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
-    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].njoints : 0u, !dev);
+    if (const int rc = check_mesh_call(r, "set_mesh_pose", mesh_id, flags, kDeformFlags)) return rc;
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, morph = morph_weights || ntargets;
+    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].count : 0u, !dev);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
-    if (dev) {
-        DeviceGuard guard(r->device);
-        if (!guard.ok) return fail(FRT_ERR_HIP, "hipSetDevice failed");
-        if (const int rc = check_device_pointer(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices", "FRT_DEFORM_DEVICE")) return rc;
-    }
-    if (const int rc = check_morph_input(r, "set_mesh_pose", mesh_id, morph_weights, ntargets, dev)) return rc;
-    const PoseInput pose{joint_mats, njoints, dev};
-    const MorphInput morph{morph_weights, ntargets, dev};
-    return edit_frame(r, true, [&]() -> int {
-        return deform_mesh(r, mesh_id, nullptr, nullptr, r->rf.vert_count[mesh_id], flags & FRT_DEFORM_RECOMPUTE_NORMALS, &pose, &morph);
-    });
+    if (dev) if (const int rc = check_device_input(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices")) return rc;
+    if (morph) if (const int rc = check_morph_input(r, "set_mesh_pose", mesh_id, morph_weights, ntargets, dev)) return rc;
+    DeformCall c;
+    c.mesh_id = mesh_id; c.nverts = r->rf.vert_count[mesh_id]; c.source = morph ? PosSource::MorphThenSkin : PosSource::Skin; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    c.palette = joint_mats; c.njoints = njoints; c.palette_on_device = dev;
+    c.weights = morph_weights; c.ntargets = ntargets; c.weights_on_device = dev;
+    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
+}
+int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, nullptr, 0u, flags);
 }
 
 // ------------------------------------------------------------------------------------------------ materials, lights, textures
@@ -1367,16 +1372,12 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             scene_free(r, f.adj[g]);
         }
         remove_elements(f.adj, gone);
-        // and so do the skins
-        if (!f.skins.empty()) {
-            f.skins.resize(old_meshes);
-            for (uint32_t g : gone) if ((rc = drop_skin(r, g))) return rc;
-            remove_elements(f.skins, gone);
-        }
-        if (!f.morphs.empty()) {      // and the morph targets
-            f.morphs.resize(old_meshes);
-            for (uint32_t g : gone) if ((rc = drop_morph(r, g))) return rc;
-            remove_elements(f.morphs, gone);
+        // and so do the skins and the morph targets
+        for (std::vector<RefitState::MeshBinding>* list : {&f.skins, &f.morphs}) {
+            if (list->empty()) continue;
+            list->resize(old_meshes);
+            for (uint32_t g : gone) if ((rc = drop_binding(r, *list, g))) return rc;
+            remove_elements(*list, gone);
         }
         drop_transform_tables(r, false);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];

@@ -20,6 +20,13 @@ def _is_device_tensor(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "is_cuda") and x.is_cuda
 
 
+def _mesh_id(mesh_id):
+    """`mesh_id` as the unsigned 32-bit index the C calls take, or FrtError."""
+    if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
+        raise FrtError("mesh id must be an unsigned 32-bit index")
+    return int(mesh_id)
+
+
 def device_transform_args(torch, ids, mats, device):
     """The record count of a device-tensor set_instance_transforms call on HIP device `device`, or FrtError: `ids` contiguous int32 [n], `mats`
     contiguous float32 [n, 16] or [n, 4, 4] (column-major, as the host form), both on that device. Looks at the tensors' descriptions only."""
@@ -273,14 +280,8 @@ class Renderer(_HostQueries, _SceneGrowth):
             raise FrtError("set_instance_transforms: ids and matrices must both be host arrays or both be device tensors")
         import torch
         n = device_transform_args(torch, ids, transforms_colmajor, self.device)
-        dev = transforms_colmajor.device
-        s = self._torch_stream(torch, dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        check(lib().frt_renderer_set_instance_transforms_ex(self._h, n, ids.data_ptr() if n else None, transforms_colmajor.data_ptr() if n else None, TRANSFORM_DEVICE))
-        done = torch.cuda.Event()
-        done.record(s)
-        self._release_held()
-        self._held.append((done, ids, transforms_colmajor))
+        self._device_call(torch, lambda: lib().frt_renderer_set_instance_transforms_ex(self._h, n, ids.data_ptr() if n else None, transforms_colmajor.data_ptr() if n else None,
+                                                                                        TRANSFORM_DEVICE), transforms_colmajor, ids)
 
     def transform_rejects(self):
         """Device-tensor set_instance_transforms calls rejected so far (a bad id, a non-finite entry, a singular 3x3; nothing of them was applied).
@@ -310,26 +311,14 @@ class Renderer(_HostQueries, _SceneGrowth):
             raise FrtError("set_mesh_vertices: positions and attributes must both be host arrays or both be device tensors")
         import torch
         flags = deform_flags(normals) | DEFORM_DEVICE
-        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
-            raise FrtError("mesh id must be an unsigned 32-bit index")
+        mid = _mesh_id(mesh_id)
         for name, t, cols in (("positions", positions, 4), ("attributes", attributes, 8)):
-            if t is None:
-                continue
-            if t.device.index != self.device:
-                raise FrtError(f"set_mesh_vertices: {name} are on {t.device}, the renderer on device {self.device}")
-            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
-                raise FrtError(f"set_mesh_vertices: device {name} must be a contiguous float32 tensor shaped [n, {cols}]")
+            if t is not None:
+                self._check_device_tensor(torch, "set_mesh_vertices", name, t, lambda t: t.dim() == 2 and t.shape[1] == cols, f"[n, {cols}]")
         if attributes is not None and attributes.shape[0] != positions.shape[0]:
             raise FrtError(f"{positions.shape[0]} positions but {attributes.shape[0]} attribute records")
-        dev = positions.device
-        s = self._torch_stream(torch, dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        check(lib().frt_renderer_set_mesh_vertices_ex(self._h, int(mesh_id), positions.data_ptr(), attributes.data_ptr() if attributes is not None else None,
-                                                      positions.shape[0], flags))
-        done = torch.cuda.Event()
-        done.record(s)
-        self._release_held()
-        self._held.append((done, positions, attributes))
+        self._device_call(torch, lambda: lib().frt_renderer_set_mesh_vertices_ex(self._h, mid, positions.data_ptr(), attributes.data_ptr() if attributes is not None else None,
+                                                                                  positions.shape[0], flags), positions, attributes)
 
     def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
         """Bind a skin to one mesh of this renderer's scene replica (include/frt.h: frt_renderer_set_mesh_skin): `joints` [n, 4] integers, `weights`
@@ -354,31 +343,33 @@ class Renderer(_HostQueries, _SceneGrowth):
             raise TypeError("set_mesh_pose: joint matrices and morph weights must both be host arrays or both be device tensors")
         import torch
         flags = deform_flags(normals) | DEFORM_DEVICE
-        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
-            raise FrtError("mesh id must be an unsigned 32-bit index")
-        t = joint_matrices
+        mid, t, w = _mesh_id(mesh_id), joint_matrices, morph_weights
+        self._check_device_tensor(torch, "set_mesh_pose", "joint matrices", t, lambda t: (t.dim() == 2 and t.shape[1] == 16) or (t.dim() == 3 and tuple(t.shape[1:]) == (4, 4)),
+                                  "[J, 16] or [J, 4, 4]")
+        if w is None:
+            return self._device_call(torch, lambda: lib().frt_renderer_set_mesh_pose(self._h, mid, t.data_ptr(), t.shape[0], flags), t)
+        self._check_device_tensor(torch, "set_mesh_pose", "morph weights", w, lambda w: w.dim() == 1, "[T]")
+        self._device_call(torch, lambda: lib().frt_renderer_set_mesh_pose_ex(self._h, mid, t.data_ptr(), t.shape[0], w.data_ptr(), w.shape[0], flags), t, w)
+
+    def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
+        """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
+        (`shape`: how the message spells that shape)."""
         if t.device.index != self.device:
-            raise FrtError(f"set_mesh_pose: joint matrices are on {t.device}, the renderer on device {self.device}")
-        if t.dtype != torch.float32 or not t.is_contiguous() or not ((t.dim() == 2 and t.shape[1] == 16) or (t.dim() == 3 and tuple(t.shape[1:]) == (4, 4))):
-            raise FrtError("set_mesh_pose: device joint matrices must be a contiguous float32 tensor shaped [J, 16] or [J, 4, 4]")
-        if morph_weights is not None:
-            self._check_device_weights(torch, "set_mesh_pose", morph_weights)
-        s = self._torch_stream(torch, t.device)
-        s.wait_stream(torch.cuda.current_stream(t.device))
-        if morph_weights is None:
-            check(lib().frt_renderer_set_mesh_pose(self._h, int(mesh_id), t.data_ptr(), t.shape[0], flags))
-        else:
-            check(lib().frt_renderer_set_mesh_pose_ex(self._h, int(mesh_id), t.data_ptr(), t.shape[0], morph_weights.data_ptr(), morph_weights.shape[0], flags))
+            raise FrtError(f"{call}: {name} are on {t.device}, the renderer on device {self.device}")
+        if t.dtype != torch.float32 or not t.is_contiguous() or not shape_ok(t):
+            raise FrtError(f"{call}: device {name} must be a contiguous float32 tensor shaped {shape}")
+
+    def _device_call(self, torch, call, *tensors):
+        """The protocol of every call that takes device tensors: the renderer's stream waits for the caller's current stream, `call` (the C call; its
+        code is checked) is enqueued there, and the renderer keeps a reference to `tensors` behind an event until that stream has passed the call."""
+        dev = tensors[0].device
+        s = self._torch_stream(torch, dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        check(call())
         done = torch.cuda.Event()
         done.record(s)
         self._release_held()
-        self._held.append((done, t, morph_weights))
-
-    def _check_device_weights(self, torch, call, w):
-        if w.device.index != self.device:
-            raise FrtError(f"{call}: morph weights are on {w.device}, the renderer on device {self.device}")
-        if w.dtype != torch.float32 or w.dim() != 1 or not w.is_contiguous():
-            raise FrtError(f"{call}: device morph weights must be a contiguous float32 tensor shaped [T]")
+        self._held.append((done,) + tensors)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Bind morph targets to one mesh of this renderer's scene replica (include/frt.h: frt_renderer_set_mesh_morph_targets): `deltas` [T, n, 3]
@@ -398,16 +389,9 @@ class Renderer(_HostQueries, _SceneGrowth):
             return set_mesh_morph_weights_call("frt_renderer_set_mesh_morph_weights", self._h, mesh_id, weights, normals)
         import torch
         flags = deform_flags(normals) | DEFORM_DEVICE
-        if not 0 <= int(mesh_id) <= 0xFFFFFFFF:
-            raise FrtError("mesh id must be an unsigned 32-bit index")
-        self._check_device_weights(torch, "set_mesh_morph_weights", weights)
-        s = self._torch_stream(torch, weights.device)
-        s.wait_stream(torch.cuda.current_stream(weights.device))
-        check(lib().frt_renderer_set_mesh_morph_weights(self._h, int(mesh_id), weights.data_ptr(), weights.shape[0], flags))
-        done = torch.cuda.Event()
-        done.record(s)
-        self._release_held()
-        self._held.append((done, weights))
+        mid = _mesh_id(mesh_id)
+        self._check_device_tensor(torch, "set_mesh_morph_weights", "morph weights", weights, lambda w: w.dim() == 1, "[T]")
+        self._device_call(torch, lambda: lib().frt_renderer_set_mesh_morph_weights(self._h, mid, weights.data_ptr(), weights.shape[0], flags), weights)
 
     def _release_held(self, all_done=False):
         """Drop the references to device tensors whose call the stream has passed (all of them after a sync)."""
