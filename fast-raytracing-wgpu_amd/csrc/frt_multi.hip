@@ -488,6 +488,11 @@ int frt_multi_renderer_set_mesh_pose_ex(frt_multi_renderer* m, uint32_t mesh_id,
     if (const int rc = refuse_device_flag("set_mesh_pose", flags)) return rc;
     return edit_every_replica(m, "multi set_mesh_pose", [&](frt_renderer* r) { return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, morph_weights, ntargets, flags); });
 }
+// Every strip poses the batch on its own replica (frt_renderer_set_mesh_poses).
+int frt_multi_renderer_set_mesh_poses(frt_multi_renderer* m, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = refuse_device_flag("set_mesh_poses", flags)) return rc;
+    return edit_every_replica(m, "multi set_mesh_poses", [&](frt_renderer* r) { return frt_renderer_set_mesh_poses(r, n, mesh_ids, joint_mats, njoints, morph_weights, ntargets, flags); });
+}
 // The material, light and texture edits on every strip's replica, as above.
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     return edit_every_replica(m, "multi set_materials", [&](frt_renderer* r) { return frt_renderer_set_materials(r, n, ids, materials); });

@@ -7,6 +7,7 @@
 #include "frt_deform.hpp"
 #include "frt_skin.hpp"
 #include "frt_morph.hpp"
+#include "frt_pose_batch.hpp"
 #include "frt_refit_device.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"

@@ -531,29 +531,75 @@ int SceneBuilder::set_mesh_morph_weights(uint32_t mesh_id, const float* weights,
     if (!bad.empty()) { error = "set_mesh_morph_weights: " + bad; return FRT_ERR_INVALID_ARG; }
     return set_mesh_vertices(mesh_id, morphed.data(), nullptr, (uint32_t)(morphed.size() / 4), flags);
 }
-// set_mesh_pose's checks in set_mesh_pose's order; with morph weights the morph's follow, and the morphed positions stand where the bind pose stood.
-int SceneBuilder::set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
-    if (const int rc = check_mesh_call("set_mesh_pose", "frt_renderer_set_mesh_pose", mesh_id, flags)) return rc;
-    std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u);
-    if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
-    const MeshSkin& k = mesh_skins[mesh_id];
-    std::vector<float> morphed;
-    if (morph_weights || ntargets) {
-        bad = check_mesh_morph_weights(morph_weights, ntargets, mesh_id < mesh_morphs.size() ? mesh_morphs[mesh_id].ntargets : 0u);
-        if (bad.empty()) bad = morph_mesh(mesh_morphs[mesh_id], morph_weights, morphed);
-        if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
-    }
-    const std::vector<float>& bind = morphed.empty() ? k.bind : morphed;
+// The skinned positions of `bind` under a checked palette; "" or what is wrong with them.
+static std::string skin_mesh(const SceneBuilder::MeshSkin& k, const std::vector<float>& bind, const float* joint_mats, std::vector<float>& skinned) {
     const uint32_t nverts = (uint32_t)(bind.size() / 4);
-    std::vector<float> skinned(bind.size());
+    skinned.resize(bind.size());
     for (uint32_t v = 0; v < nverts; ++v) {
         float m[4][16];
         for (int s = 0; s < 4; ++s) memcpy(m[s], joint_mats + 16 * (size_t)k.joints[4 * (size_t)v + s], sizeof(m[s]));
         skinned_position(&bind[4 * (size_t)v], m, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);
     }
     for (size_t c = 0; c < skinned.size(); ++c)
-        if (!std::isfinite(skinned[c])) { error = "set_mesh_pose: the skinned position of vertex " + std::to_string(c / 4) + " is not finite"; return FRT_ERR_INVALID_ARG; }
-    return set_mesh_vertices(mesh_id, skinned.data(), nullptr, nverts, flags);
+        if (!std::isfinite(skinned[c])) return "the skinned position of vertex " + std::to_string(c / 4) + " is not finite";
+    return "";
+}
+// set_mesh_pose's checks in set_mesh_pose's order; with morph weights the morph's follow, and the morphed positions stand where the bind pose stood.
+// `posed`: the positions the call would apply. "" or what refuses the call.
+std::string SceneBuilder::pose_mesh(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, bool check_inputs, std::vector<float>& posed) const {
+    std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < mesh_skins.size() ? mesh_skins[mesh_id].njoints : 0u, check_inputs);
+    if (!bad.empty()) return bad;
+    std::vector<float> morphed;
+    if (morph_weights || ntargets) {
+        bad = check_mesh_morph_weights(morph_weights, ntargets, mesh_id < mesh_morphs.size() ? mesh_morphs[mesh_id].ntargets : 0u, check_inputs);
+        if (bad.empty()) bad = morph_mesh(mesh_morphs[mesh_id], morph_weights, morphed);
+        if (!bad.empty()) return bad;
+    }
+    const MeshSkin& k = mesh_skins[mesh_id];
+    return skin_mesh(k, morphed.empty() ? k.bind : morphed, joint_mats, posed);
+}
+int SceneBuilder::set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = check_mesh_call("set_mesh_pose", "frt_renderer_set_mesh_pose", mesh_id, flags)) return rc;
+    std::vector<float> skinned;
+    const std::string bad = pose_mesh(mesh_id, joint_mats, njoints, morph_weights, ntargets, true, skinned);
+    if (!bad.empty()) { error = "set_mesh_pose: " + bad; return FRT_ERR_INVALID_ARG; }
+    return set_mesh_vertices(mesh_id, skinned.data(), nullptr, (uint32_t)(skinned.size() / 4), flags);
+}
+
+// ---------------------------------------------------------------------------------------------- posing several meshes ("Posing several meshes")
+std::string check_pose_batch(uint32_t n, const uint32_t* mesh_ids, size_t num_meshes, bool palette, bool weights) {
+    if (n == 0 || n > FRT_MAX_POSE_MESHES) return std::to_string(n) + " meshes (1 to " + std::to_string(FRT_MAX_POSE_MESHES) + ")";
+    if (!mesh_ids) return "null mesh ids";
+    if (!palette && !weights) return "neither joint matrices nor morph weights given";
+    std::vector<uint32_t> sorted(mesh_ids, mesh_ids + n);
+    for (uint32_t k = 0; k < n; ++k)
+        if (mesh_ids[k] >= num_meshes) return "mesh id " + std::to_string(mesh_ids[k]) + " out of range (" + std::to_string(num_meshes) + " meshes)";
+    std::sort(sorted.begin(), sorted.end());
+    for (uint32_t k = 1; k < n; ++k) if (sorted[k] == sorted[k - 1]) return "mesh id " + std::to_string(sorted[k]) + " is given twice";
+    return "";
+}
+// Everything is validated first, the posed vertices of every mesh included; then the meshes are applied in the order given, each through
+// set_mesh_vertices (whose refit makes the same boxes once or n times: min and max are exact).
+int SceneBuilder::set_mesh_poses(uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (!built) { error = "set_mesh_poses: scene is not built"; return FRT_ERR_STATE; }
+    if (flags & FRT_DEFORM_DEVICE) { error = "set_mesh_poses: FRT_DEFORM_DEVICE is for frt_renderer_set_mesh_poses only (a scene lives in host memory)"; return FRT_ERR_INVALID_ARG; }
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) { error = "set_mesh_poses: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
+    const bool skin = joint_mats || njoints, morph = morph_weights || ntargets;
+    std::string bad = check_pose_batch(n, mesh_ids, mesh_positions.size(), skin, morph);
+    std::vector<std::vector<float>> posed(bad.empty() ? n : 0u);
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {      // (the palette and the weights are the same for every mesh: their entries are read once)
+        const uint32_t m = mesh_ids[k];
+        if (skin) bad = pose_mesh(m, joint_mats, njoints, morph_weights, ntargets, k == 0, posed[k]);
+        else {
+            bad = check_mesh_morph_weights(morph_weights, ntargets, m < mesh_morphs.size() ? mesh_morphs[m].ntargets : 0u, k == 0);
+            if (bad.empty()) bad = morph_mesh(mesh_morphs[m], morph_weights, posed[k]);
+        }
+        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
+    }
+    if (!bad.empty()) { error = "set_mesh_poses: " + bad; return FRT_ERR_INVALID_ARG; }
+    for (uint32_t k = 0; k < n; ++k)
+        if (const int rc = set_mesh_vertices(mesh_ids[k], posed[k].data(), nullptr, (uint32_t)(posed[k].size() / 4), flags)) return rc;
+    return FRT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- materials, lights, textures

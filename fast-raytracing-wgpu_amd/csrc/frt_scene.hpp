@@ -125,6 +125,11 @@ public:
     // Morph, then skin: set_mesh_pose with the morphed position (from the morph base) in the place of the skin's bind pose, which is not read.
     // morph_weights == nullptr with ntargets == 0: set_mesh_pose. Refuses what either part refuses.
     int set_mesh_pose_ex(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags = 0);
+    // Several meshes under one palette and/or one weight vector ("Posing several meshes"): palette only skins, weights only morph, both morph
+    // then skin, for every mesh of the call alike. All or nothing: every mesh is checked as its single call checks it and every posed vertex is computed
+    // before the first mesh changes; then the meshes are applied in the order given through set_mesh_vertices. Refused besides, with nothing changed:
+    // n == 0 or above FRT_MAX_POSE_MESHES, a mesh id twice, neither palette nor weights.
+    int set_mesh_poses(uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags = 0);
     // What a built scene LOOKS like: no triangle, slot or box moves. Each is the specification its device form matches bit for bit,
     // validates everything before it applies anything, and leaves the scene equal to one built from scratch with the edited values.
     // Material ids[k] becomes mats[k], under the checks build() makes on a material (check_material).
@@ -175,6 +180,8 @@ public:
     std::vector<MeshMorph> mesh_morphs;
 private:
     int check_mesh_call(const char* call, const char* renderer_call, uint32_t mesh_id, uint32_t flags);      // the preamble of the mesh-edit calls (frt_scene.cpp)
+    // What set_mesh_pose_ex would apply to the mesh, or what refuses it (`check_inputs`: the palette's and the weights' entries are read for finiteness).
+    std::string pose_mesh(uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, bool check_inputs, std::vector<float>& posed) const;
 public:
     // built
     bool built = false;
@@ -233,6 +240,9 @@ std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t 
 // to find out, as with a pose.
 std::string check_mesh_morph_targets(const float* deltas3, uint32_t nverts, uint32_t ntargets, uint32_t mesh_nverts);
 std::string check_mesh_morph_weights(const float* weights, uint32_t ntargets, uint32_t bound_targets, bool host_memory = true);      // (device memory: the weights are not read)
+// What the scene and the renderer form of set_mesh_poses check about the batch itself: "" when mesh_ids [n] names 1 to FRT_MAX_POSE_MESHES different
+// meshes of a scene with num_meshes meshes and the call gives a palette, morph weights or both.
+std::string check_pose_batch(uint32_t n, const uint32_t* mesh_ids, size_t num_meshes, bool palette, bool weights);
 // The vertex -> corner adjacency of one mesh in CSR form: corners[offsets[v] .. offsets[v + 1]) are the corners 3 * triangle + k whose index is v,
 // ascending. offsets has nverts + 1 entries, corners nidx (an index out of range, which the checks let into no mesh, names no vertex).
 void build_vertex_corners(const uint32_t* idx, uint32_t nidx, uint32_t nverts, std::vector<uint32_t>& offsets, std::vector<uint32_t>& corners);

@@ -128,6 +128,11 @@ int frt_scene_set_mesh_pose_ex(frt_scene* s, uint32_t mesh_id, const float* join
     const int rc = s->b.set_mesh_pose_ex(mesh_id, joint_mats, njoints, morph_weights, ntargets, flags);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
+int frt_scene_set_mesh_poses(frt_scene* s, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: null");
+    const int rc = s->b.set_mesh_poses(n, mesh_ids, joint_mats, njoints, morph_weights, ntargets, flags);
+    return rc ? fail(rc, s->b.error) : FRT_OK;
+}
 int frt_scene_set_materials(frt_scene* s, uint32_t n, const uint32_t* ids, const frt_material* materials) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_materials: null");
     const int rc = s->b.set_materials(n, ids, materials);

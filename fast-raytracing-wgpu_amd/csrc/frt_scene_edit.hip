@@ -5,7 +5,7 @@
 //   new meshes, materials, texture layers and lights                        §15
 //   removing meshes, materials, layers and lights                           §16
 // The calls that only read the replica (the ray queries, frt_renderer_read_scene, the statistics and counts) are in frt_scene_read.hip; the kernels in
-// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_morph.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
+// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_morph.hip, frt_pose_batch.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
 //
 // All edits share one scheme:
 //   - the call frame (edit_frame): the device guard, the stream order behind the finished frames, the body, `failed` on a HIP error;
@@ -15,6 +15,8 @@
 // The seven calls on meshes are one family: one entry check (check_mesh_call), one check of a device pointer (check_device_input), one type and one
 // helper for what a bind call leaves with a mesh (RefitState::MeshBinding, bind_to_mesh), and one body for everything that deforms (deform_mesh: a
 // DeformCall says where the positions come from, a DeformLayout where each section of the call's blocks lies, and three steps stage, pose and apply).
+// frt_renderer_set_mesh_poses, the batch over several meshes, shares their checks and has a body of its own (pose_meshes) over the segmented kernels of
+// frt_pose_batch.hpp: the single-mesh calls are not routed through it.
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -753,6 +755,131 @@ int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float
 }
 int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
     return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, nullptr, 0u, flags);
+}
+
+// ------------------------------------------------------------------------------------------------ posing several meshes ("Posing several meshes")
+// Where everything a batch stages lies in the two blocks of RefitState::def, a sibling of DeformLayout. The pinned block goes over in one copy; the
+// device block has the call's decoded normals behind it (FRT_DEFORM_RECOMPUTE_NORMALS: the normal launch fills them, the triangle launch reads them).
+//   pinned: segments | instance records | the records' segments | palette | weights
+//   device: segments | instance records | the records' segments | palette | weights | decoded normals
+struct PoseBatchLayout {
+    Section seg, rec, rec_seg, pal, wt, d_nrm;
+    size_t h_total = 0, d_total = 0;
+    PoseBatchLayout(size_t nseg, size_t ninstances, size_t pal_bytes, size_t wt_bytes, size_t nrm_bytes) {
+        auto put = [this](size_t bytes) { const Section s{h_total, bytes}; h_total += (bytes + 15u) & ~(size_t)15u; return s; };      // (every section 16-byte aligned)
+        seg = put(nseg * sizeof(PoseSegment));
+        rec = put(ninstances * sizeof(DeformInstance));
+        rec_seg = put(ninstances * sizeof(uint32_t));
+        pal = put(pal_bytes);
+        wt = put(wt_bytes);
+        d_nrm = Section{h_total, nrm_bytes};
+        d_total = h_total + nrm_bytes;
+    }
+};
+struct PoseBatchCall {
+    uint32_t n = 0; const uint32_t* mesh_ids = nullptr;
+    const float* palette = nullptr; uint32_t njoints = 0;      // null: no skin launch
+    const float* weights = nullptr; uint32_t ntargets = 0;     // null: no morph launch
+    bool on_device = false, recompute = false;
+};
+// What follows the checks of a batch, inside its call frame: the segment table, the instance records of every mesh of the batch, one staged copy, the
+// launches of frt_pose_batch.hpp and, once, the scene extent and the refit.
+static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
+    RefitState& f = r->rf;
+    int rc;
+    if ((rc = sync_matrix_mirror(r))) return rc;      // (the instances' matrices are read below)
+    const uint32_t cap_verts = pool_cap(r, kPoolVerts), cap_indices = pool_cap(r, kPoolIndices);
+    std::vector<PoseSegment> seg(c.n);
+    std::vector<int> seg_of_mesh(f.vert_count.size(), -1);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < c.n; ++k) {
+        const uint32_t m = c.mesh_ids[k];
+        if ((uint64_t)f.pos_offset[m] + f.vert_count[m] > cap_verts || (uint64_t)f.attr_offset[m] + f.vert_count[m] > cap_verts)
+            return fail(FRT_ERR_STATE, "set_mesh_poses: mesh " + std::to_string(m) + " does not lie inside the vertex pool");
+        if ((uint64_t)f.index_offset[m] + 3ull * f.mesh_tris[m] > cap_indices)
+            return fail(FRT_ERR_STATE, "set_mesh_poses: mesh " + std::to_string(m) + " does not lie inside the index pool");
+        if (c.recompute && (rc = ensure_adjacency(r, m))) return rc;
+        PoseSegment& s = seg[k];
+        s.vert_begin = (uint32_t)total; s.nverts = f.vert_count[m]; s.pos_offset = f.pos_offset[m]; s.attr_offset = f.attr_offset[m];
+        s.index_offset = f.index_offset[m]; s.ntris = f.mesh_tris[m];
+        s.skin = c.palette ? static_cast<const uint8_t*>(f.skins[m].buf.p) : nullptr;
+        s.morph = c.weights ? static_cast<const uint8_t*>(f.morphs[m].buf.p) : nullptr;
+        s.adj = c.recompute ? f.adj[m] : nullptr;
+        seg_of_mesh[m] = (int)k;
+        total += s.nverts;
+        if (total > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 vertices in one call");
+    }
+    std::vector<DeformInstance> rec;
+    std::vector<uint32_t> rec_seg;
+    uint64_t work = 0;
+    for (size_t i = 0; i < f.inst.size(); ++i) {      // in instance order
+        const InstanceRec& in = f.inst[i];
+        if (in.mesh_id >= seg_of_mesh.size() || seg_of_mesh[in.mesh_id] < 0) continue;
+        DeformInstance d;
+        d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = (uint32_t)work; work += in.tri_count;
+        for (int col = 0; col < 4; ++col) for (int a = 0; a < 3; ++a) d.m[3 * col + a] = in.m[4 * col + a];
+        rec.push_back(d);
+        rec_seg.push_back((uint32_t)seg_of_mesh[in.mesh_id]);
+    }
+    if (work > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 triangles in one call");
+    if ((rc = f.skinned.ensure(r, (size_t)total * 16))) return rc;
+    if (c.palette && c.weights && (rc = f.morphed.ensure(r, (size_t)total * 16))) return rc;
+    if ((rc = ensure_reject_words(r, f.d_reject))) return rc;
+    const PoseBatchLayout l(c.n, rec.size(), c.palette && !c.on_device ? (size_t)c.njoints * 64 : 0, c.weights && !c.on_device ? (size_t)c.ntargets * 4 : 0,
+                            c.recompute ? (size_t)total * 16 : 0);
+    if ((rc = f.def.reserve(l.h_total, l.d_total, r->stream))) return rc;
+    uint8_t* h = f.def.h; uint8_t* d = f.def.d;
+    memset(h, 0, l.h_total);      // (the padding between the sections is copied with them)
+    memcpy(h + l.seg.off, seg.data(), l.seg.bytes);
+    if (l.rec.bytes) memcpy(h + l.rec.off, rec.data(), l.rec.bytes);
+    if (l.rec_seg.bytes) memcpy(h + l.rec_seg.off, rec_seg.data(), l.rec_seg.bytes);
+    if (l.pal.bytes) memcpy(h + l.pal.off, c.palette, l.pal.bytes);
+    if (l.wt.bytes) memcpy(h + l.wt.off, c.weights, l.wt.bytes);
+    HIP_TRY(hipMemcpyAsync(d, h, l.h_total, hipMemcpyHostToDevice, r->stream));
+    if ((rc = f.def.mark(r->stream))) return rc;
+    PoseBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.seg = reinterpret_cast<const PoseSegment*>(d + l.seg.off); a.nseg = c.n; a.total = (uint32_t)total;
+    if (c.palette) { a.palette = reinterpret_cast<const float4*>(c.on_device ? reinterpret_cast<const uint8_t*>(c.palette) : d + l.pal.off); a.njoints = c.njoints; a.check_palette = c.on_device ? 1u : 0u; }
+    if (c.weights) { a.weights = c.on_device ? c.weights : reinterpret_cast<const float*>(d + l.wt.off); a.ntargets = c.ntargets; a.check_weights = c.on_device ? 1u : 0u; }
+    a.morphed = c.palette && c.weights ? f.morphed.as<float4>() : nullptr;
+    a.skinned = f.skinned.as<float4>();
+    a.scratch_len = (uint32_t)std::min<size_t>(std::min(f.skinned.bytes, a.morphed ? f.morphed.bytes : f.skinned.bytes) / 16, 0xFFFFFFFFu);
+    a.out_pos = const_cast<float4*>(f.d_pos);
+    a.block = c.recompute ? reinterpret_cast<float4*>(d + l.d_nrm.off) : nullptr;
+    a.pool_normals = const_cast<float4*>(r->pools.d_normals);
+    a.cap_verts = cap_verts; a.cap_indices = cap_indices;
+    a.reject = f.d_reject;
+    a.rec = reinterpret_cast<const DeformInstance*>(d + l.rec.off); a.rec_seg = reinterpret_cast<const uint32_t*>(d + l.rec_seg.off);
+    a.nrec = (uint32_t)rec.size(); a.work = (uint32_t)work;
+    a.slot_of = f.d_slot_of;
+    HIP_TRY(launch_pose_batch(r->sv, a, r->stream));
+    if (work == 0) return FRT_OK;      // no instance of any mesh of the batch: no triangle changes
+    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
+    return refit_levels(r);
+}
+// The entry and the flags, the batch itself (check_pose_batch), every mesh as its single call checks it, then the device pointers. The entries of a host
+// palette and of host weights are the same for every mesh and are read once.
+int frt_renderer_set_mesh_poses(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = check_entry(r, "set_mesh_poses", kEditChecks | kRefit)) return rc;
+    if (flags & ~kDeformFlags) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: unknown flag bits");
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, skin = joint_mats || njoints, morph = morph_weights || ntargets;
+    const RefitState& f = r->rf;
+    std::string bad = check_pose_batch(n, mesh_ids, f.vert_count.size(), skin, morph);
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
+        const uint32_t m = mesh_ids[k];
+        if (skin) bad = check_mesh_pose(joint_mats, njoints, m < f.skins.size() ? f.skins[m].count : 0u, !dev && k == 0);
+        if (morph && bad.empty()) bad = check_mesh_morph_weights(morph_weights, ntargets, m < f.morphs.size() ? f.morphs[m].count : 0u, !dev && k == 0);
+        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
+    }
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: " + bad);
+    if (dev && skin) if (const int rc = check_device_input(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_poses", "joint matrices")) return rc;
+    if (dev && morph) if (const int rc = check_device_input(r, morph_weights, (size_t)ntargets * 4, 4, "set_mesh_poses", "morph weights")) return rc;
+    PoseBatchCall c;
+    c.n = n; c.mesh_ids = mesh_ids; c.on_device = dev; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    if (skin) { c.palette = joint_mats; c.njoints = njoints; }
+    if (morph) { c.weights = morph_weights; c.ntargets = ntargets; }
+    return edit_frame(r, true, [&]() -> int { return pose_meshes(r, c); });
 }
 
 // ------------------------------------------------------------------------------------------------ materials, lights, textures

@@ -127,6 +127,7 @@ SYMBOLS = {
     "frt_scene_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_scene_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_scene_set_mesh_pose_ex": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _U32]),
+    "frt_scene_set_mesh_poses": (C.c_int, [_P, _U32, _P, _P, _U32, _P, _U32, _U32]),
     "frt_scene_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_scene_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),
@@ -176,6 +177,7 @@ SYMBOLS = {
     "frt_renderer_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_renderer_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_renderer_set_mesh_pose_ex": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _U32]),
+    "frt_renderer_set_mesh_poses": (C.c_int, [_P, _U32, _P, _P, _U32, _P, _U32, _U32]),
     "frt_renderer_deform_rejects": (C.c_int, [_P, C.POINTER(_U32)]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
@@ -227,6 +229,7 @@ SYMBOLS = {
     "frt_multi_renderer_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_multi_renderer_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_multi_renderer_set_mesh_pose_ex": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _U32]),
+    "frt_multi_renderer_set_mesh_poses": (C.c_int, [_P, _U32, _P, _P, _U32, _P, _U32, _U32]),
     "frt_multi_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_multi_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_multi_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

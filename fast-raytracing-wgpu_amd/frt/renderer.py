@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from ._lib import (lib, check, FrtError, RenderOpts, Stats, CameraUniform, BUF_BPP, BUF_ACCUM, BUF_DISPLAY, PHASE_ALL, FLAG_USE_STREAM, QUERY_DEVICE, DEFORM_DEVICE, TRANSFORM_DEVICE)
-from .scene import (transform_args, set_mesh_vertices_call, set_mesh_skin_call, set_mesh_pose_call, set_mesh_morph_targets_call, set_mesh_morph_weights_call, _num_joints, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
+from .scene import (transform_args, set_mesh_vertices_call, set_mesh_skin_call, set_mesh_pose_call, set_mesh_poses_call, pose_batch_ids, set_mesh_morph_targets_call, set_mesh_morph_weights_call, _num_joints, deform_flags, material_args, id_pair_args, instance_add_args, instance_id_args, emission_args, texture_args, ray_args, hits_dict,
                     pixel_args, HIT_FIELDS, mesh_add_args, material_add_args, light_add_args, texture_add_args, light_register_args, gltf_layer_plan, id_list_args, layer_args)
 
 
@@ -351,6 +351,30 @@ class Renderer(_HostQueries, _SceneGrowth):
         self._check_device_tensor(torch, "set_mesh_pose", "morph weights", w, lambda w: w.dim() == 1, "[T]")
         self._device_call(torch, lambda: lib().frt_renderer_set_mesh_pose_ex(self._h, mid, t.data_ptr(), t.shape[0], w.data_ptr(), w.shape[0], flags), t, w)
 
+    def set_mesh_poses(self, mesh_ids, joint_matrices=None, morph_weights=None, normals="recompute"):
+        """Pose several meshes of this renderer's scene replica in one call (include/frt.h: frt_renderer_set_mesh_poses): `mesh_ids` (host integers)
+        under one palette [J, 16] or [J, 4, 4] and/or one weight vector [T] — a palette only skins, weights only morph, both morph then skin, for
+        every mesh alike. The result is that of the single calls in the order given, but the batch is atomic (a pose of any mesh that overflows
+        rejects all of it: deform_rejects() counts one), its launches do not multiply with the number of meshes, and the scene extent and the refit
+        run once. numpy in, or contiguous float32 torch tensors on the renderer's device under the protocol of set_mesh_pose; the palette and the
+        weights are then either both tensors or both arrays."""
+        dev_in = [_is_device_tensor(x) for x in (joint_matrices, morph_weights) if x is not None]
+        if not any(dev_in):
+            return set_mesh_poses_call("frt_renderer_set_mesh_poses", self._h, mesh_ids, joint_matrices, morph_weights, normals)
+        if not all(dev_in):
+            raise TypeError("set_mesh_poses: joint matrices and morph weights must both be host arrays or both be device tensors")
+        import torch
+        flags = deform_flags(normals) | DEFORM_DEVICE
+        ids, t, w = pose_batch_ids(mesh_ids), joint_matrices, morph_weights
+        if t is not None:
+            self._check_device_tensor(torch, "set_mesh_poses", "joint matrices", t, lambda t: (t.dim() == 2 and t.shape[1] == 16) or (t.dim() == 3 and tuple(t.shape[1:]) == (4, 4)),
+                                      "[J, 16] or [J, 4, 4]")
+        if w is not None:
+            self._check_device_tensor(torch, "set_mesh_poses", "morph weights", w, lambda w: w.dim() == 1, "[T]")
+        self._device_call(torch, lambda: lib().frt_renderer_set_mesh_poses(self._h, ids.size, ids.ctypes.data, t.data_ptr() if t is not None else None, t.shape[0] if t is not None else 0,
+                                                                            w.data_ptr() if w is not None else None, w.shape[0] if w is not None else 0, flags),
+                          *[x for x in (t, w) if x is not None])
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -673,6 +697,12 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         if _is_device_tensor(joint_matrices) or _is_device_tensor(morph_weights):
             raise FrtError("set_mesh_pose: a MultiRenderer takes host arrays only (its replicas live on different devices)")
         set_mesh_pose_call("frt_multi_renderer_set_mesh_pose", self._h, mesh_id, joint_matrices, normals, morph_weights)
+
+    def set_mesh_poses(self, mesh_ids, joint_matrices=None, morph_weights=None, normals="recompute"):
+        """Renderer.set_mesh_poses on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""
+        if _is_device_tensor(joint_matrices) or _is_device_tensor(morph_weights):
+            raise FrtError("set_mesh_poses: a MultiRenderer takes host arrays only (its replicas live on different devices)")
+        set_mesh_poses_call("frt_multi_renderer_set_mesh_poses", self._h, mesh_ids, joint_matrices, morph_weights, normals)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

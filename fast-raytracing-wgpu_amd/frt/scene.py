@@ -149,6 +149,25 @@ def set_mesh_morph_weights_call(name, handle, mesh_id, weights, normals):
     check(getattr(lib(), name)(handle, mid, w.ctypes.data, t, flags))
 
 
+def pose_batch_ids(mesh_ids):
+    """[n] uint32 mesh ids for the *_set_mesh_poses calls: an int or a flat sequence of unsigned 32-bit indices."""
+    ids = np.atleast_1d(np.asarray(mesh_ids, np.int64))
+    if ids.ndim != 1 or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise FrtError("set_mesh_poses: mesh ids must be a flat list of unsigned 32-bit indices")
+    return np.ascontiguousarray(ids.astype(np.uint32))
+
+
+def set_mesh_poses_call(name, handle, mesh_ids, joint_matrices, morph_weights, normals):
+    """One host-array batched pose through the entry point `name`: a palette, morph weights or both (None: not given)."""
+    flags = deform_flags(normals)
+    ids = pose_batch_ids(mesh_ids)
+    if joint_matrices is None and morph_weights is None:
+        raise FrtError("set_mesh_poses: give joint_matrices, morph_weights or both")
+    m, j = (None, 0) if joint_matrices is None else mesh_pose_args(0, joint_matrices)[1:]
+    w, t = (None, 0) if morph_weights is None else mesh_morph_weight_args(0, morph_weights)[1:]
+    check(getattr(lib(), name)(handle, ids.size, ids.ctypes.data, m.ctypes.data if m is not None else None, j, w.ctypes.data if w is not None else None, t, flags))
+
+
 def material_args(ids, materials):
     """(n, ids, [n, 16] uint32 material records) for the *_set_materials calls: `ids` an int or a sequence, `materials` one frt.Material (or a 64-byte
     row of get("materials")) per id."""
@@ -460,6 +479,12 @@ class SceneBuilder:
     # morph_weights: morph first, then skin the morphed positions (frt_scene_set_mesh_pose_ex); None is the plain pose.
     def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
         set_mesh_pose_call("frt_scene_set_mesh_pose", self._h, mesh_id, joint_matrices, normals, morph_weights)
+        return self
+
+    # Several meshes under one palette and/or one weight vector, all or nothing (include/frt.h: frt_scene_set_mesh_poses): a palette only skins, weights
+    # only morph, both morph then skin; the result is that of the single calls in the order of `mesh_ids`. Host copy only.
+    def set_mesh_poses(self, mesh_ids, joint_matrices=None, morph_weights=None, normals="recompute"):
+        set_mesh_poses_call("frt_scene_set_mesh_poses", self._h, mesh_ids, joint_matrices, morph_weights, normals)
         return self
 
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]

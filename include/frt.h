@@ -209,6 +209,17 @@ int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_m
 int frt_scene_set_mesh_morph_targets(frt_scene* s, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
 int frt_scene_set_mesh_morph_weights(frt_scene* s, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
 int frt_scene_set_mesh_pose_ex(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
+/* Pose several meshes in one call ("Posing several meshes"): mesh_ids [n] under ONE palette joint_mats [16 njoints] and/or ONE
+ * weight vector morph_weights [ntargets], as a character's primitives share one skeleton and one set of morph weights. What is given decides the source,
+ * for every mesh of the call alike: a palette only (morph_weights == NULL, ntargets == 0) skins as frt_scene_set_mesh_pose; weights only
+ * (joint_mats == NULL, njoints == 0) morph as frt_scene_set_mesh_morph_weights; both morph then skin as frt_scene_set_mesh_pose_ex. Every mesh must have
+ * the bindings this implies and is checked against njoints / ntargets exactly as its single call checks it.
+ * The call is atomic. Everything is validated first, the posed vertices of every mesh included; then the result equals, bit for bit, the n single-mesh
+ * calls in the order given. FRT_ERR_STATE: scene not built. FRT_ERR_INVALID_ARG, nothing changed: n == 0 or above FRT_MAX_POSE_MESHES, mesh_ids == NULL,
+ * a mesh id out of range or given twice, neither palette nor weights, whatever the single call refuses for any mesh (a missing binding, a count that is
+ * not the bound one, a non-finite entry, a posed coordinate that overflowed), an unknown flag bit, FRT_DEFORM_DEVICE. A mesh no instance uses is legal. */
+#define FRT_MAX_POSE_MESHES 1024u
+int frt_scene_set_mesh_poses(frt_scene* s, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* What a BUILT scene looks like: four edits that move no triangle, slot or box. Common rules: FRT_ERR_STATE: scene not built;
  * FRT_ERR_INVALID_ARG: an id or layer out of range, a null pointer with n > 0, a failed check; everything is validated before anything is applied, so
  * a refused call changes nothing. n == 0: FRT_OK. An id given twice ends with its last value. Afterwards the scene equals one built from scratch
@@ -499,6 +510,14 @@ int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* j
 int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
 int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
 int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
+/* Pose several meshes of this renderer's scene replica in one call ("Posing several meshes"): arguments, checks and results of
+ * frt_scene_set_mesh_poses, bit for bit, under the ordering and state rules of frt_renderer_set_mesh_pose. mesh_ids is always host memory.
+ * FRT_DEFORM_DEVICE covers joint_mats (16-byte aligned) and morph_weights (4-byte aligned), which are then both device memory of the renderer's device.
+ * The number of kernel launches does not depend on n: one morph and/or one skin launch over the vertices of all n meshes into the renderer's scratch,
+ * one validation, one copy-in, one normal and one triangle launch, then the scene-extent pass and the refit, once. The palette and the weights are
+ * uploaded once. The call is atomic on the device as well: a non-finite entry of a device palette or weight vector, or a posed coordinate of ANY mesh
+ * that overflowed, rejects the whole batch: no mesh of it changes, and the counter frt_renderer_deform_rejects reads goes up by one. */
+int frt_renderer_set_mesh_poses(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* Device-input deformations this renderer has rejected since it was created (non-finite input). Waits for the main stream. */
 int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
@@ -686,6 +705,8 @@ int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, co
 int frt_multi_renderer_set_mesh_morph_targets(frt_multi_renderer* m, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets);
 int frt_multi_renderer_set_mesh_morph_weights(frt_multi_renderer* m, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags);
 int frt_multi_renderer_set_mesh_pose_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
+/* frt_renderer_set_mesh_poses on every strip's replica, between frames. FRT_DEFORM_DEVICE is refused: host arrays only. */
+int frt_multi_renderer_set_mesh_poses(frt_multi_renderer* m, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* frt_renderer_set_materials, _set_instance_materials, _set_light_emission and _set_texture on every strip's replica, between frames */
 int frt_multi_renderer_set_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* ids, const frt_material* materials);
 int frt_multi_renderer_set_instance_materials(frt_multi_renderer* m, uint32_t n, const uint32_t* instance_ids, const uint32_t* material_ids);
