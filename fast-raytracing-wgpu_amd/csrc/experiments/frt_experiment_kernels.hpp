@@ -461,7 +461,7 @@ __global__ void __launch_bounds__(kBlock, 8) wf_trace_kernel(SceneView sc, Frame
     first_chunk[0] = 0u;
 #pragma unroll
     for (int j = 0; j < kWfSub; ++j) {
-        const uint32_t v = io.items_in ? io.n_items_in[j] : io.n_in[j], lim = io.items_in ? icap : rcap;
+        const uint32_t v = io.items_in ? io.n_items_in[(uint32_t)j * kRegionStride] : io.n_in[(uint32_t)j * kRegionStride], lim = io.items_in ? icap : rcap;
         cnt[j] = v < lim ? v : lim;
         first_chunk[j + 1] = first_chunk[j] + (cnt[j] + 63u) / 64u;
     }
@@ -544,7 +544,7 @@ __global__ void __launch_bounds__(kBlock, 4) wf_shade_kernel(SceneView sc, Frame
     __shared__ uint32_t s_tmp[8];
     const uint32_t region = blockIdx.x % (uint32_t)kWfSub, blk = blockIdx.x / (uint32_t)kWfSub, nblk = gridDim.x / (uint32_t)kWfSub;
     const uint32_t rcap = io.capacity / (uint32_t)kWfSub, icap = 2u * rcap, rbase = region * rcap;
-    const uint32_t n = io.n_in[region] < rcap ? io.n_in[region] : rcap;
+    const uint32_t n = io.n_in[region * kRegionStride] < rcap ? io.n_in[region * kRegionStride] : rcap;
     if (blk * (uint32_t)kBlock >= n) return;   // uniform per workgroup
     if (threadIdx.x < 2u) s_cnt[threadIdx.x] = 0u;
     __syncthreads();
@@ -585,7 +585,7 @@ __global__ void __launch_bounds__(kBlock, 4) wf_shade_kernel(SceneView sc, Frame
             }
             keep = want || !ended;
         }
-        const uint32_t lo = workgroup_reserve(io.n_out + region, keep, s_tmp);
+        const uint32_t lo = workgroup_reserve(io.n_out + region * kRegionStride, keep, s_tmp);
         const bool fits = keep && lo < rcap;
         const bool overflowed = keep && !fits;
         if (overflowed) {      // the next queue is full: finish the path in place (never dropped)
@@ -608,9 +608,9 @@ __global__ void __launch_bounds__(kBlock, 4) wf_shade_kernel(SceneView sc, Frame
             }
         }
         // ray items of depth + 1: the next closest-hit ray, the pending shadow ray (two reservations, one atomic each per workgroup)
-        const uint32_t ic = workgroup_reserve(io.n_items_out + region, fits && !ended, s_tmp);
+        const uint32_t ic = workgroup_reserve(io.n_items_out + region * kRegionStride, fits && !ended, s_tmp);
         if (fits && !ended && ic < icap) io.items_out[(size_t)region * icap + ic] = slot_out << 1;
-        const uint32_t is = workgroup_reserve(io.n_items_out + region, fits && want, s_tmp);
+        const uint32_t is = workgroup_reserve(io.n_items_out + region * kRegionStride, fits && want, s_tmp);
         if (fits && want && is < icap) io.items_out[(size_t)region * icap + is] = (slot_out << 1) | 1u;
         if (have && !fits) finish_path<STAGE>(c, pix, r, s);      // ended with nothing pending, or finished in place
         if (owned) { cnt_closest += c.n_closest; cnt_any += c.n_any; }
@@ -842,9 +842,9 @@ static bool exp_launch_continuations(int stage, const SceneView& sc, const Frame
             for (uint32_t d = L.cuts[0]; d <= fv.max_depth; ++d) {
                 const uint32_t k = d - L.cuts[0];
                 WfPass io;
-                io.qin = L.wf_words[k & 1u]; io.n_in = L.counts + 8u * k; io.qout = L.wf_words[(k + 1u) & 1u]; io.n_out = L.counts + 8u * (k + 1u);
-                io.items_in = k == 0u ? nullptr : L.wf_items[k & 1u]; io.n_items_in = L.counts + 512 + 8u * k;
-                io.items_out = L.wf_items[(k + 1u) & 1u]; io.n_items_out = L.counts + 512 + 8u * (k + 1u);
+                io.qin = L.wf_words[k & 1u]; io.n_in = L.counts + k; io.qout = L.wf_words[(k + 1u) & 1u]; io.n_out = L.counts + (k + 1u);      // (region g of pass k: word g * kRegionStride + k, as the pixel kernel parks; k < 32)
+                io.items_in = k == 0u ? nullptr : L.wf_items[k & 1u]; io.n_items_in = L.counts + 512 + k;
+                io.items_out = L.wf_items[(k + 1u) & 1u]; io.n_items_out = L.counts + 512 + (k + 1u);
                 io.hits = L.wf_hits; io.capacity = L.capacity; io.overflow = L.overflow;
                 if (sc.bvh_depth <= 17u) hipLaunchKernelGGL(wf_trace_kernel<16>, dim3(tgrid), dim3(kBlock), 0, stream, sc, fv, io, L.refill_min, (int)L.slice);
                 else hipLaunchKernelGGL(wf_trace_kernel<32>, dim3(tgrid), dim3(kBlock), 0, stream, sc, fv, io, L.refill_min, (int)L.slice);

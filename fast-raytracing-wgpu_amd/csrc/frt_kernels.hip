@@ -51,6 +51,21 @@ __device__ __forceinline__ void flush_ray_counters(const FrameView& fv, uint32_t
     }
 }
 
+// The traced kernels: a wave's ray counts, summed across its lanes, go to the ray counters of the wave's region (frt_mono.hpp: kRayRegionStride)
+// with one atomic pair of its own: no barrier and no workgroup sum at the end of a kernel whose waves finish at very different times, and the
+// pairs of a launch's 32,640 waves spread over the regions' lines. The host sums the regions (frt_renderer.hip: frt_renderer_stats).
+__device__ __forceinline__ void wave_flush_ray_counters(const FrameView& fv, uint32_t n_closest, uint32_t n_any, uint32_t region) {
+    for (int off = 32; off > 0; off >>= 1) {
+        n_closest += __shfl_down(n_closest, off, 64);
+        n_any += __shfl_down(n_any, off, 64);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        unsigned long long* const rc = fv.ray_counters + (size_t)region * kRayRegionStride;
+        if (n_closest) atomicAdd(&rc[0], (unsigned long long)n_closest);
+        if (n_any) atomicAdd(&rc[1], (unsigned long long)n_any);
+    }
+}
+
 // (stage_top_nodes, the LDS copy of the quad tree's top that the quad walks read, is in frt_kernels.hpp: the ray-query kernels stage it too)
 
 // The whole 8-wide tree copied into the workgroup's dynamic LDS (kWalkWideLds): every node step of every walk then reads its node at the LDS's
@@ -129,8 +144,9 @@ __device__ __forceinline__ void finish_path(PathCtx& c, uint32_t pix, const Rese
     else spatial_tail(c, pix, r, s.accumulated, s.v1_pos);
 }
 
+#if FRT_EXPERIMENTS
 // Slots for the lanes of a workgroup that want one, with ONE atomic for the whole workgroup. Every thread of the workgroup must call it
-// (three barriers inside). s_tmp: 8 words of LDS.
+// (three barriers inside). s_tmp: 8 words of LDS. The collective walks and the ray-level wavefront (experiments/) still park this way.
 __device__ __forceinline__ uint32_t workgroup_reserve(uint32_t* counter, bool want, uint32_t* s_tmp) {
     const unsigned long long m = __ballot(want);
     const uint32_t wave = threadIdx.x >> 6;
@@ -147,6 +163,20 @@ __device__ __forceinline__ uint32_t workgroup_reserve(uint32_t* counter, bool wa
     __syncthreads();
     return base + rank;
 }
+#endif
+// The region a workgroup parks into and counts its rays in: a function of its index in the launch alone (nsub: a power of two), so the launches
+// of a stage that share a queue (a strip's interior and edge rows) need no agreement.
+__device__ __forceinline__ uint32_t region_of_workgroup(uint32_t nsub) { return (blockIdx.x + blockIdx.y * gridDim.x) & (nsub - 1u); }
+__device__ __forceinline__ uint32_t region_capacity(const ContQueue& q) { return q.capacity >> (__ffs((int)q.nsub) - 1); }
+// The counters this stage's NEXT launch will use (the other set of the pair: nsub lines of kMaxCuts + 1 counters) are cleared by the first threads
+// of the pixel launch instead of by a memset: eight threads per line, as many workgroups as that takes (all of them, in turns, for a tiny launch).
+static_assert(kMaxCuts + 1 <= 8, "clear_next_counters gives a region's line eight threads");
+__device__ __forceinline__ void clear_next_counters(uint32_t* zero_counts, uint32_t nsub, uint32_t threads) {
+    if (!zero_counts) return;
+    const uint32_t total = nsub * 8u;
+    for (uint32_t i = (blockIdx.x + blockIdx.y * gridDim.x) * threads + threadIdx.x; i < total; i += gridDim.x * gridDim.y * threads)
+        if ((i & 7u) <= (uint32_t)kMaxCuts) zero_counts[(i >> 3) * kRegionStride + (i & 7u)] = 0u;
+}
 
 // Runs bounces [d0, d1) of the lane's path and parks a survivor in `q`; when the queue is full the lane goes on to MAX_DEPTH itself.
 // On return the path is either parked (true: state stored) or finished (false: s holds the final radiance).
@@ -158,9 +188,8 @@ __device__ __forceinline__ bool run_segment_and_park(Ctx& c, LoopState& s, uint3
     for (int trip = 0; trip < 2; ++trip) {
         if (run) path_loop<VARIANT>(c, s, d0, d1);
         if (trip == 1) break;
-        uint32_t region = 0u, rcap = q.capacity;
-        if (q.nsub > 1u) { region = (blockIdx.x + blockIdx.y * gridDim.x) % q.nsub; rcap = q.capacity / q.nsub; }
-        const uint32_t slot = wave_reserve(q.count + region, s.alive);
+        const uint32_t region = region_of_workgroup(q.nsub), rcap = region_capacity(q);
+        const uint32_t slot = wave_reserve(q.count + region * kRegionStride, s.alive);
         parked = s.alive && slot < rcap;
         run = s.alive && !parked;
         if (parked) cont_store(q, region * rcap + slot, pix, c.rng, owned, s, r);
@@ -172,16 +201,14 @@ __device__ __forceinline__ bool run_segment_and_park(Ctx& c, LoopState& s, uint3
 }
 
 template <int STAGE, int WALK>
-__global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, FrameView fv, ContQueue q, uint32_t cut, uint32_t* zero_counts, bool wg_park, WalkArgs wa) {
+__global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, FrameView fv, ContQueue q, uint32_t cut, uint32_t* zero_counts, WalkArgs wa) {
     constexpr int THREADS = kBlock;
     uint32_t* s_cnt;
     uint32_t* const s_stack = walk_stack<WALK>(wa, s_cnt);
-    uint32_t* const s_tmp = s_cnt + 8;
     typename CtxOf<WALK>::type c(sc, fv, &s_stack[threadIdx.x], (uint32_t)THREADS);
-    walk_prologue<WALK>(sc, s_cnt, c, wa);
+    walk_prologue<WALK>(sc, s_cnt, c, wa);      // (the kernel's only barrier: the LDS copy of the tree's top)
     constexpr int VARIANT = STAGE == 1 ? 0 : 1;
-    // the queue counters this stage's NEXT launch will use (the other set of the pair) are cleared here instead of by a memset
-    if (zero_counts && blockIdx.x == 0u && blockIdx.y == 0u && threadIdx.x <= (uint32_t)kMaxCuts) zero_counts[threadIdx.x] = 0u;
+    clear_next_counters(zero_counts, q.nsub, (uint32_t)THREADS);
     uint32_t px, py;
     const bool active = tile_pixel(fv, px, py);      // tile rows top to bottom (a sweep from the expensive end of the image was measured: 1-2 % slower, profiles/r2_experiments)
     const uint32_t pix = py * fv.W + px;
@@ -197,18 +224,18 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, 
         } else if (spatial_neighbors(c, pix, r)) { seed = r.y; traced = true; }
         if (traced) path_head<VARIANT>(c, pix, seed, s);
     }
-    // bounces [1, cut), then park the survivors: ONE atomic for the workgroup's four waves (tens of thousands of atomics per launch on one
-    // address are served at ~13 ns each: 32,640 wave-level reservations = 0.42 ms of a 0.8 ms kernel's life); a lane that finds the queue
-    // full keeps its path and finishes it in place
+    // bounces [1, cut), then park the survivors: one atomic per WAVE on the counter of the workgroup's region — a wave that is done with its
+    // bounces parks and retires without waiting for the slowest of the workgroup's four tiles, and the launch's 32,640 reservations spread over
+    // q.nsub lines (on one address they are served at ~13 ns each: 0.42 ms of a 0.8 ms kernel's life); a lane that finds its region full keeps
+    // its path and finishes it in place
     uint32_t d0 = 1u, d1 = cut < fv.max_depth ? cut : fv.max_depth;
     bool run = s.alive, parked = false;
 #pragma nounroll
     for (int trip = 0; trip < 2; ++trip) {      // (a loop so that path_loop is instantiated once)
         if (run) path_loop<VARIANT>(c, s, d0, d1);
         if (trip == 1) break;
-        uint32_t region = 0u, rcap = q.capacity;
-        if (q.nsub > 1u) { region = (blockIdx.x + blockIdx.y * gridDim.x) % q.nsub; rcap = q.capacity / q.nsub; }
-        const uint32_t slot = wg_park ? workgroup_reserve(q.count + region, s.alive, s_tmp) : wave_reserve(q.count + region, s.alive);
+        const uint32_t region = region_of_workgroup(q.nsub), rcap = region_capacity(q);
+        const uint32_t slot = wave_reserve(q.count + region * kRegionStride, s.alive);
         parked = s.alive && slot < rcap;
         run = s.alive && !parked;
         if (parked) cont_store(q, region * rcap + slot, pix, c.rng, counted, s, STAGE == 2 ? &r : nullptr);
@@ -217,7 +244,7 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) pixel_kernel(SceneView sc, 
         d0 = d1; d1 = fv.max_depth;
     }
     if (traced && !parked) finish_path<STAGE>(c, pix, r, s);
-    flush_ray_counters(fv, counted ? c.n_closest : 0u, counted ? c.n_any : 0u, s_cnt);   // (contains a barrier: every wave is done)
+    wave_flush_ray_counters(fv, counted ? c.n_closest : 0u, counted ? c.n_any : 0u, region_of_workgroup(q.nsub));
 }
 
 // Resumes parked paths for bounces [d0, d1); survivors are parked again in `qout` (d1 < MAX_DEPTH) or finished here.
@@ -226,47 +253,45 @@ __global__ void __launch_bounds__(kBlock, FRT_WAVES) continue_kernel(SceneView s
     constexpr int THREADS = kBlock;
     uint32_t* s_cnt;
     uint32_t* const s_stack = walk_stack<WALK>(wa, s_cnt);
-    const uint32_t filled = *qin.count;
-    const uint32_t n = filled < qin.capacity ? filled : qin.capacity;
-    // The launch that parked these paths ran out of slots (its counter ran past the capacity; the surplus paths were finished in place): tell the
-    // host through the mapped flag whose address sits behind the overflow counter (frt_mono.hpp: ContQueue). One thread per launch, here where
-    // few registers are live — in the parking code the 64-bit address cost the traced kernels two VGPRs (112 -> 114, +1.5 % per frame).
-    if (blockIdx.x == 0u && threadIdx.x == 0u && filled > qin.capacity && qin.overflow) {
+    // this workgroup's share of the queue: THREADS slots of one region (frt_kernels.hpp: cont_region_slots), as far as the region is filled
+    const RegionSlots m = cont_region_slots(blockIdx.x, qin.nsub, (uint32_t)THREADS);
+    const uint32_t rcap = region_capacity(qin);
+    const uint32_t filled = qin.count[m.region * kRegionStride];
+    const uint32_t n = filled < rcap ? filled : rcap;
+    // The launch that parked these paths ran out of slots in this region (its counter ran past the region's capacity; the surplus paths were finished
+    // in place): tell the host through the mapped flag whose address sits behind the overflow counter (frt_mono.hpp: ContQueue). One thread per region,
+    // in the region's first workgroup, here where few registers are live — in the parking code the 64-bit address cost the traced kernels two VGPRs
+    // (112 -> 114, +1.5 % per frame).
+    if (m.offset == 0u && threadIdx.x == 0u && filled > rcap && qin.overflow) {
         uint32_t* const seen = *reinterpret_cast<uint32_t* const*>(qin.overflow + 2);
         if (seen) *reinterpret_cast<volatile uint32_t*>(seen) = 1u;
     }
-    if (blockIdx.x * (uint32_t)THREADS >= n) return;   // uniform per workgroup
+    if (m.offset >= n) return;   // uniform per workgroup
     constexpr int VARIANT = STAGE == 1 ? 0 : 1;
     typename CtxOf<WALK>::type c(sc, fv, &s_stack[threadIdx.x], (uint32_t)THREADS);
     walk_prologue<WALK>(sc, s_cnt, c, wa);
-    uint32_t cnt_closest = 0u, cnt_any = 0u;
-    // stride loop: one trip with the grid of launch_trace_continuations; uniform per workgroup for any grid
-    for (uint32_t base = blockIdx.x * (uint32_t)THREADS; base < n; base += gridDim.x * (uint32_t)THREADS) {
-        const uint32_t slot_in = base + threadIdx.x;
-        LoopState s;
-        s.alive = false;
-        ReservoirView r = zero_reservoir();
-        uint32_t pix = 0u;
-        bool owned = false;
-        c.n_closest = 0u; c.n_any = 0u;
-        const bool have = slot_in < n;
-        if (have) cont_load(qin, slot_in, pix, c.rng, owned, s, STAGE == 2 ? &r : nullptr);
-        const bool parked = run_segment_and_park<VARIANT>(c, s, d0, d1, qout, pix, owned, STAGE == 2 ? &r : nullptr);
-        if (have && !parked) finish_path<STAGE>(c, pix, r, s);
-        if (owned) { cnt_closest += c.n_closest; cnt_any += c.n_any; }
-    }
-    flush_ray_counters(fv, cnt_closest, cnt_any, s_cnt);
+    LoopState s;
+    s.alive = false;
+    ReservoirView r = zero_reservoir();
+    uint32_t pix = 0u;
+    bool owned = false;
+    const bool have = m.offset + threadIdx.x < n;
+    if (have) cont_load(qin, m.region * rcap + m.offset + threadIdx.x, pix, c.rng, owned, s, STAGE == 2 ? &r : nullptr);
+    const bool parked = run_segment_and_park<VARIANT>(c, s, d0, d1, qout, pix, owned, STAGE == 2 ? &r : nullptr);
+    if (have && !parked) finish_path<STAGE>(c, pix, r, s);
+    wave_flush_ray_counters(fv, owned ? c.n_closest : 0u, owned ? c.n_any : 0u, m.region);
 }
 
 // T-merge (frt_path.hpp: temporal_merge): RIS of the fresh candidate with the reprojected previous spatial reservoir, one thread
 // per pixel over rows [y0, y1), pixel-linear (every access is a full row segment). No rays; the only kernel of the temporal stage
 // that sits on the frame-to-frame dependency chain. Its first lanes also COMMIT the ray counts of a G-buffer + T-trace pair that
-// ran ahead of its frame (frt_renderer.hip: speculation): `pending` -> `committed`, four words.
-__global__ void __launch_bounds__(kBlock) merge_kernel(SceneView sc, FrameView fv, unsigned long long* pending, unsigned long long* committed) {
-    if (pending && blockIdx.x == 0u && threadIdx.x < 4u) {
-        const unsigned long long v = atomicExch(&pending[threadIdx.x], 0ull);
-        if (v) atomicAdd(&committed[threadIdx.x], v);
-    }
+// ran ahead of its frame (frt_renderer.hip: speculation): `pending` -> `committed`, four words of each of the nsub regions, all added to region 0.
+__global__ void __launch_bounds__(kBlock) merge_kernel(SceneView sc, FrameView fv, unsigned long long* pending, unsigned long long* committed, uint32_t nsub) {
+    if (pending)
+        for (uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x; i < 4u * nsub; i += gridDim.x * (uint32_t)kBlock) {
+            const unsigned long long v = atomicExch(&pending[(size_t)(i >> 2) * kRayRegionStride + (i & 3u)], 0ull);
+            if (v) atomicAdd(&committed[i & 3u], v);
+        }
     const size_t first = (size_t)fv.y0 * fv.W, last = (size_t)fv.y1 * fv.W;
     const size_t pix = first + (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (pix < last) temporal_merge_pixel(sc, fv, (uint32_t)pix);
@@ -338,10 +363,9 @@ static dim3 grid_for(const FrameView& fv) { return dim3((fv.W + 15u) / 16u, (fv.
 static bool empty_rows(const FrameView& fv) { return fv.y1 <= fv.y0 || fv.W == 0u; }
 static ContQueue queue_of(const TraceLaunch& L, uint32_t k) {
     ContQueue q; q.words = L.qwords[k & 1u]; q.count = L.counts + k; q.capacity = (k & 1u) ? L.capacity_odd : L.capacity; q.overflow = L.overflow;
+    q.nsub = L.nsub ? L.nsub : 1u;
 #if FRT_EXPERIMENTS
-    q.nsub = L.wavefront ? (uint32_t)kWfSub : 1u;
-#else
-    q.nsub = 1u;
+    if (L.wavefront) q.nsub = (uint32_t)kWfSub;
 #endif
     return q;
 }
@@ -363,10 +387,10 @@ hipError_t launch_post(const FrameView& fv, hipStream_t stream) {
     else hipLaunchKernelGGL(post_kernel, grid_for(fv), dim3(kBlock), 0, stream, fv);
     return hipGetLastError();
 }
-hipError_t launch_merge(const SceneView& sc, const FrameView& fv, hipStream_t stream, unsigned long long* pending, unsigned long long* committed) {
+hipError_t launch_merge(const SceneView& sc, const FrameView& fv, hipStream_t stream, unsigned long long* pending, unsigned long long* committed, uint32_t nsub) {
     if (empty_rows(fv)) return hipSuccess;
     const size_t n = (size_t)(fv.y1 - fv.y0) * fv.W;
-    hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, sc, fv, pending, committed);
+    hipLaunchKernelGGL(merge_kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, sc, fv, pending, committed, nsub);
     return hipGetLastError();
 }
 #if !FRT_EXPERIMENTS
@@ -385,7 +409,7 @@ hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& 
 #endif
     const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
     const WalkArgs wa{plan.stack_rows, plan.top_nodes};
-    auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, 0), first_cut(L, fv), L.zero_counts, L.wg_park, wa); };
+    auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, 0), first_cut(L, fv), L.zero_counts, wa); };
 #if FRT_EXPERIMENTS
     if (L.walk == (uint32_t)kWalkQuadWg) {      // collective walks: dynamic LDS = stack rows + exchange rows
         const uint32_t lds = (L.wg_rows + (uint32_t)kXRows) * (uint32_t)kBlock * 4u;
@@ -402,8 +426,8 @@ hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& 
     return hipGetLastError();
 }
 bool trace_has_continuations(const TraceLaunch& L, uint32_t max_depth) { return L.ncuts > 0 && L.cuts[0] < max_depth; }
-// One continuation launch per further path segment, each over min(queue length, capacity) parked paths (the grid covers the capacity;
-// workgroups beyond the queue's length leave at once). Resident form: persistent workgroups take 64-path chunks from a counter.
+// One continuation launch per further path segment, each over the parked paths of every region of its queue (the grid covers every region's
+// capacity; workgroups beyond their region's fill leave at once). Resident form: persistent workgroups take 64-path chunks from a counter.
 hipError_t launch_trace_continuations(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream, const TraceLaunch& L) {
     if (stage != 1 && stage != 2) return hipErrorInvalidValue;
 #if FRT_EXPERIMENTS
@@ -412,8 +436,8 @@ hipError_t launch_trace_continuations(int stage, const SceneView& sc, const Fram
     const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
     const WalkArgs wa{plan.stack_rows, plan.top_nodes};
     for (uint32_t k = 0; k < L.ncuts && L.cuts[k] < fv.max_depth; ++k) {
-        const uint32_t gslots = std::max(queue_of(L, k).capacity, L.grid_min_slots);   // (workgroups beyond the queue's fill retire at once)
-        const dim3 cgrid((gslots + (uint32_t)kBlock - 1u) / (uint32_t)kBlock);
+        const ContQueue qk = queue_of(L, k);      // (workgroups beyond their region's fill retire at once)
+        const dim3 cgrid(std::max(std::max(cont_grid_blocks(qk.capacity, qk.nsub, (uint32_t)kBlock), (L.grid_min_slots + (uint32_t)kBlock - 1u) / (uint32_t)kBlock), 1u));
         const uint32_t d0 = L.cuts[k], d1 = (k + 1 < L.ncuts && L.cuts[k + 1] < fv.max_depth) ? L.cuts[k + 1] : fv.max_depth;
         auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, cgrid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, k), queue_of(L, k + 1), d0, d1, wa); };
 #if FRT_EXPERIMENTS

@@ -8,7 +8,10 @@ namespace frt {
 // segment. The two word buffers are used alternately by the segments (the second one only exists when there are two cuts or more);
 // every segment has its OWN counter (counts[0 .. ncuts], zero before the stage runs), so a buffer that is written again two launches
 // later starts from slot 0. `zero_counts`: the counter set of this stage's NEXT launch, cleared in passing by the pixel kernel.
+// A queue is cut into `nsub` regions (frt_mono.hpp: ContQueue): region g of segment k counts in counts[g * kRegionStride + k], so a region's
+// counters fill one 128-byte line of their own and a set is nsub lines.
 static constexpr int kMaxCuts = 4;
+static constexpr uint32_t kMaxRegions = 256u;
 enum { kWalkQuad = 0, kWalkWide = 2, kWalkWideLds = 3, kWalkQuadWg = 4 };      // (1 = the quad walk with the voting loop: TraceLaunch::vote; kWalkQuadWg: the quad walk, a workgroup's rays re-dealt to dense direction-sorted waves: frt_kernels.hip: wg_trace)
 #ifndef FRT_EXPERIMENTS
 #define FRT_EXPERIMENTS 0
@@ -18,7 +21,7 @@ struct TraceLaunch {
     uint32_t capacity, capacity_odd, grid_min_slots;   // capacity_odd: slots of qwords[1] (the odd segments: far fewer paths get that far); grid_min_slots: the continuation grids cover at least this many slots
     uint32_t* overflow;
     uint32_t* zero_counts;
-    bool wg_park;   // pixel kernel: one queue reservation per workgroup instead of one per wave (the product: always)
+    uint32_t nsub;  // regions of every queue and of the ray counters: a power of two <= kMaxRegions (1: the kernel families that read one counter)
     bool vote;      // the kernels whose BVH walk votes for its next step (frt_trace.hpp: trace4<ANY, VOTE>): scenes with a deep tree
     uint32_t walk;  // which tree the traced kernels walk: kWalkQuad (trace4; `vote` picks its loop), kWalkWide (trace8, nodes read from HBM), kWalkWideLds (trace8, the whole 8-wide tree copied into every workgroup's LDS: wide_lds_bytes of dynamic LDS)
     uint32_t wide_lds_bytes;
@@ -75,6 +78,18 @@ inline WalkLdsPlan walk_lds_plan(uint32_t wg_rows, uint32_t num_nodes4, uint32_t
     return p;
 }
 
+// continue_kernel: which parked paths workgroup `wg` of `threads` lanes resumes. Consecutive workgroups take consecutive regions (nsub: a power of
+// two), so the workgroups that have paths are the first of the grid whatever the regions hold; lane t resumes slot region * rcap + offset + t of the
+// queue while offset + t is below the region's fill. A grid of cont_grid_blocks workgroups visits every slot of every region exactly once.
+struct RegionSlots { uint32_t region, offset; };
+FRT_HD RegionSlots cont_region_slots(uint32_t wg, uint32_t nsub, uint32_t threads) {
+    RegionSlots m;
+    m.region = wg & (nsub - 1u);
+    m.offset = (wg / nsub) * threads;
+    return m;
+}
+inline uint32_t cont_grid_blocks(uint32_t capacity, uint32_t nsub, uint32_t threads) { return nsub * ((capacity / nsub + threads - 1u) / threads); }
+
 // All launches are asynchronous on `stream` and cover rows [fv.y0, fv.y1).
 hipError_t launch_gbuffer(const SceneView& sc, const FrameView& fv, hipStream_t stream, uint32_t wg_rows, uint32_t walk = kWalkQuad);      // wg_rows: TraceLaunch::wg_rows; walk: kWalkQuad or kWalkWide (primary rays are coherent: their nodes stay in HBM / L1)
 hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream, const TraceLaunch& L);
@@ -84,7 +99,8 @@ hipError_t launch_trace_continuations(int stage, const SceneView& sc, const Fram
 void resident_plan(const SceneView& sc, uint32_t& nodes, bool& tris);
 // T-merge; `pending` (may be null): four ray counters {G closest, G any, T-trace closest, T-trace any} of a G-buffer + T-trace pair that
 // ran ahead of its frame, added to `committed` and cleared.
-hipError_t launch_merge(const SceneView& sc, const FrameView& fv, hipStream_t stream, unsigned long long* pending, unsigned long long* committed);
+// Both are region 0 of their counters; `nsub` regions of kRayRegionStride words each are committed.
+hipError_t launch_merge(const SceneView& sc, const FrameView& fv, hipStream_t stream, unsigned long long* pending, unsigned long long* committed, uint32_t nsub);
 hipError_t launch_post(const FrameView& fv, hipStream_t stream);
 // Opt-in workgroup-compacting kernels (FRT_FLAG_COMPACTION): stage 1 = the FUSED temporal stage (trace + merge), stage 2 = spatial.
 hipError_t launch_compact(int stage, const SceneView& sc, const FrameView& fv, hipStream_t stream);

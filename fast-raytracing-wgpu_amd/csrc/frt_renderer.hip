@@ -197,7 +197,7 @@ int frt::drop_speculation(frt_renderer* r) {
     const frt_renderer::Spec sp = r->specs.front();
     int rc = fence_ahead(r);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(r->d_counters + C_PENDING, 0, 4 * kPending * sizeof(unsigned long long), r->stream));
+    HIP_TRY(hipMemset2DAsync(r->d_counters + C_PENDING, kRayRegionStride * sizeof(unsigned long long), 0, 4 * kPending * sizeof(unsigned long long), r->nsub, r->stream));   // (every region's pending sets)
     r->logical_phys[0] = sp.logical_before[0]; r->logical_phys[1] = sp.logical_before[1];
     r->stats.discarded_speculations += r->specs.size();
     r->specs.clear();
@@ -257,17 +257,22 @@ static const size_t kWfCounterWords = 1024;                        // per stage:
 static const int kWorkSlots = 3 + kMaxCuts;                       // pixel launch (interior / whole), the two edge launches, one per continuation launch
 static const size_t kWorkWords = 2 * kWorkSlots * 2;               // [stage][slot]{next, ticket}
 #endif
-static const size_t kQoverflowAt = 2 * 2 * (kMaxCuts + 1);      // (even: the pointers in the overflow blocks are 8-byte aligned)
-static const size_t kQcountWords = kQoverflowAt + 2 * kOverflowBlockWords;   // [stage][parity][segment] counters + [stage] overflow blocks {count, pad, pointer to the mapped flag}
+// d_qcount: [stage][launch parity] counter sets of nsub lines (region g, segment k: word g * kRegionStride + k; frt_kernels.hpp), then the [stage]
+// overflow blocks {count, pad, pointer to the mapped flag}
+static_assert(kMaxCuts + 1 <= (int)kRegionStride && C_COUNT <= (int)kRayRegionStride, "a region's counters fit its line");
+static size_t qcount_set_words(const frt_renderer* r) { return (size_t)r->nsub * kRegionStride; }
+static size_t qoverflow_at(const frt_renderer* r) { return 2 * 2 * qcount_set_words(r); }      // (even: the pointers in the overflow blocks are 8-byte aligned)
+static size_t qcount_words(const frt_renderer* r) { return qoverflow_at(r) + 2 * kOverflowBlockWords; }
+static size_t ray_counter_words(const frt_renderer* r) { return (size_t)r->nsub * kRayRegionStride; }
 static bool stage_is_cut(const frt_renderer* r) { return r->ncuts > 0 && r->cuts[0] < r->max_depth && !(r->flags & FRT_FLAG_COMPACTION); }
 
 // Continuation queues for `cap` parked paths per segment. T-trace parks 22 words per path, spatial 30 (its merged reservoir rides along).
 // Zeroes the queue counters and (re)writes the overflow blocks' pointers to the mapped flag (ContQueue, frt_mono.hpp). On r->stream.
 static int clear_queue_counters(frt_renderer* r) {
-    HIP_TRY(hipMemsetAsync(r->d_qcount, 0, kQcountWords * sizeof(uint32_t), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_qcount, 0, qcount_words(r) * sizeof(uint32_t), r->stream));
     if (r->d_qseen)
         for (int st = 0; st < 2; ++st)
-            HIP_TRY(hipMemcpyAsync(r->d_qcount + kQoverflowAt + (size_t)st * kOverflowBlockWords + 2, &r->d_qseen, sizeof(uint32_t*), hipMemcpyHostToDevice, r->stream));
+            HIP_TRY(hipMemcpyAsync(r->d_qcount + qoverflow_at(r) + (size_t)st * kOverflowBlockWords + 2, &r->d_qseen, sizeof(uint32_t*), hipMemcpyHostToDevice, r->stream));
     if (r->h_qseen) *reinterpret_cast<volatile uint32_t*>(r->h_qseen) = 0u;
     return FRT_OK;
 }
@@ -299,6 +304,15 @@ static int alloc_queues(frt_renderer* r, uint32_t cap) {
     for (int st = 0; st < 2; ++st)
         for (int k = 0; k < 2; ++k) {
             r->qslots[st][k] = (r->qcap_fixed || cap >= r->qcap_max) ? cap : std::min(cap, std::max(4096u, (uint32_t)(kShare[st][k] * cap)));
+            if (!r->qcap_fixed) {
+                // a region is capacity / nsub slots: whole waves of slots, so that every region starts on a 256-byte row of each word plane
+                const uint32_t g = 64u * r->nsub;
+                r->qslots[st][k] = (r->qslots[st][k] + g - 1u) / g * g;
+                // "every traced pixel parks" must hold region by region: a region takes every nsub-th workgroup of each launch of the stage
+                // (a strip: interior rows and two edges), 256 paths each
+                const uint64_t wgs = (uint64_t)((r->W + 15u) / 16u) * (std::min(r->H, (r->re - r->rb) + 2u * kHaloSpatial) / 16u + 4u);
+                if (cap >= r->qcap_max) r->qslots[st][k] = (uint32_t)std::min<uint64_t>(0x7FFFFF00ull, (wgs / r->nsub + 3u) * 256u * r->nsub);
+            }
             if (k >= nbuf) continue;
             const size_t bytes = (size_t)(st == 0 ? kContWordsPath : kContWordsSpatial) * r->qslots[st][k] * sizeof(uint32_t);
             HIP_TRY(hipMalloc((void**)&r->d_qwords[st][k], bytes));
@@ -352,7 +366,6 @@ static int exp_init(frt_renderer* r, int phase) {
     resident_plan(r->sv, x.res_nodes, x.res_tris);
     if (const char* e = getenv("FRT_RESIDENT")) x.resident = atoi(e) != 0 && x.res_nodes > 0 && !(r->flags & FRT_FLAG_COMPACTION);
     if (const char* e = getenv("FRT_STREAM")) { x.stream_mode = atoi(e) != 0; if (atoi(e) > 1) x.shade_min = (uint32_t)std::min(64, atoi(e)); }   // n > 1 = shade_min
-    if (const char* e = getenv("FRT_WG_PARK")) x.wg_park = atoi(e) != 0;
     if (const char* e = getenv("FRT_CONT_GRID")) x.cont_grid = std::max(0l, atol(e));
     if (const char* e = getenv("FRT_STREAM_SLICE")) x.stream_slice = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("FRT_REFILL")) { x.refill = atoi(e) != 0; if (atoi(e) > 1) x.refill_min = (uint32_t)std::min(64, atoi(e)); }   // 0 off, 1 on, n > 1: refill when >= n lanes are free
@@ -366,7 +379,8 @@ static int exp_init(frt_renderer* r, int phase) {
 // The experiment fields of a stage's launch description (frt_kernels.hpp: TraceLaunch).
 static void exp_fill_launch(frt_renderer* r, int stage, bool with_tile_state, TraceLaunch& L, int work_slot, bool cut) {
     const ExpState& x = r->x;
-    L.wg_park = x.wg_park;
+    // the kernel families that read a queue's fill from ONE counter
+    if (x.resident || x.refill || x.stream_mode || x.wavefront || r->walk == (uint32_t)kWalkQuadWg) L.nsub = 1u;
     L.refill = x.refill; L.refill_min = x.refill_min; L.stream = x.stream_mode; L.shade_min = x.shade_min; L.slice = x.stream_slice;
     L.resident = x.resident; L.res_nodes = x.res_nodes; L.res_tris = x.res_tris; L.num_cus = x.num_cus; L.res_batch = x.res_batch;
     L.work = x.d_work + ((size_t)(stage - 1) * kWorkSlots + (size_t)work_slot) * 2;
@@ -426,7 +440,16 @@ static int renderer_init(frt_renderer* r, const frt_scene* s, const frt_render_o
     } else {
         HIP_TRY(hipMalloc((void**)&r->arena, r->arena_bytes)); r->own_arena = true;
     }
-    HIP_TRY(hipMalloc((void**)&r->d_counters, C_COUNT * sizeof(unsigned long long)));
+    // Regions of the continuation queues and of the ray counters (frt_mono.hpp: ContQueue). FRT_QUEUE_REGIONS=<regions>[,<slots>], read once here,
+    // is the queue geometry for tests and sweeps: another power of two and, if given, the capacity the queues START with (they still grow).
+    uint32_t env_slots = 0u;
+    if (const char* e = getenv("FRT_QUEUE_REGIONS")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (v >= 1) { r->nsub = 1u; while (r->nsub * 2u <= (uint32_t)std::min<long>(v, (long)kMaxRegions)) r->nsub *= 2u; }
+        if (end && *end == ',') env_slots = (uint32_t)std::max(0l, std::min(atol(end + 1), 0x7FFFFFFFl));
+    }
+    HIP_TRY(hipMalloc((void**)&r->d_counters, ray_counter_words(r) * sizeof(unsigned long long)));
     {   // the bounce depths at which paths are cut, and the continuation queues
         // Measured with the quad-tree kernels (tools/cut_sweep.sh, tools/strip_cuts.py): a 1080p frame 2.57 ms uncut, 2.08 cut at depth 3,
         // 1.97 at 3 and 5, 1.92 at 3 and 4; half a frame 1.41 uncut, 1.13 cut at 3, 1.09 at 3 and 4; a quarter 0.76 / 0.66 / 0.69; an
@@ -454,13 +477,14 @@ static int renderer_init(frt_renderer* r, const frt_scene* s, const frt_render_o
         const uint32_t c0 = r->ncuts ? r->cuts[0] : 0u;
         const double share = c0 >= 3 ? 0.25 : (c0 == 2 ? 0.6 : 0.8);
         uint32_t cap = (uint32_t)std::min<double>(r->qcap_max, std::max(4096.0, share * r->qcap_max));
+        if (env_slots) cap = std::min(env_slots, r->qcap_max);
         if (o && o->queue_capacity) { cap = std::min(o->queue_capacity, r->qcap_max); r->qcap_fixed = true; }
 #if FRT_EXPERIMENTS
         if (const char* e = getenv("FRT_QUEUE_CAP")) { const long v = atol(e); if (v > 0) { cap = std::min<uint32_t>((uint32_t)v, r->qcap_max); r->qcap_fixed = true; } }
 #endif
         int rc = alloc_queues(r, cap);
         if (rc) return rc;
-        HIP_TRY(hipMalloc((void**)&r->d_qcount, kQcountWords * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&r->d_qcount, qcount_words(r) * sizeof(uint32_t)));
         // (no mapped host memory -> no flag: the queues are then grown by frt_renderer_stats alone, as before)
         if (hipHostMalloc((void**)&r->h_qseen, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
             *r->h_qseen = 0u;
@@ -470,7 +494,7 @@ static int renderer_init(frt_renderer* r, const frt_scene* s, const frt_render_o
     }
     HIP_TRY(hipMemsetAsync(r->arena, 0, r->arena_bytes, r->stream));   // wgpu zero-initialises textures and buffers
     if (r->extras) HIP_TRY(hipMemsetAsync(r->extras, 0, r->extras_bytes, r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_counters, 0, C_COUNT * sizeof(unsigned long long), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_counters, 0, ray_counter_words(r) * sizeof(unsigned long long), r->stream));
     int rc = upload_scene(r, s->b);
     if (rc) return rc;
 #if FRT_EXPERIMENTS
@@ -525,7 +549,7 @@ frt_renderer* frt_renderer_create(const frt_scene* s, uint32_t width, uint32_t h
 // run beside the interior one); the continuation launches use the pairs behind them.
 static void trace_launch_of(frt_renderer* r, int stage, bool with_tile_state, TraceLaunch& L, int work_slot = 0) {
     memset(&L, 0, sizeof(L));
-    L.wg_park = true;
+    L.nsub = r->nsub;
     L.vote = r->vote;
     L.walk = r->walk; L.wide_lds_bytes = r->wide_lds_bytes; L.wg_rows = r->wg_rows;
     const bool cut = stage_is_cut(r) && r->qcap > 0;
@@ -533,16 +557,16 @@ static void trace_launch_of(frt_renderer* r, int stage, bool with_tile_state, Tr
     for (int k = 0; k < kMaxCuts; ++k) L.cuts[k] = r->cuts[k];
     L.qwords[0] = r->d_qwords[stage - 1][0]; L.qwords[1] = r->d_qwords[stage - 1][1];
     const uint32_t par = r->qparity[stage - 1];
-    uint32_t* base = r->d_qcount + (size_t)(stage - 1) * 2 * (kMaxCuts + 1);
-    L.counts = base + (size_t)par * (kMaxCuts + 1);
-    L.zero_counts = cut ? base + (size_t)(par ^ 1u) * (kMaxCuts + 1) : nullptr;
+    uint32_t* base = r->d_qcount + (size_t)(stage - 1) * 2 * qcount_set_words(r);
+    L.counts = base + (size_t)par * qcount_set_words(r);
+    L.zero_counts = cut ? base + (size_t)(par ^ 1u) * qcount_set_words(r) : nullptr;
     L.capacity = r->qslots[stage - 1][0]; L.capacity_odd = r->qslots[stage - 1][1];
     // Two streams: the spatial continuation launches (main stream) get a grid over half the stage's pixels, whatever the queue holds; the
     // surplus workgroups retire at once. Measured 1.97 -> 1.92 ms per 1080p frame (grid of 0.6 / 0.8 / 1.0 / 2 / 4 M slots: 1.98 / 1.95 /
     // 1.92 / 1.92 / 1.92; no effect on one stream, none for the T-trace launches on the ahead stream): while the grid is still being
     // dispatched the main stream keeps its turn at the dispatcher beside the next frame's T-trace pixel kernel (profiles/r2_schedule_notes.md).
     L.grid_min_slots = (stage == 2 && r->pipeline()) ? (uint32_t)std::min<uint64_t>(r->qcap_max, (uint64_t)r->W * (r->re - r->rb) / 2u) : 0u;
-    L.overflow = r->d_qcount + kQoverflowAt + (size_t)(stage - 1) * kOverflowBlockWords;
+    L.overflow = r->d_qcount + qoverflow_at(r) + (size_t)(stage - 1) * kOverflowBlockWords;
 #if FRT_EXPERIMENTS
     exp_fill_launch(r, stage, with_tile_state, L, work_slot, cut);
 #else
@@ -614,21 +638,26 @@ static GSlots alloc_g(frt_renderer* r, uint32_t frame_count) {
 static int grow_queues_if_overflowed(frt_renderer* r) {
     if (!r->d_qcount) return FRT_OK;
     uint32_t blk[2 * kOverflowBlockWords] = {0};
-    HIP_TRY(hipMemcpy(blk, r->d_qcount + kQoverflowAt, sizeof(blk), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(blk, r->d_qcount + qoverflow_at(r), sizeof(blk), hipMemcpyDeviceToHost));
     const uint32_t ov[2] = {blk[0], blk[kOverflowBlockWords]};
 #if FRT_EXPERIMENTS
-    if (getenv("FRT_DEBUG_QUEUES")) {   // (debug: the queue counters of the last launches, [stage][parity][segment])
-        uint32_t qc[kQcountWords];
-        HIP_TRY(hipMemcpy(qc, r->d_qcount, sizeof(qc), hipMemcpyDeviceToHost));
-        fprintf(stderr, "queues slots T %u %u S %u %u:", r->qslots[0][0], r->qslots[0][1], r->qslots[1][0], r->qslots[1][1]);
-        for (size_t i = 0; i < kQcountWords; ++i) fprintf(stderr, " %u", qc[i]);
+    if (getenv("FRT_DEBUG_QUEUES")) {   // (debug: the queue counters of the last launches, [stage][parity][segment], summed over the regions)
+        std::vector<uint32_t> qc(qcount_words(r));
+        HIP_TRY(hipMemcpy(qc.data(), r->d_qcount, qc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        fprintf(stderr, "queues slots T %u %u S %u %u regions %u:", r->qslots[0][0], r->qslots[0][1], r->qslots[1][0], r->qslots[1][1], r->nsub);
+        for (size_t set = 0; set < 4; ++set)
+            for (int k = 0; k <= kMaxCuts; ++k) {
+                uint64_t sum = 0;
+                for (uint32_t g = 0; g < r->nsub; ++g) sum += qc[set * qcount_set_words(r) + (size_t)g * kRegionStride + (size_t)k];
+                fprintf(stderr, " %llu", (unsigned long long)sum);
+            }
         fprintf(stderr, "\n");
     }
 #endif
     if (r->h_qseen) *reinterpret_cast<volatile uint32_t*>(r->h_qseen) = 0u;
     if (ov[0] || ov[1]) {
         r->stats.queue_overflow += (uint64_t)ov[0] + ov[1];
-        for (int st = 0; st < 2; ++st) HIP_TRY(hipMemset(r->d_qcount + kQoverflowAt + (size_t)st * kOverflowBlockWords, 0, sizeof(uint32_t)));
+        for (int st = 0; st < 2; ++st) HIP_TRY(hipMemset(r->d_qcount + qoverflow_at(r) + (size_t)st * kOverflowBlockWords, 0, sizeof(uint32_t)));
         if (!r->qcap_fixed && r->qcap < r->qcap_max) {
             const int rc = alloc_queues(r, (uint32_t)std::min<uint64_t>(r->qcap_max, (uint64_t)r->qcap * 2u));
             if (rc) return rc;
@@ -749,7 +778,7 @@ static int render_phases_impl(frt_renderer* r, const frt_camera_uniform* cam, in
             if (r->from_speculation) HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_tt[r->cur_spec_idx], 0));
             frt_renderer::Timed t{};
             if (timed) { int rc = timer_begin(r, t, 4, r->stream); if (rc) return rc; }
-            HIP_TRY(launch_merge(r->sv, fv, r->stream, r->from_speculation ? r->d_counters + C_PENDING + 4 * r->cur_spec_idx : nullptr, r->d_counters + C_STAGE));
+            HIP_TRY(launch_merge(r->sv, fv, r->stream, r->from_speculation ? r->d_counters + C_PENDING + 4 * r->cur_spec_idx : nullptr, r->d_counters + C_STAGE, r->nsub));
             if (timed) { int rc = timer_end(r, t, r->stream); if (rc) return rc; }
             if (r->pipeline()) HIP_TRY(hipEventRecord(r->ev_tm[r->serial & 1u], r->stream));
         }
@@ -912,7 +941,7 @@ int frt_renderer_clear(frt_renderer* r) {
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(r->arena, 0, r->arena_bytes, r->stream));
     if (r->extras) HIP_TRY(hipMemsetAsync(r->extras, 0, r->extras_bytes, r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_counters, 0, C_COUNT * sizeof(unsigned long long), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_counters, 0, ray_counter_words(r) * sizeof(unsigned long long), r->stream));
     { int rc_ = clear_queue_counters(r); if (rc_) return rc_; }
 #if FRT_EXPERIMENTS
     HIP_TRY(hipMemsetAsync(r->x.d_work, 0, kWorkWords * sizeof(uint32_t), r->stream));
@@ -999,8 +1028,12 @@ int frt_renderer_stats(frt_renderer* r, frt_stats* out) {
     { int rc_ = sync_all(r); if (rc_) return rc_; }
     int rc = resolve_timing(r);
     if (rc) return rc;
+    // the traced kernels count their rays per region (frt_mono.hpp: kRayRegionStride); everything else counts in region 0
+    std::vector<unsigned long long> regions(ray_counter_words(r));
+    HIP_TRY(hipMemcpy(regions.data(), r->d_counters, regions.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     unsigned long long c[C_COUNT] = {0};
-    HIP_TRY(hipMemcpy(c, r->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    for (uint32_t g = 0; g < r->nsub; ++g)
+        for (int k = 0; k < C_COUNT; ++k) c[k] += regions[(size_t)g * kRayRegionStride + (size_t)k];
     r->stats.halo_overflow = c[C_HALO];
     r->stats.rays_closest = 0; r->stats.rays_any = 0;
     for (int st = 0; st < 4; ++st) {

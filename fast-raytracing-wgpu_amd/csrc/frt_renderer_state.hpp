@@ -70,7 +70,7 @@ static uint32_t bpp_of(int b) {
 }
 struct GSlots { uint32_t g, gprev, aux; };   // physical sets: this frame's G-buffer, the previous logical slot's, and motion / candidate (= g under the pipeline)
 
-// Device counters (unsigned long long each): [0..7] committed rays per stage {closest, any}; [8] halo overflow;
+// Device counters (unsigned long long each; one block of kRayRegionStride per region, summed by frt_renderer_stats): [0..7] committed rays per stage {closest, any}; [8] halo overflow;
 // [9..12] PENDING rays of a G-buffer + T-trace pair that ran ahead of its frame (committed by its T-merge, dropped with a discarded speculation)
 static const int kPending = 2;               // pending ray-count sets / T-trace events: consecutive speculated frames alternate (with three G-buffer sets
                                              // T-trace(f+1) may start before T-merge(f) has committed the counts of T-trace(f))
@@ -83,7 +83,6 @@ struct ExpState {
     int spec_depth = kSpecDepth;           // frames speculated ahead (FRT_SPEC_DEPTH, 0 .. kSpecDepth)
     long cont_grid = -1;                   // FRT_CONT_GRID: slots the spatial continuation grids cover at least (-1: half the stage's pixels)
     uint32_t* d_tiles = nullptr;           // per traced stage kTileStateWords words of sweep-direction state (FRT_TILE_ORDER=1), or null
-    bool wg_park = true;                   // pixel kernels reserve queue slots once per workgroup (FRT_WG_PARK=0: once per wave)
     bool wavefront = false;                // ray-level wavefront (FRT_WAVEFRONT=1): per bounce depth a trace launch and a shade launch
     uint32_t* d_wf_words[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; uint32_t* d_wf_items[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     uint32_t* d_wf_hits[2] = {nullptr, nullptr}; uint32_t* d_wf_counts = nullptr;   // per stage: records x 2, item lists x 2, hit buffer; 2 x 96 counters
@@ -255,7 +254,8 @@ struct frt_renderer {
     uint32_t qslots[2][2] = {{0, 0}, {0, 0}};   // slots of each word buffer [stage][first | second buffer], derived from qcap (alloc_queues)
     uint64_t qbytes = 0;                   // device bytes of the word buffers
     bool qcap_fixed = false;               // capacity given by the caller: never grown
-    uint32_t* d_qcount = nullptr;          // [stage 1|2][launch parity 0|1][kMaxCuts + 1] counters, then [stage] overflow counters
+    uint32_t nsub = 16;                    // regions of every continuation queue and of the ray counters (frt_mono.hpp: ContQueue; chosen by the sweep of profiles/r12_experiments/regional_queues.md)
+    uint32_t* d_qcount = nullptr;          // [stage 1|2][launch parity 0|1] sets of nsub counter lines, then [stage] overflow blocks (frt_renderer.hip: qcount_set_words)
     uint32_t* h_qseen = nullptr; uint32_t* d_qseen = nullptr;   // one word of mapped host memory: set by a wave that found its queue full (ContQueue::seen)
     uint32_t qparity[2] = {0, 0};
     uint32_t ncuts = 2, cuts[kMaxCuts] = {3, 4, 0, 0};   // measured best on the Cornell Box
