@@ -257,7 +257,14 @@ FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint
     float best_det = 0.0f;
     f3 inv = mk3(prune_rcp(d.x), prune_rcp(d.y), prune_rcp(d.z));
     f3 oinv = mk3(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);
-    const uint32_t sx = (f2u(d.x) >> 31) << 4, sy = 32u | ((f2u(d.y) >> 31) << 4), sz = 64u | ((f2u(d.z) >> 31) << 4);
+    const uint32_t sx = (f2u(d.x) >> 31) << 4;
+    uint32_t sy = 32u | ((f2u(d.y) >> 31) << 4), sz = 64u | ((f2u(d.z) >> 31) << 4);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the compiler sees through sy and sz: it splits the constants 32 / 64 off as immediate offsets and keeps node offset + sign bit as two 64-bit lane
+    // addresses — 4 VGPRs across the walk and three 64-bit adds per node step. Opaque, `noff | sy` is one 32-bit OR and the load keeps the scalar base
+    // (slab4): round 13, 4 - 6 VGPRs fewer in every traced kernel.)
+    asm volatile("" : "+v"(sy), "+v"(sz));
+#endif
     const uint32_t kDone = 0xFFFFFFFFu;
     const float kFar = 3.0e38f;
     uint32_t* top = stk;      // next free stack entry (entries are `stride` words apart)
@@ -343,10 +350,21 @@ FRT_HD void trace4(const SceneView& sc, f3 o, f3 d, float tmin, float tmax, uint
         //   frame, ReSTIR scene +3.3 % Mrays/s, 82k-triangle blob 3.30 -> 3.09 ms, 246k-triangle colonnade 21.5 -> 19.9 ms (4 - 8 more VGPRs);
         // * the stack entry the lane continues with (it does not depend on the tests): 1.571 -> 1.555 ms, blob 3.08 -> 3.02 ms.
         // (Fetching the NODE behind that entry as well and stepping it at once costs 10 VGPRs the kernels do not have: scratch, 1.555 -> 1.742 ms.)
-        const float4* tp = sc.tris + (size_t)first * 3u;
+        // The second triangle is selected by its ADDRESS, not by its data (round 13): a single-triangle leaf reads its own slot twice — a valid slot,
+        // the cache lines already on their way — so the six loads and the LDS read leave with no branch and no copy between them. (The form before,
+        // second = first unless count > 1, cost 10 - 11 v_mov that waited for the first triangle before the second was asked for: two dependent round
+        // trips per two-triangle leaf after all; left uninitialised instead, the allocator needed 5 - 8 more registers.) The offset is made opaque so
+        // that it stays ONE 32-bit register beside the uniform base: seen through, it becomes a 64-bit lane address (profiles/r13_experiments/leaf_fetch.md).
+        const char* const tb = reinterpret_cast<const char*>(sc.tris);
+        const uint32_t off0 = first * 48u;      // (24-bit slot numbers: the byte offsets fit 32 bits)
+        uint32_t off1 = off0 + (count > 1u ? 48u : 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(off1));
+#endif
+        const float4* tp = reinterpret_cast<const float4*>(tb + off0);
+        const float4* tq = reinterpret_cast<const float4*>(tb + off1);
         const float4 a0 = tp[0], b0 = tp[1], c0 = tp[2];
-        float4 a1 = a0, b1 = b0, c1 = c0;      // (left uninitialised the allocator needs 5 - 8 MORE registers)
-        if (count > 1u) { a1 = tp[3]; b1 = tp[4]; c1 = tp[5]; }
+        const float4 a1 = tq[0], b1 = tq[1], c1 = tq[2];
         const bool more = top != stk;
         uint32_t next = kDone;
         if (more) next = *(top - stride);
