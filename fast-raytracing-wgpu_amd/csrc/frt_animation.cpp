@@ -1,0 +1,294 @@
+// frt_animation.cpp — the host form of an animated rig (include/frt.h: frt_rig_*; DESIGN.md §11, "Animation"): frt_rig_create checks a description and
+// packs it into the one block frt_animation.hpp reads; frt_rig_evaluate is the specification of frt_renderer_animate's kernel, the same FRT_HD functions
+// run node by node in the block's order (parents first). Host code only; nothing here touches a device.
+#include "frt_animation.hpp"
+#include "frt_loader.hpp"      // frt_model: frt_rig_from_model and the frt_model_* accessors of the rig
+#include "../../include/frt.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace frt { int set_error(int code, const std::string& msg); }
+using namespace frt;
+
+static int rig_fail(const std::string& msg) { return frt::set_error(FRT_ERR_INVALID_ARG, msg); }
+static bool all_finite(const float* p, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false; return true; }
+static uint32_t path_width(uint32_t path, uint32_t ntargets) { return path == (uint32_t)kRigPathRotation ? 4u : path == (uint32_t)kRigPathWeights ? ntargets : 3u; }
+
+// "" or what is wrong with the description. Every count is checked before the array it sizes is read.
+static std::string check_rig_desc(const frt_rig_desc* d) {
+    if (!d) return "null description";
+    if (d->nnodes == 0 || d->nnodes > (1u << 20)) return "nnodes must be 1 .. 2^20";
+    if (!d->parents || !d->rest_trs) return "parents and rest_trs are required";
+    if (d->njoints > 0x10000u) return "more than 65536 joints (a joint index is 16 bits)";
+    if (d->ntargets > FRT_MAX_MORPH_TARGETS) return "more than FRT_MAX_MORPH_TARGETS targets";
+    if (d->njoints == 0 && d->ntargets == 0) return "a rig has joints, morph targets or both";
+    if (d->njoints && !d->joint_nodes) return "joint_nodes is required with njoints > 0";
+    if (d->nclips > (1u << 16)) return "more than 65536 clips";
+    if (d->nclips && !d->clips) return "clips is required with nclips > 0";
+    for (uint32_t n = 0; n < d->nnodes; ++n) {
+        const int32_t p = d->parents[n];
+        if (p < -1 || (p >= 0 && (uint32_t)p >= n)) return "node " + std::to_string(n) + ": a parent is -1 or a smaller node index (parents first)";
+        const bool mat = d->has_matrix && d->has_matrix[n];
+        if (mat && !d->matrices) return "has_matrix names node " + std::to_string(n) + " but matrices is null";
+        if (!(mat ? all_finite(d->matrices + (size_t)16 * n, 16) : all_finite(d->rest_trs + (size_t)10 * n, 10))) return "node " + std::to_string(n) + ": a rest value is not finite";
+    }
+    for (uint32_t j = 0; j < d->njoints; ++j)
+        if (d->joint_nodes[j] >= d->nnodes) return "joint " + std::to_string(j) + " is not a node";
+    if (d->inverse_bind && !all_finite(d->inverse_bind, (size_t)16 * d->njoints)) return "an inverse bind matrix entry is not finite";
+    if (d->default_weights && !all_finite(d->default_weights, d->ntargets)) return "a default morph weight is not finite";
+    uint64_t words = 0;
+    for (uint32_t c = 0; c < d->nclips; ++c) {
+        const frt_rig_clip& cl = d->clips[c];
+        const std::string where = "clip " + std::to_string(c);
+        if (cl.nchannels > (1u << 20)) return where + ": more than 2^20 channels";
+        if (cl.nchannels && !cl.channels) return where + ": channels is null";
+        std::vector<uint8_t> seen((size_t)3 * d->nnodes, 0);
+        bool weights = false;
+        for (uint32_t k = 0; k < cl.nchannels; ++k) {
+            const frt_rig_channel& ch = cl.channels[k];
+            const std::string at = where + ", channel " + std::to_string(k);
+            if (ch.path > (uint32_t)kRigPathWeights) return at + ": unknown path";
+            if (ch.interpolation > (uint32_t)kRigCubic) return at + ": unknown interpolation";
+            if (ch.nkeys == 0 || ch.nkeys > (1u << 24)) return at + ": nkeys must be 1 .. 2^24";
+            if (!ch.times || !ch.values) return at + ": times and values are required";
+            if (ch.path == (uint32_t)kRigPathWeights) {
+                if (d->ntargets == 0) return at + ": a weights channel in a rig without morph targets";
+                if (weights) return at + ": a second weights channel in one clip";
+                weights = true;
+            } else {
+                if (ch.node >= d->nnodes) return at + ": its node is not a node";
+                if (d->has_matrix && d->has_matrix[ch.node]) return at + ": a node given as a matrix cannot be animated";
+                uint8_t& s = seen[(size_t)3 * ch.node + ch.path];
+                if (s) return at + ": a second channel for the same node and path";
+                s = 1;
+            }
+            for (uint32_t i = 0; i < ch.nkeys; ++i)
+                if (!std::isfinite(ch.times[i]) || (i && !(ch.times[i] > ch.times[i - 1]))) return at + ": key times must be finite and strictly increasing";
+            const uint64_t nv = (uint64_t)ch.nkeys * path_width(ch.path, d->ntargets) * (ch.interpolation == (uint32_t)kRigCubic ? 3u : 1u);
+            if (!all_finite(ch.values, (size_t)nv)) return at + ": a key value is not finite";
+            words += nv + ch.nkeys + 8u;
+        }
+        words += (uint64_t)3 * d->nnodes + 4u;
+    }
+    words += (uint64_t)d->nnodes * 19u + (uint64_t)d->njoints * 17u + d->ntargets + 64u;
+    if (words > (1ull << 28)) return "the rig needs more than 1 GiB";
+    return "";
+}
+
+extern "C" {
+
+frt_rig* frt_rig_create(const frt_rig_desc* d) {
+    const std::string bad = check_rig_desc(d);
+    if (!bad.empty()) { rig_fail("rig_create: " + bad); return nullptr; }
+    const uint32_t N = d->nnodes, J = d->njoints, T = d->ntargets;
+    // by depth, parents in front of their children: `order[i]` is the caller's index of node i here
+    std::vector<uint32_t> depth(N, 0u), order(N), place(N);
+    for (uint32_t n = 0; n < N; ++n) { depth[n] = d->parents[n] < 0 ? 0u : depth[(uint32_t)d->parents[n]] + 1u; order[n] = n; }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return depth[a] < depth[b]; });
+    for (uint32_t i = 0; i < N; ++i) place[order[i]] = i;
+    const uint32_t nlevels = depth[order[N - 1]] + 1u;
+    uint32_t nchannels = 0;
+    for (uint32_t c = 0; c < d->nclips; ++c) nchannels += d->clips[c].nchannels;
+
+    frt_rig* rig = new frt_rig();
+    std::vector<uint32_t>& w = rig->words;
+    auto put = [&w](size_t n) { const uint32_t at = (uint32_t)w.size(); w.resize(w.size() + ((n + 3u) & ~(size_t)3u), 0u); return at; };      // (every table 16-byte aligned)
+    auto fl = [&w](uint32_t at) { return reinterpret_cast<float*>(w.data() + at); };
+    RigHeader h;
+    memset(&h, 0, sizeof(h));
+    put(sizeof(RigHeader) / 4);
+    h.nnodes = N; h.njoints = J; h.ntargets = T; h.nclips = d->nclips; h.nlevels = nlevels; h.nchannels = nchannels;
+    h.parent = put(N); h.kind = put(N); h.rest = put((size_t)16 * N); h.level_begin = put(nlevels + 1u);
+    h.joint_node = put(J); h.inv_bind = put((size_t)16 * J); h.def_weights = put(T);
+    h.clips = put((size_t)4 * d->nclips); h.channels = put((size_t)8 * nchannels);
+    for (uint32_t i = 0; i < N; ++i) {
+        const uint32_t n = order[i];
+        w[h.parent + i] = d->parents[n] < 0 ? kRigNone : place[(uint32_t)d->parents[n]];
+        const bool mat = d->has_matrix && d->has_matrix[n];
+        w[h.kind + i] = mat ? 1u : 0u;
+        float* r = fl(h.rest) + (size_t)16 * i;
+        if (mat) memcpy(r, d->matrices + (size_t)16 * n, 64);
+        else { const float* s = d->rest_trs + (size_t)10 * n; memcpy(r, s, 12); memcpy(r + 4, s + 3, 16); memcpy(r + 8, s + 7, 12); }
+        if (i == 0 || depth[n] != depth[order[i - 1]]) w[h.level_begin + depth[n]] = i;
+    }
+    w[h.level_begin + nlevels] = N;
+    for (uint32_t j = 0; j < J; ++j) {
+        w[h.joint_node + j] = place[d->joint_nodes[j]];
+        float* m = fl(h.inv_bind) + (size_t)16 * j;
+        if (d->inverse_bind) memcpy(m, d->inverse_bind + (size_t)16 * j, 64);
+        else m[0] = m[5] = m[10] = m[15] = 1.0f;
+    }
+    if (d->default_weights && T) memcpy(fl(h.def_weights), d->default_weights, (size_t)4 * T);
+    uint32_t chan = 0;
+    for (uint32_t c = 0; c < d->nclips; ++c) {
+        const frt_rig_clip& cl = d->clips[c];
+        RigClip rc; rc.node_table = put((size_t)3 * N); rc.weights_channel = kRigNone; rc.pad0 = rc.pad1 = 0u;
+        for (size_t i = 0; i < (size_t)3 * N; ++i) w[rc.node_table + i] = kRigNone;
+        float duration = 0.0f;
+        for (uint32_t k = 0; k < cl.nchannels; ++k, ++chan) {
+            const frt_rig_channel& ch = cl.channels[k];
+            RigChannel r;
+            memset(&r, 0, sizeof(r));
+            r.path = ch.path; r.interp = ch.interpolation; r.nkeys = ch.nkeys; r.width = path_width(ch.path, T);
+            const size_t nv = (size_t)ch.nkeys * r.width * (ch.interpolation == (uint32_t)kRigCubic ? 3u : 1u);
+            r.times = put(ch.nkeys); r.values = put(nv);
+            memcpy(fl(r.times), ch.times, (size_t)4 * ch.nkeys);
+            memcpy(fl(r.values), ch.values, 4 * nv);
+            if (ch.path == (uint32_t)kRigPathWeights) { r.node = kRigNone; rc.weights_channel = chan; }
+            else { r.node = place[ch.node]; w[rc.node_table + (size_t)3 * r.node + ch.path] = chan; }
+            memcpy(w.data() + h.channels + (size_t)8 * chan, &r, sizeof(r));
+            duration = std::max(duration, ch.times[ch.nkeys - 1]);
+        }
+        memcpy(w.data() + h.clips + (size_t)4 * c, &rc, sizeof(rc));
+        rig->clip_names.push_back(cl.name ? cl.name : "");
+        rig->clip_durations.push_back(duration);
+    }
+    h.words = (uint32_t)w.size();
+    memcpy(w.data(), &h, sizeof(h));
+    return rig;
+}
+
+void frt_rig_destroy(frt_rig* rig) { delete rig; }
+
+// ---- the rig a loaded glTF document holds (frt_loader.cpp: read_rig): plain copies out of LoadedModel
+int frt_model_rig_counts(const frt_model* m, uint32_t out[3]) {
+    if (!m || !out) return rig_fail("model_rig_counts: null");
+    out[0] = (uint32_t)m->m.nodes.size(); out[1] = (uint32_t)m->m.skins.size(); out[2] = (uint32_t)m->m.animations.size();
+    return FRT_OK;
+}
+int frt_model_geometry_rig(const frt_model* m, uint32_t geo, uint32_t out[4]) {
+    if (!m || !out || geo >= m->m.geometries.size()) return rig_fail("model_geometry_rig: bad arguments");
+    out[0] = 0u; out[1] = kRigNone; out[2] = 0u; out[3] = kRigNone;
+    if (geo >= m->m.geometry_rigs.size()) return FRT_OK;      // (an OBJ model)
+    const LoadedModel::GeometryRig& g = m->m.geometry_rigs[geo];
+    out[0] = g.joints.empty() ? 0u : 1u; out[1] = g.skin < 0 ? kRigNone : (uint32_t)g.skin; out[2] = g.ntargets; out[3] = g.mesh < 0 ? kRigNone : (uint32_t)g.mesh;
+    return FRT_OK;
+}
+int frt_model_geometry_skin_get(const frt_model* m, uint32_t geo, uint16_t* joints4, float* weights4) {
+    if (!m || geo >= m->m.geometry_rigs.size() || m->m.geometry_rigs[geo].joints.empty() || !joints4 || !weights4) return rig_fail("model_geometry_skin_get: bad arguments or a geometry without skin attributes");
+    const LoadedModel::GeometryRig& g = m->m.geometry_rigs[geo];
+    memcpy(joints4, g.joints.data(), g.joints.size() * 2); memcpy(weights4, g.weights.data(), g.weights.size() * 4);
+    return FRT_OK;
+}
+int frt_model_geometry_targets_get(const frt_model* m, uint32_t geo, float* deltas3, float* default_weights) {
+    if (!m || geo >= m->m.geometry_rigs.size() || m->m.geometry_rigs[geo].ntargets == 0) return rig_fail("model_geometry_targets_get: bad arguments or a geometry without morph targets");
+    const LoadedModel::GeometryRig& g = m->m.geometry_rigs[geo];
+    if (deltas3) memcpy(deltas3, g.deltas.data(), g.deltas.size() * 4);
+    if (default_weights) memcpy(default_weights, g.default_weights.data(), g.default_weights.size() * 4);
+    return FRT_OK;
+}
+int frt_model_nodes_get(const frt_model* m, int32_t* parents, float* rest_trs, uint8_t* has_matrix, float* matrices, uint32_t* document_index) {
+    if (!m) return rig_fail("model_nodes_get: null");
+    for (size_t i = 0; i < m->m.nodes.size(); ++i) {
+        const LoadedModel::Node& n = m->m.nodes[i];
+        if (parents) parents[i] = n.parent;
+        if (rest_trs) memcpy(rest_trs + 10 * i, n.trs, 40);
+        if (has_matrix) has_matrix[i] = n.has_matrix ? 1 : 0;
+        if (matrices) memcpy(matrices + 16 * i, n.matrix, 64);
+        if (document_index) document_index[i] = n.doc_index;
+    }
+    return FRT_OK;
+}
+int frt_model_skin_get(const frt_model* m, uint32_t skin, uint32_t* njoints, uint32_t* joint_nodes, float* inverse_bind) {
+    if (!m || skin >= m->m.skins.size()) return rig_fail("model_skin_get: bad arguments");
+    const LoadedModel::Skin& s = m->m.skins[skin];
+    if (njoints) *njoints = (uint32_t)s.joints.size();
+    if (joint_nodes) memcpy(joint_nodes, s.joints.data(), s.joints.size() * 4);
+    if (inverse_bind) memcpy(inverse_bind, s.inverse_bind.data(), s.inverse_bind.size() * 4);
+    return FRT_OK;
+}
+int frt_model_animation_info(const frt_model* m, uint32_t anim, const char** name_out, uint32_t* nchannels) {
+    if (!m || anim >= m->m.animations.size()) return rig_fail("model_animation_info: bad arguments");
+    if (name_out) *name_out = m->m.animations[anim].name.c_str();
+    if (nchannels) *nchannels = (uint32_t)m->m.animations[anim].channels.size();
+    return FRT_OK;
+}
+int frt_model_channel_info(const frt_model* m, uint32_t anim, uint32_t channel, uint32_t out[5]) {
+    if (!m || !out || anim >= m->m.animations.size() || channel >= m->m.animations[anim].channels.size()) return rig_fail("model_channel_info: bad arguments");
+    const LoadedModel::Channel& c = m->m.animations[anim].channels[channel];
+    out[0] = c.node; out[1] = c.path; out[2] = c.interpolation; out[3] = (uint32_t)c.times.size(); out[4] = (uint32_t)c.values.size();
+    return FRT_OK;
+}
+int frt_model_channel_get(const frt_model* m, uint32_t anim, uint32_t channel, float* times, float* values) {
+    if (!m || anim >= m->m.animations.size() || channel >= m->m.animations[anim].channels.size()) return rig_fail("model_channel_get: bad arguments");
+    const LoadedModel::Channel& c = m->m.animations[anim].channels[channel];
+    if (times) memcpy(times, c.times.data(), c.times.size() * 4);
+    if (values) memcpy(values, c.values.data(), c.values.size() * 4);
+    return FRT_OK;
+}
+// The rig of skin `skin_index` (or, with -1, a morph-only rig) of a loaded document: every node, the skin's joints and inverse binds, the targets and
+// default weights of the first geometry under that skin (with -1: of the first geometry) that has targets, and one clip per animation in document
+// order; a weights channel is taken when its node carries a mesh with that many targets.
+frt_rig* frt_rig_from_model(const frt_model* m, int32_t skin_index) {
+    if (!m) { rig_fail("rig_from_model: null"); return nullptr; }
+    const LoadedModel& L = m->m;
+    if (skin_index < -1 || (skin_index >= 0 && (size_t)skin_index >= L.skins.size())) { rig_fail("rig_from_model: skin " + std::to_string(skin_index) + " out of range (" + std::to_string(L.skins.size()) + " skins)"); return nullptr; }
+    if (L.nodes.empty()) { rig_fail("rig_from_model: the model has no nodes"); return nullptr; }
+    const LoadedModel::GeometryRig* morph = nullptr;
+    for (const LoadedModel::GeometryRig& g : L.geometry_rigs) if (g.ntargets && (skin_index < 0 || g.skin == skin_index)) { morph = &g; break; }
+    const size_t N = L.nodes.size();
+    std::vector<int32_t> parents(N); std::vector<float> trs(10 * N), mats(16 * N); std::vector<uint8_t> has(N);
+    frt_model_nodes_get(m, parents.data(), trs.data(), has.data(), mats.data(), nullptr);
+    std::vector<std::vector<frt_rig_channel>> channels(L.animations.size());
+    std::vector<frt_rig_clip> clips(L.animations.size());
+    for (size_t a = 0; a < L.animations.size(); ++a) {
+        for (const LoadedModel::Channel& c : L.animations[a].channels) {
+            if (c.path == (uint32_t)kRigPathWeights) {
+                const int mesh = L.nodes[c.node].mesh;
+                if (!morph || mesh != morph->mesh || c.values.size() != c.times.size() * morph->ntargets * (c.interpolation == (uint32_t)kRigCubic ? 3u : 1u)) continue;
+            }
+            channels[a].push_back(frt_rig_channel{c.node, c.path, c.interpolation, (uint32_t)c.times.size(), c.times.data(), c.values.data()});
+        }
+        clips[a] = frt_rig_clip{L.animations[a].name.c_str(), (uint32_t)channels[a].size(), channels[a].data()};
+    }
+    frt_rig_desc d;
+    memset(&d, 0, sizeof(d));
+    d.nnodes = (uint32_t)N; d.parents = parents.data(); d.rest_trs = trs.data(); d.has_matrix = has.data(); d.matrices = mats.data();
+    if (skin_index >= 0) { const LoadedModel::Skin& s = L.skins[(size_t)skin_index]; d.njoints = (uint32_t)s.joints.size(); d.joint_nodes = s.joints.data(); d.inverse_bind = s.inverse_bind.data(); }
+    if (morph) { d.ntargets = morph->ntargets; d.default_weights = morph->default_weights.data(); }
+    d.nclips = (uint32_t)clips.size(); d.clips = clips.data();
+    return frt_rig_create(&d);
+}
+
+void frt_acosf(uint32_t n, const float* x, float* out) { for (uint32_t i = 0; i < n; ++i) out[i] = acosf_(x[i]); }
+
+int frt_rig_counts(const frt_rig* rig, uint32_t counts[4]) {
+    if (!rig || !counts) return rig_fail("rig_counts: null");
+    const RigHeader h = rig->view().h();
+    counts[0] = h.nnodes; counts[1] = h.njoints; counts[2] = h.ntargets; counts[3] = h.nclips;
+    return FRT_OK;
+}
+
+int frt_rig_clip_info(const frt_rig* rig, uint32_t clip, const char** name_out, float* duration_out) {
+    if (!rig) return rig_fail("rig_clip_info: null");
+    if (clip >= rig->clip_names.size()) return rig_fail("rig_clip_info: clip " + std::to_string(clip) + " out of range (" + std::to_string(rig->clip_names.size()) + " clips)");
+    if (name_out) *name_out = rig->clip_names[clip].c_str();
+    if (duration_out) *duration_out = rig->clip_durations[clip];
+    return FRT_OK;
+}
+
+int frt_rig_evaluate(const frt_rig* rig, uint32_t clip, float time, float* joint_mats_out, float* morph_weights_out) {
+    if (!rig) return rig_fail("rig_evaluate: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    if (clip >= h.nclips) return rig_fail("rig_evaluate: clip " + std::to_string(clip) + " out of range (" + std::to_string(h.nclips) + " clips)");
+    if (!std::isfinite(time)) return rig_fail("rig_evaluate: time is not finite");
+    if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail("rig_evaluate: null output");
+    if (h.njoints) {
+        std::vector<m4> global(h.nnodes);
+        for (uint32_t n = 0; n < h.nnodes; ++n) {      // parents first
+            const m4 local = rig_local_matrix(v, clip, n, time);
+            const uint32_t p = v.w[h.parent + n];
+            global[n] = p == kRigNone ? local : mul(global[p], local);
+        }
+        for (uint32_t j = 0; j < h.njoints; ++j) {
+            const m4 m = mul(global[v.w[h.joint_node + j]], load_m4(v.f(h.inv_bind) + (size_t)16 * j));
+            memcpy(joint_mats_out + (size_t)16 * j, &m, 64);
+        }
+    }
+    for (uint32_t c = 0; c < h.ntargets; ++c) morph_weights_out[c] = rig_morph_weight(v, clip, c, time);
+    return FRT_OK;
+}
+
+} // extern "C"

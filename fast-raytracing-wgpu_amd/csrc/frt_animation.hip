@@ -1,0 +1,151 @@
+// frt_animation.hip — the device form of an animated rig (include/frt.h: frt_renderer_bind_rig, _animate, _read_rig_pose, _unbind_rig; DESIGN.md §11,
+// "Animation"). Built with the library's contract flags. No arithmetic is written here: the kernel calls the FRT_HD functions of frt_animation.hpp that
+// frt_rig_evaluate calls on the host, so the palette and the weights have the host's bits.
+//
+// The kernel is ONE workgroup of four waves per rig. (1) Every lane builds the local matrix of a node (sampling the clip's channels of that node),
+// strided by the workgroup's size, into LDS. (2) The globals are propagated level by level: a node's parent lies on the level above, which is complete
+// behind the workgroup barrier that ends it; a node reads its parent's global and its own local and writes its own global in place, so no two lanes touch
+// one entry. The level bounds are the same words for every lane: every barrier is reached by the whole workgroup. (3) One lane per joint multiplies the
+// joint node's global with the inverse bind matrix and stores four float4 (16-byte vector stores); one lane per target samples a morph weight.
+// LDS: FRT_MAX_RIG_NODES x 64 B = 64 KiB, column c of node n at [c * FRT_MAX_RIG_NODES + n], so the lanes of a wave, on consecutive nodes, read and
+// write consecutive 16-byte words.
+#include "frt_renderer_state.hpp"
+#include "frt_animation.hpp"
+
+namespace frt {
+
+static const int kRigBlock = 256;      // four waves of 64
+static const uint32_t kRigLds = FRT_MAX_RIG_NODES;
+
+__device__ inline m4 rig_lds_load(const float4* g, uint32_t n) {
+    m4 m;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { const float4 q = g[(uint32_t)c * kRigLds + n]; m.c[c] = mk4(q.x, q.y, q.z, q.w); }
+    return m;
+}
+__device__ inline void rig_lds_store(float4* g, uint32_t n, const m4& m) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) g[(uint32_t)c * kRigLds + n] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
+}
+
+__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, uint32_t clip, float t, float4* palette, float* weights) {
+    __shared__ float4 g[4u * kRigLds];
+    RigView v; v.w = words;
+    const RigHeader h = v.h();
+    const uint32_t tid = threadIdx.x;
+    const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig refuses a larger rig)
+    if (clip >= h.nclips) return;                                    // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
+    if (h.njoints) {
+        for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix(v, clip, n, t));
+        __syncthreads();
+        for (uint32_t level = 1u; level < h.nlevels; ++level) {
+            const uint32_t begin = words[h.level_begin + level], end = words[h.level_begin + level + 1u];
+            for (uint32_t n = begin + tid; n < end && n < N; n += (uint32_t)kRigBlock) {
+                const uint32_t p = words[h.parent + n];
+                if (p < n) rig_lds_store(g, n, mul(rig_lds_load(g, p), rig_lds_load(g, n)));
+            }
+            __syncthreads();
+        }
+        for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
+            const uint32_t n = words[h.joint_node + j];
+            if (n >= N) continue;
+            const m4 m = mul(rig_lds_load(g, n), load_m4(v.f(h.inv_bind) + (size_t)16u * j));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) palette[4u * j + (uint32_t)c] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
+        }
+    }
+    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = rig_morph_weight(v, clip, c, t);
+}
+
+} // namespace frt
+
+static RigBinding* find_binding(frt_renderer* r, uint32_t binding) { return binding < r->rigs.size() && r->rigs[binding].live ? &r->rigs[binding] : nullptr; }
+// "" when every mesh of the list has the bindings a palette of `njoints` joints and `ntargets` weights in device memory needs: what
+// frt_renderer_set_mesh_poses checks about them.
+static std::string check_rig_meshes(const frt_renderer* r, const uint32_t* ids, uint32_t n, const void* palette, uint32_t njoints, const void* weights, uint32_t ntargets) {
+    const RefitState& f = r->rf;
+    std::string bad = check_pose_batch(n, ids, f.vert_count.size(), njoints != 0, ntargets != 0);
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
+        const uint32_t m = ids[k];
+        if (njoints) bad = check_mesh_pose(static_cast<const float*>(palette), njoints, m < f.skins.size() ? f.skins[m].count : 0u, false);
+        if (ntargets && bad.empty()) bad = check_mesh_morph_weights(static_cast<const float*>(weights), ntargets, m < f.morphs.size() ? f.morphs[m].count : 0u, false);
+        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
+    }
+    return bad;
+}
+
+extern "C" {
+
+int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* mesh_ids, uint32_t n, uint32_t* binding_out) {
+    if (const int rc = check_entry(r, "bind_rig", kEditChecks | kRefit)) return rc;
+    if (!rig || !binding_out) return fail(FRT_ERR_INVALID_ARG, "bind_rig: null");
+    const RigHeader h = rig->view().h();
+    if (h.nnodes > FRT_MAX_RIG_NODES) return fail(FRT_ERR_INVALID_ARG, "bind_rig: " + std::to_string(h.nnodes) + " nodes, more than FRT_MAX_RIG_NODES");
+    const std::string bad = check_rig_meshes(r, mesh_ids, n, rig, h.njoints, rig, h.ntargets);      // (the pointers are only compared with null)
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "bind_rig: " + bad);
+    FRT_DEVICE(r);
+    RigBinding b;
+    int rc;
+    if ((rc = b.rig.ensure(r, rig->words.size() * 4))) return rc;
+    if ((rc = b.palette.ensure(r, (size_t)h.njoints * 64))) { b.rig.release(r); return rc; }
+    if ((rc = b.weights.ensure(r, (size_t)h.ntargets * 4))) { b.rig.release(r); b.palette.release(r); return rc; }
+    rc = r->rig_up.reserve(rig->words.size() * 4, 0, r->stream);
+    if (rc == FRT_OK) {
+        memcpy(r->rig_up.h, rig->words.data(), rig->words.size() * 4);
+        hipError_t e = hipMemcpyAsync(b.rig.p, r->rig_up.h, rig->words.size() * 4, hipMemcpyHostToDevice, r->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.palette.p, 0, b.palette.bytes, r->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.weights.p, 0, b.weights.bytes, r->stream);
+        rc = e == hipSuccess ? r->rig_up.mark(r->stream) : fail(FRT_ERR_HIP, std::string("bind_rig: ") + hipGetErrorString(e));
+    }
+    if (rc) { b.rig.release(r); b.palette.release(r); b.weights.release(r); return rc; }
+    b.njoints = h.njoints; b.ntargets = h.ntargets; b.nclips = h.nclips; b.mesh_ids.assign(mesh_ids, mesh_ids + n); b.live = true;
+    size_t slot = 0;      // the first free number: an unbound one is used again
+    while (slot < r->rigs.size() && r->rigs[slot].live) ++slot;
+    if (slot == r->rigs.size()) r->rigs.push_back(b); else r->rigs[slot] = b;
+    *binding_out = (uint32_t)slot;
+    return FRT_OK;
+}
+
+int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float time, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate", kEditChecks | kRefit)) return rc;
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) return fail(FRT_ERR_INVALID_ARG, "animate: unknown flag bits");
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate: unknown rig binding " + std::to_string(binding));
+    if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
+    if ((__builtin_bit_cast(uint32_t, time) & 0x7f800000u) == 0x7f800000u) return fail(FRT_ERR_INVALID_ARG, "animate: time is not finite");
+    const uint32_t n = (uint32_t)b->mesh_ids.size();
+    const std::string bad = check_rig_meshes(r, b->mesh_ids.data(), n, b->palette.p, b->njoints, b->weights.p, b->ntargets);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate: " + bad);
+    {
+        // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
+        FRT_DEVICE(r);
+        hipLaunchKernelGGL(rig_evaluate_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), clip, time, b->palette.as<float4>(), b->weights.as<float>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate: ") + hipGetErrorString(e)); }
+    }
+    return frt_renderer_set_mesh_poses(r, n, b->mesh_ids.data(), b->njoints ? b->palette.as<float>() : nullptr, b->njoints,
+                                       b->ntargets ? b->weights.as<float>() : nullptr, b->ntargets, flags | FRT_DEFORM_DEVICE);
+}
+
+int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out) {
+    if (const int rc = check_entry(r, "read_rig_pose", kNotFailed)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "read_rig_pose: unknown rig binding " + std::to_string(binding));
+    FRT_DEVICE(r);
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (joint_mats_out && b->njoints) HIP_TRY(hipMemcpy(joint_mats_out, b->palette.p, (size_t)b->njoints * 64, hipMemcpyDeviceToHost));
+    if (morph_weights_out && b->ntargets) HIP_TRY(hipMemcpy(morph_weights_out, b->weights.p, (size_t)b->ntargets * 4, hipMemcpyDeviceToHost));
+    return FRT_OK;
+}
+
+int frt_renderer_unbind_rig(frt_renderer* r, uint32_t binding) {
+    if (const int rc = check_entry(r, "unbind_rig", kNotFailed | kBetweenFrames)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "unbind_rig: unknown rig binding " + std::to_string(binding));
+    FRT_DEVICE(r);
+    b->rig.release(r); b->palette.release(r); b->weights.release(r);
+    *b = RigBinding();
+    return FRT_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,173 @@
+// frt_animation.hpp — the arithmetic of an animated rig (include/frt.h: frt_rig_evaluate, frt_renderer_animate; DESIGN.md §11, "Animation"): sampling a
+// channel at a time, the local matrix of a node, the global matrices down the hierarchy, the joint palette. Every function here is FRT_HD and is the one
+// text the host form (frt_animation.cpp) and the kernel (frt_animation.hip) both run under the library's contract flags: f32, no contraction, no
+// hand-written fma, rcpf_ / rsqrt_exact / sincosf_ / mul(m4, m4) of frt_math.hpp and acosf_ below.
+//
+// A rig is ONE block of 32-bit words (RigHeader in front, every table at a word offset from the block's start), so the device copy is the host block,
+// byte for byte, and both forms read it through the same accessors. Nodes are stored by depth (level 0: the roots), parents in front of their children.
+#pragma once
+#include "frt_math.hpp"
+
+namespace frt {
+
+enum { kRigPathTranslation = 0, kRigPathRotation = 1, kRigPathScale = 2, kRigPathWeights = 3 };      // (frt.h: FRT_RIG_PATH_*)
+enum { kRigStep = 0, kRigLinear = 1, kRigCubic = 2 };                                                 // (frt.h: FRT_RIG_*)
+static const uint32_t kRigNone = 0xFFFFFFFFu;
+
+// acos in the style of frt_math.hpp's sincosf_ (it lives here and not there because the frame kernels' translation unit includes that header, and its
+// text is what the committed counter profile is keyed on): Cephes' asinf polynomial. |x| <= 0.5: pi/2 - asin(x); above: 2 asin(sqrt((1 - |x|) / 2)),
+// mirrored for x < 0. |x| > 1 is taken as 1; NaN stays NaN. Built from +, -, * and sqrtf_ only (no libm call), so the host and the device give the same
+// bits. Against float64 over [-1, 1]: at most 1.25 ulp (tests/test_animation.py; profiles/animation_f64.md).
+FRT_HD float acosf_(float x) {
+    const float a = fminn(fabsf_(x), 1.0f);
+    const bool big = a > 0.5f;
+    const float z = big ? (1.0f - a) * 0.5f : a * a;
+    const float s = big ? sqrtf_(z) : a;
+    float p = 4.2163199048e-2f;
+    p = p * z + 2.4181311049e-2f;
+    p = p * z + 4.5470025998e-2f;
+    p = p * z + 7.4953002686e-2f;
+    p = p * z + 1.6666752422e-1f;
+    const float r = s + s * z * p;      // asin(s)
+    const float pos = big ? r + r : 1.57079637050628662109375f - r;      // acos(|x|)
+    if (x != x) return x;
+    return x < 0.0f ? 3.1415927410125732421875f - pos : pos;
+}
+
+// Word offsets into the block. parent [N] (kRigNone: a root; else a smaller index), kind [N] (1: a matrix node), rest [16 N] (a matrix node: its matrix,
+// column-major; else translation xyz, 0, rotation xyzw, scale xyz, 0, and four unused words), level_begin [nlevels + 1], joint_node [J],
+// inv_bind [16 J], def_weights [T], clips [4 nclips] (RigClip), channels [8 nchannels] (RigChannel), then per clip its node table [3 N] (the channel of
+// each node's translation, rotation and scale, or kRigNone) and the keys.
+struct RigHeader {
+    uint32_t words, nnodes, njoints, ntargets, nclips, nlevels, nchannels;
+    uint32_t parent, kind, rest, level_begin, joint_node, inv_bind, def_weights, clips, channels;
+};
+struct RigClip { uint32_t node_table, weights_channel, pad0, pad1; };
+struct RigChannel { uint32_t node, path, interp, nkeys, times, values, width, pad; };
+
+struct RigView {      // (the records are copied out of the word block: no struct is read through a cast pointer)
+    const uint32_t* w;
+    FRT_HD RigHeader h() const { RigHeader r; __builtin_memcpy(&r, w, sizeof(r)); return r; }
+    FRT_HD const float* f(uint32_t off) const { return reinterpret_cast<const float*>(w + off); }
+    FRT_HD RigClip clip(uint32_t c) const { RigClip r; __builtin_memcpy(&r, w + h().clips + 4u * c, sizeof(r)); return r; }
+    FRT_HD RigChannel channel(uint32_t c) const { RigChannel r; __builtin_memcpy(&r, w + h().channels + 8u * c, sizeof(r)); return r; }
+};
+
+// Where `t` lies among the K >= 1 strictly increasing key times: `k` the key, `between` false when the result is key k itself (t at or before the first
+// key, at or behind the last one, or exactly at key k), else u in (0, 1) and dt = times[k + 1] - times[k] for the interval [k, k + 1].
+struct RigKey { uint32_t k; bool between; float u, dt; };
+FRT_HD RigKey rig_find_key(const float* times, uint32_t K, float t) {
+    RigKey r; r.k = 0u; r.between = false; r.u = 0.0f; r.dt = 0.0f;
+    if (t <= times[0]) return r;
+    if (t >= times[K - 1u]) { r.k = K - 1u; return r; }
+    uint32_t lo = 0u, hi = K - 1u;      // times[lo] <= t < times[hi]
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (times[mid] <= t) lo = mid; else hi = mid; }
+    r.k = lo;
+    if (t == times[lo]) return r;
+    r.between = true;
+    r.dt = times[lo + 1u] - times[lo];
+    r.u = (t - times[lo]) / r.dt;
+    return r;
+}
+// glTF's cubic Hermite spline over one interval: values v0, v1, out-tangent b0 of the first key and in-tangent a1 of the second, tangents scaled by dt.
+FRT_HD float rig_hermite(float v0, float b0, float v1, float a1, float u, float dt) {
+    const float u2 = u * u, u3 = u2 * u;
+    const float h00 = (2.0f * u3 - 3.0f * u2) + 1.0f, h10 = (u3 - 2.0f * u2) + u, h01 = 3.0f * u2 - 2.0f * u3, h11 = u3 - u2;
+    return ((h00 * v0 + (dt * h10) * b0) + h01 * v1) + (dt * h11) * a1;
+}
+// Component c of a channel of `width` components at the place `key`. The values of a STEP or LINEAR channel are [K][width]; those of a CUBICSPLINE
+// channel [K][in-tangent | value | out-tangent][width].
+FRT_HD float rig_sample_component(const float* v, uint32_t width, uint32_t interp, RigKey key, uint32_t c) {
+    if (interp == (uint32_t)kRigCubic) {
+        const float* p = v + (size_t)3u * key.k * width;
+        if (!key.between) return p[width + c];
+        return rig_hermite(p[width + c], p[2u * width + c], p[4u * width + c], p[3u * width + c], key.u, key.dt);
+    }
+    const float* p = v + (size_t)key.k * width;
+    if (!key.between || interp == (uint32_t)kRigStep) return p[c];
+    return mixf(p[c], p[width + c], key.u);
+}
+FRT_HD float rig_dot4(f4 a, f4 b) { return ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w; }
+// Spherical interpolation of two rotations the short way round; nearly parallel ones (d > 0.9995) are mixed component-wise and normalised.
+FRT_HD f4 rig_slerp(f4 q0, f4 q1, float u) {
+    float d = rig_dot4(q0, q1);
+    if (d < 0.0f) { q1 = mk4(-q1.x, -q1.y, -q1.z, -q1.w); d = -d; }
+    if (d > 0.9995f) {
+        const f4 q = mk4(mixf(q0.x, q1.x, u), mixf(q0.y, q1.y, u), mixf(q0.z, q1.z, u), mixf(q0.w, q1.w, u));
+        return q * rsqrt_exact(rig_dot4(q, q));
+    }
+    const float th = acosf_(d);
+    float s, c, s0, s1;
+    sincosf_(th, s, c);
+    const float inv = rcpf_(s);
+    sincosf_((1.0f - u) * th, s0, c);
+    sincosf_(u * th, s1, c);
+    return q0 * (s0 * inv) + q1 * (s1 * inv);
+}
+FRT_HD f4 rig_sample_rotation(const float* v, uint32_t interp, RigKey key) {
+    if (interp == (uint32_t)kRigLinear && key.between) {
+        const float* p = v + (size_t)4u * key.k;
+        return rig_slerp(mk4(p[0], p[1], p[2], p[3]), mk4(p[4], p[5], p[6], p[7]), key.u);
+    }
+    const f4 q = mk4(rig_sample_component(v, 4u, interp, key, 0u), rig_sample_component(v, 4u, interp, key, 1u),
+                     rig_sample_component(v, 4u, interp, key, 2u), rig_sample_component(v, 4u, interp, key, 3u));
+    if (interp == (uint32_t)kRigCubic && key.between) return q * rsqrt_exact(rig_dot4(q, q));
+    return q;
+}
+// T * R * S: the columns of the rotation matrix (the nine products of the quaternion, each written once) scaled by s, the translation in the last column.
+FRT_HD m4 rig_trs_matrix(f3 t, f4 q, f3 s) {
+    const float x2 = q.x + q.x, y2 = q.y + q.y, z2 = q.z + q.z;
+    const float xx = q.x * x2, xy = q.x * y2, xz = q.x * z2, yy = q.y * y2, yz = q.y * z2, zz = q.z * z2, wx = q.w * x2, wy = q.w * y2, wz = q.w * z2;
+    m4 m;
+    m.c[0] = mk4((1.0f - (yy + zz)) * s.x, (xy + wz) * s.x, (xz - wy) * s.x, 0.0f);
+    m.c[1] = mk4((xy - wz) * s.y, (1.0f - (xx + zz)) * s.y, (yz + wx) * s.y, 0.0f);
+    m.c[2] = mk4((xz + wy) * s.z, (yz - wx) * s.z, (1.0f - (xx + yy)) * s.z, 0.0f);
+    m.c[3] = mk4(t.x, t.y, t.z, 1.0f);
+    return m;
+}
+// The local matrix of node n under clip `clip` at time t: a matrix node's matrix; else T * R * S with every path the clip has a channel for sampled and
+// the others at rest.
+FRT_HD m4 rig_local_matrix(RigView v, uint32_t clip, uint32_t n, float t) {
+    const RigHeader h = v.h();
+    const float* rest = v.f(h.rest) + (size_t)16u * n;
+    if (v.w[h.kind + n]) return load_m4(rest);
+    f3 tr = mk3(rest[0], rest[1], rest[2]), sc = mk3(rest[8], rest[9], rest[10]);
+    f4 q = mk4(rest[4], rest[5], rest[6], rest[7]);
+    const uint32_t* of = v.w + v.clip(clip).node_table + (size_t)3u * n;
+    if (of[0] != kRigNone) {
+        const RigChannel ch = v.channel(of[0]);
+        const RigKey key = rig_find_key(v.f(ch.times), ch.nkeys, t);
+        tr = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
+                 rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
+    }
+    if (of[1] != kRigNone) {
+        const RigChannel ch = v.channel(of[1]);
+        q = rig_sample_rotation(v.f(ch.values), ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t));
+    }
+    if (of[2] != kRigNone) {
+        const RigChannel ch = v.channel(of[2]);
+        const RigKey key = rig_find_key(v.f(ch.times), ch.nkeys, t);
+        sc = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
+                 rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
+    }
+    return rig_trs_matrix(tr, q, sc);
+}
+// Morph weight c: the clip's weights channel sampled, or the default weight.
+FRT_HD float rig_morph_weight(RigView v, uint32_t clip, uint32_t c, float t) {
+    const uint32_t wc = v.clip(clip).weights_channel;
+    if (wc == kRigNone) return v.f(v.h().def_weights)[c];
+    const RigChannel ch = v.channel(wc);
+    return rig_sample_component(v.f(ch.values), ch.width, ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t), c);
+}
+
+} // namespace frt
+
+// The host side of a rig (frt_animation.cpp): the block and what frt_rig_clip_info returns.
+#include <string>
+#include <vector>
+struct frt_rig {
+    std::vector<uint32_t> words;
+    std::vector<std::string> clip_names;
+    std::vector<float> clip_durations;
+    frt::RigView view() const { frt::RigView v; v.w = words.data(); return v; }
+};

@@ -10,6 +10,7 @@
 // reference substitutes for formats it does not handle (loader.rs:35-44), with a warning.
 #include "frt_loader.hpp"
 #include <zlib.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -748,6 +749,174 @@ bool texture_source(const Doc& d, const JVal* info, uint32_t& image_index, std::
     image_index = (uint32_t)src;
     return true;
 }
+
+// ---- the rig ("Animation"): skin attributes and morph targets of a primitive, then nodes, skins and animations ----
+// Floats or normalized integers by glTF's rule (u8: x / 255, u16: x / 65535, i8: max(x / 127, -1), i16: max(x / 32767, -1)), any element type.
+bool read_any_floats(const Acc& a, std::vector<float>& out, std::string& err, const char* what) {
+    out.resize(a.count * (size_t)a.ncomp);
+    for (size_t i = 0; i < a.count; ++i) {
+        const uint8_t* p = a.base + i * a.stride;
+        for (int c = 0; c < a.ncomp; ++c) {
+            float v;
+            if (a.comp == 5126) v = rd<float>(p + 4 * c);
+            else if (!a.normalized) { err = std::string(what) + ": integer components must be normalized"; return false; }
+            else if (a.comp == 5121) v = (float)p[c] / 255.0f;
+            else if (a.comp == 5123) v = (float)rd<uint16_t>(p + 2 * c) / 65535.0f;
+            else if (a.comp == 5120) v = std::max((float)rd<int8_t>(p + c) / 127.0f, -1.0f);
+            else if (a.comp == 5122) v = std::max((float)rd<int16_t>(p + 2 * c) / 32767.0f, -1.0f);
+            else { err = std::string(what) + ": unsupported component type"; return false; }
+            out[i * (size_t)a.ncomp + (size_t)c] = v;
+        }
+    }
+    return true;
+}
+// JOINTS_0 / WEIGHTS_0 and targets[*].POSITION of one primitive with nv vertices; `mesh` gives the default weights.
+bool read_primitive_rig(const Doc& d, const JVal& mesh, const JVal& prim, const JVal& attrs, size_t nv, LoadedModel::GeometryRig& r, std::vector<std::string>& warnings, std::string& err) {
+    Acc a; std::vector<uint8_t> zeros;
+    const long long ji = attrs.integer("JOINTS_0", -1), wi = attrs.integer("WEIGHTS_0", -1);
+    if (ji >= 0 && wi >= 0) {
+        if (!get_accessor(d, ji, a, zeros, err)) return false;
+        if (a.ncomp != 4 || (a.comp != 5121 && a.comp != 5123) || a.count != nv) { err = "JOINTS_0 must be one unsigned byte or short VEC4 per vertex"; return false; }
+        r.joints.resize(nv * 4);
+        for (size_t i = 0; i < nv; ++i) for (int c = 0; c < 4; ++c) {
+            const uint8_t* p = a.base + i * a.stride;
+            r.joints[i * 4 + (size_t)c] = a.comp == 5121 ? (uint16_t)p[c] : rd<uint16_t>(p + 2 * c);
+        }
+        std::vector<uint8_t> zeros_w;
+        if (!get_accessor(d, wi, a, zeros_w, err)) return false;
+        if (a.ncomp != 4 || a.count != nv) { err = "WEIGHTS_0 must be one VEC4 per vertex"; return false; }
+        if (a.comp != 5126 && !a.normalized) { err = "WEIGHTS_0: integer components must be normalized"; return false; }
+        if (!read_floats(a, 4, true, r.weights, err, "WEIGHTS_0")) return false;
+    } else if (ji >= 0 || wi >= 0) warnings.push_back("a primitive has only one of JOINTS_0 and WEIGHTS_0: its skin attributes are ignored");
+    if (attrs.get("JOINTS_1") || attrs.get("WEIGHTS_1")) warnings.push_back("JOINTS_1 / WEIGHTS_1 and beyond are ignored: four influences per vertex");
+    const auto& targets = prim.arr("targets");
+    if (targets.size() > FRT_MAX_MORPH_TARGETS) { warnings.push_back("a primitive has more than FRT_MAX_MORPH_TARGETS morph targets: they are ignored"); return true; }
+    std::vector<float> f;
+    for (const JVal& t : targets) {
+        const long long pi = t.integer("POSITION", -1);
+        if (pi < 0) { f.assign(nv * 3, 0.0f); }      // a target without POSITION moves nothing
+        else {
+            std::vector<uint8_t> z;
+            if (!get_accessor(d, pi, a, z, err)) return false;
+            if (a.comp != 5126 || a.count != nv) { err = "a morph target's POSITION must be one float VEC3 per vertex"; return false; }
+            if (!read_floats(a, 3, false, f, err, "target POSITION")) return false;
+        }
+        r.deltas.insert(r.deltas.end(), f.begin(), f.end());
+    }
+    r.ntargets = (uint32_t)targets.size();
+    r.default_weights.assign(r.ntargets, 0.0f);
+    const auto& w = mesh.arr("weights");
+    for (size_t k = 0; k < w.size() && k < r.ntargets; ++k) if (w[k].is_num()) r.default_weights[k] = (float)w[k].n;
+    return true;
+}
+// Nodes (parents first), skins and animations. False with a message: a cycle in the node graph, a joint that is not a node, sampler times that are not
+// finite and strictly increasing, an output count that does not match. What is merely unsupported is skipped with a warning.
+bool read_rig(const Doc& d, LoadedModel& out, std::string& err) {
+    const auto& jn = d.root.arr("nodes");
+    const size_t N = jn.size();
+    std::vector<int> parent(N, -1);
+    for (size_t i = 0; i < N; ++i)
+        for (const JVal& c : jn[i].arr("children")) {
+            if (!c.is_num() || c.n < 0 || (size_t)c.n >= N) { err = "node " + std::to_string(i) + " has a child that is not a node"; return false; }
+            const size_t k = (size_t)c.n;
+            if (k == i || parent[k] >= 0) { err = "the node graph has a cycle or a node with two parents (node " + std::to_string(k) + ")"; return false; }
+            parent[k] = (int)i;
+        }
+    std::vector<uint32_t> order;      // breadth-first from the roots, in document order
+    out.node_of_document.assign(N, 0xFFFFFFFFu);
+    for (size_t i = 0; i < N; ++i) if (parent[i] < 0) { out.node_of_document[i] = (uint32_t)order.size(); order.push_back((uint32_t)i); }
+    for (size_t at = 0; at < order.size(); ++at)
+        for (const JVal& c : jn[order[at]].arr("children")) { out.node_of_document[(size_t)c.n] = (uint32_t)order.size(); order.push_back((uint32_t)c.n); }
+    if (order.size() != N) { err = "the node graph has a cycle"; return false; }      // (a cycle has no root: its nodes are never reached)
+    auto floats = [](const JVal& j, const char* key, float* dst, size_t n) {
+        const auto& a = j.arr(key);
+        if (a.size() != n) return false;
+        for (size_t k = 0; k < n; ++k) dst[k] = a[k].is_num() ? (float)a[k].n : dst[k];
+        return true;
+    };
+    for (uint32_t di : order) {
+        const JVal& j = jn[di];
+        LoadedModel::Node n;
+        n.doc_index = di;
+        n.parent = parent[di] < 0 ? -1 : (int)out.node_of_document[(size_t)parent[di]];
+        n.has_matrix = floats(j, "matrix", n.matrix, 16);
+        floats(j, "translation", n.trs, 3); floats(j, "rotation", n.trs + 3, 4); floats(j, "scale", n.trs + 7, 3);
+        n.mesh = (int)j.integer("mesh", -1); n.skin = (int)j.integer("skin", -1);
+        out.nodes.push_back(n);
+    }
+    // skins
+    for (const JVal& js : d.root.arr("skins")) {
+        LoadedModel::Skin s;
+        for (const JVal& c : js.arr("joints")) {
+            if (!c.is_num() || c.n < 0 || (size_t)c.n >= N) { err = "skin " + std::to_string(out.skins.size()) + " has a joint that is not a node"; return false; }
+            s.joints.push_back(out.node_of_document[(size_t)c.n]);
+        }
+        const size_t J = s.joints.size();
+        if (J == 0 || J > 0x10000u) { err = "skin " + std::to_string(out.skins.size()) + " must have 1 to 65536 joints"; return false; }
+        const long long ib = js.integer("inverseBindMatrices", -1);
+        if (ib >= 0) {
+            Acc a; std::vector<uint8_t> zeros;
+            if (!get_accessor(d, ib, a, zeros, err)) return false;
+            if (a.comp != 5126 || a.ncomp != 16 || a.count < J) { err = "inverseBindMatrices must be one float MAT4 per joint"; return false; }
+            a.count = J;
+            if (!read_floats(a, 16, false, s.inverse_bind, err, "inverseBindMatrices")) return false;
+        } else {
+            s.inverse_bind.assign(16 * J, 0.0f);
+            for (size_t k = 0; k < J; ++k) for (int c = 0; c < 4; ++c) s.inverse_bind[16 * k + 5 * (size_t)c] = 1.0f;
+        }
+        out.skins.push_back(std::move(s));
+    }
+    // which skin a geometry is under: the skin of the first node that carries its mesh
+    for (LoadedModel::GeometryRig& g : out.geometry_rigs)
+        for (const LoadedModel::Node& n : out.nodes)
+            if (n.mesh == g.mesh && n.skin >= 0 && (size_t)n.skin < out.skins.size()) { g.skin = n.skin; break; }
+    // animations
+    for (const JVal& ja : d.root.arr("animations")) {
+        LoadedModel::Animation an;
+        an.name = ja.str("name");
+        const std::string where = "animation " + std::to_string(out.animations.size());
+        const auto& samplers = ja.arr("samplers");
+        std::vector<uint8_t> seen(3 * N + 1, 0);
+        for (const JVal& jc : ja.arr("channels")) {
+            const JVal* target = jc.get("target");
+            const long long si = jc.integer("sampler", -1), node = target ? target->integer("node", -1) : -1;
+            const std::string path = target ? target->str("path") : "";
+            const int p = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : path == "weights" ? 3 : -1;
+            if (p < 0 || node < 0 || (size_t)node >= N || si < 0 || (size_t)si >= samplers.size()) { out.warnings.push_back(where + ": a channel without a known path, node or sampler is skipped"); continue; }
+            const LoadedModel::Node& tn = out.nodes[out.node_of_document[(size_t)node]];
+            if (p < 3 && tn.has_matrix) { out.warnings.push_back(where + ": a channel on a node given as a matrix is skipped"); continue; }
+            uint32_t width = p == 1 ? 4u : 3u;
+            if (p == 3) {
+                width = 0;
+                for (const LoadedModel::GeometryRig& g : out.geometry_rigs) if (g.mesh == tn.mesh && g.ntargets) { width = g.ntargets; break; }
+                if (!width) { out.warnings.push_back(where + ": a weights channel on a node without morph targets is skipped"); continue; }
+            }
+            uint8_t& dup = seen[p == 3 ? 3 * N : 3 * (size_t)node + (size_t)p];
+            if (dup) { out.warnings.push_back(where + ": a second channel for the same target is skipped"); continue; }
+            const JVal& js = samplers[(size_t)si];
+            const std::string interp = js.str("interpolation", "LINEAR");
+            LoadedModel::Channel ch;
+            ch.node = out.node_of_document[(size_t)node]; ch.path = (uint32_t)p;
+            if (interp == "STEP") ch.interpolation = 0; else if (interp == "LINEAR") ch.interpolation = 1; else if (interp == "CUBICSPLINE") ch.interpolation = 2;
+            else { out.warnings.push_back(where + ": interpolation " + interp + " is not known: the channel is skipped"); continue; }
+            Acc a; std::vector<uint8_t> z0, z1;
+            if (!get_accessor(d, js.integer("input", -1), a, z0, err)) return false;
+            if (a.comp != 5126 || a.ncomp != 1 || a.count == 0) { err = where + ": a sampler's input must be a non-empty float SCALAR accessor"; return false; }
+            if (!read_floats(a, 1, false, ch.times, err, "sampler input")) return false;
+            for (size_t k = 0; k < ch.times.size(); ++k)
+                if (!std::isfinite(ch.times[k]) || (k && !(ch.times[k] > ch.times[k - 1]))) { err = where + ": sampler times must be finite and strictly increasing"; return false; }
+            if (!get_accessor(d, js.integer("output", -1), a, z1, err)) return false;
+            if (!read_any_floats(a, ch.values, err, "sampler output")) return false;
+            const size_t want = ch.times.size() * width * (ch.interpolation == 2 ? 3u : 1u);
+            if (ch.values.size() != want) { err = where + ": a sampler's output has " + std::to_string(ch.values.size()) + " components, its input and path ask for " + std::to_string(want); return false; }
+            for (float v : ch.values) if (!std::isfinite(v)) { err = where + ": a sampler output value is not finite"; return false; }
+            dup = 1;
+            an.channels.push_back(std::move(ch));
+        }
+        out.animations.push_back(std::move(an));
+    }
+    return true;
+}
 } // namespace
 
 bool load_gltf(const std::string& path, LoadedModel& out, std::string& err) {
@@ -821,7 +990,9 @@ bool load_gltf(const std::string& path, LoadedModel& out, std::string& err) {
     }
     if (out.materials.empty()) out.materials.push_back(MaterialBuilder(1, 1, 1, 1));   // loader.rs:101-104
     // 2. meshes (loader.rs:106-178)
+    int mesh_index = -1;
     for (const JVal& mesh : d.root.arr("meshes")) {
+        ++mesh_index;
         for (const JVal& prim : mesh.arr("primitives")) {
             long long mode = prim.integer("mode", 4);
             if (mode != 4) { err = "primitive mode " + std::to_string(mode) + ": only TRIANGLES (4) is supported"; return false; }
@@ -870,12 +1041,16 @@ bool load_gltf(const std::string& path, LoadedModel& out, std::string& err) {
             } else { g.indices.resize(nv); for (size_t i = 0; i < nv; ++i) g.indices[i] = (uint32_t)i; }   // loader.rs:160-163
             if (g.indices.empty() || g.indices.size() % 3 != 0) { err = "index count is not a positive multiple of 3"; return false; }
             for (uint32_t v : g.indices) if (v >= nv) { err = "index out of range"; return false; }
+            LoadedModel::GeometryRig gr;
+            gr.mesh = mesh_index;
+            if (!read_primitive_rig(d, mesh, prim, *attrs, nv, gr, out.warnings, err)) return false;
+            out.geometry_rigs.push_back(std::move(gr));
             out.geometries.push_back(std::move(g));
             long long mi = prim.integer("material", 0);
             out.material_indices.push_back(mi < 0 ? 0u : (uint32_t)mi);   // primitive.material().index().unwrap_or(0)
         }
     }
-    return true;
+    return read_rig(d, out, err);      // 3. nodes, skins, animations (an extension: DESIGN.md §11, "Animation")
 }
 
 // ================================================================================================ OBJ (extension)

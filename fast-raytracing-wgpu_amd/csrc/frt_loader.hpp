@@ -16,6 +16,26 @@ struct LoadedModel {                              // the 4-tuple load_gltf retur
     std::vector<std::vector<uint8_t>> images;     // RGBA8, TEXTURE_WIDTH x TEXTURE_HEIGHT (1024 x 1024) each
     std::vector<uint32_t> material_indices;       // per geometry: index into `materials` (0 when the primitive names none)
     std::vector<std::string> warnings;            // what the reference prints (unsupported image format, …)
+    // The rig of a glTF document ("Animation"; an extension: the reference loads none of it). All of it is empty for a document
+    // without skins, morph targets and animations, and for OBJ.
+    struct GeometryRig {                          // per geometry, in the geometry's vertex order
+        std::vector<uint16_t> joints;             // JOINTS_0 [n][4], empty: no skin attributes
+        std::vector<float> weights;               // WEIGHTS_0 [n][4]
+        int skin = -1;                            // the skin the (first) node that carries this geometry's mesh names, or -1
+        uint32_t ntargets = 0;
+        std::vector<float> deltas;                // targets[*].POSITION [T][n][3]
+        std::vector<float> default_weights;       // the mesh's `weights` [T] (zeros when absent)
+        int mesh = -1;                            // document index of the mesh
+    };
+    struct Node { int parent = -1; float trs[10] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1}; bool has_matrix = false; float matrix[16] = {}; int mesh = -1, skin = -1; uint32_t doc_index = 0; };
+    struct Skin { std::vector<uint32_t> joints; std::vector<float> inverse_bind; };      // joints: stored node indices; inverse_bind [16 J]
+    struct Channel { uint32_t node = 0, path = 0, interpolation = 1; std::vector<float> times, values; };      // node: stored index; values by glTF's layout
+    struct Animation { std::string name; std::vector<Channel> channels; };
+    std::vector<GeometryRig> geometry_rigs;       // one per geometry (glTF)
+    std::vector<Node> nodes;                      // parents first
+    std::vector<uint32_t> node_of_document;       // document node index -> index into `nodes`
+    std::vector<Skin> skins;
+    std::vector<Animation> animations;
 };
 
 bool load_gltf(const std::string& path, LoadedModel& out, std::string& err);   // .gltf (+ .bin / data: URIs) and .glb

@@ -236,7 +236,7 @@ void frt_renderer_destroy(frt_renderer* r) {
     for (hipEvent_t e : r->event_pool) (void)hipEventDestroy(e);
     for (void* p : r->scene_allocs) (void)hipFree(p);
     rebuild_release(r->rbt.scratch);
-    for (Staging* st : {&r->rf.rec, &r->rf.def, &r->rf.xf.up, &r->rf.skin_up, &r->rf.morph_up, &r->qry, &r->look, &r->ie.rec, &r->pools.up, &r->rm.tab}) st->release();
+    for (Staging* st : {&r->rf.rec, &r->rf.def, &r->rf.xf.up, &r->rf.skin_up, &r->rf.morph_up, &r->qry, &r->look, &r->ie.rec, &r->pools.up, &r->rm.tab, &r->rig_up}) st->release();
     if (r->own_arena && r->arena) (void)hipFree(r->arena);
     if (r->extras) (void)hipFree(r->extras);
     if (r->d_counters) (void)hipFree(r->d_counters);

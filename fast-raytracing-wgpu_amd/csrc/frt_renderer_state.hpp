@@ -121,6 +121,7 @@ struct OwnedBuf {
     // This buffer enters the replica as `live`; the one that leaves (with room for `live_bytes`) is what the next call builds into.
     template <class T> void trade(const T*& live, size_t live_bytes) { void* was = const_cast<T*>(live); live = static_cast<const T*>(p); p = was; bytes = live_bytes; }
     template <class T> T* as() const { return static_cast<T*>(p); }
+    void release(frt_renderer* r);         // behind a wait for the main stream: the buffer is freed (nothing if there is none)
 };
 
 // What frt_renderer_set_instance_transforms needs beside the scene replica, made at create. Device: the object-space positions of every
@@ -228,6 +229,16 @@ struct RemoveState {
     Staging tab;                           // the tables of one call: old -> new ids and removed spans
 };
 
+// What frt_renderer_bind_rig leaves with the renderer ("Animation"; frt_animation.hip): the rig's block on the device, the palette
+// [4 njoints] float4 and the weights [ntargets] its kernel writes, and the meshes frt_renderer_animate poses. A binding's number is its index; an unbound
+// one stays in the list, empty (live == false).
+struct RigBinding {
+    OwnedBuf rig, palette, weights;
+    uint32_t njoints = 0, ntargets = 0, nclips = 0;
+    std::vector<uint32_t> mesh_ids;
+    bool live = false;
+};
+
 struct frt_renderer {
     int device = 0;
     hipStream_t stream = nullptr;          // the chain: T-merge -> spatial pixels -> spatial continuations (and everything, without FRT_FLAG_PIPELINE)
@@ -300,6 +311,8 @@ struct frt_renderer {
     Staging qry;
     // The material, light and texture edits: the pinned block of one call and, for frt_renderer_set_instance_materials, its records on the device.
     Staging look;
+    std::vector<RigBinding> rigs;          // frt_renderer_bind_rig
+    Staging rig_up;                        // the pinned block a rig is uploaded through
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };

@@ -172,6 +172,12 @@ int OwnedBuf::ensure(frt_renderer* r, size_t need) {
     bytes = need;
     return FRT_OK;
 }
+void OwnedBuf::release(frt_renderer* r) {
+    if (!p) return;
+    (void)hipStreamSynchronize(r->stream);
+    scene_free(r, p);
+    p = nullptr; bytes = 0;
+}
 
 uint32_t frt::pool_count(const frt_renderer* r, int pool) {
     const RefitState& f = r->rf;
@@ -1505,6 +1511,13 @@ int frt_renderer_remove_meshes(frt_renderer* r, uint32_t n, const uint32_t* ids)
             list->resize(old_meshes);
             for (uint32_t g : gone) if ((rc = drop_binding(r, *list, g))) return rc;
             remove_elements(*list, gone);
+        }
+        // a rig binding follows its meshes to their new ids; one that names a mesh that left is unbound (animate then refuses its number)
+        for (RigBinding& b : r->rigs) {
+            if (!b.live) continue;
+            bool lost = false;
+            for (uint32_t& m : b.mesh_ids) { if (m >= old_meshes || map[m] == kGone) lost = true; else m = map[m]; }
+            if (lost) { b.rig.release(r); b.palette.release(r); b.weights.release(r); b = RigBinding(); }
         }
         drop_transform_tables(r, false);
         for (InstanceRec& in : f.inst) in.mesh_id = map[in.mesh_id];

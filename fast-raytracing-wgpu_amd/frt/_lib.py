@@ -58,6 +58,21 @@ class RayHit(C.Structure):          # include/frt.h: frt_ray_hit
                 ("primitive", C.c_uint32), ("front", C.c_uint32)]
 
 
+class RigChannel(C.Structure):      # include/frt.h: frt_rig_channel
+    _fields_ = [("node", C.c_uint32), ("path", C.c_uint32), ("interpolation", C.c_uint32), ("nkeys", C.c_uint32), ("times", C.c_void_p), ("values", C.c_void_p)]
+
+
+class RigClip(C.Structure):         # include/frt.h: frt_rig_clip
+    _fields_ = [("name", C.c_char_p), ("nchannels", C.c_uint32), ("channels", C.POINTER(RigChannel))]
+
+
+class RigDesc(C.Structure):         # include/frt.h: frt_rig_desc
+    _fields_ = [("nnodes", C.c_uint32), ("parents", C.c_void_p), ("rest_trs", C.c_void_p), ("has_matrix", C.c_void_p), ("matrices", C.c_void_p),
+                ("njoints", C.c_uint32), ("joint_nodes", C.c_void_p), ("inverse_bind", C.c_void_p),
+                ("ntargets", C.c_uint32), ("default_weights", C.c_void_p),
+                ("nclips", C.c_uint32), ("clips", C.POINTER(RigClip))]
+
+
 assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 32
 assert C.sizeof(VertexAttr) == 32 and C.sizeof(Material) == 64 and C.sizeof(Light) == 64 and C.sizeof(CameraUniform) == 288
 
@@ -74,6 +89,9 @@ QUERY_DEVICE = 1                       # include/frt.h: FRT_QUERY_DEVICE
 QUERY_MAX_RAYS = 1 << 26
 DEFORM_RECOMPUTE_NORMALS, DEFORM_DEVICE = 1, 2      # include/frt.h: FRT_DEFORM_*
 TRANSFORM_DEVICE = 1                                # include/frt.h: FRT_TRANSFORM_DEVICE
+MAX_RIG_NODES = 1024                                # include/frt.h: FRT_MAX_RIG_NODES
+RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}      # include/frt.h: FRT_RIG_PATH_*
+RIG_INTERPOLATIONS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}              # include/frt.h: FRT_RIG_*
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
 PHASE_SPATIAL_INNER, PHASE_SPATIAL_EDGE = 16, 32
 BUF_GPOS, BUF_GNORMAL, BUF_GALBEDO, BUF_GMOTION, BUF_RESERVOIR, BUF_RAW, BUF_DISPLAY, BUF_ACCUM, BUF_CANDIDATE = range(9)
@@ -179,6 +197,26 @@ SYMBOLS = {
     "frt_renderer_set_mesh_pose_ex": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _U32]),
     "frt_renderer_set_mesh_poses": (C.c_int, [_P, _U32, _P, _P, _U32, _P, _U32, _U32]),
     "frt_renderer_deform_rejects": (C.c_int, [_P, C.POINTER(_U32)]),
+    "frt_rig_create": (_P, [C.POINTER(RigDesc)]),
+    "frt_rig_destroy": (None, [_P]),
+    "frt_rig_from_model": (_P, [_P, C.c_int32]),
+    "frt_model_rig_counts": (C.c_int, [_P, C.POINTER(_U32 * 3)]),
+    "frt_model_geometry_rig": (C.c_int, [_P, _U32, C.POINTER(_U32 * 4)]),
+    "frt_model_geometry_skin_get": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_model_geometry_targets_get": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_model_nodes_get": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "frt_model_skin_get": (C.c_int, [_P, _U32, C.POINTER(_U32), _P, _P]),
+    "frt_model_animation_info": (C.c_int, [_P, _U32, C.POINTER(C.c_char_p), C.POINTER(_U32)]),
+    "frt_model_channel_info": (C.c_int, [_P, _U32, _U32, C.POINTER(_U32 * 5)]),
+    "frt_model_channel_get": (C.c_int, [_P, _U32, _U32, _P, _P]),
+    "frt_rig_counts": (C.c_int, [_P, C.POINTER(_U32 * 4)]),
+    "frt_rig_clip_info": (C.c_int, [_P, _U32, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]),
+    "frt_rig_evaluate": (C.c_int, [_P, _U32, C.c_float, _P, _P]),
+    "frt_acosf": (None, [_U32, _P, _P]),
+    "frt_renderer_bind_rig": (C.c_int, [_P, _P, _P, _U32, C.POINTER(_U32)]),
+    "frt_renderer_animate": (C.c_int, [_P, _U32, _U32, C.c_float, _U32]),
+    "frt_renderer_read_rig_pose": (C.c_int, [_P, _U32, _P, _P]),
+    "frt_renderer_unbind_rig": (C.c_int, [_P, _U32]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

@@ -1,0 +1,122 @@
+"""frt.Rig: a node hierarchy, a joint list and keyframed clips (include/frt.h: frt_rig_*; DESIGN.md section 11, "Animation"). The arithmetic is
+libfrt.so's: evaluate() is frt_rig_evaluate, the host specification of what Renderer.animate computes on the device."""
+import ctypes as C
+import numpy as np
+from ._lib import lib, check, FrtError, RigChannel, RigClip, RigDesc, RIG_PATHS, RIG_INTERPOLATIONS
+
+
+def _f32(a, shape, what):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.shape != shape:
+        raise FrtError(f"Rig: {what} must be shaped {list(shape)}, not {list(a.shape)}")
+    return a
+
+
+class Rig:
+    """Rig(parents, ...): nodes are given parents first (parents[n] is -1 or a smaller index).
+    translations [N, 3], rotations [N, 4] (x, y, z, w), scales [N, 3]: the rest values (default: identity). matrices: {node: column-major 4x4 as [16] or
+    [4, 4]} for nodes given as a matrix, which cannot be animated. joint_nodes [J] and inverse_bind [J, 16] or [J, 4, 4] (default: identities): the
+    skin. num_targets and default_weights [T]: the morph targets. clips: a sequence of (name, channels), a channel a dict with node, path
+    ("translation", "rotation", "scale", "weights"), interpolation ("STEP", "LINEAR", "CUBICSPLINE"), times [K] and values [K, width] (CUBICSPLINE:
+    [K, 3, width] as in-tangent, value, out-tangent), width 3, 4, 3 or T by path."""
+
+    def __init__(self, parents, translations=None, rotations=None, scales=None, matrices=None, joint_nodes=(), inverse_bind=None, num_targets=0,
+                 default_weights=None, clips=()):
+        par = np.ascontiguousarray(parents, np.int32).reshape(-1)
+        n = par.size
+        trs = np.zeros((n, 10), np.float32)
+        trs[:, 6] = 1.0
+        trs[:, 7:10] = 1.0
+        if translations is not None:
+            trs[:, 0:3] = _f32(translations, (n, 3), "translations")
+        if rotations is not None:
+            trs[:, 3:7] = _f32(rotations, (n, 4), "rotations")
+        if scales is not None:
+            trs[:, 7:10] = _f32(scales, (n, 3), "scales")
+        has = np.zeros(n, np.uint8)
+        mats = np.zeros((n, 16), np.float32)
+        for k, m in (matrices or {}).items():
+            if not 0 <= int(k) < n:
+                raise FrtError(f"Rig: matrices names node {k} of {n}")
+            has[int(k)] = 1
+            mats[int(k)] = _f32(np.asarray(m, np.float32).reshape(-1), (16,), "a node matrix")
+        joints = np.ascontiguousarray(joint_nodes, np.int64).reshape(-1)
+        if joints.size and (joints.min() < 0 or joints.max() > 0xFFFFFFFF):
+            raise FrtError("Rig: joint nodes must be unsigned 32-bit indices")
+        joints = joints.astype(np.uint32)
+        ib = None if inverse_bind is None else _f32(np.asarray(inverse_bind, np.float32).reshape(-1, 16), (joints.size, 16), "inverse_bind")
+        t = int(num_targets)
+        dw = None if default_weights is None else _f32(default_weights, (t,), "default_weights")
+        keep = [par, trs, has, mats, joints, ib, dw]      # (what the description points into, alive until frt_rig_create has copied it)
+        cclips = (RigClip * max(len(clips), 1))()
+        for c, (name, channels) in enumerate(clips):
+            cch = (RigChannel * max(len(channels), 1))()
+            for k, ch in enumerate(channels):
+                if ch["path"] not in RIG_PATHS or ch.get("interpolation", "LINEAR") not in RIG_INTERPOLATIONS:
+                    raise FrtError(f"Rig: clip {c}, channel {k}: unknown path or interpolation")
+                path, interp = RIG_PATHS[ch["path"]], RIG_INTERPOLATIONS[ch.get("interpolation", "LINEAR")]
+                times = np.ascontiguousarray(ch["times"], np.float32).reshape(-1)
+                width = (3, 4, 3, t)[path]
+                values = _f32(ch["values"], (times.size, 3, width) if interp == 2 else (times.size, width), f"clip {c}, channel {k}: values")
+                node = int(ch.get("node", 0))
+                if not 0 <= node <= 0xFFFFFFFF:
+                    raise FrtError(f"Rig: clip {c}, channel {k}: node must be an unsigned 32-bit index")
+                cch[k] = RigChannel(node, path, interp, times.size, times.ctypes.data, values.ctypes.data)
+                keep += [times, values]
+            cclips[c] = RigClip(str(name).encode(), len(channels), cch)
+            keep.append(cch)
+        d = RigDesc(n, par.ctypes.data, trs.ctypes.data, has.ctypes.data, mats.ctypes.data, joints.size, joints.ctypes.data if joints.size else None,
+                    ib.ctypes.data if ib is not None else None, t, dw.ctypes.data if dw is not None else None, len(clips), cclips)
+        h = lib().frt_rig_create(C.byref(d))
+        del keep
+        self._adopt(h, "frt_rig_create")
+
+    def _adopt(self, handle, call):
+        self._destroy = lib().frt_rig_destroy
+        self._h = handle
+        if not self._h:
+            raise FrtError(f"{call} failed: {lib().frt_last_error().decode()}")
+        counts = (C.c_uint32 * 4)()
+        check(lib().frt_rig_counts(self._h, C.byref(counts)))
+        self.num_nodes, self.num_joints, self.num_targets, self.num_clips = (int(x) for x in counts)
+
+    @classmethod
+    def from_model(cls, model, skin=0):
+        """The rig of skin `skin` of a loaded glTF document (frt.loader.Model; include/frt.h: frt_rig_from_model); skin=None: a morph-only rig."""
+        rig = cls.__new__(cls)
+        rig._adopt(lib().frt_rig_from_model(model._h, -1 if skin is None else int(skin)), "frt_rig_from_model")
+        return rig
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    @property
+    def clips(self):
+        """[(name, duration)] in clip order; the duration is the largest last key time of the clip's channels."""
+        out = []
+        for c in range(self.num_clips):
+            name, dur = C.c_char_p(), C.c_float()
+            check(lib().frt_rig_clip_info(self._h, c, C.byref(name), C.byref(dur)))
+            out.append((name.value.decode(), float(dur.value)))
+        return out
+
+    def clip_index(self, clip):
+        """A clip given by number or by name."""
+        if isinstance(clip, str):
+            names = [n for n, _ in self.clips]
+            if clip not in names:
+                raise FrtError(f"Rig: no clip named {clip!r} (clips: {names})")
+            return names.index(clip)
+        if not 0 <= int(clip) <= 0xFFFFFFFF:
+            raise FrtError("Rig: a clip is a name or an unsigned 32-bit index")
+        return int(clip)
+
+    def evaluate(self, clip, t):
+        """(palette [J, 16] float32 column-major or None for a rig without joints, weights [T] float32 or None for a rig without targets) of `clip` at
+        time `t` (include/frt.h: frt_rig_evaluate): what set_mesh_poses takes."""
+        pal = np.zeros((self.num_joints, 16), np.float32) if self.num_joints else None
+        w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
+        check(lib().frt_rig_evaluate(self._h, self.clip_index(clip), float(t), pal.ctypes.data if pal is not None else None, w.ctypes.data if w is not None else None))
+        return pal, w

@@ -375,6 +375,41 @@ class Renderer(_HostQueries, _SceneGrowth):
                                                                             w.data_ptr() if w is not None else None, w.shape[0] if w is not None else 0, flags),
                           *[x for x in (t, w) if x is not None])
 
+    # ---- animation (include/frt.h: frt_renderer_bind_rig and the three calls after it; DESIGN.md section 11, "Animation")
+    def bind_rig(self, rig, mesh_ids):
+        """Copy `rig` (frt.Rig) to the renderer's device and remember `mesh_ids`, every one of which already has the skin and / or the morph targets
+        the rig implies (set_mesh_skin with the rig's joint count, set_mesh_morph_targets with its target count). Returns the binding animate takes."""
+        ids, b = pose_batch_ids(mesh_ids), C.c_uint32()
+        check(lib().frt_renderer_bind_rig(self._h, rig._h, ids.ctypes.data, ids.size, C.byref(b)))
+        self._rigs = getattr(self, "_rigs", {})
+        self._rigs[int(b.value)] = rig      # (for its clip names and counts; the device copy does not depend on it)
+        return int(b.value)
+
+    def animate(self, binding, clip, t, normals="recompute"):
+        """Pose the binding's meshes under clip `clip` (a number, or a name of the bound rig) at time `t` between frames: one kernel evaluates the clip
+        into a palette and weights the renderer owns, bit for bit rig.evaluate(clip, t), and the call goes on as set_mesh_poses with those device
+        buffers. The host passes one float; nothing is read back. A pose that overflows rejects on the device: deform_rejects() counts it."""
+        check(lib().frt_renderer_animate(self._h, int(binding), self._bound_rig("animate", binding).clip_index(clip), float(t), deform_flags(normals)))
+
+    def _bound_rig(self, call, binding):
+        rig = getattr(self, "_rigs", {}).get(int(binding))
+        if rig is None:
+            raise FrtError(f"{call}: unknown rig binding {binding}")
+        return rig
+
+    def read_rig_pose(self, binding):
+        """(palette [J, 16] or None, weights [T] or None) as the binding's last animate left them on the device. Waits for the renderer's stream."""
+        rig = self._bound_rig("read_rig_pose", binding)
+        pal = np.zeros((rig.num_joints, 16), np.float32) if rig.num_joints else None
+        w = np.zeros(rig.num_targets, np.float32) if rig.num_targets else None
+        check(lib().frt_renderer_read_rig_pose(self._h, int(binding), pal.ctypes.data if pal is not None else None, w.ctypes.data if w is not None else None))
+        return pal, w
+
+    def unbind_rig(self, binding):
+        """Free the binding's device memory. Waits for the renderer's stream."""
+        check(lib().frt_renderer_unbind_rig(self._h, int(binding)))
+        getattr(self, "_rigs", {}).pop(int(binding), None)
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -703,6 +738,10 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         if _is_device_tensor(joint_matrices) or _is_device_tensor(morph_weights):
             raise FrtError("set_mesh_poses: a MultiRenderer takes host arrays only (its replicas live on different devices)")
         set_mesh_poses_call("frt_multi_renderer_set_mesh_poses", self._h, mesh_ids, joint_matrices, morph_weights, normals)
+
+    def animate(self, rig, mesh_ids, clip, t, normals="recompute"):
+        """`rig` (frt.Rig) evaluated on the host at clip `clip`, time `t`, then set_mesh_poses on every strip's replica (host arrays, as everywhere here)."""
+        self.set_mesh_poses(mesh_ids, *rig.evaluate(clip, t), normals=normals)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

@@ -487,6 +487,10 @@ class SceneBuilder:
         set_mesh_poses_call("frt_scene_set_mesh_poses", self._h, mesh_ids, joint_matrices, morph_weights, normals)
         return self
 
+    # An animated pose ("Animation"): `rig` (frt.Rig) evaluated at clip `clip`, time `t`, then set_mesh_poses on the host copy.
+    def animate(self, rig, mesh_ids, clip, t, normals="recompute"):
+        return self.set_mesh_poses(mesh_ids, *rig.evaluate(clip, t), normals=normals)
+
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
     # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
     # base in target order and applies the result as set_mesh_vertices does. Host copy only.

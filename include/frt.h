@@ -520,6 +520,101 @@ int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float
 int frt_renderer_set_mesh_poses(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags);
 /* Device-input deformations this renderer has rejected since it was created (non-finite input). Waits for the main stream. */
 int frt_renderer_deform_rejects(frt_renderer* r, uint32_t* out);
+
+/* ---- animation ("Animation"): a rig is a node hierarchy, a joint list with inverse bind matrices, morph target defaults and
+ * clips of keyframed channels, as a glTF document describes them. Evaluating clip c at time t gives the joint palette and the morph weights that
+ * frt_scene_set_mesh_poses / frt_renderer_set_mesh_poses take. frt_rig_evaluate is the specification, on the host; frt_renderer_animate runs the same
+ * text in one kernel on the renderer's device and gives the same bits.
+ * The contract, f32 without contraction and without a hand-written fma (csrc/frt_animation.hpp, csrc/frt_math.hpp):
+ *   Sampling a channel with key times times[0 .. K-1] at t: t <= times[0] gives the first key, t >= times[K-1] the last, t == times[k] key k, each as
+ *   stored. Otherwise k is the largest index with times[k] <= t (binary search), dt = times[k+1] - times[k], u = (t - times[k]) / dt. Looping is the
+ *   caller's (t % duration). STEP: key k. LINEAR (translation, scale, weights): a (1 - u) + b u per component. CUBICSPLINE (values stored per key as
+ *   in-tangent, value, out-tangent): with u2 = u u, u3 = u2 u, h00 = (2 u3 - 3 u2) + 1, h10 = (u3 - 2 u2) + u, h01 = 3 u2 - 2 u3, h11 = u3 - u2:
+ *   ((h00 v_k + (dt h10) b_k) + h01 v_k+1) + (dt h11) a_k+1 per component.
+ *   Rotations (x, y, z, w): LINEAR is spherical. d = ((x0 x1 + y0 y1) + z0 z1) + w0 w1; d < 0 negates q1 and d. d > 0.9995: the component-wise mix,
+ *   times 1 / sqrt of its own dot product. Otherwise th = acos(d) (a fixed polynomial, csrc/frt_animation.hpp: acosf_), q0 (sin((1 - u) th) / sin th) +
+ *   q1 (sin(u th) / sin th), the quotient as a product with one reciprocal. CUBICSPLINE rotations are normalised after interpolation (between keys);
+ *   STEP, key and rest rotations are used as given.
+ *   Local matrix T R S: with x2 = x + x, y2, z2 alike and the nine products xx = x x2, xy = x y2, xz = x z2, yy = y y2, yz = y z2, zz = z z2,
+ *   wx = w x2, wy = w y2, wz = w z2: columns (1 - (yy + zz), xy + wz, xz - wy) sx, (xy - wz, 1 - (xx + zz), yz + wx) sy, (xz + wy, yz - wx,
+ *   1 - (xx + yy)) sz and (tx, ty, tz, 1). A path without a channel in the clip uses the node's rest value; a node given as a matrix uses its matrix
+ *   and cannot be animated.
+ *   global[n] = global[parent[n]] * local[n], a root's global is its local; a 4x4 product is column j = ((A.c0 b0j + A.c1 b1j) + A.c2 b2j) + A.c3 b3j.
+ *   joint_mats[j] = global[joint_node[j]] * inverse_bind[j]. The transform of the node that carries a skinned mesh is not part of it (glTF): the
+ *   instance transform places the character.
+ *   Morph weights: the clip's weights channel sampled as ntargets components, or, in a clip without one, the default weights.
+ * frt_rig_create: the description is copied. Nodes are given parents first (parents[n] is -1 or < n); rest_trs [10 nnodes] is translation xyz, rotation
+ * xyzw, scale xyz per node; a node with has_matrix[n] != 0 takes matrices [16 n .. 16 n + 15] (column-major) instead (has_matrix and matrices may be
+ * NULL: no such node). inverse_bind NULL: identities; default_weights NULL: zeros. A channel's values are [nkeys][width] (CUBICSPLINE:
+ * [nkeys][3][width]) with width 3, 4, 3 or ntargets by path; a weights channel's node is not read. NULL with frt_last_error set: a count out of range
+ * (nnodes 1 .. 2^20, njoints <= 65536, ntargets <= FRT_MAX_MORPH_TARGETS, neither joints nor targets), a parent that is not an earlier node, a joint
+ * that is not a node, a channel on a node that is not a node or that is a matrix node, two channels of one clip for the same node and path or two
+ * weights channels, an unknown path or interpolation, nkeys == 0, key times that are not finite and strictly increasing, a value that is not finite.
+ * frt_rig_evaluate: joint_mats_out [16 njoints] (column-major), morph_weights_out [ntargets]; an output the rig has nothing for may be NULL.
+ * FRT_ERR_INVALID_ARG: clip out of range, a time that is NaN or infinite. */
+#define FRT_MAX_RIG_NODES 1024u         /* what frt_renderer_bind_rig takes: the kernel keeps every node's global matrix in LDS (64 bytes each) */
+#define FRT_RIG_PATH_TRANSLATION 0u
+#define FRT_RIG_PATH_ROTATION 1u
+#define FRT_RIG_PATH_SCALE 2u
+#define FRT_RIG_PATH_WEIGHTS 3u
+#define FRT_RIG_STEP 0u
+#define FRT_RIG_LINEAR 1u
+#define FRT_RIG_CUBICSPLINE 2u
+typedef struct frt_rig frt_rig;
+typedef struct frt_rig_channel { uint32_t node, path, interpolation, nkeys; const float* times; const float* values; } frt_rig_channel;
+typedef struct frt_rig_clip { const char* name; uint32_t nchannels; const frt_rig_channel* channels; } frt_rig_clip;
+typedef struct frt_rig_desc {
+    uint32_t nnodes; const int32_t* parents; const float* rest_trs; const uint8_t* has_matrix; const float* matrices;
+    uint32_t njoints; const uint32_t* joint_nodes; const float* inverse_bind;
+    uint32_t ntargets; const float* default_weights;
+    uint32_t nclips; const frt_rig_clip* clips;
+} frt_rig_desc;
+frt_rig* frt_rig_create(const frt_rig_desc* desc);
+/* The rig of a loaded glTF document (frt_model_load). The loader reads, beside the geometries: per primitive JOINTS_0 (u8 / u16) and WEIGHTS_0 (float or
+ * normalized u8 / u16) in the geometry's vertex order, targets[*].POSITION and the mesh's default weights (JOINTS_1 and beyond: ignored with a warning;
+ * target normals and tangents: ignored; sparse accessors: refused as everywhere); the nodes, stored parents first, with rest translation, rotation
+ * (x, y, z, w), scale or their matrix; the skins (inverseBindMatrices absent: identities); the animations (outputs given as normalized integers are
+ * converted by glTF's rule). frt_model_load fails for a cycle in the node graph, a joint that is not a node, sampler times that are not finite and
+ * strictly increasing, an output count that is not input count x path width (x 3 for CUBICSPLINE); what is merely unsupported is skipped with a warning.
+ * rig_counts: nodes, skins, animations. geometry_rig: {1 if the geometry has skin attributes, the skin of the node that carries its mesh or
+ * 0xFFFFFFFF, its target count, its mesh's document index}. nodes_get: parents [N] (-1: a root, else a smaller stored index), rest_trs [10 N],
+ * has_matrix [N], matrices [16 N], document_index [N] (the document's index of stored node i); any pointer may be NULL. skin_get: joint_nodes are
+ * stored indices. channel_info: {node (stored index), path, interpolation, keys, values}. frt_rig_from_model: the rig of skin `skin_index`, or with
+ * -1 a morph-only rig: every node, the skin's joints and inverse binds, the targets of the first geometry under that skin that has any, one clip per
+ * animation. NULL with frt_last_error set when the skin is out of range or frt_rig_create refuses (a model with neither). */
+int frt_model_rig_counts(const frt_model* m, uint32_t out[3]);
+int frt_model_geometry_rig(const frt_model* m, uint32_t geo, uint32_t out[4]);
+int frt_model_geometry_skin_get(const frt_model* m, uint32_t geo, uint16_t* joints4, float* weights4);
+int frt_model_geometry_targets_get(const frt_model* m, uint32_t geo, float* deltas3, float* default_weights);
+int frt_model_nodes_get(const frt_model* m, int32_t* parents, float* rest_trs, uint8_t* has_matrix, float* matrices, uint32_t* document_index);
+int frt_model_skin_get(const frt_model* m, uint32_t skin, uint32_t* njoints, uint32_t* joint_nodes, float* inverse_bind);
+int frt_model_animation_info(const frt_model* m, uint32_t anim, const char** name_out, uint32_t* nchannels);
+int frt_model_channel_info(const frt_model* m, uint32_t anim, uint32_t channel, uint32_t out[5]);
+int frt_model_channel_get(const frt_model* m, uint32_t anim, uint32_t channel, float* times, float* values);
+frt_rig* frt_rig_from_model(const frt_model* m, int32_t skin_index);
+void frt_rig_destroy(frt_rig* rig);
+int frt_rig_counts(const frt_rig* rig, uint32_t counts[4]);      /* nodes, joints, targets, clips */
+int frt_rig_clip_info(const frt_rig* rig, uint32_t clip, const char** name_out, float* duration_out);      /* duration: the largest last key time */
+int frt_rig_evaluate(const frt_rig* rig, uint32_t clip, float time, float* joint_mats_out, float* morph_weights_out);
+void frt_acosf(uint32_t n, const float* x, float* out);      /* TEST HOOK, not product API: the contract's acos of x [n], out[i] = acosf_(x[i]), so that a test can sweep it */
+/* Animate meshes of this renderer's scene replica from a rig ("Animation").
+ * bind_rig: the rig (topology, rest values, inverse binds, every clip's keys) is copied to the renderer's device once, through pinned memory, and a
+ * palette of 4 njoints float4 and ntargets weights are allocated there; mesh_ids [n] is remembered. *binding_out names the binding from then on. The
+ * rig may be destroyed afterwards. FRT_ERR_INVALID_ARG, nothing changed: more than FRT_MAX_RIG_NODES nodes, a mesh list frt_renderer_set_mesh_poses
+ * would refuse for a palette of njoints joints (if the rig has joints) and ntargets weights (if it has targets) in device memory.
+ * animate: asynchronous, between frames, on the main stream, under the ordering and state rules of frt_renderer_set_mesh_poses. One kernel (one
+ * workgroup) evaluates `clip` at `time` into the binding's palette and weights, bit for bit what frt_rig_evaluate gives; then the call IS
+ * frt_renderer_set_mesh_poses(r, n, mesh_ids, palette, njoints, weights, ntargets, flags | FRT_DEFORM_DEVICE): a rig with joints only skins, with
+ * targets only morphs, with both morphs then skins. flags: FRT_DEFORM_RECOMPUTE_NORMALS. A palette entry or posed coordinate that overflowed rejects
+ * on the device as any device palette does: nothing is applied and frt_renderer_deform_rejects counts one. Refused on the host with nothing enqueued
+ * (FRT_ERR_INVALID_ARG): an unknown binding, clip out of range, a time that is not finite, an unknown flag bit, a mesh that no longer has the binding
+ * the rig implies. read_rig_pose: waits for the main stream and copies the binding's palette [16 njoints] and weights [ntargets] as the last animate
+ * left them (either may be NULL). unbind_rig: waits for the main stream and frees the binding's device memory; its number is given out again by a later bind_rig.
+ * frt_renderer_remove_meshes renumbers a binding's meshes with the survivors and unbinds a binding that names a mesh that left. */
+int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* mesh_ids, uint32_t n, uint32_t* binding_out);
+int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float time, uint32_t flags);
+int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out);
+int frt_renderer_unbind_rig(frt_renderer* r, uint32_t binding);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
