@@ -16,13 +16,13 @@ static bool all_finite(const float* p, size_t n) { for (size_t i = 0; i < n; ++i
 static uint32_t path_width(uint32_t path, uint32_t ntargets) { return path == (uint32_t)kRigPathRotation ? 4u : path == (uint32_t)kRigPathWeights ? ntargets : 3u; }
 
 // "" or what is wrong with the description. Every count is checked before the array it sizes is read.
-static std::string check_rig_desc(const frt_rig_desc* d) {
+static std::string check_rig_desc(const frt_rig_desc* d, uint32_t flags) {
     if (!d) return "null description";
     if (d->nnodes == 0 || d->nnodes > (1u << 20)) return "nnodes must be 1 .. 2^20";
     if (!d->parents || !d->rest_trs) return "parents and rest_trs are required";
     if (d->njoints > 0x10000u) return "more than 65536 joints (a joint index is 16 bits)";
     if (d->ntargets > FRT_MAX_MORPH_TARGETS) return "more than FRT_MAX_MORPH_TARGETS targets";
-    if (d->njoints == 0 && d->ntargets == 0) return "a rig has joints, morph targets or both";
+    if (d->njoints == 0 && d->ntargets == 0 && !(flags & FRT_RIG_NODES_ONLY)) return "a rig has joints, morph targets or both";
     if (d->njoints && !d->joint_nodes) return "joint_nodes is required with njoints > 0";
     if (d->nclips > (1u << 16)) return "more than 65536 clips";
     if (d->nclips && !d->clips) return "clips is required with nclips > 0";
@@ -78,8 +78,11 @@ static std::string check_rig_desc(const frt_rig_desc* d) {
 
 extern "C" {
 
-frt_rig* frt_rig_create(const frt_rig_desc* d) {
-    const std::string bad = check_rig_desc(d);
+frt_rig* frt_rig_create(const frt_rig_desc* d) { return frt_rig_create_ex(d, 0u); }
+
+frt_rig* frt_rig_create_ex(const frt_rig_desc* d, uint32_t flags) {
+    if (flags & ~FRT_RIG_NODES_ONLY) { rig_fail("rig_create: unknown flag bits"); return nullptr; }
+    const std::string bad = check_rig_desc(d, flags);
     if (!bad.empty()) { rig_fail("rig_create: " + bad); return nullptr; }
     const uint32_t N = d->nnodes, J = d->njoints, T = d->ntargets;
     // by depth, parents in front of their children: `order[i]` is the caller's index of node i here
@@ -146,6 +149,7 @@ frt_rig* frt_rig_create(const frt_rig_desc* d) {
     }
     h.words = (uint32_t)w.size();
     memcpy(w.data(), &h, sizeof(h));
+    rig->place.swap(place);
     return rig;
 }
 
@@ -220,13 +224,14 @@ int frt_model_channel_get(const frt_model* m, uint32_t anim, uint32_t channel, f
 // The rig of skin `skin_index` (or, with -1, a morph-only rig) of a loaded document: every node, the skin's joints and inverse binds, the targets and
 // default weights of the first geometry under that skin (with -1: of the first geometry) that has targets, and one clip per animation in document
 // order; a weights channel is taken when its node carries a mesh with that many targets.
-frt_rig* frt_rig_from_model(const frt_model* m, int32_t skin_index) {
+// (`nodes_only`, frt_rig_from_model_nodes: no joints, no targets, the weights channels left out, created with FRT_RIG_NODES_ONLY)
+static frt_rig* rig_from_model(const frt_model* m, int32_t skin_index, bool nodes_only) {
     if (!m) { rig_fail("rig_from_model: null"); return nullptr; }
     const LoadedModel& L = m->m;
     if (skin_index < -1 || (skin_index >= 0 && (size_t)skin_index >= L.skins.size())) { rig_fail("rig_from_model: skin " + std::to_string(skin_index) + " out of range (" + std::to_string(L.skins.size()) + " skins)"); return nullptr; }
     if (L.nodes.empty()) { rig_fail("rig_from_model: the model has no nodes"); return nullptr; }
     const LoadedModel::GeometryRig* morph = nullptr;
-    for (const LoadedModel::GeometryRig& g : L.geometry_rigs) if (g.ntargets && (skin_index < 0 || g.skin == skin_index)) { morph = &g; break; }
+    if (!nodes_only) for (const LoadedModel::GeometryRig& g : L.geometry_rigs) if (g.ntargets && (skin_index < 0 || g.skin == skin_index)) { morph = &g; break; }
     const size_t N = L.nodes.size();
     std::vector<int32_t> parents(N); std::vector<float> trs(10 * N), mats(16 * N); std::vector<uint8_t> has(N);
     frt_model_nodes_get(m, parents.data(), trs.data(), has.data(), mats.data(), nullptr);
@@ -248,7 +253,19 @@ frt_rig* frt_rig_from_model(const frt_model* m, int32_t skin_index) {
     if (skin_index >= 0) { const LoadedModel::Skin& s = L.skins[(size_t)skin_index]; d.njoints = (uint32_t)s.joints.size(); d.joint_nodes = s.joints.data(); d.inverse_bind = s.inverse_bind.data(); }
     if (morph) { d.ntargets = morph->ntargets; d.default_weights = morph->default_weights.data(); }
     d.nclips = (uint32_t)clips.size(); d.clips = clips.data();
-    return frt_rig_create(&d);
+    return frt_rig_create_ex(&d, nodes_only ? FRT_RIG_NODES_ONLY : 0u);
+}
+frt_rig* frt_rig_from_model(const frt_model* m, int32_t skin_index) { return rig_from_model(m, skin_index, false); }
+frt_rig* frt_rig_from_model_nodes(const frt_model* m) { return rig_from_model(m, -1, true); }
+
+int frt_model_geometry_nodes(const frt_model* m, uint32_t geo, uint32_t cap, uint32_t* nodes_out, uint32_t* count_out) {
+    if (!m || !count_out || geo >= m->m.geometries.size() || (cap && !nodes_out)) return rig_fail("model_geometry_nodes: bad arguments");
+    uint32_t n = 0;
+    if (geo < m->m.geometry_rigs.size() && m->m.geometry_rigs[geo].mesh >= 0)      // (an OBJ model has no nodes)
+        for (size_t i = 0; i < m->m.nodes.size(); ++i)
+            if (m->m.nodes[i].mesh == m->m.geometry_rigs[geo].mesh) { if (n < cap) nodes_out[n] = (uint32_t)i; ++n; }
+    *count_out = n;
+    return FRT_OK;
 }
 
 void frt_acosf(uint32_t n, const float* x, float* out) { for (uint32_t i = 0; i < n; ++i) out[i] = acosf_(x[i]); }
@@ -288,6 +305,31 @@ int frt_rig_evaluate(const frt_rig* rig, uint32_t clip, float time, float* joint
         }
     }
     for (uint32_t c = 0; c < h.ntargets; ++c) morph_weights_out[c] = rig_morph_weight(v, clip, c, time);
+    return FRT_OK;
+}
+
+// The specification of rig_nodes_kernel (frt_animation.hip): the globals of frt_rig_evaluate, then rig_node_matrix per queried node.
+int frt_rig_evaluate_nodes(const frt_rig* rig, uint32_t clip, float time, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
+    if (!rig) return rig_fail("rig_evaluate_nodes: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    if (clip >= h.nclips) return rig_fail("rig_evaluate_nodes: clip " + std::to_string(clip) + " out of range (" + std::to_string(h.nclips) + " clips)");
+    if (!std::isfinite(time)) return rig_fail("rig_evaluate_nodes: time is not finite");
+    if (n == 0 || !nodes || !mats_out) return rig_fail("rig_evaluate_nodes: n is 0, or null nodes or output");
+    for (uint32_t k = 0; k < n; ++k)
+        if (nodes[k] >= h.nnodes) return rig_fail("rig_evaluate_nodes: node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
+    if (root && !all_finite(root, 16)) return rig_fail("rig_evaluate_nodes: a root entry is not finite");
+    if (offsets && !all_finite(offsets, (size_t)16 * n)) return rig_fail("rig_evaluate_nodes: an offsets entry is not finite");
+    std::vector<m4> global(h.nnodes);
+    for (uint32_t i = 0; i < h.nnodes; ++i) {      // parents first
+        const m4 local = rig_local_matrix(v, clip, i, time);
+        const uint32_t p = v.w[h.parent + i];
+        global[i] = p == kRigNone ? local : mul(global[p], local);
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
+        memcpy(mats_out + (size_t)16 * k, &M, 64);
+    }
     return FRT_OK;
 }
 

@@ -28,6 +28,23 @@ __device__ inline void rig_lds_store(float4* g, uint32_t n, const m4& m) {
     for (int c = 0; c < 4; ++c) g[(uint32_t)c * kRigLds + n] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
 }
 
+// Phases (1) and (2) of both kernels: the global matrix of every node < N is in `g` behind the last barrier. Called by the whole workgroup with uniform
+// arguments (the level bounds are the same words for every lane).
+__device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, uint32_t clip, float t, float4* g, uint32_t N) {
+    const uint32_t* words = v.w;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix(v, clip, n, t));
+    __syncthreads();
+    for (uint32_t level = 1u; level < h.nlevels; ++level) {
+        const uint32_t begin = words[h.level_begin + level], end = words[h.level_begin + level + 1u];
+        for (uint32_t n = begin + tid; n < end && n < N; n += (uint32_t)kRigBlock) {
+            const uint32_t p = words[h.parent + n];
+            if (p < n) rig_lds_store(g, n, mul(rig_lds_load(g, p), rig_lds_load(g, n)));
+        }
+        __syncthreads();
+    }
+}
+
 __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, uint32_t clip, float t, float4* palette, float* weights) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
@@ -36,16 +53,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig refuses a larger rig)
     if (clip >= h.nclips) return;                                    // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
     if (h.njoints) {
-        for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix(v, clip, n, t));
-        __syncthreads();
-        for (uint32_t level = 1u; level < h.nlevels; ++level) {
-            const uint32_t begin = words[h.level_begin + level], end = words[h.level_begin + level + 1u];
-            for (uint32_t n = begin + tid; n < end && n < N; n += (uint32_t)kRigBlock) {
-                const uint32_t p = words[h.parent + n];
-                if (p < n) rig_lds_store(g, n, mul(rig_lds_load(g, p), rig_lds_load(g, n)));
-            }
-            __syncthreads();
-        }
+        rig_globals_to_lds(v, h, clip, t, g, N);
         for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
             const uint32_t n = words[h.joint_node + j];
             if (n >= N) continue;
@@ -55,6 +63,25 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
         }
     }
     for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = rig_morph_weight(v, clip, c, t);
+}
+
+// frt_renderer_animate_instances ("Node animation"): phases (1) and (2) as above, whether or not the rig has joints; (3) one lane per bound instance,
+// strided by the workgroup's size, loads its node's global from LDS, applies root and offset through rig_node_matrix (the host's text) and stores four
+// float4 into the binding's matrices. `nodes` [n]: stored node indices; `root` [16] and `offsets` [16 n]: null when the binding has none.
+__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, uint32_t clip, float t, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
+    __shared__ float4 g[4u * kRigLds];
+    RigView v; v.w = words;
+    const RigHeader h = v.h();
+    const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig_instances refuses a larger rig)
+    if (clip >= h.nclips) return;                                    // (animate_instances refuses it; uniform, in front of the first barrier)
+    rig_globals_to_lds(v, h, clip, t, g, N);
+    for (uint32_t k = threadIdx.x; k < n; k += (uint32_t)kRigBlock) {
+        const uint32_t node = nodes[k];
+        if (node >= N) continue;                                     // (bind_rig_instances has checked it)
+        const m4 m = rig_node_matrix(rig_lds_load(g, node), root, offsets ? offsets + (size_t)16u * k : nullptr);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) mats[4u * k + (uint32_t)c] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
+    }
 }
 
 } // namespace frt
@@ -73,6 +100,15 @@ static std::string check_rig_meshes(const frt_renderer* r, const uint32_t* ids, 
     }
     return bad;
 }
+
+// The binding gets the first free number: an unbound one is used again.
+static uint32_t keep_binding(frt_renderer* r, const RigBinding& b) {
+    size_t slot = 0;
+    while (slot < r->rigs.size() && r->rigs[slot].live) ++slot;
+    if (slot == r->rigs.size()) r->rigs.push_back(b); else r->rigs[slot] = b;
+    return (uint32_t)slot;
+}
+static bool finite_bits(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) != 0x7f800000u; }
 
 extern "C" {
 
@@ -99,10 +135,94 @@ int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* m
     }
     if (rc) { b.rig.release(r); b.palette.release(r); b.weights.release(r); return rc; }
     b.njoints = h.njoints; b.ntargets = h.ntargets; b.nclips = h.nclips; b.mesh_ids.assign(mesh_ids, mesh_ids + n); b.live = true;
-    size_t slot = 0;      // the first free number: an unbound one is used again
-    while (slot < r->rigs.size() && r->rigs[slot].live) ++slot;
-    if (slot == r->rigs.size()) r->rigs.push_back(b); else r->rigs[slot] = b;
-    *binding_out = (uint32_t)slot;
+    *binding_out = keep_binding(r, b);
+    return FRT_OK;
+}
+
+int frt_renderer_bind_rig_instances(frt_renderer* r, const frt_rig* rig, uint32_t n, const uint32_t* instance_ids, const uint32_t* nodes, const float* root, const float* offsets, uint32_t* binding_out) {
+    if (const int rc = check_entry(r, "bind_rig_instances", kEditChecks | kRefit)) return rc;
+    if (!rig || !binding_out) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: null");
+    const RigHeader h = rig->view().h();
+    if (h.nnodes > FRT_MAX_RIG_NODES) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: " + std::to_string(h.nnodes) + " nodes, more than FRT_MAX_RIG_NODES");
+    if (n == 0 || n > FRT_MAX_RIG_INSTANCES) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: " + std::to_string(n) + " instances (1 .. FRT_MAX_RIG_INSTANCES)");
+    if (!instance_ids || !nodes) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: null ids or nodes");
+    const size_t ninst = r->rf.inst.size();
+    std::vector<uint8_t> seen(ninst, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t id = instance_ids[k];
+        if (id >= ninst) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: instance id " + std::to_string(id) + " out of range (" + std::to_string(ninst) + " instances)");
+        if (seen[id]) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: instance id " + std::to_string(id) + " given twice");
+        seen[id] = 1;
+        if (nodes[k] >= h.nnodes) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
+    }
+    for (size_t i = 0; root && i < 16; ++i) if (!finite_bits(root[i])) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: a root entry is not finite");
+    for (size_t i = 0; offsets && i < (size_t)16 * n; ++i) if (!finite_bits(offsets[i])) return fail(FRT_ERR_INVALID_ARG, "bind_rig_instances: an offsets entry is not finite");
+    FRT_DEVICE(r);
+    // one pinned block: [rig | ids | tab], tab = [nodes, padded to 16 bytes | root | offsets]
+    const size_t rig_bytes = rig->words.size() * 4, id_bytes = (size_t)n * 4, node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
+    const size_t root_bytes = root ? 64u : 0u, off_bytes = offsets ? (size_t)n * 64 : 0u, tab_bytes = node_bytes + root_bytes + off_bytes;
+    RigBinding b;
+    int rc;
+    if ((rc = b.rig.ensure(r, rig_bytes)) == FRT_OK && (rc = b.ids.ensure(r, id_bytes)) == FRT_OK && (rc = b.tab.ensure(r, tab_bytes)) == FRT_OK) rc = b.mats.ensure(r, (size_t)n * 64);
+    if (rc == FRT_OK) rc = r->rig_up.reserve(rig_bytes + id_bytes + tab_bytes, 0, r->stream);
+    if (rc == FRT_OK) {
+        uint8_t* up = r->rig_up.h;
+        uint8_t* tab = up + rig_bytes + id_bytes;
+        memcpy(up, rig->words.data(), rig_bytes);
+        memcpy(up + rig_bytes, instance_ids, id_bytes);
+        memset(tab, 0, node_bytes);
+        for (uint32_t k = 0; k < n; ++k) { const uint32_t stored = rig->place[nodes[k]]; memcpy(tab + (size_t)4 * k, &stored, 4); }
+        if (root) memcpy(tab + node_bytes, root, 64);
+        if (offsets) memcpy(tab + node_bytes + root_bytes, offsets, off_bytes);
+        hipError_t e = hipMemcpyAsync(b.rig.p, up, rig_bytes, hipMemcpyHostToDevice, r->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.ids.p, up + rig_bytes, id_bytes, hipMemcpyHostToDevice, r->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.tab.p, tab, tab_bytes, hipMemcpyHostToDevice, r->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b.mats.p, 0, (size_t)n * 64, r->stream);
+        rc = e == hipSuccess ? r->rig_up.mark(r->stream) : fail(FRT_ERR_HIP, std::string("bind_rig_instances: ") + hipGetErrorString(e));
+    }
+    if (rc) { b.release(r); return rc; }
+    b.kind = kRigInstances; b.nclips = h.nclips; b.instance_ids.assign(instance_ids, instance_ids + n); b.has_root = root != nullptr; b.has_offsets = offsets != nullptr; b.live = true;
+    *binding_out = keep_binding(r, b);
+    return FRT_OK;
+}
+
+int frt_renderer_animate_instances(frt_renderer* r, uint32_t binding, uint32_t clip, float time) {
+    if (const int rc = check_entry(r, "animate_instances", kEditChecks | kRefit)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate_instances: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate)");
+    if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate_instances: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
+    if (!finite_bits(time)) return fail(FRT_ERR_INVALID_ARG, "animate_instances: time is not finite");
+    const uint32_t n = (uint32_t)b->instance_ids.size();
+    {
+        // The kernel writes the binding's matrices only, which nothing but the device transform of an earlier animate_instances reads: on this stream, in front of it.
+        FRT_DEVICE(r);
+        if (b->ids_stale) {      // (remove_instances has renumbered the instances)
+            if (const int rc = r->rig_up.reserve((size_t)n * 4, 0, r->stream)) return rc;
+            memcpy(r->rig_up.h, b->instance_ids.data(), (size_t)n * 4);
+            HIP_TRY(hipMemcpyAsync(b->ids.p, r->rig_up.h, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
+            if (const int rc = r->rig_up.mark(r->stream)) return rc;
+            b->ids_stale = false;
+        }
+        const uint8_t* tab = b->tab.as<const uint8_t>();
+        const size_t node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
+        const float* root = b->has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
+        const float* offsets = b->has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b->has_root ? 64u : 0u)) : nullptr;
+        hipLaunchKernelGGL(rig_nodes_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), clip, time, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate_instances: ") + hipGetErrorString(e)); }
+    }
+    return frt_renderer_set_instance_transforms_ex(r, n, b->ids.as<const uint32_t>(), b->mats.as<const float>(), FRT_TRANSFORM_DEVICE);
+}
+
+int frt_renderer_read_rig_instances(frt_renderer* r, uint32_t binding, float* mats_out) {
+    if (const int rc = check_entry(r, "read_rig_instances", kNotFailed)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b || b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "read_rig_instances: unknown instance rig binding " + std::to_string(binding));
+    if (!mats_out) return fail(FRT_ERR_INVALID_ARG, "read_rig_instances: null");
+    FRT_DEVICE(r);
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(mats_out, b->mats.p, b->instance_ids.size() * 64, hipMemcpyDeviceToHost));
     return FRT_OK;
 }
 
@@ -111,6 +231,7 @@ int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float
     if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) return fail(FRT_ERR_INVALID_ARG, "animate: unknown flag bits");
     RigBinding* b = find_binding(r, binding);
     if (!b) return fail(FRT_ERR_INVALID_ARG, "animate: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances)");
     if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
     if ((__builtin_bit_cast(uint32_t, time) & 0x7f800000u) == 0x7f800000u) return fail(FRT_ERR_INVALID_ARG, "animate: time is not finite");
     const uint32_t n = (uint32_t)b->mesh_ids.size();
@@ -130,7 +251,7 @@ int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float
 int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out) {
     if (const int rc = check_entry(r, "read_rig_pose", kNotFailed)) return rc;
     RigBinding* b = find_binding(r, binding);
-    if (!b) return fail(FRT_ERR_INVALID_ARG, "read_rig_pose: unknown rig binding " + std::to_string(binding));
+    if (!b || b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "read_rig_pose: unknown rig binding " + std::to_string(binding));
     FRT_DEVICE(r);
     HIP_TRY(hipStreamSynchronize(r->stream));
     if (joint_mats_out && b->njoints) HIP_TRY(hipMemcpy(joint_mats_out, b->palette.p, (size_t)b->njoints * 64, hipMemcpyDeviceToHost));
@@ -143,7 +264,7 @@ int frt_renderer_unbind_rig(frt_renderer* r, uint32_t binding) {
     RigBinding* b = find_binding(r, binding);
     if (!b) return fail(FRT_ERR_INVALID_ARG, "unbind_rig: unknown rig binding " + std::to_string(binding));
     FRT_DEVICE(r);
-    b->rig.release(r); b->palette.release(r); b->weights.release(r);
+    b->release(r);
     *b = RigBinding();
     return FRT_OK;
 }

@@ -160,13 +160,24 @@ FRT_HD float rig_morph_weight(RigView v, uint32_t clip, uint32_t c, float t) {
     return rig_sample_component(v.f(ch.values), ch.width, ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t), c);
 }
 
+// The matrix a bound instance takes from the global G of its node ("Node animation"): mul(mul(root, G), offset), the palette's mul. A null `root` or
+// `offset` is no multiplication at all (a product with the identity would turn a -0 into +0).
+FRT_HD m4 rig_node_matrix(const m4& G, const float* root, const float* offset) {
+    m4 M = G;
+    if (root) M = mul(load_m4(root), M);
+    if (offset) M = mul(M, load_m4(offset));
+    return M;
+}
+
 } // namespace frt
 
-// The host side of a rig (frt_animation.cpp): the block and what frt_rig_clip_info returns.
+// The host side of a rig (frt_animation.cpp): the block and what frt_rig_clip_info returns. `place`: the caller's node index -> the index in the block
+// (frt_rig_create stores the nodes by depth), so the node numbers a caller knows stay valid after creation.
 #include <string>
 #include <vector>
 struct frt_rig {
     std::vector<uint32_t> words;
+    std::vector<uint32_t> place;
     std::vector<std::string> clip_names;
     std::vector<float> clip_durations;
     frt::RigView view() const { frt::RigView v; v.w = words.data(); return v; }

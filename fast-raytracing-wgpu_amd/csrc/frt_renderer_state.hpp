@@ -232,11 +232,21 @@ struct RemoveState {
 // What frt_renderer_bind_rig leaves with the renderer ("Animation"; frt_animation.hip): the rig's block on the device, the palette
 // [4 njoints] float4 and the weights [ntargets] its kernel writes, and the meshes frt_renderer_animate poses. A binding's number is its index; an unbound
 // one stays in the list, empty (live == false).
+// frt_renderer_bind_rig_instances ("Node animation") leaves a binding of kind kRigInstances in the same list: the rig's block, `ids` [n] the bound
+// instances, `tab` = [the nodes' stored indices, n words padded to 16 bytes | root, 16 floats | offsets, 16 n floats] (root and offsets only when
+// given) and `mats` [4 n] float4, what its kernel writes and the device transform reads. `instance_ids` is the host's copy of `ids`, which
+// remove_instances renumbers; ids_stale: the device copy is uploaded again by the next animate_instances.
+enum { kRigMeshes = 0, kRigInstances = 1 };
 struct RigBinding {
     OwnedBuf rig, palette, weights;
     uint32_t njoints = 0, ntargets = 0, nclips = 0;
     std::vector<uint32_t> mesh_ids;
     bool live = false;
+    uint32_t kind = kRigMeshes;
+    OwnedBuf ids, tab, mats;
+    std::vector<uint32_t> instance_ids;
+    bool has_root = false, has_offsets = false, ids_stale = false;
+    void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats}) b->release(r); }
 };
 
 struct frt_renderer {

@@ -1166,7 +1166,16 @@ static int remove_instances(frt_renderer* r, const std::vector<uint32_t>& gone, 
     if ((rc = e.rec.upload(rng.data(), rng.size() * sizeof(RemovedRange), r->stream))) return rc;
     const RemoveArgs a{reinterpret_cast<const RemovedRange*>(e.rec.d), (uint32_t)rng.size(), f.d_slot_of, old_tris, old_inst, num_tris, num_inst, edit_target(e)};
     HIP_TRY(launch_instances_remove(sv, a, r->stream));
-    return commit_instance_edit(r, num_tris, inst, mode, "remove_instances");
+    if ((rc = commit_instance_edit(r, num_tris, inst, mode, "remove_instances"))) return rc;
+    // an instance rig binding follows its instances to their new ids (the next animate_instances uploads them); one that names an instance that left is unbound
+    const std::vector<uint32_t> map = removal_map(old_inst, gone);
+    for (RigBinding& b : r->rigs) {
+        if (!b.live || b.kind != kRigInstances) continue;
+        bool lost = false;
+        for (uint32_t& i : b.instance_ids) { if (i >= old_inst || map[i] == kGone) lost = true; else i = map[i]; }
+        if (lost) { b.release(r); b = RigBinding(); } else b.ids_stale = true;
+    }
+    return FRT_OK;
 }
 
 static int check_rebuild_mode(const char* what, uint32_t mode) {

@@ -217,6 +217,13 @@ SYMBOLS = {
     "frt_renderer_animate": (C.c_int, [_P, _U32, _U32, C.c_float, _U32]),
     "frt_renderer_read_rig_pose": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_unbind_rig": (C.c_int, [_P, _U32]),
+    "frt_rig_create_ex": (_P, [C.POINTER(RigDesc), _U32]),
+    "frt_rig_evaluate_nodes": (C.c_int, [_P, _U32, C.c_float, _U32, _P, _P, _P, _P]),
+    "frt_model_geometry_nodes": (C.c_int, [_P, _U32, _U32, _P, C.POINTER(_U32)]),
+    "frt_rig_from_model_nodes": (_P, [_P]),
+    "frt_renderer_bind_rig_instances": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P, C.POINTER(_U32)]),
+    "frt_renderer_animate_instances": (C.c_int, [_P, _U32, _U32, C.c_float]),
+    "frt_renderer_read_rig_instances": (C.c_int, [_P, _U32, _P]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

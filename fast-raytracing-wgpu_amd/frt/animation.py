@@ -18,10 +18,11 @@ class Rig:
     [4, 4]} for nodes given as a matrix, which cannot be animated. joint_nodes [J] and inverse_bind [J, 16] or [J, 4, 4] (default: identities): the
     skin. num_targets and default_weights [T]: the morph targets. clips: a sequence of (name, channels), a channel a dict with node, path
     ("translation", "rotation", "scale", "weights"), interpolation ("STEP", "LINEAR", "CUBICSPLINE"), times [K] and values [K, width] (CUBICSPLINE:
-    [K, 3, width] as in-tangent, value, out-tangent), width 3, 4, 3 or T by path."""
+    [K, 3, width] as in-tangent, value, out-tangent), width 3, 4, 3 or T by path. nodes_only=True (frt_rig_create_ex with FRT_RIG_NODES_ONLY): a
+    rig with neither joints nor targets is accepted, for evaluate_nodes and Renderer.bind_rig_instances."""
 
     def __init__(self, parents, translations=None, rotations=None, scales=None, matrices=None, joint_nodes=(), inverse_bind=None, num_targets=0,
-                 default_weights=None, clips=()):
+                 default_weights=None, clips=(), nodes_only=False):
         par = np.ascontiguousarray(parents, np.int32).reshape(-1)
         n = par.size
         trs = np.zeros((n, 10), np.float32)
@@ -67,7 +68,7 @@ class Rig:
             keep.append(cch)
         d = RigDesc(n, par.ctypes.data, trs.ctypes.data, has.ctypes.data, mats.ctypes.data, joints.size, joints.ctypes.data if joints.size else None,
                     ib.ctypes.data if ib is not None else None, t, dw.ctypes.data if dw is not None else None, len(clips), cclips)
-        h = lib().frt_rig_create(C.byref(d))
+        h = lib().frt_rig_create_ex(C.byref(d), 1) if nodes_only else lib().frt_rig_create(C.byref(d))
         del keep
         self._adopt(h, "frt_rig_create")
 
@@ -120,3 +121,26 @@ class Rig:
         w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
         check(lib().frt_rig_evaluate(self._h, self.clip_index(clip), float(t), pal.ctypes.data if pal is not None else None, w.ctypes.data if w is not None else None))
         return pal, w
+
+    def evaluate_nodes(self, clip, t, nodes, root=None, offsets=None):
+        """float32 [n, 16], column-major: (root * global[nodes[k]]) * offsets[k] of `clip` at time `t` (include/frt.h: frt_rig_evaluate_nodes), the
+        matrices Renderer.animate_instances gives the instances bound to those nodes. nodes: the node numbers the rig was described with. root [16] or
+        [4, 4] and offsets [n, 16] or [n, 4, 4]; None is no multiplication."""
+        n, nodes, root, offsets = node_args(nodes, root, offsets)
+        out = np.zeros((n, 16), np.float32)
+        check(lib().frt_rig_evaluate_nodes(self._h, self.clip_index(clip), float(t), n, nodes.ctypes.data, root.ctypes.data if root is not None else None,
+                                           offsets.ctypes.data if offsets is not None else None, out.ctypes.data))
+        return out
+
+
+def node_args(nodes, root, offsets):
+    """(n, nodes uint32 [n], root float32 [16] or None, offsets float32 [n, 16] or None) as the C calls of node animation take them."""
+    nodes = np.ascontiguousarray(nodes, np.int64).reshape(-1)
+    if nodes.size and (nodes.min() < 0 or nodes.max() > 0xFFFFFFFF):
+        raise FrtError("Rig: nodes must be unsigned 32-bit indices")
+    nodes = nodes.astype(np.uint32)
+    if root is not None:
+        root = _f32(np.asarray(root, np.float32).reshape(-1), (16,), "root")
+    if offsets is not None:
+        offsets = _f32(np.asarray(offsets, np.float32).reshape(-1, 16), (nodes.size, 16), "offsets")
+    return nodes.size, nodes, root, offsets

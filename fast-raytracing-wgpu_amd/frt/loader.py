@@ -120,6 +120,23 @@ class Model:
         from .animation import Rig
         return Rig.from_model(self, skin)
 
+    # ---- node animation (include/frt.h: frt_model_geometry_nodes, frt_rig_from_model_nodes; DESIGN.md section 11, "Node animation")
+    def geometry_nodes(self, geo):
+        """The stored indices, ascending, of the nodes that carry the mesh of geometry `geo` (uint32 [k]; an OBJ model: none)."""
+        n = C.c_uint32()
+        check(lib().frt_model_geometry_nodes(self._h, int(geo), 0, None, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        check(lib().frt_model_geometry_nodes(self._h, int(geo), out.size, out.ctypes.data, C.byref(n)))
+        return out
+
+    def node_rig(self):
+        """frt.Rig of every node, without joints and targets, one clip per animation (weights channels left out): what bind_rig_instances and
+        animate_instances take for a document in which nothing is skinned."""
+        from .animation import Rig
+        rig = Rig.__new__(Rig)
+        rig._adopt(lib().frt_rig_from_model_nodes(self._h), "frt_rig_from_model_nodes")
+        return rig
+
 
 def bind_character(target, model, mesh_ids):
     """Bind what `model` holds for each of its geometries to the mesh it became: set_mesh_morph_targets for a geometry with targets, set_mesh_skin (with

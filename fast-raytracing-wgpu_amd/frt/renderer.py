@@ -410,6 +410,37 @@ class Renderer(_HostQueries, _SceneGrowth):
         check(lib().frt_renderer_unbind_rig(self._h, int(binding)))
         getattr(self, "_rigs", {}).pop(int(binding), None)
 
+    # ---- node animation (include/frt.h: frt_renderer_bind_rig_instances and the two calls after it; DESIGN.md section 11, "Node animation")
+    def bind_rig_instances(self, rig, instance_ids, nodes, root=None, offsets=None):
+        """Copy `rig` (frt.Rig) to the renderer's device and bind instance instance_ids[k] to node nodes[k] (the node numbers the rig was described
+        with; for Model.node_rig() the stored indices of Model.geometry_nodes). root [16] and offsets [n, 16], column-major, or None: the instance's
+        matrix is (root * global[node]) * offset. Returns the binding animate_instances takes; it shares the numbers of bind_rig."""
+        from .animation import node_args
+        n, nodes, root, offsets = node_args(nodes, root, offsets)
+        n_ids, ids = instance_id_args(instance_ids)
+        if n_ids != n:
+            raise FrtError(f"bind_rig_instances: {n_ids} instance ids but {n} nodes")
+        b = C.c_uint32()
+        check(lib().frt_renderer_bind_rig_instances(self._h, rig._h, n, ids.ctypes.data, nodes.ctypes.data, root.ctypes.data if root is not None else None,
+                                                    offsets.ctypes.data if offsets is not None else None, C.byref(b)))
+        self._rigs = getattr(self, "_rigs", {})
+        self._rigs[int(b.value)] = rig
+        self._rig_instances = getattr(self, "_rig_instances", {})
+        self._rig_instances[int(b.value)] = n
+        return int(b.value)
+
+    def animate_instances(self, binding, clip, t):
+        """Move the binding's instances under clip `clip` (a number, or a name of the bound rig) at time `t` between frames: one kernel evaluates the
+        clip into matrices the renderer owns, bit for bit rig.evaluate_nodes, and the call goes on as set_instance_transforms with device tensors
+        (validated on the device, all or nothing: transform_rejects() counts a rejected call). Asynchronous."""
+        check(lib().frt_renderer_animate_instances(self._h, int(binding), self._bound_rig("animate_instances", binding).clip_index(clip), float(t)))
+
+    def read_rig_instances(self, binding):
+        """float32 [n, 16]: the binding's matrices as the last animate_instances left them. Waits for the renderer's stream."""
+        out = np.zeros((getattr(self, "_rig_instances", {}).get(int(binding), 0), 16), np.float32)
+        check(lib().frt_renderer_read_rig_instances(self._h, int(binding), out.ctypes.data if out.size else None))
+        return out
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -742,6 +773,10 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
     def animate(self, rig, mesh_ids, clip, t, normals="recompute"):
         """`rig` (frt.Rig) evaluated on the host at clip `clip`, time `t`, then set_mesh_poses on every strip's replica (host arrays, as everywhere here)."""
         self.set_mesh_poses(mesh_ids, *rig.evaluate(clip, t), normals=normals)
+
+    def animate_instances(self, rig, instance_ids, nodes, clip, t, root=None, offsets=None):
+        """rig.evaluate_nodes on the host, then set_instance_transforms on every strip's replica."""
+        self.set_instance_transforms(instance_ids, rig.evaluate_nodes(clip, t, nodes, root, offsets))
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

@@ -491,6 +491,10 @@ class SceneBuilder:
     def animate(self, rig, mesh_ids, clip, t, normals="recompute"):
         return self.set_mesh_poses(mesh_ids, *rig.evaluate(clip, t), normals=normals)
 
+    # Node animation ("Node animation"): rig.evaluate_nodes, then set_instance_transforms on the host copy.
+    def animate_instances(self, rig, instance_ids, nodes, clip, t, root=None, offsets=None):
+        return self.set_instance_transforms(instance_ids, rig.evaluate_nodes(clip, t, nodes, root, offsets))
+
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
     # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
     # base in target order and applies the result as set_mesh_vertices does. Host copy only.

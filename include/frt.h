@@ -615,6 +615,40 @@ int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* m
 int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float time, uint32_t flags);
 int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out);
 int frt_renderer_unbind_rig(frt_renderer* r, uint32_t binding);
+/* Node animation ("Node animation"): a node's translation, rotation or scale channel moves the instance that hangs on it.
+ * frt_rig_create_ex(desc, FRT_RIG_NODES_ONLY) also accepts a rig with neither joints nor targets; every other check is frt_rig_create's, and
+ * frt_rig_create(desc) is frt_rig_create_ex(desc, 0). Node numbers are the caller's everywhere below: the rig remembers where frt_rig_create stored each
+ * node (for a rig made from a model they are the stored node indices of frt_model_nodes_get).
+ * frt_rig_evaluate_nodes is the specification, on the host: with G = global[nodes[k]] of the contract above, mats_out [16 k ..] = G, with `root` [16]
+ * root * G, with `offsets` [16 n] (that) * offsets[k]: (root * G) * offset, the 4x4 product of the palette. A NULL root or offsets is no multiplication,
+ * not a product with the identity (which would change the sign of a zero). FRT_ERR_INVALID_ARG: clip out of range (so a rig without clips cannot be
+ * evaluated: give it one clip without channels for the rest pose), a time that is not finite, n == 0, a node that is not a node, a root or offsets
+ * entry that is not finite, a null nodes or output.
+ * frt_model_geometry_nodes: the stored indices, ascending, of the nodes whose mesh is the mesh of geometry `geo`; *count_out is their number, of which
+ * the first `cap` are written (an OBJ model: none). frt_rig_from_model_nodes: every node, no joints, no targets, one clip per animation without its
+ * weights channels, created with FRT_RIG_NODES_ONLY.
+ * bind_rig_instances: the rig, instance_ids [n], the nodes' stored places, root and offsets (either may be NULL) are copied to the renderer's device
+ * once, through pinned memory on the main stream, and n x 64 bytes are allocated for the matrices. The binding shares the numbers of frt_renderer_bind_rig
+ * (the first free one is used again). FRT_ERR_INVALID_ARG, nothing changed: more than FRT_MAX_RIG_NODES nodes, n == 0 or n > FRT_MAX_RIG_INSTANCES, an
+ * id at or beyond the instance count or given twice, a node that is not a node, a root or offsets entry that is not finite; and whatever
+ * frt_renderer_set_instance_transforms refuses a renderer for. An instance with a registered light may be bound: the light moves with it.
+ * animate_instances: asynchronous, between frames, on the main stream. One kernel (one workgroup) evaluates `clip` at `time` into the binding's
+ * matrices, bit for bit frt_rig_evaluate_nodes; then the call IS frt_renderer_set_instance_transforms_ex(r, n, ids, matrices, FRT_TRANSFORM_DEVICE) on
+ * the binding's device buffers: validated on the device, all or nothing (a node scaled to zero or an overflow rejects the call and
+ * frt_renderer_transform_rejects counts one), refit, dropped speculation. Refused on the host with nothing enqueued: an unknown binding or a mesh binding
+ * (and frt_renderer_animate refuses an instance binding), clip out of range, a time that is not finite.
+ * read_rig_instances: waits for the main stream and copies the matrices [16 n] as the last animate_instances left them (zeros before the first).
+ * frt_renderer_unbind_rig serves both kinds. frt_renderer_remove_instances (and _remove_lights) renumber a binding's instances with the survivors and
+ * unbind a binding that names an instance that left. */
+#define FRT_RIG_NODES_ONLY 1u
+#define FRT_MAX_RIG_INSTANCES 65536u
+frt_rig* frt_rig_create_ex(const frt_rig_desc* desc, uint32_t flags);
+int frt_rig_evaluate_nodes(const frt_rig* rig, uint32_t clip, float time, uint32_t n, const uint32_t* nodes, const float* root16, const float* offsets16n, float* mats_out16n);
+int frt_model_geometry_nodes(const frt_model* m, uint32_t geo, uint32_t cap, uint32_t* nodes_out, uint32_t* count_out);
+frt_rig* frt_rig_from_model_nodes(const frt_model* m);
+int frt_renderer_bind_rig_instances(frt_renderer* r, const frt_rig* rig, uint32_t n, const uint32_t* instance_ids, const uint32_t* nodes, const float* root16, const float* offsets16n, uint32_t* binding_out);
+int frt_renderer_animate_instances(frt_renderer* r, uint32_t binding, uint32_t clip, float time);
+int frt_renderer_read_rig_instances(frt_renderer* r, uint32_t binding, float* mats_out16n);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
