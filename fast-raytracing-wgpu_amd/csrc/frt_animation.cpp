@@ -15,6 +15,46 @@ static int rig_fail(const std::string& msg) { return frt::set_error(FRT_ERR_INVA
 static bool all_finite(const float* p, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false; return true; }
 static uint32_t path_width(uint32_t path, uint32_t ntargets) { return path == (uint32_t)kRigPathRotation ? 4u : path == (uint32_t)kRigPathWeights ? ntargets : 3u; }
 
+// frt_renderer_animate_cast's entry checks and the layout of its buffer (frt_animation.hpp).
+std::string frt::check_cast_entries(uint32_t n, const frt_cast_entry* e, uint32_t flags, uint32_t allowed_flags, const CastBinding* bindings, size_t nbindings,
+                                    size_t nmeshes, size_t ninstances) {
+    if (n == 0 || n > FRT_MAX_CAST_ENTRIES) return std::to_string(n) + " entries (1 .. FRT_MAX_CAST_ENTRIES)";
+    if (!e) return "null entries";
+    if (flags & ~allowed_flags) return "unknown flag bits";
+    std::vector<uint8_t> named(nbindings, 0), posed(nmeshes, 0), moved(ninstances, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string at = "entry " + std::to_string(k) + ": ";
+        if (e[k].reserved != 0) return at + "reserved must be 0";
+        if (e[k].binding >= nbindings || !bindings || !bindings[e[k].binding].live) return at + "unknown rig binding " + std::to_string(e[k].binding);
+        const CastBinding& b = bindings[e[k].binding];
+        if (named[e[k].binding]) return at + "binding " + std::to_string(e[k].binding) + " is named twice";
+        named[e[k].binding] = 1;
+        if (e[k].clip >= b.nclips) return at + "clip " + std::to_string(e[k].clip) + " out of range (" + std::to_string(b.nclips) + " clips)";
+        if (!std::isfinite(e[k].time)) return at + "time is not finite";
+        std::vector<uint8_t>& seen = b.kind == 0 ? posed : moved;
+        if (b.n && !b.ids) return at + "a binding without ids";
+        for (uint32_t i = 0; i < b.n; ++i) {
+            const uint32_t id = b.ids[i];
+            if (id >= seen.size()) return at + (b.kind == 0 ? "mesh id " : "instance id ") + std::to_string(id) + " out of range";
+            if (seen[id]) return at + (b.kind == 0 ? "mesh " + std::to_string(id) + " is posed by two entries" : "instance " + std::to_string(id) + " is moved by two entries");
+            seen[id] = 1;
+        }
+    }
+    return "";
+}
+CastLayout frt::cast_layout(uint32_t n, const frt_cast_entry* e, const CastBinding* bindings) {
+    CastLayout l;
+    l.first.resize(n); l.first_weight.assign(n, 0u);
+    for (uint32_t k = 0; k < n; ++k) {
+        const CastBinding& b = bindings[e[k].binding];
+        if (b.kind == 0) { l.first[k] = l.cols; l.first_weight[k] = l.nweights; l.cols += 4u * b.njoints; l.nweights += b.ntargets; ++l.nmesh_entries; }
+        else { l.first[k] = l.ninst; l.ninst += b.n; }
+    }
+    auto put = [&l](size_t bytes) { const size_t off = l.bytes; l.bytes += (bytes + 15u) & ~(size_t)15u; return off; };
+    l.ids_off = put((size_t)l.ninst * 4); l.mats_off = put((size_t)l.ninst * 64); l.pal_off = put((size_t)l.cols * 16); l.wt_off = put((size_t)l.nweights * 4);
+    return l;
+}
+
 // "" or what is wrong with the description. Every count is checked before the array it sizes is read.
 static std::string check_rig_desc(const frt_rig_desc* d, uint32_t flags) {
     if (!d) return "null description";

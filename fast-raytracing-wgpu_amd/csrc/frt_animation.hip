@@ -1,5 +1,5 @@
 // frt_animation.hip — the device form of an animated rig (include/frt.h: frt_renderer_bind_rig, _animate, _read_rig_pose, _unbind_rig; DESIGN.md §11,
-// "Animation"). Built with the library's contract flags. No arithmetic is written here: the kernel calls the FRT_HD functions of frt_animation.hpp that
+// "Animation"; _bind_rig_instances, _animate_instances: "Node animation"; _animate_cast: "Animating a cast"). Built with the library's contract flags. No arithmetic is written here: the kernel calls the FRT_HD functions of frt_animation.hpp that
 // frt_rig_evaluate calls on the host, so the palette and the weights have the host's bits.
 //
 // The kernel is ONE workgroup of four waves per rig. (1) Every lane builds the local matrix of a node (sampling the clip's channels of that node),
@@ -81,6 +81,71 @@ __global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* wo
         const m4 m = rig_node_matrix(rig_lds_load(g, node), root, offsets ? offsets + (size_t)16u * k : nullptr);
 #pragma unroll
         for (int c = 0; c < 4; ++c) mats[4u * k + (uint32_t)c] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
+    }
+}
+
+// frt_renderer_animate_cast ("Animating a cast"): the two kernels above as one, ONE WORKGROUP PER ENTRY of the call's table (gridDim.x = entries), so a
+// cast of any size is one launch and its rigs are walked side by side on as many CUs. An entry is 96 bytes, 16-byte aligned, and is read through the
+// block's index alone: its words are the same for every lane (scalar loads), so every branch on them is taken by the whole workgroup, and all of them
+// sit in front of the first barrier or behind the last. Phases (1) and (2) are rig_globals_to_lds; phase (3) is that of the entry's kind, with every
+// store made twice: into the binding's own buffer (what read_rig_pose / read_rig_instances return) and into the entry's slice of the call's buffer,
+// where the instance half finds all ids and matrices, and the mesh half all palettes and weights, as one range each. 64 KiB of static LDS: two
+// workgroups per CU.
+struct CastEntry {
+    const uint32_t* words;      // the binding's rig block
+    uint32_t clip; float time;
+    uint32_t kind, n;           // kRigMeshes | kRigInstances; instances: the bound instances
+    float4* own; float4* all;   // meshes: the palette [4 njoints]; instances: the matrices [4 n] — the binding's, and the slice of the call's buffer
+    float* own_w; float* all_w; // meshes: the weights [ntargets]
+    const uint32_t* nodes; const float* root; const float* offsets;      // instances: as rig_nodes_kernel takes them
+    const uint32_t* ids; uint32_t* all_ids;                              // instances: the binding's ids [n] and their slice of the call's ids
+};
+static_assert(sizeof(CastEntry) == 96 && sizeof(CastEntry) % 16 == 0, "CastEntry layout");
+
+__device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, const m4& m) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float4 q = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
+        own[4u * k + (uint32_t)c] = q;
+        all[4u * k + (uint32_t)c] = q;
+    }
+}
+__global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* table) {
+    __shared__ float4 g[4u * kRigLds];
+    const CastEntry e = table[blockIdx.x];
+    RigView v; v.w = e.words;
+    const RigHeader h = v.h();
+    const uint32_t tid = threadIdx.x;
+    const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (the bind calls refuse a larger rig)
+    if (e.clip >= h.nclips) return;                                  // (animate_cast refuses it; uniform, in front of the first barrier)
+    const bool instances = e.kind == (uint32_t)kRigInstances;
+    if (instances || h.njoints) rig_globals_to_lds(v, h, e.clip, e.time, g, N);
+    if (instances) {
+        for (uint32_t k = tid; k < e.n; k += (uint32_t)kRigBlock) {
+            e.all_ids[k] = e.ids[k];
+            const uint32_t node = e.nodes[k];
+            if (node >= N) {      // (bind_rig_instances has checked it) the call's slice holds what the binding holds
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e.all[4u * k + (uint32_t)c] = e.own[4u * k + (uint32_t)c];
+                continue;
+            }
+            rig_store_twice(e.own, e.all, k, rig_node_matrix(rig_lds_load(g, node), e.root, e.offsets ? e.offsets + (size_t)16u * k : nullptr));
+        }
+        return;
+    }
+    for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
+        const uint32_t n = e.words[h.joint_node + j];
+        if (n >= N) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) e.all[4u * j + (uint32_t)c] = e.own[4u * j + (uint32_t)c];
+            continue;
+        }
+        rig_store_twice(e.own, e.all, j, mul(rig_lds_load(g, n), load_m4(v.f(h.inv_bind) + (size_t)16u * j)));
+    }
+    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) {
+        const float w = rig_morph_weight(v, e.clip, c, e.time);
+        e.own_w[c] = w;
+        e.all_w[c] = w;
     }
 }
 
@@ -246,6 +311,80 @@ int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float
     }
     return frt_renderer_set_mesh_poses(r, n, b->mesh_ids.data(), b->njoints ? b->palette.as<float>() : nullptr, b->njoints,
                                        b->ntargets ? b->weights.as<float>() : nullptr, b->ntargets, flags | FRT_DEFORM_DEVICE);
+}
+
+// The checks (check_cast_entries, then every mesh entry's meshes as animate checks them), the layout of the call's buffer, ONE staged copy — the entry
+// table and the ids of the instance bindings remove_instances has renumbered — ONE launch, then frt_scene_edit.hip's apply_cast. Past the first call of
+// a steady cast nothing here allocates, waits for the stream or copies synchronously: the pinned block's event has long passed when the next call comes.
+int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry* entries, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate_cast", kEditChecks | kRefit)) return rc;
+    std::vector<CastBinding> info(r->rigs.size());
+    for (size_t i = 0; i < r->rigs.size(); ++i) {
+        const RigBinding& b = r->rigs[i];
+        const std::vector<uint32_t>& ids = b.kind == kRigInstances ? b.instance_ids : b.mesh_ids;
+        info[i].live = b.live; info[i].kind = b.kind; info[i].nclips = b.nclips; info[i].njoints = b.njoints; info[i].ntargets = b.ntargets;
+        info[i].ids = ids.data(); info[i].n = (uint32_t)ids.size();
+    }
+    std::string bad = check_cast_entries(n, entries, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(), r->rf.inst.size());
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
+        const RigBinding& b = r->rigs[entries[k].binding];
+        if (b.kind != kRigMeshes) continue;
+        bad = check_rig_meshes(r, b.mesh_ids.data(), (uint32_t)b.mesh_ids.size(), b.palette.p, b.njoints, b.weights.p, b.ntargets);
+        if (!bad.empty()) bad = "entry " + std::to_string(k) + ": " + bad;
+    }
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast: " + bad);
+    const CastLayout l = cast_layout(n, entries, info.data());
+    CastApply call;
+    call.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    {
+        // The kernel writes the bindings' own buffers and the call's buffer only, which nothing but the launches of an earlier call read: on this stream, in front of it.
+        FRT_DEVICE(r);
+        if (const int rc = r->cast.buf.ensure(r, l.bytes)) return rc;
+        uint8_t* all = r->cast.buf.as<uint8_t>();
+        const size_t table_bytes = (size_t)n * sizeof(CastEntry);
+        size_t stale_bytes = 0;
+        for (uint32_t k = 0; k < n; ++k) { const RigBinding& b = r->rigs[entries[k].binding]; if (b.kind == kRigInstances && b.ids_stale) stale_bytes += b.instance_ids.size() * 4; }
+        if (const int rc = r->rig_up.reserve(table_bytes + stale_bytes, table_bytes, r->stream)) return rc;
+        CastEntry* table = reinterpret_cast<CastEntry*>(r->rig_up.h);
+        size_t stale_at = table_bytes;
+        for (uint32_t k = 0; k < n; ++k) {
+            RigBinding& b = r->rigs[entries[k].binding];
+            CastEntry e;
+            memset(&e, 0, sizeof(e));
+            e.words = b.rig.as<const uint32_t>(); e.clip = entries[k].clip; e.time = entries[k].time; e.kind = b.kind;
+            if (b.kind == kRigInstances) {
+                const uint32_t ni = (uint32_t)b.instance_ids.size();
+                if (b.ids_stale) {      // (remove_instances has renumbered the instances) in front of the launch, as animate_instances uploads them
+                    memcpy(r->rig_up.h + stale_at, b.instance_ids.data(), (size_t)ni * 4);
+                    HIP_TRY(hipMemcpyAsync(b.ids.p, r->rig_up.h + stale_at, (size_t)ni * 4, hipMemcpyHostToDevice, r->stream));
+                    stale_at += (size_t)ni * 4;
+                    b.ids_stale = false;
+                }
+                const uint8_t* tab = b.tab.as<const uint8_t>();
+                const size_t node_bytes = ((size_t)ni * 4 + 15u) & ~(size_t)15u;
+                e.n = ni; e.nodes = reinterpret_cast<const uint32_t*>(tab);
+                e.root = b.has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
+                e.offsets = b.has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b.has_root ? 64u : 0u)) : nullptr;
+                e.own = b.mats.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.mats_off) + 4u * (size_t)l.first[k];
+                e.ids = b.ids.as<const uint32_t>(); e.all_ids = reinterpret_cast<uint32_t*>(all + l.ids_off) + l.first[k];
+            } else {
+                e.own = b.palette.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.pal_off) + l.first[k];
+                e.own_w = b.weights.as<float>(); e.all_w = reinterpret_cast<float*>(all + l.wt_off) + l.first_weight[k];
+                for (uint32_t m : b.mesh_ids)
+                    call.meshes.push_back(CastMesh{m, b.njoints ? reinterpret_cast<const float*>(e.all) : nullptr, b.njoints, b.ntargets ? e.all_w : nullptr, b.ntargets});
+            }
+            table[k] = e;
+        }
+        HIP_TRY(hipMemcpyAsync(r->rig_up.d, r->rig_up.h, table_bytes, hipMemcpyHostToDevice, r->stream));
+        if (const int rc = r->rig_up.mark(r->stream)) return rc;
+        hipLaunchKernelGGL(rig_cast_kernel, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const CastEntry*>(r->rig_up.d));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate_cast: ") + hipGetErrorString(e)); }
+        call.ninst = l.ninst; call.ids = reinterpret_cast<const uint32_t*>(all + l.ids_off); call.mats = reinterpret_cast<const float*>(all + l.mats_off);
+        if (l.cols) { call.palettes = reinterpret_cast<const float*>(all + l.pal_off); call.cols = l.cols; }
+        if (l.nweights) { call.weights = reinterpret_cast<const float*>(all + l.wt_off); call.nweights = l.nweights; }
+    }
+    return apply_cast(r, call);
 }
 
 int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out) {

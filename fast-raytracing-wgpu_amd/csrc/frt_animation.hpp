@@ -182,3 +182,27 @@ struct frt_rig {
     std::vector<float> clip_durations;
     frt::RigView view() const { frt::RigView v; v.w = words.data(); return v; }
 };
+
+// frt_renderer_animate_cast ("Animating a cast"), the host part that reads no device: what the call checks about its entries and where each entry's
+// outputs lie in the one buffer of the call. A caller describes its bindings by CastBinding (frt_animation.hip fills them from the renderer's list).
+struct frt_cast_entry;
+namespace frt {
+struct CastBinding {
+    bool live = false; uint32_t kind = 0, nclips = 0, njoints = 0, ntargets = 0;
+    const uint32_t* ids = nullptr; uint32_t n = 0;      // the meshes it poses (kind 0) or the instances it moves (kind 1)
+};
+// "" or why the call is refused: n == 0 or above FRT_MAX_CAST_ENTRIES, null entries, reserved != 0, flag bits outside `allowed_flags`, an unknown or
+// unbound binding, a binding named twice, a clip out of range, a time that is not finite, a mesh (of `nmeshes`) two mesh entries would pose, an
+// instance (of `ninstances`) two instance entries would move, an id out of range. Every count is checked before the array it sizes is read.
+std::string check_cast_entries(uint32_t n, const frt_cast_entry* entries, uint32_t flags, uint32_t allowed_flags, const CastBinding* bindings, size_t nbindings,
+                               size_t nmeshes, size_t ninstances);
+// Where entry k's outputs begin: `first[k]` counts instances (an instance entry: its ids and matrices) or palette columns of four floats (a mesh
+// entry), `first_weight[k]` morph weights. The buffer is [ids: 4 ninst | matrices: 64 ninst | palettes: 16 cols | weights: 4 nweights], every section
+// 16-byte aligned. For entries check_cast_entries has accepted.
+struct CastLayout {
+    std::vector<uint32_t> first, first_weight;
+    uint32_t ninst = 0, cols = 0, nweights = 0, nmesh_entries = 0;
+    size_t ids_off = 0, mats_off = 0, pal_off = 0, wt_off = 0, bytes = 0;
+};
+CastLayout cast_layout(uint32_t n, const frt_cast_entry* entries, const CastBinding* bindings);
+}

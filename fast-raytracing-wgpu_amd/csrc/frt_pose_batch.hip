@@ -5,8 +5,9 @@
 // Each kernel is its single-mesh counterpart (mesh_morph_kernel, mesh_skin_kernel, deform_validate_kernel, deform_copy_in_kernel, vertex_normal_kernel,
 // mesh_deform_kernel) with the mesh's offsets and buffers taken from the thread's segment instead of the launch arguments.
 // One thread per vertex or triangle of the concatenation, consecutive threads on consecutive elements, vector loads and stores, no LDS, no fences: what a
-// launch writes, the next launch on the stream reads behind the kernel boundary. The segment table is at most FRT_MAX_POSE_MESHES records of 48 bytes
-// and the search reads the same few records in every lane of a wave that lies inside one mesh.
+// launch writes, the next launch on the stream reads behind the kernel boundary. The segment table holds records of 80 bytes and the search reads the
+// same few records in every lane of a wave that lies inside one mesh. A segment names the palette and the weights it is posed under: a wave that holds
+// vertices of several meshes may pose them under several palettes (frt_renderer_animate_cast), each lane under its own segment's.
 #include "frt_pose_batch.hpp"
 #include "frt_vertex_normal.hpp"
 #include <algorithm>
@@ -26,46 +27,47 @@ __device__ inline bool pose_finite4(float4 q) {
            ((__float_as_uint(q.z) & 0x7f800000u) != 0x7f800000u) && ((__float_as_uint(q.w) & 0x7f800000u) != 0x7f800000u);
 }
 
-// Thread g: vertex g of the concatenation, morphed from its mesh's base into the scratch the next launch reads. The first ntargets threads test one
-// device weight each. (The loads come in front of every store, as in mesh_morph_kernel.)
+// Thread g: vertex g of the concatenation, morphed from its mesh's base into the scratch the next launch reads (`morphed` when its mesh is skinned
+// afterwards, else the call's posed positions). The first check_nweights threads test one device weight each. (The loads come in front of every
+// store, as in mesh_morph_kernel.)
 __global__ void __launch_bounds__(kPoseBlock) pose_batch_morph_kernel(PoseBatchArgs a) {
     const uint32_t g = blockIdx.x * (uint32_t)kPoseBlock + threadIdx.x;
-    float4* out = a.morphed ? a.morphed : a.skinned;
     if (g < a.total && g < a.scratch_len) {
         const PoseSegment s = pose_segment_of(a.seg, a.nseg, g);
         const uint32_t v = g - s.vert_begin;
         if (v < s.nverts && s.morph) {
+            float4* out = a.morphed && s.skin ? a.morphed : a.skinned;
             const float4 p = reinterpret_cast<const float4*>(s.morph)[v];
             const float* deltas = reinterpret_cast<const float*>(s.morph + 16u * (size_t)s.nverts);
             const float pb[4] = {p.x, p.y, p.z, p.w};
             float o[4];
-            morphed_position(pb, deltas + 3u * (size_t)v, 3u * (size_t)s.nverts, a.weights, a.ntargets, o);
+            morphed_position(pb, deltas + 3u * (size_t)v, 3u * (size_t)s.nverts, s.weights, s.ntargets, o);
             out[g] = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
     // (every thread that raises the flag stores the same word: a plain store, no atomic)
-    if (a.check_weights && g < a.ntargets && (__float_as_uint(a.weights[g]) & 0x7f800000u) == 0x7f800000u) a.reject[0] = 1u;
+    if (a.check_weights && g < a.check_nweights && (__float_as_uint(a.check_weights[g]) & 0x7f800000u) == 0x7f800000u) a.reject[0] = 1u;
 }
 
-// Thread g: vertex g of the concatenation, skinned from its mesh's bind pose (or from the morph launch's result) into `skinned`. The first 4 njoints
+// Thread g: vertex g of the concatenation, skinned from its mesh's bind pose (or from the morph launch's result) into `skinned`. The first check_cols
 // threads test one float4 of a device palette each.
 __global__ void __launch_bounds__(kPoseBlock) pose_batch_skin_kernel(PoseBatchArgs a) {
     const uint32_t g = blockIdx.x * (uint32_t)kPoseBlock + threadIdx.x;
-    if (a.check_palette && g < 4u * a.njoints && !pose_finite4(a.palette[g])) a.reject[0] = 1u;
+    if (a.check_palette && g < a.check_cols && !pose_finite4(a.check_palette[g])) a.reject[0] = 1u;
     if (g >= a.total || g >= a.scratch_len) return;
     const PoseSegment s = pose_segment_of(a.seg, a.nseg, g);
     const uint32_t v = g - s.vert_begin;
     if (v >= s.nverts || !s.skin) return;
     const float4* weights = reinterpret_cast<const float4*>(s.skin + 16u * (size_t)s.nverts);
     const uint2* joints = reinterpret_cast<const uint2*>(s.skin + 32u * (size_t)s.nverts);
-    const float4 p = a.morphed ? a.morphed[g] : reinterpret_cast<const float4*>(s.skin)[v], wt = weights[v];
+    const float4 p = a.morphed && s.morph ? a.morphed[g] : reinterpret_cast<const float4*>(s.skin)[v], wt = weights[v];
     const uint2 jw = joints[v];
     const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
-    if (j[0] >= a.njoints || j[1] >= a.njoints || j[2] >= a.njoints || j[3] >= a.njoints) { a.reject[0] = 1u; return; }
+    if (j[0] >= s.njoints || j[1] >= s.njoints || j[2] >= s.njoints || j[3] >= s.njoints) { a.reject[0] = 1u; return; }
     float m[4][16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float4* c = a.palette + 4u * (size_t)j[k];
+        const float4* c = s.palette + 4u * (size_t)j[k];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { const float4 q = c[i]; m[k][4 * i] = q.x; m[k][4 * i + 1] = q.y; m[k][4 * i + 2] = q.z; m[k][4 * i + 3] = q.w; }
     }
@@ -140,7 +142,11 @@ __global__ void __launch_bounds__(kPoseBlock) pose_batch_triangle_kernel(SceneVi
     if (j >= tri_count || si >= a.nseg) return;
     const PoseSegment s = a.seg[si];
     if (j >= s.ntris) return;
-    const float m[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
+    float m[12] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, m2.x, m2.y, m2.z, m2.w};
+    if (a.inst_m) {      // the matrix table's columns, as transform_triangles_kernel reads them: the twelve floats the mirror would hold
+        if (inst >= a.num_inst) return;
+        for (int c = 0; c < 4; ++c) { const float4 q = a.inst_m[4u * (size_t)inst + (uint32_t)c]; m[3 * c] = q.x; m[3 * c + 1] = q.y; m[3 * c + 2] = q.z; }
+    }
     uint32_t v[3];
     float4 p[3];
     float w[3][3];
@@ -170,21 +176,21 @@ __global__ void __launch_bounds__(kPoseBlock) pose_batch_triangle_kernel(SceneVi
 static inline dim3 pose_grid(uint32_t threads) { return dim3((threads + kPoseBlock - 1) / kPoseBlock); }
 
 hipError_t launch_pose_batch(const SceneView& sc, const PoseBatchArgs& a, hipStream_t stream) {
-    const bool morph = a.weights != nullptr, skin = a.palette != nullptr;
+    const bool morph = a.morphs != 0, skin = a.skins != 0;
     if (a.nseg == 0 || a.total == 0) return hipSuccess;
     if (!morph && !skin) return hipErrorInvalidValue;
     if (a.total > 0xFFFFFF00u || a.work > 0xFFFFFF00u) return hipErrorInvalidValue;      // (the work-item index is 32 bits)
-    if (skin && (a.njoints == 0 || a.njoints > 0x10000u)) return hipErrorInvalidValue;  // (a joint index is 16 bits)
-    if (morph && (a.ntargets == 0 || a.ntargets > FRT_MAX_MORPH_TARGETS)) return hipErrorInvalidValue;
+    if ((a.check_palette && !skin) || (a.check_weights && !morph)) return hipErrorInvalidValue;
+    if (a.check_cols > 0xFFFFFF00u || a.check_nweights > 0xFFFFFF00u) return hipErrorInvalidValue;
     if ((morph && skin) != (a.morphed != nullptr)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.reject, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     if (morph) {
-        hipLaunchKernelGGL(pose_batch_morph_kernel, pose_grid(a.check_weights ? std::max(a.total, a.ntargets) : a.total), dim3(kPoseBlock), 0, stream, a);
+        hipLaunchKernelGGL(pose_batch_morph_kernel, pose_grid(a.check_weights ? std::max(a.total, a.check_nweights) : a.total), dim3(kPoseBlock), 0, stream, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (skin) {
-        hipLaunchKernelGGL(pose_batch_skin_kernel, pose_grid(a.check_palette ? std::max(a.total, 4u * a.njoints) : a.total), dim3(kPoseBlock), 0, stream, a);
+        hipLaunchKernelGGL(pose_batch_skin_kernel, pose_grid(a.check_palette ? std::max(a.total, a.check_cols) : a.total), dim3(kPoseBlock), 0, stream, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(pose_batch_validate_kernel, pose_grid(a.total), dim3(kPoseBlock), 0, stream, a);

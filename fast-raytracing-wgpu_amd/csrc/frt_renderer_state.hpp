@@ -248,6 +248,20 @@ struct RigBinding {
     bool has_root = false, has_offsets = false, ids_stale = false;
     void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats}) b->release(r); }
 };
+// What frt_renderer_animate_cast adds ("Animating a cast"): one device buffer, grown on demand and never shrunk, that holds what the halves of a call
+// read as ONE range each — [ids of every instance entry | their matrices | the palettes of every mesh entry | their weights] — beside the bindings' own
+// buffers, which the kernel writes too. The entry table goes through frt_renderer::rig_up, its device block included.
+struct CastState { OwnedBuf buf; };
+// One mesh of a cast's mesh half and what it is posed under (device memory: a slice of CastState::buf), and the whole call as frt_scene_edit.hip's
+// apply_cast takes it: the instance half's records, the mesh half's meshes and the one range of palette columns and of weights the pose batch tests.
+struct CastMesh { uint32_t mesh; const float* palette; uint32_t njoints; const float* weights; uint32_t ntargets; };
+struct CastApply {
+    uint32_t ninst = 0; const uint32_t* ids = nullptr; const float* mats = nullptr;
+    std::vector<CastMesh> meshes;
+    const float* palettes = nullptr; uint32_t cols = 0;
+    const float* weights = nullptr; uint32_t nweights = 0;
+    bool recompute = false;
+};
 
 struct frt_renderer {
     int device = 0;
@@ -323,6 +337,7 @@ struct frt_renderer {
     Staging look;
     std::vector<RigBinding> rigs;          // frt_renderer_bind_rig
     Staging rig_up;                        // the pinned block a rig is uploaded through
+    CastState cast;                        // frt_renderer_animate_cast
     void* buf(int b) const { return is_extra(b) ? extras + off[b] : arena + off[b]; }
     bool pipeline() const { return ahead != nullptr; }
 };
@@ -360,4 +375,5 @@ enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditCheck
 int check_entry(const frt_renderer* r, const std::string& what, unsigned parts);
 uint32_t pool_count(const frt_renderer* r, int pool);             // elements of a pool (PoolState) in use
 int ensure_normals(frt_renderer* r);                              // PoolState::d_normals exists afterwards
+int apply_cast(frt_renderer* r, const CastApply& c);              // frt_scene_edit.hip: the two halves of frt_renderer_animate_cast in one call frame
 }

@@ -428,6 +428,22 @@ int frt_renderer_set_instance_transforms(frt_renderer* r, uint32_t n, const uint
         return refit_levels(r);
     });
 }
+// The body of a device-input call, behind ensure_transform_tables: n >= 1 records in device memory through the launches of frt_refit_device.hpp. The
+// scene extent and the refit follow in the caller (refit_scene), once.
+static int transform_instances_device(frt_renderer* r, uint32_t n, const uint32_t* ids, const float* mats) {
+    RefitState& f = r->rf;
+    DeviceTransformState& x = f.xf;
+    const TransformInput a{ids, reinterpret_cast<const float4*>(mats), n, (uint32_t)f.inst.size(), x.consts.as<InstanceConst>(), x.m.as<float4>(), x.last.as<uint32_t>(), x.d_reject,
+                           f.d_pos, f.d_slot_of, pool_cap(r, kPoolVerts), pool_cap(r, kPoolIndices)};
+    HIP_TRY(launch_device_transforms(r->sv, a, r->stream));
+    x.mirror_stale = true;      // (a rejected call leaves the table as it was: reading it back then changes nothing)
+    return FRT_OK;
+}
+// What follows a body that wrote triangles, once per call: the scene extent and both trees refit.
+static int refit_scene(frt_renderer* r) {
+    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(r->rf.d_ext), r->stream));
+    return refit_levels(r);
+}
 // Device input (FRT_TRANSFORM_DEVICE): nothing of the call's data is seen by the host. The entry checks, the stream order and the dropped speculation are
 // the host form's; the kernels of frt_refit_device.hpp do the rest from the renderer's device tables, and the host's mirror of the matrices goes stale.
 static const uint32_t kMaxDeviceTransforms = 1u << 26;
@@ -442,16 +458,10 @@ int frt_renderer_set_instance_transforms_ex(frt_renderer* r, uint32_t n, const u
         if (const int rc = check_device_input(r, mats, (size_t)n * 64, 16, "set_instance_transforms", "matrices", "FRT_TRANSFORM_DEVICE")) return rc;
     }
     return edit_frame(r, true, [&]() -> int {
-        RefitState& f = r->rf;
         if (n == 0) return FRT_OK;
         if (const int rc = ensure_transform_tables(r)) return rc;
-        DeviceTransformState& x = f.xf;
-        const TransformInput a{ids, reinterpret_cast<const float4*>(mats), n, (uint32_t)f.inst.size(), x.consts.as<InstanceConst>(), x.m.as<float4>(), x.last.as<uint32_t>(), x.d_reject,
-                               f.d_pos, f.d_slot_of, pool_cap(r, kPoolVerts), pool_cap(r, kPoolIndices)};
-        HIP_TRY(launch_device_transforms(r->sv, a, r->stream));
-        x.mirror_stale = true;      // (a rejected call leaves the table as it was: reading it back then changes nothing)
-        HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
-        return refit_levels(r);
+        if (const int rc = transform_instances_device(r, n, ids, mats)) return rc;
+        return refit_scene(r);
     });
 }
 
@@ -787,19 +797,27 @@ struct PoseBatchCall {
     const float* palette = nullptr; uint32_t njoints = 0;      // null: no skin launch
     const float* weights = nullptr; uint32_t ntargets = 0;     // null: no morph launch
     bool on_device = false, recompute = false;
+    // frt_renderer_animate_cast: mesh k is posed under per_mesh[k]'s palette and weights (device memory; mesh_ids is null and per_mesh[k].mesh names
+    // the mesh). `palette` [check_cols float4] and `weights` [check_nweights] are then the one range each that holds them all, on_device is set, and
+    // the triangles take their matrices from the device matrix table, which the caller has made current: the host's mirror is not read.
+    const CastMesh* per_mesh = nullptr;
+    uint32_t check_cols = 0, check_nweights = 0;
+    uint32_t mesh(uint32_t k) const { return per_mesh ? per_mesh[k].mesh : mesh_ids[k]; }
 };
-// What follows the checks of a batch, inside its call frame: the segment table, the instance records of every mesh of the batch, one staged copy, the
-// launches of frt_pose_batch.hpp and, once, the scene extent and the refit.
-static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
+// What follows the checks of a batch, inside its call frame: the segment table, the instance records of every mesh of the batch, one staged copy and
+// the launches of frt_pose_batch.hpp. `changed`: a triangle was written, so the scene extent and the refit have to follow (pose_meshes; apply_cast).
+static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& changed) {
     RefitState& f = r->rf;
     int rc;
-    if ((rc = sync_matrix_mirror(r))) return rc;      // (the instances' matrices are read below)
+    changed = false;
+    if (!c.per_mesh && (rc = sync_matrix_mirror(r))) return rc;      // (the instances' matrices are read below)
     const uint32_t cap_verts = pool_cap(r, kPoolVerts), cap_indices = pool_cap(r, kPoolIndices);
     std::vector<PoseSegment> seg(c.n);
     std::vector<int> seg_of_mesh(f.vert_count.size(), -1);
     uint64_t total = 0;
+    bool any_skin = false, any_morph = false;
     for (uint32_t k = 0; k < c.n; ++k) {
-        const uint32_t m = c.mesh_ids[k];
+        const uint32_t m = c.mesh(k);
         if ((uint64_t)f.pos_offset[m] + f.vert_count[m] > cap_verts || (uint64_t)f.attr_offset[m] + f.vert_count[m] > cap_verts)
             return fail(FRT_ERR_STATE, "set_mesh_poses: mesh " + std::to_string(m) + " does not lie inside the vertex pool");
         if ((uint64_t)f.index_offset[m] + 3ull * f.mesh_tris[m] > cap_indices)
@@ -808,9 +826,15 @@ static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
         PoseSegment& s = seg[k];
         s.vert_begin = (uint32_t)total; s.nverts = f.vert_count[m]; s.pos_offset = f.pos_offset[m]; s.attr_offset = f.attr_offset[m];
         s.index_offset = f.index_offset[m]; s.ntris = f.mesh_tris[m];
-        s.skin = c.palette ? static_cast<const uint8_t*>(f.skins[m].buf.p) : nullptr;
-        s.morph = c.weights ? static_cast<const uint8_t*>(f.morphs[m].buf.p) : nullptr;
+        const bool skin = c.per_mesh ? c.per_mesh[k].palette != nullptr : c.palette != nullptr, morph = c.per_mesh ? c.per_mesh[k].weights != nullptr : c.weights != nullptr;
+        s.skin = skin ? static_cast<const uint8_t*>(f.skins[m].buf.p) : nullptr;
+        s.morph = morph ? static_cast<const uint8_t*>(f.morphs[m].buf.p) : nullptr;
         s.adj = c.recompute ? f.adj[m] : nullptr;
+        s.njoints = skin ? (c.per_mesh ? c.per_mesh[k].njoints : c.njoints) : 0u;
+        s.ntargets = morph ? (c.per_mesh ? c.per_mesh[k].ntargets : c.ntargets) : 0u;
+        s.palette = c.per_mesh ? reinterpret_cast<const float4*>(c.per_mesh[k].palette) : nullptr;      // (a batch under one palette: set below, once its place is known)
+        s.weights = c.per_mesh ? c.per_mesh[k].weights : nullptr;
+        any_skin = any_skin || skin; any_morph = any_morph || morph;
         seg_of_mesh[m] = (int)k;
         total += s.nverts;
         if (total > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 vertices in one call");
@@ -823,18 +847,21 @@ static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
         if (in.mesh_id >= seg_of_mesh.size() || seg_of_mesh[in.mesh_id] < 0) continue;
         DeformInstance d;
         d.id = (uint32_t)i; d.first_tri = in.first_tri; d.tri_count = in.tri_count; d.work_begin = (uint32_t)work; work += in.tri_count;
-        for (int col = 0; col < 4; ++col) for (int a = 0; a < 3; ++a) d.m[3 * col + a] = in.m[4 * col + a];
+        for (int col = 0; col < 4; ++col) for (int a = 0; a < 3; ++a) d.m[3 * col + a] = c.per_mesh ? 0.0f : in.m[4 * col + a];      // (a cast: the triangle launch reads the table)
         rec.push_back(d);
         rec_seg.push_back((uint32_t)seg_of_mesh[in.mesh_id]);
     }
     if (work > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 triangles in one call");
     if ((rc = f.skinned.ensure(r, (size_t)total * 16))) return rc;
-    if (c.palette && c.weights && (rc = f.morphed.ensure(r, (size_t)total * 16))) return rc;
+    if (any_skin && any_morph && (rc = f.morphed.ensure(r, (size_t)total * 16))) return rc;
     if ((rc = ensure_reject_words(r, f.d_reject))) return rc;
     const PoseBatchLayout l(c.n, rec.size(), c.palette && !c.on_device ? (size_t)c.njoints * 64 : 0, c.weights && !c.on_device ? (size_t)c.ntargets * 4 : 0,
                             c.recompute ? (size_t)total * 16 : 0);
     if ((rc = f.def.reserve(l.h_total, l.d_total, r->stream))) return rc;
     uint8_t* h = f.def.h; uint8_t* d = f.def.d;
+    const float4* palette = !c.palette ? nullptr : reinterpret_cast<const float4*>(c.on_device ? reinterpret_cast<const uint8_t*>(c.palette) : d + l.pal.off);
+    const float* weights = !c.weights ? nullptr : c.on_device ? c.weights : reinterpret_cast<const float*>(d + l.wt.off);
+    if (!c.per_mesh) for (PoseSegment& s : seg) { s.palette = palette; s.weights = weights; }      // every segment under the one palette and the one weight vector
     memset(h, 0, l.h_total);      // (the padding between the sections is copied with them)
     memcpy(h + l.seg.off, seg.data(), l.seg.bytes);
     if (l.rec.bytes) memcpy(h + l.rec.off, rec.data(), l.rec.bytes);
@@ -846,9 +873,10 @@ static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
     PoseBatchArgs a;
     memset(&a, 0, sizeof(a));
     a.seg = reinterpret_cast<const PoseSegment*>(d + l.seg.off); a.nseg = c.n; a.total = (uint32_t)total;
-    if (c.palette) { a.palette = reinterpret_cast<const float4*>(c.on_device ? reinterpret_cast<const uint8_t*>(c.palette) : d + l.pal.off); a.njoints = c.njoints; a.check_palette = c.on_device ? 1u : 0u; }
-    if (c.weights) { a.weights = c.on_device ? c.weights : reinterpret_cast<const float*>(d + l.wt.off); a.ntargets = c.ntargets; a.check_weights = c.on_device ? 1u : 0u; }
-    a.morphed = c.palette && c.weights ? f.morphed.as<float4>() : nullptr;
+    a.skins = any_skin ? 1u : 0u; a.morphs = any_morph ? 1u : 0u;
+    if (palette && c.on_device) { a.check_palette = palette; a.check_cols = c.per_mesh ? c.check_cols : 4u * c.njoints; }
+    if (weights && c.on_device) { a.check_weights = weights; a.check_nweights = c.per_mesh ? c.check_nweights : c.ntargets; }
+    a.morphed = any_skin && any_morph ? f.morphed.as<float4>() : nullptr;
     a.skinned = f.skinned.as<float4>();
     a.scratch_len = (uint32_t)std::min<size_t>(std::min(f.skinned.bytes, a.morphed ? f.morphed.bytes : f.skinned.bytes) / 16, 0xFFFFFFFFu);
     a.out_pos = const_cast<float4*>(f.d_pos);
@@ -859,10 +887,15 @@ static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
     a.rec = reinterpret_cast<const DeformInstance*>(d + l.rec.off); a.rec_seg = reinterpret_cast<const uint32_t*>(d + l.rec_seg.off);
     a.nrec = (uint32_t)rec.size(); a.work = (uint32_t)work;
     a.slot_of = f.d_slot_of;
+    if (c.per_mesh) { a.inst_m = f.xf.m.as<const float4>(); a.num_inst = (uint32_t)f.inst.size(); }
     HIP_TRY(launch_pose_batch(r->sv, a, r->stream));
-    if (work == 0) return FRT_OK;      // no instance of any mesh of the batch: no triangle changes
-    HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
-    return refit_levels(r);
+    changed = work != 0;      // no instance of any mesh of the batch: no triangle changes
+    return FRT_OK;
+}
+static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
+    bool changed = false;
+    if (const int rc = pose_meshes_body(r, c, changed)) return rc;
+    return changed ? refit_scene(r) : FRT_OK;
 }
 // The entry and the flags, the batch itself (check_pose_batch), every mesh as its single call checks it, then the device pointers. The entries of a host
 // palette and of host weights are the same for every mesh and are read once.
@@ -887,6 +920,30 @@ int frt_renderer_set_mesh_poses(frt_renderer* r, uint32_t n, const uint32_t* mes
     if (morph) { c.weights = morph_weights; c.ntargets = ntargets; }
     return edit_frame(r, true, [&]() -> int { return pose_meshes(r, c); });
 }
+
+} // extern "C"
+// frt_renderer_animate_cast (frt_animation.hip; DESIGN.md §11, "Animating a cast") behind its checks and its rig launch: one call frame, so the
+// speculation is dropped once; the matrix table current; the instance half as one device-input transform; the mesh half as one pose batch that reads
+// the table (the mirror, stale from the first half on, is not read back: no wait for the stream); then, if either wrote a triangle, one scene extent
+// and one refit. The halves reject on their own, each through its own flag and counter.
+int frt::apply_cast(frt_renderer* r, const CastApply& c) {
+    return edit_frame(r, true, [&]() -> int {
+        if (const int rc = ensure_transform_tables(r)) return rc;
+        bool moved = false, posed = false;
+        if (c.ninst) {
+            if (const int rc = transform_instances_device(r, c.ninst, c.ids, c.mats)) return rc;
+            moved = true;
+        }
+        if (!c.meshes.empty()) {
+            PoseBatchCall p;
+            p.n = (uint32_t)c.meshes.size(); p.per_mesh = c.meshes.data(); p.on_device = true; p.recompute = c.recompute;
+            p.palette = c.palettes; p.check_cols = c.cols; p.weights = c.weights; p.check_nweights = c.nweights;
+            if (const int rc = pose_meshes_body(r, p, posed)) return rc;
+        }
+        return moved || posed ? refit_scene(r) : FRT_OK;
+    });
+}
+extern "C" {
 
 // ------------------------------------------------------------------------------------------------ materials, lights, textures
 // The speculation is dropped: its G-buffer and T-trace have read the materials. All four calls stage through r->look: what a call uploads is written

@@ -90,6 +90,13 @@ QUERY_MAX_RAYS = 1 << 26
 DEFORM_RECOMPUTE_NORMALS, DEFORM_DEVICE = 1, 2      # include/frt.h: FRT_DEFORM_*
 TRANSFORM_DEVICE = 1                                # include/frt.h: FRT_TRANSFORM_DEVICE
 MAX_RIG_NODES = 1024                                # include/frt.h: FRT_MAX_RIG_NODES
+MAX_CAST_ENTRIES = 4096                             # include/frt.h: FRT_MAX_CAST_ENTRIES
+
+
+class CastEntry(C.Structure):                       # include/frt.h: frt_cast_entry
+    _fields_ = [("binding", C.c_uint32), ("clip", C.c_uint32), ("time", C.c_float), ("reserved", C.c_uint32)]
+
+
 RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}      # include/frt.h: FRT_RIG_PATH_*
 RIG_INTERPOLATIONS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}              # include/frt.h: FRT_RIG_*
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
@@ -224,6 +231,7 @@ SYMBOLS = {
     "frt_renderer_bind_rig_instances": (C.c_int, [_P, _P, _U32, _P, _P, _P, _P, C.POINTER(_U32)]),
     "frt_renderer_animate_instances": (C.c_int, [_P, _U32, _U32, C.c_float]),
     "frt_renderer_read_rig_instances": (C.c_int, [_P, _U32, _P]),
+    "frt_renderer_animate_cast": (C.c_int, [_P, _U32, _P, _U32]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

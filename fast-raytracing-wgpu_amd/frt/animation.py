@@ -144,3 +144,28 @@ def node_args(nodes, root, offsets):
     if offsets is not None:
         offsets = _f32(np.asarray(offsets, np.float32).reshape(-1, 16), (nodes.size, 16), "offsets")
     return nodes.size, nodes, root, offsets
+
+
+def host_cast(target, entries, normals="recompute"):
+    """What SceneBuilder.animate_cast and MultiRenderer.animate_cast do ("Animating a cast"): every entry is the arguments of
+    `target`'s animate, (rig, mesh_ids, clip, t), or of its animate_instances, (rig, instance_ids, nodes, clip, t[, root[, offsets]]), as a tuple
+    or as a dict by name (a dict with "nodes" is an instance entry). The instance entries are applied first, in the order given, then the mesh
+    entries: the order of the device call's two halves."""
+    inst, mesh = [], []
+    for k, e in enumerate(entries):
+        if isinstance(e, dict):
+            (inst if "nodes" in e else mesh).append(dict(e))
+            continue
+        e = tuple(e)
+        if len(e) == 4:
+            mesh.append(dict(zip(("rig", "mesh_ids", "clip", "t"), e)))
+        elif 5 <= len(e) <= 7:
+            inst.append(dict(zip(("rig", "instance_ids", "nodes", "clip", "t", "root", "offsets"), e)))
+        else:
+            raise FrtError(f"animate_cast: entry {k} has {len(e)} fields (4: a mesh entry, 5 to 7: an instance entry)")
+    if not inst and not mesh:
+        raise FrtError("animate_cast: no entries")
+    for e in inst:
+        target.animate_instances(**e)
+    for e in mesh:
+        target.animate(**e, normals=normals)

@@ -441,6 +441,18 @@ class Renderer(_HostQueries, _SceneGrowth):
         check(lib().frt_renderer_read_rig_instances(self._h, int(binding), out.ctypes.data if out.size else None))
         return out
 
+    # ---- a whole cast (include/frt.h: frt_renderer_animate_cast; DESIGN.md section 11, "Animating a cast")
+    def animate_cast(self, entries, normals="recompute"):
+        """Animate several bindings of either kind in one call: `entries` is an iterable of (binding, clip, t), a clip a number or a name of the
+        bound rig, in any order. One kernel evaluates every entry (one workgroup each); the instance entries are applied first, as one
+        set_instance_transforms with device tensors, then the mesh entries as one pose batch, each half all or nothing (transform_rejects() /
+        deform_rejects() count a rejected half once); one refit serves the call. Bit for bit what animate_instances for the instance entries
+        followed by animate for the mesh entries leave. Asynchronous; the call does not wait for the stream."""
+        from ._lib import CastEntry
+        rows = [(int(b), self._bound_rig("animate_cast", b).clip_index(clip), float(t)) for b, clip, t in entries]
+        table = (CastEntry * max(len(rows), 1))(*[CastEntry(b, c, t, 0) for b, c, t in rows])
+        check(lib().frt_renderer_animate_cast(self._h, len(rows), table, deform_flags(normals)))
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -777,6 +789,12 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
     def animate_instances(self, rig, instance_ids, nodes, clip, t, root=None, offsets=None):
         """rig.evaluate_nodes on the host, then set_instance_transforms on every strip's replica."""
         self.set_instance_transforms(instance_ids, rig.evaluate_nodes(clip, t, nodes, root, offsets))
+
+    def animate_cast(self, entries, normals="recompute"):
+        """The host form of Renderer.animate_cast (frt.animation.host_cast): the instance entries through animate_instances, then the mesh entries
+        through animate, on every strip's replica."""
+        from .animation import host_cast
+        host_cast(self, entries, normals)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

@@ -495,6 +495,14 @@ class SceneBuilder:
     def animate_instances(self, rig, instance_ids, nodes, clip, t, root=None, offsets=None):
         return self.set_instance_transforms(instance_ids, rig.evaluate_nodes(clip, t, nodes, root, offsets))
 
+    # A whole cast ("Animating a cast"): the host form of Renderer.animate_cast. An entry is the arguments of animate,
+    # (rig, mesh_ids, clip, t), or of animate_instances, (rig, instance_ids, nodes, clip, t[, root[, offsets]]), or a dict of them by name; the
+    # instance entries are applied first, then the mesh entries, through those two calls.
+    def animate_cast(self, entries, normals="recompute"):
+        from .animation import host_cast
+        host_cast(self, entries, normals)
+        return self
+
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
     # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
     # base in target order and applies the result as set_mesh_vertices does. Host copy only.

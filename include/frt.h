@@ -649,6 +649,24 @@ frt_rig* frt_rig_from_model_nodes(const frt_model* m);
 int frt_renderer_bind_rig_instances(frt_renderer* r, const frt_rig* rig, uint32_t n, const uint32_t* instance_ids, const uint32_t* nodes, const float* root16, const float* offsets16n, uint32_t* binding_out);
 int frt_renderer_animate_instances(frt_renderer* r, uint32_t binding, uint32_t clip, float time);
 int frt_renderer_read_rig_instances(frt_renderer* r, uint32_t binding, float* mats_out16n);
+/* Animate a whole cast in one call ("Animating a cast"): entries [n], each a binding of either kind (frt_renderer_bind_rig,
+ * frt_renderer_bind_rig_instances), a clip of its rig and a time, in any order. Asynchronous, between frames, on the main stream, under the ordering
+ * and state rules of frt_renderer_animate. One kernel, one workgroup per entry, evaluates every entry into its binding's own buffers (what
+ * read_rig_pose / read_rig_instances return) and into one buffer of the call. Then, inside one call frame:
+ *   the instance half: every instance entry's matrices as ONE frt_renderer_set_instance_transforms_ex(.., FRT_TRANSFORM_DEVICE) over their
+ *   concatenation, all or nothing (a singular or non-finite matrix anywhere applies none of it and counts one on transform_rejects);
+ *   the mesh half: every mesh entry's meshes as ONE pose batch, each mesh under its own entry's palette and weights, all or nothing (a non-finite
+ *   palette entry, weight or posed coordinate of any character applies none of it and counts one on deform_rejects); its triangles take the matrices
+ *   the instance half left, from the device's matrix table, so the call does not wait for the stream;
+ *   one scene-extent pass and one refit, if either half wrote a triangle.
+ * The halves are independent, as two calls are. With every entry accepted the replica is, bit for bit, what frt_renderer_animate_instances for the
+ * instance entries followed by frt_renderer_animate for the mesh entries leave (each group in any order). `flags`: FRT_DEFORM_RECOMPUTE_NORMALS or 0.
+ * FRT_ERR_INVALID_ARG, nothing enqueued: n == 0 or above FRT_MAX_CAST_ENTRIES, entries == NULL, reserved != 0, unknown flag bits, an unknown or
+ * unbound binding, a binding named twice, a mesh two mesh entries would pose, an instance two instance entries would move, a clip out of range, a
+ * time that is not finite, a mesh that no longer has the skin or the morph targets its rig implies. FRT_ERR_STATE: as frt_renderer_animate. */
+typedef struct frt_cast_entry { uint32_t binding, clip; float time; uint32_t reserved; } frt_cast_entry;      /* reserved must be 0 */
+#define FRT_MAX_CAST_ENTRIES 4096u
+int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry* entries, uint32_t flags);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
