@@ -152,20 +152,6 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* ta
 } // namespace frt
 
 static RigBinding* find_binding(frt_renderer* r, uint32_t binding) { return binding < r->rigs.size() && r->rigs[binding].live ? &r->rigs[binding] : nullptr; }
-// "" when every mesh of the list has the bindings a palette of `njoints` joints and `ntargets` weights in device memory needs: what
-// frt_renderer_set_mesh_poses checks about them.
-static std::string check_rig_meshes(const frt_renderer* r, const uint32_t* ids, uint32_t n, const void* palette, uint32_t njoints, const void* weights, uint32_t ntargets) {
-    const RefitState& f = r->rf;
-    std::string bad = check_pose_batch(n, ids, f.vert_count.size(), njoints != 0, ntargets != 0);
-    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
-        const uint32_t m = ids[k];
-        if (njoints) bad = check_mesh_pose(static_cast<const float*>(palette), njoints, m < f.skins.size() ? f.skins[m].count : 0u, false);
-        if (ntargets && bad.empty()) bad = check_mesh_morph_weights(static_cast<const float*>(weights), ntargets, m < f.morphs.size() ? f.morphs[m].count : 0u, false);
-        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
-    }
-    return bad;
-}
-
 // The binding gets the first free number: an unbound one is used again.
 static uint32_t keep_binding(frt_renderer* r, const RigBinding& b) {
     size_t slot = 0;
@@ -182,7 +168,7 @@ int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* m
     if (!rig || !binding_out) return fail(FRT_ERR_INVALID_ARG, "bind_rig: null");
     const RigHeader h = rig->view().h();
     if (h.nnodes > FRT_MAX_RIG_NODES) return fail(FRT_ERR_INVALID_ARG, "bind_rig: " + std::to_string(h.nnodes) + " nodes, more than FRT_MAX_RIG_NODES");
-    const std::string bad = check_rig_meshes(r, mesh_ids, n, rig, h.njoints, rig, h.ntargets);      // (the pointers are only compared with null)
+    const std::string bad = check_posed_meshes(r, n, mesh_ids, h.njoints != 0, rig, h.njoints, h.ntargets != 0, rig, h.ntargets, false);      // (the pointers are only compared with null)
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "bind_rig: " + bad);
     FRT_DEVICE(r);
     RigBinding b;
@@ -300,7 +286,7 @@ int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float
     if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
     if ((__builtin_bit_cast(uint32_t, time) & 0x7f800000u) == 0x7f800000u) return fail(FRT_ERR_INVALID_ARG, "animate: time is not finite");
     const uint32_t n = (uint32_t)b->mesh_ids.size();
-    const std::string bad = check_rig_meshes(r, b->mesh_ids.data(), n, b->palette.p, b->njoints, b->weights.p, b->ntargets);
+    const std::string bad = check_posed_meshes(r, n, b->mesh_ids.data(), b->njoints != 0, b->palette.p, b->njoints, b->ntargets != 0, b->weights.p, b->ntargets, false);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate: " + bad);
     {
         // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
@@ -329,7 +315,7 @@ int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry*
     for (uint32_t k = 0; k < n && bad.empty(); ++k) {
         const RigBinding& b = r->rigs[entries[k].binding];
         if (b.kind != kRigMeshes) continue;
-        bad = check_rig_meshes(r, b.mesh_ids.data(), (uint32_t)b.mesh_ids.size(), b.palette.p, b.njoints, b.weights.p, b.ntargets);
+        bad = check_posed_meshes(r, (uint32_t)b.mesh_ids.size(), b.mesh_ids.data(), b.njoints != 0, b.palette.p, b.njoints, b.ntargets != 0, b.weights.p, b.ntargets, false);
         if (!bad.empty()) bad = "entry " + std::to_string(k) + ": " + bad;
     }
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast: " + bad);

@@ -154,9 +154,9 @@ __global__ void __launch_bounds__(kDeformBlock) deform_copy_in_kernel(DeformInpu
     if (a.pool_normals) a.pool_normals[da] = dn;
 }
 
-hipError_t launch_deform_input(const DeformInput& a, hipStream_t stream, bool zero_flag) {
+hipError_t launch_deform_input(const DeformInput& a, hipStream_t stream) {
     if (a.nverts == 0 || a.nverts > 0x55555500u) return a.nverts ? hipErrorInvalidValue : hipSuccess;      // (3 nverts work items in 32 bits)
-    hipError_t e = zero_flag ? hipMemsetAsync(a.reject, 0, sizeof(uint32_t), stream) : hipSuccess;
+    hipError_t e = hipMemsetAsync(a.reject, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     const uint32_t words = a.attrs ? 3u * a.nverts : a.nverts;
     hipLaunchKernelGGL(deform_validate_kernel, dim3((words + kDeformBlock - 1) / kDeformBlock), dim3(kDeformBlock), 0, stream, a);

@@ -64,8 +64,8 @@ struct DeformInput {
     float4* block; float4* pool_normals;              // decoded normals, as NormalArgs (both may be null)
     uint32_t* reject;
 };
-// Zeroes the flag, validates, copies in. zero_flag = false: a launch in front of these has the flag already (frt_skin.hpp's, which the caller zeroed it for).
-hipError_t launch_deform_input(const DeformInput& a, hipStream_t stream, bool zero_flag = true);
+// Zeroes the flag, validates, copies in.
+hipError_t launch_deform_input(const DeformInput& a, hipStream_t stream);
 
 // Words 0..23 of a shading record (frt_shade.hpp: fetch_hit_geometry), shared with frt_instance_edit.hip: a gather, no arithmetic.
 //   q0 (n0.xyz, uv0.x) q1 (n1.xyz, uv0.y) q2 (n2.xyz, uv1.x) q3 (t0.xyz, uv1.y) q4 (t1.xyz, uv2.x) q5 (t2.xyz, uv2.y); q6 = (tangent sign of corner 0, mat_id, 0, 0)

@@ -1,9 +1,10 @@
-// frt_pose_batch.hip — kernels of frt_renderer_set_mesh_poses ("Posing several meshes"; frt_pose_batch.hpp). Built with the library's
-// contract flags (-ffp-contract=off, no fast math, IEEE division and square root). No arithmetic is written here: a vertex is frt_morph.hpp's
-// morphed_position and frt_skin.hpp's skinned_position, a normal frt_vertex_normal.hpp's recomputed_vertex_normal and frt_shade.hpp's
-// decode_octahedral_normal, a triangle frt_refit.hpp's instance_world_vertices — the functions the single-mesh kernels and the host specification call.
-// Each kernel is its single-mesh counterpart (mesh_morph_kernel, mesh_skin_kernel, deform_validate_kernel, deform_copy_in_kernel, vertex_normal_kernel,
-// mesh_deform_kernel) with the mesh's offsets and buffers taken from the thread's segment instead of the launch arguments.
+// frt_pose_batch.hip — kernels of every call that poses meshes: frt_renderer_set_mesh_poses, the single-mesh calls frt_renderer_set_mesh_pose(_ex) and
+// _set_mesh_morph_weights (a batch of one) and the mesh half of frt_renderer_animate_cast ("Posing several meshes"; frt_pose_batch.hpp).
+// Built with the library's contract flags (-ffp-contract=off, no fast math, IEEE division and square root). No arithmetic is written here: a vertex is
+// frt_morph.hpp's morphed_position and frt_skin.hpp's skinned_position, a normal frt_vertex_normal.hpp's recomputed_vertex_normal and frt_shade.hpp's
+// decode_octahedral_normal, a triangle frt_refit.hpp's instance_world_vertices — the functions the host specification and frt_deform.hip's kernels call.
+// The last four kernels are frt_deform.hip's (deform_validate_kernel, deform_copy_in_kernel, vertex_normal_kernel, mesh_deform_kernel) with the mesh's
+// offsets and buffers taken from the thread's segment instead of the launch arguments.
 // One thread per vertex or triangle of the concatenation, consecutive threads on consecutive elements, vector loads and stores, no LDS, no fences: what a
 // launch writes, the next launch on the stream reads behind the kernel boundary. The segment table holds records of 80 bytes and the search reads the
 // same few records in every lane of a wave that lies inside one mesh. A segment names the palette and the weights it is posed under: a wave that holds
@@ -28,8 +29,8 @@ __device__ inline bool pose_finite4(float4 q) {
 }
 
 // Thread g: vertex g of the concatenation, morphed from its mesh's base into the scratch the next launch reads (`morphed` when its mesh is skinned
-// afterwards, else the call's posed positions). The first check_nweights threads test one device weight each. (The loads come in front of every
-// store, as in mesh_morph_kernel.)
+// afterwards, else the call's posed positions). The first check_nweights threads test one device weight each, so that a bad weight whose target moves
+// nothing rejects the call as the host form refuses it. (The loads come in front of every store of this kernel.)
 __global__ void __launch_bounds__(kPoseBlock) pose_batch_morph_kernel(PoseBatchArgs a) {
     const uint32_t g = blockIdx.x * (uint32_t)kPoseBlock + threadIdx.x;
     if (g < a.total && g < a.scratch_len) {
@@ -50,7 +51,8 @@ __global__ void __launch_bounds__(kPoseBlock) pose_batch_morph_kernel(PoseBatchA
 }
 
 // Thread g: vertex g of the concatenation, skinned from its mesh's bind pose (or from the morph launch's result) into `skinned`. The first check_cols
-// threads test one float4 of a device palette each.
+// threads test one float4 of a device palette each, so that a bad joint no vertex names rejects the call as the host form refuses it. A joint index
+// that is not below the segment's njoints (the bind call lets none in) raises the flag instead of being followed.
 __global__ void __launch_bounds__(kPoseBlock) pose_batch_skin_kernel(PoseBatchArgs a) {
     const uint32_t g = blockIdx.x * (uint32_t)kPoseBlock + threadIdx.x;
     if (a.check_palette && g < a.check_cols && !pose_finite4(a.check_palette[g])) a.reject[0] = 1u;

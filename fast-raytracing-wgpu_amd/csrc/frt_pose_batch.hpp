@@ -1,10 +1,11 @@
-// frt_pose_batch.hpp — device side of frt_renderer_set_mesh_poses ("Posing several meshes"): n meshes posed under one palette and/or one
-// weight vector by launches whose number does not depend on n. frt_renderer_animate_cast ("Animating a cast") runs the same launches with a palette and
-// weights of its own per mesh: every segment names the ones it is posed under, and set_mesh_poses is the case where all segments name the same. The kernels are the single-mesh ones of frt_morph.hpp, frt_skin.hpp and frt_deform.hpp made
+// frt_pose_batch.hpp — device side of every call that poses meshes ("Posing several meshes"): n meshes posed under one palette and/or one
+// weight vector by launches whose number does not depend on n. frt_renderer_set_mesh_poses is the call; frt_renderer_set_mesh_pose(_ex) and
+// _set_mesh_morph_weights are the batch of one mesh. frt_renderer_animate_cast ("Animating a cast") runs the same launches with a palette and weights of
+// its own per mesh: every segment names the ones it is posed under, and set_mesh_poses is the case where all segments name the same. The kernels are
 // segmented: a thread handles one vertex (or triangle) of the concatenation of the batch's meshes and finds its mesh in the call's segment table by a
-// binary search over prefix sums. The arithmetic is the single-mesh route's own functions — morphed_position, skinned_position, recomputed_vertex_normal,
-// decode_octahedral_normal, instance_world_vertices — so a batch gives, bit for bit, what the n single calls give. The host specification is
-// SceneBuilder::set_mesh_poses (frt_scene.cpp).
+// binary search over prefix sums. The arithmetic is the host specification's own functions — morphed_position, skinned_position,
+// recomputed_vertex_normal, decode_octahedral_normal, instance_world_vertices — and every vertex and triangle is computed from its own mesh alone, so a
+// batch gives, bit for bit, what the n single calls give. The host specification is SceneBuilder::set_mesh_poses (frt_scene.cpp).
 #pragma once
 #include "frt_deform.hpp"
 #include "frt_skin.hpp"

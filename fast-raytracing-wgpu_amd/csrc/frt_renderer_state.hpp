@@ -5,9 +5,7 @@
 #pragma once
 #include "frt_rebuild.hpp"      // (with frt_deform.hpp: frt_refit.hpp)
 #include "frt_deform.hpp"
-#include "frt_skin.hpp"
-#include "frt_morph.hpp"
-#include "frt_pose_batch.hpp"
+#include "frt_pose_batch.hpp"   // (frt_skin.hpp, frt_morph.hpp)
 #include "frt_refit_device.hpp"
 #include "frt_instance_edit.hpp"
 #include "frt_material_edit.hpp"
@@ -151,7 +149,7 @@ struct RefitState {
     std::vector<uint32_t> pair_levels, quad_levels;   // level L of a tree = nodes [levels[L], levels[L + 1])
     Staging rec;                           // the moved-instance records of one call (MovedInstance)
     // frt_renderer_set_mesh_vertices ("Deforming meshes"): per mesh its vertex count and first attribute; `def`: the staging of one call of the family
-    // that deforms (vertices, pose, morph weights), its sections named by frt_scene_edit.hip's DeformLayout.
+    // that deforms, its sections named by frt_scene_edit.hip's DeformLayout (vertices) or PoseBatchLayout (every posing call).
     std::vector<uint32_t> vert_count, attr_offset;
     std::vector<uint32_t> mesh_tris;       // per mesh: its triangles (what an added instance of it brings)
     Staging def;
@@ -164,14 +162,15 @@ struct RefitState {
     // shorter than the mesh list; remove_meshes frees a leaving mesh's bindings and renumbers the rest.
     struct MeshBinding { OwnedBuf buf; uint32_t count = 0; };
     // frt_renderer_set_mesh_skin / _set_mesh_pose ("Skinning"): a skin is [bind positions 16 nverts | weights 16 nverts | joints 8 nverts], `count` its
-    // joints. `skin_up`: the pinned block a bind call's weights and joints go through. `skinned`: the scratch a pose call skins into, [nverts] float4.
+    // joints. `skin_up`: the pinned block a bind call's weights and joints go through. `skinned`: the posed positions of the posing call in flight, a single
+    // mesh's or a batch's ("Posing several meshes"), [the summed vertex counts] float4, whatever launch wrote them last.
     std::vector<MeshBinding> skins;
     Staging skin_up;
     OwnedBuf skinned;
     // frt_renderer_set_mesh_morph_targets / _set_mesh_morph_weights / _set_mesh_pose_ex ("Morph targets"): targets are [base positions 16 nverts |
     // deltas, target-major, 12 nverts per target], `count` the targets. `morph_up`: the pinned block a bind call's deltas go through (a block of its
-    // own: a morph bind does not wait for a skin bind's copies). A morph call morphs into `skinned`; the combined call morphs into `morphed`, [nverts]
-    // float4, which the skin launch then reads as its bind pose.
+    // own: a morph bind does not wait for a skin bind's copies). A call without a palette morphs into `skinned`; with one it morphs into `morphed`, as
+    // large as `skinned`, which the skin launch then reads as its bind pose.
     std::vector<MeshBinding> morphs;
     Staging morph_up;
     OwnedBuf morphed;
@@ -376,4 +375,8 @@ int check_entry(const frt_renderer* r, const std::string& what, unsigned parts);
 uint32_t pool_count(const frt_renderer* r, int pool);             // elements of a pool (PoolState) in use
 int ensure_normals(frt_renderer* r);                              // PoolState::d_normals exists afterwards
 int apply_cast(frt_renderer* r, const CastApply& c);              // frt_scene_edit.hip: the two halves of frt_renderer_animate_cast in one call frame
+// "" when the batch (check_pose_batch) and then every mesh of it, as its single call checks it ("mesh N: ..."), can be posed: with `skin` under a palette of
+// `njoints` joints, with `morph` under `ntargets` weights. host_memory: the entries of the palette and of the weights, the same for every mesh, are read
+// (at the first mesh only); otherwise the two pointers are only compared with null. What set_mesh_poses, bind_rig, animate and animate_cast share.
+std::string check_posed_meshes(const frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, bool skin, const void* palette, uint32_t njoints, bool morph, const void* weights, uint32_t ntargets, bool host_memory);
 }

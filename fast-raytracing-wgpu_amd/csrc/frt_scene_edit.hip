@@ -5,7 +5,7 @@
 //   new meshes, materials, texture layers and lights                        §15
 //   removing meshes, materials, layers and lights                           §16
 // The calls that only read the replica (the ray queries, frt_renderer_read_scene, the statistics and counts) are in frt_scene_read.hip; the kernels in
-// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_skin.hip, frt_morph.hip, frt_pose_batch.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
+// frt_refit.hip, frt_refit_device.hip, frt_deform.hip, frt_pose_batch.hip, frt_material_edit.hip, frt_instance_edit.hip, frt_mesh_edit.hip, frt_scene_remove.hip, frt_rebuild.hip and frt_ploc.hip.
 //
 // All edits share one scheme:
 //   - the call frame (edit_frame): the device guard, the stream order behind the finished frames, the body, `failed` on a HIP error;
@@ -13,10 +13,10 @@
 //   - the buffers beside the replica that a call writes and that then trade places with the replica's (OwnedBuf);
 //   - staging (Staging): what a call uploads goes through a pinned block that is reused once the copies out of it have completed.
 // The seven calls on meshes are one family: one entry check (check_mesh_call), one check of a device pointer (check_device_input), one type and one
-// helper for what a bind call leaves with a mesh (RefitState::MeshBinding, bind_to_mesh), and one body for everything that deforms (deform_mesh: a
-// DeformCall says where the positions come from, a DeformLayout where each section of the call's blocks lies, and three steps stage, pose and apply).
-// frt_renderer_set_mesh_poses, the batch over several meshes, shares their checks and has a body of its own (pose_meshes) over the segmented kernels of
-// frt_pose_batch.hpp: the single-mesh calls are not routed through it.
+// helper for what a bind call leaves with a mesh (RefitState::MeshBinding, bind_to_mesh), and two bodies. frt_renderer_set_mesh_vertices runs
+// deform_mesh (a DeformCall says where the positions are, a DeformLayout where each section of the call's blocks lies; two steps, stage and apply).
+// Everything that poses runs pose_meshes over the segmented kernels of frt_pose_batch.hpp: frt_renderer_set_mesh_poses, the batch over several
+// meshes, and the three single-mesh posing calls, each a batch of one behind its own checks.
 #include "frt_renderer_state.hpp"
 #include <algorithm>
 #include <cstddef>
@@ -125,6 +125,17 @@ int frt::check_entry(const frt_renderer* r, const std::string& what, unsigned pa
     if ((parts & kQuadTree) && !walks_quad_tree(r)) return fail(FRT_ERR_INVALID_ARG, what + ": this renderer's kernels do not walk the quad tree, the only tree this call keeps up or reads");
 #endif
     return FRT_OK;
+}
+std::string frt::check_posed_meshes(const frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, bool skin, const void* palette, uint32_t njoints, bool morph, const void* weights, uint32_t ntargets, bool host_memory) {
+    const RefitState& f = r->rf;
+    std::string bad = check_pose_batch(n, mesh_ids, f.vert_count.size(), skin, morph);
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
+        const uint32_t m = mesh_ids[k];
+        if (skin) bad = check_mesh_pose(static_cast<const float*>(palette), njoints, m < f.skins.size() ? f.skins[m].count : 0u, host_memory && k == 0);
+        if (morph && bad.empty()) bad = check_mesh_morph_weights(static_cast<const float*>(weights), ntargets, m < f.morphs.size() ? f.morphs[m].count : 0u, host_memory && k == 0);
+        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
+    }
+    return bad;
 }
 
 // The stream order of a call that writes the scene replica (`drop`: and changes its geometry), on the main stream.
@@ -496,52 +507,37 @@ static int ensure_adjacency(frt_renderer* r, uint32_t m) {
     return FRT_OK;
 }
 
-// One deformation, as its C call has checked it. `source` says where the new positions come from: the caller's host memory, the caller's device memory
-// (FRT_DEFORM_DEVICE), or the renderer's scratch after a skin launch, a morph launch, or a morph launch and then a skin launch over its result. Only the
-// first two read `pos4` and may bring attributes (which live where the positions live); the others read the mesh's bindings and what they name here:
-// `palette` for a skin launch, `weights` for a morph launch, each in host memory (it rides in the call's blocks) or, `*_on_device`, in the caller's
-// device memory (the launch checks its finiteness).
-enum class PosSource { Host, Device, Skin, Morph, MorphThenSkin };
+// One frt_renderer_set_mesh_vertices_ex, as the call has checked it. `pos4` and `attrs` (which live where the positions live) are the caller's host
+// memory or, `on_device` (FRT_DEFORM_DEVICE), the caller's device memory.
 struct DeformCall {
     uint32_t mesh_id = 0, nverts = 0;
-    PosSource source = PosSource::Host;
+    bool on_device = false;                       // the positions reach the replica through frt_deform.hpp's validation and copy-in
     bool recompute = false;                       // FRT_DEFORM_RECOMPUTE_NORMALS
     const float* pos4 = nullptr;
     const frt_vertex_attr* attrs = nullptr;
-    const float* palette = nullptr; uint32_t njoints = 0; bool palette_on_device = false;
-    const float* weights = nullptr; uint32_t ntargets = 0; bool weights_on_device = false;
-    bool skins() const { return source == PosSource::Skin || source == PosSource::MorphThenSkin; }
-    bool morphs() const { return source == PosSource::Morph || source == PosSource::MorphThenSkin; }
-    bool posed() const { return skins() || morphs(); }
-    bool device_route() const { return source != PosSource::Host; }      // the positions reach the replica through frt_deform.hpp's validation and copy-in
     bool shade() const { return attrs || recompute; }                    // the shading records are written again: the device block holds decoded normals
-    bool host_decode() const { return attrs && !recompute && !device_route(); }      // ... which the host decodes from the call's attributes
+    bool host_decode() const { return attrs && !recompute && !on_device; }      // ... which the host decodes from the call's attributes
 };
 // Where everything a call stages lies in the two blocks of RefitState::def, computed once; a section that a call does not use is empty.
-//   pinned: positions | attributes | instance records | decoded normals | palette | weights
-//   device:                          instance records | decoded normals | palette | weights
+//   pinned: positions | attributes | instance records | decoded normals
+//   device:                          instance records | decoded normals
 // The first two pinned sections are copied into the replica (the object-space positions the instance update reads, SceneView::attributes). Records and
 // normals are neighbours in both blocks and go over in one copy (`h_up`); the device's normals section is there whenever shading records are written
 // (the normal pass fills it where the host did not), the pinned one only for the host's decode.
 struct Section { size_t off = 0, bytes = 0; };
 struct DeformLayout {
-    Section h_pos, h_attrs, h_rec, h_nrm, h_pal, h_wt, h_up, d_rec, d_nrm, d_pal, d_wt;
+    Section h_pos, h_attrs, h_rec, h_nrm, h_up, d_rec, d_nrm;
     size_t h_total = 0, d_total = 0;
     DeformLayout(const DeformCall& c, size_t ninstances) {
         auto put = [](size_t& total, size_t bytes) { const Section s{total, bytes}; total += bytes; return s; };
         const size_t n = c.nverts, rec = ninstances * sizeof(DeformInstance);
-        const size_t pal = c.skins() && !c.palette_on_device ? (size_t)c.njoints * 64 : 0, wt = c.morphs() && !c.weights_on_device ? (size_t)c.ntargets * 4 : 0;
-        h_pos = put(h_total, c.device_route() ? 0 : n * 16);
-        h_attrs = put(h_total, c.attrs && !c.device_route() ? n * sizeof(frt_vertex_attr) : 0);
+        h_pos = put(h_total, c.on_device ? 0 : n * 16);
+        h_attrs = put(h_total, c.attrs && !c.on_device ? n * sizeof(frt_vertex_attr) : 0);
         h_rec = put(h_total, rec);
         h_nrm = put(h_total, c.host_decode() ? n * 16 : 0);
-        h_pal = put(h_total, pal);
-        h_wt = put(h_total, wt);
         h_up = Section{h_rec.off, h_rec.bytes + h_nrm.bytes};
         d_rec = put(d_total, rec);
         d_nrm = put(d_total, c.shade() ? n * 16 : 0);
-        d_pal = put(d_total, pal);
-        d_wt = put(d_total, wt);
     }
 };
 // Step 1: the call's data into the pinned block and, in stream order, out of it. RefitState::def is reused in stream order and replaced, after a wait
@@ -563,54 +559,26 @@ static int stage_deform(frt_renderer* r, const DeformCall& c, const DeformLayout
         for (uint32_t v = 0; v < c.nverts; ++v) { decoded_vertex_normal(c.attrs[v], nrm + 4 * (size_t)v); nrm[4 * (size_t)v + 3] = 0.0f; }
     }
     if (l.h_rec.bytes) memcpy(h + l.h_rec.off, rec.data(), l.h_rec.bytes);
-    if (l.h_pal.bytes) memcpy(h + l.h_pal.off, c.palette, l.h_pal.bytes);
-    if (l.h_wt.bytes) memcpy(h + l.h_wt.off, c.weights, l.h_wt.bytes);
-    if (!c.device_route()) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[m], h + l.h_pos.off, l.h_pos.bytes, hipMemcpyHostToDevice, r->stream));
+    if (!c.on_device) HIP_TRY(hipMemcpyAsync(const_cast<float4*>(f.d_pos) + f.pos_offset[m], h + l.h_pos.off, l.h_pos.bytes, hipMemcpyHostToDevice, r->stream));
     if (l.h_attrs.bytes) HIP_TRY(hipMemcpyAsync(const_cast<VertexAttrView*>(r->sv.attributes) + f.attr_offset[m], h + l.h_attrs.off, l.h_attrs.bytes, hipMemcpyHostToDevice, r->stream));
     if (l.h_up.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_rec.off, h + l.h_up.off, l.h_up.bytes, hipMemcpyHostToDevice, r->stream));
     if (c.host_decode() && pool_normals) HIP_TRY(hipMemcpyAsync(pool_normals + f.attr_offset[m], h + l.h_nrm.off, l.h_nrm.bytes, hipMemcpyHostToDevice, r->stream));
-    if (l.h_pal.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_pal.off, h + l.h_pal.off, l.h_pal.bytes, hipMemcpyHostToDevice, r->stream));
-    if (l.h_wt.bytes) HIP_TRY(hipMemcpyAsync(d + l.d_wt.off, h + l.h_wt.off, l.h_wt.bytes, hipMemcpyHostToDevice, r->stream));
     return f.def.mark(r->stream);
 }
-// Step 2, the posing sources only: the morph launch and/or the skin launch into the scratch buffers. Their result is this call's device input, so the
-// flag is zeroed here, in front of the launch that may raise it first. Morph then skin: the morph launch writes RefitState::morphed, and the skin
-// launch, otherwise unchanged, reads that buffer as its bind pose.
-static int pose_deform(frt_renderer* r, const DeformCall& c, const DeformLayout& l) {
-    RefitState& f = r->rf;
-    const size_t pos_bytes = (size_t)c.nverts * 16;      // (the first section of a binding's buffer: RefitState::MeshBinding)
-    HIP_TRY(hipMemsetAsync(f.d_reject, 0, sizeof(uint32_t), r->stream));
-    if (c.morphs()) {
-        const uint8_t* k = static_cast<const uint8_t*>(f.morphs[c.mesh_id].buf.p);
-        const OwnedBuf& out = c.skins() ? f.morphed : f.skinned;
-        const MorphArgs ma{reinterpret_cast<const float4*>(k), reinterpret_cast<const float*>(k + pos_bytes),
-                           c.weights_on_device ? c.weights : reinterpret_cast<const float*>(f.def.d + l.d_wt.off), out.as<float4>(),
-                           c.nverts, c.ntargets, (uint32_t)std::min<size_t>(out.bytes / 16, 0xFFFFFFFFu), c.weights_on_device ? 1u : 0u, f.d_reject};
-        HIP_TRY(launch_mesh_morph(ma, r->stream));
-    }
-    if (c.skins()) {
-        const uint8_t* k = static_cast<const uint8_t*>(f.skins[c.mesh_id].buf.p);
-        const SkinArgs sa{c.morphs() ? f.morphed.as<const float4>() : reinterpret_cast<const float4*>(k), reinterpret_cast<const float4*>(k + pos_bytes), reinterpret_cast<const uint2*>(k + 2 * pos_bytes),
-                          reinterpret_cast<const float4*>(c.palette_on_device ? reinterpret_cast<const uint8_t*>(c.palette) : f.def.d + l.d_pal.off), f.skinned.as<float4>(),
-                          c.nverts, c.njoints, (uint32_t)std::min<size_t>(f.skinned.bytes / 16, 0xFFFFFFFFu), c.palette_on_device ? 1u : 0u, f.d_reject};
-        HIP_TRY(launch_mesh_skin(sa, r->stream));
-    }
-    return FRT_OK;
-}
-// Step 3: device positions (the caller's, or the scratch of step 2) through the validation and copy-in launches of frt_deform.hpp, the normal pass,
-// the mesh's triangles under every instance of it, the scene extent and the refit. `work`: the triangles of those instances.
+// Step 2: the caller's device positions through the validation and copy-in launches of frt_deform.hpp, the normal pass, the mesh's triangles under
+// every instance of it, the scene extent and the refit. `work`: the triangles of those instances.
 static int apply_deform(frt_renderer* r, const DeformCall& c, const DeformLayout& l, uint32_t ninstances, uint32_t work) {
     RefitState& f = r->rf;
     const uint32_t m = c.mesh_id, cap_verts = pool_cap(r, kPoolVerts);
     float4* block = c.shade() ? reinterpret_cast<float4*>(f.def.d + l.d_nrm.off) : nullptr;
     float4* pool_normals = const_cast<float4*>(r->pools.d_normals);
-    const uint32_t* reject = c.device_route() ? f.d_reject : nullptr;      // (host input was validated by the call: there is no flag to look at)
-    if (c.device_route()) {
+    const uint32_t* reject = c.on_device ? f.d_reject : nullptr;      // (host input was validated by the call: there is no flag to look at)
+    if (c.on_device) {
         const bool decode = c.attrs && !c.recompute;
-        DeformInput in{c.posed() ? f.skinned.as<const float4>() : reinterpret_cast<const float4*>(c.pos4), reinterpret_cast<const float4*>(c.attrs), c.nverts, f.pos_offset[m], f.attr_offset[m], cap_verts,
+        DeformInput in{reinterpret_cast<const float4*>(c.pos4), reinterpret_cast<const float4*>(c.attrs), c.nverts, f.pos_offset[m], f.attr_offset[m], cap_verts,
                        const_cast<float4*>(f.d_pos), reinterpret_cast<float4*>(const_cast<VertexAttrView*>(r->sv.attributes)),
                        decode ? block : nullptr, decode ? pool_normals : nullptr, f.d_reject};
-        HIP_TRY(launch_deform_input(in, r->stream, !c.posed()));
+        HIP_TRY(launch_deform_input(in, r->stream));
     }
     if (c.recompute) {
         NormalArgs na{f.adj[m], f.adj[m] + (c.nverts + 1u), c.nverts, 3u * f.mesh_tris[m], f.index_offset[m], f.pos_offset[m], f.attr_offset[m],
@@ -631,7 +599,7 @@ static int apply_deform(frt_renderer* r, const DeformCall& c, const DeformLayout
     HIP_TRY(launch_scene_extent(r->sv, const_cast<unsigned int*>(f.d_ext), r->stream));
     return refit_levels(r);
 }
-// What follows the checks of a deformation, inside its call frame: the instance records, what the call needs beside the staging, and the three steps.
+// What follows the checks of a deformation, inside its call frame: the instance records, what the call needs beside the staging, and the two steps.
 static int deform_mesh(frt_renderer* r, const DeformCall& c) {
     RefitState& f = r->rf;
     int rc;
@@ -647,12 +615,9 @@ static int deform_mesh(frt_renderer* r, const DeformCall& c) {
         rec.push_back(d);
     }
     const DeformLayout l(c, rec.size());
-    if (c.posed() && (rc = f.skinned.ensure(r, (size_t)c.nverts * 16))) return rc;
-    if (c.skins() && c.morphs() && (rc = f.morphed.ensure(r, (size_t)c.nverts * 16))) return rc;
     if (c.recompute && (rc = ensure_adjacency(r, c.mesh_id))) return rc;
-    if (c.device_route() && (rc = ensure_reject_words(r, f.d_reject))) return rc;
+    if (c.on_device && (rc = ensure_reject_words(r, f.d_reject))) return rc;
     if ((rc = stage_deform(r, c, l, rec))) return rc;
-    if (c.posed() && (rc = pose_deform(r, c, l))) return rc;
     return apply_deform(r, c, l, (uint32_t)rec.size(), work);
 }
 int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags) {
@@ -669,7 +634,7 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
         if (attrs) if (const int rc = check_device_input(r, attrs, (size_t)nverts * sizeof(frt_vertex_attr), 16, "set_mesh_vertices", "attributes")) return rc;
     }
     DeformCall c;
-    c.mesh_id = mesh_id; c.nverts = nverts; c.source = dev ? PosSource::Device : PosSource::Host; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    c.mesh_id = mesh_id; c.nverts = nverts; c.on_device = dev; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
     c.pos4 = pos4; c.attrs = attrs;
     return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
 }
@@ -737,43 +702,13 @@ int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const
     });
 }
 
-// ------------------------------------------------------------------------------------------------ posing: skin, morph, or morph then skin
-// What the two calls that take morph weights check about them, in front of the call frame; with FRT_DEFORM_DEVICE their finiteness is the morph launch's.
+// ------------------------------------------------------------------------------------------------ posing: skin, morph, or morph then skin ("Posing several meshes")
+// What the two single-mesh calls that take morph weights check about them, in front of the call frame; with FRT_DEFORM_DEVICE their finiteness is the morph launch's.
 static int check_morph_input(frt_renderer* r, const char* call, uint32_t mesh_id, const float* weights, uint32_t ntargets, bool dev) {
     const std::string bad = check_mesh_morph_weights(weights, ntargets, mesh_id < r->rf.morphs.size() ? r->rf.morphs[mesh_id].count : 0u, !dev);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, std::string(call) + ": " + bad);
     return dev ? check_device_input(r, weights, (size_t)ntargets * 4, 4, call, "morph weights") : FRT_OK;
 }
-// The frame, the order and the staging are frt_renderer_set_mesh_vertices_ex's (deform_mesh); what these calls add runs in front of the device-input route.
-int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
-    if (const int rc = check_mesh_call(r, "set_mesh_morph_weights", mesh_id, flags, kDeformFlags)) return rc;
-    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0;
-    if (const int rc = check_morph_input(r, "set_mesh_morph_weights", mesh_id, weights, ntargets, dev)) return rc;
-    DeformCall c;
-    c.mesh_id = mesh_id; c.nverts = r->rf.vert_count[mesh_id]; c.source = PosSource::Morph; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
-    c.weights = weights; c.ntargets = ntargets; c.weights_on_device = dev;
-    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
-}
-// The pose's checks, the palette's device pointer, then (with morph weights or a target count) the morph's; the palette's finiteness is the skin launch's
-// to check when it is device memory.
-int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
-    if (const int rc = check_mesh_call(r, "set_mesh_pose", mesh_id, flags, kDeformFlags)) return rc;
-    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, morph = morph_weights || ntargets;
-    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].count : 0u, !dev);
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
-    if (dev) if (const int rc = check_device_input(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices")) return rc;
-    if (morph) if (const int rc = check_morph_input(r, "set_mesh_pose", mesh_id, morph_weights, ntargets, dev)) return rc;
-    DeformCall c;
-    c.mesh_id = mesh_id; c.nverts = r->rf.vert_count[mesh_id]; c.source = morph ? PosSource::MorphThenSkin : PosSource::Skin; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
-    c.palette = joint_mats; c.njoints = njoints; c.palette_on_device = dev;
-    c.weights = morph_weights; c.ntargets = ntargets; c.weights_on_device = dev;
-    return edit_frame(r, true, [&]() -> int { return deform_mesh(r, c); });
-}
-int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
-    return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, nullptr, 0u, flags);
-}
-
-// ------------------------------------------------------------------------------------------------ posing several meshes ("Posing several meshes")
 // Where everything a batch stages lies in the two blocks of RefitState::def, a sibling of DeformLayout. The pinned block goes over in one copy; the
 // device block has the call's decoded normals behind it (FRT_DEFORM_RECOMPUTE_NORMALS: the normal launch fills them, the triangle launch reads them).
 //   pinned: segments | instance records | the records' segments | palette | weights
@@ -793,6 +728,7 @@ struct PoseBatchLayout {
     }
 };
 struct PoseBatchCall {
+    const char* call = "";                                     // the C call's name: what a message begins with
     uint32_t n = 0; const uint32_t* mesh_ids = nullptr;
     const float* palette = nullptr; uint32_t njoints = 0;      // null: no skin launch
     const float* weights = nullptr; uint32_t ntargets = 0;     // null: no morph launch
@@ -808,6 +744,7 @@ struct PoseBatchCall {
 // the launches of frt_pose_batch.hpp. `changed`: a triangle was written, so the scene extent and the refit have to follow (pose_meshes; apply_cast).
 static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& changed) {
     RefitState& f = r->rf;
+    const std::string call(c.call);
     int rc;
     changed = false;
     if (!c.per_mesh && (rc = sync_matrix_mirror(r))) return rc;      // (the instances' matrices are read below)
@@ -819,9 +756,9 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
     for (uint32_t k = 0; k < c.n; ++k) {
         const uint32_t m = c.mesh(k);
         if ((uint64_t)f.pos_offset[m] + f.vert_count[m] > cap_verts || (uint64_t)f.attr_offset[m] + f.vert_count[m] > cap_verts)
-            return fail(FRT_ERR_STATE, "set_mesh_poses: mesh " + std::to_string(m) + " does not lie inside the vertex pool");
+            return fail(FRT_ERR_STATE, call + ": mesh " + std::to_string(m) + " does not lie inside the vertex pool");
         if ((uint64_t)f.index_offset[m] + 3ull * f.mesh_tris[m] > cap_indices)
-            return fail(FRT_ERR_STATE, "set_mesh_poses: mesh " + std::to_string(m) + " does not lie inside the index pool");
+            return fail(FRT_ERR_STATE, call + ": mesh " + std::to_string(m) + " does not lie inside the index pool");
         if (c.recompute && (rc = ensure_adjacency(r, m))) return rc;
         PoseSegment& s = seg[k];
         s.vert_begin = (uint32_t)total; s.nverts = f.vert_count[m]; s.pos_offset = f.pos_offset[m]; s.attr_offset = f.attr_offset[m];
@@ -837,7 +774,7 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
         any_skin = any_skin || skin; any_morph = any_morph || morph;
         seg_of_mesh[m] = (int)k;
         total += s.nverts;
-        if (total > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 vertices in one call");
+        if (total > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, call + ": more than 2^32 - 256 vertices in one call");
     }
     std::vector<DeformInstance> rec;
     std::vector<uint32_t> rec_seg;
@@ -851,7 +788,7 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
         rec.push_back(d);
         rec_seg.push_back((uint32_t)seg_of_mesh[in.mesh_id]);
     }
-    if (work > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: more than 2^32 - 256 triangles in one call");
+    if (work > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, call + ": more than 2^32 - 256 triangles in one call");
     if ((rc = f.skinned.ensure(r, (size_t)total * 16))) return rc;
     if (any_skin && any_morph && (rc = f.morphed.ensure(r, (size_t)total * 16))) return rc;
     if ((rc = ensure_reject_words(r, f.d_reject))) return rc;
@@ -892,33 +829,49 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
     changed = work != 0;      // no instance of any mesh of the batch: no triangle changes
     return FRT_OK;
 }
-static int pose_meshes(frt_renderer* r, const PoseBatchCall& c) {
-    bool changed = false;
-    if (const int rc = pose_meshes_body(r, c, changed)) return rc;
-    return changed ? refit_scene(r) : FRT_OK;
+// A posing call behind its checks, in its call frame: the batch, then (a triangle was written) the scene extent and the refit. Without a palette there
+// is no skin launch, without weights no morph launch.
+static int pose_meshes(frt_renderer* r, const char* call, uint32_t n, const uint32_t* mesh_ids, const float* palette, uint32_t njoints, const float* weights, uint32_t ntargets, uint32_t flags) {
+    PoseBatchCall c;
+    c.call = call; c.n = n; c.mesh_ids = mesh_ids; c.on_device = (flags & FRT_DEFORM_DEVICE) != 0; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    c.palette = palette; c.njoints = njoints;
+    c.weights = weights; c.ntargets = ntargets;
+    return edit_frame(r, true, [&]() -> int {
+        bool changed = false;
+        if (const int rc = pose_meshes_body(r, c, changed)) return rc;
+        return changed ? refit_scene(r) : FRT_OK;
+    });
 }
-// The entry and the flags, the batch itself (check_pose_batch), every mesh as its single call checks it, then the device pointers. The entries of a host
-// palette and of host weights are the same for every mesh and are read once.
+// The entry and the flags, the batch itself and every mesh as its single call checks it (check_posed_meshes), then the device pointers.
 int frt_renderer_set_mesh_poses(frt_renderer* r, uint32_t n, const uint32_t* mesh_ids, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
     if (const int rc = check_entry(r, "set_mesh_poses", kEditChecks | kRefit)) return rc;
     if (flags & ~kDeformFlags) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: unknown flag bits");
     const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, skin = joint_mats || njoints, morph = morph_weights || ntargets;
-    const RefitState& f = r->rf;
-    std::string bad = check_pose_batch(n, mesh_ids, f.vert_count.size(), skin, morph);
-    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
-        const uint32_t m = mesh_ids[k];
-        if (skin) bad = check_mesh_pose(joint_mats, njoints, m < f.skins.size() ? f.skins[m].count : 0u, !dev && k == 0);
-        if (morph && bad.empty()) bad = check_mesh_morph_weights(morph_weights, ntargets, m < f.morphs.size() ? f.morphs[m].count : 0u, !dev && k == 0);
-        if (!bad.empty()) bad = "mesh " + std::to_string(m) + ": " + bad;
-    }
+    const std::string bad = check_posed_meshes(r, n, mesh_ids, skin, joint_mats, njoints, morph, morph_weights, ntargets, !dev);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_poses: " + bad);
     if (dev && skin) if (const int rc = check_device_input(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_poses", "joint matrices")) return rc;
     if (dev && morph) if (const int rc = check_device_input(r, morph_weights, (size_t)ntargets * 4, 4, "set_mesh_poses", "morph weights")) return rc;
-    PoseBatchCall c;
-    c.n = n; c.mesh_ids = mesh_ids; c.on_device = dev; c.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
-    if (skin) { c.palette = joint_mats; c.njoints = njoints; }
-    if (morph) { c.weights = morph_weights; c.ntargets = ntargets; }
-    return edit_frame(r, true, [&]() -> int { return pose_meshes(r, c); });
+    return pose_meshes(r, "set_mesh_poses", n, mesh_ids, joint_mats, njoints, morph_weights, ntargets, flags);
+}
+// The three single-mesh calls keep their own checks, in their own order and under their own names, and then pose a batch of one mesh.
+int frt_renderer_set_mesh_morph_weights(frt_renderer* r, uint32_t mesh_id, const float* weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = check_mesh_call(r, "set_mesh_morph_weights", mesh_id, flags, kDeformFlags)) return rc;
+    if (const int rc = check_morph_input(r, "set_mesh_morph_weights", mesh_id, weights, ntargets, (flags & FRT_DEFORM_DEVICE) != 0)) return rc;
+    return pose_meshes(r, "set_mesh_morph_weights", 1u, &mesh_id, nullptr, 0u, weights, ntargets, flags);
+}
+// The pose's checks, the palette's device pointer, then (with morph weights or a target count) the morph's; the palette's finiteness is the skin launch's
+// to check when it is device memory.
+int frt_renderer_set_mesh_pose_ex(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, const float* morph_weights, uint32_t ntargets, uint32_t flags) {
+    if (const int rc = check_mesh_call(r, "set_mesh_pose", mesh_id, flags, kDeformFlags)) return rc;
+    const bool dev = (flags & FRT_DEFORM_DEVICE) != 0, morph = morph_weights || ntargets;
+    const std::string bad = check_mesh_pose(joint_mats, njoints, mesh_id < r->rf.skins.size() ? r->rf.skins[mesh_id].count : 0u, !dev);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_pose: " + bad);
+    if (dev) if (const int rc = check_device_input(r, joint_mats, (size_t)njoints * 64, 16, "set_mesh_pose", "joint matrices")) return rc;
+    if (morph) if (const int rc = check_morph_input(r, "set_mesh_pose", mesh_id, morph_weights, ntargets, dev)) return rc;
+    return pose_meshes(r, "set_mesh_pose", 1u, &mesh_id, joint_mats, njoints, morph_weights, ntargets, flags);
+}
+int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
+    return frt_renderer_set_mesh_pose_ex(r, mesh_id, joint_mats, njoints, nullptr, 0u, flags);
 }
 
 } // extern "C"
@@ -936,7 +889,7 @@ int frt::apply_cast(frt_renderer* r, const CastApply& c) {
         }
         if (!c.meshes.empty()) {
             PoseBatchCall p;
-            p.n = (uint32_t)c.meshes.size(); p.per_mesh = c.meshes.data(); p.on_device = true; p.recompute = c.recompute;
+            p.call = "animate_cast"; p.n = (uint32_t)c.meshes.size(); p.per_mesh = c.meshes.data(); p.on_device = true; p.recompute = c.recompute;
             p.palette = c.palettes; p.check_cols = c.cols; p.weights = c.weights; p.check_nweights = c.nweights;
             if (const int rc = pose_meshes_body(r, p, posed)) return rc;
         }

@@ -1,5 +1,5 @@
 // frt_skin.hpp — linear-blend skinning ("Skinning"): the arithmetic of SceneBuilder::set_mesh_pose, __host__ __device__ so that the host
-// specification (frt_scene.cpp) and the device pass (frt_skin.hip) compile the same expressions: f32, no contraction, no fma written by hand. A header of
+// specification (frt_scene.cpp) and the device pass (frt_pose_batch.hip) compile the same expressions: f32, no contraction, no fma written by hand. A header of
 // its own, beside frt_vertex_normal.hpp, because none of this is code of the frame's kernels.
 #pragma once
 #include "frt_math.hpp"
@@ -23,22 +23,7 @@ FRT_HD void skinned_position(const float p[4], const float m[4][16], const float
     out[3] = p[3];
 }
 
-// The device pass, in front of the device-input route of frt_deform.hpp (whose DeformInput::pos is `out`). One thread per vertex, consecutive threads on
-// consecutive vertices: one 16-byte load each of the bind position and the weights, one 8-byte load of the joints, four 16-byte columns of each of the four
-// joints, skinned_position, one 16-byte store. No LDS, nothing passed between the blocks. A joint index that is not below `njoints` (the bind call lets
-// none in) raises the reject flag instead of being followed, and no thread stores past `out_len`. With `check_palette` (the palette is the caller's device
-// memory, which the host has not seen) the first 4 * njoints threads also test one float4 of the palette each and raise the flag for a non-finite float,
-// so that a bad joint no vertex names rejects the call as the host form refuses it.
-struct SkinArgs {
-    const float4* bind;          // [nverts] bind positions, xyzw
-    const float4* weights;       // [nverts]
-    const uint2* joints;         // [nverts] four uint16 each
-    const float4* palette;       // [4 * njoints] columns
-    float4* out;                 // [out_len] the skinned positions of this call
-    uint32_t nverts, njoints, out_len;
-    uint32_t check_palette;
-    uint32_t* reject;            // DeformInput::reject: [0] is zeroed on the stream in front of this launch
-};
-hipError_t launch_mesh_skin(const SkinArgs& a, hipStream_t stream);
+// The device pass is pose_batch_skin_kernel (frt_pose_batch.hip): one thread per vertex, one 16-byte load each of the bind position and the weights, one
+// 8-byte load of the joints, four 16-byte columns of each of the four joints, skinned_position, one 16-byte store.
 
 } // namespace frt

@@ -30,11 +30,11 @@ def pose_meshes(frt):
     return [frt.geometry.create_plane(), strip(frt, 4), strip(frt, 3)]
 
 
-def pose_scene(frt, build=True):
+def pose_scene(frt, build=True, meshes=None):
     """(scene, meshes): the quad as a floor and as a back wall, the 8-vertex strip once (mirrored, tilted towards the camera), the 6-vertex strip in the
-    pools only; one quad light that no instance carries."""
+    pools only; one quad light that no instance carries. `meshes`: three others in their places."""
     from frt.scenes import _T, _S, _RX, _mul
-    meshes = pose_meshes(frt)
+    meshes = pose_meshes(frt) if meshes is None else meshes
     b = frt.SceneBuilder()
     for g in meshes:
         b.add_mesh(g)

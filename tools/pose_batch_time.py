@@ -3,7 +3,7 @@
 Box and to the colonnade through add_meshes / add_instances (so the replica's tree is the device-built one), for P in 1, 4, 16, 64. Four routes, every
 one with normals="recompute", microseconds per posed character (HIP events on the renderer's stream around the whole route, median of 20; the route's
 host part beside it):
-  (a) the loop of P set_mesh_pose calls: the single-mesh route, which set_mesh_poses leaves as it was
+  (a) the loop of P set_mesh_pose calls, each a batch of one mesh
   (b) one set_mesh_poses from a host palette
   (c) one set_mesh_poses from a device palette
   (d) one set_mesh_poses with morph weights as well (morph, then skin; host inputs)
