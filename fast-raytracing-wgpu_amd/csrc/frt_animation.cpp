@@ -1,6 +1,7 @@
 // frt_animation.cpp — the host form of an animated rig (include/frt.h: frt_rig_*; DESIGN.md §11, "Animation"): frt_rig_create checks a description and
 // packs it into the one block frt_animation.hpp reads; frt_rig_evaluate is the specification of frt_renderer_animate's kernel, the same FRT_HD functions
-// run node by node in the block's order (parents first). Host code only; nothing here touches a device.
+// run node by node in the block's order (parents first); frt_rig_evaluate_blend and frt_rig_evaluate_nodes_blend ("Blending clips") are the same for
+// a list of samples. Host code only; nothing here touches a device.
 #include "frt_animation.hpp"
 #include "frt_loader.hpp"      // frt_model: frt_rig_from_model and the frt_model_* accessors of the rig
 #include "../../include/frt.h"
@@ -53,6 +54,48 @@ CastLayout frt::cast_layout(uint32_t n, const frt_cast_entry* e, const CastBindi
     auto put = [&l](size_t bytes) { const size_t off = l.bytes; l.bytes += (bytes + 15u) & ~(size_t)15u; return off; };
     l.ids_off = put((size_t)l.ninst * 4); l.mats_off = put((size_t)l.ninst * 64); l.pal_off = put((size_t)l.cols * 16); l.wt_off = put((size_t)l.nweights * 4);
     return l;
+}
+
+// "Blending clips": the checks of a sample list and of a blended cast (frt_animation.hpp).
+std::string frt::check_blend_samples(uint32_t n, const frt_clip_sample* s, uint32_t nclips) {
+    if (n == 0 || n > FRT_MAX_BLEND_SAMPLES) return std::to_string(n) + " samples (1 .. FRT_MAX_BLEND_SAMPLES)";
+    if (!s) return "null samples";
+    bool positive = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = "sample " + std::to_string(i) + ": ";
+        if (s[i].reserved != 0) return at + "reserved must be 0";
+        if (s[i].clip >= nclips) return at + "clip " + std::to_string(s[i].clip) + " out of range (" + std::to_string(nclips) + " clips)";
+        if (!std::isfinite(s[i].time)) return at + "time is not finite";
+        if (!std::isfinite(s[i].weight)) return at + "weight is not finite";
+        if (s[i].weight < 0.0f) return at + "a negative weight";
+        positive = positive || s[i].weight > 0.0f;
+    }
+    return positive ? "" : "no sample has a positive weight";
+}
+std::string frt::check_cast_blend_entries(uint32_t n, const frt_cast_blend_entry* e, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags,
+                                          uint32_t allowed_flags, const CastBinding* bindings, size_t nbindings, size_t nmeshes, size_t ninstances,
+                                          std::vector<frt_cast_entry>& plain) {
+    plain.clear();
+    if (n == 0 || n > FRT_MAX_CAST_ENTRIES) return std::to_string(n) + " entries (1 .. FRT_MAX_CAST_ENTRIES)";
+    if (!e) return "null entries";
+    if (nsamples == 0) return "0 samples";
+    if (!samples) return "null samples";
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string at = "entry " + std::to_string(k) + ": ";
+        if (e[k].reserved != 0) return at + "reserved must be 0";
+        if (e[k].num_samples == 0 || e[k].num_samples > FRT_MAX_BLEND_SAMPLES) return at + std::to_string(e[k].num_samples) + " samples (1 .. FRT_MAX_BLEND_SAMPLES)";
+        if (e[k].first_sample >= nsamples || e[k].num_samples > nsamples - e[k].first_sample)
+            return at + "samples " + std::to_string(e[k].first_sample) + " + " + std::to_string(e[k].num_samples) + " overrun the " + std::to_string(nsamples) + " given";
+    }
+    plain.resize(n);
+    for (uint32_t k = 0; k < n; ++k) plain[k] = frt_cast_entry{e[k].binding, samples[e[k].first_sample].clip, samples[e[k].first_sample].time, 0u};
+    const std::string bad = check_cast_entries(n, plain.data(), flags, allowed_flags, bindings, nbindings, nmeshes, ninstances);
+    if (!bad.empty()) return bad;
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s = check_blend_samples(e[k].num_samples, samples + e[k].first_sample, bindings[e[k].binding].nclips);
+        if (!s.empty()) return "entry " + std::to_string(k) + ": " + s;
+    }
+    return "";
 }
 
 // "" or what is wrong with the description. Every count is checked before the array it sizes is read.
@@ -367,6 +410,54 @@ int frt_rig_evaluate_nodes(const frt_rig* rig, uint32_t clip, float time, uint32
         global[i] = p == kRigNone ? local : mul(global[p], local);
     }
     for (uint32_t k = 0; k < n; ++k) {
+        const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
+        memcpy(mats_out + (size_t)16 * k, &M, 64);
+    }
+    return FRT_OK;
+}
+
+// "Blending clips": the specification of the kernels run with a list of samples. The globals of a checked blend, node by node, parents first.
+static std::vector<m4> blend_globals(const RigView& v, const RigHeader& h, uint32_t n, const frt_clip_sample* samples) {
+    std::vector<m4> global(h.nnodes);
+    for (uint32_t i = 0; i < h.nnodes; ++i) {
+        const m4 local = rig_local_matrix_blend(v, n, samples, i);
+        const uint32_t p = v.w[h.parent + i];
+        global[i] = p == kRigNone ? local : mul(global[p], local);
+    }
+    return global;
+}
+
+int frt_rig_evaluate_blend(const frt_rig* rig, uint32_t n, const frt_clip_sample* samples, float* joint_mats_out, float* morph_weights_out) {
+    if (!rig) return rig_fail("rig_evaluate_blend: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    const std::string bad = check_blend_samples(n, samples, h.nclips);
+    if (!bad.empty()) return rig_fail("rig_evaluate_blend: " + bad);
+    if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail("rig_evaluate_blend: null output");
+    if (h.njoints) {
+        const std::vector<m4> global = blend_globals(v, h, n, samples);
+        for (uint32_t j = 0; j < h.njoints; ++j) {
+            const m4 m = mul(global[v.w[h.joint_node + j]], load_m4(v.f(h.inv_bind) + (size_t)16 * j));
+            memcpy(joint_mats_out + (size_t)16 * j, &m, 64);
+        }
+    }
+    for (uint32_t c = 0; c < h.ntargets; ++c) morph_weights_out[c] = rig_morph_weight_blend(v, n, samples, c);
+    return FRT_OK;
+}
+
+int frt_rig_evaluate_nodes_blend(const frt_rig* rig, uint32_t n, const frt_clip_sample* samples, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
+    if (!rig) return rig_fail("rig_evaluate_nodes_blend: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    const std::string bad = check_blend_samples(n, samples, h.nclips);
+    if (!bad.empty()) return rig_fail("rig_evaluate_nodes_blend: " + bad);
+    if (nnodes == 0 || !nodes || !mats_out) return rig_fail("rig_evaluate_nodes_blend: nnodes is 0, or null nodes or output");
+    for (uint32_t k = 0; k < nnodes; ++k)
+        if (nodes[k] >= h.nnodes) return rig_fail("rig_evaluate_nodes_blend: node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
+    if (root && !all_finite(root, 16)) return rig_fail("rig_evaluate_nodes_blend: a root entry is not finite");
+    if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail("rig_evaluate_nodes_blend: an offsets entry is not finite");
+    const std::vector<m4> global = blend_globals(v, h, n, samples);
+    for (uint32_t k = 0; k < nnodes; ++k) {
         const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
         memcpy(mats_out + (size_t)16 * k, &M, 64);
     }

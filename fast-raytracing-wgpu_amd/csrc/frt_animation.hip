@@ -1,6 +1,7 @@
 // frt_animation.hip — the device form of an animated rig (include/frt.h: frt_renderer_bind_rig, _animate, _read_rig_pose, _unbind_rig; DESIGN.md §11,
 // "Animation"; _bind_rig_instances, _animate_instances: "Node animation"; _animate_cast: "Animating a cast"). Built with the library's contract flags. No arithmetic is written here: the kernel calls the FRT_HD functions of frt_animation.hpp that
-// frt_rig_evaluate calls on the host, so the palette and the weights have the host's bits.
+// frt_rig_evaluate calls on the host, so the palette and the weights have the host's bits. The _blend forms of the three animate calls ("Blending
+// clips") run the same kernels with their list of samples; frt_rig_evaluate_blend is their host form.
 //
 // The kernel is ONE workgroup of four waves per rig. (1) Every lane builds the local matrix of a node (sampling the clip's channels of that node),
 // strided by the workgroup's size, into LDS. (2) The globals are propagated level by level: a node's parent lies on the level above, which is complete
@@ -28,12 +29,29 @@ __device__ inline void rig_lds_store(float4* g, uint32_t n, const m4& m) {
     for (int c = 0; c < 4; ++c) g[(uint32_t)c * kRigLds + n] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
 }
 
+// What the kernels evaluate ("Blending clips"): a list of 1 .. FRT_MAX_BLEND_SAMPLES samples. The one-rig kernels take it by value as a kernel argument
+// and a cast's entries point at theirs, so its words are the same for every lane (scalar loads) and every branch on them is taken by the whole
+// workgroup. The single-clip calls pass a list of one sample of weight 1, which the contract makes the single clip's bits.
+struct RigSampleList { uint32_t n, pad0, pad1, pad2; frt_clip_sample s[FRT_MAX_BLEND_SAMPLES]; };
+static_assert(sizeof(frt_clip_sample) == 16 && sizeof(RigSampleList) == 16 + 16 * FRT_MAX_BLEND_SAMPLES, "RigSampleList layout");
+// What the host calls have refused: uniform, asked in front of the first barrier.
+__device__ inline bool rig_samples_ok(const RigHeader& h, const frt_clip_sample* s, uint32_t ns) {
+    if (ns == 0u || ns > FRT_MAX_BLEND_SAMPLES) return false;
+    bool positive = false;
+    for (uint32_t i = 0; i < ns; ++i) {
+        if (s[i].clip >= h.nclips) return false;
+        positive = positive || s[i].weight > 0.0f;
+    }
+    return positive;
+}
+
 // Phases (1) and (2) of both kernels: the global matrix of every node < N is in `g` behind the last barrier. Called by the whole workgroup with uniform
-// arguments (the level bounds are the same words for every lane).
-__device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, uint32_t clip, float t, float4* g, uint32_t N) {
+// arguments (the samples and the level bounds are the same words for every lane). Phase (1) is one lane, one node: every sample's clip sampled into
+// translation, rotation and scale, blended in registers as one running pose (rig_local_matrix_blend), the local matrix stored.
+__device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, const frt_clip_sample* s, uint32_t ns, float4* g, uint32_t N) {
     const uint32_t* words = v.w;
     const uint32_t tid = threadIdx.x;
-    for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix(v, clip, n, t));
+    for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix_blend(v, ns, s, n));
     __syncthreads();
     for (uint32_t level = 1u; level < h.nlevels; ++level) {
         const uint32_t begin = words[h.level_begin + level], end = words[h.level_begin + level + 1u];
@@ -45,15 +63,15 @@ __device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, uint32_
     }
 }
 
-__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, uint32_t clip, float t, float4* palette, float* weights) {
+__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, const RigSampleList list, float4* palette, float* weights) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig refuses a larger rig)
-    if (clip >= h.nclips) return;                                    // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
+    if (!rig_samples_ok(h, list.s, list.n)) return;                  // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
     if (h.njoints) {
-        rig_globals_to_lds(v, h, clip, t, g, N);
+        rig_globals_to_lds(v, h, list.s, list.n, g, N);
         for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
             const uint32_t n = words[h.joint_node + j];
             if (n >= N) continue;
@@ -62,19 +80,19 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
             for (int c = 0; c < 4; ++c) palette[4u * j + (uint32_t)c] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
         }
     }
-    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = rig_morph_weight(v, clip, c, t);
+    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = rig_morph_weight_blend(v, list.n, list.s, c);
 }
 
 // frt_renderer_animate_instances ("Node animation"): phases (1) and (2) as above, whether or not the rig has joints; (3) one lane per bound instance,
 // strided by the workgroup's size, loads its node's global from LDS, applies root and offset through rig_node_matrix (the host's text) and stores four
 // float4 into the binding's matrices. `nodes` [n]: stored node indices; `root` [16] and `offsets` [16 n]: null when the binding has none.
-__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, uint32_t clip, float t, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
+__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, const RigSampleList list, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig_instances refuses a larger rig)
-    if (clip >= h.nclips) return;                                    // (animate_instances refuses it; uniform, in front of the first barrier)
-    rig_globals_to_lds(v, h, clip, t, g, N);
+    if (!rig_samples_ok(h, list.s, list.n)) return;                  // (animate_instances refuses it; uniform, in front of the first barrier)
+    rig_globals_to_lds(v, h, list.s, list.n, g, N);
     for (uint32_t k = threadIdx.x; k < n; k += (uint32_t)kRigBlock) {
         const uint32_t node = nodes[k];
         if (node >= N) continue;                                     // (bind_rig_instances has checked it)
@@ -85,7 +103,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* wo
 }
 
 // frt_renderer_animate_cast ("Animating a cast"): the two kernels above as one, ONE WORKGROUP PER ENTRY of the call's table (gridDim.x = entries), so a
-// cast of any size is one launch and its rigs are walked side by side on as many CUs. An entry is 96 bytes, 16-byte aligned, and is read through the
+// cast of any size is one launch and its rigs are walked side by side on as many CUs. An entry is 112 bytes, 16-byte aligned, and is read through the
 // block's index alone: its words are the same for every lane (scalar loads), so every branch on them is taken by the whole workgroup, and all of them
 // sit in front of the first barrier or behind the last. Phases (1) and (2) are rig_globals_to_lds; phase (3) is that of the entry's kind, with every
 // store made twice: into the binding's own buffer (what read_rig_pose / read_rig_instances return) and into the entry's slice of the call's buffer,
@@ -93,14 +111,17 @@ __global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* wo
 // workgroups per CU.
 struct CastEntry {
     const uint32_t* words;      // the binding's rig block
-    uint32_t clip; float time;
+    const frt_clip_sample* samples;      // the entry's samples [nsamples], behind the table in the same device block
+    uint32_t nsamples;
     uint32_t kind, n;           // kRigMeshes | kRigInstances; instances: the bound instances
+    uint32_t pad0;
     float4* own; float4* all;   // meshes: the palette [4 njoints]; instances: the matrices [4 n] — the binding's, and the slice of the call's buffer
     float* own_w; float* all_w; // meshes: the weights [ntargets]
     const uint32_t* nodes; const float* root; const float* offsets;      // instances: as rig_nodes_kernel takes them
     const uint32_t* ids; uint32_t* all_ids;                              // instances: the binding's ids [n] and their slice of the call's ids
+    uint64_t pad1;
 };
-static_assert(sizeof(CastEntry) == 96 && sizeof(CastEntry) % 16 == 0, "CastEntry layout");
+static_assert(sizeof(CastEntry) == 112 && sizeof(CastEntry) % 16 == 0, "CastEntry layout");
 
 __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, const m4& m) {
 #pragma unroll
@@ -117,9 +138,9 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* ta
     const RigHeader h = v.h();
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (the bind calls refuse a larger rig)
-    if (e.clip >= h.nclips) return;                                  // (animate_cast refuses it; uniform, in front of the first barrier)
+    if (!rig_samples_ok(h, e.samples, e.nsamples)) return;           // (animate_cast refuses it; uniform, in front of the first barrier)
     const bool instances = e.kind == (uint32_t)kRigInstances;
-    if (instances || h.njoints) rig_globals_to_lds(v, h, e.clip, e.time, g, N);
+    if (instances || h.njoints) rig_globals_to_lds(v, h, e.samples, e.nsamples, g, N);
     if (instances) {
         for (uint32_t k = tid; k < e.n; k += (uint32_t)kRigBlock) {
             e.all_ids[k] = e.ids[k];
@@ -143,7 +164,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* ta
         rig_store_twice(e.own, e.all, j, mul(rig_lds_load(g, n), load_m4(v.f(h.inv_bind) + (size_t)16u * j)));
     }
     for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) {
-        const float w = rig_morph_weight(v, e.clip, c, e.time);
+        const float w = rig_morph_weight_blend(v, e.nsamples, e.samples, c);
         e.own_w[c] = w;
         e.all_w[c] = w;
     }
@@ -160,6 +181,136 @@ static uint32_t keep_binding(frt_renderer* r, const RigBinding& b) {
     return (uint32_t)slot;
 }
 static bool finite_bits(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) != 0x7f800000u; }
+// The list a kernel takes: the n samples a call has checked, or the single clip of a call without a blend as one sample of weight 1.
+static RigSampleList sample_list(uint32_t n, const frt_clip_sample* s) {
+    RigSampleList l;
+    memset(&l, 0, sizeof(l));
+    l.n = n;
+    memcpy(l.s, s, (size_t)n * sizeof(frt_clip_sample));
+    return l;
+}
+static RigSampleList one_clip(uint32_t clip, float time) { const frt_clip_sample s{clip, time, 1.0f, 0u}; return sample_list(1u, &s); }
+
+// frt_renderer_animate_instances and _animate_instances_blend behind their checks: the kernel, then the device transform.
+static int move_bound_instances(frt_renderer* r, const std::string& call, RigBinding* b, const RigSampleList& list) {
+    const uint32_t n = (uint32_t)b->instance_ids.size();
+    {
+        // The kernel writes the binding's matrices only, which nothing but the device transform of an earlier animate_instances reads: on this stream, in front of it.
+        FRT_DEVICE(r);
+        if (b->ids_stale) {      // (remove_instances has renumbered the instances)
+            if (const int rc = r->rig_up.reserve((size_t)n * 4, 0, r->stream)) return rc;
+            memcpy(r->rig_up.h, b->instance_ids.data(), (size_t)n * 4);
+            HIP_TRY(hipMemcpyAsync(b->ids.p, r->rig_up.h, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
+            if (const int rc = r->rig_up.mark(r->stream)) return rc;
+            b->ids_stale = false;
+        }
+        const uint8_t* tab = b->tab.as<const uint8_t>();
+        const size_t node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
+        const float* root = b->has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
+        const float* offsets = b->has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b->has_root ? 64u : 0u)) : nullptr;
+        hipLaunchKernelGGL(rig_nodes_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
+    }
+    return frt_renderer_set_instance_transforms_ex(r, n, b->ids.as<const uint32_t>(), b->mats.as<const float>(), FRT_TRANSFORM_DEVICE);
+}
+// frt_renderer_animate and _animate_blend behind their checks of the samples: the meshes as animate checks them, the kernel, then the pose batch.
+static int pose_bound_meshes(frt_renderer* r, const std::string& call, RigBinding* b, const RigSampleList& list, uint32_t flags) {
+    const uint32_t n = (uint32_t)b->mesh_ids.size();
+    const std::string bad = check_posed_meshes(r, n, b->mesh_ids.data(), b->njoints != 0, b->palette.p, b->njoints, b->ntargets != 0, b->weights.p, b->ntargets, false);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, call + ": " + bad);
+    {
+        // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
+        FRT_DEVICE(r);
+        hipLaunchKernelGGL(rig_evaluate_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, b->palette.as<float4>(), b->weights.as<float>());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
+    }
+    return frt_renderer_set_mesh_poses(r, n, b->mesh_ids.data(), b->njoints ? b->palette.as<float>() : nullptr, b->njoints,
+                                       b->ntargets ? b->weights.as<float>() : nullptr, b->ntargets, flags | FRT_DEFORM_DEVICE);
+}
+
+// What check_cast_entries asks about the renderer's bindings.
+static std::vector<CastBinding> cast_bindings(const frt_renderer* r) {
+    std::vector<CastBinding> info(r->rigs.size());
+    for (size_t i = 0; i < r->rigs.size(); ++i) {
+        const RigBinding& b = r->rigs[i];
+        const std::vector<uint32_t>& ids = b.kind == kRigInstances ? b.instance_ids : b.mesh_ids;
+        info[i].live = b.live; info[i].kind = b.kind; info[i].nclips = b.nclips; info[i].njoints = b.njoints; info[i].ntargets = b.ntargets;
+        info[i].ids = ids.data(); info[i].n = (uint32_t)ids.size();
+    }
+    return info;
+}
+// frt_renderer_animate_cast and _animate_cast_blend behind the checks of their entries (`entries`: the bindings, as cast_layout takes them; `ranges`:
+// every entry's samples among samples [nsamples]): every mesh entry's meshes as animate checks them, the layout of the call's buffer, ONE staged copy —
+// the entry table, the samples and the ids of the instance bindings remove_instances has renumbered — ONE launch, then frt_scene_edit.hip's apply_cast.
+// Past the first call of a steady cast nothing here allocates, waits for the stream or copies synchronously: the pinned block's event has long passed
+// when the next call comes.
+static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, const frt_cast_entry* entries, const frt_cast_blend_entry* ranges,
+                    const std::vector<CastBinding>& info, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags) {
+    std::string bad;
+    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
+        const RigBinding& b = r->rigs[entries[k].binding];
+        if (b.kind != kRigMeshes) continue;
+        bad = check_posed_meshes(r, (uint32_t)b.mesh_ids.size(), b.mesh_ids.data(), b.njoints != 0, b.palette.p, b.njoints, b.ntargets != 0, b.weights.p, b.ntargets, false);
+        if (!bad.empty()) bad = "entry " + std::to_string(k) + ": " + bad;
+    }
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, call_name + ": " + bad);
+    const CastLayout l = cast_layout(n, entries, info.data());
+    CastApply call;
+    call.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
+    {
+        // The kernel writes the bindings' own buffers and the call's buffer only, which nothing but the launches of an earlier call read: on this stream, in front of it.
+        FRT_DEVICE(r);
+        if (const int rc = r->cast.buf.ensure(r, l.bytes)) return rc;
+        uint8_t* all = r->cast.buf.as<uint8_t>();
+        const size_t table_bytes = (size_t)n * sizeof(CastEntry), sample_bytes = (size_t)nsamples * sizeof(frt_clip_sample);      // (both multiples of 16)
+        size_t stale_bytes = 0;
+        for (uint32_t k = 0; k < n; ++k) { const RigBinding& b = r->rigs[entries[k].binding]; if (b.kind == kRigInstances && b.ids_stale) stale_bytes += b.instance_ids.size() * 4; }
+        if (const int rc = r->rig_up.reserve(table_bytes + sample_bytes + stale_bytes, table_bytes + sample_bytes, r->stream)) return rc;
+        CastEntry* table = reinterpret_cast<CastEntry*>(r->rig_up.h);
+        memcpy(r->rig_up.h + table_bytes, samples, sample_bytes);
+        const frt_clip_sample* dev_samples = reinterpret_cast<const frt_clip_sample*>(r->rig_up.d + table_bytes);
+        size_t stale_at = table_bytes + sample_bytes;
+        for (uint32_t k = 0; k < n; ++k) {
+            RigBinding& b = r->rigs[entries[k].binding];
+            CastEntry e;
+            memset(&e, 0, sizeof(e));
+            e.words = b.rig.as<const uint32_t>(); e.samples = dev_samples + ranges[k].first_sample; e.nsamples = ranges[k].num_samples; e.kind = b.kind;
+            if (b.kind == kRigInstances) {
+                const uint32_t ni = (uint32_t)b.instance_ids.size();
+                if (b.ids_stale) {      // (remove_instances has renumbered the instances) in front of the launch, as animate_instances uploads them
+                    memcpy(r->rig_up.h + stale_at, b.instance_ids.data(), (size_t)ni * 4);
+                    HIP_TRY(hipMemcpyAsync(b.ids.p, r->rig_up.h + stale_at, (size_t)ni * 4, hipMemcpyHostToDevice, r->stream));
+                    stale_at += (size_t)ni * 4;
+                    b.ids_stale = false;
+                }
+                const uint8_t* tab = b.tab.as<const uint8_t>();
+                const size_t node_bytes = ((size_t)ni * 4 + 15u) & ~(size_t)15u;
+                e.n = ni; e.nodes = reinterpret_cast<const uint32_t*>(tab);
+                e.root = b.has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
+                e.offsets = b.has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b.has_root ? 64u : 0u)) : nullptr;
+                e.own = b.mats.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.mats_off) + 4u * (size_t)l.first[k];
+                e.ids = b.ids.as<const uint32_t>(); e.all_ids = reinterpret_cast<uint32_t*>(all + l.ids_off) + l.first[k];
+            } else {
+                e.own = b.palette.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.pal_off) + l.first[k];
+                e.own_w = b.weights.as<float>(); e.all_w = reinterpret_cast<float*>(all + l.wt_off) + l.first_weight[k];
+                for (uint32_t m : b.mesh_ids)
+                    call.meshes.push_back(CastMesh{m, b.njoints ? reinterpret_cast<const float*>(e.all) : nullptr, b.njoints, b.ntargets ? e.all_w : nullptr, b.ntargets});
+            }
+            table[k] = e;
+        }
+        HIP_TRY(hipMemcpyAsync(r->rig_up.d, r->rig_up.h, table_bytes + sample_bytes, hipMemcpyHostToDevice, r->stream));
+        if (const int rc = r->rig_up.mark(r->stream)) return rc;
+        hipLaunchKernelGGL(rig_cast_kernel, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const CastEntry*>(r->rig_up.d));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call_name + ": " + hipGetErrorString(e)); }
+        call.ninst = l.ninst; call.ids = reinterpret_cast<const uint32_t*>(all + l.ids_off); call.mats = reinterpret_cast<const float*>(all + l.mats_off);
+        if (l.cols) { call.palettes = reinterpret_cast<const float*>(all + l.pal_off); call.cols = l.cols; }
+        if (l.nweights) { call.weights = reinterpret_cast<const float*>(all + l.wt_off); call.nweights = l.nweights; }
+    }
+    return apply_cast(r, call);
+}
 
 extern "C" {
 
@@ -244,26 +395,17 @@ int frt_renderer_animate_instances(frt_renderer* r, uint32_t binding, uint32_t c
     if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate)");
     if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate_instances: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
     if (!finite_bits(time)) return fail(FRT_ERR_INVALID_ARG, "animate_instances: time is not finite");
-    const uint32_t n = (uint32_t)b->instance_ids.size();
-    {
-        // The kernel writes the binding's matrices only, which nothing but the device transform of an earlier animate_instances reads: on this stream, in front of it.
-        FRT_DEVICE(r);
-        if (b->ids_stale) {      // (remove_instances has renumbered the instances)
-            if (const int rc = r->rig_up.reserve((size_t)n * 4, 0, r->stream)) return rc;
-            memcpy(r->rig_up.h, b->instance_ids.data(), (size_t)n * 4);
-            HIP_TRY(hipMemcpyAsync(b->ids.p, r->rig_up.h, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
-            if (const int rc = r->rig_up.mark(r->stream)) return rc;
-            b->ids_stale = false;
-        }
-        const uint8_t* tab = b->tab.as<const uint8_t>();
-        const size_t node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
-        const float* root = b->has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
-        const float* offsets = b->has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b->has_root ? 64u : 0u)) : nullptr;
-        hipLaunchKernelGGL(rig_nodes_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), clip, time, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate_instances: ") + hipGetErrorString(e)); }
-    }
-    return frt_renderer_set_instance_transforms_ex(r, n, b->ids.as<const uint32_t>(), b->mats.as<const float>(), FRT_TRANSFORM_DEVICE);
+    return move_bound_instances(r, "animate_instances", b, one_clip(clip, time));
+}
+
+int frt_renderer_animate_instances_blend(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_sample* samples) {
+    if (const int rc = check_entry(r, "animate_instances_blend", kEditChecks | kRefit)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate_instances_blend: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances_blend: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate_blend)");
+    const std::string bad = check_blend_samples(n, samples, b->nclips);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_instances_blend: " + bad);
+    return move_bound_instances(r, "animate_instances_blend", b, sample_list(n, samples));
 }
 
 int frt_renderer_read_rig_instances(frt_renderer* r, uint32_t binding, float* mats_out) {
@@ -285,92 +427,39 @@ int frt_renderer_animate(frt_renderer* r, uint32_t binding, uint32_t clip, float
     if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances)");
     if (clip >= b->nclips) return fail(FRT_ERR_INVALID_ARG, "animate: clip " + std::to_string(clip) + " out of range (" + std::to_string(b->nclips) + " clips)");
     if ((__builtin_bit_cast(uint32_t, time) & 0x7f800000u) == 0x7f800000u) return fail(FRT_ERR_INVALID_ARG, "animate: time is not finite");
-    const uint32_t n = (uint32_t)b->mesh_ids.size();
-    const std::string bad = check_posed_meshes(r, n, b->mesh_ids.data(), b->njoints != 0, b->palette.p, b->njoints, b->ntargets != 0, b->weights.p, b->ntargets, false);
-    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate: " + bad);
-    {
-        // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
-        FRT_DEVICE(r);
-        hipLaunchKernelGGL(rig_evaluate_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), clip, time, b->palette.as<float4>(), b->weights.as<float>());
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate: ") + hipGetErrorString(e)); }
-    }
-    return frt_renderer_set_mesh_poses(r, n, b->mesh_ids.data(), b->njoints ? b->palette.as<float>() : nullptr, b->njoints,
-                                       b->ntargets ? b->weights.as<float>() : nullptr, b->ntargets, flags | FRT_DEFORM_DEVICE);
+    return pose_bound_meshes(r, "animate", b, one_clip(clip, time), flags);
 }
 
-// The checks (check_cast_entries, then every mesh entry's meshes as animate checks them), the layout of the call's buffer, ONE staged copy — the entry
-// table and the ids of the instance bindings remove_instances has renumbered — ONE launch, then frt_scene_edit.hip's apply_cast. Past the first call of
-// a steady cast nothing here allocates, waits for the stream or copies synchronously: the pinned block's event has long passed when the next call comes.
+int frt_renderer_animate_blend(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_sample* samples, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate_blend", kEditChecks | kRefit)) return rc;
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) return fail(FRT_ERR_INVALID_ARG, "animate_blend: unknown flag bits");
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate_blend: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate_blend: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances_blend)");
+    const std::string bad = check_blend_samples(n, samples, b->nclips);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_blend: " + bad);
+    return pose_bound_meshes(r, "animate_blend", b, sample_list(n, samples), flags);
+}
+
 int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry* entries, uint32_t flags) {
     if (const int rc = check_entry(r, "animate_cast", kEditChecks | kRefit)) return rc;
-    std::vector<CastBinding> info(r->rigs.size());
-    for (size_t i = 0; i < r->rigs.size(); ++i) {
-        const RigBinding& b = r->rigs[i];
-        const std::vector<uint32_t>& ids = b.kind == kRigInstances ? b.instance_ids : b.mesh_ids;
-        info[i].live = b.live; info[i].kind = b.kind; info[i].nclips = b.nclips; info[i].njoints = b.njoints; info[i].ntargets = b.ntargets;
-        info[i].ids = ids.data(); info[i].n = (uint32_t)ids.size();
-    }
-    std::string bad = check_cast_entries(n, entries, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(), r->rf.inst.size());
-    for (uint32_t k = 0; k < n && bad.empty(); ++k) {
-        const RigBinding& b = r->rigs[entries[k].binding];
-        if (b.kind != kRigMeshes) continue;
-        bad = check_posed_meshes(r, (uint32_t)b.mesh_ids.size(), b.mesh_ids.data(), b.njoints != 0, b.palette.p, b.njoints, b.ntargets != 0, b.weights.p, b.ntargets, false);
-        if (!bad.empty()) bad = "entry " + std::to_string(k) + ": " + bad;
-    }
+    const std::vector<CastBinding> info = cast_bindings(r);
+    const std::string bad = check_cast_entries(n, entries, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(), r->rf.inst.size());
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast: " + bad);
-    const CastLayout l = cast_layout(n, entries, info.data());
-    CastApply call;
-    call.recompute = (flags & FRT_DEFORM_RECOMPUTE_NORMALS) != 0;
-    {
-        // The kernel writes the bindings' own buffers and the call's buffer only, which nothing but the launches of an earlier call read: on this stream, in front of it.
-        FRT_DEVICE(r);
-        if (const int rc = r->cast.buf.ensure(r, l.bytes)) return rc;
-        uint8_t* all = r->cast.buf.as<uint8_t>();
-        const size_t table_bytes = (size_t)n * sizeof(CastEntry);
-        size_t stale_bytes = 0;
-        for (uint32_t k = 0; k < n; ++k) { const RigBinding& b = r->rigs[entries[k].binding]; if (b.kind == kRigInstances && b.ids_stale) stale_bytes += b.instance_ids.size() * 4; }
-        if (const int rc = r->rig_up.reserve(table_bytes + stale_bytes, table_bytes, r->stream)) return rc;
-        CastEntry* table = reinterpret_cast<CastEntry*>(r->rig_up.h);
-        size_t stale_at = table_bytes;
-        for (uint32_t k = 0; k < n; ++k) {
-            RigBinding& b = r->rigs[entries[k].binding];
-            CastEntry e;
-            memset(&e, 0, sizeof(e));
-            e.words = b.rig.as<const uint32_t>(); e.clip = entries[k].clip; e.time = entries[k].time; e.kind = b.kind;
-            if (b.kind == kRigInstances) {
-                const uint32_t ni = (uint32_t)b.instance_ids.size();
-                if (b.ids_stale) {      // (remove_instances has renumbered the instances) in front of the launch, as animate_instances uploads them
-                    memcpy(r->rig_up.h + stale_at, b.instance_ids.data(), (size_t)ni * 4);
-                    HIP_TRY(hipMemcpyAsync(b.ids.p, r->rig_up.h + stale_at, (size_t)ni * 4, hipMemcpyHostToDevice, r->stream));
-                    stale_at += (size_t)ni * 4;
-                    b.ids_stale = false;
-                }
-                const uint8_t* tab = b.tab.as<const uint8_t>();
-                const size_t node_bytes = ((size_t)ni * 4 + 15u) & ~(size_t)15u;
-                e.n = ni; e.nodes = reinterpret_cast<const uint32_t*>(tab);
-                e.root = b.has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
-                e.offsets = b.has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b.has_root ? 64u : 0u)) : nullptr;
-                e.own = b.mats.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.mats_off) + 4u * (size_t)l.first[k];
-                e.ids = b.ids.as<const uint32_t>(); e.all_ids = reinterpret_cast<uint32_t*>(all + l.ids_off) + l.first[k];
-            } else {
-                e.own = b.palette.as<float4>(); e.all = reinterpret_cast<float4*>(all + l.pal_off) + l.first[k];
-                e.own_w = b.weights.as<float>(); e.all_w = reinterpret_cast<float*>(all + l.wt_off) + l.first_weight[k];
-                for (uint32_t m : b.mesh_ids)
-                    call.meshes.push_back(CastMesh{m, b.njoints ? reinterpret_cast<const float*>(e.all) : nullptr, b.njoints, b.ntargets ? e.all_w : nullptr, b.ntargets});
-            }
-            table[k] = e;
-        }
-        HIP_TRY(hipMemcpyAsync(r->rig_up.d, r->rig_up.h, table_bytes, hipMemcpyHostToDevice, r->stream));
-        if (const int rc = r->rig_up.mark(r->stream)) return rc;
-        hipLaunchKernelGGL(rig_cast_kernel, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const CastEntry*>(r->rig_up.d));
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, std::string("animate_cast: ") + hipGetErrorString(e)); }
-        call.ninst = l.ninst; call.ids = reinterpret_cast<const uint32_t*>(all + l.ids_off); call.mats = reinterpret_cast<const float*>(all + l.mats_off);
-        if (l.cols) { call.palettes = reinterpret_cast<const float*>(all + l.pal_off); call.cols = l.cols; }
-        if (l.nweights) { call.weights = reinterpret_cast<const float*>(all + l.wt_off); call.nweights = l.nweights; }
-    }
-    return apply_cast(r, call);
+    std::vector<frt_clip_sample> samples(n);      // entry k: the list of one sample k
+    std::vector<frt_cast_blend_entry> ranges(n);
+    for (uint32_t k = 0; k < n; ++k) { samples[k] = frt_clip_sample{entries[k].clip, entries[k].time, 1.0f, 0u}; ranges[k] = frt_cast_blend_entry{entries[k].binding, k, 1u, 0u}; }
+    return run_cast(r, "animate_cast", n, entries, ranges.data(), info, n, samples.data(), flags);
+}
+
+int frt_renderer_animate_cast_blend(frt_renderer* r, uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate_cast_blend", kEditChecks | kRefit)) return rc;
+    const std::vector<CastBinding> info = cast_bindings(r);
+    std::vector<frt_cast_entry> plain;
+    const std::string bad = check_cast_blend_entries(n, entries, nsamples, samples, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(),
+                                                     r->rf.inst.size(), plain);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast_blend: " + bad);
+    return run_cast(r, "animate_cast_blend", n, plain.data(), entries, info, nsamples, samples, flags);
 }
 
 int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out) {

@@ -7,6 +7,7 @@
 // byte for byte, and both forms read it through the same accessors. Nodes are stored by depth (level 0: the roots), parents in front of their children.
 #pragma once
 #include "frt_math.hpp"
+#include "../../include/frt.h"      // frt_clip_sample, FRT_MAX_BLEND_SAMPLES
 
 namespace frt {
 
@@ -125,32 +126,39 @@ FRT_HD m4 rig_trs_matrix(f3 t, f4 q, f3 s) {
     m.c[3] = mk4(t.x, t.y, t.z, 1.0f);
     return m;
 }
-// The local matrix of node n under clip `clip` at time t: a matrix node's matrix; else T * R * S with every path the clip has a channel for sampled and
-// the others at rest.
-FRT_HD m4 rig_local_matrix(RigView v, uint32_t clip, uint32_t n, float t) {
+// Translation, rotation and scale of the non-matrix node n under clip `clip` at time t: every path the clip has a channel for sampled, the others at rest.
+struct RigTrs { f3 t; f4 q; f3 s; };
+FRT_HD RigTrs rig_local_trs(RigView v, uint32_t clip, uint32_t n, float t) {
     const RigHeader h = v.h();
     const float* rest = v.f(h.rest) + (size_t)16u * n;
-    if (v.w[h.kind + n]) return load_m4(rest);
-    f3 tr = mk3(rest[0], rest[1], rest[2]), sc = mk3(rest[8], rest[9], rest[10]);
-    f4 q = mk4(rest[4], rest[5], rest[6], rest[7]);
+    RigTrs r;
+    r.t = mk3(rest[0], rest[1], rest[2]); r.s = mk3(rest[8], rest[9], rest[10]);
+    r.q = mk4(rest[4], rest[5], rest[6], rest[7]);
     const uint32_t* of = v.w + v.clip(clip).node_table + (size_t)3u * n;
     if (of[0] != kRigNone) {
         const RigChannel ch = v.channel(of[0]);
         const RigKey key = rig_find_key(v.f(ch.times), ch.nkeys, t);
-        tr = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
-                 rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
+        r.t = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
+                  rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
     }
     if (of[1] != kRigNone) {
         const RigChannel ch = v.channel(of[1]);
-        q = rig_sample_rotation(v.f(ch.values), ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t));
+        r.q = rig_sample_rotation(v.f(ch.values), ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t));
     }
     if (of[2] != kRigNone) {
         const RigChannel ch = v.channel(of[2]);
         const RigKey key = rig_find_key(v.f(ch.times), ch.nkeys, t);
-        sc = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
-                 rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
+        r.s = mk3(rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 0u), rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 1u),
+                  rig_sample_component(v.f(ch.values), 3u, ch.interp, key, 2u));
     }
-    return rig_trs_matrix(tr, q, sc);
+    return r;
+}
+// The local matrix of node n under clip `clip` at time t: a matrix node's matrix; else T * R * S of rig_local_trs.
+FRT_HD m4 rig_local_matrix(RigView v, uint32_t clip, uint32_t n, float t) {
+    const RigHeader h = v.h();
+    if (v.w[h.kind + n]) return load_m4(v.f(h.rest) + (size_t)16u * n);
+    const RigTrs r = rig_local_trs(v, clip, n, t);
+    return rig_trs_matrix(r.t, r.q, r.s);
 }
 // Morph weight c: the clip's weights channel sampled, or the default weight.
 FRT_HD float rig_morph_weight(RigView v, uint32_t clip, uint32_t c, float t) {
@@ -158,6 +166,45 @@ FRT_HD float rig_morph_weight(RigView v, uint32_t clip, uint32_t c, float t) {
     if (wc == kRigNone) return v.f(v.h().def_weights)[c];
     const RigChannel ch = v.channel(wc);
     return rig_sample_component(v.f(ch.values), ch.width, ch.interp, rig_find_key(v.f(ch.times), ch.nkeys, t), c);
+}
+
+// Blending clips (include/frt.h: frt_rig_evaluate_blend; DESIGN.md §11, "Blending clips"): the samples s [ns] of (clip, time, weight) in the order
+// given, ONE running pose. A sample of weight 0 is skipped entirely; the first sample with a positive weight gives the pose as sampled, without
+// arithmetic, and W = w; every later one W = W + w, a = w / W, translation and scale mixed per component, the rotation rig_slerp(R, R_s, a). A list
+// without a positive weight is refused by every caller (the result here is then the zero pose).
+FRT_HD m4 rig_local_matrix_blend(RigView v, uint32_t ns, const frt_clip_sample* s, uint32_t n) {
+    const RigHeader h = v.h();
+    if (v.w[h.kind + n]) return load_m4(v.f(h.rest) + (size_t)16u * n);
+    RigTrs r;
+    r.t = mk3(0.0f, 0.0f, 0.0f); r.s = mk3(0.0f, 0.0f, 0.0f); r.q = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    float W = 0.0f;
+    bool first = true;
+    for (uint32_t i = 0; i < ns; ++i) {
+        const float w = s[i].weight;
+        if (!(w > 0.0f)) continue;
+        const RigTrs x = rig_local_trs(v, s[i].clip, n, s[i].time);
+        if (first) { r = x; W = w; first = false; continue; }
+        W = W + w;
+        const float a = w / W;
+        r.t = mk3(mixf(r.t.x, x.t.x, a), mixf(r.t.y, x.t.y, a), mixf(r.t.z, x.t.z, a));
+        r.s = mk3(mixf(r.s.x, x.s.x, a), mixf(r.s.y, x.s.y, a), mixf(r.s.z, x.s.z, a));
+        r.q = rig_slerp(r.q, x.q, a);
+    }
+    return rig_trs_matrix(r.t, r.q, r.s);
+}
+// Morph weight c of a blend: rig_morph_weight of every sample (a clip's defaults included) under the same running mix.
+FRT_HD float rig_morph_weight_blend(RigView v, uint32_t ns, const frt_clip_sample* s, uint32_t c) {
+    float r = 0.0f, W = 0.0f;
+    bool first = true;
+    for (uint32_t i = 0; i < ns; ++i) {
+        const float w = s[i].weight;
+        if (!(w > 0.0f)) continue;
+        const float x = rig_morph_weight(v, s[i].clip, c, s[i].time);
+        if (first) { r = x; W = w; first = false; continue; }
+        W = W + w;
+        r = mixf(r, x, w / W);
+    }
+    return r;
 }
 
 // The matrix a bound instance takes from the global G of its node ("Node animation"): mul(mul(root, G), offset), the palette's mul. A null `root` or
@@ -205,4 +252,14 @@ struct CastLayout {
     size_t ids_off = 0, mats_off = 0, pal_off = 0, wt_off = 0, bytes = 0;
 };
 CastLayout cast_layout(uint32_t n, const frt_cast_entry* entries, const CastBinding* bindings);
+
+// "Blending clips": "" or why a sample list is refused for a rig of `nclips` clips: n == 0 or above FRT_MAX_BLEND_SAMPLES, null samples, reserved != 0,
+// a clip out of range, a time or a weight that is not finite, a negative weight, no positive weight. The count is checked before the list is read.
+std::string check_blend_samples(uint32_t n, const frt_clip_sample* samples, uint32_t nclips);
+// frt_renderer_animate_cast_blend: "" or why the call is refused. The counts, every entry's reserved word and its sample range (inside `nsamples`,
+// 1 .. FRT_MAX_BLEND_SAMPLES long) first; then check_cast_entries over `plain`, which is filled here with every entry's binding and its first sample's
+// clip and time (what cast_layout takes afterwards); then check_blend_samples of every entry's range against its binding's clips.
+std::string check_cast_blend_entries(uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags,
+                                     uint32_t allowed_flags, const CastBinding* bindings, size_t nbindings, size_t nmeshes, size_t ninstances,
+                                     std::vector<frt_cast_entry>& plain);
 }

@@ -97,6 +97,17 @@ class CastEntry(C.Structure):                       # include/frt.h: frt_cast_en
     _fields_ = [("binding", C.c_uint32), ("clip", C.c_uint32), ("time", C.c_float), ("reserved", C.c_uint32)]
 
 
+MAX_BLEND_SAMPLES = 8                               # include/frt.h: FRT_MAX_BLEND_SAMPLES
+
+
+class ClipSample(C.Structure):                      # include/frt.h: frt_clip_sample
+    _fields_ = [("clip", C.c_uint32), ("time", C.c_float), ("weight", C.c_float), ("reserved", C.c_uint32)]
+
+
+class CastBlendEntry(C.Structure):                  # include/frt.h: frt_cast_blend_entry
+    _fields_ = [("binding", C.c_uint32), ("first_sample", C.c_uint32), ("num_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}      # include/frt.h: FRT_RIG_PATH_*
 RIG_INTERPOLATIONS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}              # include/frt.h: FRT_RIG_*
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
@@ -232,6 +243,11 @@ SYMBOLS = {
     "frt_renderer_animate_instances": (C.c_int, [_P, _U32, _U32, C.c_float]),
     "frt_renderer_read_rig_instances": (C.c_int, [_P, _U32, _P]),
     "frt_renderer_animate_cast": (C.c_int, [_P, _U32, _P, _U32]),
+    "frt_rig_evaluate_blend": (C.c_int, [_P, _U32, _P, _P, _P]),
+    "frt_rig_evaluate_nodes_blend": (C.c_int, [_P, _U32, _P, _U32, _P, _P, _P, _P]),
+    "frt_renderer_animate_blend": (C.c_int, [_P, _U32, _U32, _P, _U32]),
+    "frt_renderer_animate_instances_blend": (C.c_int, [_P, _U32, _U32, _P]),
+    "frt_renderer_animate_cast_blend": (C.c_int, [_P, _U32, _P, _U32, _P, _U32]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

@@ -133,6 +133,44 @@ class Rig:
         return out
 
 
+    # ---- blending clips (include/frt.h: frt_rig_evaluate_blend; DESIGN.md section 11, "Blending clips")
+    def sample_rows(self, samples):
+        """[(clip index, t, weight)] of `samples`, an iterable of (clip, t, weight) with a clip a number or a name."""
+        rows = []
+        for k, s in enumerate(samples):
+            s = tuple(s)
+            if len(s) != 3:
+                raise FrtError(f"Rig: sample {k} has {len(s)} fields, not (clip, t, weight)")
+            rows.append((self.clip_index(s[0]), float(s[1]), float(s[2])))
+        return rows
+
+    def evaluate_blend(self, samples):
+        """evaluate() of a blend: `samples` is [(clip, t, weight), ...], 1 to MAX_BLEND_SAMPLES of them, a clip a number or a name. Weights are
+        not negative, need not sum to one, and at least one is positive. The samples are folded in order into one running pose per node: translation
+        and scale mixed, the rotation slerped, each by w / (sum of the weights so far), in front of the local matrix. One sample, or every other
+        weight zero, is evaluate(clip, t) bit for bit."""
+        pal = np.zeros((self.num_joints, 16), np.float32) if self.num_joints else None
+        w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
+        n, table = sample_table(self.sample_rows(samples))
+        check(lib().frt_rig_evaluate_blend(self._h, n, table, pal.ctypes.data if pal is not None else None, w.ctypes.data if w is not None else None))
+        return pal, w
+
+    def evaluate_nodes_blend(self, samples, nodes, root=None, offsets=None):
+        """evaluate_nodes() of a blend (`samples` as evaluate_blend takes them): the matrices Renderer.animate_instances_blend gives the instances."""
+        n, nodes, root, offsets = node_args(nodes, root, offsets)
+        out = np.zeros((n, 16), np.float32)
+        ns, table = sample_table(self.sample_rows(samples))
+        check(lib().frt_rig_evaluate_nodes_blend(self._h, ns, table, n, nodes.ctypes.data, root.ctypes.data if root is not None else None,
+                                                 offsets.ctypes.data if offsets is not None else None, out.ctypes.data))
+        return out
+
+
+def sample_table(rows):
+    """(n, frt_clip_sample [n]) of [(clip index, t, weight)]."""
+    from ._lib import ClipSample
+    return len(rows), (ClipSample * max(len(rows), 1))(*[ClipSample(c, t, w, 0) for c, t, w in rows])
+
+
 def node_args(nodes, root, offsets):
     """(n, nodes uint32 [n], root float32 [16] or None, offsets float32 [n, 16] or None) as the C calls of node animation take them."""
     nodes = np.ascontiguousarray(nodes, np.int64).reshape(-1)
@@ -169,3 +207,28 @@ def host_cast(target, entries, normals="recompute"):
         target.animate_instances(**e)
     for e in mesh:
         target.animate(**e, normals=normals)
+
+
+def host_cast_blend(target, entries, normals="recompute"):
+    """host_cast for blends ("Blending clips"): what SceneBuilder.animate_cast_blend and MultiRenderer.animate_cast_blend do.
+    Every entry is the arguments of `target`'s animate_blend, (rig, mesh_ids, samples), or of its animate_instances_blend,
+    (rig, instance_ids, nodes, samples[, root[, offsets]]), as a tuple or as a dict by name (a dict with "nodes" is an instance entry). The
+    instance entries are applied first, in the order given, then the mesh entries."""
+    inst, mesh = [], []
+    for k, e in enumerate(entries):
+        if isinstance(e, dict):
+            (inst if "nodes" in e else mesh).append(dict(e))
+            continue
+        e = tuple(e)
+        if len(e) == 3:
+            mesh.append(dict(zip(("rig", "mesh_ids", "samples"), e)))
+        elif 4 <= len(e) <= 6:
+            inst.append(dict(zip(("rig", "instance_ids", "nodes", "samples", "root", "offsets"), e)))
+        else:
+            raise FrtError(f"animate_cast_blend: entry {k} has {len(e)} fields (3: a mesh entry, 4 to 6: an instance entry)")
+    if not inst and not mesh:
+        raise FrtError("animate_cast_blend: no entries")
+    for e in inst:
+        target.animate_instances_blend(**e)
+    for e in mesh:
+        target.animate_blend(**e, normals=normals)

@@ -453,6 +453,34 @@ class Renderer(_HostQueries, _SceneGrowth):
         table = (CastEntry * max(len(rows), 1))(*[CastEntry(b, c, t, 0) for b, c, t in rows])
         check(lib().frt_renderer_animate_cast(self._h, len(rows), table, deform_flags(normals)))
 
+    # ---- blending clips (include/frt.h: frt_renderer_animate_blend and the two calls after it; DESIGN.md section 11, "Blending clips")
+    def animate_blend(self, binding, samples, normals="recompute"):
+        """animate() with a blend where it takes a clip and a time: `samples` is [(clip, t, weight), ...] as Rig.evaluate_blend takes them, e.g. a
+        cross-fade [("idle", t0, 1 - f), ("walk", t1, f)]. The same kernel; the palette and weights are rig.evaluate_blend(samples) bit for bit."""
+        from .animation import sample_table
+        n, table = sample_table(self._bound_rig("animate_blend", binding).sample_rows(samples))
+        check(lib().frt_renderer_animate_blend(self._h, int(binding), n, table, deform_flags(normals)))
+
+    def animate_instances_blend(self, binding, samples):
+        """animate_instances() with a blend: the matrices are rig.evaluate_nodes_blend(samples, ...) bit for bit."""
+        from .animation import sample_table
+        n, table = sample_table(self._bound_rig("animate_instances_blend", binding).sample_rows(samples))
+        check(lib().frt_renderer_animate_instances_blend(self._h, int(binding), n, table))
+
+    def animate_cast_blend(self, entries, normals="recompute"):
+        """animate_cast() with a blend per binding: `entries` is an iterable of (binding, samples). Every rule of animate_cast holds: one launch, the
+        instance half then the mesh half, each all or nothing, one refit. Bit for bit what animate_instances_blend for the instance entries
+        followed by animate_blend for the mesh entries leave."""
+        from ._lib import CastBlendEntry
+        from .animation import sample_table
+        rows, table = [], []
+        for b, samples in entries:
+            s = self._bound_rig("animate_cast_blend", b).sample_rows(samples)
+            table.append(CastBlendEntry(int(b), len(rows), len(s), 0))
+            rows += s
+        ns, stable = sample_table(rows)
+        check(lib().frt_renderer_animate_cast_blend(self._h, len(table), (CastBlendEntry * max(len(table), 1))(*table), ns, stable, deform_flags(normals)))
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -795,6 +823,19 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         through animate, on every strip's replica."""
         from .animation import host_cast
         host_cast(self, entries, normals)
+
+    def animate_blend(self, rig, mesh_ids, samples, normals="recompute"):
+        """rig.evaluate_blend(samples) on the host, then set_mesh_poses on every strip's replica ("Blending clips")."""
+        self.set_mesh_poses(mesh_ids, *rig.evaluate_blend(samples), normals=normals)
+
+    def animate_instances_blend(self, rig, instance_ids, nodes, samples, root=None, offsets=None):
+        """rig.evaluate_nodes_blend on the host, then set_instance_transforms on every strip's replica."""
+        self.set_instance_transforms(instance_ids, rig.evaluate_nodes_blend(samples, nodes, root, offsets))
+
+    def animate_cast_blend(self, entries, normals="recompute"):
+        """The host form of Renderer.animate_cast_blend (frt.animation.host_cast_blend) on every strip's replica."""
+        from .animation import host_cast_blend
+        host_cast_blend(self, entries, normals)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

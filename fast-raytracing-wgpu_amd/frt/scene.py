@@ -503,6 +503,19 @@ class SceneBuilder:
         host_cast(self, entries, normals)
         return self
 
+    # Blending clips ("Blending clips"): the three calls above with `samples`, [(clip, t, weight), ...], where they take a clip
+    # and a time: rig.evaluate_blend / rig.evaluate_nodes_blend on the host, then the same host calls.
+    def animate_blend(self, rig, mesh_ids, samples, normals="recompute"):
+        return self.set_mesh_poses(mesh_ids, *rig.evaluate_blend(samples), normals=normals)
+
+    def animate_instances_blend(self, rig, instance_ids, nodes, samples, root=None, offsets=None):
+        return self.set_instance_transforms(instance_ids, rig.evaluate_nodes_blend(samples, nodes, root, offsets))
+
+    def animate_cast_blend(self, entries, normals="recompute"):
+        from .animation import host_cast_blend
+        host_cast_blend(self, entries, normals)
+        return self
+
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
     # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
     # base in target order and applies the result as set_mesh_vertices does. Host copy only.

@@ -667,6 +667,39 @@ int frt_renderer_read_rig_instances(frt_renderer* r, uint32_t binding, float* ma
 typedef struct frt_cast_entry { uint32_t binding, clip; float time; uint32_t reserved; } frt_cast_entry;      /* reserved must be 0 */
 #define FRT_MAX_CAST_ENTRIES 4096u
 int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry* entries, uint32_t flags);
+/* Blending clips ("Blending clips"): a cross-fade between clips, for every animate call above. A SAMPLE is (clip, time, weight);
+ * a BLEND is an ordered list of 1 .. FRT_MAX_BLEND_SAMPLES samples of one rig. Matrices do not blend and a palette has the hierarchy composed, so the
+ * blend happens on a node's local translation, rotation and scale, in front of the local matrix; everything behind it is the contract of
+ * frt_rig_evaluate, unchanged. The contract (csrc/frt_animation.hpp: rig_local_matrix_blend, rig_morph_weight_blend; f32, no contraction, no fma), for a
+ * node that is not a matrix node, with the samples taken in the order given:
+ *   A sample whose weight is 0 is skipped entirely. The first sample with a positive weight w gives the pose (T, R, S) as that clip sampled at that
+ *   time gives it, without arithmetic, and W = w. Every later sample with a positive weight w and sampled pose (T_s, R_s, S_s):
+ *   W = W + w; a = w / W; T = T (1 - a) + T_s a and S = S (1 - a) + S_s a per component; R = slerp(R, R_s, a), the slerp of the sampling rule above
+ *   (the short way round, the mix above 0.9995). The local matrix is T R S of the result. A matrix node keeps its matrix.
+ *   A path the clip of a sample has no channel for contributes the node's rest value, so two clips that animate different limbs each arrive at their
+ *   share of the weight; there are no per-node masks.
+ *   Morph weight c: the same running mix, r = r (1 - a) + r_s a, over the weight every sample gives by the rule above (a clip without a weights
+ *   channel: the default weight).
+ * So the weights need not sum to one, a blend of one sample (of any positive weight) is frt_rig_evaluate(clip, time) bit for bit, and so is a blend
+ * whose other samples have weight 0, wherever they stand in the list.
+ * frt_rig_evaluate_blend / frt_rig_evaluate_nodes_blend are the specification, on the host: outputs and the node arguments as frt_rig_evaluate /
+ * frt_rig_evaluate_nodes take them. FRT_ERR_INVALID_ARG, nothing written: n == 0 or above FRT_MAX_BLEND_SAMPLES, samples == NULL, reserved != 0, a
+ * clip out of range, a time or a weight that is not finite, a negative weight, no positive weight; and what the single-clip forms refuse.
+ * frt_renderer_animate_blend / _animate_instances_blend / _animate_cast_blend are frt_renderer_animate / _animate_instances / _animate_cast with a
+ * blend where those take (clip, time): the same kernels (the single-clip calls run them with a list of one sample of weight 1), the same launches,
+ * rules and rejects, bit for bit the host forms; read_rig_pose / read_rig_instances return what they wrote. The samples of a one-binding call are a
+ * kernel argument; those of a cast lie in samples [nsamples], entry k naming samples [first_sample .. first_sample + num_samples), and are uploaded
+ * with the entry table in the one staged copy. Refused on the host with nothing enqueued: what the single-clip call refuses, what
+ * frt_rig_evaluate_blend refuses of a list, and for a cast nsamples == 0, an entry whose range is empty, longer than FRT_MAX_BLEND_SAMPLES or not
+ * inside nsamples. Ranges may overlap or leave samples unused. */
+#define FRT_MAX_BLEND_SAMPLES 8u
+typedef struct frt_clip_sample { uint32_t clip; float time, weight; uint32_t reserved; } frt_clip_sample;      /* reserved must be 0 */
+int frt_rig_evaluate_blend(const frt_rig* rig, uint32_t n, const frt_clip_sample* samples, float* joint_mats_out, float* morph_weights_out);
+int frt_rig_evaluate_nodes_blend(const frt_rig* rig, uint32_t n, const frt_clip_sample* samples, uint32_t nnodes, const uint32_t* nodes, const float* root16, const float* offsets16n, float* mats_out16n);
+int frt_renderer_animate_blend(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_sample* samples, uint32_t flags);
+int frt_renderer_animate_instances_blend(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_sample* samples);
+typedef struct frt_cast_blend_entry { uint32_t binding, first_sample, num_samples, reserved; } frt_cast_blend_entry;      /* reserved must be 0 */
+int frt_renderer_animate_cast_blend(frt_renderer* r, uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
