@@ -1,7 +1,8 @@
 // frt_animation.cpp — the host form of an animated rig (include/frt.h: frt_rig_*; DESIGN.md §11, "Animation"): frt_rig_create checks a description and
 // packs it into the one block frt_animation.hpp reads; frt_rig_evaluate is the specification of frt_renderer_animate's kernel, the same FRT_HD functions
 // run node by node in the block's order (parents first); frt_rig_evaluate_blend and frt_rig_evaluate_nodes_blend ("Blending clips") are the same for
-// a list of samples. Host code only; nothing here touches a device.
+// a list of samples, frt_rig_evaluate_layers and frt_rig_evaluate_nodes_layers ("Layering clips") for a list of layers under masks. Host code only;
+// nothing here touches a device.
 #include "frt_animation.hpp"
 #include "frt_loader.hpp"      // frt_model: frt_rig_from_model and the frt_model_* accessors of the rig
 #include "../../include/frt.h"
@@ -93,6 +94,65 @@ std::string frt::check_cast_blend_entries(uint32_t n, const frt_cast_blend_entry
     if (!bad.empty()) return bad;
     for (uint32_t k = 0; k < n; ++k) {
         const std::string s = check_blend_samples(e[k].num_samples, samples + e[k].first_sample, bindings[e[k].binding].nclips);
+        if (!s.empty()) return "entry " + std::to_string(k) + ": " + s;
+    }
+    return "";
+}
+
+// "Layering clips": the checks of a layer list, of masks where they enter and of a layered cast (frt_animation.hpp).
+std::string frt::check_clip_layers(uint32_t n, const frt_clip_layer* l, uint32_t nclips, uint32_t nmasks) {
+    if (n == 0 || n > FRT_MAX_LAYERS) return std::to_string(n) + " layers (1 .. FRT_MAX_LAYERS)";
+    if (!l) return "null layers";
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string at = "layer " + std::to_string(i) + ": ";
+        if (l[i].mode > (uint32_t)FRT_LAYER_ADDITIVE) return at + "unknown mode " + std::to_string(l[i].mode);
+        if (l[i].flags & ~FRT_LAYER_KEEP_MORPH) return at + "unknown flag bits";
+        if (l[i].clip >= nclips) return at + "clip " + std::to_string(l[i].clip) + " out of range (" + std::to_string(nclips) + " clips)";
+        if (l[i].mode == (uint32_t)FRT_LAYER_ADDITIVE) {
+            if (l[i].ref_clip >= nclips) return at + "reference clip " + std::to_string(l[i].ref_clip) + " out of range (" + std::to_string(nclips) + " clips)";
+        } else if (l[i].ref_clip != 0 || !(l[i].ref_time == 0.0f)) return at + "ref_clip and ref_time must be 0 unless the layer is additive";
+        if (!std::isfinite(l[i].time)) return at + "time is not finite";
+        if (!std::isfinite(l[i].ref_time)) return at + "reference time is not finite";
+        if (!std::isfinite(l[i].weight)) return at + "weight is not finite";
+        if (l[i].weight < 0.0f) return at + "a negative weight";
+        if (l[i].mode == (uint32_t)FRT_LAYER_OVERRIDE && l[i].weight > 1.0f) return at + "an override weight above 1";
+        if (l[i].mask != FRT_LAYER_NO_MASK && l[i].mask >= nmasks) return at + "mask " + std::to_string(l[i].mask) + " out of range (" + std::to_string(nmasks) + " masks)";
+    }
+    if (l[0].mode != (uint32_t)FRT_LAYER_BLEND || l[0].mask != FRT_LAYER_NO_MASK || !(l[0].weight > 0.0f) || l[0].flags)
+        return "layer 0 is the base: a blend layer without a mask, with a positive weight and no flags";
+    return "";
+}
+std::string frt::check_rig_masks(uint32_t nmasks, const float* masks, uint32_t nnodes) {
+    if (nmasks > FRT_MAX_RIG_MASKS) return std::to_string(nmasks) + " masks, more than FRT_MAX_RIG_MASKS";
+    if (nmasks && !masks) return "null masks";
+    for (size_t i = 0; i < (size_t)nmasks * nnodes; ++i)
+        if (!(masks[i] >= 0.0f && masks[i] <= 1.0f)) return "mask " + std::to_string(i / nnodes) + ", node " + std::to_string(i % nnodes) + ": a mask value is a finite number in [0, 1]";
+    return "";
+}
+std::string frt::check_cast_layers_entries(uint32_t n, const frt_cast_layers_entry* e, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags,
+                                           uint32_t allowed_flags, const CastBinding* bindings, const uint32_t* masks_of, size_t nbindings, size_t nmeshes,
+                                           size_t ninstances, std::vector<frt_cast_entry>& plain) {
+    plain.clear();
+    if (n == 0 || n > FRT_MAX_CAST_ENTRIES) return std::to_string(n) + " entries (1 .. FRT_MAX_CAST_ENTRIES)";
+    if (!e) return "null entries";
+    if (nlayers == 0) return "0 layers";
+    if (!layers) return "null layers";
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string at = "entry " + std::to_string(k) + ": ";
+        if (e[k].reserved != 0) return at + "reserved must be 0";
+        if (e[k].num_layers == 0 || e[k].num_layers > FRT_MAX_LAYERS) return at + std::to_string(e[k].num_layers) + " layers (1 .. FRT_MAX_LAYERS)";
+        if (e[k].first_layer >= nlayers || e[k].num_layers > nlayers - e[k].first_layer)
+            return at + "layers " + std::to_string(e[k].first_layer) + " + " + std::to_string(e[k].num_layers) + " overrun the " + std::to_string(nlayers) + " given";
+    }
+    plain.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {      // (a clip or a time check_cast_entries would refuse is refused there, named as the entry's)
+        const frt_clip_layer& base = layers[e[k].first_layer];
+        plain[k] = frt_cast_entry{e[k].binding, base.clip, base.time, 0u};
+    }
+    const std::string bad = check_cast_entries(n, plain.data(), flags, allowed_flags, bindings, nbindings, nmeshes, ninstances);
+    if (!bad.empty()) return bad;
+    for (uint32_t k = 0; k < n; ++k) {
+        const std::string s = check_clip_layers(e[k].num_layers, layers + e[k].first_layer, bindings[e[k].binding].nclips, masks_of ? masks_of[e[k].binding] : 0u);
         if (!s.empty()) return "entry " + std::to_string(k) + ": " + s;
     }
     return "";
@@ -457,6 +517,71 @@ int frt_rig_evaluate_nodes_blend(const frt_rig* rig, uint32_t n, const frt_clip_
     if (root && !all_finite(root, 16)) return rig_fail("rig_evaluate_nodes_blend: a root entry is not finite");
     if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail("rig_evaluate_nodes_blend: an offsets entry is not finite");
     const std::vector<m4> global = blend_globals(v, h, n, samples);
+    for (uint32_t k = 0; k < nnodes; ++k) {
+        const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
+        memcpy(mats_out + (size_t)16 * k, &M, 64);
+    }
+    return FRT_OK;
+}
+
+} // extern "C"
+
+// "Layering clips": the specification of the kernels run with a list of layers. What both calls check of the list and the masks; the masks in the
+// block's node order (`stored`; the caller gives them in its own); the globals of a checked list, node by node, parents first.
+static std::string check_layers_call(const frt_rig* rig, const RigHeader& h, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, std::vector<float>& stored) {
+    if (nmasks > FRT_MAX_RIG_MASKS) return std::to_string(nmasks) + " masks, more than FRT_MAX_RIG_MASKS";
+    std::string bad = check_clip_layers(n, layers, h.nclips, nmasks);
+    if (bad.empty()) bad = check_rig_masks(nmasks, masks, h.nnodes);
+    if (!bad.empty()) return bad;
+    stored.resize((size_t)nmasks * h.nnodes);
+    for (uint32_t m = 0; m < nmasks; ++m)
+        for (uint32_t i = 0; i < h.nnodes; ++i) stored[(size_t)m * h.nnodes + rig->place[i]] = masks[(size_t)m * h.nnodes + i];
+    return "";
+}
+static std::vector<m4> layers_globals(const RigView& v, const RigHeader& h, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* stored) {
+    std::vector<m4> global(h.nnodes);
+    for (uint32_t i = 0; i < h.nnodes; ++i) {
+        const m4 local = rig_local_matrix_layers(v, n, layers, nmasks, stored, i);
+        const uint32_t p = v.w[h.parent + i];
+        global[i] = p == kRigNone ? local : mul(global[p], local);
+    }
+    return global;
+}
+
+extern "C" {
+
+int frt_rig_evaluate_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, float* joint_mats_out, float* morph_weights_out) {
+    if (!rig) return rig_fail("rig_evaluate_layers: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    std::vector<float> stored;
+    const std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
+    if (!bad.empty()) return rig_fail("rig_evaluate_layers: " + bad);
+    if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail("rig_evaluate_layers: null output");
+    if (h.njoints) {
+        const std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
+        for (uint32_t j = 0; j < h.njoints; ++j) {
+            const m4 m = mul(global[v.w[h.joint_node + j]], load_m4(v.f(h.inv_bind) + (size_t)16 * j));
+            memcpy(joint_mats_out + (size_t)16 * j, &m, 64);
+        }
+    }
+    for (uint32_t c = 0; c < h.ntargets; ++c) morph_weights_out[c] = rig_morph_weight_layers(v, n, layers, c);
+    return FRT_OK;
+}
+
+int frt_rig_evaluate_nodes_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
+    if (!rig) return rig_fail("rig_evaluate_nodes_layers: null");
+    const RigView v = rig->view();
+    const RigHeader h = v.h();
+    std::vector<float> stored;
+    const std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
+    if (!bad.empty()) return rig_fail("rig_evaluate_nodes_layers: " + bad);
+    if (nnodes == 0 || !nodes || !mats_out) return rig_fail("rig_evaluate_nodes_layers: nnodes is 0, or null nodes or output");
+    for (uint32_t k = 0; k < nnodes; ++k)
+        if (nodes[k] >= h.nnodes) return rig_fail("rig_evaluate_nodes_layers: node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
+    if (root && !all_finite(root, 16)) return rig_fail("rig_evaluate_nodes_layers: a root entry is not finite");
+    if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail("rig_evaluate_nodes_layers: an offsets entry is not finite");
+    const std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
     for (uint32_t k = 0; k < nnodes; ++k) {
         const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
         memcpy(mats_out + (size_t)16 * k, &M, 64);

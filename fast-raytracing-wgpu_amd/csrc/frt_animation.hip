@@ -1,7 +1,8 @@
 // frt_animation.hip — the device form of an animated rig (include/frt.h: frt_renderer_bind_rig, _animate, _read_rig_pose, _unbind_rig; DESIGN.md §11,
 // "Animation"; _bind_rig_instances, _animate_instances: "Node animation"; _animate_cast: "Animating a cast"). Built with the library's contract flags. No arithmetic is written here: the kernel calls the FRT_HD functions of frt_animation.hpp that
 // frt_rig_evaluate calls on the host, so the palette and the weights have the host's bits. The _blend forms of the three animate calls ("Blending
-// clips") run the same kernels with their list of samples; frt_rig_evaluate_blend is their host form.
+// clips") run the same kernels with their list of samples; frt_rig_evaluate_blend is their host form. The _layers forms ("Layering clips") run the
+// same kernel texts instantiated for a list of layers; frt_rig_evaluate_layers is their host form.
 //
 // The kernel is ONE workgroup of four waves per rig. (1) Every lane builds the local matrix of a node (sampling the clip's channels of that node),
 // strided by the workgroup's size, into LDS. (2) The globals are propagated level by level: a node's parent lies on the level above, which is complete
@@ -29,12 +30,7 @@ __device__ inline void rig_lds_store(float4* g, uint32_t n, const m4& m) {
     for (int c = 0; c < 4; ++c) g[(uint32_t)c * kRigLds + n] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
 }
 
-// What the kernels evaluate ("Blending clips"): a list of 1 .. FRT_MAX_BLEND_SAMPLES samples. The one-rig kernels take it by value as a kernel argument
-// and a cast's entries point at theirs, so its words are the same for every lane (scalar loads) and every branch on them is taken by the whole
-// workgroup. The single-clip calls pass a list of one sample of weight 1, which the contract makes the single clip's bits.
-struct RigSampleList { uint32_t n, pad0, pad1, pad2; frt_clip_sample s[FRT_MAX_BLEND_SAMPLES]; };
-static_assert(sizeof(frt_clip_sample) == 16 && sizeof(RigSampleList) == 16 + 16 * FRT_MAX_BLEND_SAMPLES, "RigSampleList layout");
-// What the host calls have refused: uniform, asked in front of the first barrier.
+// What the host calls have refused of a sample list: uniform, asked in front of the first barrier.
 __device__ inline bool rig_samples_ok(const RigHeader& h, const frt_clip_sample* s, uint32_t ns) {
     if (ns == 0u || ns > FRT_MAX_BLEND_SAMPLES) return false;
     bool positive = false;
@@ -44,14 +40,62 @@ __device__ inline bool rig_samples_ok(const RigHeader& h, const frt_clip_sample*
     }
     return positive;
 }
+// ... and of a layer list ("Layering clips"): check_clip_layers restated on the layer words, which are uniform, a mask index the binding's masks do not
+// have included (rig_local_matrix_layers reads no mask at or beyond nmasks, and with this guard no kernel runs with a layer that names one).
+__device__ inline bool rig_finite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) != 0x7f800000u; }
+__device__ inline bool rig_layers_ok(const RigHeader& h, const frt_clip_layer* l, uint32_t nl, uint32_t nmasks, const float* masks) {
+    if (nl == 0u || nl > FRT_MAX_LAYERS || nmasks > FRT_MAX_RIG_MASKS || (nmasks && !masks)) return false;
+    for (uint32_t i = 0; i < nl; ++i) {
+        if (l[i].mode > (uint32_t)FRT_LAYER_ADDITIVE || (l[i].flags & ~FRT_LAYER_KEEP_MORPH) || l[i].clip >= h.nclips) return false;
+        if (l[i].mode == (uint32_t)FRT_LAYER_ADDITIVE) { if (l[i].ref_clip >= h.nclips) return false; }
+        else if (l[i].ref_clip != 0u || !(l[i].ref_time == 0.0f)) return false;
+        if (!rig_finite(l[i].time) || !rig_finite(l[i].ref_time) || !rig_finite(l[i].weight) || l[i].weight < 0.0f) return false;
+        if (l[i].mode == (uint32_t)FRT_LAYER_OVERRIDE && l[i].weight > 1.0f) return false;
+        if (l[i].mask != FRT_LAYER_NO_MASK && l[i].mask >= nmasks) return false;
+    }
+    return l[0].mode == (uint32_t)FRT_LAYER_BLEND && l[0].mask == FRT_LAYER_NO_MASK && l[0].weight > 0.0f && l[0].flags == 0u;
+}
 
-// Phases (1) and (2) of both kernels: the global matrix of every node < N is in `g` behind the last barrier. Called by the whole workgroup with uniform
-// arguments (the samples and the level bounds are the same words for every lane). Phase (1) is one lane, one node: every sample's clip sampled into
-// translation, rotation and scale, blended in registers as one running pose (rig_local_matrix_blend), the local matrix stored.
-__device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, const frt_clip_sample* s, uint32_t ns, float4* g, uint32_t N) {
+// The POSE SOURCE of a kernel: what phase (1) folds into a node's local matrix and what a morph weight is taken from. Either a list of samples
+// ("Blending clips"; the single-clip calls pass a list of one sample of weight 1, which the contract makes the single clip's bits) or a list of
+// layers with the binding's masks ("Layering clips"). The kernels below are templates over it, so the single-clip and blend calls run instantiations
+// that hold no layer code at all, and the layered calls instantiations of their own. A source's words are the same for every lane (a kernel
+// argument, or read through the block's index: scalar loads), so every branch on a count, a mode or a flag is taken by the whole workgroup. The one
+// divergent branch of the layers, e > 0 under a mask, lies inside phase (1), where there is no barrier; the mask read is masks[mask * N + n],
+// consecutive lanes on consecutive nodes.
+struct RigSamples {
+    const frt_clip_sample* s; uint32_t n;
+    __device__ bool ok(const RigHeader& h) const { return rig_samples_ok(h, s, n); }
+    __device__ m4 local(RigView v, uint32_t node) const { return rig_local_matrix_blend(v, n, s, node); }
+    __device__ float morph(RigView v, uint32_t c) const { return rig_morph_weight_blend(v, n, s, c); }
+};
+struct RigLayers {
+    const frt_clip_layer* l; uint32_t n, nmasks; const float* masks;
+    __device__ bool ok(const RigHeader& h) const { return rig_layers_ok(h, l, n, nmasks, masks); }
+    __device__ m4 local(RigView v, uint32_t node) const { return rig_local_matrix_layers(v, n, l, nmasks, masks, node); }
+    __device__ float morph(RigView v, uint32_t c) const { return rig_morph_weight_layers(v, n, l, c); }
+};
+// The lists the one-rig kernels take by value as a kernel argument; a cast's entries point at theirs.
+struct RigSampleList {
+    uint32_t n, pad0, pad1, pad2; frt_clip_sample s[FRT_MAX_BLEND_SAMPLES];
+    __device__ RigSamples source() const { return RigSamples{s, n}; }
+};
+static_assert(sizeof(frt_clip_sample) == 16 && sizeof(RigSampleList) == 16 + 16 * FRT_MAX_BLEND_SAMPLES, "RigSampleList layout");
+struct RigLayerList {
+    uint32_t n, nmasks; const float* masks; frt_clip_layer l[FRT_MAX_LAYERS];      // masks: the binding's, [nmasks][nnodes] in the block's node order
+    __device__ RigLayers source() const { return RigLayers{l, n, nmasks, masks}; }
+};
+static_assert(sizeof(frt_clip_layer) == 32 && sizeof(RigLayerList) == 16 + 32 * FRT_MAX_LAYERS, "RigLayerList layout");
+
+// Phases (1) and (2) of every kernel: the global matrix of every node < N is in `g` behind the last barrier. Called by the whole workgroup with uniform
+// arguments (the source and the level bounds are the same words for every lane). Phase (1) is one lane, one node: every sample's or layer's clip
+// sampled into translation, rotation and scale, folded in registers as one running pose (rig_local_matrix_blend, rig_local_matrix_layers), the local
+// matrix stored.
+template <class Source>
+__device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, const Source& src, float4* g, uint32_t N) {
     const uint32_t* words = v.w;
     const uint32_t tid = threadIdx.x;
-    for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, rig_local_matrix_blend(v, ns, s, n));
+    for (uint32_t n = tid; n < N; n += (uint32_t)kRigBlock) rig_lds_store(g, n, src.local(v, n));
     __syncthreads();
     for (uint32_t level = 1u; level < h.nlevels; ++level) {
         const uint32_t begin = words[h.level_begin + level], end = words[h.level_begin + level + 1u];
@@ -63,15 +107,17 @@ __device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, const f
     }
 }
 
-__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, const RigSampleList list, float4* palette, float* weights) {
+template <class List>
+__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, const List list, float4* palette, float* weights) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig refuses a larger rig)
-    if (!rig_samples_ok(h, list.s, list.n)) return;                  // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
+    const auto src = list.source();
+    if (!src.ok(h)) return;                                          // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
     if (h.njoints) {
-        rig_globals_to_lds(v, h, list.s, list.n, g, N);
+        rig_globals_to_lds(v, h, src, g, N);
         for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
             const uint32_t n = words[h.joint_node + j];
             if (n >= N) continue;
@@ -80,19 +126,21 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
             for (int c = 0; c < 4; ++c) palette[4u * j + (uint32_t)c] = make_float4(m.c[c].x, m.c[c].y, m.c[c].z, m.c[c].w);
         }
     }
-    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = rig_morph_weight_blend(v, list.n, list.s, c);
+    for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) weights[c] = src.morph(v, c);
 }
 
 // frt_renderer_animate_instances ("Node animation"): phases (1) and (2) as above, whether or not the rig has joints; (3) one lane per bound instance,
 // strided by the workgroup's size, loads its node's global from LDS, applies root and offset through rig_node_matrix (the host's text) and stores four
 // float4 into the binding's matrices. `nodes` [n]: stored node indices; `root` [16] and `offsets` [16 n]: null when the binding has none.
-__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, const RigSampleList list, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
+template <class List>
+__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, const List list, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig_instances refuses a larger rig)
-    if (!rig_samples_ok(h, list.s, list.n)) return;                  // (animate_instances refuses it; uniform, in front of the first barrier)
-    rig_globals_to_lds(v, h, list.s, list.n, g, N);
+    const auto src = list.source();
+    if (!src.ok(h)) return;                                          // (animate_instances refuses it; uniform, in front of the first barrier)
+    rig_globals_to_lds(v, h, src, g, N);
     for (uint32_t k = threadIdx.x; k < n; k += (uint32_t)kRigBlock) {
         const uint32_t node = nodes[k];
         if (node >= N) continue;                                     // (bind_rig_instances has checked it)
@@ -120,8 +168,28 @@ struct CastEntry {
     const uint32_t* nodes; const float* root; const float* offsets;      // instances: as rig_nodes_kernel takes them
     const uint32_t* ids; uint32_t* all_ids;                              // instances: the binding's ids [n] and their slice of the call's ids
     uint64_t pad1;
+    typedef frt_clip_sample Item;
+    void set_list(const Item* items, uint32_t count, const RigBinding&) { samples = items; nsamples = count; }
+    __device__ RigSamples source() const { return RigSamples{samples, nsamples}; }
 };
 static_assert(sizeof(CastEntry) == 112 && sizeof(CastEntry) % 16 == 0, "CastEntry layout");
+// The entry of a layered cast ("Layering clips"): CastEntry with the entry's layers in place of its samples, and its own binding's masks.
+struct CastLayersEntry {
+    const uint32_t* words;
+    const frt_clip_layer* layers;      // the entry's layers [nlayers], behind the table in the same device block
+    uint32_t nlayers;
+    uint32_t kind, n;
+    uint32_t nmasks;                   // the binding's masks [nmasks][nnodes], in the block's node order
+    float4* own; float4* all;
+    float* own_w; float* all_w;
+    const uint32_t* nodes; const float* root; const float* offsets;
+    const uint32_t* ids; uint32_t* all_ids;
+    const float* masks;
+    typedef frt_clip_layer Item;
+    void set_list(const Item* items, uint32_t count, const RigBinding& b) { layers = items; nlayers = count; nmasks = b.nmasks; masks = b.nmasks ? b.masks.as<const float>() : nullptr; }
+    __device__ RigLayers source() const { return RigLayers{layers, nlayers, nmasks, masks}; }
+};
+static_assert(sizeof(CastLayersEntry) == 112 && sizeof(CastLayersEntry) % 16 == 0 && alignof(CastLayersEntry) <= 16, "CastLayersEntry layout");
 
 __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, const m4& m) {
 #pragma unroll
@@ -131,16 +199,18 @@ __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, con
         all[4u * k + (uint32_t)c] = q;
     }
 }
-__global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* table) {
+template <class Entry>
+__global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const Entry* table) {
     __shared__ float4 g[4u * kRigLds];
-    const CastEntry e = table[blockIdx.x];
+    const Entry e = table[blockIdx.x];
     RigView v; v.w = e.words;
     const RigHeader h = v.h();
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (the bind calls refuse a larger rig)
-    if (!rig_samples_ok(h, e.samples, e.nsamples)) return;           // (animate_cast refuses it; uniform, in front of the first barrier)
+    const auto src = e.source();
+    if (!src.ok(h)) return;                                          // (animate_cast refuses it; uniform, in front of the first barrier)
     const bool instances = e.kind == (uint32_t)kRigInstances;
-    if (instances || h.njoints) rig_globals_to_lds(v, h, e.samples, e.nsamples, g, N);
+    if (instances || h.njoints) rig_globals_to_lds(v, h, src, g, N);
     if (instances) {
         for (uint32_t k = tid; k < e.n; k += (uint32_t)kRigBlock) {
             e.all_ids[k] = e.ids[k];
@@ -164,7 +234,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const CastEntry* ta
         rig_store_twice(e.own, e.all, j, mul(rig_lds_load(g, n), load_m4(v.f(h.inv_bind) + (size_t)16u * j)));
     }
     for (uint32_t c = tid; c < h.ntargets; c += (uint32_t)kRigBlock) {
-        const float w = rig_morph_weight_blend(v, e.nsamples, e.samples, c);
+        const float w = src.morph(v, c);
         e.own_w[c] = w;
         e.all_w[c] = w;
     }
@@ -190,9 +260,18 @@ static RigSampleList sample_list(uint32_t n, const frt_clip_sample* s) {
     return l;
 }
 static RigSampleList one_clip(uint32_t clip, float time) { const frt_clip_sample s{clip, time, 1.0f, 0u}; return sample_list(1u, &s); }
+// ... and the n layers a call has checked against the binding's mask count, with the binding's masks ("Layering clips").
+static RigLayerList layer_list(uint32_t n, const frt_clip_layer* l, const RigBinding& b) {
+    RigLayerList list;
+    memset(&list, 0, sizeof(list));
+    list.n = n; list.nmasks = b.nmasks; list.masks = b.nmasks ? b.masks.as<const float>() : nullptr;
+    memcpy(list.l, l, (size_t)n * sizeof(frt_clip_layer));
+    return list;
+}
 
-// frt_renderer_animate_instances and _animate_instances_blend behind their checks: the kernel, then the device transform.
-static int move_bound_instances(frt_renderer* r, const std::string& call, RigBinding* b, const RigSampleList& list) {
+// frt_renderer_animate_instances, _animate_instances_blend and _animate_instances_layers behind their checks: the kernel, then the device transform.
+template <class List>
+static int move_bound_instances(frt_renderer* r, const std::string& call, RigBinding* b, const List& list) {
     const uint32_t n = (uint32_t)b->instance_ids.size();
     {
         // The kernel writes the binding's matrices only, which nothing but the device transform of an earlier animate_instances reads: on this stream, in front of it.
@@ -208,21 +287,23 @@ static int move_bound_instances(frt_renderer* r, const std::string& call, RigBin
         const size_t node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
         const float* root = b->has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
         const float* offsets = b->has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b->has_root ? 64u : 0u)) : nullptr;
-        hipLaunchKernelGGL(rig_nodes_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
+        hipLaunchKernelGGL(rig_nodes_kernel<List>, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
     }
     return frt_renderer_set_instance_transforms_ex(r, n, b->ids.as<const uint32_t>(), b->mats.as<const float>(), FRT_TRANSFORM_DEVICE);
 }
-// frt_renderer_animate and _animate_blend behind their checks of the samples: the meshes as animate checks them, the kernel, then the pose batch.
-static int pose_bound_meshes(frt_renderer* r, const std::string& call, RigBinding* b, const RigSampleList& list, uint32_t flags) {
+// frt_renderer_animate, _animate_blend and _animate_layers behind their checks of the list: the meshes as animate checks them, the kernel, then the
+// pose batch.
+template <class List>
+static int pose_bound_meshes(frt_renderer* r, const std::string& call, RigBinding* b, const List& list, uint32_t flags) {
     const uint32_t n = (uint32_t)b->mesh_ids.size();
     const std::string bad = check_posed_meshes(r, n, b->mesh_ids.data(), b->njoints != 0, b->palette.p, b->njoints, b->ntargets != 0, b->weights.p, b->ntargets, false);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, call + ": " + bad);
     {
         // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
         FRT_DEVICE(r);
-        hipLaunchKernelGGL(rig_evaluate_kernel, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, b->palette.as<float4>(), b->weights.as<float>());
+        hipLaunchKernelGGL(rig_evaluate_kernel<List>, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, b->palette.as<float4>(), b->weights.as<float>());
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
     }
@@ -241,13 +322,16 @@ static std::vector<CastBinding> cast_bindings(const frt_renderer* r) {
     }
     return info;
 }
-// frt_renderer_animate_cast and _animate_cast_blend behind the checks of their entries (`entries`: the bindings, as cast_layout takes them; `ranges`:
-// every entry's samples among samples [nsamples]): every mesh entry's meshes as animate checks them, the layout of the call's buffer, ONE staged copy —
-// the entry table, the samples and the ids of the instance bindings remove_instances has renumbered — ONE launch, then frt_scene_edit.hip's apply_cast.
+// frt_renderer_animate_cast, _animate_cast_blend and _animate_cast_layers behind the checks of their entries (`entries`: the bindings, as cast_layout
+// takes them; `ranges`: every entry's samples among samples [nsamples] — for the layered cast, with Entry = CastLayersEntry, its layers among the
+// layers): every mesh entry's meshes as animate checks them, the layout of the call's buffer, ONE staged copy — the entry table, the samples and the
+// ids of the instance bindings remove_instances has renumbered — ONE launch, then frt_scene_edit.hip's apply_cast.
 // Past the first call of a steady cast nothing here allocates, waits for the stream or copies synchronously: the pinned block's event has long passed
 // when the next call comes.
-static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, const frt_cast_entry* entries, const frt_cast_blend_entry* ranges,
-                    const std::vector<CastBinding>& info, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags) {
+struct CastRange { uint32_t first, count; };
+template <class Entry>
+static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, const frt_cast_entry* entries, const CastRange* ranges,
+                    const std::vector<CastBinding>& info, uint32_t nsamples, const typename Entry::Item* samples, uint32_t flags) {
     std::string bad;
     for (uint32_t k = 0; k < n && bad.empty(); ++k) {
         const RigBinding& b = r->rigs[entries[k].binding];
@@ -264,19 +348,19 @@ static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, c
         FRT_DEVICE(r);
         if (const int rc = r->cast.buf.ensure(r, l.bytes)) return rc;
         uint8_t* all = r->cast.buf.as<uint8_t>();
-        const size_t table_bytes = (size_t)n * sizeof(CastEntry), sample_bytes = (size_t)nsamples * sizeof(frt_clip_sample);      // (both multiples of 16)
+        const size_t table_bytes = (size_t)n * sizeof(Entry), sample_bytes = (size_t)nsamples * sizeof(typename Entry::Item);      // (both multiples of 16)
         size_t stale_bytes = 0;
         for (uint32_t k = 0; k < n; ++k) { const RigBinding& b = r->rigs[entries[k].binding]; if (b.kind == kRigInstances && b.ids_stale) stale_bytes += b.instance_ids.size() * 4; }
         if (const int rc = r->rig_up.reserve(table_bytes + sample_bytes + stale_bytes, table_bytes + sample_bytes, r->stream)) return rc;
-        CastEntry* table = reinterpret_cast<CastEntry*>(r->rig_up.h);
+        Entry* table = reinterpret_cast<Entry*>(r->rig_up.h);
         memcpy(r->rig_up.h + table_bytes, samples, sample_bytes);
-        const frt_clip_sample* dev_samples = reinterpret_cast<const frt_clip_sample*>(r->rig_up.d + table_bytes);
+        const typename Entry::Item* dev_samples = reinterpret_cast<const typename Entry::Item*>(r->rig_up.d + table_bytes);
         size_t stale_at = table_bytes + sample_bytes;
         for (uint32_t k = 0; k < n; ++k) {
             RigBinding& b = r->rigs[entries[k].binding];
-            CastEntry e;
+            Entry e;
             memset(&e, 0, sizeof(e));
-            e.words = b.rig.as<const uint32_t>(); e.samples = dev_samples + ranges[k].first_sample; e.nsamples = ranges[k].num_samples; e.kind = b.kind;
+            e.words = b.rig.as<const uint32_t>(); e.set_list(dev_samples + ranges[k].first, ranges[k].count, b); e.kind = b.kind;
             if (b.kind == kRigInstances) {
                 const uint32_t ni = (uint32_t)b.instance_ids.size();
                 if (b.ids_stale) {      // (remove_instances has renumbered the instances) in front of the launch, as animate_instances uploads them
@@ -302,7 +386,7 @@ static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, c
         }
         HIP_TRY(hipMemcpyAsync(r->rig_up.d, r->rig_up.h, table_bytes + sample_bytes, hipMemcpyHostToDevice, r->stream));
         if (const int rc = r->rig_up.mark(r->stream)) return rc;
-        hipLaunchKernelGGL(rig_cast_kernel, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const CastEntry*>(r->rig_up.d));
+        hipLaunchKernelGGL(rig_cast_kernel<Entry>, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const Entry*>(r->rig_up.d));
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call_name + ": " + hipGetErrorString(e)); }
         call.ninst = l.ninst; call.ids = reinterpret_cast<const uint32_t*>(all + l.ids_off); call.mats = reinterpret_cast<const float*>(all + l.mats_off);
@@ -337,6 +421,7 @@ int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* m
     }
     if (rc) { b.rig.release(r); b.palette.release(r); b.weights.release(r); return rc; }
     b.njoints = h.njoints; b.ntargets = h.ntargets; b.nclips = h.nclips; b.mesh_ids.assign(mesh_ids, mesh_ids + n); b.live = true;
+    b.nnodes = h.nnodes; b.place = rig->place;
     *binding_out = keep_binding(r, b);
     return FRT_OK;
 }
@@ -384,6 +469,7 @@ int frt_renderer_bind_rig_instances(frt_renderer* r, const frt_rig* rig, uint32_
     }
     if (rc) { b.release(r); return rc; }
     b.kind = kRigInstances; b.nclips = h.nclips; b.instance_ids.assign(instance_ids, instance_ids + n); b.has_root = root != nullptr; b.has_offsets = offsets != nullptr; b.live = true;
+    b.nnodes = h.nnodes; b.place = rig->place;
     *binding_out = keep_binding(r, b);
     return FRT_OK;
 }
@@ -447,9 +533,9 @@ int frt_renderer_animate_cast(frt_renderer* r, uint32_t n, const frt_cast_entry*
     const std::string bad = check_cast_entries(n, entries, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(), r->rf.inst.size());
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast: " + bad);
     std::vector<frt_clip_sample> samples(n);      // entry k: the list of one sample k
-    std::vector<frt_cast_blend_entry> ranges(n);
-    for (uint32_t k = 0; k < n; ++k) { samples[k] = frt_clip_sample{entries[k].clip, entries[k].time, 1.0f, 0u}; ranges[k] = frt_cast_blend_entry{entries[k].binding, k, 1u, 0u}; }
-    return run_cast(r, "animate_cast", n, entries, ranges.data(), info, n, samples.data(), flags);
+    std::vector<CastRange> ranges(n);
+    for (uint32_t k = 0; k < n; ++k) { samples[k] = frt_clip_sample{entries[k].clip, entries[k].time, 1.0f, 0u}; ranges[k] = CastRange{k, 1u}; }
+    return run_cast<CastEntry>(r, "animate_cast", n, entries, ranges.data(), info, n, samples.data(), flags);
 }
 
 int frt_renderer_animate_cast_blend(frt_renderer* r, uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags) {
@@ -459,7 +545,68 @@ int frt_renderer_animate_cast_blend(frt_renderer* r, uint32_t n, const frt_cast_
     const std::string bad = check_cast_blend_entries(n, entries, nsamples, samples, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), info.size(), r->rf.vert_count.size(),
                                                      r->rf.inst.size(), plain);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast_blend: " + bad);
-    return run_cast(r, "animate_cast_blend", n, plain.data(), entries, info, nsamples, samples, flags);
+    std::vector<CastRange> ranges(n);
+    for (uint32_t k = 0; k < n; ++k) ranges[k] = CastRange{entries[k].first_sample, entries[k].num_samples};
+    return run_cast<CastEntry>(r, "animate_cast_blend", n, plain.data(), ranges.data(), info, nsamples, samples, flags);
+}
+
+// "Layering clips". The masks go into a buffer with room for FRT_MAX_RIG_MASKS of them, allocated at the binding's first call, so that every later set
+// is one staged copy in stream order: an animate call enqueued before it reads the old values, one enqueued behind it the new ones, and the count a
+// later layered call is checked against and launched with is the new one.
+int frt_renderer_set_rig_masks(frt_renderer* r, uint32_t binding, uint32_t nmasks, const float* masks) {
+    if (const int rc = check_entry(r, "set_rig_masks", kEditChecks | kRefit)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "set_rig_masks: unknown rig binding " + std::to_string(binding));
+    const std::string bad = check_rig_masks(nmasks, masks, b->nnodes);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_rig_masks: " + bad);
+    if (nmasks == 0) { b->nmasks = 0; return FRT_OK; }
+    FRT_DEVICE(r);
+    const uint32_t N = b->nnodes;
+    const size_t bytes = (size_t)nmasks * N * 4;
+    if (const int rc = b->masks.ensure(r, (size_t)FRT_MAX_RIG_MASKS * N * 4)) return rc;
+    if (const int rc = r->rig_up.reserve(bytes, 0, r->stream)) return rc;
+    float* up = reinterpret_cast<float*>(r->rig_up.h);
+    for (uint32_t m = 0; m < nmasks; ++m)
+        for (uint32_t i = 0; i < N; ++i) up[(size_t)m * N + b->place[i]] = masks[(size_t)m * N + i];
+    HIP_TRY(hipMemcpyAsync(b->masks.p, r->rig_up.h, bytes, hipMemcpyHostToDevice, r->stream));
+    if (const int rc = r->rig_up.mark(r->stream)) return rc;
+    b->nmasks = nmasks;
+    return FRT_OK;
+}
+
+int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate_layers", kEditChecks | kRefit)) return rc;
+    if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) return fail(FRT_ERR_INVALID_ARG, "animate_layers: unknown flag bits");
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate_layers: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate_layers: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances_layers)");
+    const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_layers: " + bad);
+    return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags);
+}
+
+int frt_renderer_animate_instances_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers) {
+    if (const int rc = check_entry(r, "animate_instances_layers", kEditChecks | kRefit)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: unknown rig binding " + std::to_string(binding));
+    if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate_layers)");
+    const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: " + bad);
+    return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b));
+}
+
+int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast_layers_entry* entries, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags) {
+    if (const int rc = check_entry(r, "animate_cast_layers", kEditChecks | kRefit)) return rc;
+    const std::vector<CastBinding> info = cast_bindings(r);
+    std::vector<uint32_t> masks_of(r->rigs.size());
+    for (size_t i = 0; i < r->rigs.size(); ++i) masks_of[i] = r->rigs[i].nmasks;
+    std::vector<frt_cast_entry> plain;
+    const std::string bad = check_cast_layers_entries(n, entries, nlayers, layers, flags, FRT_DEFORM_RECOMPUTE_NORMALS, info.data(), masks_of.data(), info.size(),
+                                                      r->rf.vert_count.size(), r->rf.inst.size(), plain);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast_layers: " + bad);
+    std::vector<CastRange> ranges(n);
+    for (uint32_t k = 0; k < n; ++k) ranges[k] = CastRange{entries[k].first_layer, entries[k].num_layers};
+    return run_cast<CastLayersEntry>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
 }
 
 int frt_renderer_read_rig_pose(frt_renderer* r, uint32_t binding, float* joint_mats_out, float* morph_weights_out) {

@@ -207,6 +207,67 @@ FRT_HD float rig_morph_weight_blend(RigView v, uint32_t ns, const frt_clip_sampl
     return r;
 }
 
+// Layering clips (include/frt.h: frt_rig_evaluate_layers; DESIGN.md §11, "Layering clips"). The product a * b of two rotations, every product and
+// sum written once, in this order.
+FRT_HD f4 rig_qmul(f4 a, f4 b) {
+    return mk4(((a.w * b.x + a.x * b.w) + a.y * b.z) - a.z * b.y,
+               ((a.w * b.y - a.x * b.z) + a.y * b.w) + a.z * b.x,
+               ((a.w * b.z + a.x * b.y) - a.y * b.x) + a.z * b.w,
+               ((a.w * b.w - a.x * b.x) - a.y * b.y) - a.z * b.z);
+}
+// The layers l [nl] in the order given, ONE running pose (T, R, S) with the accumulated blend weight W. Layer 0 (every caller has checked it: BLEND, no
+// mask, a positive weight) gives the pose as sampled, without arithmetic, and W = weight, so every node has a base. A later layer has
+// e = weight * m, m = 1 or masks[mask * N + n] (`masks`: [nmasks][N] in the block's node order; a mask index that is not below nmasks, FRT_LAYER_NO_MASK
+// among them, reads nothing); !(e > 0) skips it for this node with nothing sampled. BLEND: the blend's rule with e for w. OVERRIDE: a = e, at a >= 1
+// the pose becomes the sampled one without arithmetic, else the same mix and slerp by a; W stays. ADDITIVE: with Y the reference clip sampled,
+// T = T + e (X.t - Y.t), S likewise, R = R * slerp(identity, conj(Y.q) * X.q, e), not renormalised; W stays.
+FRT_HD m4 rig_local_matrix_layers(RigView v, uint32_t nl, const frt_clip_layer* l, uint32_t nmasks, const float* masks, uint32_t n) {
+    const RigHeader h = v.h();
+    if (v.w[h.kind + n]) return load_m4(v.f(h.rest) + (size_t)16u * n);
+    RigTrs r = rig_local_trs(v, l[0].clip, n, l[0].time);
+    float W = l[0].weight;
+#pragma unroll 1
+    for (uint32_t i = 1; i < nl; ++i) {
+        const float m = l[i].mask < nmasks ? masks[(size_t)l[i].mask * h.nnodes + n] : 1.0f;
+        const float e = l[i].weight * m;
+        if (!(e > 0.0f)) continue;
+        const RigTrs x = rig_local_trs(v, l[i].clip, n, l[i].time);
+        if (l[i].mode == (uint32_t)FRT_LAYER_ADDITIVE) {
+            const RigTrs y = rig_local_trs(v, l[i].ref_clip, n, l[i].ref_time);
+            r.t = mk3(r.t.x + e * (x.t.x - y.t.x), r.t.y + e * (x.t.y - y.t.y), r.t.z + e * (x.t.z - y.t.z));
+            r.s = mk3(r.s.x + e * (x.s.x - y.s.x), r.s.y + e * (x.s.y - y.s.y), r.s.z + e * (x.s.z - y.s.z));
+            const f4 d = rig_qmul(mk4(-y.q.x, -y.q.y, -y.q.z, y.q.w), x.q);
+            r.q = rig_qmul(r.q, rig_slerp(mk4(0.0f, 0.0f, 0.0f, 1.0f), d, e));
+            continue;
+        }
+        float a = e;
+        if (l[i].mode == (uint32_t)FRT_LAYER_BLEND) { W = W + e; a = e / W; }
+        else if (a >= 1.0f) { r = x; continue; }
+        r.t = mk3(mixf(r.t.x, x.t.x, a), mixf(r.t.y, x.t.y, a), mixf(r.t.z, x.t.z, a));
+        r.s = mk3(mixf(r.s.x, x.s.x, a), mixf(r.s.y, x.s.y, a), mixf(r.s.z, x.s.z, a));
+        r.q = rig_slerp(r.q, x.q, a);
+    }
+    return rig_trs_matrix(r.t, r.q, r.s);
+}
+// Morph weight c of the layers: rig_morph_weight folded the same way with e = weight (masks do not apply to targets). Layer 0 gives the base; a later
+// layer with FRT_LAYER_KEEP_MORPH or !(e > 0) is skipped; BLEND is the running mix, OVERRIDE the mix by the weight or the layer's value at >= 1,
+// ADDITIVE r + e (x - x_ref).
+FRT_HD float rig_morph_weight_layers(RigView v, uint32_t nl, const frt_clip_layer* l, uint32_t c) {
+    float r = rig_morph_weight(v, l[0].clip, c, l[0].time), W = l[0].weight;
+#pragma unroll 1
+    for (uint32_t i = 1; i < nl; ++i) {
+        const float e = l[i].weight;
+        if ((l[i].flags & FRT_LAYER_KEEP_MORPH) || !(e > 0.0f)) continue;
+        const float x = rig_morph_weight(v, l[i].clip, c, l[i].time);
+        if (l[i].mode == (uint32_t)FRT_LAYER_ADDITIVE) { r = r + e * (x - rig_morph_weight(v, l[i].ref_clip, c, l[i].ref_time)); continue; }
+        float a = e;
+        if (l[i].mode == (uint32_t)FRT_LAYER_BLEND) { W = W + e; a = e / W; }
+        else if (a >= 1.0f) { r = x; continue; }
+        r = mixf(r, x, a);
+    }
+    return r;
+}
+
 // The matrix a bound instance takes from the global G of its node ("Node animation"): mul(mul(root, G), offset), the palette's mul. A null `root` or
 // `offset` is no multiplication at all (a product with the identity would turn a -0 into +0).
 FRT_HD m4 rig_node_matrix(const m4& G, const float* root, const float* offset) {
@@ -262,4 +323,19 @@ std::string check_blend_samples(uint32_t n, const frt_clip_sample* samples, uint
 std::string check_cast_blend_entries(uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags,
                                      uint32_t allowed_flags, const CastBinding* bindings, size_t nbindings, size_t nmeshes, size_t ninstances,
                                      std::vector<frt_cast_entry>& plain);
+
+// "Layering clips": "" or why a layer list is refused for a rig of `nclips` clips seen with `nmasks` masks: n == 0 or above FRT_MAX_LAYERS, null
+// layers, an unknown mode or flag bit, a clip out of range, a reference clip out of range on an ADDITIVE layer (any other mode: ref_clip and ref_time
+// must be 0), a time, reference time or weight that is not finite, a negative weight, an OVERRIDE weight above 1, a mask that is neither
+// FRT_LAYER_NO_MASK nor below nmasks, a layer 0 that is not (BLEND, no mask, weight > 0) or that carries FRT_LAYER_KEEP_MORPH (it is the base of the
+// morph weights too). The count is checked before the list is read.
+std::string check_clip_layers(uint32_t n, const frt_clip_layer* layers, uint32_t nclips, uint32_t nmasks);
+// Masks where they enter (frt_rig_evaluate_layers, frt_renderer_set_rig_masks): "" or nmasks above FRT_MAX_RIG_MASKS, null masks with nmasks > 0, a
+// value that is not finite or lies outside [0, 1]. The count is checked before the values are read.
+std::string check_rig_masks(uint32_t nmasks, const float* masks, uint32_t nnodes);
+// frt_renderer_animate_cast_layers: check_cast_blend_entries for layers. `masks_of` [nbindings]: how many masks each binding carries. `plain` takes
+// every entry's binding and its layer 0's clip and time.
+std::string check_cast_layers_entries(uint32_t n, const frt_cast_layers_entry* entries, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags,
+                                      uint32_t allowed_flags, const CastBinding* bindings, const uint32_t* masks_of, size_t nbindings, size_t nmeshes,
+                                      size_t ninstances, std::vector<frt_cast_entry>& plain);
 }

@@ -235,6 +235,9 @@ struct RemoveState {
 // instances, `tab` = [the nodes' stored indices, n words padded to 16 bytes | root, 16 floats | offsets, 16 n floats] (root and offsets only when
 // given) and `mats` [4 n] float4, what its kernel writes and the device transform reads. `instance_ids` is the host's copy of `ids`, which
 // remove_instances renumbers; ids_stale: the device copy is uploaded again by the next animate_instances.
+// frt_renderer_set_rig_masks ("Layering clips") leaves either kind `masks` = [nmasks][nnodes] floats in the block's node order, allocated once for
+// FRT_MAX_RIG_MASKS masks so that a later set is a copy in stream order and nothing else; `place` (the caller's node index -> the block's) and `nnodes`
+// are the rig's, kept from bind time.
 enum { kRigMeshes = 0, kRigInstances = 1 };
 struct RigBinding {
     OwnedBuf rig, palette, weights;
@@ -245,7 +248,10 @@ struct RigBinding {
     OwnedBuf ids, tab, mats;
     std::vector<uint32_t> instance_ids;
     bool has_root = false, has_offsets = false, ids_stale = false;
-    void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats}) b->release(r); }
+    OwnedBuf masks;
+    uint32_t nmasks = 0, nnodes = 0;
+    std::vector<uint32_t> place;
+    void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats, &masks}) b->release(r); }
 };
 // What frt_renderer_animate_cast adds ("Animating a cast"): one device buffer, grown on demand and never shrunk, that holds what the halves of a call
 // read as ONE range each — [ids of every instance entry | their matrices | the palettes of every mesh entry | their weights] — beside the bindings' own

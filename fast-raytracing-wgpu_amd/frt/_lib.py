@@ -108,6 +108,20 @@ class CastBlendEntry(C.Structure):                  # include/frt.h: frt_cast_bl
     _fields_ = [("binding", C.c_uint32), ("first_sample", C.c_uint32), ("num_samples", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+MAX_LAYERS, MAX_RIG_MASKS, LAYER_NO_MASK = 8, 16, 0xFFFFFFFF      # include/frt.h: FRT_MAX_LAYERS, FRT_MAX_RIG_MASKS, FRT_LAYER_NO_MASK
+LAYER_MODES = {"blend": 0, "override": 1, "additive": 2}         # include/frt.h: FRT_LAYER_*
+LAYER_KEEP_MORPH = 1                                             # include/frt.h: FRT_LAYER_KEEP_MORPH
+
+
+class ClipLayer(C.Structure):                       # include/frt.h: frt_clip_layer
+    _fields_ = [("clip", C.c_uint32), ("time", C.c_float), ("weight", C.c_float), ("mask", C.c_uint32),
+                ("mode", C.c_uint32), ("ref_clip", C.c_uint32), ("ref_time", C.c_float), ("flags", C.c_uint32)]
+
+
+class CastLayersEntry(C.Structure):                 # include/frt.h: frt_cast_layers_entry
+    _fields_ = [("binding", C.c_uint32), ("first_layer", C.c_uint32), ("num_layers", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}      # include/frt.h: FRT_RIG_PATH_*
 RIG_INTERPOLATIONS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}              # include/frt.h: FRT_RIG_*
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
@@ -248,6 +262,12 @@ SYMBOLS = {
     "frt_renderer_animate_blend": (C.c_int, [_P, _U32, _U32, _P, _U32]),
     "frt_renderer_animate_instances_blend": (C.c_int, [_P, _U32, _U32, _P]),
     "frt_renderer_animate_cast_blend": (C.c_int, [_P, _U32, _P, _U32, _P, _U32]),
+    "frt_rig_evaluate_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _P, _P]),
+    "frt_rig_evaluate_nodes_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _P, _P, _P, _P]),
+    "frt_renderer_set_rig_masks": (C.c_int, [_P, _U32, _U32, _P]),
+    "frt_renderer_animate_layers": (C.c_int, [_P, _U32, _U32, _P, _U32]),
+    "frt_renderer_animate_instances_layers": (C.c_int, [_P, _U32, _U32, _P]),
+    "frt_renderer_animate_cast_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _U32]),
     "frt_renderer_set_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_instance_materials": (C.c_int, [_P, _U32, _P, _P]),
     "frt_renderer_set_light_emission": (C.c_int, [_P, _U32, _P, C.c_float]),

@@ -71,6 +71,7 @@ class Rig:
         h = lib().frt_rig_create_ex(C.byref(d), 1) if nodes_only else lib().frt_rig_create(C.byref(d))
         del keep
         self._adopt(h, "frt_rig_create")
+        self._parents = par
 
     def _adopt(self, handle, call):
         self._destroy = lib().frt_rig_destroy
@@ -86,6 +87,7 @@ class Rig:
         """The rig of skin `skin` of a loaded glTF document (frt.loader.Model; include/frt.h: frt_rig_from_model); skin=None: a morph-only rig."""
         rig = cls.__new__(cls)
         rig._adopt(lib().frt_rig_from_model(model._h, -1 if skin is None else int(skin)), "frt_rig_from_model")
+        rig._parents = model.nodes()["parents"]
         return rig
 
     def __del__(self):
@@ -164,6 +166,101 @@ class Rig:
                                                  offsets.ctypes.data if offsets is not None else None, out.ctypes.data))
         return out
 
+    # ---- layering clips (include/frt.h: frt_rig_evaluate_layers; DESIGN.md section 11, "Layering clips")
+    def mask(self, nodes, value=1.0, descendants=True, base=0.0):
+        """A mask, float32 [num_nodes] in the node order the rig was described with: `value` on `nodes` (one node or several) and, with
+        descendants=True, on everything below them; `base` elsewhere. Values lie in [0, 1]."""
+        m = np.full(self.num_nodes, base, np.float32)
+        picked = np.zeros(self.num_nodes, bool)
+        for n in np.atleast_1d(np.asarray(nodes, np.int64)):
+            if not 0 <= n < self.num_nodes:
+                raise FrtError(f"Rig.mask: node {n} is not a node ({self.num_nodes} nodes)")
+            picked[n] = True
+        if descendants:
+            for n, p in enumerate(self._parents):      # (parents first: a parent's mark is final when its children are reached)
+                if p >= 0 and picked[p]:
+                    picked[n] = True
+        m[picked] = value
+        return m
+
+    def _layer_rows(self, layers):
+        """[ClipLayer] of `layers`, an iterable of frt.Layer or of plain (clip, t, weight) tuples, which are blend layers; clips by number or name."""
+        from ._lib import ClipLayer, LAYER_MODES, LAYER_NO_MASK, LAYER_KEEP_MORPH
+        rows = []
+        for k, x in enumerate(layers):
+            if not isinstance(x, Layer):
+                x = tuple(x)
+                if len(x) != 3:
+                    raise FrtError(f"Rig: layer {k} has {len(x)} fields, not (clip, t, weight); give a frt.Layer for anything else")
+                x = Layer(*x)
+            if x.mode not in LAYER_MODES:
+                raise FrtError(f"Rig: layer {k}: unknown mode {x.mode!r} (modes: {sorted(LAYER_MODES)})")
+            if x.mask is not None and not 0 <= int(x.mask) < LAYER_NO_MASK:
+                raise FrtError(f"Rig: layer {k}: a mask is None or the index of one of the masks")
+            ref = x.reference
+            if x.mode == "additive":
+                ref = (x.clip, 0.0) if ref is None else tuple(ref)
+                if len(ref) != 2:
+                    raise FrtError(f"Rig: layer {k}: reference is (clip, t)")
+                ref = (self.clip_index(ref[0]), float(ref[1]))
+            elif ref is not None:
+                raise FrtError(f"Rig: layer {k}: only an additive layer has a reference")
+            else:
+                ref = (0, 0.0)
+            rows.append(ClipLayer(self.clip_index(x.clip), float(x.t), float(x.weight), LAYER_NO_MASK if x.mask is None else int(x.mask), LAYER_MODES[x.mode],
+                                  ref[0], ref[1], 0 if x.morph else LAYER_KEEP_MORPH))
+        return rows
+
+    def _mask_args(self, masks):
+        """(nmasks, float32 [nmasks, num_nodes] or None) of `masks`: None, one mask [num_nodes] or several [nmasks, num_nodes]."""
+        if masks is None or len(masks) == 0:
+            return 0, None
+        m = np.ascontiguousarray(masks, np.float32)
+        if m.ndim == 1:
+            m = m[None, :]
+        return m.shape[0], _f32(m, (m.shape[0], self.num_nodes), "masks")
+
+    def evaluate_layers(self, layers, masks=None):
+        """evaluate() of a stack of layers (frt.Layer, or (clip, t, weight) for a blend layer), 1 to MAX_LAYERS of them, folded in order into one
+        running pose per node. The first is the base: a blend layer without a mask and with a positive weight. A later layer acts by its weight
+        times its mask's value at the node: "blend" mixes as evaluate_blend does, "override" replaces by that much (weight <= 1), "additive" adds
+        that much of (clip at t) - (reference). masks: [nmasks, num_nodes] values in [0, 1] (Rig.mask), which Layer.mask names by index."""
+        pal = np.zeros((self.num_joints, 16), np.float32) if self.num_joints else None
+        w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
+        n, table = layer_table(self._layer_rows(layers))
+        nm, m = self._mask_args(masks)
+        check(lib().frt_rig_evaluate_layers(self._h, n, table, nm, m.ctypes.data if m is not None else None, pal.ctypes.data if pal is not None else None,
+                                            w.ctypes.data if w is not None else None))
+        return pal, w
+
+    def evaluate_nodes_layers(self, layers, nodes, root=None, offsets=None, masks=None):
+        """evaluate_nodes() of a stack of layers (as evaluate_layers takes them): the matrices Renderer.animate_instances_layers gives the instances."""
+        n, nodes, root, offsets = node_args(nodes, root, offsets)
+        out = np.zeros((n, 16), np.float32)
+        nl, table = layer_table(self._layer_rows(layers))
+        nm, m = self._mask_args(masks)
+        check(lib().frt_rig_evaluate_nodes_layers(self._h, nl, table, nm, m.ctypes.data if m is not None else None, n, nodes.ctypes.data,
+                                                  root.ctypes.data if root is not None else None, offsets.ctypes.data if offsets is not None else None, out.ctypes.data))
+        return out
+
+
+class Layer:
+    """One layer of a stack (include/frt.h: frt_clip_layer): `clip` (a number or a name) at time `t`, acting by `weight` times the value of mask
+    number `mask` (None: 1 everywhere) at each node. mode: "blend", "override" or "additive"; reference: (clip, t) an additive layer is the
+    difference from, by default the same clip at time 0. morph=False: the layer leaves the morph weights alone."""
+
+    def __init__(self, clip, t, weight=1.0, mask=None, mode="blend", reference=None, morph=True):
+        self.clip, self.t, self.weight, self.mask, self.mode, self.reference, self.morph = clip, t, weight, mask, mode, reference, morph
+
+    def __repr__(self):
+        return f"Layer({self.clip!r}, {self.t!r}, weight={self.weight!r}, mask={self.mask!r}, mode={self.mode!r}, reference={self.reference!r}, morph={self.morph!r})"
+
+
+def layer_table(rows):
+    """(n, frt_clip_layer [n]) of [ClipLayer]."""
+    from ._lib import ClipLayer
+    return len(rows), (ClipLayer * max(len(rows), 1))(*rows)
+
 
 def sample_table(rows):
     """(n, frt_clip_sample [n]) of [(clip index, t, weight)]."""
@@ -232,3 +329,39 @@ def host_cast_blend(target, entries, normals="recompute"):
         target.animate_instances_blend(**e)
     for e in mesh:
         target.animate_blend(**e, normals=normals)
+
+
+def _is_index_list(x):
+    """Whether `x` is a non-empty sequence or array of plain integers (node numbers), which no list of layers is."""
+    try:
+        return len(x) > 0 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in x)
+    except TypeError:
+        return False
+
+
+def host_cast_layers(target, entries, normals="recompute"):
+    """host_cast for layers ("Layering clips"): what SceneBuilder.animate_cast_layers and MultiRenderer.animate_cast_layers do.
+    Every entry is the arguments of `target`'s animate_layers, (rig, mesh_ids, layers[, masks]), or of its animate_instances_layers,
+    (rig, instance_ids, nodes, layers, masks[, root[, offsets]]) with masks possibly None, as a tuple or as a dict by name (a dict with "nodes" is
+    an instance entry). The instance entries are applied first, in the order given, then the mesh entries."""
+    inst, mesh = [], []
+    for k, e in enumerate(entries):
+        if isinstance(e, dict):
+            (inst if "nodes" in e else mesh).append(dict(e))
+            continue
+        e = tuple(e)
+        if 3 <= len(e) <= 4:
+            if len(e) == 4 and _is_index_list(e[2]):      # (rig, instance_ids, nodes, layers): an instance entry without its masks slot
+                raise FrtError(f"animate_cast_layers: entry {k} has four fields and the third is a list of node numbers, not of layers: an instance "
+                               "entry is (rig, instance_ids, nodes, layers, masks[, root[, offsets]]), with masks None when it has none")
+            mesh.append(dict(zip(("rig", "mesh_ids", "layers", "masks"), e)))
+        elif 5 <= len(e) <= 7:
+            inst.append(dict(zip(("rig", "instance_ids", "nodes", "layers", "masks", "root", "offsets"), e)))
+        else:
+            raise FrtError(f"animate_cast_layers: entry {k} has {len(e)} fields (3 or 4: a mesh entry, 5 to 7: an instance entry)")
+    if not inst and not mesh:
+        raise FrtError("animate_cast_layers: no entries")
+    for e in inst:
+        target.animate_instances_layers(**e)
+    for e in mesh:
+        target.animate_layers(**e, normals=normals)

@@ -135,6 +135,7 @@ class Model:
         from .animation import Rig
         rig = Rig.__new__(Rig)
         rig._adopt(lib().frt_rig_from_model_nodes(self._h), "frt_rig_from_model_nodes")
+        rig._parents = self.nodes()["parents"]
         return rig
 
 

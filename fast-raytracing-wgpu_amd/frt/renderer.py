@@ -481,6 +481,41 @@ class Renderer(_HostQueries, _SceneGrowth):
         ns, stable = sample_table(rows)
         check(lib().frt_renderer_animate_cast_blend(self._h, len(table), (CastBlendEntry * max(len(table), 1))(*table), ns, stable, deform_flags(normals)))
 
+    # ---- layering clips (include/frt.h: frt_renderer_set_rig_masks and the three calls after it; DESIGN.md section 11, "Layering clips")
+    def set_rig_masks(self, binding, masks):
+        """Give a binding of either kind its masks: [nmasks, num_nodes] values in [0, 1] in the rig's node order (Rig.mask), one mask [num_nodes], or
+        None to clear them. They replace the previous set and take effect in stream order: a call between two animate calls needs no wait."""
+        nm, m = self._bound_rig("set_rig_masks", binding)._mask_args(masks)
+        check(lib().frt_renderer_set_rig_masks(self._h, int(binding), nm, m.ctypes.data if m is not None else None))
+
+    def animate_layers(self, binding, layers, normals="recompute"):
+        """animate() with a stack of layers (frt.Layer, or (clip, t, weight) for a blend layer) as Rig.evaluate_layers takes them; a layer's mask
+        names one of the binding's masks (set_rig_masks). E.g. walk, and wave with the arm: [("walk", t, 1.0), Layer("wave", t, mask=0,
+        mode="override")]. The palette and weights are rig.evaluate_layers(layers, masks) bit for bit."""
+        from .animation import layer_table
+        n, table = layer_table(self._bound_rig("animate_layers", binding)._layer_rows(layers))
+        check(lib().frt_renderer_animate_layers(self._h, int(binding), n, table, deform_flags(normals)))
+
+    def animate_instances_layers(self, binding, layers):
+        """animate_instances() with a stack of layers: the matrices are rig.evaluate_nodes_layers(layers, ..., masks=the binding's) bit for bit."""
+        from .animation import layer_table
+        n, table = layer_table(self._bound_rig("animate_instances_layers", binding)._layer_rows(layers))
+        check(lib().frt_renderer_animate_instances_layers(self._h, int(binding), n, table))
+
+    def animate_cast_layers(self, entries, normals="recompute"):
+        """animate_cast() with a stack of layers per binding: `entries` is an iterable of (binding, layers), each under its own binding's masks.
+        Every rule of animate_cast holds. Bit for bit what animate_instances_layers for the instance entries followed by animate_layers for the
+        mesh entries leave."""
+        from ._lib import CastLayersEntry
+        from .animation import layer_table
+        rows, table = [], []
+        for b, layers in entries:
+            s = self._bound_rig("animate_cast_layers", b)._layer_rows(layers)
+            table.append(CastLayersEntry(int(b), len(rows), len(s), 0))
+            rows += s
+        nl, ltable = layer_table(rows)
+        check(lib().frt_renderer_animate_cast_layers(self._h, len(table), (CastLayersEntry * max(len(table), 1))(*table), nl, ltable, deform_flags(normals)))
+
     def _check_device_tensor(self, torch, call, name, t, shape_ok, shape):
         """What a call asks of a device tensor it is handed: it lives on the renderer's device and is contiguous float32 of a shape `shape_ok` accepts
         (`shape`: how the message spells that shape)."""
@@ -836,6 +871,19 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         """The host form of Renderer.animate_cast_blend (frt.animation.host_cast_blend) on every strip's replica."""
         from .animation import host_cast_blend
         host_cast_blend(self, entries, normals)
+
+    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute"):
+        """rig.evaluate_layers(layers, masks) on the host, then set_mesh_poses on every strip's replica ("Layering clips")."""
+        self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks), normals=normals)
+
+    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None):
+        """rig.evaluate_nodes_layers on the host, then set_instance_transforms on every strip's replica."""
+        self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks))
+
+    def animate_cast_layers(self, entries, normals="recompute"):
+        """The host form of Renderer.animate_cast_layers (frt.animation.host_cast_layers) on every strip's replica."""
+        from .animation import host_cast_layers
+        host_cast_layers(self, entries, normals)
 
     def set_mesh_morph_targets(self, mesh_id, deltas):
         """Renderer.set_mesh_morph_targets on every strip's scene replica."""

@@ -516,6 +516,19 @@ class SceneBuilder:
         host_cast_blend(self, entries, normals)
         return self
 
+    # Layering clips ("Layering clips"): the host forms of Renderer.animate_layers, animate_instances_layers and
+    # animate_cast_layers: rig.evaluate_layers / rig.evaluate_nodes_layers on the host under `masks`, then the same host calls.
+    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute"):
+        return self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks), normals=normals)
+
+    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None):
+        return self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks))
+
+    def animate_cast_layers(self, entries, normals="recompute"):
+        from .animation import host_cast_layers
+        host_cast_layers(self, entries, normals)
+        return self
+
     # Morph targets (include/frt.h: frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights). set_mesh_morph_targets binds `deltas` [T, n, 3]
     # float32; the mesh's positions at the call become the base (deltas=None removes the targets). set_mesh_morph_weights adds the weighted deltas to the
     # base in target order and applies the result as set_mesh_vertices does. Host copy only.

@@ -700,6 +700,62 @@ int frt_renderer_animate_blend(frt_renderer* r, uint32_t binding, uint32_t n, co
 int frt_renderer_animate_instances_blend(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_sample* samples);
 typedef struct frt_cast_blend_entry { uint32_t binding, first_sample, num_samples, reserved; } frt_cast_blend_entry;      /* reserved must be 0 */
 int frt_renderer_animate_cast_blend(frt_renderer* r, uint32_t n, const frt_cast_blend_entry* entries, uint32_t nsamples, const frt_clip_sample* samples, uint32_t flags);
+/* Layering clips ("Layering clips"): wave with the arm while the legs walk, lean on top of whatever plays, fade a layer over a
+ * part of the skeleton. A LAYER is a clip at a time with a weight, a mode and, optionally, a mask; a call takes an ordered list of 1 .. FRT_MAX_LAYERS
+ * layers of one rig. A MASK is one float in [0, 1] per node of the rig, in the caller's node order; a call sees nmasks <= FRT_MAX_RIG_MASKS of them
+ * as masks [nmasks][nnodes] and a layer names one by index, FRT_LAYER_NO_MASK meaning 1 everywhere. As with a blend, the layers meet on a node's
+ * local translation, rotation and scale, in front of the local matrix; everything behind it is the contract of frt_rig_evaluate, unchanged.
+ * frt_clip_sample and every call above keep their meaning and their refusals. The contract (csrc/frt_animation.hpp: rig_local_matrix_layers,
+ * rig_morph_weight_layers, rig_qmul; f32, no contraction, no fma), for a node n that is not a matrix node (a matrix node keeps its matrix), the layers
+ * folded in the order given into ONE running pose (T, R, S) with an accumulated blend weight W:
+ *   Layer 0 is the base: its mode is BLEND, it has no mask and its weight is positive. The pose is that clip sampled at that time, without
+ *   arithmetic, and W = weight. So every node has a base.
+ *   Every later layer: m = 1 or masks[mask][n], e = weight * m. If !(e > 0) the layer is skipped for this node and nothing is sampled. Otherwise
+ *   X = (X.t, X.q, X.s) is the layer's clip sampled at its time and
+ *     FRT_LAYER_BLEND: the blend's rule with e for w: W = W + e, a = e / W, T = T (1 - a) + X.t a and S likewise per component, R = slerp(R, X.q, a).
+ *     FRT_LAYER_OVERRIDE (weight <= 1): a = e. At a >= 1 the pose becomes X without arithmetic; otherwise the same mix and slerp by a. W is unchanged.
+ *     FRT_LAYER_ADDITIVE: Y is ref_clip sampled at ref_time. T = T + e (X.t - Y.t) and S = S + e (X.s - Y.s) per component; D = conj(Y.q) * X.q,
+ *     R = R * slerp((0, 0, 0, 1), D, e), the quaternion product with every product and sum written once in a fixed order (rig_qmul). R is not
+ *     renormalised, a weight above 1 is allowed (it extrapolates), W is unchanged.
+ *   The local matrix is T R S of the result.
+ *   Morph weight c: the weights every layer's clip gives, folded the same way with e = weight (masks do not apply to targets): BLEND the running mix,
+ *   OVERRIDE the mix by the weight or the layer's own value at weight >= 1, ADDITIVE r + weight (x - x_ref). A layer with FRT_LAYER_KEEP_MORPH in its
+ *   flags leaves the morph weights alone.
+ * So a list of BLEND layers without masks is frt_rig_evaluate_blend of the same (clip, time, weight) rows bit for bit; an all-ones mask is no mask;
+ * a layer of weight 0, or under an all-zero mask, anywhere but first is as good as absent; and an OVERRIDE layer of weight 1 under a 0 / 1 mask
+ * replaces exactly the masked nodes' poses.
+ * frt_rig_evaluate_layers / frt_rig_evaluate_nodes_layers are the specification, on the host: outputs and the node arguments as the _blend forms take
+ * them. FRT_ERR_INVALID_ARG, nothing written: n == 0 or above FRT_MAX_LAYERS, layers == NULL, an unknown mode or flag bit, a clip out of range, on an
+ * ADDITIVE layer a ref_clip out of range (every other mode: ref_clip and ref_time must be 0), a time, reference time or weight that is not finite, a
+ * negative weight, an OVERRIDE weight above 1, a mask index that is neither FRT_LAYER_NO_MASK nor below nmasks, a layer 0 that is not (BLEND, no mask,
+ * weight > 0) or that has FRT_LAYER_KEEP_MORPH; nmasks above FRT_MAX_RIG_MASKS, masks == NULL with nmasks > 0, a mask value that is not finite or
+ * outside [0, 1]; and what the _blend forms refuse of their other arguments.
+ * frt_renderer_set_rig_masks gives a binding of either kind its masks: they are uploaded in the rig's stored node order by a staged asynchronous
+ * copy on the main stream, replace the previous set (nmasks == 0 clears it), and take effect in stream order, so a call placed between two animate
+ * calls needs no wait. Refused with nothing changed: an unknown binding, and the mask refusals above.
+ * frt_renderer_animate_layers / _animate_instances_layers / _animate_cast_layers are frt_renderer_animate_blend / _animate_instances_blend /
+ * _animate_cast_blend with layers where those take samples: kernels of the same three phases whose first phase folds the layers in registers, the
+ * same launches, rules and rejects behind the kernel, bit for bit the host forms under the binding's masks. The layers of a one-binding call are a
+ * kernel argument; those of a cast lie in layers [nlayers], entry k naming layers [first_layer .. first_layer + num_layers), each entry under its own
+ * binding's masks. Refused on the host with nothing enqueued: what the _blend call refuses of its other arguments, what frt_rig_evaluate_layers
+ * refuses of a list (seen with the binding's mask count), and for a cast nlayers == 0, an entry whose range is empty, longer than FRT_MAX_LAYERS or
+ * not inside nlayers. */
+#define FRT_MAX_LAYERS 8u
+#define FRT_MAX_RIG_MASKS 16u
+#define FRT_LAYER_NO_MASK 0xFFFFFFFFu
+enum { FRT_LAYER_BLEND = 0, FRT_LAYER_OVERRIDE = 1, FRT_LAYER_ADDITIVE = 2 };
+#define FRT_LAYER_KEEP_MORPH 1u     /* flags: the layer leaves the morph weights alone */
+typedef struct frt_clip_layer {
+    uint32_t clip; float time, weight; uint32_t mask;
+    uint32_t mode, ref_clip; float ref_time; uint32_t flags;
+} frt_clip_layer;   /* 32 bytes */
+int frt_rig_evaluate_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, float* joint_mats_out, float* morph_weights_out);
+int frt_rig_evaluate_nodes_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t nnodes, const uint32_t* nodes, const float* root16, const float* offsets16n, float* mats_out16n);
+int frt_renderer_set_rig_masks(frt_renderer* r, uint32_t binding, uint32_t nmasks, const float* masks);
+int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers, uint32_t flags);
+int frt_renderer_animate_instances_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers);
+typedef struct frt_cast_layers_entry { uint32_t binding, first_layer, num_layers, reserved; } frt_cast_layers_entry;      /* reserved must be 0 */
+int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast_layers_entry* entries, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
