@@ -129,6 +129,66 @@ std::string frt::check_rig_masks(uint32_t nmasks, const float* masks, uint32_t n
         if (!(masks[i] >= 0.0f && masks[i] <= 1.0f)) return "mask " + std::to_string(i / nnodes) + ", node " + std::to_string(i % nnodes) + ": a mask value is a finite number in [0, 1]";
     return "";
 }
+// "Inverse kinematics": the pre-order numbers of the stored nodes, and the checks of goals and of host targets (frt_animation.hpp).
+RigTree frt::rig_tree(const RigView& v) {
+    const RigHeader h = v.h();
+    const uint32_t N = h.nnodes;
+    std::vector<uint32_t> size(N, 1u), next(N, 0u);
+    for (uint32_t n = N; n-- > 1u;) { const uint32_t p = v.w[h.parent + n]; if (p != kRigNone) size[p] += size[n]; }      // (parents in front of their children)
+    RigTree t;
+    t.enter.resize(N); t.exit.resize(N);
+    uint32_t roots = 0;      // the next free number among the roots
+    for (uint32_t n = 0; n < N; ++n) {
+        const uint32_t p = v.w[h.parent + n];
+        uint32_t& at = p == kRigNone ? roots : next[p];
+        t.enter[n] = at; t.exit[n] = at + size[n];
+        at += size[n];
+        next[n] = t.enter[n] + 1u;
+    }
+    return t;
+}
+std::string frt::check_rig_goals(uint32_t ngoals, const frt_rig_goal* goals, const std::vector<uint32_t>& place, const uint32_t* enter, const uint32_t* exit, std::vector<frt_rig_goal>& stored) {
+    stored.clear();
+    if (ngoals > FRT_MAX_RIG_GOALS) return std::to_string(ngoals) + " goals, more than FRT_MAX_RIG_GOALS";
+    if (ngoals && !goals) return "null goals";
+    const uint32_t N = (uint32_t)place.size();
+    auto below = [enter, exit](uint32_t a, uint32_t d) { return a != d && ik_in_subtree(enter, exit, a, d); };      // d a strict descendant of a
+    for (uint32_t i = 0; i < ngoals; ++i) {
+        const frt_rig_goal& g = goals[i];
+        const std::string at = "goal " + std::to_string(i) + ": ";
+        if (g.kind > (uint32_t)FRT_GOAL_AIM) return at + "unknown kind " + std::to_string(g.kind);
+        if (g.reserved != 0) return at + "reserved must be 0";
+        if (g.root >= N || g.mid >= N || g.tip >= N) return at + "a node out of range (" + std::to_string(N) + " nodes)";
+        frt_rig_goal s = g;
+        if (g.kind == (uint32_t)FRT_GOAL_AIM) {
+            if (g.mid != 0 || g.tip != 0) return at + "mid and tip of an aim goal must be 0";
+            if (!all_finite(g.axis, 3)) return at + "the axis is not finite";
+            if (g.axis[0] == 0.0f && g.axis[1] == 0.0f && g.axis[2] == 0.0f) return at + "the axis is zero";
+            s.root = place[g.root]; s.mid = 0u; s.tip = 0u;
+        } else {
+            s.root = place[g.root]; s.mid = place[g.mid]; s.tip = place[g.tip];
+            if (!below(s.root, s.mid)) return at + "mid is not a strict descendant of root";
+            if (!below(s.mid, s.tip)) return at + "tip is not a strict descendant of mid";
+            s.axis[0] = s.axis[1] = s.axis[2] = 0.0f;      // (a two-bone goal has no axis: nothing of it is kept)
+        }
+        stored.push_back(s);
+    }
+    return "";
+}
+std::string frt::check_rig_goal_targets(uint32_t ngoals, const frt_rig_goal_target* targets, uint32_t bound, const frt_rig_goal* goals) {
+    if (ngoals > FRT_MAX_RIG_GOALS) return std::to_string(ngoals) + " targets, more than FRT_MAX_RIG_GOALS";
+    if (ngoals != bound) return std::to_string(ngoals) + " targets for " + std::to_string(bound) + " goals";
+    if (ngoals && !targets) return "null targets";
+    for (uint32_t i = 0; i < ngoals; ++i) {
+        const frt_rig_goal_target& t = targets[i];
+        const std::string at = "target " + std::to_string(i) + ": ";
+        if (!all_finite(t.target, 3) || !std::isfinite(t.weight) || !all_finite(t.pole, 3) || !std::isfinite(t.pole_flag)) return at + "a word is not finite";
+        if (!(t.weight >= 0.0f && t.weight <= 1.0f)) return at + "a weight lies in [0, 1]";
+        if (t.pole_flag != 0.0f && t.pole_flag != 1.0f) return at + "the pole flag is 0 or 1";
+        if (goals[i].kind == (uint32_t)FRT_GOAL_AIM && (t.pole_flag != 0.0f || t.pole[0] != 0.0f || t.pole[1] != 0.0f || t.pole[2] != 0.0f)) return at + "an aim goal has no pole";
+    }
+    return "";
+}
 std::string frt::check_cast_layers_entries(uint32_t n, const frt_cast_layers_entry* e, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags,
                                            uint32_t allowed_flags, const CastBinding* bindings, const uint32_t* masks_of, size_t nbindings, size_t nmeshes,
                                            size_t ninstances, std::vector<frt_cast_entry>& plain) {
@@ -538,6 +598,25 @@ static std::string check_layers_call(const frt_rig* rig, const RigHeader& h, uin
         for (uint32_t i = 0; i < h.nnodes; ++i) stored[(size_t)m * h.nnodes + rig->place[i]] = masks[(size_t)m * h.nnodes + i];
     return "";
 }
+// "Inverse kinematics": what both _ik calls check of their goals and targets (`gs`: the goals with stored indices; `tree`: filled when there are any),
+// and the goals applied to the globals in list order, each from the globals the earlier ones left: the text of rig_apply_goals (frt_animation.hip).
+static std::string check_goals_call(const frt_rig* rig, uint32_t ngoals, const frt_rig_goal* goals, const frt_rig_goal_target* targets, std::vector<frt_rig_goal>& gs, RigTree& tree) {
+    if (ngoals > FRT_MAX_RIG_GOALS) return std::to_string(ngoals) + " goals, more than FRT_MAX_RIG_GOALS";
+    if (ngoals == 0) return "";
+    tree = rig_tree(rig->view());
+    const std::string bad = check_rig_goals(ngoals, goals, rig->place, tree.enter.data(), tree.exit.data(), gs);
+    return bad.empty() ? check_rig_goal_targets(ngoals, targets, ngoals, gs.data()) : bad;
+}
+static void apply_goals(std::vector<m4>& global, const std::vector<frt_rig_goal>& gs, const frt_rig_goal_target* targets, const RigTree& tree) {
+    for (size_t i = 0; i < gs.size(); ++i) {
+        const IkDelta d = ik_goal_delta(gs[i], targets[i], global[gs[i].root], global[gs[i].mid], global[gs[i].tip]);
+        if (!d.on) continue;
+        for (uint32_t n = 0; n < (uint32_t)global.size(); ++n) {
+            m4 G = global[n];
+            if (ik_move_node(d, tree.enter.data(), tree.exit.data(), n, G)) global[n] = G;
+        }
+    }
+}
 static std::vector<m4> layers_globals(const RigView& v, const RigHeader& h, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* stored) {
     std::vector<m4> global(h.nnodes);
     for (uint32_t i = 0; i < h.nnodes; ++i) {
@@ -547,19 +626,22 @@ static std::vector<m4> layers_globals(const RigView& v, const RigHeader& h, uint
     }
     return global;
 }
-
-extern "C" {
-
-int frt_rig_evaluate_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, float* joint_mats_out, float* morph_weights_out) {
-    if (!rig) return rig_fail("rig_evaluate_layers: null");
+static int evaluate_layers(const char* call, const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals,
+                           const frt_rig_goal* goals, const frt_rig_goal_target* targets, float* joint_mats_out, float* morph_weights_out) {
+    const std::string name = call;
+    if (!rig) return rig_fail(name + ": null");
     const RigView v = rig->view();
     const RigHeader h = v.h();
     std::vector<float> stored;
-    const std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
-    if (!bad.empty()) return rig_fail("rig_evaluate_layers: " + bad);
-    if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail("rig_evaluate_layers: null output");
+    std::vector<frt_rig_goal> gs;
+    RigTree tree;
+    std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
+    if (bad.empty()) bad = check_goals_call(rig, ngoals, goals, targets, gs, tree);
+    if (!bad.empty()) return rig_fail(name + ": " + bad);
+    if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail(name + ": null output");
     if (h.njoints) {
-        const std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
+        std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
+        apply_goals(global, gs, targets, tree);
         for (uint32_t j = 0; j < h.njoints; ++j) {
             const m4 m = mul(global[v.w[h.joint_node + j]], load_m4(v.f(h.inv_bind) + (size_t)16 * j));
             memcpy(joint_mats_out + (size_t)16 * j, &m, 64);
@@ -568,25 +650,48 @@ int frt_rig_evaluate_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer
     for (uint32_t c = 0; c < h.ntargets; ++c) morph_weights_out[c] = rig_morph_weight_layers(v, n, layers, c);
     return FRT_OK;
 }
-
-int frt_rig_evaluate_nodes_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
-    if (!rig) return rig_fail("rig_evaluate_nodes_layers: null");
+static int evaluate_nodes_layers(const char* call, const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals,
+                                 const frt_rig_goal* goals, const frt_rig_goal_target* targets, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets,
+                                 float* mats_out) {
+    const std::string name = call;
+    if (!rig) return rig_fail(name + ": null");
     const RigView v = rig->view();
     const RigHeader h = v.h();
     std::vector<float> stored;
-    const std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
-    if (!bad.empty()) return rig_fail("rig_evaluate_nodes_layers: " + bad);
-    if (nnodes == 0 || !nodes || !mats_out) return rig_fail("rig_evaluate_nodes_layers: nnodes is 0, or null nodes or output");
+    std::vector<frt_rig_goal> gs;
+    RigTree tree;
+    std::string bad = check_layers_call(rig, h, n, layers, nmasks, masks, stored);
+    if (bad.empty()) bad = check_goals_call(rig, ngoals, goals, targets, gs, tree);
+    if (!bad.empty()) return rig_fail(name + ": " + bad);
+    if (nnodes == 0 || !nodes || !mats_out) return rig_fail(name + ": nnodes is 0, or null nodes or output");
     for (uint32_t k = 0; k < nnodes; ++k)
-        if (nodes[k] >= h.nnodes) return rig_fail("rig_evaluate_nodes_layers: node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
-    if (root && !all_finite(root, 16)) return rig_fail("rig_evaluate_nodes_layers: a root entry is not finite");
-    if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail("rig_evaluate_nodes_layers: an offsets entry is not finite");
-    const std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
+        if (nodes[k] >= h.nnodes) return rig_fail(name + ": node " + std::to_string(nodes[k]) + " is not a node (" + std::to_string(h.nnodes) + " nodes)");
+    if (root && !all_finite(root, 16)) return rig_fail(name + ": a root entry is not finite");
+    if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail(name + ": an offsets entry is not finite");
+    std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
+    apply_goals(global, gs, targets, tree);
     for (uint32_t k = 0; k < nnodes; ++k) {
         const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
         memcpy(mats_out + (size_t)16 * k, &M, 64);
     }
     return FRT_OK;
+}
+
+extern "C" {
+
+int frt_rig_evaluate_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, float* joint_mats_out, float* morph_weights_out) {
+    return evaluate_layers("rig_evaluate_layers", rig, n, layers, nmasks, masks, 0u, nullptr, nullptr, joint_mats_out, morph_weights_out);
+}
+int frt_rig_evaluate_nodes_layers(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
+    return evaluate_nodes_layers("rig_evaluate_nodes_layers", rig, n, layers, nmasks, masks, 0u, nullptr, nullptr, nnodes, nodes, root, offsets, mats_out);
+}
+int frt_rig_evaluate_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals,
+                               const frt_rig_goal_target* targets, float* joint_mats_out, float* morph_weights_out) {
+    return evaluate_layers("rig_evaluate_layers_ik", rig, n, layers, nmasks, masks, ngoals, goals, targets, joint_mats_out, morph_weights_out);
+}
+int frt_rig_evaluate_nodes_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals,
+                                     const frt_rig_goal_target* targets, uint32_t nnodes, const uint32_t* nodes, const float* root, const float* offsets, float* mats_out) {
+    return evaluate_nodes_layers("rig_evaluate_nodes_layers_ik", rig, n, layers, nmasks, masks, ngoals, goals, targets, nnodes, nodes, root, offsets, mats_out);
 }
 
 } // extern "C"

@@ -107,17 +107,62 @@ __device__ inline void rig_globals_to_lds(RigView v, const RigHeader& h, const S
     }
 }
 
-template <class List>
-__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, const List list, float4* palette, float* weights) {
+// The GOALS of a kernel ("Inverse kinematics"), its second policy: none (the single-clip and blend calls, and a layered call on a binding without
+// goals: instantiations that hold no goal code at all), or the binding's. Bound goals are device memory the binding owns: `g` [n] the definitions
+// with stored node indices, `enter` / `exit` [nnodes] the pre-order numbers behind them in the same buffer, `t` [FRT_MAX_RIG_GOALS] the targets.
+struct RigNoGoals {
+    static constexpr bool any = false;
+    __device__ bool ok(uint32_t) const { return true; }
+};
+struct RigBoundGoals {
+    static constexpr bool any = true;
+    uint32_t n, pad; const frt_rig_goal* g; const uint32_t* enter; const uint32_t* exit; const frt_rig_goal_target* t;
+    // What set_rig_goals has refused, restated on the goal words (uniform): the count, the kinds, nodes < N. Asked in front of the first barrier.
+    __device__ bool ok(uint32_t N) const {
+        if (n > FRT_MAX_RIG_GOALS) return false;
+        if (n && (!g || !enter || !exit || !t)) return false;
+        for (uint32_t i = 0; i < n; ++i)
+            if (g[i].kind > (uint32_t)FRT_GOAL_AIM || g[i].root >= N || g[i].mid >= N || g[i].tip >= N) return false;
+        return true;
+    }
+};
+static_assert(sizeof(frt_rig_goal) == 32 && sizeof(frt_rig_goal_target) == 32 && sizeof(RigBoundGoals) == 40, "goal layouts");
+// Between phases (2) and (3): every goal is one round. READ: every lane reads the goal's words (global memory) and its pivots' globals (LDS) — the
+// same addresses for every lane — and computes the same matrices; no lane is elected and nothing is shared. BARRIER (every lane has read the pivots
+// before one of them is written). WRITE: the lanes stride over all N nodes, test membership by enter / exit and store mul(D, G) in place, one lane
+// per entry. BARRIER. Both barriers are reached by the whole workgroup in every round: a skipped goal skips its stores only. Called with uniform
+// arguments behind the last barrier of rig_globals_to_lds.
+template <class Goals>
+__device__ inline void rig_apply_goals(const Goals& goals, float4* g, uint32_t N) {
+    if constexpr (Goals::any) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < goals.n; ++i) {
+            const frt_rig_goal gl = goals.g[i];
+            const IkDelta d = ik_goal_delta(gl, goals.t[i], rig_lds_load(g, gl.root), rig_lds_load(g, gl.mid), rig_lds_load(g, gl.tip));
+            __syncthreads();
+            if (d.on) {
+                for (uint32_t n = threadIdx.x; n < N; n += (uint32_t)kRigBlock) {
+                    m4 G = rig_lds_load(g, n);
+                    if (ik_move_node(d, goals.enter, goals.exit, n, G)) rig_lds_store(g, n, G);
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <class List, class Goals>
+__global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t* words, const List list, const Goals goals, float4* palette, float* weights) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig refuses a larger rig)
     const auto src = list.source();
-    if (!src.ok(h)) return;                                          // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
+    if (!src.ok(h) || !goals.ok(N)) return;                          // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
     if (h.njoints) {
         rig_globals_to_lds(v, h, src, g, N);
+        rig_apply_goals(goals, g, N);
         for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
             const uint32_t n = words[h.joint_node + j];
             if (n >= N) continue;
@@ -132,15 +177,16 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
 // frt_renderer_animate_instances ("Node animation"): phases (1) and (2) as above, whether or not the rig has joints; (3) one lane per bound instance,
 // strided by the workgroup's size, loads its node's global from LDS, applies root and offset through rig_node_matrix (the host's text) and stores four
 // float4 into the binding's matrices. `nodes` [n]: stored node indices; `root` [16] and `offsets` [16 n]: null when the binding has none.
-template <class List>
-__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, const List list, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
+template <class List, class Goals>
+__global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* words, const List list, const Goals goals, uint32_t n, const uint32_t* nodes, const float* root, const float* offsets, float4* mats) {
     __shared__ float4 g[4u * kRigLds];
     RigView v; v.w = words;
     const RigHeader h = v.h();
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (bind_rig_instances refuses a larger rig)
     const auto src = list.source();
-    if (!src.ok(h)) return;                                          // (animate_instances refuses it; uniform, in front of the first barrier)
+    if (!src.ok(h) || !goals.ok(N)) return;                          // (animate_instances refuses it; uniform, in front of the first barrier)
     rig_globals_to_lds(v, h, src, g, N);
+    rig_apply_goals(goals, g, N);
     for (uint32_t k = threadIdx.x; k < n; k += (uint32_t)kRigBlock) {
         const uint32_t node = nodes[k];
         if (node >= N) continue;                                     // (bind_rig_instances has checked it)
@@ -179,17 +225,31 @@ struct CastLayersEntry {
     const frt_clip_layer* layers;      // the entry's layers [nlayers], behind the table in the same device block
     uint32_t nlayers;
     uint32_t kind, n;
-    uint32_t nmasks;                   // the binding's masks [nmasks][nnodes], in the block's node order
+    uint16_t nmasks, ngoals;           // the binding's masks [nmasks][nnodes], in the block's node order, and its goals ("Inverse kinematics"): both at most 16
     float4* own; float4* all;
     float* own_w; float* all_w;
     const uint32_t* nodes; const float* root; const float* offsets;
     const uint32_t* ids; uint32_t* all_ids;
     const float* masks;
+    const uint8_t* goals;              // "Inverse kinematics": the binding's goal buffer [FRT_MAX_RIG_GOALS goals | enter | exit] and its targets
+    const frt_rig_goal_target* goal_targets;
     typedef frt_clip_layer Item;
-    void set_list(const Item* items, uint32_t count, const RigBinding& b) { layers = items; nlayers = count; nmasks = b.nmasks; masks = b.nmasks ? b.masks.as<const float>() : nullptr; }
+    void set_list(const Item* items, uint32_t count, const RigBinding& b) {
+        layers = items; nlayers = count; nmasks = (uint16_t)b.nmasks; masks = b.nmasks ? b.masks.as<const float>() : nullptr;
+        ngoals = (uint16_t)b.ngoals; goals = b.ngoals ? b.goals.as<const uint8_t>() : nullptr; goal_targets = b.ngoals ? b.goal_targets.as<const frt_rig_goal_target>() : nullptr;
+    }
     __device__ RigLayers source() const { return RigLayers{layers, nlayers, nmasks, masks}; }
 };
-static_assert(sizeof(CastLayersEntry) == 112 && sizeof(CastLayersEntry) % 16 == 0 && alignof(CastLayersEntry) <= 16, "CastLayersEntry layout");
+static_assert(sizeof(CastLayersEntry) == 128 && sizeof(CastLayersEntry) % 16 == 0 && alignof(CastLayersEntry) <= 16, "CastLayersEntry layout");
+// The goals of a cast's entry: the entry's own binding's (an entry without goals runs the loop zero times); none for a cast without goals.
+__device__ inline RigBoundGoals rig_goals_at(const uint8_t* buf, const frt_rig_goal_target* t, uint32_t n, uint32_t nnodes) {
+    const uint32_t* tree = reinterpret_cast<const uint32_t*>(buf + sizeof(frt_rig_goal) * FRT_MAX_RIG_GOALS);
+    return RigBoundGoals{n, 0u, reinterpret_cast<const frt_rig_goal*>(buf), tree, tree + nnodes, t};
+}
+template <class Goals, class Entry> struct CastGoals { __device__ static RigNoGoals of(const Entry&, uint32_t) { return RigNoGoals(); } };
+template <> struct CastGoals<RigBoundGoals, CastLayersEntry> {
+    __device__ static RigBoundGoals of(const CastLayersEntry& e, uint32_t nnodes) { return e.ngoals ? rig_goals_at(e.goals, e.goal_targets, e.ngoals, nnodes) : RigBoundGoals{0u, 0u, nullptr, nullptr, nullptr, nullptr}; }
+};
 
 __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, const m4& m) {
 #pragma unroll
@@ -199,7 +259,7 @@ __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, con
         all[4u * k + (uint32_t)c] = q;
     }
 }
-template <class Entry>
+template <class Entry, class Goals>
 __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const Entry* table) {
     __shared__ float4 g[4u * kRigLds];
     const Entry e = table[blockIdx.x];
@@ -208,9 +268,10 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const Entry* table)
     const uint32_t tid = threadIdx.x;
     const uint32_t N = h.nnodes < kRigLds ? h.nnodes : kRigLds;      // (the bind calls refuse a larger rig)
     const auto src = e.source();
-    if (!src.ok(h)) return;                                          // (animate_cast refuses it; uniform, in front of the first barrier)
+    const Goals goals = CastGoals<Goals, Entry>::of(e, h.nnodes);      // (enter and exit lie behind the definitions, nnodes words each)
+    if (!src.ok(h) || !goals.ok(N)) return;                          // (animate_cast refuses it; uniform, in front of the first barrier)
     const bool instances = e.kind == (uint32_t)kRigInstances;
-    if (instances || h.njoints) rig_globals_to_lds(v, h, src, g, N);
+    if (instances || h.njoints) { rig_globals_to_lds(v, h, src, g, N); rig_apply_goals(goals, g, N); }
     if (instances) {
         for (uint32_t k = tid; k < e.n; k += (uint32_t)kRigBlock) {
             e.all_ids[k] = e.ids[k];
@@ -270,8 +331,14 @@ static RigLayerList layer_list(uint32_t n, const frt_clip_layer* l, const RigBin
 }
 
 // frt_renderer_animate_instances, _animate_instances_blend and _animate_instances_layers behind their checks: the kernel, then the device transform.
-template <class List>
-static int move_bound_instances(frt_renderer* r, const std::string& call, RigBinding* b, const List& list) {
+// The goals a layered call on binding b launches with ("Inverse kinematics"): for a binding that carries some.
+static RigBoundGoals bound_goals(const RigBinding& b) {
+    const uint32_t* tree = reinterpret_cast<const uint32_t*>(b.goals.as<const uint8_t>() + sizeof(frt_rig_goal) * FRT_MAX_RIG_GOALS);
+    return RigBoundGoals{b.ngoals, 0u, b.goals.as<const frt_rig_goal>(), tree, tree + b.nnodes, b.goal_targets.as<const frt_rig_goal_target>()};
+}
+
+template <class List, class Goals = RigNoGoals>
+static int move_bound_instances(frt_renderer* r, const std::string& call, RigBinding* b, const List& list, const Goals& goals = Goals()) {
     const uint32_t n = (uint32_t)b->instance_ids.size();
     {
         // The kernel writes the binding's matrices only, which nothing but the device transform of an earlier animate_instances reads: on this stream, in front of it.
@@ -287,7 +354,7 @@ static int move_bound_instances(frt_renderer* r, const std::string& call, RigBin
         const size_t node_bytes = ((size_t)n * 4 + 15u) & ~(size_t)15u;
         const float* root = b->has_root ? reinterpret_cast<const float*>(tab + node_bytes) : nullptr;
         const float* offsets = b->has_offsets ? reinterpret_cast<const float*>(tab + node_bytes + (b->has_root ? 64u : 0u)) : nullptr;
-        hipLaunchKernelGGL(rig_nodes_kernel<List>, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
+        hipLaunchKernelGGL((rig_nodes_kernel<List, Goals>), dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, goals, n, reinterpret_cast<const uint32_t*>(tab), root, offsets, b->mats.as<float4>());
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
     }
@@ -295,15 +362,15 @@ static int move_bound_instances(frt_renderer* r, const std::string& call, RigBin
 }
 // frt_renderer_animate, _animate_blend and _animate_layers behind their checks of the list: the meshes as animate checks them, the kernel, then the
 // pose batch.
-template <class List>
-static int pose_bound_meshes(frt_renderer* r, const std::string& call, RigBinding* b, const List& list, uint32_t flags) {
+template <class List, class Goals = RigNoGoals>
+static int pose_bound_meshes(frt_renderer* r, const std::string& call, RigBinding* b, const List& list, uint32_t flags, const Goals& goals = Goals()) {
     const uint32_t n = (uint32_t)b->mesh_ids.size();
     const std::string bad = check_posed_meshes(r, n, b->mesh_ids.data(), b->njoints != 0, b->palette.p, b->njoints, b->ntargets != 0, b->weights.p, b->ntargets, false);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, call + ": " + bad);
     {
         // The kernel writes the binding's palette and weights only, which nothing but the pose launches of an earlier animate read: on this stream, in front of it.
         FRT_DEVICE(r);
-        hipLaunchKernelGGL(rig_evaluate_kernel<List>, dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, b->palette.as<float4>(), b->weights.as<float>());
+        hipLaunchKernelGGL((rig_evaluate_kernel<List, Goals>), dim3(1), dim3(kRigBlock), 0, r->stream, b->rig.as<const uint32_t>(), list, goals, b->palette.as<float4>(), b->weights.as<float>());
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call + ": " + hipGetErrorString(e)); }
     }
@@ -329,7 +396,7 @@ static std::vector<CastBinding> cast_bindings(const frt_renderer* r) {
 // Past the first call of a steady cast nothing here allocates, waits for the stream or copies synchronously: the pinned block's event has long passed
 // when the next call comes.
 struct CastRange { uint32_t first, count; };
-template <class Entry>
+template <class Entry, class Goals = RigNoGoals>
 static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, const frt_cast_entry* entries, const CastRange* ranges,
                     const std::vector<CastBinding>& info, uint32_t nsamples, const typename Entry::Item* samples, uint32_t flags) {
     std::string bad;
@@ -386,7 +453,7 @@ static int run_cast(frt_renderer* r, const std::string& call_name, uint32_t n, c
         }
         HIP_TRY(hipMemcpyAsync(r->rig_up.d, r->rig_up.h, table_bytes + sample_bytes, hipMemcpyHostToDevice, r->stream));
         if (const int rc = r->rig_up.mark(r->stream)) return rc;
-        hipLaunchKernelGGL(rig_cast_kernel<Entry>, dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const Entry*>(r->rig_up.d));
+        hipLaunchKernelGGL((rig_cast_kernel<Entry, Goals>), dim3(n), dim3(kRigBlock), 0, r->stream, reinterpret_cast<const Entry*>(r->rig_up.d));
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { r->failed = true; return fail(FRT_ERR_HIP, call_name + ": " + hipGetErrorString(e)); }
         call.ninst = l.ninst; call.ids = reinterpret_cast<const uint32_t*>(all + l.ids_off); call.mats = reinterpret_cast<const float*>(all + l.mats_off);
@@ -421,7 +488,7 @@ int frt_renderer_bind_rig(frt_renderer* r, const frt_rig* rig, const uint32_t* m
     }
     if (rc) { b.rig.release(r); b.palette.release(r); b.weights.release(r); return rc; }
     b.njoints = h.njoints; b.ntargets = h.ntargets; b.nclips = h.nclips; b.mesh_ids.assign(mesh_ids, mesh_ids + n); b.live = true;
-    b.nnodes = h.nnodes; b.place = rig->place;
+    b.nnodes = h.nnodes; b.place = rig->place; { RigTree t = rig_tree(rig->view()); b.enter.swap(t.enter); b.exit.swap(t.exit); }
     *binding_out = keep_binding(r, b);
     return FRT_OK;
 }
@@ -469,7 +536,7 @@ int frt_renderer_bind_rig_instances(frt_renderer* r, const frt_rig* rig, uint32_
     }
     if (rc) { b.release(r); return rc; }
     b.kind = kRigInstances; b.nclips = h.nclips; b.instance_ids.assign(instance_ids, instance_ids + n); b.has_root = root != nullptr; b.has_offsets = offsets != nullptr; b.live = true;
-    b.nnodes = h.nnodes; b.place = rig->place;
+    b.nnodes = h.nnodes; b.place = rig->place; { RigTree t = rig_tree(rig->view()); b.enter.swap(t.enter); b.exit.swap(t.exit); }
     *binding_out = keep_binding(r, b);
     return FRT_OK;
 }
@@ -574,6 +641,60 @@ int frt_renderer_set_rig_masks(frt_renderer* r, uint32_t binding, uint32_t nmask
     return FRT_OK;
 }
 
+// "Inverse kinematics". The goals go into a buffer [FRT_MAX_RIG_GOALS goals | enter [nnodes] | exit [nnodes]] and the targets into one of
+// FRT_MAX_RIG_GOALS records, both allocated at the binding's first set_rig_goals with a goal, so that every later set is a staged copy in stream
+// order: a layered call enqueued before it reads the old values, one enqueued behind it the new ones, and the count a later call launches with is
+// the new one (a kernel argument, or a word of the cast's table). New goals are inert: the targets are reset to zero words, weight 0.
+int frt_renderer_set_rig_goals(frt_renderer* r, uint32_t binding, uint32_t ngoals, const frt_rig_goal* goals) {
+    if (const int rc = check_entry(r, "set_rig_goals", kEditChecks | kRefit)) return rc;
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "set_rig_goals: unknown rig binding " + std::to_string(binding));
+    std::vector<frt_rig_goal> stored;
+    const std::string bad = check_rig_goals(ngoals, goals, b->place, b->enter.data(), b->exit.data(), stored);
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_rig_goals: " + bad);
+    if (ngoals == 0) { b->ngoals = 0; b->goal_defs.clear(); return FRT_OK; }
+    FRT_DEVICE(r);
+    const uint32_t N = b->nnodes;
+    const size_t def_bytes = sizeof(frt_rig_goal) * FRT_MAX_RIG_GOALS, bytes = def_bytes + (size_t)8 * N, target_bytes = sizeof(frt_rig_goal_target) * FRT_MAX_RIG_GOALS;
+    if (const int rc = b->goals.ensure(r, bytes)) return rc;
+    if (const int rc = b->goal_targets.ensure(r, target_bytes)) return rc;
+    if (const int rc = r->rig_up.reserve(bytes, 0, r->stream)) return rc;
+    memset(r->rig_up.h, 0, def_bytes);
+    memcpy(r->rig_up.h, stored.data(), sizeof(frt_rig_goal) * ngoals);
+    memcpy(r->rig_up.h + def_bytes, b->enter.data(), (size_t)4 * N);
+    memcpy(r->rig_up.h + def_bytes + (size_t)4 * N, b->exit.data(), (size_t)4 * N);
+    HIP_TRY(hipMemcpyAsync(b->goals.p, r->rig_up.h, bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemsetAsync(b->goal_targets.p, 0, target_bytes, r->stream));
+    if (const int rc = r->rig_up.mark(r->stream)) return rc;
+    b->ngoals = ngoals; b->goal_defs.swap(stored);
+    return FRT_OK;
+}
+
+int frt_renderer_set_rig_goal_targets(frt_renderer* r, uint32_t binding, uint32_t ngoals, const frt_rig_goal_target* targets, uint32_t flags) {
+    if (const int rc = check_entry(r, "set_rig_goal_targets", kEditChecks | kRefit)) return rc;
+    if (flags & ~FRT_GOAL_TARGETS_DEVICE) return fail(FRT_ERR_INVALID_ARG, "set_rig_goal_targets: unknown flag bits");
+    RigBinding* b = find_binding(r, binding);
+    if (!b) return fail(FRT_ERR_INVALID_ARG, "set_rig_goal_targets: unknown rig binding " + std::to_string(binding));
+    const size_t bytes = sizeof(frt_rig_goal_target) * (size_t)ngoals;
+    if (flags & FRT_GOAL_TARGETS_DEVICE) {
+        if (ngoals > FRT_MAX_RIG_GOALS || ngoals != b->ngoals) return fail(FRT_ERR_INVALID_ARG, "set_rig_goal_targets: " + std::to_string(ngoals) + " targets for " + std::to_string(b->ngoals) + " goals");
+        if (ngoals && !targets) return fail(FRT_ERR_INVALID_ARG, "set_rig_goal_targets: null targets");
+        if (ngoals == 0) return FRT_OK;
+        if (const int rc = check_device_block(r, targets, bytes, 16, "set_rig_goal_targets", "targets", "FRT_GOAL_TARGETS_DEVICE")) return rc;
+        FRT_DEVICE(r);
+        HIP_TRY(hipMemcpyAsync(b->goal_targets.p, targets, bytes, hipMemcpyDeviceToDevice, r->stream));
+        return FRT_OK;
+    }
+    const std::string bad = check_rig_goal_targets(ngoals, targets, b->ngoals, b->goal_defs.data());
+    if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_rig_goal_targets: " + bad);
+    if (ngoals == 0) return FRT_OK;
+    FRT_DEVICE(r);
+    if (const int rc = r->rig_up.reserve(bytes, 0, r->stream)) return rc;
+    memcpy(r->rig_up.h, targets, bytes);
+    HIP_TRY(hipMemcpyAsync(b->goal_targets.p, r->rig_up.h, bytes, hipMemcpyHostToDevice, r->stream));
+    return r->rig_up.mark(r->stream);
+}
+
 int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers, uint32_t flags) {
     if (const int rc = check_entry(r, "animate_layers", kEditChecks | kRefit)) return rc;
     if (flags & ~FRT_DEFORM_RECOMPUTE_NORMALS) return fail(FRT_ERR_INVALID_ARG, "animate_layers: unknown flag bits");
@@ -582,6 +703,7 @@ int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, c
     if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate_layers: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances_layers)");
     const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_layers: " + bad);
+    if (b->ngoals) return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags, bound_goals(*b));
     return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags);
 }
 
@@ -592,6 +714,7 @@ int frt_renderer_animate_instances_layers(frt_renderer* r, uint32_t binding, uin
     if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate_layers)");
     const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: " + bad);
+    if (b->ngoals) return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b), bound_goals(*b));
     return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b));
 }
 
@@ -606,6 +729,9 @@ int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast_layers: " + bad);
     std::vector<CastRange> ranges(n);
     for (uint32_t k = 0; k < n; ++k) ranges[k] = CastRange{entries[k].first_layer, entries[k].num_layers};
+    bool goals = false;      // the goal instantiation when any entry's binding carries goals
+    for (uint32_t k = 0; k < n; ++k) goals = goals || r->rigs[entries[k].binding].ngoals != 0;
+    if (goals) return run_cast<CastLayersEntry, RigBoundGoals>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
     return run_cast<CastLayersEntry>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
 }
 

@@ -279,6 +279,8 @@ FRT_HD m4 rig_node_matrix(const m4& G, const float* root, const float* offset) {
 
 } // namespace frt
 
+#include "frt_ik.hpp"      // "Inverse kinematics": goals on the globals, behind the functions above (rig_slerp, rig_trs_matrix, rig_dot4)
+
 // The host side of a rig (frt_animation.cpp): the block and what frt_rig_clip_info returns. `place`: the caller's node index -> the index in the block
 // (frt_rig_create stores the nodes by depth), so the node numbers a caller knows stay valid after creation.
 #include <string>
@@ -338,4 +340,16 @@ std::string check_rig_masks(uint32_t nmasks, const float* masks, uint32_t nnodes
 std::string check_cast_layers_entries(uint32_t n, const frt_cast_layers_entry* entries, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags,
                                       uint32_t allowed_flags, const CastBinding* bindings, const uint32_t* masks_of, size_t nbindings, size_t nmeshes,
                                       size_t ninstances, std::vector<frt_cast_entry>& plain);
+
+// "Inverse kinematics": the pre-order numbers of a rig's stored nodes (d lies in subtree(a) iff enter[a] <= enter[d] < exit[a]), kept with the goals.
+struct RigTree { std::vector<uint32_t> enter, exit; };
+RigTree rig_tree(const RigView& v);
+// Goals where they enter (frt_rig_evaluate_layers_ik, frt_renderer_set_rig_goals): "" or ngoals above FRT_MAX_RIG_GOALS, null goals with ngoals > 0,
+// an unknown kind, reserved != 0, a node (the caller's number, mapped through `place`) out of range, a mid that is not a strict descendant of root,
+// a tip that is not a strict descendant of mid, an AIM axis that is not finite or is zero, AIM mid or tip != 0. The count is checked before the
+// array is read. `stored` takes the goals with the block's node indices.
+std::string check_rig_goals(uint32_t ngoals, const frt_rig_goal* goals, const std::vector<uint32_t>& place, const uint32_t* enter, const uint32_t* exit, std::vector<frt_rig_goal>& stored);
+// Host targets where they enter: "" or a count that is not `bound` (the goals they are for, `goals` [bound]), null targets with a count > 0, a word
+// that is not finite, a weight outside [0, 1], a pole flag other than 0 or 1, a pole on an AIM record. The count is checked before the array is read.
+std::string check_rig_goal_targets(uint32_t ngoals, const frt_rig_goal_target* targets, uint32_t bound, const frt_rig_goal* goals);
 }

@@ -238,6 +238,10 @@ struct RemoveState {
 // frt_renderer_set_rig_masks ("Layering clips") leaves either kind `masks` = [nmasks][nnodes] floats in the block's node order, allocated once for
 // FRT_MAX_RIG_MASKS masks so that a later set is a copy in stream order and nothing else; `place` (the caller's node index -> the block's) and `nnodes`
 // are the rig's, kept from bind time.
+// frt_renderer_set_rig_goals / _set_rig_goal_targets ("Inverse kinematics") leave either kind `goals` = [FRT_MAX_RIG_GOALS frt_rig_goal with stored node
+// indices | enter [nnodes] | exit [nnodes]] and `goal_targets` = [FRT_MAX_RIG_GOALS frt_rig_goal_target], allocated at the first set with a goal and
+// freed with the binding; `enter` / `exit` (the pre-order numbers of the stored nodes, from bind time) and `goal_defs` (the host's copy of the definitions: what host targets are
+// checked against) stay on the host.
 enum { kRigMeshes = 0, kRigInstances = 1 };
 struct RigBinding {
     OwnedBuf rig, palette, weights;
@@ -251,7 +255,11 @@ struct RigBinding {
     OwnedBuf masks;
     uint32_t nmasks = 0, nnodes = 0;
     std::vector<uint32_t> place;
-    void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats, &masks}) b->release(r); }
+    OwnedBuf goals, goal_targets;
+    uint32_t ngoals = 0;
+    std::vector<uint32_t> enter, exit;
+    std::vector<frt_rig_goal> goal_defs;
+    void release(frt_renderer* r) { for (OwnedBuf* b : {&rig, &palette, &weights, &ids, &tab, &mats, &masks, &goals, &goal_targets}) b->release(r); }
 };
 // What frt_renderer_animate_cast adds ("Animating a cast"): one device buffer, grown on demand and never shrunk, that holds what the halves of a call
 // read as ONE range each — [ids of every instance entry | their matrices | the palettes of every mesh entry | their weights] — beside the bindings' own
@@ -380,6 +388,7 @@ enum { kNotFailed = 1, kBetweenFrames = 2, kRefit = 4, kQuadTree = 8, kEditCheck
 int check_entry(const frt_renderer* r, const std::string& what, unsigned parts);
 uint32_t pool_count(const frt_renderer* r, int pool);             // elements of a pool (PoolState) in use
 int ensure_normals(frt_renderer* r);                              // PoolState::d_normals exists afterwards
+int check_device_block(const frt_renderer* r, const void* p, size_t bytes, size_t align, const char* call, const char* what, const char* flag);      // frt_scene_edit.hip: its check_device_input, for the other files
 int apply_cast(frt_renderer* r, const CastApply& c);              // frt_scene_edit.hip: the two halves of frt_renderer_animate_cast in one call frame
 // "" when the batch (check_pose_batch) and then every mesh of it, as its single call checks it ("mesh N: ..."), can be posed: with `skin` under a palette of
 // `njoints` joints, with `morph` under `ntargets` weights. host_memory: the entries of the palette and of the weights, the same for every mesh, are read

@@ -875,6 +875,8 @@ int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* j
 }
 
 } // extern "C"
+// check_device_input for the other files of the library (frt_renderer_state.hpp).
+int frt::check_device_block(const frt_renderer* r, const void* p, size_t bytes, size_t align, const char* call, const char* what, const char* flag) { return check_device_input(r, p, bytes, align, call, what, flag); }
 // frt_renderer_animate_cast (frt_animation.hip; DESIGN.md §11, "Animating a cast") behind its checks and its rig launch: one call frame, so the
 // speculation is dropped once; the matrix table current; the instance half as one device-input transform; the mesh half as one pose batch that reads
 // the table (the mirror, stale from the first half on, is not read back: no wait for the stream); then, if either wrote a triangle, one scene extent

@@ -122,6 +122,20 @@ class CastLayersEntry(C.Structure):                 # include/frt.h: frt_cast_la
     _fields_ = [("binding", C.c_uint32), ("first_layer", C.c_uint32), ("num_layers", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+MAX_RIG_GOALS = 16                                  # include/frt.h: FRT_MAX_RIG_GOALS
+GOAL_KINDS = {"two_bone": 0, "aim": 1}              # include/frt.h: FRT_GOAL_*
+GOAL_TARGETS_DEVICE = 1                             # include/frt.h: FRT_GOAL_TARGETS_DEVICE
+IK_PLANE_EPS, IK_ARC_EPS = 1e-12, 1e-6              # include/frt.h: FRT_IK_PLANE_EPS, FRT_IK_ARC_EPS (float32 constants of the contract)
+
+
+class RigGoal(C.Structure):                         # include/frt.h: frt_rig_goal
+    _fields_ = [("kind", C.c_uint32), ("root", C.c_uint32), ("mid", C.c_uint32), ("tip", C.c_uint32), ("axis", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class RigGoalTarget(C.Structure):                   # include/frt.h: frt_rig_goal_target
+    _fields_ = [("target", C.c_float * 3), ("weight", C.c_float), ("pole", C.c_float * 3), ("pole_flag", C.c_float)]
+
+
 RIG_PATHS = {"translation": 0, "rotation": 1, "scale": 2, "weights": 3}      # include/frt.h: FRT_RIG_PATH_*
 RIG_INTERPOLATIONS = {"STEP": 0, "LINEAR": 1, "CUBICSPLINE": 2}              # include/frt.h: FRT_RIG_*
 PHASE_GBUFFER, PHASE_TEMPORAL, PHASE_SPATIAL, PHASE_POST, PHASE_ALL = 1, 2, 4, 8, 15
@@ -265,6 +279,10 @@ SYMBOLS = {
     "frt_rig_evaluate_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _P, _P]),
     "frt_rig_evaluate_nodes_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _P, _P, _P, _P]),
     "frt_renderer_set_rig_masks": (C.c_int, [_P, _U32, _U32, _P]),
+    "frt_rig_evaluate_layers_ik": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _P, _P, _P, _P]),
+    "frt_rig_evaluate_nodes_layers_ik": (C.c_int, [_P, _U32, _P, _U32, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]),
+    "frt_renderer_set_rig_goals": (C.c_int, [_P, _U32, _U32, _P]),
+    "frt_renderer_set_rig_goal_targets": (C.c_int, [_P, _U32, _U32, _P, _U32]),
     "frt_renderer_animate_layers": (C.c_int, [_P, _U32, _U32, _P, _U32]),
     "frt_renderer_animate_instances_layers": (C.c_int, [_P, _U32, _U32, _P]),
     "frt_renderer_animate_cast_layers": (C.c_int, [_P, _U32, _P, _U32, _P, _U32]),

@@ -220,28 +220,105 @@ class Rig:
             m = m[None, :]
         return m.shape[0], _f32(m, (m.shape[0], self.num_nodes), "masks")
 
-    def evaluate_layers(self, layers, masks=None):
+    # ---- inverse kinematics (include/frt.h: frt_rig_evaluate_layers_ik; DESIGN.md section 11, "Inverse kinematics")
+    def _goal_rows(self, goals):
+        """(n, frt_rig_goal [n] or None) of `goals`: None, or an iterable of frt.TwoBone and frt.Aim with the node numbers the rig was described with."""
+        from ._lib import RigGoal, GOAL_KINDS
+        rows = []
+        for k, g in enumerate(goals if goals is not None else ()):
+            if isinstance(g, TwoBone):
+                nodes, kind, axis = (g.root, g.mid, g.tip), GOAL_KINDS["two_bone"], (0.0, 0.0, 0.0)
+            elif isinstance(g, Aim):
+                axis = tuple(float(x) for x in g.axis)
+                if len(axis) != 3:
+                    raise FrtError(f"Rig: goal {k}: an axis has three components")
+                nodes, kind = (g.node, 0, 0), GOAL_KINDS["aim"]
+            else:
+                raise FrtError(f"Rig: goal {k} is neither a frt.TwoBone nor a frt.Aim")
+            if not all(0 <= int(x) <= 0xFFFFFFFF for x in nodes):
+                raise FrtError(f"Rig: goal {k}: nodes are unsigned 32-bit indices")
+            rows.append(RigGoal(kind, int(nodes[0]), int(nodes[1]), int(nodes[2]), (C.c_float * 3)(*axis), 0))
+        return len(rows), ((RigGoal * len(rows))(*rows) if rows else None)
+
+    def _goal_args(self, goals, targets):
+        """(n, frt_rig_goal [n] or None, float32 [n, 8] or None): `targets` rows are (target xyz, weight, pole xyz, pole flag), one per goal."""
+        n, table = self._goal_rows(goals)
+        if targets is None:
+            if n:
+                raise FrtError("Rig: goals need targets, float32 [G, 8] rows of (target xyz, weight, pole xyz, pole flag)")
+            return 0, None, None
+        t = goal_target_rows(targets)
+        if t.shape[0] != n:
+            raise FrtError(f"Rig: {t.shape[0]} targets for {n} goals")
+        return n, table, (t if n else None)
+
+    def evaluate_layers(self, layers, masks=None, goals=None, targets=None):
         """evaluate() of a stack of layers (frt.Layer, or (clip, t, weight) for a blend layer), 1 to MAX_LAYERS of them, folded in order into one
         running pose per node. The first is the base: a blend layer without a mask and with a positive weight. A later layer acts by its weight
         times its mask's value at the node: "blend" mixes as evaluate_blend does, "override" replaces by that much (weight <= 1), "additive" adds
-        that much of (clip at t) - (reference). masks: [nmasks, num_nodes] values in [0, 1] (Rig.mask), which Layer.mask names by index."""
+        that much of (clip at t) - (reference). masks: [nmasks, num_nodes] values in [0, 1] (Rig.mask), which Layer.mask names by index.
+        goals (frt.TwoBone, frt.Aim; at most MAX_RIG_GOALS) and targets ([G, 8] float32 rows of target xyz, weight, pole xyz, pole flag) act on
+        the layered pose's global matrices in the rig's model space, in list order (frt_rig_evaluate_layers_ik); without goals the plain call."""
         pal = np.zeros((self.num_joints, 16), np.float32) if self.num_joints else None
         w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
         n, table = layer_table(self._layer_rows(layers))
         nm, m = self._mask_args(masks)
-        check(lib().frt_rig_evaluate_layers(self._h, n, table, nm, m.ctypes.data if m is not None else None, pal.ctypes.data if pal is not None else None,
-                                            w.ctypes.data if w is not None else None))
+        ng, gtable, t = self._goal_args(goals, targets)
+        out = (pal.ctypes.data if pal is not None else None, w.ctypes.data if w is not None else None)
+        if ng:
+            check(lib().frt_rig_evaluate_layers_ik(self._h, n, table, nm, m.ctypes.data if m is not None else None, ng, gtable, t.ctypes.data, *out))
+        else:
+            check(lib().frt_rig_evaluate_layers(self._h, n, table, nm, m.ctypes.data if m is not None else None, *out))
         return pal, w
 
-    def evaluate_nodes_layers(self, layers, nodes, root=None, offsets=None, masks=None):
-        """evaluate_nodes() of a stack of layers (as evaluate_layers takes them): the matrices Renderer.animate_instances_layers gives the instances."""
+    def evaluate_nodes_layers(self, layers, nodes, root=None, offsets=None, masks=None, goals=None, targets=None):
+        """evaluate_nodes() of a stack of layers (as evaluate_layers takes them, goals and targets included): the matrices
+        Renderer.animate_instances_layers gives the instances. Goals act in the rig's model space, in front of root and offsets."""
         n, nodes, root, offsets = node_args(nodes, root, offsets)
         out = np.zeros((n, 16), np.float32)
         nl, table = layer_table(self._layer_rows(layers))
         nm, m = self._mask_args(masks)
-        check(lib().frt_rig_evaluate_nodes_layers(self._h, nl, table, nm, m.ctypes.data if m is not None else None, n, nodes.ctypes.data,
-                                                  root.ctypes.data if root is not None else None, offsets.ctypes.data if offsets is not None else None, out.ctypes.data))
+        ng, gtable, t = self._goal_args(goals, targets)
+        tail = (n, nodes.ctypes.data, root.ctypes.data if root is not None else None, offsets.ctypes.data if offsets is not None else None, out.ctypes.data)
+        if ng:
+            check(lib().frt_rig_evaluate_nodes_layers_ik(self._h, nl, table, nm, m.ctypes.data if m is not None else None, ng, gtable, t.ctypes.data, *tail))
+        else:
+            check(lib().frt_rig_evaluate_nodes_layers(self._h, nl, table, nm, m.ctypes.data if m is not None else None, *tail))
         return out
+
+
+class TwoBone:
+    """A two-bone goal (include/frt.h: FRT_GOAL_TWO_BONE): the limb root -> mid -> tip (mid below root, tip below mid; nodes between them are carried
+    rigidly) is bent at mid so that tip's origin reaches the goal's target; its target row may carry a pole point the bend faces."""
+
+    def __init__(self, root, mid, tip):
+        self.root, self.mid, self.tip = root, mid, tip
+
+    def __repr__(self):
+        return f"TwoBone({self.root!r}, {self.mid!r}, {self.tip!r})"
+
+
+class Aim:
+    """An aim goal (include/frt.h: FRT_GOAL_AIM): `node` and everything below it is turned about the node's origin so that its local direction
+    `axis` points at the goal's target, by the target's weight of the way."""
+
+    def __init__(self, node, axis=(0, 0, 1)):
+        self.node, self.axis = node, tuple(axis)
+
+    def __repr__(self):
+        return f"Aim({self.node!r}, axis={self.axis!r})"
+
+
+def goal_target_rows(targets):
+    """float32 [G, 8] of `targets`: rows of (target xyz, weight, pole xyz, pole flag)."""
+    t = np.ascontiguousarray(targets, np.float32)
+    if t.size == 0:
+        t = t.reshape(0, 8)
+    if t.ndim == 1 and t.size == 8:
+        t = t[None, :]
+    if t.ndim != 2 or t.shape[1] != 8:
+        raise FrtError(f"goal targets must be shaped [G, 8] (target xyz, weight, pole xyz, pole flag), not {list(t.shape)}")
+    return t
 
 
 class Layer:
@@ -343,7 +420,8 @@ def host_cast_layers(target, entries, normals="recompute"):
     """host_cast for layers ("Layering clips"): what SceneBuilder.animate_cast_layers and MultiRenderer.animate_cast_layers do.
     Every entry is the arguments of `target`'s animate_layers, (rig, mesh_ids, layers[, masks]), or of its animate_instances_layers,
     (rig, instance_ids, nodes, layers, masks[, root[, offsets]]) with masks possibly None, as a tuple or as a dict by name (a dict with "nodes" is
-    an instance entry). The instance entries are applied first, in the order given, then the mesh entries."""
+    an instance entry). The instance entries are applied first, in the order given, then the mesh entries. Goals ("Inverse kinematics"): a dict
+    entry of either kind may carry "goals" and "targets"; an instance tuple takes them as its eighth and ninth field."""
     inst, mesh = [], []
     for k, e in enumerate(entries):
         if isinstance(e, dict):
@@ -355,10 +433,10 @@ def host_cast_layers(target, entries, normals="recompute"):
                 raise FrtError(f"animate_cast_layers: entry {k} has four fields and the third is a list of node numbers, not of layers: an instance "
                                "entry is (rig, instance_ids, nodes, layers, masks[, root[, offsets]]), with masks None when it has none")
             mesh.append(dict(zip(("rig", "mesh_ids", "layers", "masks"), e)))
-        elif 5 <= len(e) <= 7:
-            inst.append(dict(zip(("rig", "instance_ids", "nodes", "layers", "masks", "root", "offsets"), e)))
+        elif 5 <= len(e) <= 9:
+            inst.append(dict(zip(("rig", "instance_ids", "nodes", "layers", "masks", "root", "offsets", "goals", "targets"), e)))
         else:
-            raise FrtError(f"animate_cast_layers: entry {k} has {len(e)} fields (3 or 4: a mesh entry, 5 to 7: an instance entry)")
+            raise FrtError(f"animate_cast_layers: entry {k} has {len(e)} fields (3 or 4: a mesh entry, 5 to 9: an instance entry)")
     if not inst and not mesh:
         raise FrtError("animate_cast_layers: no entries")
     for e in inst:

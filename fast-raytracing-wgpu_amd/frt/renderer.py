@@ -488,6 +488,30 @@ class Renderer(_HostQueries, _SceneGrowth):
         nm, m = self._bound_rig("set_rig_masks", binding)._mask_args(masks)
         check(lib().frt_renderer_set_rig_masks(self._h, int(binding), nm, m.ctypes.data if m is not None else None))
 
+    # ---- inverse kinematics (include/frt.h: frt_renderer_set_rig_goals, _set_rig_goal_targets; DESIGN.md section 11, "Inverse kinematics")
+    def set_rig_goals(self, binding, goals):
+        """Give a binding of either kind its goals (frt.TwoBone, frt.Aim; at most MAX_RIG_GOALS; None clears them). They replace the previous set, in
+        stream order, and do nothing until set_rig_goal_targets gives them targets. Only the _layers calls apply goals."""
+        n, table = self._bound_rig("set_rig_goals", binding)._goal_rows(goals)
+        check(lib().frt_renderer_set_rig_goals(self._h, int(binding), n, table))
+
+    def set_rig_goal_targets(self, binding, targets):
+        """The targets of the binding's goals, [G, 8] float32 rows of (target xyz, weight, pole xyz, pole flag) in the rig's model space, one per
+        goal. numpy (or array-like) in: checked and copied during the call. A contiguous float32 torch tensor on the renderer's device in (e.g.
+        built from trace_closest's device output): the protocol of the device form of set_mesh_vertices — the renderer's stream waits for the
+        caller's current stream, one device-to-device copy is enqueued, the renderer keeps a reference to the tensor until the stream has passed
+        it, nothing waits. A device row with a non-finite word or a weight outside (0, 1] makes the kernel skip that goal. Takes effect in stream
+        order."""
+        from ._lib import GOAL_TARGETS_DEVICE
+        if not _is_device_tensor(targets):
+            from .animation import goal_target_rows
+            t = goal_target_rows(targets)
+            return check(lib().frt_renderer_set_rig_goal_targets(self._h, int(binding), t.shape[0], t.ctypes.data if t.shape[0] else None, 0))
+        import torch
+        self._check_device_tensor(torch, "set_rig_goal_targets", "targets", targets, lambda t: t.dim() == 2 and t.shape[1] == 8, "[G, 8]")
+        self._device_call(torch, lambda: lib().frt_renderer_set_rig_goal_targets(self._h, int(binding), targets.shape[0], targets.data_ptr() if targets.shape[0] else None,
+                                                                                  GOAL_TARGETS_DEVICE), targets)
+
     def animate_layers(self, binding, layers, normals="recompute"):
         """animate() with a stack of layers (frt.Layer, or (clip, t, weight) for a blend layer) as Rig.evaluate_layers takes them; a layer's mask
         names one of the binding's masks (set_rig_masks). E.g. walk, and wave with the arm: [("walk", t, 1.0), Layer("wave", t, mask=0,
@@ -872,13 +896,14 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
         from .animation import host_cast_blend
         host_cast_blend(self, entries, normals)
 
-    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute"):
-        """rig.evaluate_layers(layers, masks) on the host, then set_mesh_poses on every strip's replica ("Layering clips")."""
-        self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks), normals=normals)
+    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute", goals=None, targets=None):
+        """rig.evaluate_layers(layers, masks, goals, targets) on the host, then set_mesh_poses on every strip's replica (DESIGN.md section 11,
+        "Layering clips", "Inverse kinematics"). The targets are host arrays."""
+        self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks, goals, targets), normals=normals)
 
-    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None):
+    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None, goals=None, targets=None):
         """rig.evaluate_nodes_layers on the host, then set_instance_transforms on every strip's replica."""
-        self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks))
+        self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks, goals, targets))
 
     def animate_cast_layers(self, entries, normals="recompute"):
         """The host form of Renderer.animate_cast_layers (frt.animation.host_cast_layers) on every strip's replica."""

@@ -518,11 +518,12 @@ class SceneBuilder:
 
     # Layering clips ("Layering clips"): the host forms of Renderer.animate_layers, animate_instances_layers and
     # animate_cast_layers: rig.evaluate_layers / rig.evaluate_nodes_layers on the host under `masks`, then the same host calls.
-    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute"):
-        return self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks), normals=normals)
+    # goals= and targets= ("Inverse kinematics"): frt.TwoBone / frt.Aim and their [G, 8] target rows, applied to the layered pose on the host.
+    def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute", goals=None, targets=None):
+        return self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks, goals, targets), normals=normals)
 
-    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None):
-        return self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks))
+    def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None, goals=None, targets=None):
+        return self.set_instance_transforms(instance_ids, rig.evaluate_nodes_layers(layers, nodes, root, offsets, masks, goals, targets))
 
     def animate_cast_layers(self, entries, normals="recompute"):
         from .animation import host_cast_layers

@@ -756,6 +756,55 @@ int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, c
 int frt_renderer_animate_instances_layers(frt_renderer* r, uint32_t binding, uint32_t n, const frt_clip_layer* layers);
 typedef struct frt_cast_layers_entry { uint32_t binding, first_layer, num_layers, reserved; } frt_cast_layers_entry;      /* reserved must be 0 */
 int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast_layers_entry* entries, uint32_t nlayers, const frt_clip_layer* layers, uint32_t flags);
+/* Inverse kinematics ("Inverse kinematics"): goals on a rig, behind the layers. A GOAL acts on the GLOBAL matrices of the rig,
+ * in the rig's model space: for a mesh binding the space of the palette, for an instance binding the space in front of `root` and the offsets (the
+ * caller maps world space into it). Goals act after the layers have been folded and the hierarchy walked, and before joints or instances read the
+ * globals; they are applied in list order, each seeing what the earlier ones left. 0 .. FRT_MAX_RIG_GOALS of them, of two kinds; node numbers are
+ * the caller's. The contract (csrc/frt_ik.hpp: ik_arc, ik_about, ik_two_bone, ik_aim; f32, no contraction, no fma, one text for host and kernel):
+ *   arc(u, v), unit vectors: q = (cross(u, v), 1 + dot(u, v)) * rsqrt(|q|^2); if 1 + dot < FRT_IK_ARC_EPS, the half turn about cross(u, e), e the
+ *   coordinate axis of u's smallest |component|. about(p, q): the m4 whose 3x3 is q's rotation and whose last column is p - R p.
+ *   A target record is (target xyz, weight w, pole xyz, pole flag). A goal whose record has a word that is not finite, or w outside (0, 1], is
+ *   SKIPPED: nothing is written, as if the goal were absent.
+ *   FRT_GOAL_TWO_BONE (root, mid, tip; mid a strict descendant of root, tip of mid; nodes between them are carried rigidly): A, B, C the origins
+ *   (last columns) of their globals. Te = C + w (T - C), at w == 1 T itself. lab = |B - A|, lcb = |C - B|, d = |Te - A|; skipped unless all three
+ *   are > 0. dir = (Te - A) / d, lat = min(max(d, |lab - lcb|), lab + lcb). side = P - A with a pole (flag != 0), else B - A; nrm = cross(dir, side);
+ *   unless dot(nrm, nrm) > FRT_IK_PLANE_EPS dot(side, side), a goal with a pole tries side = B - A, and one that still fails is skipped (a straight
+ *   limb without a usable pole has no bend plane). perp = cross(nrm / |nrm|, dir); c = (lab^2 + lat^2 - lcb^2) / (2 lab lat) clamped to [-1, 1],
+ *   s = sqrt(max((lat + (lcb - lab)) ((lab + lcb) - lat) (lat + (lab - lcb)) ((lab + lcb) + lat), 0)) / (2 lab lat) (the sine from the triangle's
+ *   area: sqrt(1 - c c) would lose half the digits where c = 1, and a clamped lat makes this form exactly 0); B' = A + lab (c dir + s perp), C' = A + lat dir. Da = about(A, arc(norm(B - A), norm(B' - A))), C1 = Da C,
+ *   Db = about(B', arc(norm(C1 - B'), norm(C' - B'))). Every node of subtree(mid) takes G = mul(mul(Db, Da), G), every other node of subtree(root)
+ *   G = mul(Da, G).
+ *   FRT_GOAL_AIM (root = the node, mid = tip = 0; axis: a non-zero local direction): O the origin of G[node], cur = norm(G[node]'s 3x3 * axis),
+ *   want = norm(T - O); skipped when either length is not > 0. q = arc(cur, want), for w < 1 rig_slerp((0, 0, 0, 1), q, w); every node of
+ *   subtree(node) takes G = mul(about(O, q), G). The pole words of an AIM record are 0.
+ *   FRT_IK_PLANE_EPS and FRT_IK_ARC_EPS are design constants of the contract, not measurements.
+ * frt_rig_evaluate_layers_ik / frt_rig_evaluate_nodes_layers_ik are the specification, on the host: the layered calls with goals [ngoals] and their
+ * targets [ngoals]; ngoals == 0 is the layered call bit for bit. FRT_ERR_INVALID_ARG, nothing written: what the layered call refuses; ngoals above
+ * FRT_MAX_RIG_GOALS; a null array with ngoals > 0; an unknown kind; reserved != 0; a node out of range; a mid that is not a strict descendant of
+ * root or a tip that is not one of mid; an AIM axis that is not finite or is zero, or AIM mid / tip != 0; a target word that is not finite, a
+ * weight outside [0, 1] (0: the goal is skipped), a pole flag other than 0 or 1, a non-zero pole word on an AIM record.
+ * Goals and targets are state of a binding of either kind, as masks are. frt_renderer_set_rig_goals uploads the definitions (staged, asynchronous,
+ * on the main stream), replaces the previous set (ngoals == 0 clears it) and resets every target to weight 0, so new goals do nothing until
+ * targets arrive. frt_renderer_set_rig_goal_targets is one asynchronous copy of ngoals records (ngoals: the binding's goal count) into the
+ * binding's targets: from host memory (flags 0) checked as above and staged; with FRT_GOAL_TARGETS_DEVICE from device memory of the renderer's
+ * device (16-byte aligned, ordered by the caller on the main stream or on a stream the main stream has been made to wait for, alive until the
+ * stream has passed the call), unseen by the host: the kernel then applies the skip rule above to each record, and any other pole flag than 0
+ * uses the pole. Both calls take effect in stream order, without a wait. Refused with nothing enqueued: an unknown binding, what the host form
+ * refuses of goals or host targets, a count that is not the binding's, unknown flag bits, a pointer that is not such device memory.
+ * Only frt_renderer_animate_layers / _animate_instances_layers / _animate_cast_layers apply a binding's goals (a single clip under goals is a stack
+ * of one layer): their results are the _ik host forms' bit for bit. frt_renderer_animate, _animate_blend, _animate_instances,
+ * _animate_instances_blend and the plain and blended casts ignore them. */
+#define FRT_MAX_RIG_GOALS 16u
+enum { FRT_GOAL_TWO_BONE = 0, FRT_GOAL_AIM = 1 };
+#define FRT_IK_PLANE_EPS 1e-12f
+#define FRT_IK_ARC_EPS 1e-6f
+#define FRT_GOAL_TARGETS_DEVICE 1u
+typedef struct frt_rig_goal { uint32_t kind, root, mid, tip; float axis[3]; uint32_t reserved; } frt_rig_goal;            /* 32 bytes; AIM: root = node, mid = tip = 0 */
+typedef struct frt_rig_goal_target { float target[3], weight, pole[3], pole_flag; } frt_rig_goal_target;                  /* 32 bytes; pole_flag 0 or 1 */
+int frt_rig_evaluate_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals, const frt_rig_goal_target* targets, float* joint_mats_out, float* morph_weights_out);
+int frt_rig_evaluate_nodes_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals, const frt_rig_goal_target* targets, uint32_t nnodes, const uint32_t* nodes, const float* root16, const float* offsets16n, float* mats_out16n);
+int frt_renderer_set_rig_goals(frt_renderer* r, uint32_t binding, uint32_t ngoals, const frt_rig_goal* goals);
+int frt_renderer_set_rig_goal_targets(frt_renderer* r, uint32_t binding, uint32_t ngoals, const frt_rig_goal_target* targets, uint32_t flags);
 /* Edit what this renderer's scene replica looks like between two frames: arguments, checks and results of the frt_scene_* calls
  * of the same names, bit for bit. set_materials, set_light_emission and set_texture are copies into the replica's tables (a texture: one 4 MiB
  * host-to-device copy); set_instance_materials is one kernel that stores the changed word of every affected shading and instance record. The inputs
