@@ -470,7 +470,10 @@ int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id
 }
 // Every strip binds the skin to, and poses, its own replica (frt_renderer_set_mesh_skin, frt_renderer_set_mesh_pose).
 int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
-    return edit_every_replica(m, "multi set_mesh_skin", [&](frt_renderer* r) { return frt_renderer_set_mesh_skin(r, mesh_id, joints4, weights4, nverts, njoints); });
+    return frt_multi_renderer_set_mesh_skin_ex(m, mesh_id, joints4, weights4, nverts, njoints, 0u);
+}
+int frt_multi_renderer_set_mesh_skin_ex(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags) {
+    return edit_every_replica(m, "multi set_mesh_skin", [&](frt_renderer* r) { return frt_renderer_set_mesh_skin_ex(r, mesh_id, joints4, weights4, nverts, njoints, flags); });
 }
 int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {
     if (const int rc = refuse_device_flag("set_mesh_pose", flags)) return rc;

@@ -1,7 +1,7 @@
 // frt_pose_batch.hip — kernels of every call that poses meshes: frt_renderer_set_mesh_poses, the single-mesh calls frt_renderer_set_mesh_pose(_ex) and
 // _set_mesh_morph_weights (a batch of one) and the mesh half of frt_renderer_animate_cast ("Posing several meshes"; frt_pose_batch.hpp).
 // Built with the library's contract flags (-ffp-contract=off, no fast math, IEEE division and square root). No arithmetic is written here: a vertex is
-// frt_morph.hpp's morphed_position and frt_skin.hpp's skinned_position, a normal frt_vertex_normal.hpp's recomputed_vertex_normal and frt_shade.hpp's
+// frt_morph.hpp's morphed_position and frt_skin.hpp's skinned_position or (a mesh bound with FRT_SKIN_DUAL_QUATERNION) skinned_position_dq, a normal frt_vertex_normal.hpp's recomputed_vertex_normal and frt_shade.hpp's
 // decode_octahedral_normal, a triangle frt_refit.hpp's instance_world_vertices — the functions the host specification and frt_deform.hip's kernels call.
 // The last four kernels are frt_deform.hip's (deform_validate_kernel, deform_copy_in_kernel, vertex_normal_kernel, mesh_deform_kernel) with the mesh's
 // offsets and buffers taken from the thread's segment instead of the launch arguments.
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(kPoseBlock) pose_batch_skin_kernel(PoseBatchAr
     if (g >= a.total || g >= a.scratch_len) return;
     const PoseSegment s = pose_segment_of(a.seg, a.nseg, g);
     const uint32_t v = g - s.vert_begin;
-    if (v >= s.nverts || !s.skin) return;
+    if (v >= s.nverts || !s.skin || s.skin_mode != 0u) return;      // (a segment of another mode is the dual-quaternion launch's)
     const float4* weights = reinterpret_cast<const float4*>(s.skin + 16u * (size_t)s.nverts);
     const uint2* joints = reinterpret_cast<const uint2*>(s.skin + 32u * (size_t)s.nverts);
     const float4 p = a.morphed && s.morph ? a.morphed[g] : reinterpret_cast<const float4*>(s.skin)[v], wt = weights[v];
@@ -76,6 +76,38 @@ __global__ void __launch_bounds__(kPoseBlock) pose_batch_skin_kernel(PoseBatchAr
     const float pb[4] = {p.x, p.y, p.z, p.w}, w[4] = {wt.x, wt.y, wt.z, wt.w};
     float o[4];
     skinned_position(pb, m, w, o);
+    a.skinned[g] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// Thread g: vertex g of the concatenation when its segment was bound with FRT_SKIN_DUAL_QUATERNION, from the same loads into the same store as the
+// kernel above. Each of the vertex's four joints is converted in the lane as its four columns arrive (skin_dq_of_joint: scale, rotation quaternion,
+// dual part), so one matrix is live at a time; no converted palette is staged anywhere. The palette test is this launch's when no linear launch ran in
+// front of it: launch_pose_batch leaves check_palette to exactly one of the two.
+__global__ void __launch_bounds__(kPoseBlock) pose_batch_skin_dq_kernel(PoseBatchArgs a) {
+    const uint32_t g = blockIdx.x * (uint32_t)kPoseBlock + threadIdx.x;
+    if (a.check_palette && g < a.check_cols && !pose_finite4(a.check_palette[g])) a.reject[0] = 1u;
+    if (g >= a.total || g >= a.scratch_len) return;
+    const PoseSegment s = pose_segment_of(a.seg, a.nseg, g);
+    const uint32_t v = g - s.vert_begin;
+    if (v >= s.nverts || !s.skin || s.skin_mode != FRT_SKIN_DUAL_QUATERNION) return;
+    const float4* weights = reinterpret_cast<const float4*>(s.skin + 16u * (size_t)s.nverts);
+    const uint2* joints = reinterpret_cast<const uint2*>(s.skin + 32u * (size_t)s.nverts);
+    const float4 p = a.morphed && s.morph ? a.morphed[g] : reinterpret_cast<const float4*>(s.skin)[v], wt = weights[v];
+    const uint2 jw = joints[v];
+    const uint32_t j[4] = {jw.x & 0xFFFFu, jw.x >> 16, jw.y & 0xFFFFu, jw.y >> 16};
+    if (j[0] >= s.njoints || j[1] >= s.njoints || j[2] >= s.njoints || j[3] >= s.njoints) { a.reject[0] = 1u; return; }
+    SkinDualQuat dq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4* c = s.palette + 4u * (size_t)j[k];
+        float m[16];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const float4 q = c[i]; m[4 * i] = q.x; m[4 * i + 1] = q.y; m[4 * i + 2] = q.z; m[4 * i + 3] = q.w; }
+        dq[k] = skin_dq_of_joint(m);
+    }
+    const float pb[4] = {p.x, p.y, p.z, p.w}, w[4] = {wt.x, wt.y, wt.z, wt.w};
+    float o[4];
+    skinned_position_dq(pb, dq, w, o);
     a.skinned[g] = make_float4(o[0], o[1], o[2], o[3]);
 }
 
@@ -180,7 +212,7 @@ static inline dim3 pose_grid(uint32_t threads) { return dim3((threads + kPoseBlo
 hipError_t launch_pose_batch(const SceneView& sc, const PoseBatchArgs& a, hipStream_t stream) {
     const bool morph = a.morphs != 0, skin = a.skins != 0;
     if (a.nseg == 0 || a.total == 0) return hipSuccess;
-    if (!morph && !skin) return hipErrorInvalidValue;
+    if ((!morph && !skin) || a.skins_dq > a.skins) return hipErrorInvalidValue;
     if (a.total > 0xFFFFFF00u || a.work > 0xFFFFFF00u) return hipErrorInvalidValue;      // (the work-item index is 32 bits)
     if ((a.check_palette && !skin) || (a.check_weights && !morph)) return hipErrorInvalidValue;
     if (a.check_cols > 0xFFFFFF00u || a.check_nweights > 0xFFFFFF00u) return hipErrorInvalidValue;
@@ -191,8 +223,14 @@ hipError_t launch_pose_batch(const SceneView& sc, const PoseBatchArgs& a, hipStr
         hipLaunchKernelGGL(pose_batch_morph_kernel, pose_grid(a.check_weights ? std::max(a.total, a.check_nweights) : a.total), dim3(kPoseBlock), 0, stream, a);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (skin) {
+    if (a.skins > a.skins_dq) {      // a linear skin: the launch of every call before there was a second mode
         hipLaunchKernelGGL(pose_batch_skin_kernel, pose_grid(a.check_palette ? std::max(a.total, a.check_cols) : a.total), dim3(kPoseBlock), 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (a.skins_dq) {      // the palette test runs once per call: here only when the launch above did not
+        PoseBatchArgs b = a;
+        if (a.skins > a.skins_dq) { b.check_palette = nullptr; b.check_cols = 0u; }
+        hipLaunchKernelGGL(pose_batch_skin_dq_kernel, pose_grid(b.check_palette ? std::max(b.total, b.check_cols) : b.total), dim3(kPoseBlock), 0, stream, b);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(pose_batch_validate_kernel, pose_grid(a.total), dim3(kPoseBlock), 0, stream, a);

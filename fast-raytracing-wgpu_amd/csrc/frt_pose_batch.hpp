@@ -3,7 +3,7 @@
 // _set_mesh_morph_weights are the batch of one mesh. frt_renderer_animate_cast ("Animating a cast") runs the same launches with a palette and weights of
 // its own per mesh: every segment names the ones it is posed under, and set_mesh_poses is the case where all segments name the same. The kernels are
 // segmented: a thread handles one vertex (or triangle) of the concatenation of the batch's meshes and finds its mesh in the call's segment table by a
-// binary search over prefix sums. The arithmetic is the host specification's own functions — morphed_position, skinned_position,
+// binary search over prefix sums. The arithmetic is the host specification's own functions — morphed_position, skinned_position, skinned_position_dq,
 // recomputed_vertex_normal, decode_octahedral_normal, instance_world_vertices — and every vertex and triangle is computed from its own mesh alone, so a
 // batch gives, bit for bit, what the n single calls give. The host specification is SceneBuilder::set_mesh_poses (frt_scene.cpp).
 #pragma once
@@ -27,7 +27,8 @@ struct PoseSegment {
     const float4* palette;    // [4 njoints] columns this mesh is skinned under (`skin` given), else null
     const float* weights;     // [ntargets] this mesh is morphed under (`morph` given), else null
     uint32_t njoints, ntargets;
-    uint32_t pad[2];          // (16-byte loads: the record is a multiple of 16 bytes)
+    uint32_t skin_mode;       // how `skin` is posed: 0 the linear blend, FRT_SKIN_DUAL_QUATERNION (the mode the mesh was bound with)
+    uint32_t pad;             // (16-byte loads: the record is a multiple of 16 bytes)
 };
 static_assert(sizeof(PoseSegment) == 80 && sizeof(PoseSegment) % 16 == 0, "PoseSegment layout");
 
@@ -36,8 +37,9 @@ static_assert(sizeof(PoseSegment) == 80 && sizeof(PoseSegment) % 16 == 0, "PoseS
 // segment up. `total`: the summed vertex counts; no thread stores at or past `scratch_len` in a scratch or at or past a pool's capacity.
 struct PoseBatchArgs {
     const PoseSegment* seg; uint32_t nseg, total;
-    uint32_t skins, morphs;   // a segment has a skin / morph targets: the skin launch / the morph launch runs
-    // Device memory the host has not seen, tested by the skin launch and the morph launch: ONE range each per call, which holds every palette (weight
+    uint32_t skins, morphs;   // segments with a skin / with morph targets: a skin launch / the morph launch runs
+    uint32_t skins_dq;        // of `skins`, those bound with FRT_SKIN_DUAL_QUATERNION: the dual-quaternion launch runs; fewer than `skins`: the linear one
+    // Device memory the host has not seen, tested by the first skin launch of the call and the morph launch: ONE range each per call, which holds every palette (weight
     // vector) a segment names. check_palette [check_cols] float4, check_weights [check_nweights]; null: the values came from the host, which checked them.
     const float4* check_palette; uint32_t check_cols;
     const float* check_weights; uint32_t check_nweights;
@@ -57,7 +59,8 @@ struct PoseBatchArgs {
     const float4* inst_m; uint32_t num_inst;
 };
 
-// Zeroes the flag, then the morph launch and/or the skin launch (`morphs`, `skins`; a segment with both is morphed into `morphed`, which its skin reads),
+// Zeroes the flag, then the morph launch and/or the skin launches (`morphs`, `skins`; a segment with both is morphed into `morphed`, which its skin
+// reads): the linear launch when a skinned segment is linear, the dual-quaternion launch when one is not, each over the segments of its own mode,
 // the validation launch over `skinned`, the copy-in launch into `out_pos`, the normal launch (when `block` is given) and the triangle launch (when there
 // is work). The scene-extent pass and the refit follow in the caller, once.
 hipError_t launch_pose_batch(const SceneView& sc, const PoseBatchArgs& a, hipStream_t stream);

@@ -160,7 +160,8 @@ struct RefitState {
     uint32_t* d_reject = nullptr;
     // What a bind call leaves with a mesh: one device buffer and how many joints or targets it was bound with (0: nothing bound). The lists may be
     // shorter than the mesh list; remove_meshes frees a leaving mesh's bindings and renumbers the rest.
-    struct MeshBinding { OwnedBuf buf; uint32_t count = 0; };
+    // `mode`: of a skin, how it is posed (0 the linear blend, FRT_SKIN_DUAL_QUATERNION); it travels with the binding wherever that goes.
+    struct MeshBinding { OwnedBuf buf; uint32_t count = 0, mode = 0; };
     // frt_renderer_set_mesh_skin / _set_mesh_pose ("Skinning"): a skin is [bind positions 16 nverts | weights 16 nverts | joints 8 nverts], `count` its
     // joints. `skin_up`: the pinned block a bind call's weights and joints go through. `skinned`: the posed positions of the posing call in flight, a single
     // mesh's or a batch's ("Posing several meshes"), [the summed vertex counts] float4, whatever launch wrote them last.

@@ -463,8 +463,9 @@ std::string check_mesh_pose(const float* joint_mats, uint32_t njoints, uint32_t 
     for (size_t k = 0; host_memory && k < (size_t)njoints * 16; ++k) if (!std::isfinite(joint_mats[k])) return "joint matrix " + std::to_string(k / 16) + " has a non-finite entry";
     return "";
 }
-int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t skin_flags) {
     if (const int rc = check_mesh_call("set_mesh_skin", "", mesh_id, 0u)) return rc;
+    if (skin_flags & ~FRT_SKIN_DUAL_QUATERNION) { error = "set_mesh_skin: unknown flag bits"; return FRT_ERR_INVALID_ARG; }
     if (!joints4) {
         if (mesh_id < mesh_skins.size()) mesh_skins[mesh_id] = MeshSkin();
         return FRT_OK;
@@ -473,7 +474,7 @@ int SceneBuilder::set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const
     if (!bad.empty()) { error = "set_mesh_skin: " + bad; return FRT_ERR_INVALID_ARG; }
     if (mesh_skins.size() <= mesh_id) mesh_skins.resize((size_t)mesh_id + 1u);
     MeshSkin& k = mesh_skins[mesh_id];
-    k.njoints = njoints;
+    k.njoints = njoints; k.mode = skin_flags;
     k.joints.assign(joints4, joints4 + (size_t)nverts * 4);
     k.weights.assign(weights4, weights4 + (size_t)nverts * 4);
     k.bind = mesh_positions[mesh_id];
@@ -536,6 +537,12 @@ static std::string skin_mesh(const SceneBuilder::MeshSkin& k, const std::vector<
     const uint32_t nverts = (uint32_t)(bind.size() / 4);
     skinned.resize(bind.size());
     for (uint32_t v = 0; v < nverts; ++v) {
+        if (k.mode == FRT_SKIN_DUAL_QUATERNION) {      // each of the vertex's joints converted where it is named, as the kernel's lane converts it
+            SkinDualQuat dq[4];
+            for (int s = 0; s < 4; ++s) dq[s] = skin_dq_of_joint(joint_mats + 16 * (size_t)k.joints[4 * (size_t)v + s]);
+            skinned_position_dq(&bind[4 * (size_t)v], dq, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);
+            continue;
+        }
         float m[4][16];
         for (int s = 0; s < 4; ++s) memcpy(m[s], joint_mats + 16 * (size_t)k.joints[4 * (size_t)v + s], sizeof(m[s]));
         skinned_position(&bind[4 * (size_t)v], m, &k.weights[4 * (size_t)v], &skinned[4 * (size_t)v]);

@@ -106,7 +106,9 @@ public:
     // mesh's object-space positions as they are at the call are copied and become the bind pose. No vertex and no triangle changes. joints4 == nullptr
     // removes the skin. Refused, with nothing changed (check_mesh_skin): a vertex count that is not the mesh's, njoints == 0 or above 65,536 (a joint
     // index is 16 bits), a joint index >= njoints, a weight that is negative or not finite.
-    int set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+    // `skin_flags`: the mode the mesh is posed in from then on, 0 (the linear blend) or FRT_SKIN_DUAL_QUATERNION ("Dual-quaternion
+    // skinning": frt_skin.hpp's skinned_position_dq); any other bit is refused. Binding again replaces the mode with the skin.
+    int set_mesh_skin(uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t skin_flags = 0);
     // Every vertex of the bind pose through frt_skin.hpp's skinned_position under the palette `joint_mats` (njoints column-major 4x4), then
     // set_mesh_vertices(mesh_id, skinned, nullptr, nverts, flags). Refused, with nothing changed: a mesh without a skin, njoints that is not the bound
     // count, a matrix entry or a skinned coordinate that is not finite, FRT_DEFORM_DEVICE, an unknown flag bit. A set_mesh_vertices on a skinned mesh
@@ -173,7 +175,7 @@ public:
     std::vector<uint32_t> mesh_index_counts;
     std::vector<InstanceRec> instances;
     // Per mesh its skin (set_mesh_skin); njoints == 0: none. Shorter than the mesh list while the last meshes have none.
-    struct MeshSkin { uint32_t njoints = 0; std::vector<uint16_t> joints; std::vector<float> weights, bind; };
+    struct MeshSkin { uint32_t njoints = 0, mode = 0; std::vector<uint16_t> joints; std::vector<float> weights, bind; };
     std::vector<MeshSkin> mesh_skins;
     // Per mesh its morph targets (set_mesh_morph_targets); ntargets == 0: none. Shorter than the mesh list while the last meshes have none.
     struct MeshMorph { uint32_t ntargets = 0; std::vector<float> deltas, base; };      // deltas [ntargets][nverts][3], base [nverts][4]

@@ -104,8 +104,11 @@ int frt_scene_set_mesh_vertices(frt_scene* s, uint32_t mesh_id, const float* pos
     return frt_scene_set_mesh_vertices_ex(s, mesh_id, pos4, attrs, nverts, 0u);
 }
 int frt_scene_set_mesh_skin(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    return frt_scene_set_mesh_skin_ex(s, mesh_id, joints4, weights4, nverts, njoints, 0u);
+}
+int frt_scene_set_mesh_skin_ex(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags) {
     if (!s) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: null");
-    const int rc = s->b.set_mesh_skin(mesh_id, joints4, weights4, nverts, njoints);
+    const int rc = s->b.set_mesh_skin(mesh_id, joints4, weights4, nverts, njoints, flags);
     return rc ? fail(rc, s->b.error) : FRT_OK;
 }
 int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags) {

@@ -678,16 +678,23 @@ static int bind_to_mesh(frt_renderer* r, const char* call, std::vector<RefitStat
     return FRT_OK;
 }
 // Skinning: [bind positions | weights | joints]. The speculation is kept: nothing a frame reads changes.
-int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+// `flags`: the mode the mesh is posed in (0, FRT_SKIN_DUAL_QUATERNION), kept beside the binding: the buffer is the same in either mode.
+int frt_renderer_set_mesh_skin_ex(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags) {
     if (const int rc = check_mesh_call(r, "set_mesh_skin", mesh_id, 0u, 0u)) return rc;
+    if (flags & ~FRT_SKIN_DUAL_QUATERNION) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: unknown flag bits");
     if (joints4) {
         const std::string bad = check_mesh_skin(joints4, weights4, nverts, njoints, r->rf.vert_count[mesh_id]);
         if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "set_mesh_skin: " + bad);
     }
     return edit_frame(r, false, [&]() -> int {
         if (!joints4) return drop_binding(r, r->rf.skins, mesh_id);
-        return bind_to_mesh(r, "set_mesh_skin", r->rf.skins, r->rf.skin_up, mesh_id, nverts, {{weights4, (size_t)nverts * 16}, {joints4, (size_t)nverts * 8}}, njoints);
+        if (const int rc = bind_to_mesh(r, "set_mesh_skin", r->rf.skins, r->rf.skin_up, mesh_id, nverts, {{weights4, (size_t)nverts * 16}, {joints4, (size_t)nverts * 8}}, njoints)) return rc;
+        r->rf.skins[mesh_id].mode = flags;
+        return FRT_OK;
     });
+}
+int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints) {
+    return frt_renderer_set_mesh_skin_ex(r, mesh_id, joints4, weights4, nverts, njoints, 0u);
 }
 // Morph targets: [base positions | deltas], the deltas in the caller's layout (target-major). The speculation is kept, as above.
 int frt_renderer_set_mesh_morph_targets(frt_renderer* r, uint32_t mesh_id, const float* deltas3, uint32_t nverts, uint32_t ntargets) {
@@ -752,7 +759,8 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
     std::vector<PoseSegment> seg(c.n);
     std::vector<int> seg_of_mesh(f.vert_count.size(), -1);
     uint64_t total = 0;
-    bool any_skin = false, any_morph = false;
+    uint32_t skins = 0, skins_dq = 0;
+    bool any_morph = false;
     for (uint32_t k = 0; k < c.n; ++k) {
         const uint32_t m = c.mesh(k);
         if ((uint64_t)f.pos_offset[m] + f.vert_count[m] > cap_verts || (uint64_t)f.attr_offset[m] + f.vert_count[m] > cap_verts)
@@ -768,10 +776,12 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
         s.morph = morph ? static_cast<const uint8_t*>(f.morphs[m].buf.p) : nullptr;
         s.adj = c.recompute ? f.adj[m] : nullptr;
         s.njoints = skin ? (c.per_mesh ? c.per_mesh[k].njoints : c.njoints) : 0u;
+        s.skin_mode = skin ? f.skins[m].mode : 0u;      // the mode the mesh was bound with (set_mesh_skin_ex)
         s.ntargets = morph ? (c.per_mesh ? c.per_mesh[k].ntargets : c.ntargets) : 0u;
         s.palette = c.per_mesh ? reinterpret_cast<const float4*>(c.per_mesh[k].palette) : nullptr;      // (a batch under one palette: set below, once its place is known)
         s.weights = c.per_mesh ? c.per_mesh[k].weights : nullptr;
-        any_skin = any_skin || skin; any_morph = any_morph || morph;
+        if (skin) { ++skins; if (s.skin_mode == FRT_SKIN_DUAL_QUATERNION) ++skins_dq; }
+        any_morph = any_morph || morph;
         seg_of_mesh[m] = (int)k;
         total += s.nverts;
         if (total > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, call + ": more than 2^32 - 256 vertices in one call");
@@ -790,6 +800,7 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
     }
     if (work > 0xFFFFFF00ull) return fail(FRT_ERR_INVALID_ARG, call + ": more than 2^32 - 256 triangles in one call");
     if ((rc = f.skinned.ensure(r, (size_t)total * 16))) return rc;
+    const bool any_skin = skins != 0;
     if (any_skin && any_morph && (rc = f.morphed.ensure(r, (size_t)total * 16))) return rc;
     if ((rc = ensure_reject_words(r, f.d_reject))) return rc;
     const PoseBatchLayout l(c.n, rec.size(), c.palette && !c.on_device ? (size_t)c.njoints * 64 : 0, c.weights && !c.on_device ? (size_t)c.ntargets * 4 : 0,
@@ -810,7 +821,7 @@ static int pose_meshes_body(frt_renderer* r, const PoseBatchCall& c, bool& chang
     PoseBatchArgs a;
     memset(&a, 0, sizeof(a));
     a.seg = reinterpret_cast<const PoseSegment*>(d + l.seg.off); a.nseg = c.n; a.total = (uint32_t)total;
-    a.skins = any_skin ? 1u : 0u; a.morphs = any_morph ? 1u : 0u;
+    a.skins = skins; a.skins_dq = skins_dq; a.morphs = any_morph ? 1u : 0u;
     if (palette && c.on_device) { a.check_palette = palette; a.check_cols = c.per_mesh ? c.check_cols : 4u * c.njoints; }
     if (weights && c.on_device) { a.check_weights = weights; a.check_nweights = c.per_mesh ? c.check_nweights : c.ntargets; }
     a.morphed = any_skin && any_morph ? f.morphed.as<float4>() : nullptr;

@@ -187,6 +187,7 @@ SYMBOLS = {
     "frt_scene_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_scene_set_mesh_vertices_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
     "frt_scene_set_mesh_skin": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
+    "frt_scene_set_mesh_skin_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32, _U32]),
     "frt_scene_set_mesh_pose": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_scene_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_scene_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),
@@ -237,6 +238,7 @@ SYMBOLS = {
     "frt_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_renderer_set_mesh_vertices_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
     "frt_renderer_set_mesh_skin": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
+    "frt_renderer_set_mesh_skin_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32, _U32]),
     "frt_renderer_set_mesh_pose": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_renderer_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_renderer_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),
@@ -332,6 +334,7 @@ SYMBOLS = {
     "frt_multi_renderer_set_mesh_vertices": (C.c_int, [_P, _U32, _P, _P, _U32]),
     "frt_multi_renderer_set_mesh_vertices_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
     "frt_multi_renderer_set_mesh_skin": (C.c_int, [_P, _U32, _P, _P, _U32, _U32]),
+    "frt_multi_renderer_set_mesh_skin_ex": (C.c_int, [_P, _U32, _P, _P, _U32, _U32, _U32]),
     "frt_multi_renderer_set_mesh_pose": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_multi_renderer_set_mesh_morph_targets": (C.c_int, [_P, _U32, _P, _U32, _U32]),
     "frt_multi_renderer_set_mesh_morph_weights": (C.c_int, [_P, _U32, _P, _U32, _U32]),

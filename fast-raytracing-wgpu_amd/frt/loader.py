@@ -139,17 +139,18 @@ class Model:
         return rig
 
 
-def bind_character(target, model, mesh_ids):
+def bind_character(target, model, mesh_ids, skin_mode="linear"):
     """Bind what `model` holds for each of its geometries to the mesh it became: set_mesh_morph_targets for a geometry with targets, set_mesh_skin (with
     its skin's joint count) for one with skin attributes. `target`: a built scene, a Renderer or a MultiRenderer; mesh_ids[g]: the mesh id of geometry g
-    (what add_gltf_meshes / add_meshes returned). Returns the mesh ids that got a binding."""
+    (what add_gltf_meshes / add_meshes returned); skin_mode: set_mesh_skin's `mode` for every skin bound here ("linear" or "dual_quaternion"). Returns
+    the mesh ids that got a binding."""
     bound = []
     for g, mesh in enumerate(mesh_ids):
         targets, skin = model.morph_targets(g), model.skin(g)
         if targets is not None:
             target.set_mesh_morph_targets(int(mesh), targets[0])
         if skin is not None and skin[2] is not None:
-            target.set_mesh_skin(int(mesh), skin[0], skin[1], num_joints=len(model.skin_joints(skin[2])[0]))
+            target.set_mesh_skin(int(mesh), skin[0], skin[1], num_joints=len(model.skin_joints(skin[2])[0]), mode=skin_mode)
         if targets is not None or (skin is not None and skin[2] is not None):
             bound.append(int(mesh))
     return bound

@@ -320,11 +320,12 @@ class Renderer(_HostQueries, _SceneGrowth):
         self._device_call(torch, lambda: lib().frt_renderer_set_mesh_vertices_ex(self._h, mid, positions.data_ptr(), attributes.data_ptr() if attributes is not None else None,
                                                                                   positions.shape[0], flags), positions, attributes)
 
-    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None, mode="linear"):
         """Bind a skin to one mesh of this renderer's scene replica (include/frt.h: frt_renderer_set_mesh_skin): `joints` [n, 4] integers, `weights`
         [n, 4] float32, copied during the call; the replica's positions of the mesh, as the renderer's stream finds them, become the bind pose.
-        joints=None removes the skin; num_joints defaults to the largest joint index + 1. The host scene is not changed."""
-        set_mesh_skin_call("frt_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+        joints=None removes the skin; num_joints defaults to the largest joint index + 1. mode: "linear", or "dual_quaternion" (frt_renderer_set_mesh_skin_ex,
+        FRT_SKIN_DUAL_QUATERNION): every later pose of the mesh blends its joints as rigid transforms. The host scene is not changed."""
+        set_mesh_skin_call("frt_renderer_set_mesh_skin",self._h, mesh_id, joints, weights, _num_joints(joints, num_joints), mode)
 
     def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
         """Pose a skinned mesh of this renderer's scene replica between frames (include/frt.h: frt_renderer_set_mesh_pose): one column-major 4x4 per
@@ -853,9 +854,9 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
             raise FrtError("set_mesh_vertices: a MultiRenderer takes host arrays only (its replicas live on different devices)")
         set_mesh_vertices_call("frt_multi_renderer_set_mesh_vertices", self._h, mesh_id, positions, attributes, normals)
 
-    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None, mode="linear"):
         """Renderer.set_mesh_skin on every strip's scene replica."""
-        set_mesh_skin_call("frt_multi_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+        set_mesh_skin_call("frt_multi_renderer_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints), mode)
 
     def set_mesh_pose(self, mesh_id, joint_matrices, normals="recompute", morph_weights=None):
         """Renderer.set_mesh_pose on every strip's scene replica. Host arrays only: the strips' replicas live on different devices."""

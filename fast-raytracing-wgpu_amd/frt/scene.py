@@ -83,11 +83,19 @@ def _num_joints(joints, num_joints):
     return int(j.max()) + 1 if j.size else 0
 
 
-def set_mesh_skin_call(name, handle, mesh_id, joints, weights, njoints):
-    """One bind call through the entry point `name`; joints None removes the skin."""
+SKIN_MODES = {"linear": 0, "dual_quaternion": 1}      # include/frt.h: 0, FRT_SKIN_DUAL_QUATERNION
+
+
+def set_mesh_skin_call(name, handle, mesh_id, joints, weights, njoints, mode="linear"):
+    """One bind call through the entry point `name`; joints None removes the skin. `mode`: "linear" (the call `name` itself) or "dual_quaternion"
+    (`name`_ex with FRT_SKIN_DUAL_QUATERNION); anything else is refused before the library is called."""
+    if not isinstance(mode, str) or mode not in SKIN_MODES:
+        raise FrtError(f"set_mesh_skin: mode must be 'linear' or 'dual_quaternion', not {mode!r}")
     if joints is None:
         return check(getattr(lib(), name)(handle, int(mesh_id), None, None, 0, 0))
     mid, j, w, n = mesh_skin_args(mesh_id, joints, weights)
+    if SKIN_MODES[mode]:
+        return check(getattr(lib(), name + "_ex")(handle, mid, j.ctypes.data, w.ctypes.data, n, int(njoints), SKIN_MODES[mode]))
     check(getattr(lib(), name)(handle, mid, j.ctypes.data, w.ctypes.data, n, int(njoints)))
 
 
@@ -472,8 +480,9 @@ class SceneBuilder:
     # Linear-blend skinning (include/frt.h: frt_scene_set_mesh_skin, frt_scene_set_mesh_pose). set_mesh_skin binds four joints and four weights per vertex;
     # the mesh's positions at the call become the bind pose (joints=None removes the skin; num_joints defaults to the largest index + 1). set_mesh_pose
     # skins the bind pose under one column-major 4x4 per joint and applies the result as set_mesh_vertices does. Host copy only.
-    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None):
-        set_mesh_skin_call("frt_scene_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints))
+    # mode="dual_quaternion" (frt_scene_set_mesh_skin_ex, FRT_SKIN_DUAL_QUATERNION) binds the mesh to be posed by the dual-quaternion blend instead.
+    def set_mesh_skin(self, mesh_id, joints, weights=None, num_joints=None, mode="linear"):
+        set_mesh_skin_call("frt_scene_set_mesh_skin", self._h, mesh_id, joints, weights, _num_joints(joints, num_joints), mode)
         return self
 
     # morph_weights: morph first, then skin the morphed positions (frt_scene_set_mesh_pose_ex); None is the plain pose.

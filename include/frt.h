@@ -185,6 +185,39 @@ int frt_scene_set_mesh_vertices_ex(frt_scene* s, uint32_t mesh_id, const float* 
  * bit, FRT_DEFORM_DEVICE. A later frt_scene_set_mesh_vertices on a skinned mesh is allowed and leaves the bind pose untouched; frt_scene_remove_meshes
  * drops the skin of a mesh that leaves, and the survivors' skins follow their ids. */
 int frt_scene_set_mesh_skin(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+/* Dual-quaternion skinning ("Dual-quaternion skinning"; Kavan et al.): the skin MODE of a mesh, chosen when the skin is bound.
+ * set_mesh_skin_ex is set_mesh_skin with `flags`: 0 binds the linear blend above (set_mesh_skin IS this call with flags 0), FRT_SKIN_DUAL_QUATERNION
+ * binds the same joints and weights to be blended as rigid transforms, which keeps the volume a linear blend loses under a twist. Any other bit:
+ * FRT_ERR_INVALID_ARG, nothing changed (checked behind the built scene and the mesh id, in front of the arrays; also when joints4 is NULL).
+ * Binding again replaces the mode with the skin; frt_scene_remove_meshes drops and renumbers it with the skin. No pose call takes a mode: set_mesh_pose,
+ * set_mesh_pose_ex, set_mesh_poses and everything that ends in them pose each mesh in the mode it was bound with (a batch may mix them under one
+ * palette; morph then skin works in either). The checks and refusals of the pose calls are those above.
+ * The contract of the mode, f32 without contraction and without a hand-written fma, sqrt and 1 / sqrt exactly rounded (rsq(x) = 1 / sqrt(x) below),
+ * quaternions as (x, y, z, w), dot4(a, b) = ((a.x b.x + a.y b.y) + a.z b.z) + a.w b.w,
+ * cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x):
+ * PER JOINT MATRIX M (column-major, row 3 not read), with n_c = (M[4c]^2 + M[4c+1]^2) + M[4c+2]^2 for c in 0..2:
+ *   s = ((sqrt(n_0) + sqrt(n_1)) + sqrt(n_2)) * 0.333333343f                                    (the uniform scale)
+ *   R_rc = M[4c + r] * rsq(n_c)                                                                 (the rotation; t = (R_00 + R_11) + R_22)
+ *   q = the branch of the greatest of (t, R_00, R_11, R_22), the first of equals in that order:
+ *     t:    (R_21 - R_12, R_02 - R_20, R_10 - R_01, 1 + t)
+ *     R_00: (((1 + R_00) - R_11) - R_22, R_01 + R_10, R_02 + R_20, R_21 - R_12)
+ *     R_11: (R_01 + R_10, ((1 + R_11) - R_00) - R_22, R_12 + R_21, R_02 - R_20)
+ *     R_22: (R_02 + R_20, R_12 + R_21, ((1 + R_22) - R_00) - R_11, R_10 - R_01)
+ *   qr = q * rsq(dot4(q, q))            (Shepperd's choice; its square root and division are this normalisation)
+ *   with (tx, ty, tz) = M[12..14]:      qd = 0.5 (t, 0) qr, that is
+ *     qd.x = 0.5 ((tx qr.w + ty qr.z) - tz qr.y)   qd.y = 0.5 ((ty qr.w + tz qr.x) - tx qr.z)   qd.z = 0.5 ((tz qr.w + tx qr.y) - ty qr.x)
+ *     qd.w = -0.5 ((tx qr.x + ty qr.y) + tz qr.z)
+ * Shear and non-uniform scale are NOT represented: the columns are normalised one by one and their lengths averaged.
+ * PER VERTEX with bind position p, joints j[0..3] and weights w[0..3]: the pivot P is the first slot of greatest weight;
+ *   sigma_k = dot4(qr_k, qr_P) < 0 ? -1 : 1
+ *   b[c]  = ((w0 (sigma_0 dq_0[c]) + w1 (sigma_1 dq_1[c])) + w2 (sigma_2 dq_2[c])) + w3 (sigma_3 dq_3[c])        for the eight components of (qr, qd)
+ *   s_b   = ((w0 s_0 + w1 s_1) + w2 s_2) + w3 s_3
+ *   (r, d) = (b_r, b_d) * rsq(dot4(b_r, b_r));  u = r.xyz;  v = s_b * p.xyz
+ *   out.xyz = (v + 2 cross(u, cross(u, v) + r.w v)) + 2 ((r.w d.xyz - d.w u) + cross(u, d.xyz)),   out.w = p.w
+ * All four terms are always evaluated and the weights are used as given, as in the linear form. A zero column of a joint some vertex names, and a
+ * blend whose real part cancels to zero, have an infinite rsq and give NaN coordinates: the pose is refused as a non-finite skinned coordinate. */
+#define FRT_SKIN_DUAL_QUATERNION 1u
+int frt_scene_set_mesh_skin_ex(frt_scene* s, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags);
 int frt_scene_set_mesh_pose(frt_scene* s, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* Morph targets, or blend shapes ("Morph targets"). A set of per-vertex position deltas is bound to a mesh of a BUILT scene once; a
  * morph is then only one weight per target. The contract, f32 without contraction and without a hand-written fma: for vertex v with base position
@@ -492,6 +525,13 @@ int frt_renderer_set_mesh_vertices_ex(frt_renderer* r, uint32_t mesh_id, const f
  * entry of a device palette (in a joint no vertex names too) and, for either kind of palette, a skinned coordinate that overflowed. Such a call changes
  * nothing of the replica and adds one to the counter frt_renderer_deform_rejects reads. */
 int frt_renderer_set_mesh_skin(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+/* ... with the skin mode (frt_scene_set_mesh_skin_ex: 0 or FRT_SKIN_DUAL_QUATERNION; set_mesh_skin is this call with flags 0). The mode is kept beside
+ * the mesh's skin buffers, whose layout does not depend on it, and follows frt_renderer_remove_meshes with them. Every posing call of the renderer
+ * (set_mesh_pose(_ex), set_mesh_poses, animate*, animate_cast*) poses a mesh in its mode, bit for bit what the scene's form gives: a call with a
+ * dual-quaternion mesh runs one more kernel over the batch, which converts each vertex's four joint matrices in the lane; a call without one runs
+ * exactly the launches it ran before the mode existed. The device rejects (deform_rejects) what the scene refuses: a zero column in a named joint and
+ * a blend that cancels become non-finite coordinates, and a non-finite entry of a device palette is found by whichever skin kernel runs first. */
+int frt_renderer_set_mesh_skin_ex(frt_renderer* r, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags);
 int frt_renderer_set_mesh_pose(frt_renderer* r, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* Morph a mesh of this renderer's scene replica ("Morph targets"): arguments, checks and results of
  * frt_scene_set_mesh_morph_targets, frt_scene_set_mesh_morph_weights and frt_scene_set_mesh_pose_ex, bit for bit, under the ordering and state rules of
@@ -984,6 +1024,7 @@ int frt_multi_renderer_set_mesh_vertices(frt_multi_renderer* m, uint32_t mesh_id
 int frt_multi_renderer_set_mesh_vertices_ex(frt_multi_renderer* m, uint32_t mesh_id, const float* pos4, const frt_vertex_attr* attrs, uint32_t nverts, uint32_t flags);
 /* frt_renderer_set_mesh_skin and frt_renderer_set_mesh_pose on every strip's replica, between frames. FRT_DEFORM_DEVICE is refused. */
 int frt_multi_renderer_set_mesh_skin(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints);
+int frt_multi_renderer_set_mesh_skin_ex(frt_multi_renderer* m, uint32_t mesh_id, const uint16_t* joints4, const float* weights4, uint32_t nverts, uint32_t njoints, uint32_t flags);
 int frt_multi_renderer_set_mesh_pose(frt_multi_renderer* m, uint32_t mesh_id, const float* joint_mats, uint32_t njoints, uint32_t flags);
 /* frt_renderer_set_mesh_morph_targets, frt_renderer_set_mesh_morph_weights and frt_renderer_set_mesh_pose_ex on every strip's replica, between frames.
  * FRT_DEFORM_DEVICE is refused. */
