@@ -156,11 +156,21 @@ std::string frt::check_rig_goals(uint32_t ngoals, const frt_rig_goal* goals, con
     for (uint32_t i = 0; i < ngoals; ++i) {
         const frt_rig_goal& g = goals[i];
         const std::string at = "goal " + std::to_string(i) + ": ";
-        if (g.kind > (uint32_t)FRT_GOAL_AIM) return at + "unknown kind " + std::to_string(g.kind);
+        if (g.kind > FRT_GOAL_CHAIN) return at + "unknown kind " + std::to_string(g.kind);
         if (g.reserved != 0) return at + "reserved must be 0";
-        if (g.root >= N || g.mid >= N || g.tip >= N) return at + "a node out of range (" + std::to_string(N) + " nodes)";
+        const bool chain = g.kind == FRT_GOAL_CHAIN;      // (its mid is a number of sweeps, not a node)
+        if (g.root >= N || (!chain && g.mid >= N) || g.tip >= N) return at + "a node out of range (" + std::to_string(N) + " nodes)";
         frt_rig_goal s = g;
-        if (g.kind == (uint32_t)FRT_GOAL_AIM) {
+        if (chain) {
+            s.root = place[g.root]; s.tip = place[g.tip];
+            if (!below(s.root, s.tip)) return at + "the tip of a chain is not a strict descendant of its root";
+            uint32_t K = 0;      // the bones of the path: the nodes of subtree(root) that hold the tip below them
+            for (uint32_t a = 0; a < N; ++a) K += ik_in_subtree(enter, exit, s.root, a) && below(a, s.tip);
+            if (K + 1u > FRT_IK_CHAIN_MAX_NODES) return at + "a chain of " + std::to_string(K + 1u) + " nodes, more than FRT_IK_CHAIN_MAX_NODES";
+            if (g.mid < 1u || g.mid > FRT_IK_CHAIN_MAX_SWEEPS) return at + std::to_string(g.mid) + " sweeps (1 .. FRT_IK_CHAIN_MAX_SWEEPS)";
+            s.axis[0] = s.axis[1] = s.axis[2] = 0.0f;      // (a chain has no axis: nothing of it is kept)
+            s.reserved = K;                                // the stored form carries the path's length
+        } else if (g.kind == (uint32_t)FRT_GOAL_AIM) {
             if (g.mid != 0 || g.tip != 0) return at + "mid and tip of an aim goal must be 0";
             if (!all_finite(g.axis, 3)) return at + "the axis is not finite";
             if (g.axis[0] == 0.0f && g.axis[1] == 0.0f && g.axis[2] == 0.0f) return at + "the axis is zero";
@@ -607,8 +617,36 @@ static std::string check_goals_call(const frt_rig* rig, uint32_t ngoals, const f
     const std::string bad = check_rig_goals(ngoals, goals, rig->place, tree.enter.data(), tree.exit.data(), gs);
     return bad.empty() ? check_rig_goal_targets(ngoals, targets, ngoals, gs.data()) : bad;
 }
-static void apply_goals(std::vector<m4>& global, const std::vector<frt_rig_goal>& gs, const frt_rig_goal_target* targets, const RigTree& tree) {
+// "Chain IK": one chain goal in its stored form (mid: the sweeps; reserved: K, the bones of the path), over arrays where rig_apply_chain
+// (frt_animation.hip) holds the chain in the lanes of a wave. `parent`: the block's parents, stored order.
+static void apply_chain_goal(std::vector<m4>& global, const frt_rig_goal& g, const frt_rig_goal_target& t, const RigTree& tree, const uint32_t* parent) {
+    if (!ik_target_ok(t)) return;
+    const uint32_t K = g.reserved, S = g.mid;
+    std::vector<uint32_t> c(K + 1u);
+    c[K] = g.tip;
+    for (uint32_t j = K; j-- > 0u;) c[j] = parent[c[j + 1u]];      // (check_rig_goals has counted the path: c[0] is the root)
+    std::vector<f3> P(K + 1u);
+    std::vector<m4> D(K + 1u, ik_identity());
+    for (uint32_t j = 0; j <= K; ++j) P[j] = xyz(global[c[j]].c[3]);
+    const f3 Te = ik_chain_target(P[K], t);
+    for (uint32_t s = 0; s < S; ++s)
+        for (uint32_t k = K; k-- > 0u;) {
+            m4 R;
+            if (!ik_chain_step(P[k], P[K], Te, R)) continue;
+            for (uint32_t j = k + 1u; j <= K; ++j) P[j] = ik_point(R, P[j]);
+            for (uint32_t j = k; j <= K; ++j) D[j] = mul(R, D[j]);
+        }
+    const uint32_t* enter = tree.enter.data(); const uint32_t* exit = tree.exit.data();
+    for (uint32_t n = 0; n < (uint32_t)global.size(); ++n) {
+        if (!ik_in_subtree(enter, exit, c[0], n)) continue;
+        uint32_t j = 0;      // the deepest chain node whose subtree holds n; the tip's own subtree moves with the last bone
+        for (uint32_t i = 1u; i <= K; ++i) if (ik_in_subtree(enter, exit, c[i], n)) j = i;
+        global[n] = mul(D[j < K ? j : K - 1u], global[n]);
+    }
+}
+static void apply_goals(std::vector<m4>& global, const std::vector<frt_rig_goal>& gs, const frt_rig_goal_target* targets, const RigTree& tree, const uint32_t* parent) {
     for (size_t i = 0; i < gs.size(); ++i) {
+        if (gs[i].kind == FRT_GOAL_CHAIN) { apply_chain_goal(global, gs[i], targets[i], tree, parent); continue; }
         const IkDelta d = ik_goal_delta(gs[i], targets[i], global[gs[i].root], global[gs[i].mid], global[gs[i].tip]);
         if (!d.on) continue;
         for (uint32_t n = 0; n < (uint32_t)global.size(); ++n) {
@@ -641,7 +679,7 @@ static int evaluate_layers(const char* call, const frt_rig* rig, uint32_t n, con
     if ((h.njoints && !joint_mats_out) || (h.ntargets && !morph_weights_out)) return rig_fail(name + ": null output");
     if (h.njoints) {
         std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
-        apply_goals(global, gs, targets, tree);
+        apply_goals(global, gs, targets, tree, v.w + h.parent);
         for (uint32_t j = 0; j < h.njoints; ++j) {
             const m4 m = mul(global[v.w[h.joint_node + j]], load_m4(v.f(h.inv_bind) + (size_t)16 * j));
             memcpy(joint_mats_out + (size_t)16 * j, &m, 64);
@@ -669,7 +707,7 @@ static int evaluate_nodes_layers(const char* call, const frt_rig* rig, uint32_t 
     if (root && !all_finite(root, 16)) return rig_fail(name + ": a root entry is not finite");
     if (offsets && !all_finite(offsets, (size_t)16 * nnodes)) return rig_fail(name + ": an offsets entry is not finite");
     std::vector<m4> global = layers_globals(v, h, n, layers, nmasks, stored.data());
-    apply_goals(global, gs, targets, tree);
+    apply_goals(global, gs, targets, tree, v.w + h.parent);
     for (uint32_t k = 0; k < nnodes; ++k) {
         const m4 M = rig_node_matrix(global[rig->place[nodes[k]]], root, offsets ? offsets + (size_t)16 * k : nullptr);
         memcpy(mats_out + (size_t)16 * k, &M, 64);

@@ -114,30 +114,115 @@ struct RigNoGoals {
     static constexpr bool any = false;
     __device__ bool ok(uint32_t) const { return true; }
 };
-struct RigBoundGoals {
+// The third policy ("Chain IK") is the second with Chain = true: launched only when the binding (for a cast: any entry's binding) carries a
+// FRT_GOAL_CHAIN goal, so bindings with two-bone and aim goals only run the instantiations without a line of chain code.
+template <bool Chain>
+struct RigBoundGoalsT {
     static constexpr bool any = true;
+    static constexpr bool chain = Chain;
     uint32_t n, pad; const frt_rig_goal* g; const uint32_t* enter; const uint32_t* exit; const frt_rig_goal_target* t;
-    // What set_rig_goals has refused, restated on the goal words (uniform): the count, the kinds, nodes < N. Asked in front of the first barrier.
+    // What set_rig_goals has refused, restated on the goal words (uniform): the count, the kinds, nodes < N; of a chain (whose mid is its sweeps
+    // and whose reserved word is K, the bones of its path) the two caps. Asked in front of the first barrier.
     __device__ bool ok(uint32_t N) const {
         if (n > FRT_MAX_RIG_GOALS) return false;
         if (n && (!g || !enter || !exit || !t)) return false;
-        for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t i = 0; i < n; ++i) {
+            if constexpr (Chain) {
+                if (g[i].kind == FRT_GOAL_CHAIN) {
+                    if (g[i].root >= N || g[i].tip >= N || g[i].mid < 1u || g[i].mid > FRT_IK_CHAIN_MAX_SWEEPS || g[i].reserved < 1u || g[i].reserved >= FRT_IK_CHAIN_MAX_NODES) return false;
+                    continue;
+                }
+            }
             if (g[i].kind > (uint32_t)FRT_GOAL_AIM || g[i].root >= N || g[i].mid >= N || g[i].tip >= N) return false;
+        }
         return true;
     }
 };
-static_assert(sizeof(frt_rig_goal) == 32 && sizeof(frt_rig_goal_target) == 32 && sizeof(RigBoundGoals) == 40, "goal layouts");
+typedef RigBoundGoalsT<false> RigBoundGoals;
+typedef RigBoundGoalsT<true> RigChainGoals;
+static_assert(sizeof(frt_rig_goal) == 32 && sizeof(frt_rig_goal_target) == 32 && sizeof(RigBoundGoals) == 40 && sizeof(RigChainGoals) == 40, "goal layouts");
+
+// "Chain IK": one FRT_GOAL_CHAIN goal, the chain held in registers across the lanes of a wave. The solve is strictly sequential (every step reads
+// the tip the step before it moved), so it is not run as READ / BARRIER / WRITE rounds (2 S K workgroup barriers and S K sweeps over the N nodes)
+// but inside each wave, with no barrier and no LDS traffic:
+// GATHER: each of the four waves holds the whole chain, redundantly (every lane computes the same, nobody is elected). Lane j <= K of a wave owns
+// c_j, P_j and D_j; the lanes find their node by the uniform parent walk from the tip, K steps over the rig block's parents, and read their
+// node's origin from LDS once. Lanes above K own the tip: what they compute is never read.
+// SOLVE: S K steps; P_K and P_k come by wave broadcast (__shfl from a uniform lane), every lane computes the same R through ik_chain_step, and
+// the lanes with j > k (j >= k for D) update their own words under a lane predicate. No register array is indexed by a variable.
+// APPLY: one barrier (every wave has read its origins before a global is rewritten), then all 256 lanes stride over the N nodes in whole rounds,
+// so that every lane of a wave executes every __shfl: the chain's enter / exit numbers are broadcast lane by lane, the deepest hit is kept and
+// clamped to K - 1, the sixteen words of D_j come from lane j of the node's own wave (__shfl with a per-lane source; all sixteen, so that
+// mul(D_j, G) has the host's operands to the bit whatever D's last row holds), and mul(D_j, G) is stored in place. One barrier follows. Both
+// barriers are reached by the whole workgroup whether or not the goal is on. Called with uniform arguments.
+__device__ inline float rig_lane(float x, uint32_t lane) { return __shfl(x, (int)lane); }
+__device__ inline uint32_t rig_lane(uint32_t x, uint32_t lane) { return (uint32_t)__shfl((int)x, (int)lane); }
+__device__ inline f3 rig_lane(f3 p, uint32_t lane) { return mk3(rig_lane(p.x, lane), rig_lane(p.y, lane), rig_lane(p.z, lane)); }
+__device__ inline f4 rig_lane(f4 p, uint32_t lane) { return mk4(rig_lane(p.x, lane), rig_lane(p.y, lane), rig_lane(p.z, lane), rig_lane(p.w, lane)); }
+__device__ inline void rig_apply_chain(const frt_rig_goal& gl, const frt_rig_goal_target& t, const uint32_t* enter, const uint32_t* exit, const uint32_t* parent, float4* g, uint32_t N) {
+    const uint32_t K = gl.reserved, S = gl.mid;      // (ok() has held them to 1 .. 31 and 1 .. 16, root and tip below N)
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool on = ik_target_ok(t);                 // (uniform)
+    uint32_t mine = gl.tip, en = 0u, ex = 0u;
+    m4 D = ik_identity();
+    if (on) {
+        uint32_t c = gl.tip;
+        for (uint32_t i = K; i > 0u; --i) {          // c: c_i
+            if (lane == i) mine = c;
+            const uint32_t p = parent[c];
+            c = p < c ? p : c;                       // (a root has no parent: set_rig_goals has counted the path, so none is met)
+        }
+        if (lane == 0u) mine = c;
+        en = enter[mine]; ex = exit[mine];
+        const float4 o = g[3u * kRigLds + mine];
+        f3 P = mk3(o.x, o.y, o.z);
+        const f3 Te = ik_chain_target(rig_lane(P, K), t);
+#pragma unroll 1
+        for (uint32_t s = 0; s < S; ++s) {
+#pragma unroll 1
+            for (uint32_t k = K; k-- > 0u;) {
+                m4 R;
+                if (!ik_chain_step(rig_lane(P, k), rig_lane(P, K), Te, R)) continue;      // (the same for every lane)
+                if (lane > k) P = ik_point(R, P);
+                if (lane >= k) D = mul(R, D);
+            }
+        }
+    }
+    __syncthreads();
+    if (on) {
+        for (uint32_t base = 0; base < N; base += (uint32_t)kRigBlock) {
+            const uint32_t n = base + threadIdx.x;
+            const bool live = n < N;
+            const uint32_t at = enter[live ? n : 0u];
+            bool hit = false;
+            uint32_t j = 0u;
+            for (uint32_t i = 0; i <= K; ++i) {      // nested subtrees: the last hit is the deepest
+                const uint32_t a = rig_lane(en, i), b = rig_lane(ex, i);
+                if (a <= at && at < b) { hit = true; j = i; }
+            }
+            j = j < K ? j : K - 1u;
+            m4 Dj;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) Dj.c[c] = rig_lane(D.c[c], j);
+            if (live && hit) rig_lds_store(g, n, mul(Dj, rig_lds_load(g, n)));
+        }
+    }
+    __syncthreads();
+}
 // Between phases (2) and (3): every goal is one round. READ: every lane reads the goal's words (global memory) and its pivots' globals (LDS) — the
 // same addresses for every lane — and computes the same matrices; no lane is elected and nothing is shared. BARRIER (every lane has read the pivots
 // before one of them is written). WRITE: the lanes stride over all N nodes, test membership by enter / exit and store mul(D, G) in place, one lane
 // per entry. BARRIER. Both barriers are reached by the whole workgroup in every round: a skipped goal skips its stores only. Called with uniform
 // arguments behind the last barrier of rig_globals_to_lds.
 template <class Goals>
-__device__ inline void rig_apply_goals(const Goals& goals, float4* g, uint32_t N) {
+__device__ inline void rig_apply_goals(const Goals& goals, RigView v, const RigHeader& h, float4* g, uint32_t N) {
     if constexpr (Goals::any) {
 #pragma unroll 1
         for (uint32_t i = 0; i < goals.n; ++i) {
             const frt_rig_goal gl = goals.g[i];
+            if constexpr (Goals::chain) {      // ("Chain IK": a uniform branch; a chain goal is one round of its own, with the two barriers of every round)
+                if (gl.kind == FRT_GOAL_CHAIN) { rig_apply_chain(gl, goals.t[i], goals.enter, goals.exit, v.w + h.parent, g, N); continue; }
+            }
             const IkDelta d = ik_goal_delta(gl, goals.t[i], rig_lds_load(g, gl.root), rig_lds_load(g, gl.mid), rig_lds_load(g, gl.tip));
             __syncthreads();
             if (d.on) {
@@ -162,7 +247,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_evaluate_kernel(const uint32_t*
     if (!src.ok(h) || !goals.ok(N)) return;                          // (animate refuses it; uniform: no barrier is skipped by a part of the workgroup)
     if (h.njoints) {
         rig_globals_to_lds(v, h, src, g, N);
-        rig_apply_goals(goals, g, N);
+        rig_apply_goals(goals, v, h, g, N);
         for (uint32_t j = tid; j < h.njoints; j += (uint32_t)kRigBlock) {
             const uint32_t n = words[h.joint_node + j];
             if (n >= N) continue;
@@ -186,7 +271,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_nodes_kernel(const uint32_t* wo
     const auto src = list.source();
     if (!src.ok(h) || !goals.ok(N)) return;                          // (animate_instances refuses it; uniform, in front of the first barrier)
     rig_globals_to_lds(v, h, src, g, N);
-    rig_apply_goals(goals, g, N);
+    rig_apply_goals(goals, v, h, g, N);
     for (uint32_t k = threadIdx.x; k < n; k += (uint32_t)kRigBlock) {
         const uint32_t node = nodes[k];
         if (node >= N) continue;                                     // (bind_rig_instances has checked it)
@@ -242,13 +327,14 @@ struct CastLayersEntry {
 };
 static_assert(sizeof(CastLayersEntry) == 128 && sizeof(CastLayersEntry) % 16 == 0 && alignof(CastLayersEntry) <= 16, "CastLayersEntry layout");
 // The goals of a cast's entry: the entry's own binding's (an entry without goals runs the loop zero times); none for a cast without goals.
-__device__ inline RigBoundGoals rig_goals_at(const uint8_t* buf, const frt_rig_goal_target* t, uint32_t n, uint32_t nnodes) {
+template <bool Chain>
+__device__ inline RigBoundGoalsT<Chain> rig_goals_at(const uint8_t* buf, const frt_rig_goal_target* t, uint32_t n, uint32_t nnodes) {
     const uint32_t* tree = reinterpret_cast<const uint32_t*>(buf + sizeof(frt_rig_goal) * FRT_MAX_RIG_GOALS);
-    return RigBoundGoals{n, 0u, reinterpret_cast<const frt_rig_goal*>(buf), tree, tree + nnodes, t};
+    return RigBoundGoalsT<Chain>{n, 0u, reinterpret_cast<const frt_rig_goal*>(buf), tree, tree + nnodes, t};
 }
 template <class Goals, class Entry> struct CastGoals { __device__ static RigNoGoals of(const Entry&, uint32_t) { return RigNoGoals(); } };
-template <> struct CastGoals<RigBoundGoals, CastLayersEntry> {
-    __device__ static RigBoundGoals of(const CastLayersEntry& e, uint32_t nnodes) { return e.ngoals ? rig_goals_at(e.goals, e.goal_targets, e.ngoals, nnodes) : RigBoundGoals{0u, 0u, nullptr, nullptr, nullptr, nullptr}; }
+template <bool Chain> struct CastGoals<RigBoundGoalsT<Chain>, CastLayersEntry> {
+    __device__ static RigBoundGoalsT<Chain> of(const CastLayersEntry& e, uint32_t nnodes) { return e.ngoals ? rig_goals_at<Chain>(e.goals, e.goal_targets, e.ngoals, nnodes) : RigBoundGoalsT<Chain>{0u, 0u, nullptr, nullptr, nullptr, nullptr}; }
 };
 
 __device__ inline void rig_store_twice(float4* own, float4* all, uint32_t k, const m4& m) {
@@ -271,7 +357,7 @@ __global__ void __launch_bounds__(kRigBlock) rig_cast_kernel(const Entry* table)
     const Goals goals = CastGoals<Goals, Entry>::of(e, h.nnodes);      // (enter and exit lie behind the definitions, nnodes words each)
     if (!src.ok(h) || !goals.ok(N)) return;                          // (animate_cast refuses it; uniform, in front of the first barrier)
     const bool instances = e.kind == (uint32_t)kRigInstances;
-    if (instances || h.njoints) { rig_globals_to_lds(v, h, src, g, N); rig_apply_goals(goals, g, N); }
+    if (instances || h.njoints) { rig_globals_to_lds(v, h, src, g, N); rig_apply_goals(goals, v, h, g, N); }
     if (instances) {
         for (uint32_t k = tid; k < e.n; k += (uint32_t)kRigBlock) {
             e.all_ids[k] = e.ids[k];
@@ -332,9 +418,15 @@ static RigLayerList layer_list(uint32_t n, const frt_clip_layer* l, const RigBin
 
 // frt_renderer_animate_instances, _animate_instances_blend and _animate_instances_layers behind their checks: the kernel, then the device transform.
 // The goals a layered call on binding b launches with ("Inverse kinematics"): for a binding that carries some.
-static RigBoundGoals bound_goals(const RigBinding& b) {
+template <bool Chain = false>
+static RigBoundGoalsT<Chain> bound_goals(const RigBinding& b) {
     const uint32_t* tree = reinterpret_cast<const uint32_t*>(b.goals.as<const uint8_t>() + sizeof(frt_rig_goal) * FRT_MAX_RIG_GOALS);
-    return RigBoundGoals{b.ngoals, 0u, b.goals.as<const frt_rig_goal>(), tree, tree + b.nnodes, b.goal_targets.as<const frt_rig_goal_target>()};
+    return RigBoundGoalsT<Chain>{b.ngoals, 0u, b.goals.as<const frt_rig_goal>(), tree, tree + b.nnodes, b.goal_targets.as<const frt_rig_goal_target>()};
+}
+// "Chain IK": whether the binding's goals hold a chain, which is what picks the third goal policy.
+static bool has_chain_goal(const RigBinding& b) {
+    for (uint32_t i = 0; i < b.ngoals; ++i) if (b.goal_defs[i].kind == FRT_GOAL_CHAIN) return true;
+    return false;
 }
 
 template <class List, class Goals = RigNoGoals>
@@ -703,6 +795,7 @@ int frt_renderer_animate_layers(frt_renderer* r, uint32_t binding, uint32_t n, c
     if (b->kind != kRigMeshes) return fail(FRT_ERR_INVALID_ARG, "animate_layers: binding " + std::to_string(binding) + " binds instances (frt_renderer_animate_instances_layers)");
     const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_layers: " + bad);
+    if (has_chain_goal(*b)) return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags, bound_goals<true>(*b));
     if (b->ngoals) return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags, bound_goals(*b));
     return pose_bound_meshes(r, "animate_layers", b, layer_list(n, layers, *b), flags);
 }
@@ -714,6 +807,7 @@ int frt_renderer_animate_instances_layers(frt_renderer* r, uint32_t binding, uin
     if (b->kind != kRigInstances) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: binding " + std::to_string(binding) + " binds meshes (frt_renderer_animate_layers)");
     const std::string bad = check_clip_layers(n, layers, b->nclips, b->nmasks);
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_instances_layers: " + bad);
+    if (has_chain_goal(*b)) return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b), bound_goals<true>(*b));
     if (b->ngoals) return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b), bound_goals(*b));
     return move_bound_instances(r, "animate_instances_layers", b, layer_list(n, layers, *b));
 }
@@ -729,8 +823,9 @@ int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast
     if (!bad.empty()) return fail(FRT_ERR_INVALID_ARG, "animate_cast_layers: " + bad);
     std::vector<CastRange> ranges(n);
     for (uint32_t k = 0; k < n; ++k) ranges[k] = CastRange{entries[k].first_layer, entries[k].num_layers};
-    bool goals = false;      // the goal instantiation when any entry's binding carries goals
-    for (uint32_t k = 0; k < n; ++k) goals = goals || r->rigs[entries[k].binding].ngoals != 0;
+    bool goals = false, chain = false;      // the goal instantiation when any entry's binding carries goals; the chain one when any carries a chain
+    for (uint32_t k = 0; k < n; ++k) { goals = goals || r->rigs[entries[k].binding].ngoals != 0; chain = chain || has_chain_goal(r->rigs[entries[k].binding]); }
+    if (chain) return run_cast<CastLayersEntry, RigChainGoals>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
     if (goals) return run_cast<CastLayersEntry, RigBoundGoals>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
     return run_cast<CastLayersEntry>(r, "animate_cast_layers", n, plain.data(), ranges.data(), info, nlayers, layers, flags);
 }

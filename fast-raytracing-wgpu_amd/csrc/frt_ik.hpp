@@ -2,7 +2,8 @@
 // "Inverse kinematics"). Included by frt_animation.hpp behind its own functions; every function here is FRT_HD and is the one text the host form
 // (frt_animation.cpp: apply_goals) and the kernels (frt_animation.hip: rig_apply_goals) both run under the library's contract flags: f32, no
 // contraction, no hand-written fma, every product and sum written once, rsqrt_exact / sqrtf_ / rcpf_ of frt_math.hpp and rig_slerp / rig_trs_matrix
-// of frt_animation.hpp. No acos is taken: a rotation between two directions is built from their cross and dot products.
+// of frt_animation.hpp. No acos is taken: a rotation between two directions is built from their cross and dot products. The third kind, a CCD
+// chain ("Chain IK"), is at the end of the file: it is built from ik_arc, ik_about and ik_point alone.
 //
 // A GOAL acts on the GLOBAL matrices of a rig, in the rig's model space, behind the hierarchy walk: it is a rotation about a pivot (an m4 `D`) that
 // every node of a subtree takes as G = mul(D, G). Nodes are stored by depth, so a subtree is not a range of the block: `enter` / `exit` are pre-order
@@ -112,6 +113,28 @@ FRT_HD bool ik_move_node(const IkDelta& d, const uint32_t* enter, const uint32_t
     if (ik_in_subtree(enter, exit, d.inner_node, n)) { G = mul(d.inner, G); return true; }
     if (ik_in_subtree(enter, exit, d.outer_node, n)) { G = mul(d.outer, G); return true; }
     return false;
+}
+
+// CHAIN ("Chain IK"): cyclic coordinate descent over the parent path c_0 = root .. c_K = tip. P_j the origin of G[c_j] and D_j the identity at the
+// start; the caller (frt_animation.cpp: apply_chain_goal over arrays; frt_animation.hip: rig_apply_chain over the lanes of a wave) runs S sweeps of
+// k = K - 1 .. 0 and, where ik_chain_step says so, takes P_j = ik_point(R, P_j) for j > k and D_j = mul(R, D_j) for j >= k. These two functions
+// are all the arithmetic and all the decisions of a sweep: both callers only index.
+FRT_HD f3 ik_chain_target(f3 tip, const frt_rig_goal_target& t) {
+    const f3 T = mk3(t.target[0], t.target[1], t.target[2]);
+    const float w = t.weight;
+    return w == 1.0f ? T : tip + w * (T - tip);
+}
+// One step at joint k: the rotation about Pk that turns the tip PK towards Te; false (the step changes nothing) when either length is not > 0.
+FRT_HD bool ik_chain_step(f3 Pk, f3 PK, f3 Te, m4& R) {
+    const f3 e = PK - Pk, t = Te - Pk;
+    if (!(sqrtf_(dot(e, e)) > 0.0f && sqrtf_(dot(t, t)) > 0.0f)) return false;
+    R = ik_about(Pk, ik_arc(normalize(e), normalize(t)));
+    return true;
+}
+FRT_HD m4 ik_identity() {
+    m4 m;
+    m.c[0] = mk4(1.0f, 0.0f, 0.0f, 0.0f); m.c[1] = mk4(0.0f, 1.0f, 0.0f, 0.0f); m.c[2] = mk4(0.0f, 0.0f, 1.0f, 0.0f); m.c[3] = mk4(0.0f, 0.0f, 0.0f, 1.0f);
+    return m;
 }
 
 } // namespace frt

@@ -125,6 +125,8 @@ class CastLayersEntry(C.Structure):                 # include/frt.h: frt_cast_la
 MAX_RIG_GOALS = 16                                  # include/frt.h: FRT_MAX_RIG_GOALS
 GOAL_KINDS = {"two_bone": 0, "aim": 1}              # include/frt.h: FRT_GOAL_*
 GOAL_TARGETS_DEVICE = 1                             # include/frt.h: FRT_GOAL_TARGETS_DEVICE
+GOAL_CHAIN = 2                                      # include/frt.h: FRT_GOAL_CHAIN ("Chain IK"; beside GOAL_KINDS, which keeps the first two kinds)
+IK_CHAIN_MAX_NODES, IK_CHAIN_MAX_SWEEPS = 32, 16    # include/frt.h: FRT_IK_CHAIN_MAX_NODES, FRT_IK_CHAIN_MAX_SWEEPS
 IK_PLANE_EPS, IK_ARC_EPS = 1e-12, 1e-6              # include/frt.h: FRT_IK_PLANE_EPS, FRT_IK_ARC_EPS (float32 constants of the contract)
 
 

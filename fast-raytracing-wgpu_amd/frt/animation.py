@@ -222,8 +222,9 @@ class Rig:
 
     # ---- inverse kinematics (include/frt.h: frt_rig_evaluate_layers_ik; DESIGN.md section 11, "Inverse kinematics")
     def _goal_rows(self, goals):
-        """(n, frt_rig_goal [n] or None) of `goals`: None, or an iterable of frt.TwoBone and frt.Aim with the node numbers the rig was described with."""
-        from ._lib import RigGoal, GOAL_KINDS
+        """(n, frt_rig_goal [n] or None) of `goals`: None, or an iterable of frt.TwoBone, frt.Aim and frt.Chain with the node numbers the rig was
+        described with."""
+        from ._lib import RigGoal, GOAL_KINDS, GOAL_CHAIN
         rows = []
         for k, g in enumerate(goals if goals is not None else ()):
             if isinstance(g, TwoBone):
@@ -233,10 +234,12 @@ class Rig:
                 if len(axis) != 3:
                     raise FrtError(f"Rig: goal {k}: an axis has three components")
                 nodes, kind = (g.node, 0, 0), GOAL_KINDS["aim"]
+            elif isinstance(g, Chain):
+                nodes, kind, axis = (g.root, g.sweeps, g.tip), GOAL_CHAIN, (0.0, 0.0, 0.0)      # (a chain's `mid` word is its number of sweeps)
             else:
-                raise FrtError(f"Rig: goal {k} is neither a frt.TwoBone nor a frt.Aim")
+                raise FrtError(f"Rig: goal {k} is neither a frt.TwoBone nor a frt.Aim nor a frt.Chain")
             if not all(0 <= int(x) <= 0xFFFFFFFF for x in nodes):
-                raise FrtError(f"Rig: goal {k}: nodes are unsigned 32-bit indices")
+                raise FrtError(f"Rig: goal {k}: nodes (and a chain's sweeps) are unsigned 32-bit numbers")
             rows.append(RigGoal(kind, int(nodes[0]), int(nodes[1]), int(nodes[2]), (C.c_float * 3)(*axis), 0))
         return len(rows), ((RigGoal * len(rows))(*rows) if rows else None)
 
@@ -257,7 +260,7 @@ class Rig:
         running pose per node. The first is the base: a blend layer without a mask and with a positive weight. A later layer acts by its weight
         times its mask's value at the node: "blend" mixes as evaluate_blend does, "override" replaces by that much (weight <= 1), "additive" adds
         that much of (clip at t) - (reference). masks: [nmasks, num_nodes] values in [0, 1] (Rig.mask), which Layer.mask names by index.
-        goals (frt.TwoBone, frt.Aim; at most MAX_RIG_GOALS) and targets ([G, 8] float32 rows of target xyz, weight, pole xyz, pole flag) act on
+        goals (frt.TwoBone, frt.Aim, frt.Chain; at most MAX_RIG_GOALS) and targets ([G, 8] float32 rows of target xyz, weight, pole xyz, pole flag) act on
         the layered pose's global matrices in the rig's model space, in list order (frt_rig_evaluate_layers_ik); without goals the plain call."""
         pal = np.zeros((self.num_joints, 16), np.float32) if self.num_joints else None
         w = np.zeros(self.num_targets, np.float32) if self.num_targets else None
@@ -307,6 +310,19 @@ class Aim:
 
     def __repr__(self):
         return f"Aim({self.node!r}, axis={self.axis!r})"
+
+
+class Chain:
+    """A chain goal (include/frt.h: FRT_GOAL_CHAIN; DESIGN.md section 11, "Chain IK"): the parent path root -> ... -> tip (tip below root, 2 to
+    IK_CHAIN_MAX_NODES nodes, every one of them a joint of the chain) is bent by `sweeps` sweeps of cyclic coordinate descent (1 to
+    IK_CHAIN_MAX_SWEEPS; there is no convergence test) so that tip's origin approaches the goal's target. What hangs off a chain node moves with
+    it; the tip does not turn itself. The pole words of its target row are ignored."""
+
+    def __init__(self, root, tip, sweeps=8):
+        self.root, self.tip, self.sweeps = root, tip, sweeps
+
+    def __repr__(self):
+        return f"Chain({self.root!r}, {self.tip!r}, sweeps={self.sweeps!r})"
 
 
 def goal_target_rows(targets):

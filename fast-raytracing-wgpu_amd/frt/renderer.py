@@ -491,7 +491,7 @@ class Renderer(_HostQueries, _SceneGrowth):
 
     # ---- inverse kinematics (include/frt.h: frt_renderer_set_rig_goals, _set_rig_goal_targets; DESIGN.md section 11, "Inverse kinematics")
     def set_rig_goals(self, binding, goals):
-        """Give a binding of either kind its goals (frt.TwoBone, frt.Aim; at most MAX_RIG_GOALS; None clears them). They replace the previous set, in
+        """Give a binding of either kind its goals (frt.TwoBone, frt.Aim, frt.Chain; at most MAX_RIG_GOALS; None clears them). They replace the previous set, in
         stream order, and do nothing until set_rig_goal_targets gives them targets. Only the _layers calls apply goals."""
         n, table = self._bound_rig("set_rig_goals", binding)._goal_rows(goals)
         check(lib().frt_renderer_set_rig_goals(self._h, int(binding), n, table))
@@ -899,7 +899,7 @@ class MultiRenderer(_HostQueries, _SceneGrowth):
 
     def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute", goals=None, targets=None):
         """rig.evaluate_layers(layers, masks, goals, targets) on the host, then set_mesh_poses on every strip's replica (DESIGN.md section 11,
-        "Layering clips", "Inverse kinematics"). The targets are host arrays."""
+        "Layering clips", "Inverse kinematics", "Chain IK": frt.Chain goals are solved on the host here). The targets are host arrays."""
         self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks, goals, targets), normals=normals)
 
     def animate_instances_layers(self, rig, instance_ids, nodes, layers, masks=None, root=None, offsets=None, goals=None, targets=None):

@@ -527,7 +527,7 @@ class SceneBuilder:
 
     # Layering clips ("Layering clips"): the host forms of Renderer.animate_layers, animate_instances_layers and
     # animate_cast_layers: rig.evaluate_layers / rig.evaluate_nodes_layers on the host under `masks`, then the same host calls.
-    # goals= and targets= ("Inverse kinematics"): frt.TwoBone / frt.Aim and their [G, 8] target rows, applied to the layered pose on the host.
+    # goals= and targets= ("Inverse kinematics", "Chain IK"): frt.TwoBone / frt.Aim / frt.Chain and their [G, 8] target rows, applied to the layered pose on the host.
     def animate_layers(self, rig, mesh_ids, layers, masks=None, normals="recompute", goals=None, targets=None):
         return self.set_mesh_poses(mesh_ids, *rig.evaluate_layers(layers, masks, goals, targets), normals=normals)
 

@@ -799,7 +799,7 @@ int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast
 /* Inverse kinematics ("Inverse kinematics"): goals on a rig, behind the layers. A GOAL acts on the GLOBAL matrices of the rig,
  * in the rig's model space: for a mesh binding the space of the palette, for an instance binding the space in front of `root` and the offsets (the
  * caller maps world space into it). Goals act after the layers have been folded and the hierarchy walked, and before joints or instances read the
- * globals; they are applied in list order, each seeing what the earlier ones left. 0 .. FRT_MAX_RIG_GOALS of them, of two kinds; node numbers are
+ * globals; they are applied in list order, each seeing what the earlier ones left. 0 .. FRT_MAX_RIG_GOALS of them, of three kinds; node numbers are
  * the caller's. The contract (csrc/frt_ik.hpp: ik_arc, ik_about, ik_two_bone, ik_aim; f32, no contraction, no fma, one text for host and kernel):
  *   arc(u, v), unit vectors: q = (cross(u, v), 1 + dot(u, v)) * rsqrt(|q|^2); if 1 + dot < FRT_IK_ARC_EPS, the half turn about cross(u, e), e the
  *   coordinate axis of u's smallest |component|. about(p, q): the m4 whose 3x3 is q's rotation and whose last column is p - R p.
@@ -817,12 +817,22 @@ int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast
  *   FRT_GOAL_AIM (root = the node, mid = tip = 0; axis: a non-zero local direction): O the origin of G[node], cur = norm(G[node]'s 3x3 * axis),
  *   want = norm(T - O); skipped when either length is not > 0. q = arc(cur, want), for w < 1 rig_slerp((0, 0, 0, 1), q, w); every node of
  *   subtree(node) takes G = mul(about(O, q), G). The pole words of an AIM record are 0.
+ *   FRT_GOAL_CHAIN ("Chain IK"; csrc/frt_ik.hpp: ik_chain_target, ik_chain_step): cyclic coordinate descent over the parent path c_0 = root, ...,
+ *   c_K = tip (tip a strict descendant of root; every node of the path is a joint of the chain; 2 <= K + 1 <= FRT_IK_CHAIN_MAX_NODES). `mid` is
+ *   the number of sweeps S, 1 <= S <= FRT_IK_CHAIN_MAX_SWEEPS; `axis` is unused and not kept; `reserved` is 0. P_j the origin of G[c_j], D_j the
+ *   identity, j = 0 .. K. Te = P_K + w (T - P_K), at w == 1 T itself, taken once. For s = 0 .. S - 1 and, within a sweep, k = K - 1 down to 0:
+ *   e = P_K - P_k, t = Te - P_k; if sqrt(dot(e, e)) > 0 and sqrt(dot(t, t)) > 0: R = about(P_k, arc(norm(e), norm(t))), P_j = R P_j for j > k,
+ *   D_j = mul(R, D_j) for j >= k; otherwise the step changes nothing. No convergence test, no early exit: the cost is S K steps. Every node n of
+ *   subtree(root) takes G = mul(D_j, G), c_j the deepest chain node whose subtree holds n, the tip's own subtree D_(K-1): the tip is an end
+ *   effector and does not turn itself. The pole words are ignored (but a record with a non-finite one is skipped, as above). Both caps are design
+ *   constants, not measurements: 32 nodes is what half a wave's lanes hold.
  *   FRT_IK_PLANE_EPS and FRT_IK_ARC_EPS are design constants of the contract, not measurements.
  * frt_rig_evaluate_layers_ik / frt_rig_evaluate_nodes_layers_ik are the specification, on the host: the layered calls with goals [ngoals] and their
  * targets [ngoals]; ngoals == 0 is the layered call bit for bit. FRT_ERR_INVALID_ARG, nothing written: what the layered call refuses; ngoals above
  * FRT_MAX_RIG_GOALS; a null array with ngoals > 0; an unknown kind; reserved != 0; a node out of range; a mid that is not a strict descendant of
  * root or a tip that is not one of mid; an AIM axis that is not finite or is zero, or AIM mid / tip != 0; a target word that is not finite, a
- * weight outside [0, 1] (0: the goal is skipped), a pole flag other than 0 or 1, a non-zero pole word on an AIM record.
+ * weight outside [0, 1] (0: the goal is skipped), a pole flag other than 0 or 1, a non-zero pole word on an AIM record; a CHAIN tip that is not
+ * a strict descendant of root, a path of more than FRT_IK_CHAIN_MAX_NODES nodes, sweeps (`mid`) outside 1 .. FRT_IK_CHAIN_MAX_SWEEPS.
  * Goals and targets are state of a binding of either kind, as masks are. frt_renderer_set_rig_goals uploads the definitions (staged, asynchronous,
  * on the main stream), replaces the previous set (ngoals == 0 clears it) and resets every target to weight 0, so new goals do nothing until
  * targets arrive. frt_renderer_set_rig_goal_targets is one asynchronous copy of ngoals records (ngoals: the binding's goal count) into the
@@ -836,10 +846,13 @@ int frt_renderer_animate_cast_layers(frt_renderer* r, uint32_t n, const frt_cast
  * _animate_instances_blend and the plain and blended casts ignore them. */
 #define FRT_MAX_RIG_GOALS 16u
 enum { FRT_GOAL_TWO_BONE = 0, FRT_GOAL_AIM = 1 };
+#define FRT_GOAL_CHAIN 2u
+#define FRT_IK_CHAIN_MAX_NODES 32u
+#define FRT_IK_CHAIN_MAX_SWEEPS 16u
 #define FRT_IK_PLANE_EPS 1e-12f
 #define FRT_IK_ARC_EPS 1e-6f
 #define FRT_GOAL_TARGETS_DEVICE 1u
-typedef struct frt_rig_goal { uint32_t kind, root, mid, tip; float axis[3]; uint32_t reserved; } frt_rig_goal;            /* 32 bytes; AIM: root = node, mid = tip = 0 */
+typedef struct frt_rig_goal { uint32_t kind, root, mid, tip; float axis[3]; uint32_t reserved; } frt_rig_goal;            /* 32 bytes; AIM: root = node, mid = tip = 0; CHAIN: mid = sweeps */
 typedef struct frt_rig_goal_target { float target[3], weight, pole[3], pole_flag; } frt_rig_goal_target;                  /* 32 bytes; pole_flag 0 or 1 */
 int frt_rig_evaluate_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals, const frt_rig_goal_target* targets, float* joint_mats_out, float* morph_weights_out);
 int frt_rig_evaluate_nodes_layers_ik(const frt_rig* rig, uint32_t n, const frt_clip_layer* layers, uint32_t nmasks, const float* masks, uint32_t ngoals, const frt_rig_goal* goals, const frt_rig_goal_target* targets, uint32_t nnodes, const uint32_t* nodes, const float* root16, const float* offsets16n, float* mats_out16n);

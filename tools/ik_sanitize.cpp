@@ -51,7 +51,7 @@ int main() {
     const float nan = std::nanf(""), inf = INFINITY;
     bool ok = refuse("more than FRT_MAX_RIG_GOALS", 17u, G.get(), T.get()) && refuse("a huge count", 0xFFFFFFFFu, G.get(), T.get()) && refuse("null goals", 3u, nullptr, T.get()) &&
               refuse("null targets", 3u, G.get(), nullptr) &&
-              with_goal("an unknown kind", 0, {2u, 0u, 2u, 4u, {0, 0, 0}, 0u}) && with_goal("reserved", 1, {FRT_GOAL_AIM, 4u, 0u, 0u, {0, 1, 0}, 1u}) &&
+              with_goal("an unknown kind", 0, {3u, 0u, 2u, 4u, {0, 0, 0}, 0u}) && with_goal("reserved", 1, {FRT_GOAL_AIM, 4u, 0u, 0u, {0, 1, 0}, 1u}) &&
               with_goal("a node out of range", 0, {FRT_GOAL_TWO_BONE, 0u, 2u, 5u, {0, 0, 0}, 0u}) && with_goal("mid is root", 0, {FRT_GOAL_TWO_BONE, 2u, 2u, 4u, {0, 0, 0}, 0u}) &&
               with_goal("mid above root", 0, {FRT_GOAL_TWO_BONE, 2u, 1u, 4u, {0, 0, 0}, 0u}) && with_goal("tip is mid", 2, {FRT_GOAL_TWO_BONE, 1u, 3u, 3u, {0, 0, 0}, 0u}) &&
               with_goal("tip above mid", 2, {FRT_GOAL_TWO_BONE, 1u, 3u, 2u, {0, 0, 0}, 0u}) && with_goal("a zero axis", 1, {FRT_GOAL_AIM, 4u, 0u, 0u, {0, 0, 0}, 0u}) &&
