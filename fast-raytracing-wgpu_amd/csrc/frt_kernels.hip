@@ -15,8 +15,9 @@ static constexpr int kBlock = 256;
 // LDS of a quad-walk workgroup is DYNAMIC, sized at launch from the scene's tree (frt_kernels.hpp: walk_lds_plan): `stack_rows` rows of kBlock words
 // — the tree's stack need; the builder accepts no tree that needs more than kStackDepth - 1 entries per lane (frt_bvh.cpp: build_quad_nodes folds only
 // within that budget; a plain binary subtree is at most kMaxBvhDepth = 30 deep) — then the workgroup's few shared words (ray-count partial sums, the
-// queue reservation scratch: 128 bytes) and behind them the copy of the tree's top (stage_top_nodes). The traced kernels' budget is 40 KiB (four
-// workgroups per CU, all their 128 VGPRs allow): the Cornell Box's 24 rows leave room for 127 of its 326 quad nodes.
+// queue reservation scratch: 128 bytes) and behind them the copy of the tree's top (stage_top_nodes). The traced kernels' budget is 32 KiB (four
+// workgroups per CU and 32 KiB left for one workgroup of a light kernel beside them: frt_kernels.hpp: traced_lds_budget): the Cornell Box's 24 rows
+// leave room for 63 of its 326 quad nodes (127 under the 40 KiB that FRT_LDS_BUDGET=40 selects).
 extern __shared__ __attribute__((aligned(128))) uint32_t s_walk[];
 struct WalkArgs { uint32_t stack_rows, top_nodes; };      // kernel argument: WalkLdsPlan without the byte count
 // Kernels that walk the 8-wide tree (WALK >= kWalkWide; frt_trace.hpp: trace8) need one stack word per level: kStack8 rows + one row for the shared
@@ -407,7 +408,7 @@ hipError_t launch_trace_pixels(int stage, const SceneView& sc, const FrameView& 
 #if FRT_EXPERIMENTS
     if (L.resident) return exp_launch_resident_pixels(stage, sc, fv, stream, L);
 #endif
-    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
+    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, L.lds_budget ? traced_lds_budget(L.wg_rows, L.lds_budget) : traced_lds_budget(L.wg_rows));
     const WalkArgs wa{plan.stack_rows, plan.top_nodes};
     auto go = [&](auto kernel, uint32_t lds) { hipLaunchKernelGGL(kernel, grid, dim3(kBlock), lds, stream, sc, fv, queue_of(L, 0), first_cut(L, fv), L.zero_counts, wa); };
 #if FRT_EXPERIMENTS
@@ -433,7 +434,7 @@ hipError_t launch_trace_continuations(int stage, const SceneView& sc, const Fram
 #if FRT_EXPERIMENTS
     { hipError_t e_; if (exp_launch_continuations(stage, sc, fv, stream, L, e_)) return e_; }      // wavefront / stream / refill / resident forms
 #endif
-    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, kLdsTracedBudget);
+    const WalkLdsPlan plan = walk_lds_plan(L.wg_rows, sc.num_nodes4, L.lds_budget ? traced_lds_budget(L.wg_rows, L.lds_budget) : traced_lds_budget(L.wg_rows));
     const WalkArgs wa{plan.stack_rows, plan.top_nodes};
     for (uint32_t k = 0; k < L.ncuts && L.cuts[k] < fv.max_depth; ++k) {
         const ContQueue qk = queue_of(L, k);      // (workgroups beyond their region's fill retire at once)

@@ -26,6 +26,7 @@ struct TraceLaunch {
     uint32_t walk;  // which tree the traced kernels walk: kWalkQuad (trace4; `vote` picks its loop), kWalkWide (trace8, nodes read from HBM), kWalkWideLds (trace8, the whole 8-wide tree copied into every workgroup's LDS: wide_lds_bytes of dynamic LDS)
     uint32_t wide_lds_bytes;
     uint32_t wg_rows;   // rows of a quad-walk workgroup's dynamic LDS: the quad tree's stack need + the shared row (walk_lds_plan below; kWalkQuadWg adds its exchange rows)
+    uint32_t lds_budget;   // bytes of LDS a traced workgroup may use (traced_lds_budget below); 0 = the default
 #if FRT_EXPERIMENTS
     // lib/libfrt_exp.so only (csrc/experiments/frt_experiment_kernels.hpp): the measured-and-not-kept kernel designs
     uint32_t* tile_state;   // the stage's sweep-direction state (TileOrder) or null = tile rows top to bottom
@@ -57,12 +58,20 @@ __device__ __forceinline__ const uint32_t* stage_top_nodes(const SceneView& sc, 
 struct WalkLdsPlan { uint32_t stack_rows, top_nodes, bytes; };
 static constexpr uint32_t kLdsGranule = 512u;                   // LDS is allocated in 128-dword granules (the kernel descriptor's granulated size field)
 static constexpr uint32_t kLdsPerCu = 160u * 1024u;
-static constexpr uint32_t kLdsTracedBudget = kLdsPerCu / 4u;    // four workgroups per CU: the traced kernels' 128 VGPRs allow no more
+static constexpr uint32_t kLdsTracedBudget = kLdsPerCu / 4u;    // four workgroups per CU and nothing beside them: the traced kernels' registers allow no more traced waves
+static constexpr uint32_t kLdsSharedBudget = kLdsPerCu / 5u;    // four traced workgroups leave 32 KiB of a CU for one workgroup of a light kernel (G-buffer, T-merge, post)
+// The bytes a traced workgroup may use: `want` (kLdsSharedBudget unless a renderer is told otherwise: FRT_LDS_BUDGET) where the tree's stack rows
+// and the shared words leave room in it for the kLdsTopNodes nodes every walk expects in LDS, kLdsTracedBudget otherwise.
+inline uint32_t traced_lds_budget(uint32_t wg_rows, uint32_t want = kLdsSharedBudget) {
+    const uint32_t least = (wg_rows < 2u ? 1u : wg_rows - 1u) * 1024u + kLdsSharedWords * 4u + (uint32_t)kLdsTopNodes * 128u;
+    return want >= least ? want : std::max(want, kLdsTracedBudget);
+}
 #ifndef FRT_LDS_TOP_MAX
 #define FRT_LDS_TOP_MAX 0xFFFFFFFFu      // (A/B builds only: a cap on the cached nodes)
 #endif
 // The G-buffer kernel's registers allow six and more waves per SIMD: its budget is the smallest share of a CU's LDS (a sixth, a fifth, a quarter,
-// in whole granules) that holds the stack rows and the shared row.
+// in whole granules) that holds the stack rows and the shared row. Every tree the builder accepts (31 stack rows at the most) gets a sixth or a
+// fifth: at most kLdsSharedBudget, what four traced workgroups under that budget leave free on a CU.
 inline uint32_t gbuffer_lds_budget(uint32_t wg_rows) {
     const uint32_t least = (wg_rows < 2u ? 2u : wg_rows) * 1024u;
     for (uint32_t wgs = 6u; wgs > 4u; --wgs) { const uint32_t b = kLdsPerCu / wgs / kLdsGranule * kLdsGranule; if (b >= least) return b; }

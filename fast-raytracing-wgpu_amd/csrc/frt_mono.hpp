@@ -19,6 +19,14 @@ FRT_HD bool trace_shadow_ray(Ctx& c, f3 origin, f3 dir, float dist) {
     return !c.any(origin, dir, t_min, t_max);
 }
 
+// The estimate's value is worked out BEFORE its shadow ray (round 14): it is a pure function of the hit and the light sample, so the operations and
+// their operands are the ones the reference has behind the visibility test, and an occluded lane still returns zero. What the any-hit walk — the
+// place where the traced kernels hold the most registers — then carries for the estimate is three words instead of eight (the light's emission,
+// the weight, the two cosines and the distance): 8 VGPRs fewer in every traced kernel (115 - 119 -> 107 - 111, profiles/r14_kernel_resources.txt).
+// The value is pinned, or the compiler sinks the arithmetic back behind the walk. A wave whose lanes are all occluded now computes a value nobody uses.
+#ifndef FRT_NEE_EARLY
+#define FRT_NEE_EARLY 1   // (A/B builds only: 0 = the value behind the shadow ray, as the reference writes it)
+#endif
 template <int VARIANT, class Ctx>
 FRT_HD f3 eval_direct_lighting(Ctx& c, const Surf& hit, f3 wo, const MatParams& m, f3 base_color, const LightSmp& ls, float weight) {   // :443-459
     f3 offset_pos = hit.pos + hit.ffnormal * 0.001f;
@@ -27,11 +35,21 @@ FRT_HD f3 eval_direct_lighting(Ctx& c, const Surf& hit, f3 wo, const MatParams& 
     float n_dot_l = fmaxn(dot(hit.ffnormal, L), 0.0f);
     float l_dot_n = fmaxn(dot(-L, ls.normal), 0.0f);
     if (n_dot_l > 0.0f && l_dot_n > 0.0f) {
+#if FRT_NEE_EARLY
+        f3 f = eval_bsdf(hit.ffnormal, L, wo, m, base_color);
+        float G = (n_dot_l * l_dot_n) / (dist * dist);
+        f3 lit = xyz(ls.emission) * ls.emission.w * f * G * weight;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(lit.x), "+v"(lit.y), "+v"(lit.z));
+#endif
+        if (trace_shadow_ray<VARIANT>(c, offset_pos, L, dist)) return lit;
+#else
         if (trace_shadow_ray<VARIANT>(c, offset_pos, L, dist)) {
             f3 f = eval_bsdf(hit.ffnormal, L, wo, m, base_color);
             float G = (n_dot_l * l_dot_n) / (dist * dist);
             return xyz(ls.emission) * ls.emission.w * f * G * weight;
         }
+#endif
     }
     return splat3(0.0f);
 }

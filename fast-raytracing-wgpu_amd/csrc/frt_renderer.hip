@@ -449,6 +449,9 @@ static int renderer_init(frt_renderer* r, const frt_scene* s, const frt_render_o
         if (v >= 1) { r->nsub = 1u; while (r->nsub * 2u <= (uint32_t)std::min<long>(v, (long)kMaxRegions)) r->nsub *= 2u; }
         if (end && *end == ',') env_slots = (uint32_t)std::max(0l, std::min(atol(end + 1), 0x7FFFFFFFl));
     }
+    // LDS of a traced workgroup (frt_kernels.hpp: traced_lds_budget). FRT_LDS_BUDGET=<KiB>, read once here, is for tests and A/B runs: 40 gives the
+    // traced kernels a whole quarter of a CU's LDS (the longest node copy, no room for a light kernel's workgroup beside four of theirs).
+    if (const char* e = getenv("FRT_LDS_BUDGET")) { const long v = atol(e); if (v >= 1 && v <= (long)(kLdsTracedBudget / 1024u)) r->lds_budget = (uint32_t)v * 1024u; }
     HIP_TRY(hipMalloc((void**)&r->d_counters, ray_counter_words(r) * sizeof(unsigned long long)));
     {   // the bounce depths at which paths are cut, and the continuation queues
         // Measured with the quad-tree kernels (tools/cut_sweep.sh, tools/strip_cuts.py): a 1080p frame 2.57 ms uncut, 2.08 cut at depth 3,
@@ -551,7 +554,7 @@ static void trace_launch_of(frt_renderer* r, int stage, bool with_tile_state, Tr
     memset(&L, 0, sizeof(L));
     L.nsub = r->nsub;
     L.vote = r->vote;
-    L.walk = r->walk; L.wide_lds_bytes = r->wide_lds_bytes; L.wg_rows = r->wg_rows;
+    L.walk = r->walk; L.wide_lds_bytes = r->wide_lds_bytes; L.wg_rows = r->wg_rows; L.lds_budget = r->lds_budget;
     const bool cut = stage_is_cut(r) && r->qcap > 0;
     L.ncuts = cut ? r->ncuts : 0u;
     for (int k = 0; k < kMaxCuts; ++k) L.cuts[k] = r->cuts[k];

@@ -310,6 +310,7 @@ struct frt_renderer {
     uint32_t ncuts = 2, cuts[kMaxCuts] = {3, 4, 0, 0};   // measured best on the Cornell Box
     bool vote = false;                     // traced kernels with the voting BVH walk (set from the size of the scene's quad tree, upload_scene)
     uint32_t walk = kWalkQuad, wide_lds_bytes = 0, wg_rows = 0;      // which tree the traced kernels walk and how (frt_kernels.hpp: kWalk*; upload_scene)
+    uint32_t lds_budget = 0;               // bytes of LDS a traced workgroup may use; 0 = the default (frt_kernels.hpp: traced_lds_budget; FRT_LDS_BUDGET)
 #if FRT_EXPERIMENTS
     ExpState x;                            // lib/libfrt_exp.so only: state and FRT_* knobs of the measured-and-not-kept kernel designs (csrc/experiments/)
 #endif
